@@ -2,7 +2,15 @@
 """bench.py — headline benchmark: Msamples/s of the path-tracing hot path on BASELINE config 2
 (Cornell box 800x800, 1024 spp, depth 50) in f64 (the reference's arithmetic type).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps of the headline workload and prints the line: `value`, `ms_per_step`, the
+`roofline` figures priced from that run's own kernel time, `loop`.  `--full` adds what needs runs of its own: the other BASELINE
+configs (`workloads`) and the CPU baseline (`cpu_baseline`); without it both are null / empty unless `--also` / `--cpu-spp` ask for
+them explicitly.  `--dump-outputs DIR` writes the last timed step's frame (what the timed path hands its caller: the (H, W, 3) f64
+per-pixel sums of every sample) as DIR/frame.npy after the timed region (a frame above 64 MB, C5's, as a seeded sample of its rows:
+DIR/frame_rows.npy + DIR/frame_row_index.npy); the inputs are fixed by the workload and the seed, so two builds can be compared
+output for output.
 
 A "step" is one whole frame: every GPU renders its interleaved tiles (one persistent HIP kernel launch per GPU), then ONE gather
 (RCCL over xGMI) moves them to the first GPU, which un-permutes them into the frame.  The frame is fixed as N grows (strong scaling).
@@ -33,10 +41,10 @@ tree; `--loop persistent|lockstep` sets the shape instead, which is what the pro
 are replayed only from a committed profile of this build AND this instantiation; `roofline.frac` is reference-equivalent throughput,
 `roofline.executed_valu_frac` what the SIMDs really issue.
 
-`workloads`: the other BASELINE configs (C1, C3, C4, C5) timed the same way, one reduced-spp warm-up frame + one full frame each
-(twenty for C1, whose frame is a few milliseconds), so that every config's Msamples/s and roofline fraction is on the driver's clock.
+`workloads` (`--full`): the other BASELINE configs (C1, C3, C4, C5) timed the same way, one reduced-spp warm-up frame + one full
+frame each (twenty for C1, whose frame is a few milliseconds), so that every config's Msamples/s and roofline fraction is on the driver's clock.
 
-`cpu_baseline` (N = 1 only): the CPU oracle — a restatement of the reference, not the Rust binary, which cannot be built here —
+`cpu_baseline` (`--full`, N = 1 only): the CPU oracle — a restatement of the reference, not the Rust binary, which cannot be built here —
 on a bounded sample of the same workload, in both threading shapes BASELINE.md names, counters compiled out.
 """
 import argparse
@@ -50,6 +58,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md
 N_SIMD = 1024               # 256 CUs x 4 SIMDs
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: at most 64 MB in all
 
 
 def usable_cores():
@@ -243,8 +252,14 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="C2")
-    ap.add_argument("--also", default="C1,C3,C4,C5",
-                    help="other BASELINE configs to time after the main one (one reduced-spp warm-up frame + one full frame each); 'none' to skip")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the other BASELINE configs and the CPU baseline (runs of their own; a plain run times only the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's frame (H x W x 3 per-pixel sums, float64) as DIR/frame.npy "
+                         "(above 64 MB: a seeded sample of its rows)")
+    ap.add_argument("--also", default=None,
+                    help="other BASELINE configs to time after the main one (one reduced-spp warm-up frame + one full frame each); "
+                         "'none' to skip.  Default: C1,C3,C4,C5 with --full, none without")
     ap.add_argument("--mode", default="auto", choices=("auto", "inproc", "procs"),
                     help="N > 1: `procs` = one process per GPU under torch.distributed.run (rt_render_device + one torch.distributed.gather); "
                          "`inproc` = this one process drives the N GPUs through rt_render_multi_device (ncclCommInitAll + one ncclGather); "
@@ -266,8 +281,15 @@ def main():
                          "(rt_scene_calibrate: four small launches outside every timed region; at N > 1 rank 0's result is handed to every rank); "
                          "the other two set it (rt_scene_set_loop_shape) and skip the measurement — what a profiled run uses so that no "
                          "calibration launch lands in its per-kernel averages.  No effect on the other scenes")
-    ap.add_argument("--cpu-spp", type=int, default=-1, help="spp of the bounded CPU-baseline sample (0 = skip, -1 = sized for ~8 s of wall time)")
+    ap.add_argument("--cpu-spp", type=int, default=None,
+                    help="spp of the bounded CPU-baseline sample (0 = skip, -1 = sized for ~8 s of wall time).  Default: -1 with --full, 0 without")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.also is None:
+        args.also = "C1,C3,C4,C5" if args.full else "none"
+    if args.cpu_spp is None:
+        args.cpu_spp = -1 if args.full else 0
 
     import torch
     import torch.distributed as dist
@@ -379,9 +401,10 @@ def main():
         return {"rows": [r0, r0 + 1], "max_abs_diff": float(diff.max()), "tolerance": "1e-12 * (spp + |x|) per channel sum",
                 "reference": "the same rows rendered by one launch each on rank 0's device alone (tile = row, no gather, no un-permute)", "ok": ok}
 
-    def run_procs(w, steps, warmup, warm_spp=None, pipeline=1):
+    def run_procs(w, steps, warmup, warm_spp=None, pipeline=1, keep_frame=False):
         """One process per GPU (or the one GPU): time `steps` frames of workload `w` (after `warmup` untimed ones; `warm_spp` renders the
-        warm-up frames at a reduced sample count through the same kernel and scene).  Returns what rank 0 needs for its line."""
+        warm-up frames at a reduced sample count through the same kernel and scene).  Returns what rank 0 needs for its line
+        (`keep_frame`: and a host copy of the last timed frame, for --dump-outputs)."""
         b, cam, bg = build_scene(w)
         # one-time initialisation (scene flatten + upload, code-object load, event creation) is not part of a step
         R.prepare(b, flags)
@@ -423,11 +446,13 @@ def main():
             assert frame is not None and tuple(frame.shape) == (w.H, w.W, 3)
             res["mean_radiance"] = float(torch.nan_to_num(frame).mean().item()) / w.spp
             res["multi_check"] = check_rows(b, cam, bg, w, frame[w.H // 2: w.H // 2 + 2].cpu().numpy())
+            if keep_frame:
+                res["frame"] = frame.cpu().numpy()
         del tr, frame, b
         torch.cuda.empty_cache()
         return res
 
-    def run_inproc(w, steps, warmup, warm_spp=None, pipeline=1):
+    def run_inproc(w, steps, warmup, warm_spp=None, pipeline=1, keep_frame=False):
         """This one process, N GPUs: every step is one rt_render_multi_device call — N persistent launches on N streams, one ncclGather,
         the un-permute on the first device — with the frame left in that device's memory (as the N = 1 bench leaves it); the calls do
         not wait for each other's frames beyond what the library's one-frame-in-flight rule asks for."""
@@ -464,6 +489,8 @@ def main():
                          "devices": rk["devices"], "kernel_ms": rk["kernel_ms"], "local_samples": per_rank}}
         torch.cuda.set_device(rk["devices"][0] if rk["devices"] else 0)
         res["multi_check"] = check_rows(b, cam, bg, w, frame[w.H // 2: w.H // 2 + 2])
+        if keep_frame:
+            res["frame"] = frame
         del b
         torch.cuda.empty_cache()
         return res
@@ -472,9 +499,23 @@ def main():
     run = run_inproc if inproc else run_procs
     w = workloads.WORKLOADS[args.workload]
     pipelines = [1] if (inproc or n_gpus == 1 and args.pipeline == "auto") else ([1, 2] if args.pipeline == "auto" else [int(args.pipeline)])
-    tried = {pl: run(w, args.steps, args.warmup, pipeline=pl) for pl in pipelines}
+    tried = {pl: run(w, args.steps, args.warmup, pipeline=pl, keep_frame=args.dump_outputs is not None) for pl in pipelines}
     best = min(tried, key=lambda pl: tried[pl]["elapsed"])         # (max-over-ranks times: the same choice on every rank)
     main_res = tried[best]
+    if args.dump_outputs is not None and rank == 0:
+        # what the timed path handed its caller in its last step: the frame's per-pixel sums, (H, W, 3) float64 (15 MB for C2).
+        # A frame above DUMP_MAX_BYTES (C5: 199 MB) is written as a fixed, seeded sample of whole rows and their row numbers.
+        frame = np.ascontiguousarray(main_res["frame"], dtype=np.float64)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        if frame.nbytes <= DUMP_MAX_BYTES:
+            np.save(os.path.join(args.dump_outputs, "frame.npy"), frame)
+        else:
+            n_rows = DUMP_MAX_BYTES // (frame.nbytes // frame.shape[0]) - 1
+            rows = np.sort(np.random.default_rng(0x5EED).choice(frame.shape[0], size=n_rows, replace=False))
+            np.save(os.path.join(args.dump_outputs, "frame_rows.npy"), frame[rows])
+            np.save(os.path.join(args.dump_outputs, "frame_row_index.npy"), rows.astype(np.float64))
+    for r in tried.values():
+        r.pop("frame", None)
     extra = []
     if args.also.lower() != "none":
         for key in args.also.split(","):

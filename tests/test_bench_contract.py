@@ -8,7 +8,7 @@ from conftest import ROOT
 
 
 def _latest():
-    """The newest committed DEFAULT line (`python bench.py`: C2 headline + CPU baseline + the other configs); round 1 committed
+    """The newest committed DEFAULT line (`python bench.py --full`: C2 headline + CPU baseline + the other configs); round 1 committed
     only per-workload lines."""
     files = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_bench_default.json"))) or sorted(glob.glob(os.path.join(ROOT, "profiles", "*_bench_C2.json")))
     assert files, "no committed bench line"
@@ -59,7 +59,7 @@ def test_bench_line_is_self_consistent():
 
 
 def test_bench_line_times_the_other_configs():
-    """Round 2 on: the default line carries C1, C3, C4 and C5 on the driver's clock, each with the committed bytes/sample."""
+    """Round 2 on: the default (`--full`) line carries C1, C3, C4 and C5 on the driver's clock, each with the committed bytes/sample."""
     from raytracinginrust_amd import workloads
     d = _latest()
     if "workloads" not in d:

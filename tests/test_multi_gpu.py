@@ -186,8 +186,8 @@ def test_bench_runs_in_process_without_a_launcher(gpus):
     from conftest import ROOT
     env = dict(os.environ, RT_MULTI_VIRTUAL_RANKS=str(gpus))
     env.pop("WORLD_SIZE", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--also", "C1",
-                        "--cpu-spp", "0"], env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--full", "--also",
+                        "C1", "--cpu-spp", "0"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads(p.stdout.strip().splitlines()[-1])
     assert d["n_gpus"] == gpus and d["steps"] == 2 and d["scaling"] == "strong" and d["config"]["mode"] == "inproc"
@@ -218,7 +218,7 @@ def test_bench_runs_one_process_per_gpu_under_the_launcher():
     env = dict(os.environ, RT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     env.pop("RT_MULTI_VIRTUAL_RANKS", None)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29631",
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--also", "C1,C4"],
+                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--also", "C1,C4"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.strip().splitlines() if l.startswith("{")]
