@@ -117,17 +117,26 @@ int rt_parse_obj(const char* data, size_t size, const double offset[3], double s
 int rt_flip_normal(rt_scene*, int hittable);                                                           /* FlipNormal::new, src/hit.rs:105      */
 int rt_translate(rt_scene*, int hittable, const double offset[3]);                                     /* Translate::new, src/translate.rs:13  */
 int rt_rotate(rt_scene*, int axis, int hittable, double angle_deg);                                    /* Rotate::new, src/rotate.rs:32        */
-int rt_constant_medium(rt_scene*, int boundary, double density, int texture);                          /* ConstantMedium::new, src/medium.rs:17 */
+/* ConstantMedium::new, src/medium.rs:17.  The boundary may be any Hittable but one that holds a ConstantMedium ("nested ConstantMedium is
+ * not supported", at flatten time): a list of several objects — primitives, wrapped objects, BVHs, meshes — is searched as
+ * HittableList::hit for each of the two boundary queries (medium.rs:29-30).  The medium may stand at the top level, under wrappers, in
+ * BVH leaves. */
+int rt_constant_medium(rt_scene*, int boundary, double density, int texture);
 /* BVH::new, src/bvh.rs:18-73: `hittables` may be handles of ANY kind, as the reference's Vec<Box<dyn Hittable>> — bare primitives, lists,
  * FlipNormal / Translate / Rotate of anything (a Rotate child has the whole-space box of src/rotate.rs:40-57: such a tree is walked with
  * the exact box test everywhere), ConstantMedium, another BVH (one level of BVHs inside BVH leaves; deeper is an error at flatten time).
  * Errors where the reference panics: n = 0 ("no object in the scene", src/bvh.rs:55); a child without a bounding box — an empty list or a
- * wrapper of one ("no bounding box in bvh node", src/bvh.rs:28,61) — at flatten time. */
+ * wrapper of one ("no bounding box in bvh node", src/bvh.rs:28,61) — at flatten time.  BVHs nested more than RT_MAX_NEST deep inside
+ * BVH leaves (a ConstantMedium's boundary counts as the level it stands at) are refused at flatten time. */
 int rt_bvh(rt_scene*, const int* hittables, uint32_t n, double time0, double time1);
 int rt_bvh_of_list(rt_scene*, int list, double time0, double time1);                                   /* BVH::new(list.list, ..), src/main.rs:442 */
 
 /* the (world, lights) pair every scene fn returns, src/main.rs:153,278,348,453 */
 int rt_scene_set_world(rt_scene*, int hittable);
+/* lights.push (the reference's `lights` HittableList): AARect and Sphere (under any FlipNormals) are sampled; HittableLists nest (hit.rs:90-96:
+ * pdf_value the mean over the items, random one item drawn uniformly), up to RT_MAX_LIGHT_NEST levels; anything else — Translate, Rotate,
+ * Cube, BVH, MovingSphere, Triangle — has the trait defaults (pdf 0, direction (1,0,0)).  An empty nested list is an error at flatten time
+ * (the reference panics, src/hit.rs:95; an empty top level is deviation D2). */
 int rt_lights_push(rt_scene*, int hittable);
 
 /* ---- host-side pieces of the boundary ------------------------------------------------------ */
@@ -321,6 +330,10 @@ int rt_debug_room_hit(uint32_t n, double rect_m, const double* boxes, const doub
  * material.  Host pointers.  What the room form's order argument rests on is tested through this: rays that start ON planes, with zero
  * direction components (0 / 0 plane distances), non-finite rays. */
 int rt_debug_list_hit(rt_scene*, uint32_t n, const double* rays, const double* t_min, double* out);
+/* Known-answer access to the scene's `lights` pdf_value (HittableList::pdf_value, hit.rs:90-92, nested lists included) on the device, through
+ * the function the all-features kernel with object leaves runs (the instantiation every scene with a list inside `lights` gets).  origins,
+ * dirs: n x 3; out: n.  Host pointers. */
+int rt_debug_light_pdf(rt_scene*, uint32_t n, const double* origins, const double* dirs, double* out);
 /* Debugging aid for parity work: the hits of ONE camera path, level by level.  rt_debug_trace_path chooses the path (local pixel index =
  * output-order pixel for an unsharded render, sample index; -1 switches it off); the following renders record, per level of ray_color
  * that found a hit, 16 doubles at out[16 * level]: t, position[3], normal[3], front_face, object, primitive kind, primitive index,

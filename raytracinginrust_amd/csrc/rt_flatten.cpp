@@ -25,10 +25,15 @@ struct Flattener {
     std::map<int, uint32_t> prim_of_node;   // node id -> first primitive index in its pool (emitted once, shared)
     std::string err;
     // the wrappers an object stands in, outermost first; n_outer of them lie outside the BVH whose leaf the object is (0 at the top
-    // level), med_at of them outside its ConstantMedium (-1: no medium met yet)
-    struct Chain { DOp<double> ops[RT_MAX_OPS]; int n = 0; int n_outer = 0; int med_at = -1; };
+    // level), med_at of them outside its ConstantMedium (-1: no medium met yet).  Any length up to RT_MAX_OPS (the reference has no limit:
+    // translate.rs:13, rotate.rs:32, hit.rs:105), so the ops are a growable vector; each recursion level copies the chain once.
+    struct Chain {
+        std::vector<DOp<double>> ops; int n_outer = 0; int med_at = -1;
+        int n() const { return (int)ops.size(); }
+    };
     std::vector<DObject> subs;              // sub-objects of G_OBJ leaves, appended to f.objects behind the world's own once the world is done
     std::vector<DObject>* target = nullptr; // where emit_object puts an object: f.objects (the world list) or subs
+    int in_boundary = 0;                    // > 0 while a multi-object ConstantMedium boundary is emitted (a medium inside it stays refused)
     explicit Flattener(Scene& sc) : s(sc), f(sc.flat) {}
 
     bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
@@ -262,7 +267,7 @@ struct Flattener {
                 std::vector<DObject>* const saved = target;
                 std::vector<DObject> mine;
                 target = &mine;
-                Chain c2 = chain; c2.n_outer = chain.n; c2.med_at = -1;
+                Chain c2 = chain; c2.n_outer = chain.n(); c2.med_at = -1;
                 const bool ok = emit(items[0], c2, -1, nest + 1);
                 target = saved;
                 if (!ok) return false;
@@ -299,14 +304,16 @@ struct Flattener {
     bool emit_object(uint32_t kind, uint32_t first, uint32_t count, const Chain& chain, int medium, bool is_cube = false) {
         DObject o{};
         o.geom_kind = kind; o.geom_first = first; o.geom_count = count; o.is_cube = is_cube ? 1u : 0u;
-        o.first_op = (uint32_t)f.ops.size(); o.n_ops = (uint32_t)chain.n; o.medium = medium;
+        o.first_op = (uint32_t)f.ops.size(); o.n_ops = (uint32_t)chain.n(); o.medium = medium;
         const int med_at = medium >= 0 ? chain.med_at : 0;
+        static_assert(RT_MAX_OPS < 256, "DObject::nest packs n_outer and med_at into 8 bits each");
         o.nest = (uint32_t)chain.n_outer | ((uint32_t)med_at << 8);
-        bool flips_only = chain.n > 0 && medium < 0;
-        for (int i = 0; i < chain.n; i++) flips_only = flips_only && chain.ops[i].kind == OP_FLIP;
+        bool flips_only = chain.n() > 0 && medium < 0;
+        for (const DOp<double>& op : chain.ops) flips_only = flips_only && op.kind == OP_FLIP;
         if (flips_only) o.nest |= 0x10000u;            // every wrapper is a FlipNormal: the hit test may use the incoming ray as it is
         if (med_at != 0) f.feats |= F_NESTED;          // a ConstantMedium under a wrapper: the all-features kernel's object_hit serves it
-        for (int i = 0; i < chain.n; i++) f.ops.push_back(chain.ops[i]);
+        if (chain.n() > RT_SHORT_CHAIN) f.feats |= F_NESTED;
+        f.ops.insert(f.ops.end(), chain.ops.begin(), chain.ops.end());
         target->push_back(o);
         return true;
     }
@@ -322,9 +329,10 @@ struct Flattener {
         case HNode::LIST: {
             // HittableList::hit (hit.rs:59-71) keeps the closest hit, later items winning ties, and wrappers
             // act per hit, so Wrapper(List[a,b]) == List[Wrapper(a), Wrapper(b)].  A ConstantMedium boundary
-            // is different (two boundary queries, medium.rs:29-30) and must stay one object.
-            // (As a medium boundary a list must flatten to exactly one object: one wrapped item, or a homogeneous run of
-            // bare primitives such as a Mesh's triangles, which becomes one typed range.)
+            // is different (two boundary queries, medium.rs:29-30): it stays ONE object.  A list that is one object anyway (one item,
+            // or a homogeneous run of bare primitives such as a Mesh's triangles: one typed range) is that object; any other list
+            // becomes a run of sub-objects behind the medium (emit_boundary).
+            if (medium >= 0 && !one_object(h)) return emit_boundary(n, chain, medium, nest);
             size_t i = 0;
             bool emitted_any = false;
             while (i < h.items.size()) {
@@ -358,10 +366,10 @@ struct Flattener {
             return true;
         }
         case HNode::FLIP: case HNode::TRANSLATE: case HNode::ROTATE: {
-            if (chain.n >= RT_MAX_OPS) return fail("wrapper chain longer than RT_MAX_OPS");
+            if (chain.n() >= RT_MAX_OPS) return fail("wrapper chain longer than RT_MAX_OPS");
             Chain c2 = chain;
-            DOp<double>& op = c2.ops[c2.n++];
-            op = DOp<double>{};
+            c2.ops.push_back(DOp<double>{});
+            DOp<double>& op = c2.ops.back();
             if (h.kind == HNode::FLIP) op.kind = OP_FLIP;
             else if (h.kind == HNode::TRANSLATE) { op.kind = OP_TRANSLATE; op.x = h.v[0]; op.y = h.v[1]; op.z = h.v[2]; }
             else {
@@ -377,14 +385,14 @@ struct Flattener {
             return emit(h.child, c2, medium, nest);
         }
         case HNode::MEDIUM: {
-            if (medium >= 0) return fail("nested ConstantMedium is not supported");
+            if (medium >= 0 || in_boundary > 0) return fail("nested ConstantMedium is not supported");
             // Isotropic::new(texture), medium.rs:21
             DMaterial<double> iso{}; iso.kind = M_ISOTROPIC; iso.tex = (uint32_t)h.mat;
             f.materials.push_back(iso);
             DMedium<double> m{}; m.neg_inv_density = -(1.0 / h.v[0]); m.mat = (uint32_t)f.materials.size() - 1;
             f.media.push_back(m);
             f.feats |= F_MEDIUM;
-            Chain c2 = chain; c2.med_at = chain.n;      // the wrappers met so far lie outside the medium
+            Chain c2 = chain; c2.med_at = chain.n();    // the wrappers met so far lie outside the medium
             return emit(h.child, c2, (int)f.media.size() - 1, nest);
         }
         case HNode::BVH: {
@@ -396,6 +404,40 @@ struct Flattener {
         }
         }
         return fail("unknown node kind");
+    }
+
+    // A ConstantMedium boundary list that flattens to ONE object (the list loop of emit): no item or one item (which decides for itself),
+    // or two or more distinct bare primitives of one kind that have no record yet (one typed range)
+    bool one_object(const HNode& h) const {
+        if (h.items.size() <= 1) return true;
+        const HNode::Kind k = s.nodes[h.items[0]].kind;
+        if (!is_bare_prim(k)) return false;
+        std::vector<int> seen(h.items);
+        std::sort(seen.begin(), seen.end());
+        if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return false;     // `[a, a]`: the run ends at the second `a`
+        for (int it : h.items) if (s.nodes[it].kind != k || prim_of_node.count(it)) return false;
+        return true;
+    }
+    // A ConstantMedium whose boundary is a list of several objects (ConstantMedium<H: Hittable> takes any boundary, medium.rs:10-24):
+    // the medium is one object of kind G_OBJ whose geometry is a run of sub-objects, as a BVH leaf's is; each of its two boundary
+    // queries (medium.rs:29-30) is HittableList::hit over the run (rt_kernel.hip: boundary_hit).  The sub-objects carry the whole chain
+    // from the world down; the first n_outer of its ops — all the medium object's own, those outside the medium and those between it
+    // and the list — are applied to the ray the boundary receives.  Their records are never built (a medium's hit is the medium's).
+    bool emit_boundary(int n, const Chain& chain, int medium, int nest) {
+        std::vector<DObject>* const saved = target;
+        std::vector<DObject> mine;
+        target = &mine;
+        Chain c2 = chain; c2.n_outer = chain.n(); c2.med_at = -1;
+        in_boundary++;
+        const bool ok = emit(n, c2, -1, nest);
+        in_boundary--;
+        target = saved;
+        if (!ok) return false;
+        if (mine.empty()) return true;          // lists of empty lists: never hit (hit.rs:59-71), as an empty boundary (below)
+        const size_t s0 = subs.size();
+        subs.insert(subs.end(), mine.begin(), mine.end());
+        f.feats |= F_NESTED;
+        return emit_object(G_OBJ, (uint32_t)s0, (uint32_t)mine.size(), chain, medium);
     }
 
     // ---- a ROOM: bare AARects of the world list that are exact faces of ONE axis-aligned box become one object (list scenes only)
@@ -533,6 +575,11 @@ struct Flattener {
         Chain c;
         target = &f.objects;
         if (!emit(s.world, c, -1)) return false;
+        for (int l : s.lights) {            // a list inside `lights` is served by the all-features kernel (below), which has no room form
+            int n = l;
+            while (s.nodes[n].kind == HNode::FLIP) n = s.nodes[n].child;
+            if (s.nodes[n].kind == HNode::LIST) f.feats |= F_NESTED;
+        }
         form_room();
         // the sub-objects follow the world's own objects in the one table: G_OBJ leaves learn their final indices
         f.n_top = room_n_top ? room_n_top : (uint32_t)f.objects.size();
@@ -544,6 +591,7 @@ struct Flattener {
                     nd.a = BVH_LEAF | (G_OBJ << 28) | first;
                 }
             f.objects.insert(f.objects.end(), subs.begin(), subs.end());
+            for (DObject& o : f.objects) if (o.geom_kind == G_OBJ) o.geom_first += f.n_top;     // media with a boundary run (emit_boundary)
         }
         // which materials' textures read (u, v): ImageTexture, possibly under CheckTextures (texture.rs:45-54)
         {
@@ -559,16 +607,35 @@ struct Flattener {
             for (auto& m : f.materials)
                 if ((m.kind == M_LAMBERTIAN || m.kind == M_DIFFUSE_LIGHT || m.kind == M_ISOTROPIC || m.kind == M_PBR) && reads_uv(m.tex, 0)) m.kind |= MAT_NEEDS_UV;
         }
-        // lights: HittableList of FlipNormal(AARect) / AARect / Sphere (hit.rs:90-96, 125-132; rect.rs:91-111; sphere.rs:104-119);
-        // anything else has the trait defaults pdf_value = 0, random = (1,0,0) (hit.rs:29-30)
-        for (int l : s.lights) {
-            int n = l;
+        // lights: a HittableList of FlipNormal(..) / AARect / Sphere / HittableList (hit.rs:90-96, 125-132; rect.rs:91-111;
+        // sphere.rs:104-119); anything else has the trait defaults pdf_value = 0, random = (1,0,0) (hit.rs:29-30) — Translate, Rotate,
+        // Cube, BVH, MovingSphere, Triangle override neither.  A nested list is a tree node: its children are one contiguous run of
+        // records in push order, lights[index .. index + count) (rt_ir.h L_LIST), emitted breadth first behind the top level, which
+        // keeps lights[0, n) — a flat list's table is what it always was.
+        struct Pending { size_t slot; int node; uint32_t depth; };
+        std::vector<Pending> todo;
+        f.lights.resize(s.lights.size());
+        f.n_lights = (uint32_t)s.lights.size();
+        for (size_t i = 0; i < s.lights.size(); i++) todo.push_back({i, s.lights[i], 0u});
+        for (size_t q = 0; q < todo.size(); q++) {
+            const Pending p = todo[q];
+            int n = p.node;
             while (s.nodes[n].kind == HNode::FLIP) n = s.nodes[n].child;
             const HNode& h = s.nodes[n];
-            if (h.kind == HNode::RECT) f.lights.push_back({L_RECT, rect_of(n)});
-            else if (h.kind == HNode::SPHERE) f.lights.push_back({L_SPHERE, sphere_of(n)});
-            else if (h.kind == HNode::LIST) return fail("a HittableList nested inside `lights` is not supported");
-            else f.lights.push_back({L_OTHER, 0});
+            if (h.kind == HNode::RECT) f.lights[p.slot] = {L_RECT, rect_of(n)};
+            else if (h.kind == HNode::SPHERE) f.lights[p.slot] = {L_SPHERE, sphere_of(n)};
+            else if (h.kind == HNode::LIST) {
+                // deviation D16: the reference panics on an empty nested list (`choose(..).unwrap()`, hit.rs:95) and its
+                // pdf_value is 0 / 0
+                if (h.items.empty()) return fail("an empty HittableList inside `lights` (the reference panics: hit.rs:95)");
+                if (p.depth >= (uint32_t)RT_MAX_LIGHT_NEST) return fail("HittableLists nested more than RT_MAX_LIGHT_NEST deep inside `lights`");
+                if (h.items.size() >= (1u << 24)) return fail("too many lights in one HittableList");
+                const size_t first = f.lights.size();
+                f.lights.resize(first + h.items.size());
+                for (size_t j = 0; j < h.items.size(); j++) todo.push_back({first + j, h.items[j], p.depth + 1u});
+                f.lights[p.slot] = {L_LIST | ((uint32_t)h.items.size() << 8), (uint32_t)first};
+                f.feats |= F_NESTED;
+            } else f.lights[p.slot] = {L_OTHER, 0};
         }
         return true;
     }

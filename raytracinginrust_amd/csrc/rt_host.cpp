@@ -633,7 +633,7 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     P.n_bvh = (uint32_t)f.bvh.size();
     P.bvh_f = (const DFNode*)d.bvh_f; P.filter_m = f.filter_m; P.rect_m = f.rect_m;
     P.materials = (const DMaterial<T>*)d.materials; P.textures = (const DTexture<T>*)d.textures; P.media = (const DMedium<T>*)d.media;
-    P.lights = (const DLight*)d.lights; P.n_lights = (uint32_t)f.lights.size();
+    P.lights = (const DLight*)d.lights; P.n_lights = f.n_lights;
     P.perlins = (const DPerlin<T>*)d.perlins; P.pbr = (const DPbr<T>*)d.pbr; P.image_bytes = (const uint8_t*)d.image;
     {   // the f32 tables are rounded copies: the tame bound is checked at the precision that is uploaded
         const double big = sizeof(T) == 8 ? 1e300 : 1e30;
@@ -1044,6 +1044,30 @@ int rt_debug_list_hit(rt_scene* sc, uint32_t n, const double* rays, const double
         launch_list_hit_kat(P, n, dr, dt, dout, nullptr) == hipSuccess && hipMemcpy(out, dout, n * 96ull, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
     (void)hipFree(dr); (void)hipFree(dt); (void)hipFree(dout);
     return rc == 0 ? 0 : set_err("rt_debug_list_hit: a HIP call failed");
+}
+// Known-answer access to HittableList::pdf_value of the scene's `lights` (hit.rs:90-92, nested lists included) on the device, through the
+// function the F_ALL | F_NESTED kernels run (rt_kernel.hip lights_pdf_tree).  origins, dirs: n x 3; out: n.  Host pointers.
+int rt_debug_light_pdf(rt_scene* sc, uint32_t n, const double* origins, const double* dirs, double* out) {
+    if (!sc || !origins || !dirs || !out) return set_err("null argument");
+    if (n == 0) return 0;
+    Scene& s = sc->s;
+    if (!flatten_scene(s)) { g_err = s.error; return -1; }
+    Scene::DeviceCtx* cp = nullptr;
+    if (current_ctx(s, &cp)) return -1;
+    DeviceScene<double>& d = dev_of<double>(*cp);
+    if (ensure_uploaded<double>(s, d)) return -1;
+    const HostFlat& f = s.flat;
+    KParams<double> P;
+    std::memset((void*)&P, 0, sizeof(P));
+    P.lights = (const DLight*)d.lights; P.n_lights = f.n_lights;
+    P.rects = (const DRect<double>*)d.rects; P.spheres = (const DSphere<double>*)d.spheres;
+    double *dor = nullptr, *ddi = nullptr, *dout = nullptr;
+    int rc = -1;
+    if (hipMalloc(&dor, n * 24ull) == hipSuccess && hipMalloc(&ddi, n * 24ull) == hipSuccess && hipMalloc(&dout, n * 8ull) == hipSuccess &&
+        hipMemcpy(dor, origins, n * 24ull, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(ddi, dirs, n * 24ull, hipMemcpyHostToDevice) == hipSuccess &&
+        launch_light_pdf_kat(P, n, dor, ddi, dout, nullptr) == hipSuccess && hipMemcpy(out, dout, n * 8ull, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    (void)hipFree(dor); (void)hipFree(ddi); (void)hipFree(dout);
+    return rc == 0 ? 0 : set_err("rt_debug_light_pdf: a HIP call failed");
 }
 int rt_debug_trace_path(rt_scene* sc, long long local_pixel, long long sample) {
     if (!sc) return set_err("null argument");

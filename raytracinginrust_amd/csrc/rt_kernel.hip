@@ -820,6 +820,23 @@ DEV bool geom_hit(const KParams<T>& P, const DObject& ob, const RayT<T>& r, T t_
     // (a room — is_cube & 2 — exists in list scenes only and has no wrappers: one call site knows about it, the others' code is unchanged)
     return range_hit<T, FEATS>(P, ob.geom_kind, ob.geom_first, ob.geom_count, r, t_min, t_max, t, prim, ob.is_cube != 0u, rooms && (ob.is_cube & 2u) ? ob.is_cube : 0u);
 }
+// A ConstantMedium boundary that is a list of several objects (rt_flatten.cpp emit_boundary): HittableList::hit over its run of sub-objects
+// (hit.rs:59-71), the closest hit so far the next item's t_max — Cube and BVH box tests depend on it, so this is not the minimum of
+// independent queries.  `ray` is the ray the boundary receives (the medium object's ops applied: each sub-object's first n_outer).  Only t
+// is wanted; no medium stands in the run (the flattener refuses one), so nothing draws from `rng`.
+template <typename T, uint32_t FEATS, int NEST>
+DEV bool boundary_hit(const KParams<T>& P, uint32_t first, uint32_t count, const RayT<T>& ray, T t_min, T t_max, Rng& rng, T& t_out) {
+    T closest = t_max; bool any = false;
+    for (uint32_t i = first; i < first + count; i++) {
+        const DObject sb = ld_obj(P.objects + i);
+        RayT<T> r = ray;
+        for (uint32_t k = sb.nest & 0xFFu; k < sb.n_ops; k++) op_fwd(ld_op(P.ops + sb.first_op + k), r);
+        T t; uint32_t prim, sub = NO_SUB;
+        if (geom_hit<T, FEATS, NEST>(P, sb, r, t_min, closest, t, prim, nullptr, rng, sub)) { closest = t; any = true; }
+    }
+    t_out = closest;
+    return any;
+}
 // One object under HittableList::hit in an F_NESTED kernel — a top-level object (NEST 0) or a sub-object of a BVH leaf (NEST >= 1; `ray` is
 // then the ray as the enclosing BVH received it: the first n_outer ops of the object's chain are already in it).  Same arithmetic as
 // object_hit's general form; additionally a ConstantMedium may stand anywhere in the chain (medium.rs:27-61 measures the free flight with
@@ -838,18 +855,28 @@ DEV void object_hit_nested(const KParams<T>& P, uint32_t oi, const DObject& ob, 
     for (uint32_t k = n_outer; k < med_at; k++) op_fwd(ld_op(P.ops + ob.first_op + k), r);        // the ray ConstantMedium::hit receives
     const T len = length(r.d);                                                                     // medium.rs:40
     for (uint32_t k = med_at; k < ob.n_ops; k++) op_fwd(ld_op(P.ops + ob.first_op + k), r);        // ... and its boundary
-    T t1, t2; uint32_t p1, p2;
-    if (geom_hit<T, FEATS, NEST>(P, ob, r, -Lim<T>::max(), Lim<T>::max(), t1, p1, nullptr, rng, sub)) {          // medium.rs:29
-        if (geom_hit<T, FEATS, NEST>(P, ob, r, t1 + T(0.0001), Lim<T>::max(), t2, p2, nullptr, rng, sub)) {      // medium.rs:30
-            if (t1 < t_min) t1 = t_min;
-            if (t2 > closest) t2 = closest;
-            if (t1 < t2) {
-                T distance_inside_boundary = (t2 - t1) * len;
-                T hit_distance = cl(&P.media[ob.medium].neg_inv_density) * m_log(rng_u01(rng, T(0)));
-                if (hit_distance < distance_inside_boundary) {
-                    closest = t1 + hit_distance / len;
-                    id.obj = oi; id.prim = PRIM_MEDIUM; any = true;
-                }
+    // the two boundary queries, boundary.hit(r, -MAX, MAX) and boundary.hit(r, t1 + 0.0001, MAX) (medium.rs:29-30): of one object's
+    // geometry, or of a run of sub-objects (a boundary list of several objects).  One copy of each search in the code, the loop not unrolled.
+    const bool run = ob.geom_kind == G_OBJ;
+    T t1 = T(0), t2 = T(0), lo = -Lim<T>::max();
+    bool both = true;
+#pragma nounroll
+    for (int q = 0; q < 2 && both; q++) {
+        T t; uint32_t p;
+        both = run ? boundary_hit<T, FEATS, NEST>(P, ob.geom_first, ob.geom_count, r, lo, Lim<T>::max(), rng, t)
+                   : geom_hit<T, FEATS, NEST>(P, ob, r, lo, Lim<T>::max(), t, p, nullptr, rng, sub);
+        if (q == 0) t1 = t; else t2 = t;
+        lo = t + T(0.0001);
+    }
+    if (both) {
+        if (t1 < t_min) t1 = t_min;
+        if (t2 > closest) t2 = closest;
+        if (t1 < t2) {
+            T distance_inside_boundary = (t2 - t1) * len;
+            T hit_distance = cl(&P.media[ob.medium].neg_inv_density) * m_log(rng_u01(rng, T(0)));
+            if (hit_distance < distance_inside_boundary) {
+                closest = t1 + hit_distance / len;
+                id.obj = oi; id.prim = PRIM_MEDIUM; any = true;
             }
         }
     }
@@ -1252,6 +1279,40 @@ template <typename T, uint32_t FEATS> DEV T light_pdf_value(const KParams<T>& P,
     }
     return T(0);                                                                      // Hittable::pdf_value default, hit.rs:29
 }
+// `lights` with HittableLists inside (F_NESTED kernels; rt_ir.h L_LIST).  HittableList::random (hit.rs:94-96): one index per list level,
+// top down — one draw even for a list of one —, then the leaf's own draws (light_random).
+template <typename T> DEV DLight light_pick(const KParams<T>& P, Rng& rng) {
+    DLight L = ld_light(P.lights + rng_index(rng, P.n_lights));
+    for (int d = 0; d < RT_MAX_LIGHT_NEST && (L.kind & 0xFFu) == L_LIST; d++) L = ld_light(P.lights + L.index + rng_index(rng, L.kind >> 8));
+    return L;
+}
+// HittableList::pdf_value (hit.rs:90-92) of the whole tree: at every level the children in push order, ((0 + p0) + p1) + ..., divided by
+// the count.  No recursion: a depth-first walk that keeps, per open level, the partial sum and the child it is at (the flattener bounds the
+// depth by RT_MAX_LIGHT_NEST); a level's list record — where its run ends, what it divides by — is the parent's current child, read again
+// when the level closes.  A flat list gives what the plain loops give.  (rt_debug_light_pdf runs this very function.)
+template <typename T, uint32_t FEATS> DEV T lights_pdf_tree(const KParams<T>& P, V3<T> o, V3<T> v) {
+    constexpr int N = RT_MAX_LIGHT_NEST + 1;
+    T sum[N]; uint32_t at[N];
+    int d = 0;
+    uint32_t end = P.n_lights, cnt = P.n_lights;            // of level d
+    sum[0] = T(0); at[0] = 0u;
+    for (;;) {
+        if (at[d] == end) {                                     // level d is done
+            const T val = sum[d] / T(cnt);
+            if (d == 0) return val;
+            d--; sum[d] += val; at[d]++;
+            if (d == 0) { end = P.n_lights; cnt = P.n_lights; }
+            else { const DLight up = ld_light(P.lights + at[d - 1]); cnt = up.kind >> 8; end = up.index + cnt; }
+            continue;
+        }
+        const DLight L = ld_light(P.lights + at[d]);
+        if ((L.kind & 0xFFu) == L_LIST && d + 1 < N) {
+            d++; sum[d] = T(0); at[d] = L.index; cnt = L.kind >> 8; end = L.index + cnt;
+        } else {
+            sum[d] += light_pdf_value<T, FEATS>(P, L, o, v); at[d]++;
+        }
+    }
+}
 template <typename T, uint32_t FEATS> DEV V3<T> light_random(const KParams<T>& P, DLight L, V3<T> o, Rng& rng) {
     if (L.kind == L_RECT) {                                                           // rect.rs:103-111
         const DRect<T> rc = ld_rect(P.rects + L.index);
@@ -1636,7 +1697,8 @@ DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& 
             uvw.u = cross(uvw.w, uvw.v);
             if (P.n_lights != 0u && rng_bool(rng)) {                        // pdf.rs:167-173 (no lights: deviation D2, cosine only)
                 to_light = true;
-                L = ld_light(P.lights + rng_index(rng, P.n_lights));        // hit.rs:94-96
+                if constexpr (Nested<FEATS>::on) L = light_pick<T>(P, rng);
+                else L = ld_light(P.lights + rng_index(rng, P.n_lights));   // hit.rs:94-96
             }
         }
         const bool two = !to_light || L.kind == L_RECT;
@@ -1666,9 +1728,13 @@ DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& 
             T cosine = dot(normalized(dir), uvw.w);                         // pdf.rs:131-139
             T pdf_value = (cosine > T(0)) ? cosine / PI_T : T(0);
             if (P.n_lights != 0u) {
+                T lpdf;
+                if constexpr (Nested<FEATS>::on) lpdf = lights_pdf_tree<T, FEATS>(P, rec.p, dir);
+                else {
                 T lsum = T(0);                                              // hit.rs:90-92
                 for (uint32_t li = 0; li < P.n_lights; li++) lsum += light_pdf_value<T, FEATS>(P, ld_light(P.lights + li), rec.p, dir);
-                T lpdf = P.n_lights == 1u ? lsum : lsum / T(P.n_lights);    // x / 1.0 is x
+                lpdf = P.n_lights == 1u ? lsum : lsum / T(P.n_lights);      // x / 1.0 is x
+                }
                 pdf_value = T(0.5) * lpdf + T(0.5) * pdf_value;             // pdf.rs:143-145
             }
             T sc = m_max(dot(rec.n, normalized(dir)), T(0)) / PI_T;         // scattering_pdf, mat.rs:246-249
@@ -1692,14 +1758,21 @@ DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& 
             pdf_value = (cosine > T(0)) ? cosine / PI_T : T(0);
         } else {
             if (rng_bool(rng)) {                                            // pdf.rs:167-173
+                if constexpr (Nested<FEATS>::on) dir = light_random<T, FEATS>(P, light_pick<T>(P, rng), rec.p, rng);
+                else {
                 uint32_t li = rng_index(rng, P.n_lights);                   // hit.rs:94-96
                 dir = light_random<T, FEATS>(P, ld_light(P.lights + li), rec.p, rng);
+                }
             } else {
                 dir = onb_local(uvw, random_cosine_direction<T>(rng));
             }
+            T lpdf;
+            if constexpr (Nested<FEATS>::on) lpdf = lights_pdf_tree<T, FEATS>(P, rec.p, dir);
+            else {
             T lsum = T(0);                                                  // hit.rs:90-92
             for (uint32_t li = 0; li < P.n_lights; li++) lsum += light_pdf_value<T, FEATS>(P, ld_light(P.lights + li), rec.p, dir);
-            T lpdf = lsum / T(P.n_lights);
+            lpdf = lsum / T(P.n_lights);
+            }
             T cosine = dot(normalized(dir), uvw.w);                         // pdf.rs:131-139
             T cpdf = (cosine > T(0)) ? cosine / PI_T : T(0);
             pdf_value = T(0.5) * lpdf + T(0.5) * cpdf;                      // pdf.rs:143-145
@@ -1745,14 +1818,22 @@ DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& 
             pdf_value = brdf_pdf_value(pm, uvw, ray.d, dir);
         } else {
             if (rng_bool(rng)) {
+                if constexpr (Nested<FEATS>::on) dir = light_random<T, FEATS>(P, light_pick<T>(P, rng), rec.p, rng);
+                else {
                 uint32_t li = rng_index(rng, P.n_lights);
                 dir = light_random<T, FEATS>(P, ld_light(P.lights + li), rec.p, rng);
+                }
             } else {
                 dir = brdf_pdf_generate(pm, uvw, ray.d, rng);
             }
+            T lpdf;
+            if constexpr (Nested<FEATS>::on) lpdf = lights_pdf_tree<T, FEATS>(P, rec.p, dir);
+            else {
             T lsum = T(0);
             for (uint32_t li = 0; li < P.n_lights; li++) lsum += light_pdf_value<T, FEATS>(P, ld_light(P.lights + li), rec.p, dir);
-            pdf_value = T(0.5) * (lsum / T(P.n_lights)) + T(0.5) * brdf_pdf_value(pm, uvw, ray.d, dir);
+            lpdf = lsum / T(P.n_lights);
+            }
+            pdf_value = T(0.5) * lpdf + T(0.5) * brdf_pdf_value(pm, uvw, ray.d, dir);
         }
         V3<T> base = tex_eval<T, FEATS>(P, mt.tex, rec.u, rec.v, rec.p);
         V3<T> f = pbr_brdf(pm, base, ray.d, dir, rec.n);
@@ -2339,6 +2420,19 @@ __global__ void aabb_kat_kernel(uint32_t n, const double* boxes, const double* r
     const BoxFilter Ff = make_filter(box_ok ? m : 0.0f, of, invf, tmin_f, tmax_f);
     out[i] = (exact ? 1 : 0) | (tame ? 2 : 0) | (tame_ray ? 4 : 0) | (F.ok ? 8 : 0) | (filter_pass(fn, F) ? 16 : 0)
              | (exact_f ? 32 : 0) | ((tame_f && Ff.ok) ? 64 : 0) | (filter_pass(fn, Ff) ? 128 : 0);
+}
+}
+namespace rt {
+// Known-answer access to the lights' pdf_value (rt_debug_light_pdf): lights_pdf_tree of the all-features kernel with object leaves
+// (F_ALL | F_NESTED, the instantiation that serves `lights` with lists inside), one (origin, direction) per lane.
+__global__ void light_pdf_kat_kernel(const KParams<double> P, uint32_t n, const double* o, const double* v, double* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = lights_pdf_tree<double, F_ALL | F_NESTED>(P, mk<double>(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk<double>(v[3 * i], v[3 * i + 1], v[3 * i + 2]));
+}
+hipError_t launch_light_pdf_kat(const KParams<double>& P, uint32_t n, const double* d_o, const double* d_v, double* d_out, hipStream_t stream) {
+    hipLaunchKernelGGL(light_pdf_kat_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_o, d_v, d_out);
+    return hipGetLastError();
 }
 }
 // out[i]: bit 0 = AABB::hit by the exact form, bit 1 = by the NaN-free form, bit 2 = the ray qualifies for the NaN-free form,

@@ -36,7 +36,8 @@ struct HostFlat {             // canonical f64 flattening
     std::vector<DMaterial<double>> materials;
     std::vector<DTexture<double>> textures;
     std::vector<DMedium<double>> media;
-    std::vector<DLight> lights;
+    std::vector<DLight> lights;        // the top level of `lights` [0, n_lights), then the children of HittableLists inside it (rt_ir.h L_LIST)
+    uint32_t n_lights = 0;
     uint32_t feats = 0;
     uint32_t bvh_depth = 0;
     bool bvh_tame = true;          // all BVH boxes finite, |.| < 1e300 (1e30 matters for the f32 variant: checked there too), min <= max

@@ -63,6 +63,22 @@ def debug_objects(b: SceneBuilder, top_only: bool = True) -> list:
     return [dict(zip(OBJECT_FIELDS, [int(x) for x in r])) for r in rows]
 
 
+def debug_light_pdf(b: SceneBuilder, origins: np.ndarray, dirs: np.ndarray) -> np.ndarray:
+    """rt_debug_light_pdf (needs a GPU): the scene's `lights` pdf_value (HittableList::pdf_value, nested lists included) for n
+    (origin, direction) pairs, computed on the device by the function the all-features kernel with object leaves runs."""
+    be = _lib.load()
+    be.lib.rt_debug_light_pdf.restype = C.c_int
+    be.lib.rt_debug_light_pdf.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and dirs differ in shape")
+    out = np.zeros(len(o), np.float64)
+    if be.lib.rt_debug_light_pdf(b.h, len(o), o.ctypes.data, d.ctypes.data, out.ctypes.data) != 0:
+        raise RenderError(_err(be))
+    return out
+
+
 RT_BVH_MEDIAN, RT_BVH_SAH = 0, 1
 
 
