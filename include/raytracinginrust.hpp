@@ -9,6 +9,8 @@
 // reference reports by panic (src/bvh.rs:55, src/main.rs:431) surface as rtr::Error.
 #pragma once
 #include <array>
+#include <cstdio>
+#include <cstring>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -162,6 +164,39 @@ inline std::vector<double> render_multi(Scene& s, const Camera& cam, Color backg
 // main.rs:767-769,832
 inline void write_ppm(const char* path, const std::vector<double>& rgb_sum, uint32_t W, uint32_t H, uint64_t spp) {
     if (rt_write_ppm(path, rgb_sum.data(), W, H, spp) != 0) throw Error(rt_last_error());
+}
+
+// A progressive frame (rt_progressive_*): the same loop in passes of samples that accumulate on the device, with the reference's
+// format_color (src/vec.rs:125-131) resolved there too — progress, preview, stop half-way, "another 1000 samples", save and resume.
+class Progressive {
+public:
+    Progressive(Scene& s, const Camera& cam, Color background, uint32_t W, uint32_t H, uint32_t max_depth, uint64_t seed = 0x5EED, uint32_t flags = RT_F64)
+        : p_(rt_progressive_create(s.raw(), &cam.c, background.e, W, H, max_depth, seed, flags)), n_px_((size_t)W * H) { if (!p_) throw Error(rt_last_error()); }
+    ~Progressive() { rt_progressive_destroy(p_); }
+    Progressive(const Progressive&) = delete; Progressive& operator=(const Progressive&) = delete;
+    void* raw() const { return p_; }
+    void add(uint32_t n_samples) { chk(rt_progressive_add(p_, n_samples, nullptr)); }                 // samples [done, done + n) of every pixel
+    uint64_t samples() const { uint64_t n = 0; chk(rt_progressive_samples(p_, &n)); return n; }
+    // format_color(samples()) of every pixel, W*H*3 bytes in output order; changed_px: pixels that differ from the previous resolve
+    std::vector<uint8_t> rgb8(uint64_t* changed_px = nullptr) { std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_rgb8(p_, out.data(), changed_px)); return out; }
+    std::vector<double> sum() const { std::vector<double> out(n_px_ * 3); chk(rt_progressive_read_sum(p_, out.data())); return out; }
+    void load(const std::vector<double>& rgb_sum, uint64_t samples_done) {
+        if (rgb_sum.size() != n_px_ * 3) throw Error("checkpoint of another frame size");
+        chk(rt_progressive_load_sum(p_, rgb_sum.data(), samples_done));
+    }
+    void reset() { chk(rt_progressive_reset(p_)); }
+private:
+    static void chk(int rc) { if (rc != 0) throw Error(rt_last_error()); }
+    void* p_; size_t n_px_;
+};
+// main.rs:767-769,832 from an image that is already format_color's output (Progressive::rgb8): the same bytes write_ppm emits
+inline void write_ppm_rgb8(const char* path, const std::vector<uint8_t>& rgb8, uint32_t W, uint32_t H) {
+    if (rgb8.size() != (size_t)W * H * 3) throw Error("write_ppm_rgb8: image of another size");
+    FILE* f = (!path || std::strcmp(path, "-") == 0) ? stdout : std::fopen(path, "w");
+    if (!f) throw Error(std::string("cannot open ") + path);
+    std::fprintf(f, "P3\n%u %u\n255\n", W, H);
+    for (size_t p = 0; p < (size_t)W * H; p++) std::fprintf(f, "%u %u %u\n", (unsigned)rgb8[p * 3], (unsigned)rgb8[p * 3 + 1], (unsigned)rgb8[p * 3 + 2]);
+    if (f != stdout) std::fclose(f); else std::fflush(f);
 }
 
 } // namespace rtr

@@ -178,9 +178,67 @@ int rt_render_device(rt_scene*, const rt_camera*, const double background[3], ui
                      uint32_t samples_per_pixel, uint32_t max_depth, uint64_t seed, uint32_t flags,
                      uint32_t tile_px, uint32_t rank, uint32_t world_size,
                      void* d_out, size_t d_out_bytes, void* hip_stream);
+/* The same launch for samples [first_sample, first_sample + samples_per_pixel) of every pixel — the very samples a frame of more samples
+ * per pixel and the same seed holds at those indices: a path's stream is keyed by z = seed + 2*((pixel << 32) | sample)*G (csrc/rt_rng.h),
+ * so the offset is folded into the seed the launch receives, z(seed, pixel, sample + first) = z(seed + 2*first*G mod 2^64, pixel, sample)
+ * while sample + first < 2^32; first_sample + samples_per_pixel > 2^32 - 1 is an error.  accumulate != 0: d_out is not zeroed first, the
+ * pass is ADDED to what it holds (the kernels' only global writes are f64 atomic adds).  The building block of rt_progressive_* below for
+ * one-process-per-GPU callers; asynchronous, never calibrates — like rt_render_device, which is this with (0, 0). */
+int rt_render_device_pass(rt_scene*, const rt_camera*, const double background[3], uint32_t W, uint32_t H,
+                          uint32_t samples_per_pixel, uint32_t max_depth, uint64_t seed, uint32_t flags,
+                          uint32_t first_sample, int accumulate,
+                          uint32_t tile_px, uint32_t rank, uint32_t world_size,
+                          void* d_out, size_t d_out_bytes, void* hip_stream);
 /* (rt_render_device and rt_render_multi_device never wait: everything that has to — the first use of a scene on a device, see
  * rt_scene_prepare, and the loop-shape calibration of a mesh scene, see rt_scene_calibrate — is done inside them only as far as it can
  * be done without a wait; call those two first where it matters.) */
+/* ---- progressive frames: the reference's loop shows its progress (`Scanlines remaining`, src/main.rs:772-775) and formats every pixel as
+ *      it is finished (src/main.rs:832); rt_render is silent until the last sample.  A progressive frame owns a device-resident f64 sum
+ *      frame for ONE fixed view of one scene, takes passes of samples that accumulate into it, and resolves it to the reference's 8-bit
+ *      output ON THE DEVICE at any time: progress, preview, "another 1000 samples", stop half-way, save and resume.
+ * The handle is an opaque pointer (`void* frame`; NULL + rt_last_error() when create fails).  The sum frame, the RGB8 image and the
+ * previous RGB8 image live on the HIP device that was current at create; every call below works on that device whatever the current
+ * device is, and restores it.  rt_render* are untouched, and a frame and one-shot renders of the same scene may be interleaved freely.
+ * A change to the scene after create makes the next add an error (the scene forgets everything on a change; so does the frame) until
+ * rt_progressive_reset; a frame outlives its scene (it can still be resolved, read and destroyed; add is an error). */
+/* One fixed view: the arguments of rt_render without the sample count.  Fails without a HIP device, as rt_render does. */
+void* rt_progressive_create(rt_scene*, const rt_camera*, const double background[3], uint32_t W, uint32_t H,
+                            uint32_t max_depth, uint64_t seed, uint32_t flags);
+/* One pass of the sample loop src/main.rs:811-830: samples [done, done + n_samples) of every pixel — the very samples rt_render with
+ * samples_per_pixel >= done + n_samples and the same seed renders at those indices (rt_render_device_pass) — added to the frame.
+ * samples_out (NULL, or n_samples*W*H*3 doubles) receives the pass's samples laid out as rt_render_samples lays out a frame of n_samples.
+ * Errors, nothing launched: n_samples = 0; done + n_samples > 2^32 - 1.  Goes through the launch rt_render uses (loop shape, filter tuning,
+ * chunking; rt_last_kernel_ms, rt_last_stats, rt_last_loop_info report the pass).  Synchronous; it tunes / calibrates as rt_render does,
+ * deciding by the VIEW as accumulated so far: a mesh scene's loop shape is measured at the pass with which W*H*(done + n_samples) reaches
+ * the 1e8 samples at which a one-shot frame measures it (either shape gives the same samples, so a frame may change shape between passes). */
+int rt_progressive_add(void* frame, uint32_t n_samples, double* samples_out);
+/* The same pass enqueued on hip_stream (a hipStream_t of the frame's device, may be NULL); never waits, never calibrates — like
+ * rt_render_device.  Passes on different streams may overlap: they only ever add. */
+int rt_progressive_add_async(void* frame, uint32_t n_samples, void* hip_stream);
+int rt_progressive_samples(void* frame, uint64_t* done_out);               /* samples per pixel accumulated so far (enqueued passes included) */
+/* Vec3::format_color(samples done), src/vec.rs:125-131, for every pixel ON THE DEVICE (csrc/rt_resolve.hip) — equal to rt_format_color
+ * on every input, bit for bit — copied to rgb8_out (W*H*3 bytes, output order: what src/main.rs:832 prints).  *changed_px_out (may be
+ * NULL): the pixels whose triple differs from the previous resolve of this frame — a convergence signal: stop when the 8-bit image has
+ * stopped moving; the first resolve of a frame (also after load_sum / reset) reports W*H.  Waits for every pass enqueued so far.
+ * An error while the frame holds 0 samples. */
+int rt_progressive_resolve_rgb8(void* frame, uint8_t* rgb8_out, uint64_t* changed_px_out);
+/* The same resolve enqueued on hip_stream, never waits: *d_rgb8_out (may be NULL) receives the DEVICE address of the W*H*3 bytes, owned by
+ * the frame.  Resolves alternate between TWO images, so an address stays valid, and its pixels untouched, until the next-but-one resolve.
+ * Ordered after the passes of the same stream only.  rt_progressive_copy_rgb8 waits and copies the most recent resolve and its
+ * changed-pixel count to host memory without resolving again: rt_progressive_resolve_rgb8 = wait + the two. */
+int rt_progressive_resolve_rgb8_device(void* frame, void** d_rgb8_out, void* hip_stream);
+int rt_progressive_copy_rgb8(void* frame, uint8_t* rgb8_out, uint64_t* changed_px_out);
+/* The accumulated sums, W*H*3 doubles in output order, as rt_render returns them (waits for the passes enqueued so far): with
+ * rt_progressive_samples, a checkpoint.  The f64 atomic adds reach a pixel in no fixed order, so sums of the same samples differ between
+ * runs and from rt_render's within the bound that holds for any order of adding N terms, 2*gamma*sum|x_i|, gamma = (N-1)u / (1 - (N-1)u), u = 2^-53. */
+int rt_progressive_read_sum(void* frame, double* rgb_sum_out);
+/* Resume from a checkpoint: the frame becomes rgb_sum (W*H*3 doubles) holding samples_done samples per pixel; the next pass starts at sample
+ * samples_done.  Errors: samples_done > 2^32 - 1; samples_done = 0 with a frame that is not all zero. */
+int rt_progressive_load_sum(void* frame, const double* rgb_sum, uint64_t samples_done);
+/* Back to 0 samples, same view — of the scene as it is now (this is what makes a frame usable again after the scene changed). */
+int rt_progressive_reset(void* frame);
+void rt_progressive_destroy(void* frame);                                  /* waits for the frame's work; the scene may be gone already */
+
 /* The whole frame on several GPUs of this node from ONE call: what a host that owns the node's GPUs itself (the reference's `main`,
  * src/main.rs:767-835) calls instead of rt_render.  device_mask: bit d selects HIP device d (0 = every visible device).  The scene
  * is replicated on each selected device; tiles of tile_px output-order pixels (0 = the default, 67) are dealt round-robin, each

@@ -69,6 +69,20 @@ def load_path(path: str) -> Backend:
         lib.rt_multi_sync.argtypes = [C.c_void_p]
         lib.rt_multi_copy_frame.restype = C.c_int
         lib.rt_multi_copy_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    if hasattr(lib, "rt_progressive_create"):        # progressive frames (tools/ab.py also loads builds that predate them)
+        lib.rt_render_device_pass.restype = C.c_int
+        lib.rt_render_device_pass.argtypes = common + [C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.rt_progressive_create.restype = C.c_void_p
+        lib.rt_progressive_create.argtypes = [C.c_void_p, cam_p, c_double_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]
+        lib.rt_progressive_destroy.restype = None
+        lib.rt_progressive_destroy.argtypes = [C.c_void_p]
+        for name, args in (("add", [C.c_uint32, C.c_void_p]), ("add_async", [C.c_uint32, C.c_void_p]), ("samples", [C.POINTER(C.c_uint64)]),
+                           ("resolve_rgb8", [C.c_void_p, C.POINTER(C.c_uint64)]), ("resolve_rgb8_device", [C.POINTER(C.c_void_p), C.c_void_p]),
+                           ("copy_rgb8", [C.c_void_p, C.POINTER(C.c_uint64)]), ("read_sum", [C.c_void_p]),
+                           ("load_sum", [C.c_void_p, C.c_uint64]), ("reset", [])):
+            fn = getattr(lib, "rt_progressive_" + name)
+            fn.restype = C.c_int
+            fn.argtypes = [C.c_void_p] + args
     lib.rt_last_multi_ms.restype = C.c_int
     lib.rt_last_multi_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     lib.rt_kernel_time_total.restype = C.c_int

@@ -13,6 +13,7 @@
 #include "../../include/rt_amd.h"
 #include "rt_scene.h"
 #include "rt_launch.h"
+#include "rt_resolve.h"
 
 using namespace rt;
 
@@ -22,6 +23,22 @@ bool parse_obj(const char* data, size_t size, const double offset[3], double sca
 }
 
 struct rt_rng { Rng r; };
+
+// A progressive frame (rt_progressive_*, include/rt_amd.h): one fixed view of one scene, the device-resident f64 sum frame its passes
+// accumulate into, and two RGB8 images — the most recent resolve and the one before it, which the next resolve is compared with and
+// then overwrites.  Everything lives on `device`.  The handle the C-ABI passes around (a void*) is a pointer to this.
+struct Progressive {
+    rt_scene* sc = nullptr;                // nullptr once the scene has been destroyed: the frame can still be read, resolved and destroyed
+    unsigned long long scene_version = 0;  // Scene::version at create / reset: a pass after a change to the scene is refused
+    rt_camera cam; double bg[3] = {0, 0, 0};
+    uint32_t W = 0, H = 0, max_depth = 0, flags = 0; uint64_t seed = 0;
+    int device = -1;
+    uint64_t done = 0;                     // samples per pixel accumulated so far
+    void* d_sum = nullptr;                 // W*H*3 doubles, output order
+    void* d_rgb8[2] = {nullptr, nullptr}; int cur = 0; bool have_prev = false, resolved = false;     // d_rgb8[cur]: the most recent resolve
+    void* d_changed = nullptr;             // one 64-bit word: the most recent resolve's changed-pixel count
+    size_t n_px() const { return (size_t)W * H; }
+};
 
 static thread_local std::string g_err;
 static int set_err(const std::string& m) { g_err = m; return -1; }
@@ -61,6 +78,7 @@ rt_scene* rt_scene_create(void) { return new rt_scene(); }
 void rt_scene_destroy(rt_scene* sc) {
     if (!sc) return;
     int cur = 0; (void)hipGetDevice(&cur);
+    for (void* f : sc->s.frames) ((Progressive*)f)->sc = nullptr;      // progressive frames outlive their scene (they own their buffers)
     rt::multi_release(sc->s);
     if (sc->s.d_trace) { (void)hipSetDevice(sc->s.trace_device); (void)hipFree(sc->s.d_trace); sc->s.d_trace = nullptr; (void)hipSetDevice(cur); }
     if (sc->s.d_calib) { (void)hipSetDevice(sc->s.calib_device); (void)hipDeviceSynchronize(); (void)hipFree(sc->s.d_calib); sc->s.d_calib = nullptr; (void)hipSetDevice(cur); }
@@ -618,7 +636,7 @@ static bool room_nan_path() { return std::getenv("RT_ROOM_NO_NAN_PATH") == nullp
 template <typename T>
 int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
                 uint64_t seed, uint32_t flags, uint32_t tile_px, uint32_t rank, uint32_t world, void* d_out, size_t d_out_bytes,
-                void* d_samples, hipStream_t stream) {
+                void* d_samples, hipStream_t stream, bool accumulate = false) {
     Scene::DeviceCtx* cp = nullptr;
     if (current_ctx(s, &cp)) return -1;
     Scene::DeviceCtx& c = *cp;
@@ -733,7 +751,7 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     }
     HIP_OK(hipMemsetAsync(slot->d_queue, 0, 64, stream));
     HIP_OK(hipMemsetAsync(slot->d_stats, 0, RT_STATS_BYTES, stream));
-    HIP_OK(hipMemsetAsync(d_out, 0, (size_t)n_local_px * 3 * sizeof(double), stream));
+    if (!accumulate) HIP_OK(hipMemsetAsync(d_out, 0, (size_t)n_local_px * 3 * sizeof(double), stream));      // (a pass of a progressive frame adds to what is there)
     HIP_OK(hipEventRecord((hipEvent_t)slot->ev_start, stream));
     HIP_OK(launch_pathtrace<T>(P, f.feats, (uint32_t)n_blocks, shmem, stream));
     HIP_OK(hipEventRecord((hipEvent_t)slot->ev_stop, stream));
@@ -830,14 +848,24 @@ static int calibrate_loop_shape(Scene& s, const rt_camera* cam, const double bg[
 
 int render_any(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
                uint64_t seed, uint32_t flags, uint32_t tile_px, uint32_t rank, uint32_t world, void* d_out, size_t d_out_bytes,
-               void* d_samples, hipStream_t stream, bool may_calibrate) {
+               void* d_samples, hipStream_t stream, bool may_calibrate, uint32_t first_sample = 0u, bool accumulate = false) {
     if (check_frame_args(sc, cam, bg, W, H, spp)) return -1;
     if (tile_px == 0 || world == 0 || rank >= world) return set_err("bad tile decomposition");
+    if ((uint64_t)first_sample + spp > 0xFFFFFFFFull) return set_err("first_sample + samples_per_pixel must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
     if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
     if (!flatten_scene(sc->s)) { g_err = sc->s.error; return -1; }
-    if (may_calibrate && (tune_for_view(sc->s, cam, W, H) || calibrate_loop_shape(sc->s, cam, bg, W, H, spp, max_depth, seed, flags, stream, true))) return -1;
-    if (flags & RT_F32) return render_impl<float>(sc->s, cam, bg, W, H, spp, max_depth, seed, flags, tile_px, rank, world, d_out, d_out_bytes, d_samples, stream);
-    return render_impl<double>(sc->s, cam, bg, W, H, spp, max_depth, seed, flags, tile_px, rank, world, d_out, d_out_bytes, d_samples, stream);
+    // A pass decides by the VIEW as accumulated so far — first_sample + spp samples per pixel — not by its own sample count: a frame fed in
+    // 16-sample passes calibrates at the pass with which it reaches the size at which a one-shot frame would have.
+    const uint32_t view_spp = first_sample + spp;
+    if (may_calibrate && (tune_for_view(sc->s, cam, W, H) || calibrate_loop_shape(sc->s, cam, bg, W, H, view_spp, max_depth, seed, flags, stream, true))) return -1;
+    // Samples [first_sample, first_sample + spp) of every pixel as an ordinary frame of spp samples: the kernels key a path's stream by
+    // z = seed + 2 * ((pixel << 32) | sample) * G  (mod 2^64; rt_rng.h rng_for_path), and while sample + first_sample < 2^32 the sum stays
+    // inside the sample field, so  z(seed, pixel, sample + first_sample) = z(seed + 2 * first_sample * G, pixel, sample): the offset is
+    // folded into the seed the launch receives, and no kernel knows about passes (tests/test_progressive_host.py pins the identity).
+    const uint64_t G = 0x9E3779B97F4A7C15ULL;
+    const uint64_t pass_seed = seed + 2ULL * (uint64_t)first_sample * G;
+    if (flags & RT_F32) return render_impl<float>(sc->s, cam, bg, W, H, spp, max_depth, pass_seed, flags, tile_px, rank, world, d_out, d_out_bytes, d_samples, stream, accumulate);
+    return render_impl<double>(sc->s, cam, bg, W, H, spp, max_depth, pass_seed, flags, tile_px, rank, world, d_out, d_out_bytes, d_samples, stream, accumulate);
 }
 
 } // namespace
@@ -847,6 +875,14 @@ extern "C" {
 int rt_render_device(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
                      uint64_t seed, uint32_t flags, uint32_t tile_px, uint32_t rank, uint32_t world, void* d_out, size_t d_out_bytes, void* hip_stream) {
     return render_any(sc, cam, bg, W, H, spp, max_depth, seed, flags, tile_px, rank, world, d_out, d_out_bytes, nullptr, (hipStream_t)hip_stream, false);
+}
+
+// rt_render_device for samples [first_sample, first_sample + spp) of every pixel; accumulate != 0: added to what d_out holds
+int rt_render_device_pass(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
+                          uint64_t seed, uint32_t flags, uint32_t first_sample, int accumulate, uint32_t tile_px, uint32_t rank, uint32_t world,
+                          void* d_out, size_t d_out_bytes, void* hip_stream) {
+    return render_any(sc, cam, bg, W, H, spp, max_depth, seed, flags, tile_px, rank, world, d_out, d_out_bytes, nullptr, (hipStream_t)hip_stream, false,
+                      first_sample, accumulate != 0);
 }
 
 // Mesh scenes: measure which loop shape is faster for this view (see calibrate_loop_shape) — synchronous, on the calling thread's current
@@ -1082,6 +1118,159 @@ int rt_debug_get_trace(rt_scene* sc, double* out, uint32_t n_levels) {
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(out, sc->s.d_trace, (size_t)n_levels * 16u * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---------------------------------------------------------------- progressive frames
+// (the reference's loop prints `Scanlines remaining` while it works, src/main.rs:772-775, and formats each pixel as it is finished,
+// src/main.rs:832: a frame that accumulates passes of samples and can be resolved to the 8-bit image at any time is that, per pass)
+static void progressive_free(Progressive* p) {
+    DeviceGuard guard(p->device);
+    (void)hipDeviceSynchronize();                   // passes and resolves may still be in flight on the caller's streams
+    free_dev(p->d_sum); free_dev(p->d_rgb8[0]); free_dev(p->d_rgb8[1]); free_dev(p->d_changed);
+}
+void* rt_progressive_create(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t max_depth,
+                            uint64_t seed, uint32_t flags) {
+    if (check_frame_args(sc, cam, bg, W, H, 1u)) return nullptr;
+    if (rt_device_count() <= 0) { set_err("no HIP device: librt_amd has no CPU rendering path"); return nullptr; }
+    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return nullptr; }
+    Progressive* p = new Progressive();
+    p->sc = sc; p->scene_version = sc->s.version; std::memcpy(&p->cam, cam, sizeof(rt_camera));
+    for (int k = 0; k < 3; k++) p->bg[k] = bg[k];
+    p->W = W; p->H = H; p->max_depth = max_depth; p->flags = flags; p->seed = seed;
+    const size_t n = p->n_px();
+    hipError_t e = hipGetDevice(&p->device);
+    if (e == hipSuccess) e = hipMalloc(&p->d_sum, n * 3 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&p->d_rgb8[0], n * 3);
+    if (e == hipSuccess) e = hipMalloc(&p->d_rgb8[1], n * 3);
+    if (e == hipSuccess) e = hipMalloc(&p->d_changed, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_sum, 0, n * 3 * sizeof(double), nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        set_err(std::string("rt_progressive_create: ") + hipGetErrorString(e));
+        if (p->device >= 0) progressive_free(p);
+        delete p; return nullptr;
+    }
+    sc->s.frames.push_back(p);
+    return p;
+}
+void rt_progressive_destroy(void* frame) {
+    Progressive* p = (Progressive*)frame;
+    if (!p) return;
+    if (p->sc) { std::vector<void*>& fr = p->sc->s.frames; fr.erase(std::remove(fr.begin(), fr.end(), (void*)p), fr.end()); }
+    progressive_free(p);
+    delete p;
+}
+// what both forms of a pass check before anything is launched
+static int progressive_pass_args(Progressive* p, uint32_t n) {
+    if (n == 0) return set_err("n_samples must be >= 1");
+    if (!p) return set_err("null argument");
+    if (!p->sc) return set_err("the scene of this progressive frame has been destroyed");
+    if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
+    if (p->done + n > 0xFFFFFFFFull) return set_err("samples done + n_samples must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
+    return 0;
+}
+static int progressive_pass(Progressive* p, uint32_t n, void* d_samples, hipStream_t stream, bool may_calibrate) {
+    const size_t n_px = p->n_px();
+    if (render_any(p->sc, &p->cam, p->bg, p->W, p->H, n, p->max_depth, p->seed, p->flags, (uint32_t)n_px, 0, 1, p->d_sum, n_px * 3 * sizeof(double),
+                   d_samples, stream, may_calibrate, (uint32_t)p->done, true)) return -1;
+    p->done += n;
+    return 0;
+}
+int rt_progressive_add(void* frame, uint32_t n, double* samples_out) {
+    Progressive* p = (Progressive*)frame;
+    if (progressive_pass_args(p, n)) return -1;
+    DeviceGuard guard(p->device);
+    void* d_samples = nullptr;
+    const size_t sample_bytes = p->n_px() * n * 3 * sizeof(double);
+    if (samples_out) HIP_OK(hipMalloc(&d_samples, sample_bytes));
+    int rc = progressive_pass(p, n, d_samples, nullptr, true);
+    if (rc == 0) {
+        hipError_t e = hipStreamSynchronize(nullptr);
+        if (e == hipSuccess && samples_out) e = hipMemcpy(samples_out, d_samples, sample_bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { g_err = std::string("rt_progressive_add: ") + hipGetErrorString(e); rc = -1; }
+    }
+    if (d_samples) (void)hipFree(d_samples);
+    return rc;
+}
+int rt_progressive_add_async(void* frame, uint32_t n, void* hip_stream) {
+    Progressive* p = (Progressive*)frame;
+    if (progressive_pass_args(p, n)) return -1;
+    DeviceGuard guard(p->device);
+    return progressive_pass(p, n, nullptr, (hipStream_t)hip_stream, false);
+}
+int rt_progressive_samples(void* frame, uint64_t* done_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !done_out) return set_err("null argument");
+    *done_out = p->done;
+    return 0;
+}
+int rt_progressive_resolve_rgb8_device(void* frame, void** d_rgb8_out, void* hip_stream) {
+    Progressive* p = (Progressive*)frame;
+    if (!p) return set_err("null argument");
+    if (p->done == 0) return set_err("nothing to resolve: the frame holds 0 samples (format_color divides by the sample count, src/vec.rs:126)");
+    DeviceGuard guard(p->device);
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int next = 1 - p->cur;
+    HIP_OK(hipMemsetAsync(p->d_changed, 0, sizeof(unsigned long long), stream));
+    HIP_OK(launch_resolve_rgb8((const double*)p->d_sum, p->done, p->have_prev ? (const uint8_t*)p->d_rgb8[p->cur] : nullptr, (uint8_t*)p->d_rgb8[next],
+                               (unsigned long long*)p->d_changed, (uint32_t)p->n_px(), stream));
+    p->cur = next; p->have_prev = true; p->resolved = true;
+    if (d_rgb8_out) *d_rgb8_out = p->d_rgb8[next];
+    return 0;
+}
+int rt_progressive_copy_rgb8(void* frame, uint8_t* rgb8_out, uint64_t* changed_px_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !rgb8_out) return set_err("null argument");
+    if (!p->resolved) return set_err("the frame has not been resolved (rt_progressive_resolve_rgb8_device)");
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(rgb8_out, p->d_rgb8[p->cur], p->n_px() * 3, hipMemcpyDeviceToHost));
+    unsigned long long changed = 0;
+    HIP_OK(hipMemcpy(&changed, p->d_changed, sizeof(changed), hipMemcpyDeviceToHost));
+    if (changed_px_out) *changed_px_out = changed;
+    return 0;
+}
+int rt_progressive_resolve_rgb8(void* frame, uint8_t* rgb8_out, uint64_t* changed_px_out) {
+    if (!frame || !rgb8_out) return set_err("null argument");
+    {   // passes enqueued on the caller's streams (rt_progressive_add_async) belong to the image
+        DeviceGuard guard(((Progressive*)frame)->device);
+        HIP_OK(hipDeviceSynchronize());
+    }
+    if (rt_progressive_resolve_rgb8_device(frame, nullptr, nullptr)) return -1;
+    return rt_progressive_copy_rgb8(frame, rgb8_out, changed_px_out);
+}
+int rt_progressive_read_sum(void* frame, double* rgb_sum_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !rgb_sum_out) return set_err("null argument");
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(rgb_sum_out, p->d_sum, p->n_px() * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+static int progressive_restart(Progressive* p, const double* rgb_sum, uint64_t samples_done) {
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());                 // nothing of the old frame may still be adding to the buffer
+    if (rgb_sum) HIP_OK(hipMemcpy(p->d_sum, rgb_sum, p->n_px() * 3 * sizeof(double), hipMemcpyHostToDevice));
+    else { HIP_OK(hipMemsetAsync(p->d_sum, 0, p->n_px() * 3 * sizeof(double), nullptr)); HIP_OK(hipStreamSynchronize(nullptr)); }
+    p->done = samples_done; p->have_prev = false; p->resolved = false;       // the next resolve is a first one: every pixel counts as changed
+    return 0;
+}
+int rt_progressive_load_sum(void* frame, const double* rgb_sum, uint64_t samples_done) {
+    Progressive* p = (Progressive*)frame;
+    if (!rgb_sum) return set_err("null argument");
+    if (samples_done > 0xFFFFFFFFull) return set_err("samples_done must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
+    if (!p) return set_err("null argument");
+    if (samples_done == 0) {                        // 0 samples is the empty frame and nothing else (-0.0 is not empty either: its bits are a checkpoint's)
+        const size_t n = p->n_px() * 3;
+        for (size_t i = 0; i < n; i++) { uint64_t w; std::memcpy(&w, rgb_sum + i, sizeof(w)); if (w != 0) return set_err("samples_done = 0 with a non-zero frame: a checkpoint is a sum AND its sample count"); }
+    }
+    return progressive_restart(p, rgb_sum, samples_done);
+}
+int rt_progressive_reset(void* frame) {
+    Progressive* p = (Progressive*)frame;
+    if (!p) return set_err("null argument");
+    if (p->sc) p->scene_version = p->sc->s.version;     // a new frame, of the scene as it is now
+    return progressive_restart(p, nullptr, 0);
 }
 
 int rt_render_samples(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,

@@ -134,7 +134,11 @@ struct Scene {
     // debugging aid (rt_debug_trace_path; -DRT_TRACE_PATH builds of the kernels): the path whose hits are recorded, and the device buffer
     long long trace_px = -1, trace_s = -1; void* d_trace = nullptr; int trace_device = -1; uint32_t trace_levels = 0;     // trace_levels: 16-double records d_trace holds
 
-    void invalidate() { flat_valid = false; loop_choice = -1; loop_how = 0; loop_ms[0] = loop_ms[1] = 0.f; filter_key = 0; }
+    // Progressive frames (rt_progressive_*, rt_host.cpp) of this scene: a frame holds the `version` it was created at — every change to the
+    // scene moves it on, and the frame's next pass is refused — and is told when the scene is destroyed before it.
+    unsigned long long version = 0; std::vector<void*> frames;
+
+    void invalidate() { flat_valid = false; loop_choice = -1; loop_how = 0; loop_ms[0] = loop_ms[1] = 0.f; filter_key = 0; version++; }
     DeviceCtx& ctx_for(int device) {
         for (DeviceCtx* c : ctxs) if (c->device == device) return *c;
         DeviceCtx* c = new DeviceCtx(); c->device = device; ctxs.push_back(c); return *c;

@@ -4,9 +4,13 @@
 // (same constructor names and argument order).  Usage mirrors `cargo run --release > image.ppm` (README.md:4):
 //
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
-//              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] > image.ppm
+//              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] > image.ppm
+//
+// --progressive N (opt-in, one GPU): the frame in passes of N samples per pixel (rt_progressive_*), the reference's style of progress on
+// stderr (main.rs:772-775), and the same PPM bytes at the end, built from the image the device resolved.
 //
 // The reference hard-codes its settings as consts (main.rs:579-583, :623); they are flags here.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -218,6 +222,7 @@ int main(int argc, char** argv) {
     SceneKind scene = SceneKind::CornellBox;
     uint32_t image_width = 500, image_height = 500, samples_per_pixel = 800, max_depth = 100;    // main.rs:579-583
     uint64_t seed = 0x5EED; uint32_t flags = RT_F64; bool fast_bvh = false;
+    uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
     int gpus = 1;                                                           // --gpus N: the first N devices (0 = all) through rt_render_multi
     std::string obj_path = "teapot.obj", earth_path = "earthmap.jpg";       // the reference's asset names (main.rs:248,491)
     for (int i = 1; i < argc; i++) {
@@ -240,6 +245,7 @@ int main(int argc, char** argv) {
         else if (a == "--earth") earth_path = next();
         else if (a == "--f32") flags |= RT_F32;
         else if (a == "--gpus") gpus = std::atoi(next());
+        else if (a == "--progressive") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--progressive needs a pass size >= 1\n"); return 2; } progressive = (uint32_t)n; }
         else if (a == "--collective") flags |= RT_MULTI_COLLECTIVE;         // with --gpus 1: run the RCCL gather anyway
         else if (a == "--fast-bvh") { fast_bvh = true; flags |= RT_NEAR_FIRST_BVH; }      // opt-in, not the reference's tree / visiting order
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
@@ -309,6 +315,18 @@ int main(int argc, char** argv) {
         }
         }
         // main.rs:772-833: the whole loop nest is this one call
+        if (progressive) {
+            if (gpus != 1 || (flags & RT_MULTI_COLLECTIVE)) throw Error("--progressive renders on one GPU");
+            Progressive frame(s, camera, background, image_width, image_height, max_depth, seed, flags);
+            while (frame.samples() < samples_per_pixel) {
+                frame.add((uint32_t)std::min<uint64_t>(progressive, samples_per_pixel - frame.samples()));
+                std::fprintf(stderr, "\rSamples: %llu / %u", (unsigned long long)frame.samples(), samples_per_pixel);    // main.rs:772-775
+            }
+            std::fprintf(stderr, "\n");
+            write_ppm_rgb8("-", frame.rgb8(), image_width, image_height);                        // main.rs:767-769,832
+            std::fprintf(stderr, "Done.\n");                                                    // main.rs:835
+            return 0;
+        }
         std::vector<double> pixel_sums;
         if (gpus == 1 && !(flags & RT_MULTI_COLLECTIVE)) {
             pixel_sums = render(s, camera, background, image_width, image_height, samples_per_pixel, max_depth, seed, flags);

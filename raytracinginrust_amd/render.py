@@ -161,6 +161,124 @@ def render(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, spp: 
     return (out, samples) if want_samples else out
 
 
+class Progressive:
+    """A progressive frame (rt_progressive_*): one fixed view of one scene, a device-resident f64 sum frame that passes of samples
+    accumulate into, resolved to the reference's 8-bit output on the device at any time.  Pass k holds samples [done, done + n) of every
+    pixel — the very samples `render` with spp >= done + n and the same seed holds at those indices.  A context manager:
+
+        with Progressive(b, cam, bg, W, H, max_depth) as frame:
+            while frame.samples < 1024:
+                frame.add(64)
+                image, changed = frame.rgb8()        # (H, W, 3) uint8 and the pixels that differ from the previous resolve
+    """
+
+    def __init__(self, b: SceneBuilder, cam: CameraParams, background, W: int, H: int, max_depth: int, seed: int = 0x5EED, flags: int = RT_F64):
+        self._be = _lib.load()
+        self.W, self.H = int(W), int(H)
+        bg = (C.c_double * 3)(*[float(x) for x in background])
+        self._h = self._be.lib.rt_progressive_create(b.h, C.byref(cam), bg, W, H, max_depth, seed, flags)
+        if not self._h:
+            raise RenderError(_err(self._be))
+        self._builder = b              # the scene stays alive at least as long as the frame
+
+    def _check(self, rc) -> None:
+        if rc != 0:
+            raise RenderError(_err(self._be))
+
+    def add(self, n: int, want_samples: bool = False):
+        """One synchronous pass of n samples per pixel; with want_samples returns them, (H, W, n, 3) as `render` lays them out."""
+        samples = np.zeros((self.H, self.W, n, 3), dtype=np.float64) if want_samples else None
+        self._check(self._be.lib.rt_progressive_add(self._h, n, samples.ctypes.data if want_samples else None))
+        return samples
+
+    def add_async(self, n: int, stream: int = 0) -> None:
+        """The same pass enqueued on a HIP stream of the frame's device; never waits."""
+        self._check(self._be.lib.rt_progressive_add_async(self._h, n, C.c_void_p(stream)))
+
+    @property
+    def samples(self) -> int:
+        done = C.c_uint64()
+        self._check(self._be.lib.rt_progressive_samples(self._h, C.byref(done)))
+        return int(done.value)
+
+    def rgb8(self):
+        """format_color(samples) of every pixel, computed on the device: ((H, W, 3) uint8, pixels changed since the previous resolve)."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        changed = C.c_uint64()
+        self._check(self._be.lib.rt_progressive_resolve_rgb8(self._h, out.ctypes.data, C.byref(changed)))
+        return out, int(changed.value)
+
+    def rgb8_device(self, stream: int = 0) -> int:
+        """Enqueue the resolve on a HIP stream; returns the DEVICE address of the W*H*3 bytes (valid until the next-but-one resolve)."""
+        ptr = C.c_void_p()
+        self._check(self._be.lib.rt_progressive_resolve_rgb8_device(self._h, C.byref(ptr), C.c_void_p(stream)))
+        return int(ptr.value or 0)
+
+    def rgb8_copy(self):
+        """Wait for the most recent resolve and fetch it with its changed-pixel count, without resolving again."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        changed = C.c_uint64()
+        self._check(self._be.lib.rt_progressive_copy_rgb8(self._h, out.ctypes.data, C.byref(changed)))
+        return out, int(changed.value)
+
+    def sum(self) -> np.ndarray:
+        """The accumulated per-pixel sums, (H, W, 3) f64 as `render` returns them; with `samples`, a checkpoint."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.float64)
+        self._check(self._be.lib.rt_progressive_read_sum(self._h, out.ctypes.data))
+        return out
+
+    def load(self, rgb_sum: np.ndarray, samples: int) -> None:
+        """Resume from a checkpoint: the frame becomes `rgb_sum` holding `samples` samples per pixel."""
+        a = np.ascontiguousarray(rgb_sum, dtype=np.float64)
+        if a.shape != (self.H, self.W, 3):
+            raise ValueError(f"checkpoint of shape {a.shape} for a frame of {(self.H, self.W, 3)}")
+        self._check(self._be.lib.rt_progressive_load_sum(self._h, a.ctypes.data, samples))
+
+    def reset(self) -> None:
+        self._check(self._be.lib.rt_progressive_reset(self._h))
+
+    def close(self) -> None:
+        if self._h:
+            self._be.lib.rt_progressive_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+# Samples per pass `render_progressive` uses by default: every pass is one persistent launch that fills and drains the chip (~0.5 ms) and
+# ends with a tail, so small passes cost throughput; DESIGN.md ("Progressive frames") has the measured cost by pass size.
+DEFAULT_PASS_SPP = 64
+
+
+def render_progressive(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, spp: int, max_depth: int, passes=None,
+                       seed: int = 0x5EED, flags: int = RT_F64):
+    """Generator: renders `spp` samples per pixel in passes and yields (samples_done, rgb8, changed_px) after each; the last item is the
+    full frame — the image `format_image(render(..., spp), spp)` gives.  passes: None (passes of DEFAULT_PASS_SPP), an int (that many
+    passes of equal size, the remainder in the first ones), or a sequence of pass sizes that sums to spp."""
+    if passes is None:
+        sizes = [DEFAULT_PASS_SPP] * (spp // DEFAULT_PASS_SPP) + ([spp % DEFAULT_PASS_SPP] if spp % DEFAULT_PASS_SPP else [])
+    elif isinstance(passes, int):
+        if not 1 <= passes <= spp:
+            raise ValueError("passes must be between 1 and spp")
+        sizes = [spp // passes + (1 if k < spp % passes else 0) for k in range(passes)]
+    else:
+        sizes = [int(n) for n in passes]
+        if sum(sizes) != spp or min(sizes, default=0) < 1:
+            raise ValueError("pass sizes must be >= 1 and sum to spp")
+    with Progressive(b, cam, background, W, H, max_depth, seed, flags) as frame:
+        for n in sizes:
+            frame.add(n)
+            image, changed = frame.rgb8()
+            yield frame.samples, image, changed
+
+
 def render_multi(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, spp: int, max_depth: int, device_mask: int = 0,
                  seed: int = 0x5EED, flags: int = RT_F64, tile_px: int = 0):
     """The whole frame on the GPUs of this node selected by `device_mask` (bit d = HIP device d; 0 = all visible) from ONE call:

@@ -1,0 +1,131 @@
+"""Progressive frames (rt_progressive_*, rt_render_device_pass) without a GPU: the identity the feature rests on, and argument handling.
+
+A pass that starts at sample `base` is handed to the unchanged path-tracing kernels as an ordinary frame with the seed
+`seed + 2*base*G (mod 2^64)`: the kernels key a path's stream by z = seed + 2*((pixel << 32) | sample)*G (csrc/rt_rng.h rng_for_path), so
+for sample + base < 2^32 the two keys are the same number.  The first test pins that through the library's own rt_rng_path; a re-keying of
+rt_rng.h that broke it would silently make passes render other samples than a one-shot frame."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from raytracinginrust_amd import render as R, scenes
+
+G = 0x9E3779B97F4A7C15
+M64 = (1 << 64) - 1
+
+
+def _state(lib, seed, pixel, sample):
+    out = (C.c_uint32 * 4)()
+    lib.rt_rng_path(C.c_uint64(seed), C.c_uint32(pixel), C.c_uint32(sample), out)
+    return tuple(out)
+
+
+def test_seed_fold_identity(pbe):
+    lib = pbe.lib
+    lib.rt_rng_path.restype = None
+    lib.rt_rng_path.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
+    rng = np.random.default_rng(20240607)
+    cases = []
+    for _ in range(2000):
+        seed = int(rng.integers(0, 1 << 64, dtype=np.uint64))
+        pixel = int(rng.integers(0, 1 << 31))                      # frames hold at most 2^31 - 1 pixels
+        s = int(rng.integers(0, 1 << 32))
+        for base in (1, 1 << 31, (1 << 32) - 1 - s, int(rng.integers(0, (1 << 32) - s))):
+            if s + base < (1 << 32):
+                cases.append((seed, pixel, s, base))
+    cases += [(0, 0, 0, (1 << 32) - 1), (M64, (1 << 31) - 2, 0, 1), (0x5EED, 123456, (1 << 32) - 2, 1), (0x5EED, 7, 0, 1 << 31)]
+    assert len(cases) > 6000
+    for seed, pixel, s, base in cases:
+        folded = (seed + 2 * base * G) & M64
+        assert _state(lib, seed, pixel, s + base) == _state(lib, folded, pixel, s), (seed, pixel, s, base)
+    # the identity ends where the sample field would carry into the pixel field: that is why done + n <= 2^32 - 1 is enforced
+    assert _state(lib, 1, 6, 0) == _state(lib, (1 + 2 * (1 << 32) * G) & M64, 5, 0)        # a carry IS the next pixel's stream
+
+
+def _has_gpu():
+    """The no-device messages can only be seen on a machine without one (the GPU suite covers the other side)."""
+    return R.device_count() > 0
+
+
+def test_create_without_a_device_fails_like_rt_render(pbe):
+    if _has_gpu():
+        return
+    b, cam, bg = scenes.cornell_box(pbe)
+    with pytest.raises(R.RenderError, match="no HIP device") as one_shot:
+        R.render(b, cam, bg, 8, 8, 1, 4)
+    with pytest.raises(R.RenderError, match="no HIP device") as prog:
+        R.Progressive(b, cam, bg, 8, 8, 4)
+    assert str(prog.value) == str(one_shot.value)
+    with pytest.raises(R.RenderError, match="no HIP device"):
+        next(R.render_progressive(b, cam, bg, 8, 8, 4, 4))
+
+
+def test_create_checks_its_arguments_first(pbe):
+    lib = pbe.lib
+    b, cam, bg = scenes.cornell_box(pbe)
+    bgc = (C.c_double * 3)(*bg)
+    assert not lib.rt_progressive_create(None, C.byref(cam), bgc, 8, 8, 4, 1, 0)
+    assert "null argument" in lib.rt_last_error().decode()
+    assert not lib.rt_progressive_create(b.h, None, bgc, 8, 8, 4, 1, 0)
+    assert "null argument" in lib.rt_last_error().decode()
+    assert not lib.rt_progressive_create(b.h, C.byref(cam), bgc, 1, 8, 4, 1, 0)
+    assert "W and H must be >= 2" in lib.rt_last_error().decode()
+    assert not lib.rt_progressive_create(b.h, C.byref(cam), bgc, 65536, 65536, 4, 1, 0)
+    assert "frame too large" in lib.rt_last_error().decode()
+
+
+def test_null_handles_and_bad_counts_are_errors_not_crashes(pbe):
+    lib = pbe.lib
+    buf = np.zeros(12, np.float64)
+    img = np.zeros(12, np.uint8)
+    n64 = C.c_uint64(77)
+    ptr = C.c_void_p()
+
+    def err():
+        return lib.rt_last_error().decode()
+
+    assert lib.rt_progressive_add(None, 4, None) != 0 and "null argument" in err()
+    assert lib.rt_progressive_add(None, 0, None) != 0 and "n_samples must be >= 1" in err()
+    assert lib.rt_progressive_add_async(None, 0, None) != 0 and "n_samples must be >= 1" in err()
+    assert lib.rt_progressive_add_async(None, 4, None) != 0 and "null argument" in err()
+    assert lib.rt_progressive_add(None, 0xFFFFFFFF, None) != 0 and err()
+    assert lib.rt_progressive_samples(None, C.byref(n64)) != 0 and "null argument" in err()
+    assert n64.value == 77
+    assert lib.rt_progressive_resolve_rgb8(None, img.ctypes.data, C.byref(n64)) != 0 and "null argument" in err()
+    assert lib.rt_progressive_resolve_rgb8_device(None, C.byref(ptr), None) != 0 and "null argument" in err()
+    assert lib.rt_progressive_copy_rgb8(None, img.ctypes.data, None) != 0 and "null argument" in err()
+    assert lib.rt_progressive_read_sum(None, buf.ctypes.data) != 0 and "null argument" in err()
+    assert lib.rt_progressive_load_sum(None, buf.ctypes.data, 4) != 0 and "null argument" in err()
+    assert lib.rt_progressive_load_sum(None, None, 4) != 0 and "null argument" in err()
+    buf[3] = 1.0                                                   # samples_done = 0 with a non-zero frame
+    assert lib.rt_progressive_load_sum(None, buf.ctypes.data, 0) != 0 and err()
+    assert lib.rt_progressive_load_sum(None, buf.ctypes.data, 1 << 32) != 0 and "2^32 - 1" in err()
+    assert lib.rt_progressive_reset(None) != 0 and "null argument" in err()
+    lib.rt_progressive_destroy(None)                               # like rt_scene_destroy(NULL): nothing happens
+
+
+def test_device_pass_checks_the_sample_range_before_anything_else(pbe):
+    """rt_render_device_pass: first_sample + samples_per_pixel beyond the 32-bit sample field is refused with its own message — before the
+    device is looked for, so the check is the same on every machine."""
+    lib = pbe.lib
+    b, cam, bg = scenes.cornell_box(pbe)
+    bgc = (C.c_double * 3)(*bg)
+    rc = lib.rt_render_device_pass(b.h, C.byref(cam), bgc, 8, 8, 2, 4, 1, 0, 0xFFFFFFFE, 1, 64, 0, 1, None, 0, None)
+    assert rc != 0 and "2^32 - 1" in lib.rt_last_error().decode()
+    rc = lib.rt_render_device_pass(b.h, C.byref(cam), bgc, 8, 8, 0, 4, 1, 0, 0, 1, 64, 0, 1, None, 0, None)
+    assert rc != 0 and "samples_per_pixel must be >= 1" in lib.rt_last_error().decode()
+    if _has_gpu():
+        return
+    rc = lib.rt_render_device_pass(b.h, C.byref(cam), bgc, 8, 8, 1, 4, 1, 0, 0xFFFFFFFE, 1, 64, 0, 1, None, 0, None)      # exactly 2^32 - 1: in range
+    assert rc != 0 and "no HIP device" in lib.rt_last_error().decode()
+
+
+def test_render_progressive_checks_its_pass_list(pbe):
+    b, cam, bg = scenes.cornell_box(pbe)
+    with pytest.raises(ValueError):
+        next(R.render_progressive(b, cam, bg, 8, 8, 16, 4, passes=[8, 4]))
+    with pytest.raises(ValueError):
+        next(R.render_progressive(b, cam, bg, 8, 8, 16, 4, passes=0))
+    with pytest.raises(ValueError):
+        next(R.render_progressive(b, cam, bg, 8, 8, 16, 4, passes=[16, 0]))
