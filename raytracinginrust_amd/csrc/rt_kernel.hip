@@ -340,7 +340,14 @@ template <typename T> DEV bool tri_test(const DTri<T>& tr, const RayT<T>& ray, T
 // so of the faces that exist the list accepts the entry face if it exists and lies in range, else the exit face if it exists and lies in
 // range, else nothing — an absent face is classed "out of range", whatever its distance.  face_out is then the record's place in the run.
 // map == 0: a Cube, all six faces, face_out in cube.rs order (the code above, unchanged).
-// (SITE: which call site family an instantiation serves — 0 everything, 1 the mesh kernels' world list.  The compiler's interprocedural
+// SITE 2 (the list-scene kernels; the known-answer kernels): a clear lane with a face to test keeps ONLY the division.  That face's exact test
+// cannot fail, by the two points above: its bounds tests pass because the lane is `through` (s1 < e1 by more than mu: entry and exit pass
+// theirs), and its range test is the comparison en_in / ex_in already decided with a margin that covers the approximation — the face is
+// chosen as the entry one only if en_in, as the exit one only if en_out and ex_in.  So `o + t d` on three axes, six compares and the range
+// test after the division only ever confirmed what was known, and the hit record is rebuilt from t afterwards anyway (finalize_hit).
+// The known-answer kernels run this form: wherever it says (t, face) and the six exact tests say the same (t, face), that face's exact
+// test passed — so the form that still runs it (SITE 0, 1) returns the same thing, and both are covered by the same 600 000 cases.
+// (SITE: which call site family an instantiation serves — 0 everything else, 1 the mesh kernels' world list.  The compiler's interprocedural
 // constant propagation folds `map == 0` INTO these functions where every caller of the translation unit passes it; a caller with a real map
 // would undo that for all of them and shift the other kernels' register allocation: its own copy keeps the others' machine code as it was.)
 template <bool WAVE, int SITE = 0>
@@ -391,6 +398,11 @@ DEV bool cube_fast(float rect_m, double mnx, double mxx, double mny, double mxy,
         const bool hi_side = (den < 0.0) != use_exit;
         const double k = hi_side ? (on_x ? mxx : (on_y ? mxy : mxz)) : (on_x ? mnx : (on_y ? mny : mnz));
         const double t = (k - org) / den;                                 // rect.rs:50
+        if constexpr (SITE == 2) {                                        // the division only: this face's range and bounds tests pass (proof above)
+            t_out = t; any = true;
+            face_out = (on_x ? 4u : (on_y ? 2u : 0u)) + (hi_side ? 0u : 1u);                                          // (XY, XZ, YZ) x (max, min)
+            if (map != 0u) face_out = (map >> (3u * face_out)) & 7u;                                                  // a room: the record's place in its run
+        } else
         if (!(t < t_min || t > t_max)) {                                  // rect.rs:51-53
             const double px = ray.o.x + t * ray.d.x, py = ray.o.y + t * ray.d.y, pz = ray.o.z + t * ray.d.z;          // rect.rs:54-55, the two axes that are not the face's
             const bool out_x = px < mnx || px > mxx, out_y = py < mny || py > mxy, out_z = pz < mnz || pz > mxz;      // rect.rs:56-58
@@ -433,7 +445,7 @@ DEV bool range_hit(const KParams<T>& P, uint32_t kind, uint32_t first, uint32_t 
     bool any = false;
     T closest = t_max;
     if constexpr (CubeFast<T, FEATS>::on) {
-        if (kind == G_RECT && (is_cube || room != 0u) && cube_hit(P, first, count, room, ray, t_min, t_max, closest, prim_out, any)) { t_out = closest; return any; }
+        if (kind == G_RECT && (is_cube || room != 0u) && cube_hit<FEATS == 0u ? 2 : 0>(P, first, count, room, ray, t_min, t_max, closest, prim_out, any)) { t_out = closest; return any; }
     }
     if (kind == G_RECT) {
         // software-pipelined record fetch: record i+1 is requested before record i is tested (the table carries one
@@ -2469,7 +2481,7 @@ __global__ void cube_kat_kernel(uint32_t n, float rect_m, const double* boxes, c
     double closest = t_max, t_ref = __builtin_nan(""); int face_ref = -1;
     for (int k = 0; k < 6; k++) { double t; if (rect_test(f[k], ray, t_min, closest, t)) { closest = t; t_ref = t; face_ref = k; } }
     double t_fast = __builtin_nan(""); uint32_t face = 0xFFFFFFFFu; bool hit = false, clear = false;
-    { double t; uint32_t fc = 0u; (void)cube_fast<false>(rect_m, b.mnx, b.mxx, b.mny, b.mxy, b.mnz, b.mxz, ray, t_min, t_max, t, fc, hit, clear); if (hit) { t_fast = t; face = fc; } }
+    { double t; uint32_t fc = 0u; (void)cube_fast<false, 2>(rect_m, b.mnx, b.mxx, b.mny, b.mxy, b.mnz, b.mxz, ray, t_min, t_max, t, fc, hit, clear); if (hit) { t_fast = t; face = fc; } }
     out[i * 4] = t_ref; out[i * 4 + 1] = (double)face_ref; out[i * 4 + 2] = t_fast; out[i * 4 + 3] = (double)((clear ? 8 : 0) + (int)(face + 1u));
 }
 }
@@ -2494,7 +2506,7 @@ __global__ void room_kat_kernel(uint32_t n, float rect_m, const double* boxes, c
     }
     map |= 1u << 18;        // (never 0: a Cube with all six faces is a valid room too — the word the flattener makes has its flag bits above the map as well)
     double t_fast = __builtin_nan(""); uint32_t face = 0xFFFFFFFFu; bool hit = false, clear = false;
-    { double t; uint32_t fc = 0u; (void)cube_fast<false>(rect_m, b.mnx, b.mxx, b.mny, b.mxy, b.mnz, b.mxz, ray, t_min, t_max, t, fc, hit, clear, map); if (hit) { t_fast = t; face = fc; } }
+    { double t; uint32_t fc = 0u; (void)cube_fast<false, 2>(rect_m, b.mnx, b.mxx, b.mny, b.mxy, b.mnz, b.mxz, ray, t_min, t_max, t, fc, hit, clear, map); if (hit) { t_fast = t; face = fc; } }
     out[i * 4] = t_ref; out[i * 4 + 1] = (double)face_ref; out[i * 4 + 2] = t_fast; out[i * 4 + 3] = (double)((clear ? 8 : 0) + (int)(face + 1u));
 }
 }
