@@ -13,6 +13,7 @@
 #include "../../include/rt_amd.h"
 #include "rt_scene.h"
 #include "rt_launch.h"
+#include "rt_device.h"
 #include "rt_resolve.h"
 
 using namespace rt;
@@ -48,6 +49,8 @@ static int scene_err(rt_scene* sc, const std::string& m) { sc->s.error = m; g_er
 #define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_err = std::string(#call) + ": " + hipGetErrorString(e_); return -1; } } while (0)
 
 static void free_dev(void*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
+// a buffer kept with the scene (d_trace, d_calib), freed on the device it lives on once nothing there can still be using it
+static void free_on_device(void*& p, int device) { if (p) { DeviceGuard guard(device); (void)hipDeviceSynchronize(); free_dev(p); } }
 template <typename T> static void free_device_scene(DeviceScene<T>& d) {
     free_dev(d.objects); free_dev(d.ops); free_dev(d.rects); free_dev(d.spheres); free_dev(d.mspheres); free_dev(d.tris);
     free_dev(d.bvh); free_dev(d.materials); free_dev(d.textures); free_dev(d.media); free_dev(d.lights); free_dev(d.perlins); free_dev(d.image); free_dev(d.pbr); free_dev(d.bvh_f);
@@ -77,13 +80,12 @@ rt_scene* rt_scene_create(void) { return new rt_scene(); }
 
 void rt_scene_destroy(rt_scene* sc) {
     if (!sc) return;
-    int cur = 0; (void)hipGetDevice(&cur);
     for (void* f : sc->s.frames) ((Progressive*)f)->sc = nullptr;      // progressive frames outlive their scene (they own their buffers)
     rt::multi_release(sc->s);
-    if (sc->s.d_trace) { (void)hipSetDevice(sc->s.trace_device); (void)hipFree(sc->s.d_trace); sc->s.d_trace = nullptr; (void)hipSetDevice(cur); }
-    if (sc->s.d_calib) { (void)hipSetDevice(sc->s.calib_device); (void)hipDeviceSynchronize(); (void)hipFree(sc->s.d_calib); sc->s.d_calib = nullptr; (void)hipSetDevice(cur); }
+    free_on_device(sc->s.d_trace, sc->s.trace_device);
+    free_on_device(sc->s.d_calib, sc->s.calib_device);
     for (Scene::DeviceCtx* c : sc->s.ctxs) {
-        (void)hipSetDevice(c->device);
+        DeviceGuard guard(c->device);
         free_device_scene(c->dev64);
         free_device_scene(c->dev32);
         for (Scene::LaunchSlot& l : c->slots) {
@@ -96,19 +98,13 @@ void rt_scene_destroy(rt_scene* sc) {
         if (c->stream) (void)hipStreamDestroy((hipStream_t)c->stream);
         delete c;
     }
-    if (!sc->s.ctxs.empty()) (void)hipSetDevice(cur);
     delete sc;
 }
 const char* rt_scene_error(rt_scene* sc) { return sc->s.error.c_str(); }
 
 static void touch(rt_scene* sc) {
     sc->s.invalidate();
-    if (sc->s.ctxs.empty()) return;
-    int cur = 0; (void)hipGetDevice(&cur);
-    for (Scene::DeviceCtx* c : sc->s.ctxs) {
-        (void)hipSetDevice(c->device); free_device_scene(c->dev64); free_device_scene(c->dev32);
-    }
-    (void)hipSetDevice(cur);
+    for (Scene::DeviceCtx* c : sc->s.ctxs) { DeviceGuard guard(c->device); free_device_scene(c->dev64); free_device_scene(c->dev32); }
 }
 int rt_scene_set_traversal_schedule(rt_scene* sc, uint32_t start_at, uint32_t stop_below, uint32_t leaf_share64) {
     if (!sc) return set_err("null argument");
@@ -347,7 +343,7 @@ uint8_t* rt_decode_jpeg_rgb8(const uint8_t* data, size_t size, uint32_t* width, 
 void rt_free(void* p) { std::free(p); }
 
 int rt_scene_flatten(rt_scene* sc, uint32_t counts[12]) {
-    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return -1; }
+    if (!flatten_for_render(sc->s)) return -1;
     const HostFlat& f = sc->s.flat;
     if (counts) {
         uint32_t c[12] = {(uint32_t)f.objects.size(), (uint32_t)f.ops.size(), (uint32_t)f.rects.size(), (uint32_t)f.spheres.size(),
@@ -362,7 +358,7 @@ int rt_scene_flatten(rt_scene* sc, uint32_t counts[12]) {
 // device copy; 1 if the tree was rebuilt, 0 if the scene is not of that kind, -1 on error.  rt_debug_filter_nodes then shows the result.
 int rt_debug_tune_filter(rt_scene* sc, const rt_camera* cam) {
     if (!sc || !cam) return set_err("null argument");
-    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return -1; }
+    if (!flatten_for_render(sc->s)) return -1;
     rt_camera_args ca; std::memcpy(&ca, cam, sizeof(ca));
     DCamera<double> dcam; camera_new(ca, dcam);
     return tune_filter_tree(sc->s, dcam) ? 1 : 0;
@@ -373,7 +369,7 @@ int rt_debug_tune_filter(rt_scene* sc, const rt_camera* cam) {
 // objects (all of them), *n_top_out the number of top-level ones; -1 on error.
 int rt_debug_objects(rt_scene* sc, uint32_t* out, uint32_t max_objects, uint32_t* n_top_out) {
     if (!sc) return set_err("null argument");
-    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return -1; }
+    if (!flatten_for_render(sc->s)) return -1;
     const HostFlat& f = sc->s.flat;
     if (n_top_out) *n_top_out = f.n_top;
     for (size_t i = 0; i < f.objects.size() && i < max_objects && out; i++) {
@@ -388,7 +384,7 @@ int rt_debug_objects(rt_scene* sc, uint32_t* out, uint32_t max_objects, uint32_t
 // the root node of every BVH object in list order (at most max_roots).  Returns the number of nodes, or -1.
 int rt_debug_bvh_links(rt_scene* sc, uint32_t* out, uint32_t max_nodes, uint32_t* roots_out, uint32_t max_roots, uint32_t* n_roots_out) {
     if (!sc) return -1;
-    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return -1; }
+    if (!flatten_for_render(sc->s)) return -1;
     const HostFlat& f = sc->s.flat;
     if (out) for (size_t i = 0; i < f.bvh.size() && i < max_nodes; i++) { out[4 * i] = f.bvh[i].a; out[4 * i + 1] = f.bvh[i].b; out[4 * i + 2] = f.bvh[i].c; out[4 * i + 3] = f.bvh[i].skip; }
     uint32_t n_roots = 0;
@@ -403,7 +399,7 @@ int rt_debug_bvh_links(rt_scene* sc, uint32_t* out, uint32_t max_nodes, uint32_t
 // {min[3], max[3]}.  *filter_m_out = KParams::filter_m.  Returns the number of nodes, or -1.
 int rt_debug_filter_nodes(rt_scene* sc, float* boxes6_out, uint32_t* links2_out, double* f64_boxes_out, uint32_t max_nodes, float* filter_m_out) {
     if (!sc) return -1;
-    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return -1; }
+    if (!flatten_for_render(sc->s)) return -1;
     const HostFlat& f = sc->s.flat;
     for (size_t i = 0; i < f.bvh_f.size() && i < max_nodes; i++) {
         if (boxes6_out) for (int k = 0; k < 6; k++) boxes6_out[6 * i + k] = f.bvh_f[i].b[k];
@@ -498,12 +494,6 @@ static int current_ctx(Scene& s, Scene::DeviceCtx** out) {
     return 0;
 }
 
-// Events and counter blocks belong to one device: waits, elapsed times and copies run with that device current.
-struct DeviceGuard {
-    int prev = -1; bool switched = false;
-    explicit DeviceGuard(int device) { if (hipGetDevice(&prev) == hipSuccess && prev != device) switched = hipSetDevice(device) == hipSuccess; }
-    ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-};
 // A finished launch's kernel time joins the running total exactly once (rt_kernel_time_total).  Current device: the slot's.
 static int settle_slot(Scene& s, Scene::LaunchSlot& l) {
     if (!l.recorded || l.timed) return 0;
@@ -543,10 +533,7 @@ static int acquire_slot(Scene& s, Scene::DeviceCtx& c, hipStream_t stream, Scene
     if (!pick) { pick = &c.slots[0]; for (Scene::LaunchSlot& l : c.slots) if (l.seq < pick->seq) pick = &l; }
     if (settle_slot(s, *pick)) return -1;             // also waits for a launch that may still be running in this slot
     if (pick->group == s.frame_group && harvest_slot(s, *pick)) return -1;      // an earlier share of the frame being enqueued (virtual ranks): keep its counters
-    if (!pick->d_queue) HIP_OK(hipMalloc(&pick->d_queue, 64));
-    if (!pick->d_stats) HIP_OK(hipMalloc(&pick->d_stats, RT_STATS_BYTES));
-    if (!pick->ev_start) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); pick->ev_start = e; }
-    if (!pick->ev_stop) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); pick->ev_stop = e; }
+    HIP_OK(ensure_slot_resources(*pick));
     pick->stream = (void*)stream;
     *out = pick;
     return 0;
@@ -633,6 +620,21 @@ template <typename T> uint32_t cached_nodes(const LaunchShape& g, const HostFlat
 // tests/test_fuzz_gpu.py uses to show that its hostile rays do find the order-dependent NaN hits that path exists for.
 static bool room_nan_path() { return std::getenv("RT_ROOM_NO_NAN_PATH") == nullptr; }
 
+// The scene's tables as the kernels receive them: device pointers and counts (every launch binds all of them; a kernel reads what it needs).
+template <typename T> void bind_tables(KParams<T>& P, const DeviceScene<T>& d, const HostFlat& f) {
+    P.objects = (const DObject*)d.objects; P.n_objects = f.n_top; P.n_objects_alt = room_nan_path() ? f.n_alt : 0u;
+    P.ops = (const DOp<T>*)d.ops; P.rects = (const DRect<T>*)d.rects; P.spheres = (const DSphere<T>*)d.spheres;
+    P.mspheres = (const DMSphere<T>*)d.mspheres; P.tris = (const DTri<T>*)d.tris; P.bvh = (const DBvhNode<T>*)d.bvh;
+    P.n_bvh = (uint32_t)f.bvh.size();
+    P.bvh_f = (const DFNode*)d.bvh_f; P.filter_m = f.filter_m; P.rect_m = f.rect_m;
+    P.materials = (const DMaterial<T>*)d.materials; P.textures = (const DTexture<T>*)d.textures; P.media = (const DMedium<T>*)d.media;
+    P.lights = (const DLight*)d.lights; P.n_lights = f.n_lights;
+    P.perlins = (const DPerlin<T>*)d.perlins; P.pbr = (const DPbr<T>*)d.pbr; P.image_bytes = (const uint8_t*)d.image;
+}
+
+// f<float> or f<double>, as the caller's flags ask
+#define BY_PRECISION(flags, f, ...) (((flags) & RT_F32) ? f<float>(__VA_ARGS__) : f<double>(__VA_ARGS__))
+
 template <typename T>
 int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
                 uint64_t seed, uint32_t flags, uint32_t tile_px, uint32_t rank, uint32_t world, void* d_out, size_t d_out_bytes,
@@ -645,14 +647,7 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     const HostFlat& f = s.flat;
     KParams<T> P;
     std::memset((void*)&P, 0, sizeof(P));
-    P.objects = (const DObject*)d.objects; P.n_objects = f.n_top; P.n_objects_alt = room_nan_path() ? f.n_alt : 0u;
-    P.ops = (const DOp<T>*)d.ops; P.rects = (const DRect<T>*)d.rects; P.spheres = (const DSphere<T>*)d.spheres;
-    P.mspheres = (const DMSphere<T>*)d.mspheres; P.tris = (const DTri<T>*)d.tris; P.bvh = (const DBvhNode<T>*)d.bvh;
-    P.n_bvh = (uint32_t)f.bvh.size();
-    P.bvh_f = (const DFNode*)d.bvh_f; P.filter_m = f.filter_m; P.rect_m = f.rect_m;
-    P.materials = (const DMaterial<T>*)d.materials; P.textures = (const DTexture<T>*)d.textures; P.media = (const DMedium<T>*)d.media;
-    P.lights = (const DLight*)d.lights; P.n_lights = f.n_lights;
-    P.perlins = (const DPerlin<T>*)d.perlins; P.pbr = (const DPbr<T>*)d.pbr; P.image_bytes = (const uint8_t*)d.image;
+    bind_tables(P, d, f);
     {   // the f32 tables are rounded copies: the tame bound is checked at the precision that is uploaded
         const double big = sizeof(T) == 8 ? 1e300 : 1e30;
         bool tame = f.bvh_tame;
@@ -742,7 +737,7 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
         if (world > 1) return set_err("rt_debug_trace_path: tracing a path is for unsharded renders (world = 1)");
         const size_t bytes = ((size_t)max_depth + 1u) * 16u * sizeof(double);
         if (!s.d_trace || s.trace_device != c.device || s.trace_levels != max_depth + 1u) {      // one buffer per (device, depth): earlier launches keep a valid pointer
-            if (s.d_trace) { DeviceGuard guard(s.trace_device); (void)hipDeviceSynchronize(); (void)hipFree(s.d_trace); s.d_trace = nullptr; }
+            free_on_device(s.d_trace, s.trace_device);
             HIP_OK(hipMalloc(&s.d_trace, bytes));
             s.trace_device = c.device; s.trace_levels = max_depth + 1u;
         }
@@ -772,6 +767,16 @@ int check_frame_args(rt_scene* sc, const rt_camera* cam, const double* bg, uint3
     if (spp == 0) return set_err("samples_per_pixel must be >= 1");
     if ((uint64_t)W * H > 0x7FFFFFFFull) return set_err("frame too large: W*H must be <= 2^31 - 1 (per-path RNG keys, csrc/rt_rng.h)");
     return 0;
+}
+
+// What every entry point that takes a frame does first, in this order (tests/test_entry_prologue.py): the frame's arguments, then — after
+// the checks of its own that rt_render_device* has in between — a device and the flattened scene.
+int need_device_and_flat(Scene& s) {
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    return flatten_for_render(s) ? 0 : -1;
+}
+int frame_prologue(rt_scene* sc, const rt_camera* cam, const double* bg, uint32_t W, uint32_t H, uint32_t spp) {
+    return check_frame_args(sc, cam, bg, W, H, spp) ? -1 : need_device_and_flat(sc->s);
 }
 
 // Worlds that are ONE bare BVH: tune the filter tree's contraction for this view (rt_flatten.cpp tune_filter_tree: host arithmetic, < 1 ms)
@@ -818,7 +823,7 @@ static int calibrate_loop_shape(Scene& s, const rt_camera* cam, const double bg[
     int dev = 0; HIP_OK(hipGetDevice(&dev));
     if (settle_all_launches(s)) return -1;
     if (!s.d_calib || s.calib_device != dev || s.calib_bytes < bytes) {
-        if (s.d_calib) { DeviceGuard guard(s.calib_device); (void)hipDeviceSynchronize(); (void)hipFree(s.d_calib); s.d_calib = nullptr; }
+        free_on_device(s.d_calib, s.calib_device);
         HIP_OK(hipMalloc(&s.d_calib, bytes));
         s.calib_device = dev; s.calib_bytes = bytes;
     }
@@ -830,8 +835,7 @@ static int calibrate_loop_shape(Scene& s, const rt_camera* cam, const double bg[
     for (int round = 0; round < 2 && rc == 0; round++)
         for (int shape = 0; shape < 2 && rc == 0; shape++) {
             const uint32_t fl = flags | (shape ? RT_PERSISTENT_BVH : RT_LOCKSTEP_BVH);
-            rc = (flags & RT_F32) ? render_impl<float>(s, cam, bg, Wc, Hc, sc_spp, max_depth, seed, fl, Wc * Hc, 0, 1, s.d_calib, bytes, nullptr, stream)
-                                  : render_impl<double>(s, cam, bg, Wc, Hc, sc_spp, max_depth, seed, fl, Wc * Hc, 0, 1, s.d_calib, bytes, nullptr, stream);
+            rc = BY_PRECISION(flags, render_impl, s, cam, bg, Wc, Hc, sc_spp, max_depth, seed, fl, Wc * Hc, 0, 1, s.d_calib, bytes, nullptr, stream);
             float ms = 0.f;
             if (rc == 0 && device_kernel_ms(s, dev, &ms) == 0) best[shape] = std::min(best[shape], ms); else rc = -1;
         }
@@ -852,8 +856,7 @@ int render_any(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t 
     if (check_frame_args(sc, cam, bg, W, H, spp)) return -1;
     if (tile_px == 0 || world == 0 || rank >= world) return set_err("bad tile decomposition");
     if ((uint64_t)first_sample + spp > 0xFFFFFFFFull) return set_err("first_sample + samples_per_pixel must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return -1; }
+    if (need_device_and_flat(sc->s)) return -1;
     // A pass decides by the VIEW as accumulated so far — first_sample + spp samples per pixel — not by its own sample count: a frame fed in
     // 16-sample passes calibrates at the pass with which it reaches the size at which a one-shot frame would have.
     const uint32_t view_spp = first_sample + spp;
@@ -864,8 +867,7 @@ int render_any(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t 
     // folded into the seed the launch receives, and no kernel knows about passes (tests/test_progressive_host.py pins the identity).
     const uint64_t G = 0x9E3779B97F4A7C15ULL;
     const uint64_t pass_seed = seed + 2ULL * (uint64_t)first_sample * G;
-    if (flags & RT_F32) return render_impl<float>(sc->s, cam, bg, W, H, spp, max_depth, pass_seed, flags, tile_px, rank, world, d_out, d_out_bytes, d_samples, stream, accumulate);
-    return render_impl<double>(sc->s, cam, bg, W, H, spp, max_depth, pass_seed, flags, tile_px, rank, world, d_out, d_out_bytes, d_samples, stream, accumulate);
+    return BY_PRECISION(flags, render_impl, sc->s, cam, bg, W, H, spp, max_depth, pass_seed, flags, tile_px, rank, world, d_out, d_out_bytes, d_samples, stream, accumulate);
 }
 
 } // namespace
@@ -889,11 +891,7 @@ int rt_render_device_pass(rt_scene* sc, const rt_camera* cam, const double bg[3]
 // device; a no-op for every other scene, for a view already measured and after rt_scene_set_loop_shape.
 int rt_scene_calibrate(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
                        uint64_t seed, uint32_t flags) {
-    if (check_frame_args(sc, cam, bg, W, H, spp)) return -1;
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return -1; }
-    if (tune_for_view(sc->s, cam, W, H)) return -1;
-    return calibrate_loop_shape(sc->s, cam, bg, W, H, spp, max_depth, seed, flags, nullptr, false);
+    return rt::calibrate_view(sc, cam, bg, W, H, spp, max_depth, seed, flags, false);
 }
 int rt_scene_set_loop_shape(rt_scene* sc, int shape) {
     if (!sc) return set_err("null argument");
@@ -914,8 +912,7 @@ int rt_last_loop_info(rt_scene* sc, int32_t out4[4], float calibration_ms2[2]) {
 // create events / scratch words, and make the runtime load the kernel's code object (occupancy query).  No kernel is launched.
 int rt_scene_prepare(rt_scene* sc, uint32_t flags) {
     if (!sc) return set_err("null argument");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return -1; }
+    if (need_device_and_flat(sc->s)) return -1;
     Scene::DeviceCtx* cp = nullptr;
     if (current_ctx(sc->s, &cp)) return -1;
     return rt::prepare_device(sc->s, *cp, flags);
@@ -923,50 +920,43 @@ int rt_scene_prepare(rt_scene* sc, uint32_t flags) {
 
 } // extern "C"
 namespace rt {
-// what the synchronous multi-GPU entry point (rt_render_multi) does before it enqueues its frame: the implicit calibration of a first large frame
-int calibrate_if_worth_it(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
-                          uint64_t seed, uint32_t flags) {
-    if (check_frame_args(sc, cam, bg, W, H, spp)) return -1;
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return -1; }
-    if (tune_for_view(sc->s, cam, W, H)) return -1;
-    return calibrate_loop_shape(sc->s, cam, bg, W, H, spp, max_depth, seed, flags, nullptr, true);
+// rt_scene_calibrate; with only_if_worth_it what the synchronous multi-GPU entry point (rt_render_multi) does before it enqueues its
+// frame: the implicit calibration of a first large frame
+int calibrate_view(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
+                   uint64_t seed, uint32_t flags, bool only_if_worth_it) {
+    if (frame_prologue(sc, cam, bg, W, H, spp) || tune_for_view(sc->s, cam, W, H)) return -1;
+    return calibrate_loop_shape(sc->s, cam, bg, W, H, spp, max_depth, seed, flags, nullptr, only_if_worth_it);
 }
-// rt_scene_prepare's work for one device context; the calling thread's current HIP device must be c.device and the scene must be
-// flattened.  Touches only `c` and reads s.flat, so rt_render_multi may run it for several devices from several threads at once.
-int prepare_device(Scene& s, Scene::DeviceCtx& c, uint32_t flags) {
-    if (flags & RT_F32) { if (ensure_uploaded<float>(s, c.dev32)) return -1; }
-    else { if (ensure_uploaded<double>(s, c.dev64)) return -1; }
-    for (Scene::LaunchSlot& l : c.slots) {
-        if (!l.d_queue) HIP_OK(hipMalloc(&l.d_queue, 64));
-        if (!l.d_stats) HIP_OK(hipMalloc(&l.d_stats, RT_STATS_BYTES));
-        if (!l.ev_start) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); l.ev_start = e; }
-        if (!l.ev_stop) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); l.ev_stop = e; }
-    }
+template <typename T> static int prepare_device_as(Scene& s, Scene::DeviceCtx& c, uint32_t flags) {
+    if (ensure_uploaded<T>(s, dev_of<T>(c))) return -1;
+    for (Scene::LaunchSlot& l : c.slots) HIP_OK(ensure_slot_resources(l));
     const uint32_t eff = effective_flags(s.flat, flags, s.loop_how == 4 ? s.loop_choice : -1);
     const LaunchShape shape = pathtrace_shape(s.flat.feats, eff);
     hipDeviceProp_t prop; HIP_OK(hipGetDeviceProperties(&prop, c.device));
-    int bpc;
     const uint32_t sd = stack_depth_of(s.flat, eff);
-    if (flags & RT_F32) bpc = pathtrace_blocks_per_cu<float>(s.flat.feats, eff, pathtrace_lds_bytes(shape, sd, cached_nodes<float>(shape, s.flat, prop, sd, eff), lds_node_bytes<float>(eff)));
-    else bpc = pathtrace_blocks_per_cu<double>(s.flat.feats, eff, pathtrace_lds_bytes(shape, sd, cached_nodes<double>(shape, s.flat, prop, sd, eff), lds_node_bytes<double>(eff)));
-    if (bpc <= 0) return set_err("occupancy query failed for the path-tracing kernel");
+    const size_t shmem = pathtrace_lds_bytes(shape, sd, cached_nodes<T>(shape, s.flat, prop, sd, eff), lds_node_bytes<T>(eff));
+    if (pathtrace_blocks_per_cu<T>(s.flat.feats, eff, shmem) <= 0) return set_err("occupancy query failed for the path-tracing kernel");
     HIP_OK(hipDeviceSynchronize());
     return 0;
 }
+// rt_scene_prepare's work for one device context; the calling thread's current HIP device must be c.device and the scene must be
+// flattened.  Touches only `c` and reads s.flat, so rt_render_multi may run it for several devices from several threads at once.
+int prepare_device(Scene& s, Scene::DeviceCtx& c, uint32_t flags) { return BY_PRECISION(flags, prepare_device_as, s, c, flags); }
 int settle_all_launches(Scene& s) {
     for (Scene::DeviceCtx* c : s.ctxs) { DeviceGuard guard(c->device); for (Scene::LaunchSlot& l : c->slots) if (settle_slot(s, l)) return -1; }
     return 0;
 }
 bool flatten_for_render(Scene& s) { if (flatten_scene(s)) return true; set_err(s.error); return false; }
+// duration of the most recent launch on c's device (waits for it)
+static int last_launch_ms(Scene::DeviceCtx& c, float* ms) {
+    Scene::LaunchSlot& l = c.slots[c.last_slot];
+    DeviceGuard guard(c.device);
+    HIP_OK(hipEventSynchronize((hipEvent_t)l.ev_stop));
+    HIP_OK(hipEventElapsedTime(ms, (hipEvent_t)l.ev_start, (hipEvent_t)l.ev_stop));
+    return 0;
+}
 int device_kernel_ms(Scene& s, int device, float* ms) {
-    for (Scene::DeviceCtx* c : s.ctxs) if (c->device == device && c->last_slot >= 0) {
-        Scene::LaunchSlot& l = c->slots[c->last_slot];
-        DeviceGuard guard(c->device);
-        HIP_OK(hipEventSynchronize((hipEvent_t)l.ev_stop));
-        HIP_OK(hipEventElapsedTime(ms, (hipEvent_t)l.ev_start, (hipEvent_t)l.ev_stop));
-        return 0;
-    }
+    for (Scene::DeviceCtx* c : s.ctxs) if (c->device == device && c->last_slot >= 0) return last_launch_ms(*c, ms);
     return set_err("no kernel has been launched on that device");
 }
 }
@@ -975,11 +965,7 @@ extern "C" {
 int rt_last_kernel_ms(rt_scene* sc, float* ms_out) {
     Scene::DeviceCtx* c = sc ? sc->s.last_ctx() : nullptr;
     if (!sc || !ms_out || !c || c->last_slot < 0) return set_err("no kernel has been launched for this scene");
-    Scene::LaunchSlot& l = c->slots[c->last_slot];
-    DeviceGuard guard(c->device);
-    HIP_OK(hipEventSynchronize((hipEvent_t)l.ev_stop));
-    HIP_OK(hipEventElapsedTime(ms_out, (hipEvent_t)l.ev_start, (hipEvent_t)l.ev_stop));
-    return 0;
+    return rt::last_launch_ms(*c, ms_out);
 }
 
 // [0] non-finite samples, [1] wave bounce-loop iterations, [2] lane-iterations with a live path  (last finished launch)
@@ -1053,6 +1039,26 @@ int rt_debug_section_cycles(rt_scene* sc, unsigned long long out[8]) {
     return 0;
 }
 
+// A known-answer launch (rt_launch.h) on the calling thread's device: zeroed launch parameters with the scene's f64 tables bound in, two
+// host arrays of n records in (a_rec, b_rec bytes per record), one out.
+typedef hipError_t (*KatLaunch)(const KParams<double>&, uint32_t, const double*, const double*, double*, hipStream_t);
+static int run_kat(Scene& s, KatLaunch launch, uint32_t n, const double* a, size_t a_rec, const double* b, size_t b_rec, double* out, size_t out_rec) {
+    Scene::DeviceCtx* cp = nullptr;
+    if (current_ctx(s, &cp)) return -1;
+    DeviceScene<double>& d = dev_of<double>(*cp);
+    if (ensure_uploaded<double>(s, d)) return -1;
+    KParams<double> P;
+    std::memset((void*)&P, 0, sizeof(P));
+    bind_tables(P, d, s.flat);
+    DeviceBuffer d_a, d_b, d_out;
+    HIP_OK(d_a.alloc(n * a_rec)); HIP_OK(d_b.alloc(n * b_rec)); HIP_OK(d_out.alloc(n * out_rec));
+    HIP_OK(hipMemcpy(d_a.get(), a, n * a_rec, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_b.get(), b, n * b_rec, hipMemcpyHostToDevice));
+    HIP_OK(launch(P, n, (const double*)d_a.get(), (const double*)d_b.get(), (double*)d_out.get(), nullptr));
+    HIP_OK(hipMemcpy(out, d_out.get(), n * out_rec, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // Debugging aid (see include/rt_amd.h): choose the path whose hits the next renders record / fetch the record
 // Known-answer access to the closest-hit search of a LIST scene (no feature bit set: what the lean kernels serve): world.hit (main.rs:48)
 // and the hit record for n given rays, through the kernels' own world_hit / finalize_hit.  rays: n x (origin[3], direction[3]); t_min: n;
@@ -1061,25 +1067,9 @@ int rt_debug_list_hit(rt_scene* sc, uint32_t n, const double* rays, const double
     if (!sc || !rays || !t_min || !out) return set_err("null argument");
     if (n == 0) return 0;
     Scene& s = sc->s;
-    if (!flatten_scene(s)) { g_err = s.error; return -1; }
+    if (!flatten_for_render(s)) return -1;
     if (s.flat.feats != 0u) return set_err("rt_debug_list_hit serves list scenes only (no BVH, sphere, triangle, medium, texture, dielectric or PBR)");
-    Scene::DeviceCtx* cp = nullptr;
-    if (current_ctx(s, &cp)) return -1;
-    DeviceScene<double>& d = dev_of<double>(*cp);
-    if (ensure_uploaded<double>(s, d)) return -1;
-    const HostFlat& f = s.flat;
-    KParams<double> P;
-    std::memset((void*)&P, 0, sizeof(P));
-    P.objects = (const DObject*)d.objects; P.n_objects = f.n_top; P.n_objects_alt = room_nan_path() ? f.n_alt : 0u;
-    P.ops = (const DOp<double>*)d.ops; P.rects = (const DRect<double>*)d.rects; P.rect_m = f.rect_m;
-    P.materials = (const DMaterial<double>*)d.materials; P.textures = (const DTexture<double>*)d.textures;
-    double *dr = nullptr, *dt = nullptr, *dout = nullptr;
-    int rc = -1;
-    if (hipMalloc(&dr, n * 48ull) == hipSuccess && hipMalloc(&dt, n * 8ull) == hipSuccess && hipMalloc(&dout, n * 96ull) == hipSuccess &&
-        hipMemcpy(dr, rays, n * 48ull, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dt, t_min, n * 8ull, hipMemcpyHostToDevice) == hipSuccess &&
-        launch_list_hit_kat(P, n, dr, dt, dout, nullptr) == hipSuccess && hipMemcpy(out, dout, n * 96ull, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
-    (void)hipFree(dr); (void)hipFree(dt); (void)hipFree(dout);
-    return rc == 0 ? 0 : set_err("rt_debug_list_hit: a HIP call failed");
+    return run_kat(s, launch_list_hit_kat, n, rays, 48u, t_min, 8u, out, 96u);
 }
 // Known-answer access to HittableList::pdf_value of the scene's `lights` (hit.rs:90-92, nested lists included) on the device, through the
 // function the F_ALL | F_NESTED kernels run (rt_kernel.hip lights_pdf_tree).  origins, dirs: n x 3; out: n.  Host pointers.
@@ -1087,23 +1077,8 @@ int rt_debug_light_pdf(rt_scene* sc, uint32_t n, const double* origins, const do
     if (!sc || !origins || !dirs || !out) return set_err("null argument");
     if (n == 0) return 0;
     Scene& s = sc->s;
-    if (!flatten_scene(s)) { g_err = s.error; return -1; }
-    Scene::DeviceCtx* cp = nullptr;
-    if (current_ctx(s, &cp)) return -1;
-    DeviceScene<double>& d = dev_of<double>(*cp);
-    if (ensure_uploaded<double>(s, d)) return -1;
-    const HostFlat& f = s.flat;
-    KParams<double> P;
-    std::memset((void*)&P, 0, sizeof(P));
-    P.lights = (const DLight*)d.lights; P.n_lights = f.n_lights;
-    P.rects = (const DRect<double>*)d.rects; P.spheres = (const DSphere<double>*)d.spheres;
-    double *dor = nullptr, *ddi = nullptr, *dout = nullptr;
-    int rc = -1;
-    if (hipMalloc(&dor, n * 24ull) == hipSuccess && hipMalloc(&ddi, n * 24ull) == hipSuccess && hipMalloc(&dout, n * 8ull) == hipSuccess &&
-        hipMemcpy(dor, origins, n * 24ull, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(ddi, dirs, n * 24ull, hipMemcpyHostToDevice) == hipSuccess &&
-        launch_light_pdf_kat(P, n, dor, ddi, dout, nullptr) == hipSuccess && hipMemcpy(out, dout, n * 8ull, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
-    (void)hipFree(dor); (void)hipFree(ddi); (void)hipFree(dout);
-    return rc == 0 ? 0 : set_err("rt_debug_light_pdf: a HIP call failed");
+    if (!flatten_for_render(s)) return -1;
+    return run_kat(s, launch_light_pdf_kat, n, origins, 24u, dirs, 24u, out, 8u);
 }
 int rt_debug_trace_path(rt_scene* sc, long long local_pixel, long long sample) {
     if (!sc) return set_err("null argument");
@@ -1130,9 +1105,7 @@ static void progressive_free(Progressive* p) {
 }
 void* rt_progressive_create(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t max_depth,
                             uint64_t seed, uint32_t flags) {
-    if (check_frame_args(sc, cam, bg, W, H, 1u)) return nullptr;
-    if (rt_device_count() <= 0) { set_err("no HIP device: librt_amd has no CPU rendering path"); return nullptr; }
-    if (!flatten_scene(sc->s)) { g_err = sc->s.error; return nullptr; }
+    if (frame_prologue(sc, cam, bg, W, H, 1u)) return nullptr;
     Progressive* p = new Progressive();
     p->sc = sc; p->scene_version = sc->s.version; std::memcpy(&p->cam, cam, sizeof(rt_camera));
     for (int k = 0; k < 3; k++) p->bg[k] = bg[k];
@@ -1180,17 +1153,13 @@ int rt_progressive_add(void* frame, uint32_t n, double* samples_out) {
     Progressive* p = (Progressive*)frame;
     if (progressive_pass_args(p, n)) return -1;
     DeviceGuard guard(p->device);
-    void* d_samples = nullptr;
+    DeviceBuffer d_samples;
     const size_t sample_bytes = p->n_px() * n * 3 * sizeof(double);
-    if (samples_out) HIP_OK(hipMalloc(&d_samples, sample_bytes));
-    int rc = progressive_pass(p, n, d_samples, nullptr, true);
-    if (rc == 0) {
-        hipError_t e = hipStreamSynchronize(nullptr);
-        if (e == hipSuccess && samples_out) e = hipMemcpy(samples_out, d_samples, sample_bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { g_err = std::string("rt_progressive_add: ") + hipGetErrorString(e); rc = -1; }
-    }
-    if (d_samples) (void)hipFree(d_samples);
-    return rc;
+    if (samples_out) HIP_OK(d_samples.alloc(sample_bytes));
+    if (progressive_pass(p, n, d_samples.get(), nullptr, true)) return -1;
+    hipError_t e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess && samples_out) e = hipMemcpy(samples_out, d_samples.get(), sample_bytes, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? 0 : set_err(std::string("rt_progressive_add: ") + hipGetErrorString(e));
 }
 int rt_progressive_add_async(void* frame, uint32_t n, void* hip_stream) {
     Progressive* p = (Progressive*)frame;
@@ -1276,25 +1245,16 @@ int rt_progressive_reset(void* frame) {
 int rt_render_samples(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
                       uint64_t seed, uint32_t flags, double* rgb_sum_out, double* samples_out) {
     if (!rgb_sum_out) return set_err("null output");
-    if (check_frame_args(sc, cam, bg, W, H, spp)) return -1;
-    size_t n_px = (size_t)W * H;
-    void* d_out = nullptr; void* d_samples = nullptr;
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    HIP_OK(hipMalloc(&d_out, n_px * 3 * sizeof(double)));
-    if (samples_out) {
-        hipError_t e = hipMalloc(&d_samples, n_px * spp * 3 * sizeof(double));
-        if (e != hipSuccess) { (void)hipFree(d_out); return set_err(std::string("hipMalloc(samples): ") + hipGetErrorString(e)); }
-    }
-    int rc = render_any(sc, cam, bg, W, H, spp, max_depth, seed, flags, (uint32_t)n_px, 0, 1, d_out, n_px * 3 * sizeof(double), d_samples, nullptr, true);
-    if (rc == 0) {
-        hipError_t e = hipStreamSynchronize(nullptr);
-        if (e == hipSuccess) e = hipMemcpy(rgb_sum_out, d_out, n_px * 3 * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && samples_out) e = hipMemcpy(samples_out, d_samples, n_px * spp * 3 * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { g_err = std::string("copy back: ") + hipGetErrorString(e); rc = -1; }
-    }
-    (void)hipFree(d_out);
-    if (d_samples) (void)hipFree(d_samples);
-    return rc;
+    if (frame_prologue(sc, cam, bg, W, H, spp)) return -1;
+    const size_t n_px = (size_t)W * H, sum_bytes = n_px * 3 * sizeof(double), sample_bytes = sum_bytes * spp;
+    DeviceBuffer d_out, d_samples;
+    HIP_OK(d_out.alloc(sum_bytes));
+    if (samples_out) { const hipError_t e = d_samples.alloc(sample_bytes); if (e != hipSuccess) return set_err(std::string("hipMalloc(samples): ") + hipGetErrorString(e)); }
+    if (render_any(sc, cam, bg, W, H, spp, max_depth, seed, flags, (uint32_t)n_px, 0, 1, d_out.get(), sum_bytes, d_samples.get(), nullptr, true)) return -1;
+    hipError_t e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = hipMemcpy(rgb_sum_out, d_out.get(), sum_bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && samples_out) e = hipMemcpy(samples_out, d_samples.get(), sample_bytes, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? 0 : set_err(std::string("copy back: ") + hipGetErrorString(e));
 }
 
 int rt_render(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,

@@ -28,6 +28,7 @@
 #include <vector>
 #include "../../include/rt_amd.h"
 #include "rt_scene.h"
+#include "rt_device.h"
 
 using namespace rt;
 
@@ -100,32 +101,47 @@ bool ensure_buffer(void*& p, size_t& have, size_t need, std::string& err) {
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // Wait for everything the frame in flight put on the devices' streams (also the way out of a failed call: nothing of it may still
-// be running when its buffers are reused or freed).  Leaves the current device at the last one visited.
+// be running when its buffers are reused or freed).
 void drain(Scene& s) {
     for (int d : s.multi_devs) {
-        for (Scene::DeviceCtx* c : s.ctxs) if (c->device == d && c->stream) { (void)hipSetDevice(d); (void)hipStreamSynchronize((hipStream_t)c->stream); }
+        for (Scene::DeviceCtx* c : s.ctxs) if (c->device == d && c->stream) { DeviceGuard guard(d); (void)hipStreamSynchronize((hipStream_t)c->stream); }
     }
+}
+// The visible devices a device mask selects (bit d = HIP device d; 0 = all of them), in ascending order.
+std::vector<int> devices_of_mask(uint32_t device_mask, int n_visible) {
+    std::vector<int> devs;
+    for (int d = 0; d < n_visible && d < 32; d++) if (device_mask == 0u || (device_mask >> d) & 1u) devs.push_back(d);
+    return devs;
+}
+// Test hooks (tests/test_multi_gpu.py), never set in production.  RT_MULTI_VIRTUAL_RANKS=N (1..64; anything else: none) deals the tiles
+// to N ranks that all live on the FIRST selected device, one after the other, and "gathers" with device-to-device copies — the tile
+// arithmetic and the un-permute kernel of an N-GPU frame on a one-GPU box.  RT_MULTI_FAIL_RANK=r makes rank r's launch fail after the
+// ranks before it were launched — the error path of an N-GPU frame.
+uint32_t virtual_ranks_hook() {
+    if (const char* v = std::getenv("RT_MULTI_VIRTUAL_RANKS")) { const long n = std::strtol(v, nullptr, 10); if (n >= 1 && n <= 64) return (uint32_t)n; }
+    return 0u;
+}
+// The four events of the frame in flight and the virtual-rank hook's tile buffers live on one device each: released there.
+void destroy_multi_events(Scene& s) {
+    if (s.multi_ev_device < 0) return;
+    DeviceGuard guard(s.multi_ev_device);
+    for (void*& e : s.multi_ev) if (e) { (void)hipEventDestroy((hipEvent_t)e); e = nullptr; }
+    s.multi_ev_device = -1;
+}
+void free_virtual_tiles(Scene& s) {
+    if (s.virtual_tiles.empty()) return;
+    DeviceGuard guard(s.virtual_tiles_device);
+    for (void* p : s.virtual_tiles) if (p) (void)hipFree(p);
+    s.virtual_tiles.clear(); s.virtual_tiles_bytes = 0; s.virtual_tiles_device = -1;
 }
 
 } // namespace
 
 namespace rt {
 void multi_release(Scene& s) {
-    if (s.multi_pending) { int cur = 0; (void)hipGetDevice(&cur); drain(s); (void)hipSetDevice(cur); s.multi_pending = false; }
-    if (s.multi_ev_device >= 0) {
-        int cur = 0; (void)hipGetDevice(&cur);
-        (void)hipSetDevice(s.multi_ev_device);
-        for (void*& e : s.multi_ev) if (e) { (void)hipEventDestroy((hipEvent_t)e); e = nullptr; }
-        s.multi_ev_device = -1;
-        (void)hipSetDevice(cur);
-    }
-    if (!s.virtual_tiles.empty()) {
-        int cur = 0; (void)hipGetDevice(&cur);
-        (void)hipSetDevice(s.virtual_tiles_device);
-        for (void* p : s.virtual_tiles) if (p) (void)hipFree(p);
-        s.virtual_tiles.clear(); s.virtual_tiles_bytes = 0; s.virtual_tiles_device = -1;
-        (void)hipSetDevice(cur);
-    }
+    if (s.multi_pending) { drain(s); s.multi_pending = false; }
+    destroy_multi_events(s);
+    free_virtual_tiles(s);
     if (s.comms.empty()) return;                 // single-GPU users never touch (or load) RCCL, not even at teardown
     Rccl* R = rccl();
     if (R->lib) for (void* c : s.comms) if (c) (void)R->CommDestroy(c);
@@ -142,17 +158,11 @@ bool enqueue_frame(rt_scene* sc, const rt_camera* cam, const double bg[3], uint3
     Scene& s = sc->s;
     const int n_visible = rt_device_count();
     if (n_visible <= 0) { err = "no HIP device: librt_amd has no CPU rendering path"; return false; }
-    std::vector<int> devs;
-    for (int d = 0; d < n_visible && d < 32; d++) if (device_mask == 0u || (device_mask >> d) & 1u) devs.push_back(d);
+    std::vector<int> devs = devices_of_mask(device_mask, n_visible);
     if (devs.empty() || (device_mask != 0u && n_visible < 32 && (device_mask >> n_visible) != 0u)) {
         err = "device_mask selects a device that is not visible (rt_device_count() = " + std::to_string(n_visible) + ")"; return false;
     }
-    // Test hooks (tests/test_multi_gpu.py), never set in production.  RT_MULTI_VIRTUAL_RANKS=N deals the tiles to N ranks that all
-    // live on the FIRST selected device, one after the other, and "gathers" with device-to-device copies — the tile arithmetic and the
-    // un-permute kernel of an N-GPU frame on a one-GPU box.  RT_MULTI_FAIL_RANK=r makes rank r's launch fail after the ranks before
-    // it were launched — the error path of an N-GPU frame.
-    uint32_t virtual_ranks = 0;
-    if (const char* v = std::getenv("RT_MULTI_VIRTUAL_RANKS")) { long n = std::strtol(v, nullptr, 10); if (n >= 1 && n <= 64) virtual_ranks = (uint32_t)n; }
+    const uint32_t virtual_ranks = virtual_ranks_hook();      // (test hooks: see virtual_ranks_hook)
     long fail_rank = -1;
     if (const char* v = std::getenv("RT_MULTI_FAIL_RANK")) fail_rank = std::strtol(v, nullptr, 10);
     if (virtual_ranks) devs.assign(virtual_ranks, devs[0]);
@@ -203,14 +213,14 @@ bool enqueue_frame(rt_scene* sc, const rt_camera* cam, const double bg[3], uint3
     Scene::DeviceCtx& root = *ctx[0];
     if ((e = hipSetDevice(devs[0])) != hipSuccess) { err = hip_msg("hipSetDevice", e); return false; }
     if (s.multi_ev_device != devs[0]) {
-        if (s.multi_ev_device >= 0) { (void)hipSetDevice(s.multi_ev_device); for (void*& ev : s.multi_ev) if (ev) { (void)hipEventDestroy((hipEvent_t)ev); ev = nullptr; } (void)hipSetDevice(devs[0]); }
+        destroy_multi_events(s);
         s.multi_ev_device = devs[0];
         for (void*& ev : s.multi_ev) { hipEvent_t x; if ((e = hipEventCreate(&x)) != hipSuccess) { err = hip_msg("hipEventCreate", e); return false; } ev = x; }
     }
     std::vector<void*> rank_tiles(N, nullptr);      // each rank's packed tile buffer (virtual ranks: buffers on the one device, kept with the scene)
     if (virtual_ranks) {
         if (s.virtual_tiles.size() != N || s.virtual_tiles_bytes < tiles_bytes || s.virtual_tiles_device != devs[0]) {
-            if (!s.virtual_tiles.empty()) { (void)hipSetDevice(s.virtual_tiles_device); for (void* p : s.virtual_tiles) if (p) (void)hipFree(p); (void)hipSetDevice(devs[0]); }
+            free_virtual_tiles(s);
             s.virtual_tiles.assign(N, nullptr); s.virtual_tiles_bytes = tiles_bytes; s.virtual_tiles_device = devs[0];
             for (uint32_t r = 0; r < N; r++) if ((e = hipMalloc(&s.virtual_tiles[r], tiles_bytes)) != hipSuccess) { s.virtual_tiles[r] = nullptr; err = hip_msg("hipMalloc", e); return false; }
         }
@@ -282,10 +292,9 @@ bool enqueue_frame(rt_scene* sc, const rt_camera* cam, const double bg[3], uint3
 // Wait for the frame in flight and settle rt_last_multi_ms.
 int settle(Scene& s) {
     if (!s.multi_pending) return 0;
-    int cur = 0; (void)hipGetDevice(&cur);
     drain(s);
     s.multi_pending = false;
-    (void)hipSetDevice(s.multi_devs[0]);
+    DeviceGuard guard(s.multi_devs[0]);
     float g_ms = 0.f, u_ms = 0.f, k_max = 0.f;
     // both on the root's stream: [0] fires when the root's own kernel is done, [1] when the gather behind it is — the collective
     // including the wait for the slowest other device
@@ -301,7 +310,6 @@ int settle(Scene& s) {
         float k = 0.f; if (device_kernel_ms(s, d, &k) == 0 && k > k_max) k_max = k;
     }
     s.multi_ms[0] = k_max; s.multi_ms[1] = g_ms; s.multi_ms[2] = u_ms; s.multi_ms[3] = now_ms() - s.multi_t0;
-    (void)hipSetDevice(cur);
     return rc;
 }
 
@@ -320,14 +328,13 @@ int rt_render_multi_device(rt_scene* sc, const rt_camera* cam, const double bg[3
     // devices go from one frame's kernel to the next without a launch gap.  Timings are kept for the most recent frame only.
     if (tile_px == 0) tile_px = 67;                 // the default of dist.py: a prime, so that tile columns drift across rows
     {   // (a frame of another shape or on other devices may reallocate buffers or communicators: that one waits)
-        unsigned long long virt = 0; if (const char* v = std::getenv("RT_MULTI_VIRTUAL_RANKS")) virt = (unsigned long long)std::strtol(v, nullptr, 10);
+        const unsigned long long virt = virtual_ranks_hook();
         const unsigned long long sig[4] = {W, H, tile_px, (unsigned long long)device_mask | ((unsigned long long)(flags & (RT_F32 | RT_MULTI_COLLECTIVE)) << 32) | (virt << 48)};
         bool same = true; for (int k = 0; k < 4; k++) same = same && sig[k] == s.multi_sig[k];
         if (!same && settle(s)) return -1;
         for (int k = 0; k < 4; k++) s.multi_sig[k] = sig[k];
     }
-    int cur = 0;
-    { const hipError_t e = hipGetDevice(&cur); if (e != hipSuccess) return set_error(hip_msg("hipGetDevice", e)); }
+    DeviceGuard keep;                               // enqueue_frame goes from device to device: a PyTorch host keeps its current device
     s.multi_t0 = now_ms();
     std::string err;
     const std::vector<int> devs_before = s.multi_devs;
@@ -342,7 +349,6 @@ int rt_render_multi_device(rt_scene* sc, const rt_camera* cam, const double bg[3
         if (d_frame_out) *d_frame_out = s.ctx_for(s.multi_devs[0]).d_frame[s.multi_frames & 1ull];
         s.multi_frame_doubles = (size_t)W * H * 3; s.multi_frames++;
     }
-    (void)hipSetDevice(cur);                        // a PyTorch host keeps its current device
     return ok ? 0 : set_error(err);
 }
 
@@ -360,10 +366,8 @@ int rt_multi_copy_frame(rt_scene* sc, double* rgb_sum_out, size_t n_doubles) {
     if (s.multi_frames == 0) return set_error("no rt_render_multi frame has been rendered for this scene");
     const void* frame = root.d_frame[(s.multi_frames - 1ull) & 1ull];          // the most recent frame's buffer
     if (!frame || n_doubles > s.multi_frame_doubles) return set_error("rt_multi_copy_frame: more doubles asked for than the last frame holds (W*H*3)");
-    int cur = 0; (void)hipGetDevice(&cur);
-    (void)hipSetDevice(s.multi_devs[0]);
+    DeviceGuard guard(s.multi_devs[0]);
     const hipError_t e = hipMemcpy(rgb_sum_out, frame, n_doubles * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipSetDevice(cur);
     return e == hipSuccess ? 0 : set_error(hip_msg("hipMemcpy(frame)", e));
 }
 
@@ -372,15 +376,10 @@ int rt_render_multi(rt_scene* sc, const rt_camera* cam, const double bg[3], uint
     if (!rgb_sum_out || !sc || !cam || !bg) return set_error("null argument");
     {   // this entry point is synchronous: a first large frame of a mesh scene measures its loop shape here (rt_host.cpp:
         // calibrate_loop_shape), on the frame's first device; the asynchronous rt_render_multi_device never does
-        const int n_visible = rt_device_count();
-        int first = -1;
-        for (int d = 0; d < n_visible && d < 32 && first < 0; d++) if (device_mask == 0u || (device_mask >> d) & 1u) first = d;
-        if (first >= 0) {
-            int cur = 0; (void)hipGetDevice(&cur);
-            (void)hipSetDevice(first);
-            const int rc = rt::calibrate_if_worth_it(sc, cam, bg, W, H, spp, max_depth, seed, flags & ~(uint32_t)RT_MULTI_COLLECTIVE);
-            (void)hipSetDevice(cur);
-            if (rc) return -1;
+        const std::vector<int> devs = devices_of_mask(device_mask, rt_device_count());
+        if (!devs.empty()) {
+            DeviceGuard guard(devs[0]);
+            if (rt::calibrate_view(sc, cam, bg, W, H, spp, max_depth, seed, flags & ~(uint32_t)RT_MULTI_COLLECTIVE, true)) return -1;
         }
     }
     if (rt_render_multi_device(sc, cam, bg, W, H, spp, max_depth, seed, flags, device_mask, tile_px, nullptr)) return -1;

@@ -166,5 +166,5 @@ void camera_new(const rt_camera_args& a, DCamera<double>& out);
 struct rt_scene { rt::Scene s; };       // the opaque handle of include/rt_amd.h
 struct rt_camera;
 namespace rt {
-int calibrate_if_worth_it(::rt_scene* sc, const ::rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth, uint64_t seed, uint32_t flags);   // rt_render_multi: the implicit loop-shape calibration of a first large frame (current device = the frame's first)
+int calibrate_view(::rt_scene* sc, const ::rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth, uint64_t seed, uint32_t flags, bool only_if_worth_it);   // rt_scene_calibrate; only_if_worth_it: rt_render_multi's implicit loop-shape calibration of a first large frame (current device = the frame's first)
 }
