@@ -15,10 +15,7 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import Sequence
 
-c_double_p = C.POINTER(C.c_double)
-c_u32_p = C.POINTER(C.c_uint32)
-c_u64_p = C.POINTER(C.c_uint64)
-c_int_p = C.POINTER(C.c_int)
+from ._abi import BUILDER_NAMES, CameraParams, c_double_p, declare  # noqa: F401  (CameraParams, c_double_p: part of this module's interface)
 
 
 class Plane:      # src/rect.rs:9-13
@@ -31,13 +28,6 @@ class Axis:       # src/rotate.rs:8-12
 
 def _v3(v: Sequence[float]):
     return (C.c_double * 3)(float(v[0]), float(v[1]), float(v[2]))
-
-
-class CameraParams(C.Structure):
-    """Arguments of Camera::new (src/camera.rs:19)."""
-    _fields_ = [("lookfrom", C.c_double * 3), ("lookat", C.c_double * 3), ("vup", C.c_double * 3),
-                ("vfov", C.c_double), ("aspect", C.c_double), ("aperture", C.c_double),
-                ("focus_dist", C.c_double), ("time0", C.c_double), ("time1", C.c_double)]
 
 
 def Camera(lookfrom, lookat, vup, vfov, aspect_ratio, aperture, focus_dist, time0, time1) -> CameraParams:
@@ -53,53 +43,9 @@ def Camera(lookfrom, lookat, vup, vfov, aspect_ratio, aperture, focus_dist, time
 class Backend:
     """A loaded C library plus the symbol prefix of its builder API."""
 
-    _BUILDER_SIGS = {
-        "scene_create": (C.c_void_p, []),
-        "scene_destroy": (None, [C.c_void_p]),
-        "scene_error": (C.c_char_p, [C.c_void_p]),
-        "rng_create": (C.c_void_p, [C.c_uint64, C.c_uint32]),
-        "rng_destroy": (None, [C.c_void_p]),
-        "rng_f64": (C.c_double, [C.c_void_p]),
-        "rng_range": (C.c_double, [C.c_void_p, C.c_double, C.c_double]),
-        "rng_bool": (C.c_int, [C.c_void_p]),
-        "rng_index": (C.c_uint32, [C.c_void_p, C.c_uint32]),
-        "rng_u32": (C.c_uint32, [C.c_void_p]),
-        "rng_path": (None, [C.c_uint64, C.c_uint32, C.c_uint32, c_u32_p]),
-        "texture_constant": (C.c_int, [C.c_void_p, c_double_p]),
-        "texture_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
-        "texture_noise": (C.c_int, [C.c_void_p, C.c_double, C.c_void_p]),
-        "texture_image": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32]),
-        "material_lambertian": (C.c_int, [C.c_void_p, C.c_int]),
-        "material_metal": (C.c_int, [C.c_void_p, c_double_p, C.c_double]),
-        "material_dielectric": (C.c_int, [C.c_void_p, C.c_double]),
-        "material_diffuse_light": (C.c_int, [C.c_void_p, C.c_int]),
-        "material_isotropic": (C.c_int, [C.c_void_p, C.c_int]),
-        "material_pbr": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
-        "sphere": (C.c_int, [C.c_void_p, c_double_p, C.c_double, C.c_int]),
-        "moving_sphere": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_int]),
-        "aarect": (C.c_int, [C.c_void_p, C.c_int] + [C.c_double] * 5 + [C.c_int]),
-        "cube": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_int]),
-        "triangle": (C.c_int, [C.c_void_p, c_double_p, C.c_int]),
-        "list_create": (C.c_int, [C.c_void_p]),
-        "list_push": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
-        "mesh": (C.c_int, [C.c_void_p, c_double_p, C.c_uint32, c_u32_p, C.c_uint32, C.c_int]),
-        "flip_normal": (C.c_int, [C.c_void_p, C.c_int]),
-        "translate": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
-        "rotate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double]),
-        "constant_medium": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int]),
-        "bvh": (C.c_int, [C.c_void_p, c_int_p, C.c_uint32, C.c_double, C.c_double]),
-        "bvh_of_list": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double]),
-        "scene_set_world": (C.c_int, [C.c_void_p, C.c_int]),
-        "lights_push": (C.c_int, [C.c_void_p, C.c_int]),
-        "camera_fields": (None, [C.POINTER(CameraParams), c_double_p]),
-        "format_color": (None, [c_double_p, C.c_uint64, c_u64_p]),
-    }
-
     def __init__(self, lib: C.CDLL, prefix: str):
         self.lib, self.prefix = lib, prefix
-        for name, (res, args) in self._BUILDER_SIGS.items():
-            fn = getattr(lib, prefix + name)
-            fn.restype, fn.argtypes = res, args
+        declare(lib, prefix, BUILDER_NAMES)
 
     def fn(self, name: str):
         return getattr(self.lib, self.prefix + name)

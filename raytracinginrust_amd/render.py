@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._abi import c_u32_p
 from .api import CameraParams, SceneBuilder
 
 RT_F64, RT_F32, RT_STOP_ON_ZERO, RT_ISOTROPIC_SCATTER, RT_NEAR_FIRST_BVH = 0, 1, 2, 4, 8
@@ -24,20 +25,28 @@ class RenderError(RuntimeError):
     pass
 
 
-def _err(be) -> str:
-    return be.lib.rt_last_error().decode()
+def _rt():
+    """The loaded library, every rt_* function declared (_abi.SIGNATURES)."""
+    return _lib.load().lib
+
+
+def _err() -> str:
+    return _rt().rt_last_error().decode()
+
+
+def _check(rc) -> None:
+    if rc != 0:
+        raise RenderError(_err())
 
 
 def device_count() -> int:
-    return _lib.load().lib.rt_device_count()
+    return _rt().rt_device_count()
 
 
 def flatten(b: SceneBuilder) -> dict:
     """Flatten the Hittable tree into the device scene (host only) and return the table sizes."""
-    be = _lib.load()
     counts = (C.c_uint32 * 12)()
-    if be.lib.rt_scene_flatten(b.h, counts) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_scene_flatten(b.h, counts))
     return dict(zip(FLATTEN_COUNT_NAMES, [int(x) for x in counts]))
 
 
@@ -49,33 +58,94 @@ def debug_objects(b: SceneBuilder, top_only: bool = True) -> list:
     kernels search them.  is_cube: 1 = a Cube's six faces; 2 | map << 8 = a ROOM (bare AARects that are faces of one box, tested through
     the Cube fast path: rt_flatten.cpp form_room) — map: three bits per face in cube.rs:17-24 order, the wall's place in the room's run
     of rect records or 7 = no such wall; first_op then holds, five bits per wall, the tie-rule index."""
-    be = _lib.load()
-    be.lib.rt_debug_objects.restype = C.c_int
-    be.lib.rt_debug_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    rows, n_top = debug_object_rows(b)
+    return [dict(zip(OBJECT_FIELDS, [int(x) for x in r])) for r in (rows[:n_top] if top_only else rows)]
+
+
+def debug_object_rows(b: SceneBuilder):
+    """The same table as it comes: ((n, 8) uint32, columns in OBJECT_FIELDS order; how many of the rows are top-level objects)."""
     n_top = C.c_uint32(0)
-    n = be.lib.rt_debug_objects(b.h, None, 0, C.byref(n_top))
+    n = _rt().rt_debug_objects(b.h, None, 0, C.byref(n_top))
     if n < 0:
-        raise RenderError(_err(be))
+        raise RenderError(_err())
     out = np.zeros((max(n, 1), 8), np.uint32)
-    if be.lib.rt_debug_objects(b.h, out.ctypes.data, n, C.byref(n_top)) != n:
-        raise RenderError(_err(be))
-    rows = out[: (int(n_top.value) if top_only else n)]
-    return [dict(zip(OBJECT_FIELDS, [int(x) for x in r])) for r in rows]
+    if _rt().rt_debug_objects(b.h, out.ctypes.data, n, C.byref(n_top)) != n:
+        raise RenderError(_err())
+    return out[:n], int(n_top.value)
 
 
 def debug_light_pdf(b: SceneBuilder, origins: np.ndarray, dirs: np.ndarray) -> np.ndarray:
     """rt_debug_light_pdf (needs a GPU): the scene's `lights` pdf_value (HittableList::pdf_value, nested lists included) for n
     (origin, direction) pairs, computed on the device by the function the all-features kernel with object leaves runs."""
-    be = _lib.load()
-    be.lib.rt_debug_light_pdf.restype = C.c_int
-    be.lib.rt_debug_light_pdf.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
     d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
     if o.shape != d.shape:
         raise ValueError("origins and dirs differ in shape")
     out = np.zeros(len(o), np.float64)
-    if be.lib.rt_debug_light_pdf(b.h, len(o), o.ctypes.data, d.ctypes.data, out.ctypes.data) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_debug_light_pdf(b.h, len(o), o.ctypes.data, d.ctypes.data, out.ctypes.data))
+    return out
+
+
+def debug_bvh_links(b: SceneBuilder):
+    """rt_debug_bvh_links (host only): the flattened BVHs' link words, (n, 4) uint32 {a, b, c, skip} per node, and the root node of every
+    BVH object of the world list (uint32)."""
+    n_roots = C.c_uint32(0)
+    n = _rt().rt_debug_bvh_links(b.h, None, 0, None, 0, C.byref(n_roots))
+    if n < 0:
+        raise RenderError(_err())
+    links = np.zeros((n, 4), np.uint32); roots = np.zeros(n_roots.value, np.uint32)
+    if _rt().rt_debug_bvh_links(b.h, links.ctypes.data_as(c_u32_p), n, roots.ctypes.data_as(c_u32_p), len(roots), None) != n:
+        raise RenderError(_err())
+    return links, roots
+
+
+def debug_filter_nodes(b: SceneBuilder):
+    """rt_debug_filter_nodes (host only): the filter tree the kernels' box steps walk, for the n nodes of debug_bvh_links: the f32 boxes
+    (n, 6) {min.x, max.x, min.y, max.y, min.z, max.z}, the links (n, 2) uint32 {skip, info}, the exact f64 boxes (n, 6) {min[3], max[3]},
+    and filter_m (0: filter off)."""
+    n = _rt().rt_debug_filter_nodes(b.h, None, None, None, 0, None)
+    if n < 0:
+        raise RenderError(_err())
+    boxes = np.zeros((n, 6), np.float32); links = np.zeros((n, 2), np.uint32); f64_boxes = np.zeros((n, 6)); filter_m = C.c_float(0)
+    if _rt().rt_debug_filter_nodes(b.h, boxes.ctypes.data, links.ctypes.data, f64_boxes.ctypes.data, n, C.byref(filter_m)) != n:
+        raise RenderError(_err())
+    return boxes, links, f64_boxes, filter_m.value
+
+
+def _hit_inputs(boxes, rays, tlim):
+    """(n, 6) boxes {min[3], max[3]}, (n, 6) rays {origin[3], direction[3]}, (n, 2) [t_min, t_max] as contiguous f64 arrays."""
+    boxes, rays, tlim = (np.ascontiguousarray(a, np.float64) for a in (boxes, rays, tlim))
+    n = len(boxes)
+    if boxes.shape != (n, 6) or rays.shape != (n, 6) or tlim.shape != (n, 2):
+        raise ValueError(f"boxes {boxes.shape}, rays {rays.shape}, tlim {tlim.shape}: want (n, 6), (n, 6), (n, 2)")
+    return n, boxes, rays, tlim
+
+
+def debug_aabb_hit(boxes, rays, tlim) -> np.ndarray:
+    """rt_debug_aabb_hit (needs a GPU): AABB::hit on the device for n (box, ray, [t_min, t_max]) triples -> (n,) int32 of verdict bits."""
+    n, boxes, rays, tlim = _hit_inputs(boxes, rays, tlim)
+    out = np.zeros(n, np.int32)
+    _check(_rt().rt_debug_aabb_hit(n, boxes.ctypes.data, rays.ctypes.data, tlim.ctypes.data, out.ctypes.data))
+    return out
+
+
+def debug_cube_hit(boxes, rays, tlim, rect_m: float) -> np.ndarray:
+    """rt_debug_cube_hit (needs a GPU): Cube::hit on the device by the six exact rect tests and by the fast path -> (n, 4) f64
+    {exact t, exact face, fast t, 8 * clear + face + 1}."""
+    n, boxes, rays, tlim = _hit_inputs(boxes, rays, tlim)
+    out = np.zeros((n, 4))
+    _check(_rt().rt_debug_cube_hit(n, rect_m, boxes.ctypes.data, rays.ctypes.data, tlim.ctypes.data, out.ctypes.data))
+    return out
+
+
+def debug_room_hit(boxes, rays, tlim, rect_m: float, masks) -> np.ndarray:
+    """rt_debug_room_hit (needs a GPU): the same for the ROOM form; masks[i]: which of the six faces exist -> (n, 4) f64 as debug_cube_hit."""
+    n, boxes, rays, tlim = _hit_inputs(boxes, rays, tlim)
+    masks = np.ascontiguousarray(masks, np.uint32)
+    if masks.shape != (n,):
+        raise ValueError(f"masks {masks.shape}: want ({n},)")
+    out = np.zeros((n, 4))
+    _check(_rt().rt_debug_room_hit(n, rect_m, boxes.ctypes.data, rays.ctypes.data, tlim.ctypes.data, masks.ctypes.data, out.ctypes.data))
     return out
 
 
@@ -84,23 +154,17 @@ RT_BVH_MEDIAN, RT_BVH_SAH = 0, 1
 
 def set_bvh_builder(b: SceneBuilder, mode: int) -> None:
     """RT_BVH_MEDIAN: the reference's BVH::new (default); RT_BVH_SAH: opt-in binned surface-area heuristic."""
-    be = _lib.load()
-    if be.lib.rt_scene_set_bvh_builder(b.h, mode) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_scene_set_bvh_builder(b.h, mode))
 
 
 def set_traversal_schedule(b: SceneBuilder, start_at: int = 40, stop_below: int = 24, leaf_share64: int = 16) -> None:
     """Tuning knob of the persistent-traversal loop (scheduling only)."""
-    be = _lib.load()
-    if be.lib.rt_scene_set_traversal_schedule(b.h, start_at, stop_below, leaf_share64) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_scene_set_traversal_schedule(b.h, start_at, stop_below, leaf_share64))
 
 
 def prepare(b: SceneBuilder, flags: int = RT_F64) -> None:
     """Flatten, upload and load the kernel now instead of inside the first render (no launch)."""
-    be = _lib.load()
-    if be.lib.rt_scene_prepare(b.h, flags) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_scene_prepare(b.h, flags))
 
 
 LOOP_SHAPES = ("list", "lock-step", "persistent")
@@ -111,31 +175,25 @@ def calibrate(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, sp
               seed: int = 0x5EED, flags: int = RT_F64) -> None:
     """rt_scene_calibrate: mesh scenes measure now, synchronously, which loop shape is faster for this view (four small launches);
     a no-op for every other scene.  The asynchronous entry points (render_tiles_device, render_multi_device) never do it themselves."""
-    be = _lib.load()
     bg = (C.c_double * 3)(*[float(x) for x in background])
-    if be.lib.rt_scene_calibrate(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_scene_calibrate(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags))
 
 
 def set_loop_shape(b: SceneBuilder, shape: int) -> None:
     """rt_scene_set_loop_shape: 1 persistent traversal, 0 lock-step (every view, until the scene changes), -1 forget."""
-    be = _lib.load()
-    if be.lib.rt_scene_set_loop_shape(b.h, shape) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_scene_set_loop_shape(b.h, shape))
 
 
 def stored_loop_shape(b: SceneBuilder) -> int:
     """rt_scene_loop_shape: 1 persistent traversal, 0 lock-step, -1 nothing stored."""
-    return int(_lib.load().lib.rt_scene_loop_shape(b.h))
+    return int(_rt().rt_scene_loop_shape(b.h))
 
 
 def last_loop_info(b: SceneBuilder) -> dict:
     """rt_last_loop_info: the loop shape and instantiation the most recent launch ran, how the shape was chosen, and the stored
     calibration's kernel times."""
-    be = _lib.load()
     out = (C.c_int32 * 4)(); ms = (C.c_float * 2)()
-    if be.lib.rt_last_loop_info(b.h, out, ms) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_last_loop_info(b.h, out, ms))
     t = "float" if out[3] else "double"
     return {"shape": LOOP_SHAPES[out[0]], "feats": int(out[1]), "kernel": f"rt::pathtrace_kernel<{t}, {int(out[1])}u>",
             "chosen_by": LOOP_CHOSEN_BY[out[2]],
@@ -147,17 +205,15 @@ def render(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, spp: 
     """Per-pixel sums of ray_color over `spp` samples, shape (H, W, 3) f64, row 0 = top (what `.sum()`
     yields at src/main.rs:830, in the order the reference prints pixels).  With want_samples also returns
     the (H, W, spp, 3) per-sample radiance."""
-    be = _lib.load()
     out = np.zeros((H, W, 3), dtype=np.float64)
     bg = (C.c_double * 3)(*[float(x) for x in background])
     if want_samples:
         samples = np.zeros((H, W, spp, 3), dtype=np.float64)
-        rc = be.lib.rt_render_samples(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags, out.ctypes.data, samples.ctypes.data)
+        rc = _rt().rt_render_samples(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags, out.ctypes.data, samples.ctypes.data)
     else:
         samples = None
-        rc = be.lib.rt_render(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags, out.ctypes.data)
-    if rc != 0:
-        raise RenderError(_err(be))
+        rc = _rt().rt_render(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags, out.ctypes.data)
+    _check(rc)
     return (out, samples) if want_samples else out
 
 
@@ -173,58 +229,54 @@ class Progressive:
     """
 
     def __init__(self, b: SceneBuilder, cam: CameraParams, background, W: int, H: int, max_depth: int, seed: int = 0x5EED, flags: int = RT_F64):
-        self._be = _lib.load()
+        self._lib = _rt()
         self.W, self.H = int(W), int(H)
         bg = (C.c_double * 3)(*[float(x) for x in background])
-        self._h = self._be.lib.rt_progressive_create(b.h, C.byref(cam), bg, W, H, max_depth, seed, flags)
+        self._h = self._lib.rt_progressive_create(b.h, C.byref(cam), bg, W, H, max_depth, seed, flags)
         if not self._h:
-            raise RenderError(_err(self._be))
+            raise RenderError(_err())
         self._builder = b              # the scene stays alive at least as long as the frame
-
-    def _check(self, rc) -> None:
-        if rc != 0:
-            raise RenderError(_err(self._be))
 
     def add(self, n: int, want_samples: bool = False):
         """One synchronous pass of n samples per pixel; with want_samples returns them, (H, W, n, 3) as `render` lays them out."""
         samples = np.zeros((self.H, self.W, n, 3), dtype=np.float64) if want_samples else None
-        self._check(self._be.lib.rt_progressive_add(self._h, n, samples.ctypes.data if want_samples else None))
+        _check(self._lib.rt_progressive_add(self._h, n, samples.ctypes.data if want_samples else None))
         return samples
 
     def add_async(self, n: int, stream: int = 0) -> None:
         """The same pass enqueued on a HIP stream of the frame's device; never waits."""
-        self._check(self._be.lib.rt_progressive_add_async(self._h, n, C.c_void_p(stream)))
+        _check(self._lib.rt_progressive_add_async(self._h, n, C.c_void_p(stream)))
 
     @property
     def samples(self) -> int:
         done = C.c_uint64()
-        self._check(self._be.lib.rt_progressive_samples(self._h, C.byref(done)))
+        _check(self._lib.rt_progressive_samples(self._h, C.byref(done)))
         return int(done.value)
 
     def rgb8(self):
         """format_color(samples) of every pixel, computed on the device: ((H, W, 3) uint8, pixels changed since the previous resolve)."""
         out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
         changed = C.c_uint64()
-        self._check(self._be.lib.rt_progressive_resolve_rgb8(self._h, out.ctypes.data, C.byref(changed)))
+        _check(self._lib.rt_progressive_resolve_rgb8(self._h, out.ctypes.data, C.byref(changed)))
         return out, int(changed.value)
 
     def rgb8_device(self, stream: int = 0) -> int:
         """Enqueue the resolve on a HIP stream; returns the DEVICE address of the W*H*3 bytes (valid until the next-but-one resolve)."""
         ptr = C.c_void_p()
-        self._check(self._be.lib.rt_progressive_resolve_rgb8_device(self._h, C.byref(ptr), C.c_void_p(stream)))
+        _check(self._lib.rt_progressive_resolve_rgb8_device(self._h, C.byref(ptr), C.c_void_p(stream)))
         return int(ptr.value or 0)
 
     def rgb8_copy(self):
         """Wait for the most recent resolve and fetch it with its changed-pixel count, without resolving again."""
         out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
         changed = C.c_uint64()
-        self._check(self._be.lib.rt_progressive_copy_rgb8(self._h, out.ctypes.data, C.byref(changed)))
+        _check(self._lib.rt_progressive_copy_rgb8(self._h, out.ctypes.data, C.byref(changed)))
         return out, int(changed.value)
 
     def sum(self) -> np.ndarray:
         """The accumulated per-pixel sums, (H, W, 3) f64 as `render` returns them; with `samples`, a checkpoint."""
         out = np.zeros((self.H, self.W, 3), dtype=np.float64)
-        self._check(self._be.lib.rt_progressive_read_sum(self._h, out.ctypes.data))
+        _check(self._lib.rt_progressive_read_sum(self._h, out.ctypes.data))
         return out
 
     def load(self, rgb_sum: np.ndarray, samples: int) -> None:
@@ -232,14 +284,14 @@ class Progressive:
         a = np.ascontiguousarray(rgb_sum, dtype=np.float64)
         if a.shape != (self.H, self.W, 3):
             raise ValueError(f"checkpoint of shape {a.shape} for a frame of {(self.H, self.W, 3)}")
-        self._check(self._be.lib.rt_progressive_load_sum(self._h, a.ctypes.data, samples))
+        _check(self._lib.rt_progressive_load_sum(self._h, a.ctypes.data, samples))
 
     def reset(self) -> None:
-        self._check(self._be.lib.rt_progressive_reset(self._h))
+        _check(self._lib.rt_progressive_reset(self._h))
 
     def close(self) -> None:
         if self._h:
-            self._be.lib.rt_progressive_destroy(self._h)
+            self._lib.rt_progressive_destroy(self._h)
             self._h = None
 
     def __enter__(self):
@@ -284,11 +336,9 @@ def render_multi(b: SceneBuilder, cam: CameraParams, background, W: int, H: int,
     """The whole frame on the GPUs of this node selected by `device_mask` (bit d = HIP device d; 0 = all visible) from ONE call:
     per-device replicas of the scene, tiles dealt round-robin, one RCCL gather to the first device, un-permuted there
     (rt_render_multi, csrc/rt_multi.cpp).  Returns the (H, W, 3) per-pixel sums like render()."""
-    be = _lib.load()
     out = np.zeros((H, W, 3), dtype=np.float64)
     bg = (C.c_double * 3)(*[float(x) for x in background])
-    if be.lib.rt_render_multi(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags, device_mask, tile_px, out.ctypes.data) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_render_multi(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags, device_mask, tile_px, out.ctypes.data))
     return out
 
 
@@ -296,132 +346,104 @@ def render_multi_device(b: SceneBuilder, cam: CameraParams, background, W: int, 
                         seed: int = 0x5EED, flags: int = RT_F64, tile_px: int = 0) -> int:
     """rt_render_multi_device: enqueue the frame on the selected devices and return the DEVICE address (first selected device) of
     its W*H*3 per-pixel sums; `multi_sync` waits for it, `multi_frame` fetches it."""
-    be = _lib.load()
     bg = (C.c_double * 3)(*[float(x) for x in background])
     ptr = C.c_void_p()
-    if be.lib.rt_render_multi_device(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags, device_mask, tile_px, C.byref(ptr)) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_render_multi_device(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags, device_mask, tile_px, C.byref(ptr)))
     return int(ptr.value or 0)
 
 
 def multi_sync(b: SceneBuilder) -> None:
-    be = _lib.load()
-    if be.lib.rt_multi_sync(b.h) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_multi_sync(b.h))
 
 
 def multi_frame(b: SceneBuilder, W: int, H: int) -> np.ndarray:
     """The last rt_render_multi_device frame as an (H, W, 3) host array (waits for it)."""
-    be = _lib.load()
     out = np.zeros((H, W, 3), dtype=np.float64)
-    if be.lib.rt_multi_copy_frame(b.h, out.ctypes.data, out.size) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_multi_copy_frame(b.h, out.ctypes.data, out.size))
     return out
 
 
 def last_multi_ms(b: SceneBuilder) -> dict:
-    be = _lib.load()
     ms = (C.c_double * 4)()
-    if be.lib.rt_last_multi_ms(b.h, ms) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_last_multi_ms(b.h, ms))
     return {"slowest_kernel_ms": ms[0], "gather_ms": ms[1], "unpermute_ms": ms[2], "call_ms": ms[3]}
 
 
 def last_multi_ranks(b: SceneBuilder) -> dict:
     """rt_last_multi_ranks: HIP device and kernel ms of every rank of the last rt_render_multi* frame, and the rank count RCCL
     reports for the communicator its gather ran on (0: no collective ran)."""
-    be = _lib.load()
     n, coll = C.c_uint32(), C.c_uint32()
     dev = (C.c_int * 64)(); ms = (C.c_double * 64)()
-    be.lib.rt_last_multi_ranks.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
-    if be.lib.rt_last_multi_ranks(b.h, 64, C.byref(n), dev, ms, C.byref(coll)) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_last_multi_ranks(b.h, 64, C.byref(n), dev, ms, C.byref(coll)))
     k = min(int(n.value), 64)
     return {"n_ranks": int(n.value), "devices": [int(dev[i]) for i in range(k)], "kernel_ms": [float(ms[i]) for i in range(k)],
             "collective_ranks": int(coll.value)}
 
 
 def local_tiles(W: int, H: int, tile_px: int, rank: int, world: int) -> int:
-    return int(_lib.load().lib.rt_local_tiles(W, H, tile_px, rank, world))
+    return int(_rt().rt_local_tiles(W, H, tile_px, rank, world))
 
 
 def render_tiles_device(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, spp: int, max_depth: int,
                         seed: int, flags: int, tile_px: int, rank: int, world: int, d_out_ptr: int, d_out_bytes: int,
                         stream: int = 0) -> None:
     """Asynchronously render tiles t ≡ rank (mod world) into device memory at d_out_ptr on `stream`."""
-    be = _lib.load()
     bg = (C.c_double * 3)(*[float(x) for x in background])
-    rc = be.lib.rt_render_device(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags, tile_px, rank, world,
+    rc = _rt().rt_render_device(b.h, C.byref(cam), bg, W, H, spp, max_depth, seed, flags, tile_px, rank, world,
                                  C.c_void_p(d_out_ptr), d_out_bytes, C.c_void_p(stream))
-    if rc != 0:
-        raise RenderError(_err(be))
+    _check(rc)
 
 
 def kernel_time_total(b: SceneBuilder, reset: bool = False):
     """(total ms, launches) of this scene's kernels since the last reset; waits for launches in flight."""
-    be = _lib.load()
     ms, n = C.c_double(), C.c_ulonglong()
-    if be.lib.rt_kernel_time_total(b.h, C.byref(ms), C.byref(n), 1 if reset else 0) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_kernel_time_total(b.h, C.byref(ms), C.byref(n), 1 if reset else 0))
     return float(ms.value), int(n.value)
 
 
 def last_flush_count(b: SceneBuilder) -> int:
     """Accumulator flushes of the last launch (three f64 atomics to the frame each)."""
-    be = _lib.load()
     out = C.c_ulonglong()
-    if be.lib.rt_last_flush_count(b.h, C.byref(out)) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_last_flush_count(b.h, C.byref(out)))
     return int(out.value)
 
 
 def last_traversal_stats(b: SceneBuilder) -> dict:
     """BVH scenes: advance passes / traversal steps of the last launch and the lanes busy in each (summed over wavefronts)."""
-    be = _lib.load()
     out = (C.c_ulonglong * 4)()
-    if be.lib.rt_last_traversal_stats(b.h, out) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_last_traversal_stats(b.h, out))
     leaf = (C.c_ulonglong * 2)()
-    if be.lib.rt_last_leaf_steps(b.h, leaf) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_last_leaf_steps(b.h, leaf))
     return {"advance_passes": out[0], "advance_lanes": out[1], "traversal_steps": out[2], "traversal_lanes": out[3],
             "leaf_steps": leaf[0], "leaf_lanes": leaf[1]}          # of the traversal steps: the primitive-test steps (the rest test boxes)
 
 
 def last_launch_info(b: SceneBuilder) -> dict:
     """Geometry of the most recent launch (workgroups, threads, LDS bytes, BVH nodes staged in LDS / in the scene, workgroups per CU)."""
-    be = _lib.load()
     out = (C.c_uint32 * 6)()
-    be.lib.rt_last_launch_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
-    if be.lib.rt_last_launch_info(b.h, out) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_last_launch_info(b.h, out))
     return dict(zip(("workgroups", "threads", "lds_bytes", "bvh_nodes_in_lds", "bvh_nodes", "workgroups_per_cu"), [int(x) for x in out]))
 
 
 def last_kernel_ms(b: SceneBuilder) -> float:
-    be = _lib.load()
     ms = C.c_float()
-    if be.lib.rt_last_kernel_ms(b.h, C.byref(ms)) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_last_kernel_ms(b.h, C.byref(ms)))
     return float(ms.value)
 
 
 def last_stats(b: SceneBuilder) -> dict:
-    be = _lib.load()
     st = (C.c_ulonglong * 3)()
-    if be.lib.rt_last_stats(b.h, st) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_last_stats(b.h, st))
     return {"nonfinite_samples": int(st[0]), "wave_iterations": int(st[1]), "live_lane_iterations": int(st[2])}
 
 
 def format_image(rgb_sum: np.ndarray, spp: int) -> np.ndarray:
     """Vec3::format_color (src/vec.rs:125-131) over a whole frame -> (H, W, 3) uint8-range ints."""
-    be = _lib.load()
     H, W, _ = rgb_sum.shape
     out = np.zeros((H, W, 3), dtype=np.uint64)
     flat = np.ascontiguousarray(rgb_sum, dtype=np.float64).reshape(-1, 3)
     o = out.reshape(-1, 3)
-    fn = be.fn("format_color")
+    fn = _lib.load().fn("format_color")
     buf = (C.c_uint64 * 3)()
     for p in range(flat.shape[0]):
         fn(flat[p].ctypes.data_as(C.POINTER(C.c_double)), spp, buf)
@@ -431,8 +453,6 @@ def format_image(rgb_sum: np.ndarray, spp: int) -> np.ndarray:
 
 def write_ppm(path: str, rgb_sum: np.ndarray, spp: int) -> None:
     """The reference's P3 emitter (src/main.rs:767-769,832)."""
-    be = _lib.load()
     H, W, _ = rgb_sum.shape
     a = np.ascontiguousarray(rgb_sum, dtype=np.float64)
-    if be.lib.rt_write_ppm(path.encode(), a.ctypes.data, W, H, spp) != 0:
-        raise RenderError(_err(be))
+    _check(_rt().rt_write_ppm(path.encode(), a.ctypes.data, W, H, spp))

@@ -280,9 +280,6 @@ def load_image_rgb8(path: str):
         import ctypes as C
         from . import _lib
         lib = _lib.load().lib
-        lib.rt_decode_jpeg_rgb8.restype = C.c_void_p
-        lib.rt_decode_jpeg_rgb8.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        lib.rt_free.argtypes = [C.c_void_p]
         data = open(path, "rb").read()
         w, h = C.c_uint32(), C.c_uint32()
         ptr = lib.rt_decode_jpeg_rgb8(data, len(data), C.byref(w), C.byref(h))

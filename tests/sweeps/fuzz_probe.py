@@ -13,8 +13,6 @@ from test_fuzz_gpu import _rand_scene, SAMPLE_RTOL
 pbe, obe = _lib.load(), orc.load()
 earth = scenes.load_earthmap()
 W = H = 40; spp, depth = 8, 12
-pbe.lib.rt_debug_trace_path.argtypes = [C.c_void_p, C.c_longlong, C.c_longlong]
-pbe.lib.rt_debug_get_trace.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
 obe.lib.orc_trace_path.restype = C.c_int
 obe.lib.orc_trace_path.argtypes = [C.c_void_p, C.POINTER(CameraParams), C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int]
 for seed in [int(x) for x in sys.argv[1:]]:

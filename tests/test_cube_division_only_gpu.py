@@ -3,7 +3,6 @@ no bounds test after it.  The fast path runs for a WAVE only when all 64 of its 
 hostile (test_fuzz_gpu.test_list_search_ray_by_ray_on_hostile_rays) sends nearly every wave to the six exact tests.  Here the waves are
 made of the rays a frame is made of — camera rays and bounces off the surfaces they hit — so that the division-only form is what answers,
 and every answer is compared with the oracle's HittableList::hit bit for bit."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -34,12 +33,8 @@ def _cornell(be):
 def _room_clear(pbe, mn, mx, rays, t_min):
     """which rays the fast path calls clear against the box [mn, mx] with every face there (rt_debug_cube_hit)"""
     n = len(rays)
-    out = np.zeros((n, 4))
-    boxes = np.ascontiguousarray(np.tile(np.concatenate([mn, mx]), (n, 1)))
-    tl = np.ascontiguousarray(np.tile([t_min, np.inf], (n, 1)))
-    pbe.lib.rt_debug_cube_hit.restype = C.c_int
-    pbe.lib.rt_debug_cube_hit.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    assert pbe.lib.rt_debug_cube_hit(n, float(np.abs(boxes).max()) * 1.0000002, boxes.ctypes.data, rays.ctypes.data, tl.ctypes.data, out.ctypes.data) == 0
+    boxes = np.tile(np.concatenate([mn, mx]), (n, 1))
+    out = R.debug_cube_hit(boxes, rays, np.tile([t_min, np.inf], (n, 1)), float(np.abs(boxes).max()) * 1.0000002)
     return (out[:, 3].astype(int) & 8) != 0
 
 

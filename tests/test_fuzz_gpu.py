@@ -572,11 +572,8 @@ def _hostile_rays(rnd, n, mn, mx, planes_y=()):
 
 
 def _list_hits_gpu(pbe, b, rays, t_min):
-    import ctypes as C
     n = len(rays)
     out = np.zeros((n, 12))
-    pbe.lib.rt_debug_list_hit.restype = C.c_int
-    pbe.lib.rt_debug_list_hit.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     tm = np.full(n, t_min)
     assert pbe.lib.rt_debug_list_hit(b.h, n, rays.ctypes.data, tm.ctypes.data, out.ctypes.data) == 0, pbe.lib.rt_last_error()
     return out

@@ -99,21 +99,10 @@ def test_flatten_tables(pbe, earth):
     assert t["triangles"] == 1024 and t["bvh_nodes"] == 2047 and t["rects"] == 6 + 5 + 2 and t["objects"] == 3
 
 
-def _objects(pbe, b):
-    pbe.lib.rt_debug_objects.restype = C.c_int
-    pbe.lib.rt_debug_objects.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
-    n_top = C.c_uint32(0)
-    n = pbe.lib.rt_debug_objects(b.h, None, 0, C.byref(n_top))
-    assert n >= 0
-    out = np.zeros((max(n, 1), 8), np.uint32)
-    assert pbe.lib.rt_debug_objects(b.h, out.ctypes.data, n, C.byref(n_top)) == n
-    return out[:n], int(n_top.value)
-
-
 def test_object_table_of_the_cornell_box(pbe, monkeypatch):
     """rt_debug_objects: [FlipNormal(light)] [room: the five walls] [box] [box] — and, with RT_NO_ROOM, the list as the reference has it:
     [green, red] [FlipNormal(light)] [floor, ceiling, back] [box] [box] (runs of bare rects merge; a Cube and a FlipNormal-only chain are marked)."""
-    ob, n_top = _objects(pbe, build_scene("cornell", pbe)[0])
+    ob, n_top = R.debug_object_rows(build_scene("cornell", pbe)[0])
     assert n_top == 4 and len(ob) == 4 + 5
     reference_list = [(0, 2, 0, 0, 0), (0, 1, 1, 0, 0x10000), (0, 3, 0, 0, 0), (0, 6, 2, 1, 0), (0, 6, 2, 1, 0)]
     assert [tuple(int(x) for x in o[[0, 2, 4, 6, 7]]) for o in ob[4:]] == reference_list      # behind the world list: the list as the reference has it (world_hit's NaN-proof path)
@@ -127,7 +116,7 @@ def test_object_table_of_the_cornell_box(pbe, monkeypatch):
     # the tie rule: the light (new index 0) stood after the first two walls and before the other three (whose entry is the room's own index)
     assert [(int(room[3]) >> (5 * j)) & 31 for j in range(5)] == [0, 0, 1, 1, 1]
     monkeypatch.setenv("RT_NO_ROOM", "1")
-    ob, n_top = _objects(pbe, build_scene("cornell", pbe)[0])
+    ob, n_top = R.debug_object_rows(build_scene("cornell", pbe)[0])
     assert n_top == len(ob) == 5
     assert [tuple(int(x) for x in o[[0, 2, 4, 6, 7]]) for o in ob] == reference_list
 
@@ -432,32 +421,29 @@ def test_bvh_accepts_every_hittable_kind(kind, pbe, obe):
     c = R.flatten(b)
     n = c["bvh_nodes"]
     assert n == 2 * 7 - 1 + (3 * (2 * 3 - 1) if kind == "bvh" else 0)
-    links = (C.c_uint32 * (4 * n))(); roots = (C.c_uint32 * 8)(); n_roots = C.c_uint32(0)
-    assert pbe.lib.rt_debug_bvh_links(b.h, links, n, roots, 8, C.byref(n_roots)) == n
-    L = np.frombuffer(links, np.uint32).reshape(n, 4)
+    L, roots = R.debug_bvh_links(b)
+    assert len(L) == n
     LEAF = 1 << 31
     leaf_kinds = ((L[:, 0] >> 28) & 7)[(L[:, 0] & LEAF) != 0]
     assert (leaf_kinds == 5).sum() == (3 + 3 if kind == "bvh" else 3)          # G_OBJ: the three children (and, nested, one FlipNormal(Sphere) in each inner BVH)
-    assert n_roots.value == (4 if kind == "bvh" else 1)
+    assert len(roots) == (4 if kind == "bvh" else 1)
     # every sub-object belongs to exactly one G_OBJ leaf: the leaves' runs partition [n_top, n_objects) (a nested BVH's own leaves put
     # their sub-objects into the table while the BVH is being built as a sub-object of the outer leaf: the runs must not interleave)
-    objs, n_top = _objects(pbe, b)
+    objs, n_top = R.debug_object_rows(b)
     runs = sorted((int(a & 0x0FFFFFFF), int(cnt)) for a, cnt in L[((L[:, 0] & LEAF) != 0) & (((L[:, 0] >> 28) & 7) == 5)][:, :2])
     assert runs and runs[0][0] == n_top and all(x[0] + x[1] == y[0] for x, y in zip(runs, runs[1:])) and runs[-1][0] + runs[-1][1] == len(objs)
     assert sorted(r[1] for r in runs) == {"list": [3, 3, 3], "bvh": [1] * 6}.get(kind, [1, 1, 1])
     # 2 top-level objects; the sub-objects behind them: one per child (a list: its three items)
     assert c["objects"] == 2 + {"list": 9, "bvh": 3 + 3}.get(kind, 3)
-    eb = np.zeros((n, 6)); fm = C.c_float(0)
-    pbe.lib.rt_debug_filter_nodes.restype = C.c_int
-    pbe.lib.rt_debug_filter_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
-    assert pbe.lib.rt_debug_filter_nodes(b.h, None, None, eb.ctypes.data, n, C.byref(fm)) == n
+    _, _, eb, fm = R.debug_filter_nodes(b)
+    assert len(eb) == n
     box = np.zeros(6)
     assert obe.lib.orc_bounding_box(ob.h, oh.id, 0.0, 1.0, box.ctypes.data_as(C.POINTER(C.c_double))) == 1
     assert np.array_equal(eb[roots[0]].view(np.uint64), box.view(np.uint64)), (eb[roots[0]], box)
     if kind in ("rotate", "rotate_translate"):
-        assert np.abs(box).max() > 1e308 and fm.value == 0.0                   # quirk B3: all of space; no f32 filter over such a tree (the exact walk)
+        assert np.abs(box).max() > 1e308 and fm == 0.0                   # quirk B3: all of space; no f32 filter over such a tree (the exact walk)
     else:
-        assert fm.value >= 1.0
+        assert fm >= 1.0
 
 
 @pytest.mark.parametrize("name", ["random", "final", "teapot"])
@@ -465,16 +451,14 @@ def test_bvh_skip_links_thread_the_recursions_order(name, pbe, earth):
     """The kernels walk a BVH in the reference's order without a stack: `node = hit && inner ? left : skip` (rt_kernel.hip bvh_hit_ww; the f64 kernels' filtered walk threads the same links, bvh_hit_filt).
     For ANY pattern of box-test outcomes that walk must meet the nodes BVH::hit's recursion meets (src/bvh.rs:77-91: bbox, left, right),
     in the same order.  Checked on the flattened trees of the shipped scenes with all-hit, all-miss and random outcome patterns."""
-    be = pbe
     b, _, _ = build_scene(name, pbe, earth)
     n = R.flatten(b)["bvh_nodes"]
-    links = (C.c_uint32 * (4 * n))(); roots = (C.c_uint32 * 8)(); n_roots = C.c_uint32(0)
-    assert be.lib.rt_debug_bvh_links(b.h, links, n, roots, 8, C.byref(n_roots)) == n
-    L = np.frombuffer(links, np.uint32).reshape(n, 4)
+    L, roots = R.debug_bvh_links(b)
+    assert len(L) == n
     LEAF, DONE = 1 << 31, 0xFFFFFFFF
-    assert n_roots.value >= 1
+    assert len(roots) >= 1
     seen = np.zeros(n, bool)
-    for root in list(roots)[:n_roots.value]:
+    for root in roots:
         assert L[root, 3] == DONE
         for trial in range(4):
             rng = np.random.default_rng(trial)
@@ -508,35 +492,26 @@ def test_filter_tree_is_a_conservative_hierarchy_over_the_same_leaves(name, pbe,
     if tuned:
         # round 6: worlds that are ONE bare BVH get their contraction from a view's estimated pass rates (rt_flatten.cpp tune_filter_tree,
         # what rt_scene_calibrate and the synchronous renders do): the tree it leaves must pass the very same checks
-        pbe.lib.rt_debug_tune_filter.restype = C.c_int
-        pbe.lib.rt_debug_tune_filter.argtypes = [C.c_void_p, C.c_void_p]
-        before = np.zeros((n, 2), np.uint32)
-        pbe.lib.rt_debug_filter_nodes.restype = C.c_int
-        pbe.lib.rt_debug_filter_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
-        assert pbe.lib.rt_debug_filter_nodes(b.h, None, before.ctypes.data, None, n, None) == n
+        before = R.debug_filter_nodes(b)[1]
         assert pbe.lib.rt_debug_tune_filter(b.h, C.byref(cam)) == 1
-        after = np.zeros((n, 2), np.uint32)
-        assert pbe.lib.rt_debug_filter_nodes(b.h, None, after.ctypes.data, None, n, None) == n
+        after = R.debug_filter_nodes(b)[1]
+        assert len(before) == len(after) == n
         assert not np.array_equal(before, after)                               # another set of nodes left the tree
         for other in ("final", "teapot", "cornell"):                           # scenes whose BVHs stand beside other objects (or have none) are left alone
             ob, ocam, _ = build_scene(other, pbe, earth)
             R.flatten(ob)
             assert pbe.lib.rt_debug_tune_filter(ob.h, C.byref(ocam)) == 0
-    links = (C.c_uint32 * (4 * n))(); roots = (C.c_uint32 * 8)(); n_roots = C.c_uint32(0)
-    assert pbe.lib.rt_debug_bvh_links(b.h, links, n, roots, 8, C.byref(n_roots)) == n
-    L = np.frombuffer(links, np.uint32).reshape(n, 4)
-    fb = np.zeros((n, 6), np.float32); fl = np.zeros((n, 2), np.uint32); eb = np.zeros((n, 6)); fm = C.c_float(0)
-    pbe.lib.rt_debug_filter_nodes.restype = C.c_int
-    pbe.lib.rt_debug_filter_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
-    assert pbe.lib.rt_debug_filter_nodes(b.h, fb.ctypes.data, fl.ctypes.data, eb.ctypes.data, n, C.byref(fm)) == n
+    L, roots = R.debug_bvh_links(b)
+    fb, fl, eb, fm = R.debug_filter_nodes(b)
+    assert len(L) == len(fb) == n
     LEAF, FLEAF, DONE = 1 << 31, 0x40000000, 0xFFFFFFFF
     # (1)
     assert (fb[:, 0::2].astype(np.float64) <= eb[:, :3]).all() and (fb[:, 1::2].astype(np.float64) >= eb[:, 3:]).all()
-    assert fm.value >= max(1.0, float(np.abs(fb).max())) and fm.value <= 2.0 ** 40
+    assert fm >= max(1.0, float(np.abs(fb).max())) and fm <= 2.0 ** 40
     is_leaf = (L[:, 0] & LEAF) != 0
     assert np.array_equal((fl[:, 1] & FLEAF) != 0, is_leaf) and np.array_equal(fl[is_leaf, 1] & ~np.uint32(FLEAF), np.flatnonzero(is_leaf).astype(np.uint32))
     visited_inner = set()
-    for root in list(roots)[:n_roots.value]:
+    for root in roots:
         want = []                                                  # the reference's leaves in depth-first order (bvh.rs:77-91)
         todo = [int(root)]
         while todo:

@@ -14,9 +14,6 @@ from raytracinginrust_amd import scenes
 
 
 def _decode(lib, data: bytes):
-    lib.rt_decode_jpeg_rgb8.restype = C.c_void_p
-    lib.rt_decode_jpeg_rgb8.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-    lib.rt_free.argtypes = [C.c_void_p]
     w, h = C.c_uint32(), C.c_uint32()
     ptr = lib.rt_decode_jpeg_rgb8(data, len(data), C.byref(w), C.byref(h))
     if not ptr:
@@ -27,10 +24,6 @@ def _decode(lib, data: bytes):
 
 
 def _parse_obj(lib, data: bytes, offset=(0.0, 0.0, 0.0), scale=1.0):
-    lib.rt_parse_obj.restype = C.c_int
-    lib.rt_parse_obj.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.c_double, C.POINTER(C.POINTER(C.c_double)),
-                                 C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.c_uint32)]
-    lib.rt_free.argtypes = [C.c_void_p]
     pos, idx = C.POINTER(C.c_double)(), C.POINTER(C.c_uint32)()
     n_pos, n_idx = C.c_uint32(), C.c_uint32()
     rc = lib.rt_parse_obj(data, len(data), (C.c_double * 3)(*offset), scale, C.byref(pos), C.byref(n_pos), C.byref(idx), C.byref(n_idx))
@@ -93,8 +86,6 @@ def test_mesh_load_obj_errors_do_not_crash(pbe, tmp_path):
     b = SceneBuilder(pbe)
     m = b.Lambertian(b.ConstantTexture((1, 1, 1)))
     lib = pbe.lib
-    lib.rt_mesh_load_obj.restype = C.c_int
-    lib.rt_mesh_load_obj.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.c_double, C.c_int]
     off = (C.c_double * 3)(0, 0, 0)
     assert lib.rt_mesh_load_obj(b.h, str(tmp_path / "missing.obj").encode(), off, 1.0, m.id) < 0          # the reference: Err -> unwrap panic
     assert b"Failed to load obj file" in lib.rt_last_error()

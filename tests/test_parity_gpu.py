@@ -714,7 +714,6 @@ def test_aabb_hit_on_the_device_against_the_oracle(pbe, obe):
     """AABB::hit (src/aabb.rs:19-36) on the device vs the oracle's, on random and on hostile inputs: rays through box corners and
     along faces, zero direction components (1/d = inf, 0 * inf = NaN which f64::max / min ignore), infinite / NaN origins, inverted
     boxes.  The traversal's NaN-free form must agree with the reference's form wherever it may be used (tame ray, min <= max)."""
-    import ctypes as C
     rnd = np.random.default_rng(7)
     n = 20000
     lo = rnd.uniform(-10, 10, (n, 3)); ext = rnd.uniform(0, 5, (n, 3))
@@ -732,12 +731,7 @@ def test_aabb_hit_on_the_device_against_the_oracle(pbe, obe):
         elif which == 4: boxes[i, k], boxes[i, 3 + k] = boxes[i, 3 + k], boxes[i, k] - 1.0   # inverted box
         else: o[i] = boxes[i, :3]; d[i] = boxes[i, 3:] - boxes[i, :3]             # through two corners
     rays = np.concatenate([o, d], axis=1)
-    out = np.zeros(n, dtype=np.int32)
-    lib = pbe.lib
-    lib.rt_debug_aabb_hit.restype = C.c_int
-    lib.rt_debug_aabb_hit.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    boxes, rays, tl = (np.ascontiguousarray(x, dtype=np.float64) for x in (boxes, rays, tl))
-    assert lib.rt_debug_aabb_hit(n, boxes.ctypes.data, rays.ctypes.data, tl.ctypes.data, out.ctypes.data) == 0
+    out = R.debug_aabb_hit(boxes, rays, tl)
     from oracle import orc
     d3 = lambda v: orc._d(*v)
     ref = np.array([obe.lib.orc_aabb_hit(d3(boxes[i, :3]), d3(boxes[i, 3:]), d3(rays[i, :3]), d3(rays[i, 3:]), tl[i, 0], tl[i, 1]) for i in range(n)])
@@ -843,16 +837,12 @@ def test_view_tuned_filter_tree_is_scheduling_only(pbe, monkeypatch):
     first synchronous render of a view, or by rt_scene_calibrate (rt_host.cpp tune_for_view, rt_flatten.cpp tune_filter_tree).  Any
     conservative hierarchy over the leaves gives the reference's samples: every sample bit-identical with the area rule's tree
     (RT_NO_FILTER_TUNING), for the view the tree was tuned for and for another one; the asynchronous entry point keeps the tree it finds."""
-    import ctypes as C
     W, H, spp, depth = 64, 48, 8, 8
-    lib = pbe.lib
-    lib.rt_debug_filter_nodes.restype = C.c_int
-    lib.rt_debug_filter_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
 
     def links(b):
         n = R.flatten(b)["bvh_nodes"]
-        fl = np.zeros((n, 2), np.uint32)
-        assert lib.rt_debug_filter_nodes(b.h, None, fl.ctypes.data, None, n, None) == n
+        fl = R.debug_filter_nodes(b)[1]
+        assert len(fl) == n
         return fl
 
     monkeypatch.setenv("RT_NO_FILTER_TUNING", "1")
@@ -995,7 +985,6 @@ def test_box_filter_is_conservative_on_grazing_rays(pbe):
     of the box size, boxes far from the origin (coordinates up to 1e6: the f32 grid is coarse there), thin boxes (the reference's
     0.0001-thick rect boxes), and [t_min, t_max] ending within a few ulps of the entry / exit distance.  Checked against the exact
     form on the device, which test_aabb_hit_on_the_device_against_the_oracle ties to the oracle."""
-    import ctypes as C
     rnd = np.random.default_rng(11)
     n = 400000
     scale = 10.0 ** rnd.uniform(-2, 6, (n, 1))
@@ -1017,12 +1006,7 @@ def test_box_filter_is_conservative_on_grazing_rays(pbe):
     tmin = np.where(rnd.integers(0, 3, n) == 0, t_hit * (1.0 + rnd.choice([-4, -1, 0, 1, 4], n) * 2.0 ** -52), 1e-5)
     tl = np.stack([tmin, tmax], axis=1)
     rays = np.concatenate([o, d], axis=1)
-    out = np.zeros(n, dtype=np.int32)
-    lib = pbe.lib
-    lib.rt_debug_aabb_hit.restype = C.c_int
-    lib.rt_debug_aabb_hit.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    boxes, rays, tl = (np.ascontiguousarray(x, dtype=np.float64) for x in (boxes, rays, tl))
-    assert lib.rt_debug_aabb_hit(n, boxes.ctypes.data, rays.ctypes.data, tl.ctypes.data, out.ctypes.data) == 0
+    out = R.debug_aabb_hit(boxes, rays, tl)
     use = ((out & 4) != 0) & ((out & 8) != 0)
     assert use.sum() > 0.9 * n
     exact = (out & 1) != 0
@@ -1084,18 +1068,13 @@ def test_cube_fast_path_against_the_six_rect_tests(pbe, obe):
     no hit.  Cases aimed at where it could go wrong: rays through points on faces, edges and corners moved by 1e-15 ... 1e-3 of the
     cube, origins on a face (every bounce off a cube), inside the cube, far away; thin and tiny cubes; cubes far from the origin;
     [t_min, t_max] ending within ulps of a hit; axis-parallel rays (zero direction components: never clear)."""
-    import ctypes as C
     rnd = np.random.default_rng(23)
     n = 600000
     boxes, rays, tl, about = _cube_kat_cases(rnd, n)
     kind, axis_par, tiny, thin, tmax, tmin = (about[k] for k in ("kind", "axis_par", "tiny", "thin", "tmax", "tmin"))
-    out = np.zeros((n, 4))
-    lib = pbe.lib
-    lib.rt_debug_cube_hit.restype = C.c_int
-    lib.rt_debug_cube_hit.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     boxes, rays, tl = (np.ascontiguousarray(x, dtype=np.float64) for x in (boxes, rays, tl))
     rect_m = float(np.abs(boxes).max()) * 1.0000002
-    assert lib.rt_debug_cube_hit(n, rect_m, boxes.ctypes.data, rays.ctypes.data, tl.ctypes.data, out.ctypes.data) == 0
+    out = R.debug_cube_hit(boxes, rays, tl, rect_m)
     t_ref, face_ref, t_fast, code = out[:, 0], out[:, 1].astype(int), out[:, 2], out[:, 3].astype(int)
     clear = (code & 8) != 0
     face_fast = (code & 7) - 1
@@ -1116,7 +1095,7 @@ def test_cube_fast_path_against_the_six_rect_tests(pbe, obe):
     differ = (face_orc != face_ref) | ((t_orc.view(np.uint64) != t_ref.view(np.uint64)) & ~(np.isnan(t_orc) & np.isnan(t_ref)))
     assert not differ.any(), f"{int(differ.sum())} cases: the device's six rect tests differ from the oracle's Cube::hit, e.g. case {int(np.flatnonzero(differ)[0])}"
     # the same cubes with the scene-wide bound far larger than their own coordinates (other rects of the scene): still exact
-    assert lib.rt_debug_cube_hit(n, rect_m * 1000.0, boxes.ctypes.data, rays.ctypes.data, tl.ctypes.data, out.ctypes.data) == 0
+    out = R.debug_cube_hit(boxes, rays, tl, rect_m * 1000.0)
     clear2 = (out[:, 3].astype(int) & 8) != 0
     bad2 = clear2 & (((out[:, 3].astype(int) & 7) - 1 != out[:, 1].astype(int)) | (out[:, 2].view(np.uint64) != out[:, 0].view(np.uint64)) & ~(np.isnan(out[:, 2]) & np.isnan(out[:, 0])))
     assert not bad2.any()
@@ -1131,7 +1110,6 @@ def test_room_form_of_the_cube_fast_path_against_the_walls_rect_tests(pbe, obe):
     path declares a case CLEAR its answer must be HittableList::hit's over the rects of the faces that exist, bit for bit — the entry face
     if it exists and is in range, else the exit face if it exists and is in range, else no hit — and the device's exact side IS the
     oracle's list over those AARects (orc_room_hit_batch) on every case.  With all six faces the room form must say what the Cube form says."""
-    import ctypes as C
     rnd = np.random.default_rng(29)
     n = 600000
     boxes, rays, tl, about = _cube_kat_cases(rnd, n)
@@ -1140,13 +1118,9 @@ def test_room_form_of_the_cube_fast_path_against_the_walls_rect_tests(pbe, obe):
     masks[rnd.integers(0, 5, n) == 0] = 0x3D                                    # the Cornell room of main.rs:291-296: everything but the face at min z, the open front
     masks[rnd.integers(0, 10, n) == 0] = 0x3E                                   # ... but the one at max z
     masks[rnd.integers(0, 20, n) == 0] = 0x3F                                   # all six
-    out = np.zeros((n, 4))
-    lib = pbe.lib
-    lib.rt_debug_room_hit.restype = C.c_int
-    lib.rt_debug_room_hit.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     boxes, rays, tl = (np.ascontiguousarray(x, dtype=np.float64) for x in (boxes, rays, tl))
     rect_m = float(np.abs(boxes).max()) * 1.0000002
-    assert lib.rt_debug_room_hit(n, rect_m, boxes.ctypes.data, rays.ctypes.data, tl.ctypes.data, masks.ctypes.data, out.ctypes.data) == 0
+    out = R.debug_room_hit(boxes, rays, tl, rect_m, masks)
     t_ref, face_ref, t_fast, code = out[:, 0].copy(), out[:, 1].astype(int), out[:, 2].copy(), out[:, 3].astype(int)
     clear = (code & 8) != 0
     face_fast = (code & 7) - 1
@@ -1166,10 +1140,7 @@ def test_room_form_of_the_cube_fast_path_against_the_walls_rect_tests(pbe, obe):
     differ = (face_orc != face_ref) | ((t_orc.view(np.uint64) != t_ref.view(np.uint64)) & ~(np.isnan(t_orc) & np.isnan(t_ref)))
     assert not differ.any(), f"{int(differ.sum())} cases: the device's wall tests differ from the oracle's list, e.g. case {int(np.flatnonzero(differ)[0])}"
     # an absent face matters: among the clear cases some hit the exit face BECAUSE the entry face does not exist, some nothing at all
-    full = np.zeros((n, 4))
-    lib.rt_debug_cube_hit.restype = C.c_int
-    lib.rt_debug_cube_hit.argtypes = [C.c_uint32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    assert lib.rt_debug_cube_hit(n, rect_m, boxes.ctypes.data, rays.ctypes.data, tl.ctypes.data, full.ctypes.data) == 0
+    full = R.debug_cube_hit(boxes, rays, tl, rect_m)
     cube_face = (full[:, 3].astype(int) & 7) - 1
     cube_clear = (full[:, 3].astype(int) & 8) != 0
     both = clear & cube_clear

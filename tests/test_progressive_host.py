@@ -23,8 +23,6 @@ def _state(lib, seed, pixel, sample):
 
 def test_seed_fold_identity(pbe):
     lib = pbe.lib
-    lib.rt_rng_path.restype = None
-    lib.rt_rng_path.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]
     rng = np.random.default_rng(20240607)
     cases = []
     for _ in range(2000):

@@ -31,7 +31,7 @@ for spec in a.libs:
     path, vflags = parts[0], int(parts[1]) if len(parts) > 1 and parts[1] else 0
     venv = dict(kv.split('=') for kv in parts[2].split(';')) if len(parts) > 2 and parts[2] else {}
     path = os.path.abspath(path)
-    be = _loaded.get(path) or _lib.load_path(path)
+    be = _loaded.get(path) or _lib.load_path(path, allow_missing=True)
     _loaded[path] = be
     b, cam, bg = build(be)
     variants.append((name, be, b, cam, bg, vflags, venv))

@@ -16,7 +16,7 @@ def build(be):
 ref = None
 for spec in a.libs:
     name, path = spec.split('=', 1)
-    be = _lib.load_path(os.path.abspath(path))
+    be = _lib.load_path(os.path.abspath(path), allow_missing=True)
     b, cam, bg = build(be)
     W = H = a.size
     out = np.zeros((H, W, 3)); smp = np.zeros((H, W, a.spp, 3))

@@ -14,7 +14,7 @@ rows = []
 vs = []
 for spec in a.libs:
     name, path = spec.split('=', 1)
-    be = _lib.load_path(os.path.abspath(path)); b, cam, bg = scenes.cornell_box(be)
+    be = _lib.load_path(os.path.abspath(path), allow_missing=True); b, cam, bg = scenes.cornell_box(be)
     vs.append((name, be, b, cam, bg))
 res = {v[0]: [] for v in vs}
 for r in range(a.rounds + 1):

@@ -91,11 +91,9 @@ for name in (sys.argv[1:] or ["final", "random", "teapot"]):
     cnt = np.zeros((n, 2), np.uint64)
     assert lib.rt_debug_node_counts(b.h, cnt.ctypes.data, n) == n
     os.environ.pop('RT_NODE_COUNTS'); os.environ.pop('RT_COLLAPSE_TAU')
-    links = (C.c_uint32 * (4 * n))(); roots = (C.c_uint32 * 16)(); nr = C.c_uint32(0)
-    lib.rt_debug_bvh_links(b.h, links, n, roots, 16, C.byref(nr))
-    L = np.frombuffer(links, np.uint32).reshape(n, 4)
+    L, roots = R.debug_bvh_links(b)
     inner = (L[:, 0] & (1 << 31)) == 0
-    is_root = np.zeros(n, bool); is_root[list(roots)[:nr.value]] = True
+    is_root = np.zeros(n, bool); is_root[roots] = True
     visits, passes = cnt[:, 0].astype(np.float64), cnt[:, 1].astype(np.float64)
     rate = np.where(visits > 0, passes / np.maximum(visits, 1), 0.0)
     print(f"== {name}: {n} nodes, {int(inner.sum())} inner; box tests per frame {visits.sum():.3e}, passed {passes.sum() / visits.sum():.3f}; "
@@ -104,14 +102,11 @@ for name in (sys.argv[1:] or ["final", "random", "teapot"]):
     print(f"   no contraction            {base_ms:9.3f} ms")
     area_ms, _ = timed(name, {}, want=want)
     print(f"   area rule, tau = 0.75     {area_ms:9.3f} ms   ({(base_ms / area_ms - 1) * 100:+.1f} % vs none)")
-    eb = np.zeros((n, 6)); fm = C.c_float(0)
-    lib.rt_debug_filter_nodes.restype = C.c_int
-    lib.rt_debug_filter_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
-    lib.rt_debug_filter_nodes(b.h, None, None, eb.ctypes.data, n, C.byref(fm))
+    eb = R.debug_filter_nodes(b)[2]
     from raytracinginrust_amd.api import camera_fields
     cam21 = camera_fields(be, cam)
     for label, kw in (("no view", {}), ("half of the rays are the view's primary rays", {"cam21": cam21}), ("primary rays only", {"cam21": cam21, "cam_share": 1.0})):
-        hv, hp = host_estimate(L, eb, list(roots)[:nr.value], **kw)
+        hv, hp = host_estimate(L, eb, roots, **kw)
         hrate = np.where(hv > 0, hp / np.maximum(hv, 1), 0.0)
         both = inner & ~is_root & (visits > 0) & (hv > 0)
         print(f"   host estimate (3000 rays, {label}): correlation with the measured pass rates {np.corrcoef(rate[both], hrate[both])[0, 1]:.3f}")

@@ -11,7 +11,7 @@ from test_fuzz_gpu import _rand_scene
 libs = [a.split('=', 1) for a in sys.argv[1:] if '=' in a]
 seeds = [int(a) for a in sys.argv[1:] if '=' not in a]
 assert len(libs) == 2 and seeds, __doc__
-backends = [(n, _lib.load_path(os.path.abspath(p))) for n, p in libs]
+backends = [(n, _lib.load_path(os.path.abspath(p), allow_missing=True)) for n, p in libs]
 earth = scenes.load_earthmap()
 W = H = 40; spp, depth = 8, 12                 # the sweep's frame
 total = 0
