@@ -166,6 +166,49 @@ inline void write_ppm(const char* path, const std::vector<double>& rgb_sum, uint
     if (rt_write_ppm(path, rgb_sum.data(), W, H, spp) != 0) throw Error(rt_last_error());
 }
 
+// Ray queries (rt_query_*): `world.hit(&r, 0.00001, f64::INFINITY)` (src/main.rs:48) as a call — the closest hit of rays of the caller's, or
+// of the camera rays of one sample of every pixel (picking, auto-focus, depth / normal / material-id frames).  Hit is HitRecord
+// (src/hit.rs:9-24) plus what identifies the thing that was hit; `material` is the id of the Material the builder returned (-1: a
+// ConstantMedium's, or a miss), `object` the index in the flattened object table, prim_kind 0 rect, 1 sphere, 2 moving sphere, 3 triangle
+// (-1: a medium, or a miss).
+struct Hit {
+    bool hit = false; double t = 0.0; Point3 position; Vec3 normal; bool front_face = false; double u = 0.0, v = 0.0;
+    int material = -1, object = -1, prim_kind = -1, prim_index = -1;
+    static Hit from_record(const double* r) {
+        Hit h; h.hit = r[0] != 0.0; h.t = r[1]; h.position = Point3(r[2], r[3], r[4]); h.normal = Vec3(r[5], r[6], r[7]); h.front_face = r[8] != 0.0;
+        h.u = r[9]; h.v = r[10]; h.material = (int)r[11]; h.object = (int)r[12]; h.prim_kind = (int)r[13]; h.prim_index = (int)r[14];
+        return h;
+    }
+};
+struct Ray { Point3 origin; Vec3 direction; double time = 0.0; };        // src/ray.rs:6-10
+// world.hit(ray, t_min, +inf) for every ray; ray k draws from the stream Rng(seed, k) where a ConstantMedium needs a random number
+inline std::vector<Hit> query_hits(Scene& s, const std::vector<Ray>& rays, double t_min = 0.00001, uint64_t seed = 0) {
+    std::vector<double> in(rays.size() * 7), rec(rays.size() * 16);
+    for (size_t k = 0; k < rays.size(); k++) {
+        for (int a = 0; a < 3; a++) { in[k * 7 + a] = rays[k].origin.e[a]; in[k * 7 + 3 + a] = rays[k].direction.e[a]; }
+        in[k * 7 + 6] = rays[k].time;
+    }
+    if (rt_query_hits(s.raw(), (uint32_t)rays.size(), in.data(), t_min, seed, 0, rec.data()) != 0) throw Error(rt_last_error());
+    std::vector<Hit> out(rays.size());
+    for (size_t k = 0; k < rays.size(); k++) out[k] = Hit::from_record(&rec[k * 16]);
+    return out;
+}
+// The camera ray of sample `sample` of every pixel — the ray a frame with that seed traces — and its closest hit: W*H hits in output
+// order (row 0 = top); rays_out (optional) receives the rays.
+inline std::vector<Hit> query_camera(Scene& s, const Camera& cam, uint32_t W, uint32_t H, uint32_t sample = 0, uint64_t seed = 0x5EED,
+                                     std::vector<Ray>* rays_out = nullptr) {
+    const size_t n = (size_t)W * H;
+    std::vector<double> rec(n * 16), rays(rays_out ? n * 7 : 0);
+    if (rt_query_camera(s.raw(), &cam.c, W, H, sample, seed, 0, rays_out ? rays.data() : nullptr, rec.data()) != 0) throw Error(rt_last_error());
+    std::vector<Hit> out(n);
+    for (size_t k = 0; k < n; k++) out[k] = Hit::from_record(&rec[k * 16]);
+    if (rays_out) {
+        rays_out->resize(n);
+        for (size_t k = 0; k < n; k++) { Ray& r = (*rays_out)[k]; r.origin = Point3(rays[k * 7], rays[k * 7 + 1], rays[k * 7 + 2]); r.direction = Vec3(rays[k * 7 + 3], rays[k * 7 + 4], rays[k * 7 + 5]); r.time = rays[k * 7 + 6]; }
+    }
+    return out;
+}
+
 // A progressive frame (rt_progressive_*): the same loop in passes of samples that accumulate on the device, with the reference's
 // format_color (src/vec.rs:125-131) resolved there too — progress, preview, stop half-way, "another 1000 samples", save and resume.
 class Progressive {

@@ -239,6 +239,40 @@ int rt_progressive_load_sum(void* frame, const double* rgb_sum, uint64_t samples
 int rt_progressive_reset(void* frame);
 void rt_progressive_destroy(void* frame);                                  /* waits for the frame's work; the scene may be gone already */
 
+/* ---- ray queries: the reference's `world.hit(r, 0.00001, f64::INFINITY)` (src/main.rs:48, Hittable::hit) as a function of its own — the
+ *      closest hit of rays the caller chooses, or of the camera rays of one sample of every pixel: which object is under pixel (i, j), how far
+ *      away it is (auto-focus), depth / normal / material-id frames for a denoiser or a compositor, visibility probes.  The search and the
+ *      record are the frames' own device code (csrc/rt_query.hip), for every kind of scene; no shading.  f64 and the reference's traversal
+ *      order only: `flags` must be 0 (RT_F32 and every other flag are an error); t_max is +inf; one device, the current one.
+ * A ray is 7 doubles: origin[3], direction[3], time.  Non-finite and zero direction components are legal.
+ * A hit record is 16 doubles (128 bytes): [0] hit (0 / 1), [1] t, [2..4] position, [5..7] normal, [8] front_face, [9], [10] u, v — computed
+ * where the hit's material reads them (only an ImageTexture does, as in the frames), 0 elsewhere —, [11] the material handle rt_material_*
+ * returned (handles are indices of the scene's material table; a ConstantMedium hit reports -1: its Isotropic is made by the flattener and
+ * has no handle), [12] the object's index in the flattened object table as rt_debug_objects numbers it, [13] the primitive kind (0 rect,
+ * 1 sphere, 2 moving sphere, 3 triangle, -1 medium), [14] the index in that primitive pool (-1 medium), [15] 0.  A miss is [0] = 0,
+ * [11..14] = -1 and the rest 0.
+ * The host forms are synchronous.  The _device forms take DEVICE pointers, 16-byte aligned, only enqueue on hip_stream (a hipStream_t, may be
+ * NULL) and never wait.  A scene not yet prepared is flattened and uploaded first, as rt_render_device does it.  Errors (non-zero, a message
+ * for rt_last_error, nothing launched): null arguments, flags != 0, d_hits_bytes < 128 bytes per record, W < 2 or H < 2, W*H > 2^31 - 1, no
+ * HIP device (there is no CPU path).  n = 0 returns 0 and touches nothing.  Queries leave what rt_last_kernel_ms and friends report alone. */
+/* Camera::get_ray for sample `sample` of pixel (i, j), j counted from the BOTTOM row as main.rs:811-820 does: the draws of
+ * rng_for_path(seed, (H-1-j)*W + i, sample) in the kernels' order (refill_queue): u, v, lens disk (rejection loop), time.
+ * Host only, no GPU.  ray_out = origin[3], direction[3], time. */
+int rt_camera_ray(const rt_camera*, uint32_t W, uint32_t H, uint32_t i, uint32_t j, uint64_t seed, uint32_t sample, double ray_out[7]);
+/* world.hit(ray, t_min, +inf) for n caller rays: rays = n x 7 (origin[3], direction[3], time), hits_out = n x 16 doubles.  ConstantMedium::hit
+ * draws a random number (src/medium.rs:28): ray k draws from the stream of rt_rng_create(seed, k). */
+int rt_query_hits(rt_scene*, uint32_t n, const double* rays, double t_min, uint64_t seed, uint32_t flags, double* hits_out);
+int rt_query_hits_device(rt_scene*, uint32_t n, const void* d_rays, double t_min, uint64_t seed, uint32_t flags,
+                         void* d_hits_out, size_t d_hits_bytes, void* hip_stream);
+/* The camera ray of sample `sample` of every pixel, generated ON THE DEVICE (the very ray a frame with that seed traces for that
+ * sample), and its closest hit with t_min = 0.00001: the path's own stream simply continues after the camera's draws, so the hit is the one
+ * a frame finds at depth 0.  W*H records in output order (row 0 = top).  rays_out may be NULL (else W*H*7). */
+int rt_query_camera(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t sample, uint64_t seed, uint32_t flags,
+                    double* rays_out, double* hits_out);
+int rt_query_camera_device(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t sample, uint64_t seed, uint32_t flags,
+                           void* d_rays_out, void* d_hits_out, size_t d_hits_bytes, void* hip_stream);
+int rt_last_query_ms(rt_scene*, float* ms_out);   /* HIP events around the most recent query kernel of this scene; waits */
+
 /* The whole frame on several GPUs of this node from ONE call: what a host that owns the node's GPUs itself (the reference's `main`,
  * src/main.rs:767-835) calls instead of rt_render.  device_mask: bit d selects HIP device d (0 = every visible device).  The scene
  * is replicated on each selected device; tiles of tile_px output-order pixels (0 = the default, 67) are dealt round-robin, each

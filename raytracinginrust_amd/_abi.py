@@ -104,6 +104,13 @@ SIGNATURES = {
     "progressive_load_sum": (_int, [_ptr, _ptr, _u64]),
     "progressive_reset": (_int, [_ptr]),
     "progressive_destroy": (None, [_ptr]),
+    # ray queries
+    "camera_ray": (_int, [_cam_p, _u32, _u32, _u32, _u32, _u64, _u32, c_double_p]),
+    "query_hits": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _ptr]),
+    "query_hits_device": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _ptr, C.c_size_t, _ptr]),
+    "query_camera": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u64, _u32, _ptr, _ptr]),
+    "query_camera_device": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u64, _u32, _ptr, _ptr, C.c_size_t, _ptr]),
+    "last_query_ms": (_int, [_ptr, c_float_p]),
     "render_multi": (_int, _FRAME + [_u32, _u32, _ptr]),
     "render_multi_device": (_int, _FRAME + [_u32, _u32, c_void_pp]),
     "multi_sync": (_int, [_ptr]),

@@ -204,6 +204,7 @@ class SceneBuilder:
 
     def set_scene(self, world: Handle, lights: Sequence[Handle]):
         """The `(world, lights)` pair a scene fn returns (src/main.rs:153)."""
+        self.world = world          # (kept for callers that ask about the world object itself: function-level checks against an oracle)
         if self._call("scene_set_world", world.id) < 0:
             raise SceneError(self.b.fn("scene_error")(self.h).decode())
         for l in lights:

@@ -15,6 +15,7 @@
 #include "rt_launch.h"
 #include "rt_device.h"
 #include "rt_resolve.h"
+#include "rt_query.h"
 
 using namespace rt;
 
@@ -84,6 +85,11 @@ void rt_scene_destroy(rt_scene* sc) {
     rt::multi_release(sc->s);
     free_on_device(sc->s.d_trace, sc->s.trace_device);
     free_on_device(sc->s.d_calib, sc->s.calib_device);
+    if (sc->s.q_ev[0]) {
+        DeviceGuard guard(sc->s.q_device);
+        if (sc->s.q_recorded) (void)hipEventSynchronize((hipEvent_t)sc->s.q_ev[1]);
+        (void)hipEventDestroy((hipEvent_t)sc->s.q_ev[0]); (void)hipEventDestroy((hipEvent_t)sc->s.q_ev[1]);
+    }
     for (Scene::DeviceCtx* c : sc->s.ctxs) {
         DeviceGuard guard(c->device);
         free_device_scene(c->dev64);
@@ -632,6 +638,15 @@ template <typename T> void bind_tables(KParams<T>& P, const DeviceScene<T>& d, c
     P.perlins = (const DPerlin<T>*)d.perlins; P.pbr = (const DPbr<T>*)d.pbr; P.image_bytes = (const uint8_t*)d.image;
 }
 
+// KParams::bvh_tame for the tables of precision T (the f32 tables are rounded copies: the bound is checked at the precision that is
+// uploaded).  Without it every walk is the slow exact one.
+template <typename T> uint32_t tables_are_tame(const HostFlat& f) {
+    const double big = sizeof(T) == 8 ? 1e300 : 1e30;
+    bool tame = f.bvh_tame;
+    for (const DBvhNode<double>& nd : f.bvh) for (int k = 0; k < 3 && tame; k++) tame = std::fabs(nd.mn[k]) < big && std::fabs(nd.mx[k]) < big;
+    return tame ? 1u : 0u;
+}
+
 // f<float> or f<double>, as the caller's flags ask
 #define BY_PRECISION(flags, f, ...) (((flags) & RT_F32) ? f<float>(__VA_ARGS__) : f<double>(__VA_ARGS__))
 
@@ -648,12 +663,7 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     KParams<T> P;
     std::memset((void*)&P, 0, sizeof(P));
     bind_tables(P, d, f);
-    {   // the f32 tables are rounded copies: the tame bound is checked at the precision that is uploaded
-        const double big = sizeof(T) == 8 ? 1e300 : 1e30;
-        bool tame = f.bvh_tame;
-        for (const DBvhNode<double>& nd : f.bvh) for (int k = 0; k < 3 && tame; k++) tame = std::fabs(nd.mn[k]) < big && std::fabs(nd.mx[k]) < big;
-        P.bvh_tame = tame ? 1u : 0u;
-    }
+    P.bvh_tame = tables_are_tame<T>(f);
     rt_camera_args ca; std::memcpy(&ca, camp, sizeof(ca));
     DCamera<double> cam; camera_new(ca, cam);
     for (int k = 0; k < 3; k++) {
@@ -1092,6 +1102,169 @@ int rt_debug_get_trace(rt_scene* sc, double* out, uint32_t n_levels) {
     DeviceGuard guard(sc->s.trace_device);
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(out, sc->s.d_trace, (size_t)n_levels * 16u * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---------------------------------------------------------------- ray queries
+// world.hit (main.rs:48) for rays the caller chooses, or for the camera rays of one sample of every pixel (csrc/rt_query.hip).
+// Camera::get_ray for one sample of one pixel on the host: the arithmetic of the kernels' camera code (rt_kernel.hip refill_queue,
+// rt_query.hip camera_ray) in the same order, with the same draws; this file is compiled without contraction, as they are.
+int rt_camera_ray(const rt_camera* camp, uint32_t W, uint32_t H, uint32_t i, uint32_t j, uint64_t seed, uint32_t sample, double ray_out[7]) {
+    if (!camp || !ray_out) return set_err("null argument");
+    if (W < 2 || H < 2) return set_err("W and H must be >= 2 (u,v divide by W-1 and H-1, src/main.rs:817-818)");
+    if ((uint64_t)W * H > 0x7FFFFFFFull) return set_err("frame too large: W*H must be <= 2^31 - 1 (per-path RNG keys, csrc/rt_rng.h)");
+    if (i >= W || j >= H) return set_err("rt_camera_ray: pixel (i, j) outside the W x H frame");
+    rt_camera_args ca; std::memcpy(&ca, camp, sizeof(ca));
+    DCamera<double> cam; camera_new(ca, cam);
+    Rng g = rng_for_path(seed, (H - 1u - j) * W + i, sample);
+    const double random_u = rng_u01(g, 0.0);
+    const double random_v = rng_u01(g, 0.0);
+    const double u = ((double)i + random_u) / (double)(W - 1u);
+    const double v = ((double)j + random_v) / (double)(H - 1u);
+    double da, db;
+    for (;;) {                                                          // random_in_unit_disk, vec.rs:96-105
+        da = rng_range(g, -1.0, 1.0);
+        db = rng_range(g, -1.0, 1.0);
+        if (da * da + db * db + 0.0 * 0.0 < 1.0) break;
+    }
+    const double rdx = cam.lens_radius * da, rdy = cam.lens_radius * db;
+    const double time = cam.time0 + rng_u01(g, 0.0) * (cam.time1 - cam.time0);
+    for (int k = 0; k < 3; k++) {
+        const double offset = cam.cu[k] * rdx + cam.cv[k] * rdy;
+        ray_out[k] = cam.origin[k] + offset;
+        ray_out[3 + k] = cam.lower_left_corner[k] + u * cam.horizontal[k] + v * cam.vertical[k] - (cam.origin[k] + offset);
+    }
+    ray_out[6] = time;
+    return 0;
+}
+
+static int query_flags(uint32_t flags) {
+    if (flags != 0u) return set_err("ray queries take flags = 0: they run in f64 and in the reference's traversal order (RT_F32 and every other flag: not supported)");
+    return 0;
+}
+static int query_aligned(const void* p, const char* what) {
+    if (((uintptr_t)p & 15u) != 0u) return set_err(std::string(what) + " must be 16-byte aligned");
+    return 0;
+}
+// One query launch on the calling thread's current device, enqueued on `stream`: the scene's f64 tables bound into zeroed launch
+// parameters, as a known-answer launch does it, plus what the walks need — bvh_tame, and the LDS node cache: the filter tree, staged by
+// every workgroup when all of it fits the share of the CU's LDS that keeps the workgroups the registers allow resident.
+static int query_launch(Scene& s, const rt_camera* camp, uint32_t W, uint32_t H, QueryArgs Q, hipStream_t stream) {
+    Scene::DeviceCtx* cp = nullptr;
+    if (current_ctx(s, &cp)) return -1;
+    Scene::DeviceCtx& c = *cp;
+    DeviceScene<double>& d = dev_of<double>(c);
+    if (ensure_uploaded<double>(s, d)) return -1;
+    const HostFlat& f = s.flat;
+    KParams<double> P;
+    std::memset((void*)&P, 0, sizeof(P));
+    bind_tables(P, d, f);
+    P.bvh_tame = tables_are_tame<double>(f);
+    const bool camera = camp != nullptr;
+    if (camera) {
+        rt_camera_args ca; std::memcpy(&ca, camp, sizeof(ca));
+        camera_new(ca, P.cam);
+        P.W = W; P.H = H; P.spp = 1u; P.seed = Q.seed;
+    }
+    hipDeviceProp_t prop; HIP_OK(hipGetDeviceProperties(&prop, c.device));
+    int bpc = query_blocks_per_cu(f.feats, camera, 0u);
+    if (bpc <= 0) return set_err("occupancy query failed for the ray-query kernel");
+    size_t shmem = 0;
+    if ((f.feats & F_BVH) && !f.bvh.empty()) {
+        size_t lds_total = (size_t)prop.maxSharedMemoryPerMultiProcessor;
+        if (lds_total < 65536u) lds_total = 65536u;
+        size_t room = ((lds_total / (size_t)bpc) & ~(size_t)1023u) / sizeof(DFNode);
+        // RT_NODE_CACHE_MAX (tests, A/B runs): as for the frames — a tree of more nodes than that is not staged
+        if (const char* v = std::getenv("RT_NODE_CACHE_MAX")) { const long n = std::strtol(v, nullptr, 10); if (n >= 0 && (size_t)n < room) room = (size_t)n; }
+        // The whole tree or nothing (*measured*, profiles/ray_queries.log: the top levels of a tree that does not fit lose to no staging).
+        // n_cached is exactly what the kernel stages: all_in_lds() turns links into LDS addresses.
+        P.n_cached = f.bvh.size() <= room ? (uint32_t)f.bvh.size() : 0u;
+        shmem = (size_t)P.n_cached * sizeof(DFNode);
+        if (shmem != 0u) bpc = query_blocks_per_cu(f.feats, camera, shmem);
+        if (bpc <= 0) return set_err("occupancy query failed for the ray-query kernel (LDS: " + std::to_string(shmem) + " bytes per workgroup)");
+    }
+    uint64_t n_blocks = (uint64_t)prop.multiProcessorCount * (uint64_t)bpc;
+    const uint64_t blocks_needed = ((uint64_t)Q.n + QUERY_THREADS - 1u) / QUERY_THREADS;
+    if (n_blocks > blocks_needed) n_blocks = blocks_needed;
+    if (s.q_ev[0] && s.q_device != c.device) {                          // the event pair lives on one device
+        DeviceGuard guard(s.q_device);
+        if (s.q_recorded) (void)hipEventSynchronize((hipEvent_t)s.q_ev[1]);
+        (void)hipEventDestroy((hipEvent_t)s.q_ev[0]); (void)hipEventDestroy((hipEvent_t)s.q_ev[1]);
+        s.q_ev[0] = s.q_ev[1] = nullptr; s.q_recorded = false;
+    }
+    if (!s.q_ev[0]) {
+        hipEvent_t e0, e1;
+        HIP_OK(hipEventCreate(&e0));
+        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return set_err("hipEventCreate failed"); }
+        s.q_ev[0] = e0; s.q_ev[1] = e1; s.q_device = c.device;
+    }
+    HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[0], stream));
+    HIP_OK(launch_query(P, Q, f.feats, camera, (uint32_t)n_blocks, shmem, stream));
+    HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[1], stream));
+    s.q_recorded = true;
+    return 0;
+}
+
+int rt_query_hits_device(rt_scene* sc, uint32_t n, const void* d_rays, double t_min, uint64_t seed, uint32_t flags,
+                         void* d_hits_out, size_t d_hits_bytes, void* hip_stream) {
+    if (!sc || !d_rays || !d_hits_out) return set_err("null argument");
+    if (query_flags(flags)) return -1;
+    if (n == 0) return 0;
+    if (d_hits_bytes < (size_t)n * QUERY_HIT_DOUBLES * sizeof(double)) return set_err("hit buffer too small for n * 16 doubles (128 bytes per ray)");
+    if (query_aligned(d_rays, "d_rays") || query_aligned(d_hits_out, "d_hits_out")) return -1;
+    if (need_device_and_flat(sc->s)) return -1;
+    QueryArgs Q; Q.rays = (const double*)d_rays; Q.rays_out = nullptr; Q.hits = (double*)d_hits_out; Q.n = n; Q.sample = 0u; Q.t_min = t_min; Q.seed = seed;
+    return query_launch(sc->s, nullptr, 0u, 0u, Q, (hipStream_t)hip_stream);
+}
+int rt_query_hits(rt_scene* sc, uint32_t n, const double* rays, double t_min, uint64_t seed, uint32_t flags, double* hits_out) {
+    if (!sc || !rays || !hits_out) return set_err("null argument");
+    if (query_flags(flags)) return -1;
+    if (n == 0) return 0;
+    if (need_device_and_flat(sc->s)) return -1;
+    const size_t ray_bytes = (size_t)n * QUERY_RAY_DOUBLES * sizeof(double), hit_bytes = (size_t)n * QUERY_HIT_DOUBLES * sizeof(double);
+    DeviceBuffer d_rays, d_hits;
+    HIP_OK(d_rays.alloc(ray_bytes)); HIP_OK(d_hits.alloc(hit_bytes));
+    HIP_OK(hipMemcpy(d_rays.get(), rays, ray_bytes, hipMemcpyHostToDevice));
+    if (rt_query_hits_device(sc, n, d_rays.get(), t_min, seed, flags, d_hits.get(), hit_bytes, nullptr)) return -1;
+    HIP_OK(hipMemcpy(hits_out, d_hits.get(), hit_bytes, hipMemcpyDeviceToHost));       // (waits for the kernel: the null stream)
+    return 0;
+}
+
+static int query_camera_args(rt_scene* sc, const rt_camera* cam, const void* hits, uint32_t W, uint32_t H, uint32_t flags) {
+    if (!sc || !cam || !hits) return set_err("null argument");
+    if (W < 2 || H < 2) return set_err("W and H must be >= 2 (u,v divide by W-1 and H-1, src/main.rs:817-818)");
+    if ((uint64_t)W * H > 0x7FFFFFFFull) return set_err("frame too large: W*H must be <= 2^31 - 1 (per-path RNG keys, csrc/rt_rng.h)");
+    return query_flags(flags);
+}
+int rt_query_camera_device(rt_scene* sc, const rt_camera* cam, uint32_t W, uint32_t H, uint32_t sample, uint64_t seed, uint32_t flags,
+                           void* d_rays_out, void* d_hits_out, size_t d_hits_bytes, void* hip_stream) {
+    if (query_camera_args(sc, cam, d_hits_out, W, H, flags)) return -1;
+    const uint32_t n = W * H;
+    if (d_hits_bytes < (size_t)n * QUERY_HIT_DOUBLES * sizeof(double)) return set_err("hit buffer too small for W * H * 16 doubles (128 bytes per pixel)");
+    if (query_aligned(d_hits_out, "d_hits_out") || (d_rays_out && query_aligned(d_rays_out, "d_rays_out"))) return -1;
+    if (need_device_and_flat(sc->s)) return -1;
+    QueryArgs Q; Q.rays = nullptr; Q.rays_out = (double*)d_rays_out; Q.hits = (double*)d_hits_out; Q.n = n; Q.sample = sample; Q.t_min = 0.00001; Q.seed = seed;
+    return query_launch(sc->s, cam, W, H, Q, (hipStream_t)hip_stream);
+}
+int rt_query_camera(rt_scene* sc, const rt_camera* cam, uint32_t W, uint32_t H, uint32_t sample, uint64_t seed, uint32_t flags,
+                    double* rays_out, double* hits_out) {
+    if (query_camera_args(sc, cam, hits_out, W, H, flags)) return -1;
+    if (need_device_and_flat(sc->s)) return -1;
+    const size_t n = (size_t)W * H, ray_bytes = n * QUERY_RAY_DOUBLES * sizeof(double), hit_bytes = n * QUERY_HIT_DOUBLES * sizeof(double);
+    DeviceBuffer d_rays, d_hits;
+    if (rays_out) HIP_OK(d_rays.alloc(ray_bytes));
+    HIP_OK(d_hits.alloc(hit_bytes));
+    if (rt_query_camera_device(sc, cam, W, H, sample, seed, flags, d_rays.get(), d_hits.get(), hit_bytes, nullptr)) return -1;
+    HIP_OK(hipMemcpy(hits_out, d_hits.get(), hit_bytes, hipMemcpyDeviceToHost));       // (waits for the kernel: the null stream)
+    if (rays_out) HIP_OK(hipMemcpy(rays_out, d_rays.get(), ray_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+int rt_last_query_ms(rt_scene* sc, float* ms_out) {
+    if (!sc || !ms_out) return set_err("null argument");
+    if (!sc->s.q_recorded) return set_err("no ray query has been launched for this scene");
+    DeviceGuard guard(sc->s.q_device);
+    HIP_OK(hipEventSynchronize((hipEvent_t)sc->s.q_ev[1]));
+    HIP_OK(hipEventElapsedTime(ms_out, (hipEvent_t)sc->s.q_ev[0], (hipEvent_t)sc->s.q_ev[1]));
     return 0;
 }
 

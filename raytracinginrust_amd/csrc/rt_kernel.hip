@@ -2283,6 +2283,7 @@ __global__ void __launch_bounds__(Shape<FEATS>::THREADS, Shape<FEATS>::WAVES_PER
     else trace_lockstep<T, FEATS>(P, lane, q_real, q_u32, stack);
 }
 
+#if RT_TU != 3      // (RT_TU == 3: csrc/rt_query.hip includes this file for the device functions above and brings its own kernels and launch code)
 // ------------------------------------------------------------------ launch
 template <typename T, uint32_t FEATS>
 static hipError_t allow_lds(size_t shmem) {            // more than the default 64 KB of dynamic LDS needs to be asked for
@@ -2389,10 +2390,11 @@ template hipError_t launch_pathtrace<float>(const KParams<float>&, uint32_t, uin
 template int pathtrace_blocks_per_cu<double>(uint32_t, uint32_t, size_t);
 template int pathtrace_blocks_per_cu<float>(uint32_t, uint32_t, size_t);
 #endif
+#endif      // RT_TU != 3
 
 } // namespace rt
 
-#if RT_TU != 1
+#if RT_TU != 1 && RT_TU != 3
 // ------------------------------------------------------------------ known-answer access to AABB::hit on the device (tests only)
 namespace rt {
 __global__ void aabb_kat_kernel(uint32_t n, const double* boxes, const double* rays, const double* tlim, int* out) {

@@ -134,6 +134,10 @@ struct Scene {
     // debugging aid (rt_debug_trace_path; -DRT_TRACE_PATH builds of the kernels): the path whose hits are recorded, and the device buffer
     long long trace_px = -1, trace_s = -1; void* d_trace = nullptr; int trace_device = -1; uint32_t trace_levels = 0;     // trace_levels: 16-double records d_trace holds
 
+    // Ray queries (rt_query_*, rt_host.cpp): the event pair around the most recent query kernel (rt_last_query_ms), on q_device.  Queries
+    // use none of the launch slots above: what rt_last_kernel_ms and friends report about the frames is untouched by them.
+    void* q_ev[2] = {nullptr, nullptr}; int q_device = -1; bool q_recorded = false;
+
     // Progressive frames (rt_progressive_*, rt_host.cpp) of this scene: a frame holds the `version` it was created at — every change to the
     // scene moves it on, and the frame's next pass is refused — and is told when the scene is destroyed before it.
     unsigned long long version = 0; std::vector<void*> frames;

@@ -4,10 +4,13 @@
 // (same constructor names and argument order).  Usage mirrors `cargo run --release > image.ppm` (README.md:4):
 //
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
-//              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] > image.ppm
+//              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material FILE] > image.ppm
 //
 // --progressive N (opt-in, one GPU): the frame in passes of N samples per pixel (rt_progressive_*), the reference's style of progress on
 // stderr (main.rs:772-775), and the same PPM bytes at the end, built from the image the device resolved.
+//
+// --aov KIND FILE (opt-in, one GPU, instead of the frame): a feature frame for a denoiser or a compositor — the closest hit of sample 0's
+// camera ray of every pixel (rt_query_camera: the ray the frame traces for that sample) as a P3 PPM in FILE ("-": stdout); AOV_HELP has the mappings.
 //
 // The reference hard-codes its settings as consts (main.rs:579-583, :623); they are flags here.
 #include <algorithm>
@@ -216,12 +219,41 @@ static bool read_image(const std::string& path, std::vector<uint8_t>& data, uint
     return read_p6(path, data, w, h);
 }
 
+static const char* AOV_HELP =
+    "  --aov normal|depth|material FILE   write a feature frame instead of the image: the closest hit of the camera ray of sample 0 of\n"
+    "                                     every pixel (the ray the frame with this --seed traces), as a P3 PPM in FILE (- = stdout):\n"
+    "      normal    r g b = 0.5 * (n + 1) * 255.999 truncated, per component of the hit's normal (a miss has the zero normal: 127 127 127)\n"
+    "      depth     grey, linear in the hit's t between the frame's smallest finite t (255) and its largest (0): (max - t) / (max - min) *\n"
+    "                255.999 truncated; a miss is 0\n"
+    "      material  grey, the hit's material handle mod 256 (a miss or a ConstantMedium hit, handle -1: 255)\n";
+
+// One channel value of the mappings above (a NaN gives 0)
+static unsigned aov_level(double x) { return x >= 0.0 ? (x > 255.0 ? 255u : (unsigned)x) : 0u; }
+static void write_aov(const std::string& kind, const std::string& path, const std::vector<Hit>& hits, uint32_t W, uint32_t H) {
+    double lo = 0.0, hi = 0.0; bool have = false;
+    for (const Hit& h : hits) if (h.hit && h.t - h.t == 0.0) { lo = have ? std::min(lo, h.t) : h.t; hi = have ? std::max(hi, h.t) : h.t; have = true; }
+    std::vector<uint8_t> img(hits.size() * 3);
+    for (size_t p = 0; p < hits.size(); p++) {
+        const Hit& h = hits[p];
+        unsigned c[3];
+        if (kind == "normal") for (int k = 0; k < 3; k++) c[k] = aov_level(0.5 * (h.normal.e[k] + 1.0) * 255.999);
+        else if (kind == "depth") {
+            unsigned g = 0u;
+            if (h.hit && h.t - h.t == 0.0) g = hi > lo ? aov_level((hi - h.t) / (hi - lo) * 255.999) : 255u;
+            c[0] = c[1] = c[2] = g;
+        } else c[0] = c[1] = c[2] = (unsigned)((long long)h.material & 255);
+        for (int k = 0; k < 3; k++) img[p * 3 + k] = (uint8_t)c[k];
+    }
+    write_ppm_rgb8(path.c_str(), img, W, H);
+}
+
 enum class SceneKind { Random, TwoSphere, TwoPerlinSphere, Earth, LightRoom, CornellBox, CornellSmoke, CornellTest, FinalScene, Progress };   // src/main.rs:564-575
 
 int main(int argc, char** argv) {
     SceneKind scene = SceneKind::CornellBox;
     uint32_t image_width = 500, image_height = 500, samples_per_pixel = 800, max_depth = 100;    // main.rs:579-583
     uint64_t seed = 0x5EED; uint32_t flags = RT_F64; bool fast_bvh = false;
+    std::string aov_kind, aov_path;                                         // --aov KIND FILE: a feature frame instead of the image
     uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
     int gpus = 1;                                                           // --gpus N: the first N devices (0 = all) through rt_render_multi
     std::string obj_path = "teapot.obj", earth_path = "earthmap.jpg";       // the reference's asset names (main.rs:248,491)
@@ -246,6 +278,15 @@ int main(int argc, char** argv) {
         else if (a == "--f32") flags |= RT_F32;
         else if (a == "--gpus") gpus = std::atoi(next());
         else if (a == "--progressive") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--progressive needs a pass size >= 1\n"); return 2; } progressive = (uint32_t)n; }
+        else if (a == "--aov") {
+            aov_kind = next(); aov_path = next();
+            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material") { std::fprintf(stderr, "--aov needs normal, depth or material\n%s", AOV_HELP); return 2; }
+        }
+        else if (a == "--help" || a == "-h") {
+            std::printf("rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N]\n"
+                        "         [--depth D] [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] > image.ppm\n%s", AOV_HELP);
+            return 0;
+        }
         else if (a == "--collective") flags |= RT_MULTI_COLLECTIVE;         // with --gpus 1: run the RCCL gather anyway
         else if (a == "--fast-bvh") { fast_bvh = true; flags |= RT_NEAR_FIRST_BVH; }      // opt-in, not the reference's tree / visiting order
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
@@ -313,6 +354,12 @@ int main(int argc, char** argv) {
             camera = Camera::new_(Point3(478.0, 278.0, -600.0), Point3(278.0, 278.0, 0.0), vup, 40.0, aspect_ratio, 0.01, 10.0, 0.0, 1.0);
             break;
         }
+        }
+        if (!aov_kind.empty()) {
+            if (flags & RT_F32) throw Error("--aov runs in f64");
+            write_aov(aov_kind, aov_path, query_camera(s, camera, image_width, image_height, 0u, seed), image_width, image_height);
+            std::fprintf(stderr, "Done.\n");
+            return 0;
         }
         // main.rs:772-833: the whole loop nest is this one call
         if (progressive) {

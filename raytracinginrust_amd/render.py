@@ -394,6 +394,107 @@ def render_tiles_device(b: SceneBuilder, cam: CameraParams, background, W: int, 
     _check(rc)
 
 
+# ---- ray queries (rt_query_*): world.hit (src/main.rs:48) for rays of the caller's, or for the camera rays of one sample of every pixel
+DEFAULT_SEED = 0x5EED
+# the hit record's 16 doubles by name (include/rt_amd.h): material = the handle the builder returned (-1: a ConstantMedium hit, or a miss),
+# object = the index in the flattened object table (debug_objects), prim_kind 0 rect, 1 sphere, 2 moving sphere, 3 triangle, -1 medium
+HIT_FIELDS = {"hit": slice(0, 1), "t": slice(1, 2), "position": slice(2, 5), "normal": slice(5, 8), "front_face": slice(8, 9),
+              "u": slice(9, 10), "v": slice(10, 11), "material": slice(11, 12), "object": slice(12, 13), "prim_kind": slice(13, 14),
+              "prim_index": slice(14, 15)}
+RAY_DOUBLES, HIT_DOUBLES = 7, 16
+
+
+def camera_ray(cam: CameraParams, W: int, H: int, i: int, j: int, seed: int = DEFAULT_SEED, sample: int = 0) -> np.ndarray:
+    """rt_camera_ray (host only): Camera::get_ray for sample `sample` of pixel (i, j), j counted from the bottom row (main.rs:811-820) —
+    the very ray a frame with that seed traces -> (7,) f64: origin, direction, time."""
+    out = (C.c_double * RAY_DOUBLES)()
+    _check(_rt().rt_camera_ray(C.byref(cam), W, H, i, j, seed, sample, out))
+    return np.array(out, dtype=np.float64)
+
+
+def query_hits(b: SceneBuilder, rays, t_min: float = 1e-5, seed: int = 0) -> np.ndarray:
+    """rt_query_hits: world.hit(ray, t_min, +inf) for n rays, (n, 7) f64 {origin, direction, time} -> (n, 16) hit records (HIT_FIELDS).
+    Ray k draws from the stream of Rng(seed, k) where a ConstantMedium needs a random number."""
+    r = np.ascontiguousarray(rays, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] != RAY_DOUBLES:
+        raise ValueError(f"rays of shape {r.shape}: want (n, {RAY_DOUBLES})")
+    out = np.zeros((len(r), HIT_DOUBLES), dtype=np.float64)
+    _check(_rt().rt_query_hits(b.h, len(r), r.ctypes.data, float(t_min), seed, 0, out.ctypes.data))
+    return out
+
+
+def query_camera(b: SceneBuilder, cam: CameraParams, W: int, H: int, sample: int = 0, seed: int = DEFAULT_SEED, want_rays: bool = False):
+    """rt_query_camera: the camera ray of sample `sample` of every pixel, generated on the device as a frame with that seed generates
+    it, and its closest hit -> (H, W, 16) hit records, row 0 = top; with want_rays also the (H, W, 7) rays."""
+    hits = np.zeros((H, W, HIT_DOUBLES), dtype=np.float64)
+    rays = np.zeros((H, W, RAY_DOUBLES), dtype=np.float64) if want_rays else None
+    _check(_rt().rt_query_camera(b.h, C.byref(cam), W, H, sample, seed, 0, rays.ctypes.data if want_rays else None, hits.ctypes.data))
+    return (hits, rays) if want_rays else hits
+
+
+def _device_buffer(x):
+    """(address, bytes) of a device buffer given as a torch tensor, or (address, None) for a raw pointer."""
+    if hasattr(x, "data_ptr"):
+        return int(x.data_ptr()), int(x.numel() * x.element_size())
+    return int(x), None
+
+
+def query_hits_device(b: SceneBuilder, n: int, d_rays, d_hits, t_min: float = 1e-5, seed: int = 0, stream: int = 0, d_hits_bytes=None) -> None:
+    """rt_query_hits_device: the same for rays and records in device memory (torch tensors of f64, or raw pointers — then d_hits_bytes
+    says how large the record buffer is), enqueued on `stream`; never waits.  Both buffers 16-byte aligned."""
+    rays_ptr, _ = _device_buffer(d_rays)
+    hits_ptr, nbytes = _device_buffer(d_hits)
+    nbytes = nbytes if d_hits_bytes is None else int(d_hits_bytes)
+    if nbytes is None:
+        raise ValueError("d_hits_bytes is needed with a raw pointer")
+    _check(_rt().rt_query_hits_device(b.h, n, C.c_void_p(rays_ptr), float(t_min), seed, 0, C.c_void_p(hits_ptr), nbytes, C.c_void_p(stream)))
+
+
+def query_camera_device(b: SceneBuilder, cam: CameraParams, W: int, H: int, d_hits, sample: int = 0, seed: int = DEFAULT_SEED,
+                        d_rays_out=None, stream: int = 0, d_hits_bytes=None) -> None:
+    """rt_query_camera_device: W*H records (and, with d_rays_out, rays) into device memory, enqueued on `stream`; never waits."""
+    hits_ptr, nbytes = _device_buffer(d_hits)
+    nbytes = nbytes if d_hits_bytes is None else int(d_hits_bytes)
+    if nbytes is None:
+        raise ValueError("d_hits_bytes is needed with a raw pointer")
+    rays_ptr = None if d_rays_out is None else _device_buffer(d_rays_out)[0]
+    _check(_rt().rt_query_camera_device(b.h, C.byref(cam), W, H, sample, seed, 0, C.c_void_p(rays_ptr), C.c_void_p(hits_ptr), nbytes,
+                                        C.c_void_p(stream)))
+
+
+def last_query_ms(b: SceneBuilder) -> float:
+    """Milliseconds of the most recent query kernel of this scene (HIP events; waits for it)."""
+    ms = C.c_float()
+    _check(_rt().rt_last_query_ms(b.h, C.byref(ms)))
+    return float(ms.value)
+
+
+def aov_image(hits: np.ndarray, which: str) -> np.ndarray:
+    """An (H, W, 3) 8-bit image of one field of (H, W, 16) hit records, as `rtrender --aov` writes it: "normal" = 0.5 (n + 1) * 255.999
+    truncated (a miss: the zero normal, 127); "depth" = t linear between the frame's smallest (255) and largest (0) finite hit t, a miss 0;
+    "material" = the handle mod 256 in all channels (a miss or a medium, -1: 255)."""
+    H, W, _ = hits.shape
+
+    def level(x):                                   # one channel value: truncated, held to 0 .. 255, a NaN gives 0
+        x = np.asarray(x, dtype=np.float64)
+        return np.where(x >= 0.0, np.minimum(np.nan_to_num(x, nan=0.0), 255.0), 0.0).astype(np.int64)
+
+    if which == "normal":
+        return level(0.5 * (hits[..., 5:8] + 1.0) * 255.999).astype(np.uint8)
+    if which == "depth":
+        t = hits[..., 1]
+        ok = (hits[..., 0] != 0.0) & np.isfinite(t)
+        out = np.zeros((H, W), dtype=np.int64)
+        if ok.any():
+            lo, hi = t[ok].min(), t[ok].max()
+            out[ok] = level((hi - t[ok]) / (hi - lo) * 255.999) if hi > lo else 255
+        return np.repeat(out[..., None], 3, axis=2).astype(np.uint8)
+    if which == "material":
+        m = hits[..., 11].astype(np.int64) & 255
+        return np.repeat(m[..., None], 3, axis=2).astype(np.uint8)
+    raise KeyError(which)
+
+
 def kernel_time_total(b: SceneBuilder, reset: bool = False):
     """(total ms, launches) of this scene's kernels since the last reset; waits for launches in flight."""
     ms, n = C.c_double(), C.c_ulonglong()
