@@ -9,6 +9,7 @@
 // reference reports by panic (src/bvh.rs:55, src/main.rs:431) surface as rtr::Error.
 #pragma once
 #include <array>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <cstdint>
@@ -207,6 +208,37 @@ inline std::vector<Hit> query_camera(Scene& s, const Camera& cam, uint32_t W, ui
         for (size_t k = 0; k < n; k++) { Ray& r = (*rays_out)[k]; r.origin = Point3(rays[k * 7], rays[k * 7 + 1], rays[k * 7 + 2]); r.direction = Vec3(rays[k * 7 + 3], rays[k * 7 + 4], rays[k * 7 + 5]); r.time = rays[k * 7 + 6]; }
     }
     return out;
+}
+
+// ray_color (src/main.rs:41-120) along rays the caller chooses (rt_query_radiance), samples_per_ray samples of each: per ray the SUM over
+// its samples, n x 3, as render() returns per pixel — another projection than Camera's, a light probe, a baked light map.  Sample s of ray k
+// draws from the stream of rt_rng_path(seed, k, s).  samples_out (optional) receives every sample, ray-major; nonfinite_out (optional) the
+// number of samples with a non-finite component.
+inline std::vector<double> query_radiance(Scene& s, const std::vector<Ray>& rays, uint32_t samples_per_ray, uint32_t max_depth,
+                                          Color background = Color(0.0, 0.0, 0.0), uint64_t seed = 0x5EED, uint32_t flags = 0,
+                                          std::vector<double>* samples_out = nullptr, uint64_t* nonfinite_out = nullptr) {
+    std::vector<double> in(rays.size() * 7), sums(rays.size() * 3);
+    for (size_t k = 0; k < rays.size(); k++) {
+        for (int a = 0; a < 3; a++) { in[k * 7 + a] = rays[k].origin.e[a]; in[k * 7 + 3 + a] = rays[k].direction.e[a]; }
+        in[k * 7 + 6] = rays[k].time;
+    }
+    if (samples_out) samples_out->assign(rays.size() * (size_t)samples_per_ray * 3, 0.0);
+    if (rt_query_radiance(s.raw(), (uint32_t)rays.size(), in.data(), background.e, samples_per_ray, max_depth, seed, flags, sums.data(),
+                          samples_out ? samples_out->data() : nullptr, nonfinite_out) != 0) throw Error(rt_last_error());
+    return sums;
+}
+// The rays of a W x H equirectangular (360 x 180 degree) panorama seen from `origin`, in output order (row 0 = top): row r, column i looks
+// along (sin t cos p, cos t, sin t sin p) with t = pi (r + 0.5) / H from +y, p = 2 pi (i + 0.5) / W.  No jitter.
+inline std::vector<Ray> equirect_rays(Point3 origin, uint32_t W, uint32_t H, double time = 0.0) {
+    const double pi = 3.141592653589793;
+    std::vector<double> sp(W), cp(W);
+    for (uint32_t i = 0; i < W; i++) { const double phi = 2.0 * pi * ((double)i + 0.5) / (double)W; sp[i] = std::sin(phi); cp[i] = std::cos(phi); }
+    std::vector<Ray> rays((size_t)W * H);
+    for (uint32_t r = 0; r < H; r++) {
+        const double theta = pi * ((double)r + 0.5) / (double)H, st = std::sin(theta), ct = std::cos(theta);
+        for (uint32_t i = 0; i < W; i++) { Ray& q = rays[(size_t)r * W + i]; q.origin = origin; q.direction = Vec3(st * cp[i], ct, st * sp[i]); q.time = time; }
+    }
+    return rays;
 }
 
 // A progressive frame (rt_progressive_*): the same loop in passes of samples that accumulate on the device, with the reference's

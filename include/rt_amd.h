@@ -271,7 +271,42 @@ int rt_query_camera(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_
                     double* rays_out, double* hits_out);
 int rt_query_camera_device(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t sample, uint64_t seed, uint32_t flags,
                            void* d_rays_out, void* d_hits_out, size_t d_hits_bytes, void* hip_stream);
-int rt_last_query_ms(rt_scene*, float* ms_out);   /* HIP events around the most recent query kernel of this scene; waits */
+int rt_last_query_ms(rt_scene*, float* ms_out);   /* HIP events around the most recent query kernel of this scene (ray or radiance query); waits */
+
+/* ---- radiance queries: the reference's `ray_color(r, background, world, lights, depth)` (src/main.rs:41-120) as a function of its own — the
+ *      radiance along rays the caller chooses, samples_per_ray samples of each: another projection than camera.rs's (360-degree panorama,
+ *      orthographic, fisheye, a measured lens), a light or irradiance probe at a point, a baked light map over a surface, "how bright is it
+ *      along THIS ray".  The bounce loop is the frames' own device code (csrc/rt_radiance.hip), for every kind of scene, the principled
+ *      material included.  f64 and the reference's traversal order only; one device, the current one.
+ * A ray is the 7 doubles of rt_query_hits: origin[3], direction[3], time.  Non-finite and zero components are legal; the direction is not
+ * normalised (the reference does not normalise it either).
+ * Sample s of ray k is ray_color(ray_k, background, world, lights, max_depth) drawing from the stream of rt_rng_path(seed, k, first_sample + s)
+ * from its first draw on: the frames' keying with the ray's index in the pixel's place, and no camera draws.  Hence n <= 2^31 - 1 and
+ * first_sample + samples_per_ray <= 2^32 - 1 (the offset is folded into the seed, as rt_render_device_pass does it).
+ * rgb_sum_out = n x 3: per ray the SUM over its samples, as rt_render returns per pixel (divide by samples_per_ray, or hand to
+ * rt_write_ppm / rt_format_color).  The sums are built with f64 atomic adds: a ray's samples may be spread over many waves, so a sum's
+ * rounding depends on the order the partial sums arrive in — |sum - exact| <= 2 * gamma_N * sum |x_i|, gamma_N = N u / (1 - N u), u = 2^-53,
+ * N = the samples added (the bound rt_progressive_read_sum states); the samples themselves are the same words in every run.
+ * samples_out: NULL, or n x samples_per_ray x 3, every sample, ray-major (the layout of rt_render_samples).  nonfinite_out: NULL, or the number
+ * of samples with a non-finite component (the B8 count of rt_last_stats, for this call).
+ * flags: RT_STOP_ON_ZERO and RT_ISOTROPIC_SCATTER as for the frames; every other bit, RT_F32 included, is an error.
+ * The host form is synchronous: the device form with (first_sample, accumulate) = (0, 0).  The _device form takes DEVICE pointers (d_rays
+ * 16-byte aligned, the others 8-byte), only enqueues on hip_stream (a hipStream_t, may be NULL) and never waits; accumulate = 0: d_rgb_sum is
+ * zeroed on the stream first; accumulate != 0: the pass is added to what d_rgb_sum holds.  d_samples_out (may be NULL) receives THIS pass's
+ * n x samples_per_ray x 3 samples.  d_nonfinite_out (may be NULL) is one u64 that is only ever added to: the caller zeroes it.  There is no
+ * global work counter, so launches on different streams may overlap.  A scene not yet prepared is flattened and uploaded first, as
+ * rt_render_device does it.
+ * Errors (non-zero, a message for rt_last_error, nothing launched): null arguments, samples_per_ray = 0, either limit above exceeded, a flag
+ * other than the two, d_rgb_sum_bytes < 24 n, a misaligned pointer, no HIP device (there is no CPU path).  n = 0 returns 0 and touches nothing.
+ * rt_last_query_ms reports this kernel too; what rt_last_kernel_ms, rt_last_stats and friends report about the frames is left alone. */
+int rt_query_radiance(rt_scene*, uint32_t n, const double* rays, const double background[3],
+                      uint32_t samples_per_ray, uint32_t max_depth, uint64_t seed, uint32_t flags,
+                      double* rgb_sum_out, double* samples_out, uint64_t* nonfinite_out);
+int rt_query_radiance_device(rt_scene*, uint32_t n, const void* d_rays, const double background[3],
+                             uint32_t samples_per_ray, uint32_t max_depth, uint64_t seed, uint32_t flags,
+                             uint32_t first_sample, int accumulate,
+                             void* d_rgb_sum, size_t d_rgb_sum_bytes, void* d_samples_out, void* d_nonfinite_out,
+                             void* hip_stream);
 
 /* The whole frame on several GPUs of this node from ONE call: what a host that owns the node's GPUs itself (the reference's `main`,
  * src/main.rs:767-835) calls instead of rt_render.  device_mask: bit d selects HIP device d (0 = every visible device).  The scene

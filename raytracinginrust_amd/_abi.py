@@ -111,6 +111,9 @@ SIGNATURES = {
     "query_camera": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u64, _u32, _ptr, _ptr]),
     "query_camera_device": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u64, _u32, _ptr, _ptr, C.c_size_t, _ptr]),
     "last_query_ms": (_int, [_ptr, c_float_p]),
+    # radiance queries
+    "query_radiance": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _ptr, _ptr, c_u64_p]),
+    "query_radiance_device": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _u32, _int, _ptr, C.c_size_t, _ptr, _ptr, _ptr]),
     "render_multi": (_int, _FRAME + [_u32, _u32, _ptr]),
     "render_multi_device": (_int, _FRAME + [_u32, _u32, c_void_pp]),
     "multi_sync": (_int, [_ptr]),

@@ -16,6 +16,7 @@
 #include "rt_device.h"
 #include "rt_resolve.h"
 #include "rt_query.h"
+#include "rt_radiance.h"
 
 using namespace rt;
 
@@ -1146,6 +1147,46 @@ static int query_aligned(const void* p, const char* what) {
     if (((uintptr_t)p & 15u) != 0u) return set_err(std::string(what) + " must be 16-byte aligned");
     return 0;
 }
+// The LDS node cache of a query launch: P.n_cached / shmem for the filter tree staged whole or not at all, and the resident workgroups per CU
+// (`occupancy(shmem)`: the kernel's own) that go with it.
+extern "C++" {     // (a template inside this file's extern "C" block)
+template <typename Occ> static int query_node_cache(const HostFlat& f, const hipDeviceProp_t& prop, Occ&& occupancy, const char* kernel,
+                                                    KParams<double>& P, size_t& shmem, int& bpc) {
+    bpc = occupancy((size_t)0u);
+    if (bpc <= 0) return set_err(std::string("occupancy query failed for the ") + kernel + " kernel");
+    shmem = 0;
+    if ((f.feats & F_BVH) && !f.bvh.empty()) {
+        size_t lds_total = (size_t)prop.maxSharedMemoryPerMultiProcessor;
+        if (lds_total < 65536u) lds_total = 65536u;
+        size_t room = ((lds_total / (size_t)bpc) & ~(size_t)1023u) / sizeof(DFNode);
+        // RT_NODE_CACHE_MAX (tests, A/B runs): as for the frames — a tree of more nodes than that is not staged
+        if (const char* v = std::getenv("RT_NODE_CACHE_MAX")) { const long n = std::strtol(v, nullptr, 10); if (n >= 0 && (size_t)n < room) room = (size_t)n; }
+        // The whole tree or nothing (*measured*, profiles/ray_queries.log: the top levels of a tree that does not fit lose to no staging).
+        // n_cached is exactly what the kernel stages: all_in_lds() turns links into LDS addresses.
+        P.n_cached = f.bvh.size() <= room ? (uint32_t)f.bvh.size() : 0u;
+        shmem = (size_t)P.n_cached * sizeof(DFNode);
+        if (shmem != 0u) bpc = occupancy(shmem);
+        if (bpc <= 0) return set_err(std::string("occupancy query failed for the ") + kernel + " kernel (LDS: " + std::to_string(shmem) + " bytes per workgroup)");
+    }
+    return 0;
+}
+}
+// The event pair around the most recent query kernel (rt_last_query_ms): it lives on one device
+static int query_events(Scene& s, int device) {
+    if (s.q_ev[0] && s.q_device != device) {
+        DeviceGuard guard(s.q_device);
+        if (s.q_recorded) (void)hipEventSynchronize((hipEvent_t)s.q_ev[1]);
+        (void)hipEventDestroy((hipEvent_t)s.q_ev[0]); (void)hipEventDestroy((hipEvent_t)s.q_ev[1]);
+        s.q_ev[0] = s.q_ev[1] = nullptr; s.q_recorded = false;
+    }
+    if (!s.q_ev[0]) {
+        hipEvent_t e0, e1;
+        HIP_OK(hipEventCreate(&e0));
+        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return set_err("hipEventCreate failed"); }
+        s.q_ev[0] = e0; s.q_ev[1] = e1; s.q_device = device;
+    }
+    return 0;
+}
 // One query launch on the calling thread's current device, enqueued on `stream`: the scene's f64 tables bound into zeroed launch
 // parameters, as a known-answer launch does it, plus what the walks need — bvh_tame, and the LDS node cache: the filter tree, staged by
 // every workgroup when all of it fits the share of the CU's LDS that keeps the workgroups the registers allow resident.
@@ -1167,37 +1208,12 @@ static int query_launch(Scene& s, const rt_camera* camp, uint32_t W, uint32_t H,
         P.W = W; P.H = H; P.spp = 1u; P.seed = Q.seed;
     }
     hipDeviceProp_t prop; HIP_OK(hipGetDeviceProperties(&prop, c.device));
-    int bpc = query_blocks_per_cu(f.feats, camera, 0u);
-    if (bpc <= 0) return set_err("occupancy query failed for the ray-query kernel");
-    size_t shmem = 0;
-    if ((f.feats & F_BVH) && !f.bvh.empty()) {
-        size_t lds_total = (size_t)prop.maxSharedMemoryPerMultiProcessor;
-        if (lds_total < 65536u) lds_total = 65536u;
-        size_t room = ((lds_total / (size_t)bpc) & ~(size_t)1023u) / sizeof(DFNode);
-        // RT_NODE_CACHE_MAX (tests, A/B runs): as for the frames — a tree of more nodes than that is not staged
-        if (const char* v = std::getenv("RT_NODE_CACHE_MAX")) { const long n = std::strtol(v, nullptr, 10); if (n >= 0 && (size_t)n < room) room = (size_t)n; }
-        // The whole tree or nothing (*measured*, profiles/ray_queries.log: the top levels of a tree that does not fit lose to no staging).
-        // n_cached is exactly what the kernel stages: all_in_lds() turns links into LDS addresses.
-        P.n_cached = f.bvh.size() <= room ? (uint32_t)f.bvh.size() : 0u;
-        shmem = (size_t)P.n_cached * sizeof(DFNode);
-        if (shmem != 0u) bpc = query_blocks_per_cu(f.feats, camera, shmem);
-        if (bpc <= 0) return set_err("occupancy query failed for the ray-query kernel (LDS: " + std::to_string(shmem) + " bytes per workgroup)");
-    }
+    int bpc = 0; size_t shmem = 0;
+    if (query_node_cache(f, prop, [&](size_t lds) { return query_blocks_per_cu(f.feats, camera, lds); }, "ray-query", P, shmem, bpc)) return -1;
     uint64_t n_blocks = (uint64_t)prop.multiProcessorCount * (uint64_t)bpc;
     const uint64_t blocks_needed = ((uint64_t)Q.n + QUERY_THREADS - 1u) / QUERY_THREADS;
     if (n_blocks > blocks_needed) n_blocks = blocks_needed;
-    if (s.q_ev[0] && s.q_device != c.device) {                          // the event pair lives on one device
-        DeviceGuard guard(s.q_device);
-        if (s.q_recorded) (void)hipEventSynchronize((hipEvent_t)s.q_ev[1]);
-        (void)hipEventDestroy((hipEvent_t)s.q_ev[0]); (void)hipEventDestroy((hipEvent_t)s.q_ev[1]);
-        s.q_ev[0] = s.q_ev[1] = nullptr; s.q_recorded = false;
-    }
-    if (!s.q_ev[0]) {
-        hipEvent_t e0, e1;
-        HIP_OK(hipEventCreate(&e0));
-        if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return set_err("hipEventCreate failed"); }
-        s.q_ev[0] = e0; s.q_ev[1] = e1; s.q_device = c.device;
-    }
+    if (query_events(s, c.device)) return -1;
     HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[0], stream));
     HIP_OK(launch_query(P, Q, f.feats, camera, (uint32_t)n_blocks, shmem, stream));
     HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[1], stream));
@@ -1265,6 +1281,87 @@ int rt_last_query_ms(rt_scene* sc, float* ms_out) {
     DeviceGuard guard(sc->s.q_device);
     HIP_OK(hipEventSynchronize((hipEvent_t)sc->s.q_ev[1]));
     HIP_OK(hipEventElapsedTime(ms_out, (hipEvent_t)sc->s.q_ev[0], (hipEvent_t)sc->s.q_ev[1]));
+    return 0;
+}
+
+// ---------------------------------------------------------------- radiance queries
+// ray_color(r, background, world, lights, depth) (main.rs:41-120) for rays the caller chooses (csrc/rt_radiance.hip): the frames' bounce loop
+// behind the caller's rays instead of Camera::get_ray.
+static int radiance_args(rt_scene* sc, uint32_t n, const void* rays, const double* bg, uint32_t spp, uint32_t flags, uint32_t first_sample, const void* sums) {
+    if (!sc || !rays || !bg || !sums) return set_err("null argument");
+    if (spp == 0) return set_err("samples_per_ray must be >= 1");
+    if (n > 0x7FFFFFFFu) return set_err("too many rays: n must be <= 2^31 - 1 (per-path RNG keys, csrc/rt_rng.h)");
+    if ((uint64_t)first_sample + spp > 0xFFFFFFFFull) return set_err("first_sample + samples_per_ray must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
+    if (flags & ~(uint32_t)(RT_STOP_ON_ZERO | RT_ISOTROPIC_SCATTER))
+        return set_err("radiance queries take RT_STOP_ON_ZERO and RT_ISOTROPIC_SCATTER only: they run in f64 and in the reference's traversal order (RT_F32 and every other flag: not supported)");
+    return 0;
+}
+int rt_query_radiance_device(rt_scene* sc, uint32_t n, const void* d_rays, const double bg[3], uint32_t spp, uint32_t max_depth, uint64_t seed,
+                             uint32_t flags, uint32_t first_sample, int accumulate, void* d_rgb_sum, size_t d_rgb_sum_bytes,
+                             void* d_samples_out, void* d_nonfinite_out, void* hip_stream) {
+    if (radiance_args(sc, n, d_rays, bg, spp, flags, first_sample, d_rgb_sum)) return -1;
+    if (n == 0) return 0;
+    if (d_rgb_sum_bytes < (size_t)n * 3u * sizeof(double)) return set_err("sum buffer too small for n * 3 doubles (24 bytes per ray)");
+    if (query_aligned(d_rays, "d_rays")) return -1;
+    if (((uintptr_t)d_rgb_sum & 7u) || ((uintptr_t)d_samples_out & 7u) || ((uintptr_t)d_nonfinite_out & 7u)) return set_err("d_rgb_sum, d_samples_out and d_nonfinite_out must be 8-byte aligned");
+    Scene& s = sc->s;
+    if (need_device_and_flat(s)) return -1;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    Scene::DeviceCtx* cp = nullptr;
+    if (current_ctx(s, &cp)) return -1;
+    Scene::DeviceCtx& c = *cp;
+    DeviceScene<double>& d = dev_of<double>(c);
+    if (ensure_uploaded<double>(s, d)) return -1;
+    const HostFlat& f = s.flat;
+    KParams<double> P;
+    std::memset((void*)&P, 0, sizeof(P));
+    bind_tables(P, d, f);
+    P.bvh_tame = tables_are_tame<double>(f);
+    for (int k = 0; k < 3; k++) P.background[k] = bg[k];
+    P.spp = spp; P.max_depth = max_depth; P.flags = flags;
+    // samples [first_sample, first_sample + spp) of every ray: the offset folded into the seed, as launch_pass does it for the frames
+    const uint64_t G = 0x9E3779B97F4A7C15ULL;
+    P.seed = seed + 2ULL * (uint64_t)first_sample * G;
+    P.out = (double*)d_rgb_sum; P.samples_out = (double*)d_samples_out;
+    RadianceArgs R;
+    R.rays = (const double*)d_rays; R.nonfinite = (unsigned long long*)d_nonfinite_out;
+    R.chunk = RADIANCE_CHUNK;
+    // RT_RADIANCE_CHUNK (A/B runs, tools/radiance_probe.py): paths per chunk of the static dealing — same samples with any value
+    if (const char* v = std::getenv("RT_RADIANCE_CHUNK")) { const long m = std::strtol(v, nullptr, 10); if (m >= 1 && m <= 65536) R.chunk = (uint32_t)m; }
+    R.n_paths = (uint64_t)n * spp;
+    R.n_chunks = (R.n_paths + R.chunk - 1u) / R.chunk;
+    hipDeviceProp_t prop; HIP_OK(hipGetDeviceProperties(&prop, c.device));
+    int bpc = 0; size_t shmem = 0;
+    if (query_node_cache(f, prop, [&](size_t lds) { return radiance_blocks_per_cu(f.feats, lds); }, "radiance-query", P, shmem, bpc)) return -1;
+    uint64_t n_blocks = (uint64_t)prop.multiProcessorCount * (uint64_t)bpc;
+    const uint64_t waves_per_block = RADIANCE_THREADS / 64u;
+    const uint64_t blocks_needed = (R.n_chunks + waves_per_block - 1u) / waves_per_block;      // a chunk per wave at least
+    if (n_blocks > blocks_needed) n_blocks = blocks_needed;
+    if (query_events(s, c.device)) return -1;
+    if (!accumulate) HIP_OK(hipMemsetAsync(d_rgb_sum, 0, (size_t)n * 3u * sizeof(double), stream));
+    HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[0], stream));
+    HIP_OK(launch_radiance(P, R, f.feats, (uint32_t)n_blocks, shmem, stream));
+    HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[1], stream));
+    s.q_recorded = true;
+    return 0;
+}
+int rt_query_radiance(rt_scene* sc, uint32_t n, const double* rays, const double bg[3], uint32_t spp, uint32_t max_depth, uint64_t seed,
+                      uint32_t flags, double* rgb_sum_out, double* samples_out, uint64_t* nonfinite_out) {
+    if (radiance_args(sc, n, rays, bg, spp, flags, 0u, rgb_sum_out)) return -1;
+    if (n == 0) return 0;
+    if (need_device_and_flat(sc->s)) return -1;
+    const size_t ray_bytes = (size_t)n * QUERY_RAY_DOUBLES * sizeof(double), sum_bytes = (size_t)n * 3u * sizeof(double);
+    if (samples_out && (uint64_t)n * spp > (uint64_t)(SIZE_MAX / (3u * sizeof(double)))) return set_err("samples_out: n * samples_per_ray * 24 bytes do not fit a size_t");
+    const size_t sample_bytes = sum_bytes * spp;
+    DeviceBuffer d_rays, d_sum, d_samples, d_nonfinite;
+    HIP_OK(d_rays.alloc(ray_bytes)); HIP_OK(d_sum.alloc(sum_bytes));
+    if (samples_out) HIP_OK(d_samples.alloc(sample_bytes));
+    if (nonfinite_out) { HIP_OK(d_nonfinite.alloc(sizeof(uint64_t))); HIP_OK(hipMemset(d_nonfinite.get(), 0, sizeof(uint64_t))); }
+    HIP_OK(hipMemcpy(d_rays.get(), rays, ray_bytes, hipMemcpyHostToDevice));
+    if (rt_query_radiance_device(sc, n, d_rays.get(), bg, spp, max_depth, seed, flags, 0u, 0, d_sum.get(), sum_bytes, d_samples.get(), d_nonfinite.get(), nullptr)) return -1;
+    HIP_OK(hipMemcpy(rgb_sum_out, d_sum.get(), sum_bytes, hipMemcpyDeviceToHost));       // (waits for the kernel: the null stream)
+    if (samples_out) HIP_OK(hipMemcpy(samples_out, d_samples.get(), sample_bytes, hipMemcpyDeviceToHost));
+    if (nonfinite_out) HIP_OK(hipMemcpy(nonfinite_out, d_nonfinite.get(), sizeof(uint64_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -4,13 +4,17 @@
 // (same constructor names and argument order).  Usage mirrors `cargo run --release > image.ppm` (README.md:4):
 //
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
-//              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material FILE] > image.ppm
+//              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material FILE] [--panorama FILE] > image.ppm
 //
 // --progressive N (opt-in, one GPU): the frame in passes of N samples per pixel (rt_progressive_*), the reference's style of progress on
 // stderr (main.rs:772-775), and the same PPM bytes at the end, built from the image the device resolved.
 //
 // --aov KIND FILE (opt-in, one GPU, instead of the frame): a feature frame for a denoiser or a compositor — the closest hit of sample 0's
 // camera ray of every pixel (rt_query_camera: the ray the frame traces for that sample) as a P3 PPM in FILE ("-": stdout); AOV_HELP has the mappings.
+//
+// --panorama FILE (opt-in, one GPU, instead of the frame): the 2:1 equirectangular image of everything around the scene's lookfrom —
+// image_width x image_width/2 rays through rt_query_radiance (ray_color for caller rays), the scene's spp, depth and background — as the
+// frame's kind of PPM in FILE ("-": stdout).
 //
 // The reference hard-codes its settings as consts (main.rs:579-583, :623); they are flags here.
 #include <algorithm>
@@ -254,6 +258,7 @@ int main(int argc, char** argv) {
     uint32_t image_width = 500, image_height = 500, samples_per_pixel = 800, max_depth = 100;    // main.rs:579-583
     uint64_t seed = 0x5EED; uint32_t flags = RT_F64; bool fast_bvh = false;
     std::string aov_kind, aov_path;                                         // --aov KIND FILE: a feature frame instead of the image
+    std::string panorama_path;                                              // --panorama FILE: the equirectangular image around lookfrom instead
     uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
     int gpus = 1;                                                           // --gpus N: the first N devices (0 = all) through rt_render_multi
     std::string obj_path = "teapot.obj", earth_path = "earthmap.jpg";       // the reference's asset names (main.rs:248,491)
@@ -282,9 +287,12 @@ int main(int argc, char** argv) {
             aov_kind = next(); aov_path = next();
             if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material") { std::fprintf(stderr, "--aov needs normal, depth or material\n%s", AOV_HELP); return 2; }
         }
+        else if (a == "--panorama") panorama_path = next();
         else if (a == "--help" || a == "-h") {
             std::printf("rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N]\n"
-                        "         [--depth D] [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] > image.ppm\n%s", AOV_HELP);
+                        "         [--depth D] [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] > image.ppm\n%s"
+                        "  --panorama FILE                    write the 2:1 equirectangular image (width x width/2) of everything around the scene's\n"
+                        "                                     lookfrom instead of the image: --spp samples per ray, --depth, the scene's background\n", AOV_HELP);
             return 0;
         }
         else if (a == "--collective") flags |= RT_MULTI_COLLECTIVE;         // with --gpus 1: run the RCCL gather anyway
@@ -358,6 +366,16 @@ int main(int argc, char** argv) {
         if (!aov_kind.empty()) {
             if (flags & RT_F32) throw Error("--aov runs in f64");
             write_aov(aov_kind, aov_path, query_camera(s, camera, image_width, image_height, 0u, seed), image_width, image_height);
+            std::fprintf(stderr, "Done.\n");
+            return 0;
+        }
+        if (!panorama_path.empty()) {
+            if (flags & RT_F32) throw Error("--panorama runs in f64");
+            const uint32_t pw = image_width, ph = image_width / 2u;
+            if (ph == 0u) throw Error("--panorama needs --width >= 2");
+            const Point3 from(camera.c.lookfrom[0], camera.c.lookfrom[1], camera.c.lookfrom[2]);
+            write_ppm(panorama_path.c_str(), query_radiance(s, equirect_rays(from, pw, ph), samples_per_pixel, max_depth, background, seed,
+                                                            flags & (uint32_t)RT_ISOTROPIC_SCATTER), pw, ph, samples_per_pixel);
             std::fprintf(stderr, "Done.\n");
             return 0;
         }

@@ -6,6 +6,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -460,6 +461,59 @@ def query_camera_device(b: SceneBuilder, cam: CameraParams, W: int, H: int, d_hi
     rays_ptr = None if d_rays_out is None else _device_buffer(d_rays_out)[0]
     _check(_rt().rt_query_camera_device(b.h, C.byref(cam), W, H, sample, seed, 0, C.c_void_p(rays_ptr), C.c_void_p(hits_ptr), nbytes,
                                         C.c_void_p(stream)))
+
+
+def query_radiance(b: SceneBuilder, rays, spp: int, max_depth: int, background=(0.0, 0.0, 0.0), seed: int = DEFAULT_SEED, flags: int = 0,
+                   want_samples: bool = False):
+    """rt_query_radiance: ray_color (main.rs:41-120) along n caller rays, (n, 7) f64 {origin, direction, time}, spp samples of each; sample s
+    of ray k draws from the stream of rng_path(seed, k, s) -> (sums (n, 3)[, samples (n, spp, 3)], nonfinite): per ray the SUM over its
+    samples, as render() returns per pixel; nonfinite = the samples with a non-finite component."""
+    r = np.ascontiguousarray(rays, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] != RAY_DOUBLES:
+        raise ValueError(f"rays of shape {r.shape}: want (n, {RAY_DOUBLES})")
+    bg = (C.c_double * 3)(*[float(x) for x in background])
+    sums = np.zeros((len(r), 3), dtype=np.float64)
+    samples = np.zeros((len(r), spp, 3), dtype=np.float64) if want_samples else None
+    nonfinite = C.c_uint64(0)
+    _check(_rt().rt_query_radiance(b.h, len(r), r.ctypes.data, bg, spp, max_depth, seed, flags, sums.ctypes.data,
+                                   samples.ctypes.data if want_samples else None, C.byref(nonfinite)))
+    return (sums, samples, int(nonfinite.value)) if want_samples else (sums, int(nonfinite.value))
+
+
+def query_radiance_device(b: SceneBuilder, n: int, d_rays, d_rgb_sum, spp: int, max_depth: int, background=(0.0, 0.0, 0.0),
+                          seed: int = DEFAULT_SEED, flags: int = 0, first_sample: int = 0, accumulate: bool = False, d_samples=None,
+                          d_nonfinite=None, stream: int = 0, d_rgb_sum_bytes=None) -> None:
+    """rt_query_radiance_device: the same for rays and sums in device memory (torch tensors of f64, or raw pointers — then d_rgb_sum_bytes
+    says how large the sum buffer is), samples [first_sample, first_sample + spp) of every ray, enqueued on `stream`; never waits.
+    accumulate: added to what d_rgb_sum holds instead of overwriting it.  d_samples (n * spp * 3 f64) and d_nonfinite (one 64-bit word,
+    only ever added to: the caller zeroes it) are optional."""
+    rays_ptr, _ = _device_buffer(d_rays)
+    sum_ptr, nbytes = _device_buffer(d_rgb_sum)
+    nbytes = nbytes if d_rgb_sum_bytes is None else int(d_rgb_sum_bytes)
+    if nbytes is None:
+        raise ValueError("d_rgb_sum_bytes is needed with a raw pointer")
+    samples_ptr = None if d_samples is None else _device_buffer(d_samples)[0]
+    nonfinite_ptr = None if d_nonfinite is None else _device_buffer(d_nonfinite)[0]
+    bg = (C.c_double * 3)(*[float(x) for x in background])
+    _check(_rt().rt_query_radiance_device(b.h, n, C.c_void_p(rays_ptr), bg, spp, max_depth, seed, flags, first_sample, 1 if accumulate else 0,
+                                          C.c_void_p(sum_ptr), nbytes, C.c_void_p(samples_ptr), C.c_void_p(nonfinite_ptr), C.c_void_p(stream)))
+
+
+def equirect_rays(origin, W: int, H: int, time: float = 0.0) -> np.ndarray:
+    """The rays of a W x H equirectangular (360 x 180 degree) panorama seen from `origin` -> (H * W, 7) in output order, row 0 = top:
+    row r, column i looks along (sin t cos p, cos t, sin t sin p) with t = pi (r + 0.5) / H from +y, p = 2 pi (i + 0.5) / W.  No jitter."""
+    # (sines and cosines from libm, one row / column at a time: the very doubles include/raytracinginrust.hpp's equirect_rays computes)
+    theta = [math.pi * (r + 0.5) / H for r in range(H)]
+    phi = [2.0 * math.pi * (i + 0.5) / W for i in range(W)]
+    st, ct = np.array([math.sin(t) for t in theta]), np.array([math.cos(t) for t in theta])
+    sp, cp = np.array([math.sin(p) for p in phi]), np.array([math.cos(p) for p in phi])
+    rays = np.empty((H, W, RAY_DOUBLES), dtype=np.float64)
+    rays[..., 0:3] = np.asarray(origin, dtype=np.float64)
+    rays[..., 3] = st[:, None] * cp[None, :]
+    rays[..., 4] = ct[:, None]
+    rays[..., 5] = st[:, None] * sp[None, :]
+    rays[..., 6] = float(time)
+    return rays.reshape(H * W, RAY_DOUBLES)
 
 
 def last_query_ms(b: SceneBuilder) -> float:
