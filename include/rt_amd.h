@@ -461,6 +461,17 @@ int rt_debug_list_hit(rt_scene*, uint32_t n, const double* rays, const double* t
  * the function the all-features kernel with object leaves runs (the instantiation every scene with a list inside `lights` gets).  origins,
  * dirs: n x 3; out: n.  Host pointers. */
 int rt_debug_light_pdf(rt_scene*, uint32_t n, const double* origins, const double* dirs, double* out);
+/* Known-answer access to the per-face ONB memo of the lean f64 list-scene kernel (rt_kernel.hip onb_memo_probe / onb_memo_load: the
+ * device functions its Lambertian arm calls) for n pairs of (rect index, normal).  rects: n doubles, each a rect record's index;
+ * normals: n x 3; out: n x 7 = memo hit (0 / 1), then v[3], u[3] of ONB::build_from_w(normal) (onb.rs:8-20) as the table holds them
+ * (zeros on a miss).  A hit requires |normal| to equal the entry's magnitudes bit for bit.  Host pointers. */
+int rt_debug_onb(rt_scene*, uint32_t n, const double* rects, const double* normals, double* out);
+/* Test aid (host only, no GPU): the per-face ONB memo as flattened, one entry per rect record: mag_out[3 i ..] = the bit patterns of
+ * |n.x|, |n.y|, |n.z| of the hit normal the rect's owner produces (all ones: no valid entry — an f32-only use, a scene with a feature bit,
+ * a chain other than bare / FlipNormals / Translate(RotateY(..)), a rect reachable through more than one chain, RT_NO_ONB_TABLE),
+ * slots_out[48 i + 6 s ..] = {v[3], u[3]} for the sign bits s = sx | sy << 1 | sz << 2.  Either pointer may be NULL.  Returns the number
+ * of rect records, *n_valid_out the number of valid entries; -1 on error. */
+int rt_debug_onb_table(rt_scene*, uint64_t* mag_out, double* slots_out, uint32_t max_rects, uint32_t* n_valid_out);
 /* Debugging aid for parity work: the hits of ONE camera path, level by level.  rt_debug_trace_path chooses the path (local pixel index =
  * output-order pixel for an unsharded render, sample index; -1 switches it off); the following renders record, per level of ray_color
  * that found a hit, 16 doubles at out[16 * level]: t, position[3], normal[3], front_face, object, primitive kind, primitive index,

@@ -729,6 +729,69 @@ void make_filter_nodes(HostFlat& f, const std::vector<unsigned char>* take_out =
     }
 }
 
+// ---- the per-face ONB memo (rt_ir.h DOnbEntry; rt_kernel.hip onb_memo_probe) of the lean f64 list-scene kernel
+// A Lambertian hit builds ONB::build_from_w(rec.normal) (onb.rs:8-20): a pure function of the normal's 192 bits.  In a list scene the
+// normal of a rect reached bare, through FlipNormals only, or through the fused Translate(RotateY(..)) chain is the rect's axis unit
+// vector after at most one rotation by the op record's sin / cos and exact sign flips (rt_kernel.hip finalize_hit): its three MAGNITUDES
+// are constants of the rect, only the sign bits vary with the ray.  The entry holds those magnitudes — obtained by running finalize_hit's
+// own operations here — and, for each of the eight sign combinations, v and u evaluated exactly as shade_hit's merged Lambertian arm
+// writes them.  The kernel uses a slot only when |rec.n| equals mag bit for bit, so a slot is by construction what the formula gives on
+// those very bits: which entries are valid decides how often the memo hits, never what a sample is.  This translation unit is compiled
+// with -ffp-contract=off (Makefile) and IEEE divide / sqrt round correctly on host and device: the same facts the per-sample parity
+// with the CPU oracle rests on.  RT_NO_ONB_TABLE (A/B runs, tests): every entry invalid.
+void onb_slot(const double w0[3], double vu[6]) {
+    auto norm = [](const double a[3], double o[3]) { const double l = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); for (int k = 0; k < 3; k++) o[k] = a[k] / l; };
+    auto cross = [](const double a[3], const double b[3], double o[3]) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; };
+    double w[3], c[3];
+    norm(w0, w);                                                            // onb.rs:10
+    const double ay[3] = {0.0, 1.0, 0.0}, ax[3] = {1.0, 0.0, 0.0};
+    cross(w, std::fabs(w[0]) > 0.9 ? ay : ax, c);
+    norm(c, vu);                                                            // v
+    cross(w, vu, vu + 3);                                                   // u
+}
+void build_onb_table(HostFlat& f) {
+    DOnbEntry none; std::memset((void*)&none, 0, sizeof(none));
+    for (int k = 0; k < 3; k++) none.mag[k] = ONB_MAG_INVALID;
+    f.onb.assign(f.rects.size(), none);
+    f.onb_any = false;
+    if (f.feats != 0u || std::getenv("RT_NO_ONB_TABLE")) return;
+    // per rect: the chain it is reached through — 0 none yet, 1 no rotation (bare / FlipNormals only), 2 + first_op the fused idiom,
+    // ~0 more than one chain or any other chain (invalid)
+    const uint64_t OTHER = ~0ull;
+    std::vector<uint64_t> how(f.rects.size(), 0ull);
+    for (const DObject& o : f.objects) {
+        if (o.geom_kind != G_RECT) continue;
+        uint64_t h = OTHER;
+        if (o.medium < 0 && (o.n_ops == 0u || (o.nest & 0x10000u))) h = 1ull;
+        else if (o.medium < 0 && o.n_ops == 2u && (size_t)o.first_op + 1u < f.ops.size() && f.ops[o.first_op].kind == OP_TRANSLATE &&
+                 f.ops[o.first_op + 1u].kind == OP_ROTATE && f.ops[o.first_op + 1u].axis == 1u) h = 2ull + o.first_op;
+        for (uint32_t r = 0; r < o.geom_count && (size_t)o.geom_first + r < how.size(); r++) {
+            uint64_t& x = how[(size_t)o.geom_first + r];
+            x = (x == 0ull || x == h) ? h : OTHER;
+        }
+    }
+    for (size_t i = 0; i < f.rects.size(); i++) {
+        if (how[i] == 0ull || how[i] == OTHER || f.rects[i].plane > 2u) continue;
+        double n[3] = {0.0, 0.0, 0.0};
+        n[2u - f.rects[i].plane] = 1.0;                                     // rect.rs:70-76
+        if (how[i] >= 2ull) {                                               // rotate.rs:95-99 (rt_kernel.hip rot_back, axis 1)
+            const DOp<double>& op = f.ops[(size_t)(how[i] - 2ull) + 1u];
+            const double a = n[0], b = n[2];
+            n[0] = op.y * a + op.x * b; n[2] = (-op.x) * a + op.y * b;
+        }
+        DOnbEntry& e = f.onb[i];
+        bool ok = true;
+        for (int k = 0; k < 3; k++) { const double m = std::fabs(n[k]); std::memcpy(&e.mag[k], &m, 8); ok = ok && !std::isnan(m); }
+        if (!ok) { e = none; continue; }
+        for (int s = 0; s < 8; s++) {
+            double w[3];
+            for (int k = 0; k < 3; k++) w[k] = std::copysign(std::fabs(n[k]), ((s >> k) & 1) ? -1.0 : 1.0);
+            onb_slot(w, e.slot[s]);
+        }
+        f.onb_any = true;
+    }
+}
+
 } // namespace
 
 // Worlds that are ONE bare BVH (every ray walks the tree: the random-spheres scene): which inner nodes leave the filter tree is decided by
@@ -807,6 +870,7 @@ bool flatten_scene(Scene& s) {
         for (const HNode& h : s.nodes) if (h.kind == HNode::CUBE) for (int k = 0; k < 3; k++) ok = ok && h.v[k] <= h.v[3 + k];
         s.flat.rect_m = ok ? m : 0.0f;
     }
+    build_onb_table(s.flat);
     s.flat_valid = true;
     return true;
 }

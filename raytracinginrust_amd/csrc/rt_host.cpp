@@ -55,7 +55,7 @@ static void free_dev(void*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
 static void free_on_device(void*& p, int device) { if (p) { DeviceGuard guard(device); (void)hipDeviceSynchronize(); free_dev(p); } }
 template <typename T> static void free_device_scene(DeviceScene<T>& d) {
     free_dev(d.objects); free_dev(d.ops); free_dev(d.rects); free_dev(d.spheres); free_dev(d.mspheres); free_dev(d.tris);
-    free_dev(d.bvh); free_dev(d.materials); free_dev(d.textures); free_dev(d.media); free_dev(d.lights); free_dev(d.perlins); free_dev(d.image); free_dev(d.pbr); free_dev(d.bvh_f);
+    free_dev(d.bvh); free_dev(d.materials); free_dev(d.textures); free_dev(d.media); free_dev(d.lights); free_dev(d.perlins); free_dev(d.image); free_dev(d.pbr); free_dev(d.bvh_f); free_dev(d.onb);
     d.valid = false;
 }
 
@@ -417,6 +417,25 @@ int rt_debug_filter_nodes(rt_scene* sc, float* boxes6_out, uint32_t* links2_out,
     return (int)f.bvh_f.size();
 }
 
+// Test aid (host only): the per-face ONB memo as flattened (rt_ir.h DOnbEntry, rt_flatten.cpp build_onb_table), one entry per rect record:
+// mag_out[3*i ..] = the bit patterns of |n| (all ones: invalid), slots_out[48*i + 6*s ..] = {v[3], u[3]} for the sign bits s.  Returns the
+// number of rects, *n_valid_out the number of valid entries; -1 on error.
+int rt_debug_onb_table(rt_scene* sc, uint64_t* mag_out, double* slots_out, uint32_t max_rects, uint32_t* n_valid_out) {
+    if (!sc) return set_err("null argument");
+    if (!flatten_for_render(sc->s)) return -1;
+    const HostFlat& f = sc->s.flat;
+    uint32_t n_valid = 0;
+    for (size_t i = 0; i < f.onb.size(); i++) {
+        const DOnbEntry& e = f.onb[i];
+        if (e.mag[0] != ONB_MAG_INVALID) n_valid++;
+        if (i >= max_rects) continue;
+        if (mag_out) for (int k = 0; k < 3; k++) mag_out[3 * i + k] = e.mag[k];
+        if (slots_out) std::memcpy(slots_out + 48 * i, e.slot, sizeof(e.slot));
+    }
+    if (n_valid_out) *n_valid_out = n_valid;
+    return (int)f.onb.size();
+}
+
 uint32_t rt_local_tiles(uint32_t W, uint32_t H, uint32_t tile_px, uint32_t rank, uint32_t world) {
     (void)rank;
     if (tile_px == 0 || world == 0) return 0;
@@ -487,6 +506,8 @@ template <typename T> int ensure_uploaded(Scene& s, DeviceScene<T>& d) {
     if (upload_raw(pl, d.perlins)) return -1;
     if (upload_vec<DPbr<T>>(s.pbr, d.pbr)) return -1;
     if (upload_raw(s.image_bytes, d.image)) return -1;
+    d.onb = nullptr;                       // the ONB memo: f64 tables only, and only when some entry is valid (the kernel tests the pointer)
+    if (sizeof(T) == 8u && f.onb_any) { std::vector<DOnbEntry> ot(f.onb); ot.push_back(DOnbEntry{}); if (upload_raw(ot, d.onb)) return -1; }
     d.valid = true;
     return 0;
 }
@@ -633,7 +654,7 @@ template <typename T> void bind_tables(KParams<T>& P, const DeviceScene<T>& d, c
     P.ops = (const DOp<T>*)d.ops; P.rects = (const DRect<T>*)d.rects; P.spheres = (const DSphere<T>*)d.spheres;
     P.mspheres = (const DMSphere<T>*)d.mspheres; P.tris = (const DTri<T>*)d.tris; P.bvh = (const DBvhNode<T>*)d.bvh;
     P.n_bvh = (uint32_t)f.bvh.size();
-    P.bvh_f = (const DFNode*)d.bvh_f; P.filter_m = f.filter_m; P.rect_m = f.rect_m;
+    P.bvh_f = (const DFNode*)d.bvh_f; P.filter_m = f.filter_m; P.rect_m = f.rect_m; P.onb = (const DOnbEntry*)d.onb;
     P.materials = (const DMaterial<T>*)d.materials; P.textures = (const DTexture<T>*)d.textures; P.media = (const DMedium<T>*)d.media;
     P.lights = (const DLight*)d.lights; P.n_lights = f.n_lights;
     P.perlins = (const DPerlin<T>*)d.perlins; P.pbr = (const DPbr<T>*)d.pbr; P.image_bytes = (const uint8_t*)d.image;
@@ -1090,6 +1111,18 @@ int rt_debug_light_pdf(rt_scene* sc, uint32_t n, const double* origins, const do
     Scene& s = sc->s;
     if (!flatten_for_render(s)) return -1;
     return run_kat(s, launch_light_pdf_kat, n, origins, 24u, dirs, 24u, out, 8u);
+}
+// Known-answer access to the per-face ONB memo of the lean f64 kernel (rt_kernel.hip onb_memo_probe / onb_memo_load, the functions the
+// merged Lambertian arm calls): n pairs of (rect index, normal).  rects: n doubles (the index as a number), normals: n x 3;
+// out: n x 7 = memo hit (0 / 1), v[3], u[3] (zeros on a miss).  A scene without a valid entry misses everywhere.  Host pointers.
+int rt_debug_onb(rt_scene* sc, uint32_t n, const double* rects, const double* normals, double* out) {
+    if (!sc || !rects || !normals || !out) return set_err("null argument");
+    if (n == 0) return 0;
+    Scene& s = sc->s;
+    if (!flatten_for_render(s)) return -1;
+    for (uint32_t i = 0; i < n; i++)
+        if (!(rects[i] >= 0.0 && rects[i] < (double)s.flat.rects.size() && rects[i] == std::floor(rects[i]))) return set_err("rt_debug_onb: rect index out of range");
+    return run_kat(s, launch_onb_kat, n, rects, 8u, normals, 24u, out, 56u);
 }
 int rt_debug_trace_path(rt_scene* sc, long long local_pixel, long long sample) {
     if (!sc) return set_err("null argument");

@@ -93,6 +93,12 @@ template <typename T> struct DPbr { T metallic, subsurface, specular, roughness,
 template <typename T> struct alignas(16) DTexture { uint32_t kind, a, b, c; T color[3]; T scale; }; // check: a = odd, b = even; noise: a = perlin; image: a = byte offset, b = width, c = height
 template <typename T> struct DMedium { T neg_inv_density; uint32_t mat, pad; };               // -(1.0/density), src/medium.rs:42
 struct DLight { uint32_t kind, index; };
+// Per-face ONB memo of the lean f64 list-scene kernel (rt_flatten.cpp build_onb_table, rt_kernel.hip onb_memo_probe), one entry per rect
+// record: mag = the bit patterns of |n.x|, |n.y|, |n.z| of the hit normal this rect's owner produces (all ones: no valid entry — a word
+// with its sign bit set, which a sign-masked word never equals), slot[s] = {v[3], u[3]} of onb.rs:8-20 for that normal with the sign
+// bits s = sx | sy << 1 | sz << 2.  416 B, 16-byte aligned pieces.
+struct alignas(16) DOnbEntry { uint64_t mag[3]; uint64_t pad; double slot[8][6]; };
+static const uint64_t ONB_MAG_INVALID = ~0ull;
 template <typename T> struct DPerlin { T rd_vec[256 * 3]; uint8_t perm_x[256], perm_y[256], perm_z[256]; };   // src/perlin.rs:59-65
 template <typename T> struct DCamera {                                                        // src/camera.rs:6-16
     T origin[3], lower_left_corner[3], horizontal[3], vertical[3], cu[3], cv[3];
@@ -155,6 +161,9 @@ template <typename T> struct KParams {
     // plane distance can be NaN, and a NaN hit makes HittableList::hit depend on the order of the items — searches that list instead
     // (rt_kernel.hip: world_hit_list).  0: none.
     uint32_t n_objects_alt;
+    // Per-face ONB memo (DOnbEntry, above): onb[i] belongs to rects[i]; null when the scene has no valid entry (every f32 scene, every
+    // scene with a feature bit, RT_NO_ONB_TABLE).  Read by the lean f64 kernel's merged Lambertian arm only.
+    const DOnbEntry* onb;
 };
 
 } // namespace rt

@@ -1046,6 +1046,29 @@ template <typename T> DEV void sphere_uv(V3<T> p, T& u, T& v) {
 // (u, v) are read by ImageTexture alone; the flag rides on the material's kind word (rt_ir.h)
 template <typename T> DEV bool mat_reads_uv(const KParams<T>& P, uint32_t mat) { return (cl(&P.materials[mat].kind) & MAT_NEEDS_UV) != 0u; }
 
+// ---- the per-face ONB memo (rt_ir.h DOnbEntry, rt_flatten.cpp build_onb_table; lean f64 kernel, merged Lambertian arm)
+// v and u of onb.rs:8-20 are pure functions of the hit normal's 192 bits.  The flattener stores, per rect, the magnitudes the normal of
+// that rect's hits has and v, u for each of the eight sign combinations, evaluated by the same IEEE operations without contraction.
+// The probe compares the three SIGN-MASKED WORDS of the normal with the stored magnitudes as integers (an f64 == would call -0 and +0
+// equal and NaN unequal to itself; as words every pattern, NaNs included, is just itself, and the invalid entry's all-ones word has the
+// sign bit a masked word never has) and picks the slot by the three sign bits: on a hit the slot holds exactly what the formula gives on
+// these very bits, whatever chain, zero sign or hostile normal produced them; anything else is a miss and runs the arithmetic.
+DEV bool onb_memo_probe(const DOnbEntry* tab, uint32_t rect, V3<double> n, const double*& slot) {
+    const unsigned long long S = 0x7FFFFFFFFFFFFFFFull;
+    const unsigned long long bx = (unsigned long long)__double_as_longlong(n.x), by = (unsigned long long)__double_as_longlong(n.y), bz = (unsigned long long)__double_as_longlong(n.z);
+    const DOnbEntry* e = tab + rect;
+    typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
+    const ull2 m01 = *(const CAS ull2*)&e->mag[0];
+    const unsigned long long m2 = cl((const unsigned long long*)&e->mag[2]);
+    slot = e->slot[(uint32_t)(bx >> 63) | ((uint32_t)(by >> 63) << 1) | ((uint32_t)(bz >> 63) << 2)];
+    return (bx & S) == m01.x && (by & S) == m01.y && (bz & S) == m2;
+}
+DEV void onb_memo_load(const double* slot, V3<double>& v, V3<double>& u) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    const d2 a = *(const CAS d2*)slot, b = *(const CAS d2*)(slot + 2), c = *(const CAS d2*)(slot + 4);
+    v = mk<double>(a.x, a.y, b.x); u = mk<double>(b.y, c.x, c.y);
+}
+
 // Rebuild the full HitRecord of the winning (object, primitive, t): the same arithmetic the reference runs
 // eagerly inside every `hit`, run once.  Per-lane gathers: lanes may hold different objects.
 template <typename T, uint32_t FEATS>
@@ -1684,9 +1707,10 @@ DEV double rng_range_of(uint64_t u, double a, double b) {
 }
 // ------------------------------------------------------------------ one level of ray_color after the hit: main.rs:50-116
 // In: the hit record.  In/out: ray (becomes the scattered ray), beta, rng, depth_left.  Out: done (the path ends here) and
-// e, the terminal radiance to be multiplied by beta.
+// e, the terminal radiance to be multiplied by beta.  rect: the rect record the hit came from — read by the lean f64 kernel only (every hit
+// of a list scene is a rect's), where it names the hit's entry in the ONB memo; the other callers leave it out.
 template <typename T, uint32_t FEATS>
-DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& beta, Rng& rng, uint32_t& depth_left, bool& done, V3<T>& e) {
+DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& beta, Rng& rng, uint32_t& depth_left, bool& done, V3<T>& e, uint32_t rect = 0u) {
     const DMaterial<T> mt = ld_mat(P.materials + rec.mat);
     // Lambertian (its two sampling arms) and Metal in one instruction stream where they run the same instructions on their own
     // values — per lane the operations and the draw order are exactly those of the separate arms below (bit-identical samples):
@@ -1705,8 +1729,16 @@ DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& 
         if (lam) {                                                          // mat.rs:225-249, main.rs:92-98
             attenuation = const_or_tex<T, FEATS>(P, mt, rec);
             V3<T> a = (m_abs(uvw.w.x) > T(0.9)) ? mk<T>(T(0), T(1.0), T(0)) : mk<T>(T(1.0), T(0), T(0));   // onb.rs:8-20
+            // the ONB memo: WAVE-level — when every Lambertian lane of the wave (the lanes active here) finds its normal in its rect's
+            // entry, v and u are loaded and the second normalisation and both cross products are not executed; otherwise all of them
+            // run the arithmetic.  No per-lane select between two computed results.
+            bool memo = false; const double* slot = nullptr;
+            if constexpr (FEATS == 0u) if (P.onb != nullptr) memo = __ballot(!onb_memo_probe(P.onb, rect, rec.n, slot)) == 0ull;
+            if (memo) onb_memo_load(slot, uvw.v, uvw.u);
+            else {
             uvw.v = normalized(cross(uvw.w, a));
             uvw.u = cross(uvw.w, uvw.v);
+            }
             if (P.n_lights != 0u && rng_bool(rng)) {                        // pdf.rs:167-173 (no lights: deviation D2, cosine only)
                 to_light = true;
                 if constexpr (Nested<FEATS>::on) L = light_pick<T>(P, rng);
@@ -1964,7 +1996,8 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
                         o[12] = (double)ray.d.x; o[13] = (double)ray.d.y; o[14] = (double)ray.d.z; o[15] = 1.0;
                     }
 #endif
-                    shade_hit<T, FEATS>(P, rec, ray, beta, rng, depth_left, done, e);
+                    if constexpr (FEATS == 0u) shade_hit<T, FEATS>(P, rec, ray, beta, rng, depth_left, done, e, id.prim & 0x0FFFFFFFu);
+                    else shade_hit<T, FEATS>(P, rec, ray, beta, rng, depth_left, done, e);
                 }
             }
             DIAG_ADD(4);
@@ -2343,6 +2376,22 @@ __global__ void list_hit_kat_kernel(const KParams<double> P, uint32_t n, const d
         o[0] = any ? 1.0 : 0.0; o[1] = any ? rec.t : 0.0; o[2] = rec.p.x; o[3] = rec.p.y; o[4] = rec.p.z; o[5] = rec.n.x; o[6] = rec.n.y; o[7] = rec.n.z;
         o[8] = rec.front ? 1.0 : 0.0; o[9] = any ? (double)id.obj : -1.0; o[10] = any ? (double)(id.prim & 0x0FFFFFFFu) : -1.0; o[11] = any ? (double)rec.mat : -1.0;
     }
+}
+// Known-answer access to the ONB memo (rt_debug_onb): the two device functions the merged Lambertian arm calls, one (rect, normal) pair
+// per lane; per lane — no vote: a test wants each pair's own answer.  out[7 i ..] = hit, v[3], u[3].
+__global__ void onb_kat_kernel(const KParams<double> P, uint32_t n, const double* rects, const double* normals, double* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    V3<double> v = mk<double>(0.0, 0.0, 0.0), u = v;
+    const double* slot = nullptr;
+    const bool hit = P.onb != nullptr && onb_memo_probe(P.onb, (uint32_t)rects[i], mk<double>(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]), slot);
+    if (hit) onb_memo_load(slot, v, u);
+    double* o = out + 7ull * i;
+    o[0] = hit ? 1.0 : 0.0; o[1] = v.x; o[2] = v.y; o[3] = v.z; o[4] = u.x; o[5] = u.y; o[6] = u.z;
+}
+hipError_t launch_onb_kat(const KParams<double>& P, uint32_t n, const double* d_rects, const double* d_normals, double* d_out, hipStream_t stream) {
+    hipLaunchKernelGGL(onb_kat_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_rects, d_normals, d_out);
+    return hipGetLastError();
 }
 hipError_t launch_list_hit_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream) {
     hipLaunchKernelGGL(list_hit_kat_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_rays, d_tlim, d_out);

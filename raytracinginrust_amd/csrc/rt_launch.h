@@ -24,6 +24,8 @@ static const size_t RT_STATS_BYTES = (size_t)RT_STATS_SLOTS * RT_STATS_ROWS * si
 template <typename T> hipError_t launch_pathtrace(const KParams<T>& P, uint32_t scene_feats, uint32_t n_blocks, size_t shmem, hipStream_t stream);
 // Known-answer access to the list-scene kernels' closest-hit search (rt_debug_list_hit; the kernel lives in the lean translation unit)
 hipError_t launch_list_hit_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream);
+// Known-answer access to the per-face ONB memo as the lean f64 kernel's Lambertian arm reads it (rt_debug_onb; the lean translation unit)
+hipError_t launch_onb_kat(const KParams<double>& P, uint32_t n, const double* d_rects, const double* d_normals, double* d_out, hipStream_t stream);
 // Known-answer access to the lights' pdf_value as the F_ALL | F_NESTED kernels compute it (rt_debug_light_pdf; the "rest" translation unit)
 hipError_t launch_light_pdf_kat(const KParams<double>& P, uint32_t n, const double* d_o, const double* d_v, double* d_out, hipStream_t stream);
 // Resident blocks per CU for the instantiation that serves `scene_feats`.

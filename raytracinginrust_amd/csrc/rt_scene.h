@@ -41,6 +41,8 @@ struct HostFlat {             // canonical f64 flattening
     uint32_t feats = 0;
     uint32_t bvh_depth = 0;
     bool bvh_tame = true;          // all BVH boxes finite, |.| < 1e300 (1e30 matters for the f32 variant: checked there too), min <= max
+    std::vector<DOnbEntry> onb;    // per-face ONB memo, one entry per rect (rt_flatten.cpp build_onb_table); onb_any: some entry is valid
+    bool onb_any = false;
 };
 
 template <typename T> struct DeviceScene {   // device copies of HostFlat for one arithmetic type
@@ -48,6 +50,7 @@ template <typename T> struct DeviceScene {   // device copies of HostFlat for on
     void* objects = nullptr; void* ops = nullptr; void* rects = nullptr; void* spheres = nullptr; void* mspheres = nullptr;
     void* tris = nullptr; void* bvh = nullptr; void* materials = nullptr; void* textures = nullptr; void* media = nullptr;
     void* lights = nullptr; void* perlins = nullptr; void* image = nullptr; void* pbr = nullptr; void* bvh_f = nullptr;
+    void* onb = nullptr;           // f64 only, and only when HostFlat::onb_any
 };
 
 struct Scene {

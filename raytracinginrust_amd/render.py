@@ -75,6 +75,36 @@ def debug_object_rows(b: SceneBuilder):
     return out[:n], int(n_top.value)
 
 
+ONB_MAG_INVALID = 0xFFFFFFFFFFFFFFFF
+
+
+def debug_onb_table(b: SceneBuilder):
+    """rt_debug_onb_table (host only): the per-face ONB memo of the lean f64 list-scene kernel as flattened, one entry per rect record:
+    (mag (n, 3) uint64 — the bit patterns of |n| of the hit normal, ONB_MAG_INVALID in all three for an invalid entry —,
+    slots (n, 8, 2, 3) float64 — [sign bits sx | sy << 1 | sz << 2][v, u] —, the number of valid entries)."""
+    n_valid = C.c_uint32(0)
+    n = _rt().rt_debug_onb_table(b.h, None, None, 0, C.byref(n_valid))
+    if n < 0:
+        raise RenderError(_err())
+    mag = np.zeros((max(n, 1), 3), np.uint64)
+    slots = np.zeros((max(n, 1), 8, 2, 3), np.float64)
+    if _rt().rt_debug_onb_table(b.h, mag.ctypes.data, slots.ctypes.data, n, C.byref(n_valid)) != n:
+        raise RenderError(_err())
+    return mag[:n], slots[:n], int(n_valid.value)
+
+
+def debug_onb(b: SceneBuilder, rects: np.ndarray, normals: np.ndarray):
+    """rt_debug_onb (needs a GPU): the memo as the kernel's Lambertian arm reads it, for n pairs of (rect index, normal):
+    (hit (n,) bool, v (n, 3), u (n, 3)); v and u are zero on a miss."""
+    r = np.ascontiguousarray(rects, np.float64).reshape(-1)
+    nm = np.ascontiguousarray(normals, np.float64).reshape(-1, 3)
+    if len(r) != len(nm):
+        raise ValueError("rects and normals differ in length")
+    out = np.zeros((len(r), 7), np.float64)
+    _check(_rt().rt_debug_onb(b.h, len(r), r.ctypes.data, nm.ctypes.data, out.ctypes.data))
+    return out[:, 0] != 0.0, out[:, 1:4].copy(), out[:, 4:7].copy()
+
+
 def debug_light_pdf(b: SceneBuilder, origins: np.ndarray, dirs: np.ndarray) -> np.ndarray:
     """rt_debug_light_pdf (needs a GPU): the scene's `lights` pdf_value (HittableList::pdf_value, nested lists included) for n
     (origin, direction) pairs, computed on the device by the function the all-features kernel with object leaves runs."""
