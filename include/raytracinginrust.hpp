@@ -210,6 +210,36 @@ inline std::vector<Hit> query_camera(Scene& s, const Camera& cam, uint32_t W, ui
     return out;
 }
 
+// The same query as the raw records rt_query_camera writes, 16 doubles per pixel: what `denoise` takes as its guide.
+inline std::vector<double> query_camera_records(Scene& s, const Camera& cam, uint32_t W, uint32_t H, uint32_t sample = 0, uint64_t seed = 0x5EED) {
+    std::vector<double> rec((size_t)W * H * 16);
+    if (rt_query_camera(s.raw(), &cam.c, W, H, sample, seed, 0, nullptr, rec.data()) != 0) throw Error(rt_last_error());
+    return rec;
+}
+
+// Denoising (rt_denoise*): an edge-avoiding a-trous wavelet filter over a frame of sums, guided by query_camera_records — K iterations of a
+// 5x5 B3 kernel dilated by 2^i, with stops on colour (sigma_c), normal (sigma_n), plane distance relative to the hit distance (sigma_p) and
+// hit / miss (with RT_DENOISE_SAME_MATERIAL: the material too).  The defaults are render.py's (DESIGN.md §14's error table).  Returns sums
+// again (mean times samples): write_ppm takes them with the same sample count.
+struct DenoiseSettings {
+    uint32_t iterations = 2; double sigma[3] = {4.0, 0.5, 0.02}; uint32_t flags = 0;
+};
+inline std::vector<double> denoise(const std::vector<double>& rgb_sum, uint64_t samples, const std::vector<double>& hit_records, uint32_t W, uint32_t H,
+                                   const DenoiseSettings& d = DenoiseSettings()) {
+    if (rgb_sum.size() != (size_t)W * H * 3 || hit_records.size() != (size_t)W * H * 16) throw Error("denoise: frame or records of another size");
+    std::vector<double> out(rgb_sum.size());
+    if (rt_denoise(rgb_sum.data(), samples, hit_records.data(), W, H, d.iterations, d.sigma, d.flags, out.data()) != 0) throw Error(rt_last_error());
+    return out;
+}
+// the host twin: the same words without a device
+inline std::vector<double> denoise_host(const std::vector<double>& rgb_sum, uint64_t samples, const std::vector<double>& hit_records, uint32_t W, uint32_t H,
+                                        const DenoiseSettings& d = DenoiseSettings()) {
+    if (rgb_sum.size() != (size_t)W * H * 3 || hit_records.size() != (size_t)W * H * 16) throw Error("denoise_host: frame or records of another size");
+    std::vector<double> out(rgb_sum.size());
+    if (rt_denoise_host(rgb_sum.data(), samples, hit_records.data(), W, H, d.iterations, d.sigma, d.flags, out.data()) != 0) throw Error(rt_last_error());
+    return out;
+}
+
 // ray_color (src/main.rs:41-120) along rays the caller chooses (rt_query_radiance), samples_per_ray samples of each: per ray the SUM over
 // its samples, n x 3, as render() returns per pixel — another projection than Camera's, a light probe, a baked light map.  Sample s of ray k
 // draws from the stream of rt_rng_path(seed, k, s).  samples_out (optional) receives every sample, ray-major; nonfinite_out (optional) the
@@ -254,6 +284,10 @@ public:
     uint64_t samples() const { uint64_t n = 0; chk(rt_progressive_samples(p_, &n)); return n; }
     // format_color(samples()) of every pixel, W*H*3 bytes in output order; changed_px: pixels that differ from the previous resolve
     std::vector<uint8_t> rgb8(uint64_t* changed_px = nullptr) { std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_rgb8(p_, out.data(), changed_px)); return out; }
+    // the frame as it is now through `denoise` and format_color on the device (the frame builds and keeps its own guide); rgb8 and its count are untouched
+    std::vector<uint8_t> rgb8_denoised(const DenoiseSettings& d = DenoiseSettings()) {
+        std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_denoised_rgb8(p_, d.iterations, d.sigma, d.flags, out.data())); return out;
+    }
     std::vector<double> sum() const { std::vector<double> out(n_px_ * 3); chk(rt_progressive_read_sum(p_, out.data())); return out; }
     void load(const std::vector<double>& rgb_sum, uint64_t samples_done) {
         if (rgb_sum.size() != n_px_ * 3) throw Error("checkpoint of another frame size");

@@ -308,6 +308,42 @@ int rt_query_radiance_device(rt_scene*, uint32_t n, const void* d_rays, const do
                              void* d_rgb_sum, size_t d_rgb_sum_bytes, void* d_samples_out, void* d_nonfinite_out,
                              void* hip_stream);
 
+/* ---- denoising: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a frame of per-pixel sums, guided by the hit records
+ *      of rt_query_camera (sample 0's camera ray: normal, position, hit distance, hit / material) — what the 16 .. 64 samples of a preview
+ *      need.  A 5x5 B3-spline kernel, dilated by 2^i in iteration i, with stops on colour, normal, plane distance (relative to the centre's
+ *      hit distance: sigma_p has no scene scale) and a hit / material key.  The filter is an exact f64 specification (csrc/rt_denoise.h: only
+ *      + - * / and comparisons, a fixed order) that the HIP kernels (csrc/rt_denoise.hip) and the host twin below satisfy bit for bit.
+ * rgb_sum: W*H*3 doubles in output order, as rt_render returns them; samples >= 1: how many samples they hold; hits: W*H records of 16 doubles,
+ * as rt_query_camera returns them; iterations: 1 .. 8; sigma = {sigma_c, sigma_n, sigma_p}: each > 0, +inf switches that stop off (0, negative
+ * and NaN are errors); flags: RT_DENOISE_SAME_MATERIAL or 0.  rgb_sum_out: W*H*3 doubles, the filtered frame in SUM units again (mean times
+ * samples), so that rt_write_ppm, rt_format_color and the resolve apply to it unchanged; it may be rgb_sum itself.  W, H >= 1, W*H <= 2^31 - 1.
+ * Non-finite input pixels are left out as neighbours and, as centres, take their neighbours' values: the filter repairs NaN pixels.
+ * Not done: guides beyond sample 0's camera ray (no averaging over the lens or the pixel), albedo demodulation (textured surfaces rely on
+ * sigma_c).  Errors (non-zero, a message for rt_last_error, nothing written): null arguments and everything outside the ranges above. */
+enum { RT_DENOISE_SAME_MATERIAL = 1 /* pixels are neighbours only if their hits have the same material handle (default: only hit beside hit, miss beside miss) */ };
+/* The host twin: the specification as plain C++; needs no device. */
+int rt_denoise_host(const double* rgb_sum, uint64_t samples, const double* hits, uint32_t W, uint32_t H, uint32_t iterations,
+                    const double sigma[3], uint32_t flags, double* rgb_sum_out);
+/* The same call, the same words, computed on the current HIP device (host pointers; synchronous).  Fails without a device, as rt_render does. */
+int rt_denoise(const double* rgb_sum, uint64_t samples, const double* hits, uint32_t W, uint32_t H, uint32_t iterations,
+               const double sigma[3], uint32_t flags, double* rgb_sum_out);
+/* Bytes of device memory rt_denoise_device needs as its workspace for a W x H frame: 128 per pixel (two padded colour frames, one packed guide). */
+size_t rt_denoise_workspace_bytes(uint32_t W, uint32_t H);
+/* The same filter for DEVICE pointers on the current device: d_rgb_sum and d_rgb_sum_out 8-byte aligned (they may be the same buffer), d_hits and
+ * d_workspace 16-byte aligned, sigma a HOST pointer.  Only enqueues on hip_stream (a hipStream_t, may be NULL): it never waits and never
+ * allocates.  A workspace smaller than rt_denoise_workspace_bytes(W, H) is an error before anything is launched. */
+int rt_denoise_device(const void* d_rgb_sum, uint64_t samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
+                      const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, void* hip_stream);
+/* A progressive frame's sums as they are now, filtered and resolved on the device: rgb8_out receives W*H*3 bytes, format_color of the
+ * filtered sums — byte for byte rt_format_color of rt_denoise_host(rt_progressive_read_sum, rt_progressive_samples, rt_query_camera(sample 0,
+ * the frame's seed)).  The frame builds the packed guide itself at the first call (rt_query_camera_device on its device; what rt_last_query_ms
+ * reports for the scene is that launch then) and keeps it until rt_progressive_reset; another `flags` than the guide was keyed for rebuilds it.
+ * Everything happens in buffers of the frame's own, allocated at the first call (155 bytes per pixel) and freed by rt_progressive_destroy:
+ * the accumulated sums, the images of rt_progressive_resolve_rgb8* and its changed-pixel count are untouched, and the two kinds of resolve may
+ * be interleaved freely.  Waits for every pass enqueued so far.  Errors: the arguments of rt_denoise; a frame of 0 samples; a scene that is
+ * gone, or has changed, while the frame holds no guide (with a guide the frame still resolves after its scene is destroyed). */
+int rt_progressive_resolve_denoised_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out);
+
 /* The whole frame on several GPUs of this node from ONE call: what a host that owns the node's GPUs itself (the reference's `main`,
  * src/main.rs:767-835) calls instead of rt_render.  device_mask: bit d selects HIP device d (0 = every visible device).  The scene
  * is replicated on each selected device; tiles of tile_px output-order pixels (0 = the default, 67) are dealt round-robin, each
@@ -404,6 +440,10 @@ int rt_last_leaf_steps(rt_scene*, unsigned long long out2[2]);
 /* Diagnostic builds (-DRT_DIAG) only (zeros in a normal build): [0..5] wave-cycle sums of the six kernel sections, [6] rect tests
  * counted per wavefront, [7] those among them in which no lane's plane distance lay in [t_min, closest] (-DRT_DIAG_RECTS builds). */
 int rt_debug_section_cycles(rt_scene*, unsigned long long out8[8]);
+/* Measuring aid (tools/denoise_probe.py): rt_denoise_device on the null stream, synchronously, once to warm up and once with HIP events between its
+ * launches: ms_out[0] = the pack kernel, ms_out[1 + i] = iteration i (iterations + 1 floats). */
+int rt_debug_denoise_ms(const void* d_rgb_sum, uint64_t samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
+                        const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, float* ms_out);
 /* Test aid (host only, no GPU): what rt_scene_calibrate does to the filter tree of a world that is ONE bare BVH — inner nodes leave it by
  * their estimated pass rate for the view instead of by box areas (rt_flatten.cpp tune_filter_tree; scheduling only: any conservative
  * hierarchy over the leaves gives the same samples) — without touching a device copy.  1: rebuilt, 0: not that kind of scene, -1: error. */

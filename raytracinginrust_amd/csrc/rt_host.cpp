@@ -17,6 +17,7 @@
 #include "rt_resolve.h"
 #include "rt_query.h"
 #include "rt_radiance.h"
+#include "rt_denoise.h"
 
 using namespace rt;
 
@@ -40,6 +41,11 @@ struct Progressive {
     void* d_sum = nullptr;                 // W*H*3 doubles, output order
     void* d_rgb8[2] = {nullptr, nullptr}; int cur = 0; bool have_prev = false, resolved = false;     // d_rgb8[cur]: the most recent resolve
     void* d_changed = nullptr;             // one 64-bit word: the most recent resolve's changed-pixel count
+    // rt_progressive_resolve_denoised_rgb8's own buffers, allocated at its first call: the filter's workspace (two packed colour frames and
+    // the packed guide, rt_denoise.h), the filtered sums, their RGB8 image and the count word its resolve launch needs.  The guide — sample
+    // 0's camera hits of this view, keyed for guide_flags — is built once and kept until rt_progressive_reset.
+    void* d_dn_ws = nullptr; void* d_dn_sum = nullptr; void* d_dn_rgb8 = nullptr; void* d_dn_changed = nullptr;
+    bool guide_valid = false; uint32_t guide_flags = 0;
     size_t n_px() const { return (size_t)W * H; }
 };
 
@@ -1405,6 +1411,7 @@ static void progressive_free(Progressive* p) {
     DeviceGuard guard(p->device);
     (void)hipDeviceSynchronize();                   // passes and resolves may still be in flight on the caller's streams
     free_dev(p->d_sum); free_dev(p->d_rgb8[0]); free_dev(p->d_rgb8[1]); free_dev(p->d_changed);
+    free_dev(p->d_dn_ws); free_dev(p->d_dn_sum); free_dev(p->d_dn_rgb8); free_dev(p->d_dn_changed);
 }
 void* rt_progressive_create(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t max_depth,
                             uint64_t seed, uint32_t flags) {
@@ -1542,7 +1549,113 @@ int rt_progressive_reset(void* frame) {
     Progressive* p = (Progressive*)frame;
     if (!p) return set_err("null argument");
     if (p->sc) p->scene_version = p->sc->s.version;     // a new frame, of the scene as it is now
+    p->guide_valid = false;                             // ... and so is its denoising guide, rebuilt when it is next needed
     return progressive_restart(p, nullptr, 0);
+}
+
+// ---------------------------------------------------------------- denoiser (csrc/rt_denoise.h: the specification; rt_denoise.hip: the kernels)
+size_t rt_denoise_workspace_bytes(uint32_t W, uint32_t H) { return (size_t)W * H * DENOISE_WORKSPACE_BYTES_PER_PX; }
+
+// The launches of one run, enqueued on `stream`: pack (the colour always; the guide when d_hits is given — a progressive frame brings a guide
+// it packed earlier), then the iterations, alternating between the workspace's two colour frames, the last one writing sums to d_out.
+// The workspace is {colour A, colour B, guide}: 32 + 32 + 64 bytes per pixel.
+// `marks` (rt_debug_denoise_ms only): iterations + 2 events, recorded in front of every launch and behind the last.
+static int denoise_enqueue(const double* d_sum, uint64_t samples, const double* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
+                           const double sigma[3], uint32_t flags, double* d_out, void* d_workspace, hipStream_t stream, hipEvent_t* marks = nullptr) {
+    const size_t n = (size_t)W * H;
+    double* color[2] = {(double*)d_workspace, (double*)d_workspace + n * DENOISE_COLOR_DOUBLES};
+    double* guide = (double*)d_workspace + 2u * n * DENOISE_COLOR_DOUBLES;
+    double inv[3];
+    denoise_inverse_squares(sigma, inv);
+    if (marks) HIP_OK(hipEventRecord(marks[0], stream));
+    HIP_OK((hipError_t)launch_denoise_pack(d_sum, samples, d_hits, flags, color[0], guide, (uint32_t)n, stream));
+    for (uint32_t i = 0; i < iterations; i++) {
+        const bool last = i + 1u == iterations;
+        if (marks) HIP_OK(hipEventRecord(marks[i + 1u], stream));
+        HIP_OK((hipError_t)launch_denoise_filter(color[i & 1u], guide, last ? nullptr : color[(i + 1u) & 1u], last ? d_out : nullptr, W, H, 1u << i,
+                                                 inv[0] * (double)(1ull << (2u * i)), inv[1], inv[2], samples, stream));
+    }
+    if (marks) HIP_OK(hipEventRecord(marks[iterations + 1u], stream));
+    return 0;
+}
+int rt_denoise_device(const void* d_rgb_sum, uint64_t samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
+                      const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!d_rgb_sum || !d_hits || !sigma || !d_rgb_sum_out || !d_workspace) return set_err("null argument");
+    const std::string problem = denoise_check(samples, W, H, iterations, sigma, flags);
+    if (!problem.empty()) return set_err(problem);
+    if (workspace_bytes < rt_denoise_workspace_bytes(W, H)) return set_err("denoise: workspace too small: rt_denoise_workspace_bytes(W, H) = 128 bytes per pixel are needed");
+    if (query_aligned(d_hits, "d_hits") || query_aligned(d_workspace, "d_workspace")) return -1;
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_rgb_sum_out) & 7u) != 0u) return set_err("d_rgb_sum and d_rgb_sum_out must be 8-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    return denoise_enqueue((const double*)d_rgb_sum, samples, (const double*)d_hits, W, H, iterations, sigma, flags, (double*)d_rgb_sum_out,
+                           d_workspace, (hipStream_t)hip_stream);
+}
+int rt_denoise(const double* rgb_sum, uint64_t samples, const double* hits, uint32_t W, uint32_t H, uint32_t iterations,
+               const double sigma[3], uint32_t flags, double* rgb_sum_out) {
+    if (!rgb_sum || !hits || !sigma || !rgb_sum_out) return set_err("null argument");
+    const std::string problem = denoise_check(samples, W, H, iterations, sigma, flags);
+    if (!problem.empty()) return set_err(problem);
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
+    DeviceBuffer d_sum, d_hits, d_ws;
+    HIP_OK(d_sum.alloc(sum_bytes)); HIP_OK(d_hits.alloc(hit_bytes)); HIP_OK(d_ws.alloc(rt_denoise_workspace_bytes(W, H)));
+    HIP_OK(hipMemcpy(d_sum.get(), rgb_sum, sum_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_hits.get(), hits, hit_bytes, hipMemcpyHostToDevice));
+    if (rt_denoise_device(d_sum.get(), samples, d_hits.get(), W, H, iterations, sigma, flags, d_sum.get(), d_ws.get(), rt_denoise_workspace_bytes(W, H), nullptr)) return -1;
+    HIP_OK(hipMemcpy(rgb_sum_out, d_sum.get(), sum_bytes, hipMemcpyDeviceToHost));       // (waits for the kernels: the null stream)
+    return 0;
+}
+int rt_debug_denoise_ms(const void* d_rgb_sum, uint64_t samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
+                        const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, float* ms_out) {
+    if (!ms_out) return set_err("null argument");
+    hipEvent_t marks[DENOISE_MAX_ITERATIONS + 2u] = {};
+    const uint32_t n_marks = (iterations <= DENOISE_MAX_ITERATIONS ? iterations : 0u) + 2u;
+    int rc = 0;
+    for (uint32_t k = 0; k < n_marks && rc == 0; k++) if (hipEventCreate(&marks[k]) != hipSuccess) rc = set_err("hipEventCreate failed");
+    // (the arguments are rt_denoise_device's and are checked there; nothing is recorded for a refused call)
+    if (rc == 0) {
+        if (!d_rgb_sum || !d_hits || !sigma || !d_rgb_sum_out || !d_workspace) rc = set_err("null argument");
+        else if (rt_denoise_device(d_rgb_sum, samples, d_hits, W, H, iterations, sigma, flags, d_rgb_sum_out, d_workspace, workspace_bytes, nullptr)) rc = -1;     // the checks, and a warm run
+        else rc = denoise_enqueue((const double*)d_rgb_sum, samples, (const double*)d_hits, W, H, iterations, sigma, flags, (double*)d_rgb_sum_out, d_workspace, nullptr, marks);
+    }
+    if (rc == 0 && hipEventSynchronize(marks[iterations + 1u]) != hipSuccess) rc = set_err("hipEventSynchronize failed");
+    for (uint32_t k = 0; k <= iterations && rc == 0; k++) if (hipEventElapsedTime(&ms_out[k], marks[k], marks[k + 1u]) != hipSuccess) rc = set_err("hipEventElapsedTime failed");
+    for (uint32_t k = 0; k < n_marks; k++) if (marks[k]) (void)hipEventDestroy(marks[k]);
+    return rc;
+}
+// The frame's sums filtered and resolved, into buffers of the frame's own: d_sum, the plain resolve's two images and its count stay as they are.
+int rt_progressive_resolve_denoised_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !sigma || !rgb8_out) return set_err("null argument");
+    const std::string problem = denoise_check(p->done ? p->done : 1u, p->W, p->H, iterations, sigma, flags);
+    if (!problem.empty()) return set_err(problem);
+    if (p->done == 0) return set_err("nothing to resolve: the frame holds 0 samples (format_color divides by the sample count, src/vec.rs:126)");
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the image
+    const size_t n = p->n_px();
+    if (!p->guide_valid || p->guide_flags != flags) {
+        if (!p->sc) return set_err("the scene of this progressive frame has been destroyed and the frame holds no denoising guide for these flags: the guide is built from the scene (rt_query_camera_device)");
+        if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
+    }
+    if (!p->d_dn_ws) HIP_OK(hipMalloc(&p->d_dn_ws, rt_denoise_workspace_bytes(p->W, p->H)));
+    if (!p->d_dn_sum) HIP_OK(hipMalloc(&p->d_dn_sum, n * 3 * sizeof(double)));
+    if (!p->d_dn_rgb8) HIP_OK(hipMalloc(&p->d_dn_rgb8, n * 3));
+    if (!p->d_dn_changed) HIP_OK(hipMalloc(&p->d_dn_changed, sizeof(unsigned long long)));
+    if (!p->guide_valid || p->guide_flags != flags) {           // sample 0's camera hits of this view, packed; the records themselves are not kept
+        const size_t hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
+        DeviceBuffer d_hits;
+        HIP_OK(d_hits.alloc(hit_bytes));
+        p->guide_valid = false;
+        if (rt_query_camera_device(p->sc, &p->cam, p->W, p->H, 0u, p->seed, 0u, nullptr, d_hits.get(), hit_bytes, nullptr)) return -1;
+        HIP_OK((hipError_t)launch_denoise_pack(nullptr, 1u, (const double*)d_hits.get(), flags, nullptr, (double*)p->d_dn_ws + 2u * n * DENOISE_COLOR_DOUBLES, (uint32_t)n, nullptr));
+        HIP_OK(hipStreamSynchronize(nullptr));
+        p->guide_valid = true; p->guide_flags = flags;
+    }
+    if (denoise_enqueue((const double*)p->d_sum, p->done, nullptr, p->W, p->H, iterations, sigma, flags, (double*)p->d_dn_sum, p->d_dn_ws, nullptr)) return -1;
+    HIP_OK(hipMemsetAsync(p->d_dn_changed, 0, sizeof(unsigned long long), nullptr));
+    HIP_OK(launch_resolve_rgb8((const double*)p->d_dn_sum, p->done, nullptr, (uint8_t*)p->d_dn_rgb8, (unsigned long long*)p->d_dn_changed, (uint32_t)n, nullptr));
+    HIP_OK(hipMemcpy(rgb8_out, p->d_dn_rgb8, n * 3, hipMemcpyDeviceToHost));             // (waits for the kernels: the null stream)
+    return 0;
 }
 
 int rt_render_samples(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,

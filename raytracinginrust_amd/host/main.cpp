@@ -4,7 +4,11 @@
 // (same constructor names and argument order).  Usage mirrors `cargo run --release > image.ppm` (README.md:4):
 //
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
-//              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material FILE] [--panorama FILE] > image.ppm
+//              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material FILE] [--panorama FILE]
+//              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] > image.ppm
+//
+// --denoise K[,c,n,p] (opt-in): the frame through the edge-avoiding a-trous filter before it is written (rt_denoise: K iterations, guided by
+// sample 0's camera hits of this --seed); with --progressive the frame resolves itself denoised on the device (rt_progressive_resolve_denoised_rgb8).
 //
 // --progressive N (opt-in, one GPU): the frame in passes of N samples per pixel (rt_progressive_*), the reference's style of progress on
 // stderr (main.rs:772-775), and the same PPM bytes at the end, built from the image the device resolved.
@@ -259,6 +263,7 @@ int main(int argc, char** argv) {
     uint64_t seed = 0x5EED; uint32_t flags = RT_F64; bool fast_bvh = false;
     std::string aov_kind, aov_path;                                         // --aov KIND FILE: a feature frame instead of the image
     std::string panorama_path;                                              // --panorama FILE: the equirectangular image around lookfrom instead
+    bool want_denoise = false; DenoiseSettings dn;                          // --denoise K[,sigma_c,sigma_n,sigma_p]: filter the frame before it is written
     uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
     int gpus = 1;                                                           // --gpus N: the first N devices (0 = all) through rt_render_multi
     std::string obj_path = "teapot.obj", earth_path = "earthmap.jpg";       // the reference's asset names (main.rs:248,491)
@@ -288,9 +293,18 @@ int main(int argc, char** argv) {
             if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material") { std::fprintf(stderr, "--aov needs normal, depth or material\n%s", AOV_HELP); return 2; }
         }
         else if (a == "--panorama") panorama_path = next();
+        else if (a == "--denoise") {
+            const std::string v = next();
+            unsigned k = 0; double c = dn.sigma[0], n = dn.sigma[1], p = dn.sigma[2];
+            const int got = std::sscanf(v.c_str(), "%u,%lf,%lf,%lf", &k, &c, &n, &p);
+            if (got != 1 && got != 4) { std::fprintf(stderr, "--denoise needs K or K,SIGMA_C,SIGMA_N,SIGMA_P\n"); return 2; }
+            want_denoise = true; dn.iterations = k; dn.sigma[0] = c; dn.sigma[1] = n; dn.sigma[2] = p;
+        }
         else if (a == "--help" || a == "-h") {
             std::printf("rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N]\n"
                         "         [--depth D] [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] > image.ppm\n%s"
+                        "  --denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]  write the frame through K (1 .. 8) iterations of the edge-avoiding a-trous filter, guided by\n"
+                        "                                     the camera hits of sample 0 (default sigmas 4, 0.5, 0.02; inf switches a stop off); also with --progressive\n"
                         "  --panorama FILE                    write the 2:1 equirectangular image (width x width/2) of everything around the scene's\n"
                         "                                     lookfrom instead of the image: --spp samples per ray, --depth, the scene's background\n", AOV_HELP);
             return 0;
@@ -388,7 +402,7 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "\rSamples: %llu / %u", (unsigned long long)frame.samples(), samples_per_pixel);    // main.rs:772-775
             }
             std::fprintf(stderr, "\n");
-            write_ppm_rgb8("-", frame.rgb8(), image_width, image_height);                        // main.rs:767-769,832
+            write_ppm_rgb8("-", want_denoise ? frame.rgb8_denoised(dn) : frame.rgb8(), image_width, image_height);     // main.rs:767-769,832
             std::fprintf(stderr, "Done.\n");                                                    // main.rs:835
             return 0;
         }
@@ -402,6 +416,7 @@ int main(int argc, char** argv) {
             double ms[4]; rt_last_multi_ms(s.raw(), ms);
             std::fprintf(stderr, "rt_render_multi: slowest kernel %.2f ms, gather %.3f ms, un-permute %.3f ms, call %.2f ms\n", ms[0], ms[1], ms[2], ms[3]);
         }
+        if (want_denoise) pixel_sums = denoise(pixel_sums, samples_per_pixel, query_camera_records(s, camera, image_width, image_height, 0u, seed), image_width, image_height, dn);
         write_ppm("-", pixel_sums, image_width, image_height, samples_per_pixel);              // main.rs:767-769,832
         std::fprintf(stderr, "Done.\n");                                                      // main.rs:835
     } catch (const Error& e) {

@@ -304,6 +304,15 @@ class Progressive:
         _check(self._lib.rt_progressive_copy_rgb8(self._h, out.ctypes.data, C.byref(changed)))
         return out, int(changed.value)
 
+    def rgb8_denoised(self, iterations: int = None, sigma=None, flags: int = 0) -> np.ndarray:
+        """rt_progressive_resolve_denoised_rgb8: the frame's sums as they are now through the edge-avoiding a-trous filter (`denoise`) and
+        format_color, all on the device -> (H, W, 3) uint8.  The frame builds its guide (sample 0's camera hits) at the first call and keeps
+        it until reset; `sum`, `rgb8` and its changed-pixel count are untouched."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        k, sg = _denoise_settings(iterations, sigma)
+        _check(self._lib.rt_progressive_resolve_denoised_rgb8(self._h, k, sg, flags, out.ctypes.data))
+        return out
+
     def sum(self) -> np.ndarray:
         """The accumulated per-pixel sums, (H, W, 3) f64 as `render` returns them; with `samples`, a checkpoint."""
         out = np.zeros((self.H, self.W, 3), dtype=np.float64)
@@ -577,6 +586,77 @@ def aov_image(hits: np.ndarray, which: str) -> np.ndarray:
         m = hits[..., 11].astype(np.int64) & 255
         return np.repeat(m[..., None], 3, axis=2).astype(np.uint8)
     raise KeyError(which)
+
+
+# ---- denoising (rt_denoise*): the edge-avoiding a-trous filter of csrc/rt_denoise.h over a frame of sums, guided by query_camera's records
+RT_DENOISE_SAME_MATERIAL = 1
+# Defaults of the Python layer (the C entry points take them explicitly), read off DESIGN.md §14's error table (profiles/denoise.log): with
+# sigma = (colour 4, normal 0.5, plane 0.02) — the setting of that table and of tests/test_denoise_host.py's quality check — two iterations
+# (a 9 x 9 footprint) have the lowest or second-lowest error at 16 and at 64 samples per pixel on the two untextured preview scenes (Cornell
+# box 0.20 / 0.17 of the raw error, teapot room 0.09 / 0.20), and every further iteration raises the error on the two textured ones.
+DENOISE_ITERATIONS = 2
+DENOISE_SIGMA = (4.0, 0.5, 0.02)
+
+
+def _denoise_settings(iterations, sigma):
+    k = DENOISE_ITERATIONS if iterations is None else int(iterations)
+    sg = DENOISE_SIGMA if sigma is None else tuple(float(x) for x in sigma)
+    if len(sg) != 3:
+        raise ValueError("sigma = (sigma_c, sigma_n, sigma_p)")
+    return k, (C.c_double * 3)(*sg)
+
+
+def _denoise_frames(rgb_sum, hits):
+    a = np.ascontiguousarray(rgb_sum, dtype=np.float64)
+    g = np.ascontiguousarray(hits, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3 or g.shape != a.shape[:2] + (HIT_DOUBLES,):
+        raise ValueError(f"rgb_sum of shape {a.shape} and hits of shape {g.shape}: want (H, W, 3) and (H, W, {HIT_DOUBLES})")
+    return a, g
+
+
+def _denoise_call(fn, rgb_sum, samples, hits, iterations, sigma, flags):
+    a, g = _denoise_frames(rgb_sum, hits)
+    k, sg = _denoise_settings(iterations, sigma)
+    out = np.zeros_like(a)
+    _check(fn(a.ctypes.data, int(samples), g.ctypes.data, a.shape[1], a.shape[0], k, sg, flags, out.ctypes.data))
+    return out
+
+
+def denoise_host(rgb_sum, samples: int, hits, iterations: int = None, sigma=None, flags: int = 0) -> np.ndarray:
+    """rt_denoise_host (no GPU): the filter's specification as plain C++.  rgb_sum (H, W, 3) sums holding `samples` samples per pixel, hits
+    (H, W, 16) records of query_camera -> the filtered frame, (H, W, 3), in sum units (hand it to format_image / write_ppm with `samples`)."""
+    return _denoise_call(_rt().rt_denoise_host, rgb_sum, samples, hits, iterations, sigma, flags)
+
+
+def denoise(rgb_sum, samples: int, hits, iterations: int = None, sigma=None, flags: int = 0) -> np.ndarray:
+    """rt_denoise: the same call computed by the HIP kernels on the current device — the same words as denoise_host."""
+    return _denoise_call(_rt().rt_denoise, rgb_sum, samples, hits, iterations, sigma, flags)
+
+
+def denoise_workspace_bytes(W: int, H: int) -> int:
+    return int(_rt().rt_denoise_workspace_bytes(W, H))
+
+
+def denoise_device(d_rgb_sum, samples: int, d_hits, W: int, H: int, d_rgb_sum_out=None, d_workspace=None, iterations: int = None, sigma=None,
+                   flags: int = 0, stream: int = 0, workspace_bytes=None):
+    """rt_denoise_device: the filter for sums and records in device memory (torch tensors of f64, or raw pointers), enqueued on `stream`;
+    never waits.  d_rgb_sum_out: None filters in place.  d_workspace: a tensor (or a raw pointer with workspace_bytes) of at least
+    denoise_workspace_bytes(W, H) bytes; None allocates a torch tensor on d_rgb_sum's device, which is returned so that the caller keeps it
+    alive until the stream has run."""
+    sum_ptr, _ = _device_buffer(d_rgb_sum)
+    hits_ptr, _ = _device_buffer(d_hits)
+    out_ptr = sum_ptr if d_rgb_sum_out is None else _device_buffer(d_rgb_sum_out)[0]
+    if d_workspace is None:
+        import torch
+        d_workspace = torch.empty(denoise_workspace_bytes(W, H), dtype=torch.uint8, device=d_rgb_sum.device)
+    ws_ptr, nbytes = _device_buffer(d_workspace)
+    nbytes = nbytes if workspace_bytes is None else int(workspace_bytes)
+    if nbytes is None:
+        raise ValueError("workspace_bytes is needed with a raw pointer")
+    k, sg = _denoise_settings(iterations, sigma)
+    _check(_rt().rt_denoise_device(C.c_void_p(sum_ptr), int(samples), C.c_void_p(hits_ptr), W, H, k, sg, flags, C.c_void_p(out_ptr),
+                                   C.c_void_p(ws_ptr), nbytes, C.c_void_p(stream)))
+    return d_workspace
 
 
 def kernel_time_total(b: SceneBuilder, reset: bool = False):

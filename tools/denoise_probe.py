@@ -1,0 +1,115 @@
+"""Denoiser timing and error table.  Part 1: kernel times of the pack kernel and of every iteration of rt_denoise_device (K = 5)
+at 800 x 800 and 3840 x 2160 — HIP events between the launches (rt_debug_denoise_ms), warm, best of REPS; once as shipped (steps 1 and 2
+from LDS tiles) and once with RT_DENOISE_NO_LDS=1 (every step straight from global memory: the A/B behind that choice) — beside the traffic floor of
+each launch (pack: 152 B in, 96 B out per pixel; an iteration: 96 B in, 32 B out, the last one 24 B out) as achieved bytes/s.  The frames are
+synthetic (a smooth colour field plus noise over a guide of a few planes): the kernels' time depends on the frame's size and, through the
+skipped taps, on how many neighbours share a key, not on what the scene is.  Part 2: the clipped mean squared error against a converged
+frame (tests/denoise_cases.py clipped_mse) of raw and denoised frames at 16 and 64 samples per pixel for K = 1 .. 5 on the four preview
+scenes at reduced size, with the Python defaults' sigmas: what render.DENOISE_ITERATIONS is chosen from.
+usage: python tools/denoise_probe.py [timing] [errors] > profiles/denoise.log"""
+import ctypes as C
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402  (before the library: see _lib.load_path)
+
+from raytracinginrust_amd import _lib, scenes  # noqa: E402
+from raytracinginrust_amd import render as R  # noqa: E402
+
+REPS = 5
+K = 5
+HBM_ACHIEVABLE = 6.3e12
+
+
+def synthetic(W, H, dev):
+    """A frame of sums (16 samples) and hit records on the device: three planes side by side, ~10 % misses along the top, noisy colours."""
+    g = torch.Generator(device=dev); g.manual_seed(1)
+    y, x = torch.meshgrid(torch.arange(H, device=dev, dtype=torch.float64), torch.arange(W, device=dev, dtype=torch.float64), indexing="ij")
+    rgb = torch.stack([0.5 + 0.4 * torch.sin(x / 97.0), 0.5 + 0.4 * torch.cos(y / 61.0), 0.3 + 0.2 * torch.sin((x + y) / 131.0)], dim=2)
+    rgb = (rgb + 0.3 * torch.rand((H, W, 3), generator=g, device=dev, dtype=torch.float64)) * 16.0
+    hits = torch.zeros((H, W, 16), device=dev, dtype=torch.float64)
+    third = (x * 3.0 / W).floor()
+    hits[..., 0] = 1.0
+    hits[..., 1] = 5.0 + 0.01 * y
+    hits[..., 2] = x / W * 10.0; hits[..., 3] = y / H * 10.0; hits[..., 4] = third
+    hits[..., 5] = torch.where(third == 1.0, 0.6, 0.0); hits[..., 7] = torch.where(third == 1.0, 0.8, 1.0)
+    hits[..., 11] = third
+    miss = y < H * 0.1
+    hits[miss] = 0.0
+    hits[..., 11:15] = torch.where(miss[..., None], -1.0, hits[..., 11:15])
+    return rgb.contiguous(), hits.contiguous()
+
+
+def timing():
+    for no_lds in (False, True):
+        if no_lds:
+            os.environ["RT_DENOISE_NO_LDS"] = "1"
+        else:
+            os.environ.pop("RT_DENOISE_NO_LDS", None)
+        print("# ---- " + ("RT_DENOISE_NO_LDS=1: every iteration reads its taps from global memory" if no_lds else "as shipped: steps 1 and 2 from LDS tiles"))
+        _timing()
+    os.environ.pop("RT_DENOISE_NO_LDS", None)
+
+
+def _timing():
+    lib = _lib.load().lib
+    dev = torch.device("cuda", torch.cuda.current_device())
+    sigma = (C.c_double * 3)(*R.DENOISE_SIGMA)
+    print(f"# denoiser kernel times, K = {K}, sigma = {R.DENOISE_SIGMA}, flags 0; HIP events, warm, best of {REPS}")
+    print("# frame  kernel  ms  floor bytes  achieved TB/s  share of the 6.3 TB/s achievable HBM rate")
+    for W, H in ((800, 800), (3840, 2160)):
+        rgb, hits = synthetic(W, H, dev)
+        out = torch.empty_like(rgb)
+        need = R.denoise_workspace_bytes(W, H)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        best = np.full(K + 1, 1e30)
+        for _ in range(REPS):
+            ms = (C.c_float * (K + 1))()
+            rc = lib.rt_debug_denoise_ms(C.c_void_p(rgb.data_ptr()), 16, C.c_void_p(hits.data_ptr()), W, H, K, sigma, 0, C.c_void_p(out.data_ptr()),
+                                         C.c_void_p(ws.data_ptr()), need, ms)
+            if rc != 0:
+                raise RuntimeError(lib.rt_last_error().decode())
+            best = np.minimum(best, np.array(ms[:]))
+        n = W * H
+        floors = [n * (152 + 96)] + [n * (96 + 32)] * (K - 1) + [n * (96 + 24)]
+        for k in range(K + 1):
+            name = "pack" if k == 0 else f"iteration {k - 1} (step {1 << (k - 1)})"
+            rate = floors[k] / (best[k] * 1e-3)
+            print(f"{W}x{H}  {name}  {best[k]:.4f}  {floors[k]}  {rate / 1e12:.3f}  {rate / HBM_ACHIEVABLE:.2f}", flush=True)
+        print(f"{W}x{H}  all {K + 1} launches  {best.sum():.4f} ms; working set of an iteration {n * 96 / 1e6:.0f} MB read + {n * 32 / 1e6:.0f} MB written", flush=True)
+        del rgb, hits, out, ws
+
+
+def errors():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import build_scene
+    from denoise_cases import clipped_mse
+    be = _lib.load()
+    earth = scenes.load_earthmap()
+    depth, truth_spp = 20, 4096
+    print(f"# clipped MSE against {truth_spp} spp (seed 99), depth {depth}, sigma = {R.DENOISE_SIGMA}, flags 0: raw, then K = 1 .. 5 (ratio to raw)")
+    for name, (W, H) in (("cornell", (100, 100)), ("random", (160, 90)), ("final", (100, 100)), ("teapot", (160, 90))):
+        b, cam, bg = build_scene(name, be, earth)
+        truth = R.render(b, cam, bg, W, H, truth_spp, depth, 99)
+        hits = R.query_camera(b, cam, W, H, 0, 7)
+        for spp in (16, 64):
+            noisy = R.render(b, cam, bg, W, H, spp, depth, 7)
+            raw = clipped_mse(noisy, spp, truth, truth_spp)
+            row = []
+            for k in range(1, 6):
+                e = clipped_mse(R.denoise(noisy, spp, hits, k, R.DENOISE_SIGMA, 0), spp, truth, truth_spp)
+                row.append(f"{e:.5f} ({e / raw:.2f})")
+            print(f"{name} {W}x{H} {spp} spp  raw {raw:.5f}  " + "  ".join(row), flush=True)
+
+
+if __name__ == "__main__":
+    what = sys.argv[1:] or ["timing", "errors"]
+    if "timing" in what:
+        timing()
+    if "errors" in what:
+        errors()

@@ -8,6 +8,6 @@ name=$1; f1=$2; src=${3:-rt_kernel.hip}
 mkdir -p abx
 BASE="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -Wno-pass-failed --offload-arch=gfx950 -I. -mllvm -disable-machine-licm"   # as the Makefile
 /opt/rocm/bin/hipcc $BASE -mllvm -enable-misched=0 $f1 -DRT_TU=1 -c $src -o abx/${name}_lean.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abx/$name.so abx/${name}_lean.o rt_kernel_rest.o rt_query.o rt_radiance.o rt_resolve.o rt_host.o rt_multi.o rt_flatten.o rt_jpeg.o rt_obj.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abx/$name.so abx/${name}_lean.o rt_kernel_rest.o rt_query.o rt_radiance.o rt_resolve.o rt_denoise.o rt_denoise_cpu.o rt_host.o rt_multi.o rt_flatten.o rt_jpeg.o rt_obj.o
 rm -f abx/${name}_lean.o
 echo built abx/$name.so
