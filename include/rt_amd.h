@@ -512,6 +512,17 @@ int rt_debug_onb(rt_scene*, uint32_t n, const double* rects, const double* norma
  * slots_out[48 i + 6 s ..] = {v[3], u[3]} for the sign bits s = sx | sy << 1 | sz << 2.  Either pointer may be NULL.  Returns the number
  * of rect records, *n_valid_out the number of valid entries; -1 on error. */
 int rt_debug_onb_table(rt_scene*, uint64_t* mag_out, double* slots_out, uint32_t max_rects, uint32_t* n_valid_out);
+/* Known-answer access to the exact short forms of the lean f64 list-scene kernel (csrc/rt_short.h; rt_kernel.hip div_pi_pair, div_frame,
+ * rng_u01_of, rect_absdot: the device functions its sites call) on n caller operands, one per lane, waves of 64 — the guards vote per wave.
+ * op 0, the Lambertian arm's two divisions by pi: a = n cosines, b = n values of max(dot, 0); out = n x 3: cosine > 0 ? cosine / pi : 0,
+ *       b / pi, and 1 if the record's wave took the three-instruction form (0: the plain divisions).
+ * op 1, the camera's division by W - 1 or H - 1: a = n numerators, b = n x 2: the divisor and its reciprocal as the host enabled it (0: the
+ *       plain division); out = n quotients.
+ * op 2, U01: a = n 64-bit words (each a u64 as drawn, stored in the double's place), b unused (may be NULL); out = n values of U01.
+ * op 3, AARect::pdf_value after its hit test: a = n x 3 directions v, b = n x 3: t, the plane's axis k (0, 1, 2), the area; out = n x 2: the
+ *       pdf, and 1 if the record's wave took |v_k| for |dot(v, n)| (0: the two dot products).
+ * Host pointers; no scene.  Returns 0, -1 on a bad argument or a device error. */
+int rt_debug_short_forms(uint32_t op, uint32_t n, const double* a, const double* b, double* out);
 /* Debugging aid for parity work: the hits of ONE camera path, level by level.  rt_debug_trace_path chooses the path (local pixel index =
  * output-order pixel for an unsharded render, sample index; -1 switches it off); the following renders record, per level of ray_color
  * that found a hit, 16 doubles at out[16 * level]: t, position[3], normal[3], front_face, object, primitive kind, primitive index,

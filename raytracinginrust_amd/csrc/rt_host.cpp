@@ -13,6 +13,7 @@
 #include "../../include/rt_amd.h"
 #include "rt_scene.h"
 #include "rt_launch.h"
+#include "rt_short.h"
 #include "rt_device.h"
 #include "rt_resolve.h"
 #include "rt_query.h"
@@ -701,6 +702,9 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     }
     P.cam.lens_radius = (T)cam.lens_radius; P.cam.time0 = (T)cam.time0; P.cam.time1 = (T)cam.time1;
     P.W = W; P.H = H; P.spp = spp; P.max_depth = max_depth; P.seed = seed; int loop_how = 0;
+    // the camera's two divisions by W - 1 and H - 1 (main.rs:817-818) in their short form where it is proven exact (rt_short.h); 0: the kernel
+    // divides.  RT_NO_SHORT_DIV (A/B runs, tests): the plain division everywhere.
+    if (!std::getenv("RT_NO_SHORT_DIV")) { P.rcp_wm1 = sf_recip_for((double)(W - 1u)); P.rcp_hm1 = sf_recip_for((double)(H - 1u)); }
     P.flags = effective_flags(f, flags, loop_choice_for(s, camp, W, H, flags), &loop_how);
     if (loop_how == 2 && s.loop_how == 4) loop_how = 4;
     P.stack_depth = stack_depth_of(f, P.flags);

@@ -164,6 +164,10 @@ template <typename T> struct KParams {
     // Per-face ONB memo (DOnbEntry, above): onb[i] belongs to rects[i]; null when the scene has no valid entry (every f32 scene, every
     // scene with a feature bit, RT_NO_ONB_TABLE).  Read by the lean f64 kernel's merged Lambertian arm only.
     const DOnbEntry* onb;
+    // Short division by the frame's two constant divisors (rt_short.h sf_recip_for, rt_kernel.hip refill_queue; lean f64 kernel only):
+    // RN(1 / (W - 1)) and RN(1 / (H - 1)) where the three-instruction form is proven to equal `/`, 0 where it is not (a divisor of 0,
+    // 2^53 |zh C - 1| >= 1/2, RT_NO_SHORT_DIV): the kernel then divides.  Always f64; zero in every launch that is not a frame.
+    double rcp_wm1, rcp_hm1;
 };
 
 } // namespace rt

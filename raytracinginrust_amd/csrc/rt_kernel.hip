@@ -29,6 +29,7 @@
 #include <type_traits>
 #include "rt_ir.h"
 #include "rt_rng.h"
+#include "rt_short.h"
 #include "rt_launch.h"
 
 // The kernels are built as two translation units from this one source (csrc/Makefile): RT_TU == 1 holds the lean (list-scene)
@@ -66,6 +67,13 @@ static constexpr uint32_t SPEC_NUM = 5u, SPEC_DEN = 8u;   // ... in the walk-ahe
 static constexpr bool SHARED_DIV3 = RT_TU == 2;  // shared-denominator Vec3 division: +3.8 % teapot room, +1.7 % final scene; -1.2 % Cornell box
 static constexpr bool MERGE_ARMS = RT_TU == 1;   // shade_hit: Lambertian's two sampling arms and Metal share their common instruction runs (round 4,
                                                  // samples bit-identical): Cornell box +2.5 %; in the BVH kernels -3 ... -7 % (register allocation)
+// rt_short.h: exact short forms for f64 operations on constants of the scene or the frame, in the lean f64 kernel only (the sites test
+// sizeof(T) too: the lean f32 kernel keeps its instructions); samples bit-identical.  RT_SHORT_PARTS (A/B builds): bit 0 division by pi and
+// by W - 1, H - 1 in three instructions, bit 1 U01 without conversions, bit 2 the rect light's |dot(v, n)| as |v_k|.
+#ifndef RT_SHORT_PARTS
+#define RT_SHORT_PARTS 7
+#endif
+static constexpr bool SHORT_DIV = RT_TU == 1 && (RT_SHORT_PARTS & 1), SHORT_U01 = RT_TU == 1 && (RT_SHORT_PARTS & 2), SHORT_LPDF = RT_TU == 1 && (RT_SHORT_PARTS & 4);
 
 // ------------------------------------------------------------------ small vector algebra (src/vec.rs)
 template <typename T> struct V3 { T x, y, z; };
@@ -1291,6 +1299,13 @@ template <typename T> DEV V3<T> random_in_unit_sphere(Rng& rng) {               
     }
 }
 
+// |dot(v, n)| of AARect::pdf_value (rect.rs:96), n = the rect's axis vector turned against v.  rt_short.h: it is |v_k| for every v with
+// finite components, which a finite length(v) implies.  WAVE-level: when some lane's length is not finite all of them run the full form.
+// took: the wave took the short form (rt_debug_short_forms reports it).
+DEV double rect_absdot(V3<double> v, uint32_t ki, double len, bool& took) {
+    took = __ballot(!sf_finite(len)) == 0ull;
+    return took ? sf_rect_absdot_short(v.x, v.y, v.z, ki) : sf_rect_absdot_full(v.x, v.y, v.z, ki);
+}
 template <typename T, uint32_t FEATS> DEV T light_pdf_value(const KParams<T>& P, DLight L, V3<T> o, V3<T> v) {
     RayT<T> r; r.o = o; r.d = v; r.tm = T(0);
     if (L.kind == L_RECT) {                                                           // rect.rs:91-101
@@ -1298,6 +1313,12 @@ template <typename T, uint32_t FEATS> DEV T light_pdf_value(const KParams<T>& P,
         T t;
         if (rect_test(rc, r, T(0.001), Lim<T>::inf(), t)) {
             uint32_t ki, ai, bi; plane_axes(rc.plane, ki, ai, bi);
+            if constexpr (SHORT_LPDF && FEATS == 0u && sizeof(T) == 8u) {
+                // (the record has no free slot for the area — 48 B, three 16-byte loads —: its three instructions stay)
+                bool took;
+                const T len = length(v);
+                return sf_rect_pdf_tail(rect_absdot(v, ki, len, took), len, t, (rc.a1 - rc.a0) * (rc.b1 - rc.b0));
+            }
             V3<T> axis = mk<T>(ki == 0u ? T(1.0) : T(0), ki == 1u ? T(1.0) : T(0), ki == 2u ? T(1.0) : T(0));
             V3<T> n = (dot(v, axis) < T(0)) ? axis : T(-1.0) * axis;
             T area = (rc.a1 - rc.a0) * (rc.b1 - rc.b0);
@@ -1608,6 +1629,13 @@ template <typename T> DEV void take_chunk(const KParams<T>& P, WaveWork& w, uint
     w.cur_s = w.s_lo;
     locate(P, w);
 }
+// x / C by rt_short.h's three instructions when the host proved them exact for this C (zh = RN(1 / C)), the division when it gave 0
+DEV double div_frame(double x, double C, double zh) { return sf_bits(zh) != 0ull ? sf_div3(x, C, zh) : x / C; }
+// U01 of the camera code: rt_rng.h's rng_u01, in the lean f64 kernel by rt_short.h's three additions (the same value, every step exact)
+template <typename T> DEV T cam_u01(Rng& g) {
+    if constexpr (SHORT_U01 && sizeof(T) == 8u) return sf_u01(rng_u64(g));
+    else return rng_u01(g, T(0));
+}
 // Refill the queue: the next (up to) 64 samples of the cursor, all lanes generating (main.rs:813-820).  False when the
 // global work queue is exhausted and nothing was generated.
 template <typename T>
@@ -1638,10 +1666,18 @@ DEV bool refill_queue(const KParams<T>& P, WaveWork& w, uint32_t lane, T* q_real
     if (n_gen == 0) return false;
     if (have) {
         Rng g = rng_for_path(PK(seed), g_gp, g_s);
-        T random_u = rng_u01(g, T(0));
-        T random_v = rng_u01(g, T(0));
-        T u = (T(g_i) + random_u) / T(PK(W) - 1u);
-        T v = (T(g_j) + random_v) / T(PK(H) - 1u);
+        T random_u = cam_u01<T>(g);
+        T random_v = cam_u01<T>(g);
+        T u, v;
+        if constexpr (SHORT_DIV && sizeof(T) == 8u) {
+            // rt_short.h: the numerators are +0 or at least 2^-53 (an integer below 2^31 plus a U01, both >= +0: never -0) and below 2^31 by
+            // construction — inside the short form's range without a test; a reciprocal of 0 (wave-uniform) keeps the division
+            u = (T)div_frame(T(g_i) + random_u, T(PK(W) - 1u), PK(rcp_wm1));
+            v = (T)div_frame(T(g_j) + random_v, T(PK(H) - 1u), PK(rcp_hm1));
+        } else {
+        u = (T(g_i) + random_u) / T(PK(W) - 1u);
+        v = (T(g_j) + random_v) / T(PK(H) - 1u);
+        }
         // Camera::get_ray, camera.rs:51-59 (random_in_unit_disk, vec.rs:96-105)
         T da, db;
         for (;;) {
@@ -1652,7 +1688,7 @@ DEV bool refill_queue(const KParams<T>& P, WaveWork& w, uint32_t lane, T* q_real
         }
         V3<T> rd = PK(cam.lens_radius) * mk<T>(da, db, T(0));
         V3<T> offset = cl3(K->cam.cu) * rd.x + cl3(K->cam.cv) * rd.y;
-        T time = PK(cam.time0) + rng_u01(g, T(0)) * (PK(cam.time1) - PK(cam.time0));
+        T time = PK(cam.time0) + cam_u01<T>(g) * (PK(cam.time1) - PK(cam.time0));
         V3<T> go = cl3(K->cam.origin) + offset;
         V3<T> gd = cl3(K->cam.lower_left_corner) + u * cl3(K->cam.horizontal) + v * cl3(K->cam.vertical) - (cl3(K->cam.origin) + offset);
         q_real[0u * QN + lane] = go.x; q_real[1u * QN + lane] = go.y; q_real[2u * QN + lane] = go.z;
@@ -1704,11 +1740,29 @@ template <typename T, uint32_t FEATS> DEV V3<T> const_or_tex(const KParams<T>& P
     return tex_eval<T, FEATS>(P, mt.tex, rec.u, rec.v, rec.p);
 }
 // U01 / R(a,b) of rt_rng.h from a u64 that was drawn earlier (shade_hit draws for several arms at once)
-DEV double rng_u01_of(uint64_t u, double) { const uint64_t v = u >> 11; return ((double)(uint32_t)(v >> 32) * 4294967296.0 + (double)(uint32_t)v) * 0x1.0p-53; }
+DEV double rng_u01_of(uint64_t u, double) { if constexpr (SHORT_U01) return sf_u01(u); const uint64_t v = u >> 11; return ((double)(uint32_t)(v >> 32) * 4294967296.0 + (double)(uint32_t)v) * 0x1.0p-53; }
 DEV double rng_range_of(uint64_t u, double a, double b) {
     double res = (__longlong_as_double((long long)(0x3FF0000000000000ULL | (u >> 12))) - 1.0) * (b - a) + a;
     if (!(res < b)) { uint64_t bb = (uint64_t)__double_as_longlong(b); if (b > 0.0) bb -= 1; else if (b < 0.0) bb += 1; else bb = 0x8000000000000001ULL; res = __longlong_as_double((long long)bb); }
     return res;
+}
+// The merged Lambertian arm's two divisions by pi (rt_short.h sf_div3): pdf = cosine > 0 ? cosine / pi : 0 (pdf.rs:131-139) and
+// sc = m / pi with m = max(dot(n, unit dir), 0) (mat.rs:246-249).  WAVE-level, one vote for both: the short form serves a numerator in
+// [2^-900, 2^900) (sf_in_range: one unsigned comparison on the high dword; it implies `> 0`).  A cosine outside it that is not `> 0` — a
+// zero, a negative number, NaN — is not divided at all, and an m outside it that is a zero of either sign is its own quotient (+-0 / pi
+// = +-0; f64::max may deliver -0, which the three instructions would turn into +0): the selects below.  Any other numerator — below
+// 2^-900, a denormal, an infinity — sends its wave through the plain divisions.
+// True: the wave took the short form (rt_debug_short_forms reports it; the frames do not read it).
+DEV bool div_pi_pair(double cosine, double m, double& pdf, double& sc) {
+    const bool r1 = sf_in_range(cosine), r2 = sf_in_range(m);
+    if (__ballot(!((r1 || !(cosine > 0.0)) && (r2 || m == 0.0))) == 0ull) {
+        pdf = r1 ? sf_div3(cosine, SF_PI, SF_RCP_PI) : 0.0;
+        sc = r2 ? sf_div3(m, SF_PI, SF_RCP_PI) : m;
+        return true;
+    }
+    pdf = (cosine > 0.0) ? cosine / SF_PI : 0.0;
+    sc = m / SF_PI;
+    return false;
 }
 // ------------------------------------------------------------------ one level of ray_color after the hit: main.rs:50-116
 // In: the hit record.  In/out: ray (becomes the scattered ray), beta, rng, depth_left.  Out: done (the path ends here) and
@@ -1775,7 +1829,9 @@ DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& 
                 dir = light_random<T, FEATS>(P, L, rec.p, rng);
             }
             T cosine = dot(normalized(dir), uvw.w);                         // pdf.rs:131-139
-            T pdf_value = (cosine > T(0)) ? cosine / PI_T : T(0);
+            T pdf_value, sc;
+            if constexpr (SHORT_DIV) div_pi_pair(cosine, m_max(dot(rec.n, normalized(dir)), T(0)), pdf_value, sc);   // both divisions by pi, here
+            else pdf_value = (cosine > T(0)) ? cosine / PI_T : T(0);
             if (P.n_lights != 0u) {
                 T lpdf;
                 if constexpr (Nested<FEATS>::on) lpdf = lights_pdf_tree<T, FEATS>(P, rec.p, dir);
@@ -1786,7 +1842,7 @@ DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& 
                 }
                 pdf_value = T(0.5) * lpdf + T(0.5) * pdf_value;             // pdf.rs:143-145
             }
-            T sc = m_max(dot(rec.n, normalized(dir)), T(0)) / PI_T;         // scattering_pdf, mat.rs:246-249
+            if constexpr (!SHORT_DIV) sc = m_max(dot(rec.n, normalized(dir)), T(0)) / PI_T;   // scattering_pdf, mat.rs:246-249
             beta = (beta * (attenuation * sc)) / pdf_value;                 // main.rs:97 (emitted is the literal zero here)
             ray.o = rec.p; ray.d = dir;                                     // time unchanged
         } else {                                                            // mat.rs:280-293
@@ -2402,6 +2458,30 @@ hipError_t launch_list_hit_kat(const KParams<double>& P, uint32_t n, const doubl
     hipLaunchKernelGGL(list_hit_kat_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_rays, d_tlim, d_out);
     return hipGetLastError();
 }
+// Known-answer access to the short forms as the lean f64 kernel runs them (rt_debug_short_forms): the device functions its sites call, on
+// caller operands, one record per lane, waves of 64 (the guards vote; a partial last wave repeats the last record).  op 0: the two
+// divisions by pi — a = cosine, b = m -> pdf, sc, 1 if the wave took the short form; op 1: the camera's division — a = x, b = (C, zh) ->
+// the quotient; op 2: U01 — a = the u64 (as a word) -> U01; op 3: the rect light's pdf after its hit test — a = v[3], b = (t, k, area) ->
+// the pdf, 1 if the wave took the short form.
+__global__ void short_forms_kat_kernel(uint32_t op, uint32_t n, const double* a, const double* b, double* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t j = i < n ? i : n - 1u;
+    double o0 = 0.0, o1 = 0.0, o2 = 0.0;
+    if (op == 0u) o2 = div_pi_pair(a[j], b[j], o0, o1) ? 1.0 : 0.0;
+    else if (op == 1u) o0 = div_frame(a[j], b[2u * j], b[2u * j + 1u]);
+    else if (op == 2u) o0 = rng_u01_of(sf_bits(a[j]), 0.0);
+    else {
+        const V3<double> v = mk<double>(a[3u * j], a[3u * j + 1u], a[3u * j + 2u]);
+        const double t = b[3u * j], area = b[3u * j + 2u]; const uint32_t ki = (uint32_t)b[3u * j + 1u];
+        bool took; const double len = length(v);
+        o0 = sf_rect_pdf_tail(rect_absdot(v, ki, len, took), len, t, area);
+        o1 = took ? 1.0 : 0.0;
+    }
+    if (i >= n) return;
+    if (op == 0u) { out[3u * i] = o0; out[3u * i + 1u] = o1; out[3u * i + 2u] = o2; }
+    else if (op == 3u) { out[2u * i] = o0; out[2u * i + 1u] = o1; }
+    else out[i] = o0;
+}
 #endif
 
 #if defined(RT_KRES_ONLY)      // tools/kres.py: one instantiation only (compile-time exploration, never the product build)
@@ -2592,6 +2672,27 @@ extern "C" int rt_debug_cube_hit(uint32_t n, double rect_m, const double* boxes,
         if (hipGetLastError() == hipSuccess && hipMemcpy(out, dout, n * 32ull, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
     }
     (void)hipFree(db); (void)hipFree(dr); (void)hipFree(dt); (void)hipFree(dout);
+    return rc;
+}
+#endif
+
+#if RT_TU != 2 && RT_TU != 3
+// Known-answer access to the short forms of the lean f64 kernel (rt::short_forms_kat_kernel above says what each op computes).  Records of
+// doubles per operand: op 0: a 1, b 1, out 3; op 1: a 1, b 2, out 1; op 2: a 1 (the u64's bits), b unused (may be null), out 1; op 3: a 3, b 3,
+// out 2.  Host pointers.
+extern "C" int rt_debug_short_forms(uint32_t op, uint32_t n, const double* a, const double* b, double* out) {
+    static const uint32_t rec[4][3] = {{1u, 1u, 3u}, {1u, 2u, 1u}, {1u, 0u, 1u}, {3u, 3u, 2u}};
+    if (op > 3u || !a || !out || (!b && rec[op][1] != 0u)) return -1;
+    if (n == 0) return 0;
+    const size_t na = (size_t)n * rec[op][0] * 8u, nb = (size_t)n * rec[op][1] * 8u, no = (size_t)n * rec[op][2] * 8u;
+    double *da = nullptr, *db = nullptr, *dout = nullptr;
+    int rc = -1;
+    if (hipMalloc(&da, na) == hipSuccess && (nb == 0u || hipMalloc(&db, nb) == hipSuccess) && hipMalloc(&dout, no) == hipSuccess &&
+        hipMemcpy(da, a, na, hipMemcpyHostToDevice) == hipSuccess && (nb == 0u || hipMemcpy(db, b, nb, hipMemcpyHostToDevice) == hipSuccess)) {
+        hipLaunchKernelGGL(rt::short_forms_kat_kernel, dim3((n + 63u) / 64u), dim3(64), 0, nullptr, op, n, da, db, dout);
+        if (hipGetLastError() == hipSuccess && hipMemcpy(out, dout, no, hipMemcpyDeviceToHost) == hipSuccess) rc = 0;
+    }
+    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
     return rc;
 }
 #endif

@@ -105,6 +105,22 @@ def debug_onb(b: SceneBuilder, rects: np.ndarray, normals: np.ndarray):
     return out[:, 0] != 0.0, out[:, 1:4].copy(), out[:, 4:7].copy()
 
 
+def debug_short_forms(op: int, a: np.ndarray, b: np.ndarray | None = None) -> np.ndarray:
+    """rt_debug_short_forms (needs a GPU): the lean f64 kernel's exact short forms (csrc/rt_short.h) on caller operands, one record per
+    lane, waves of 64.  op 0: a (n,) cosines, b (n,) max(dot, 0) -> (n, 3) pdf, sc, wave took the short form; op 1: a (n,) numerators,
+    b (n, 2) divisor and enabled reciprocal -> (n,) quotients; op 2: a (n,) uint64 words -> (n,) U01; op 3: a (n, 3) directions, b (n, 3)
+    t, axis, area -> (n, 2) pdf, wave took the short form."""
+    a_cols, b_cols, out_cols = ((1, 1, 3), (1, 2, 1), (1, 0, 1), (3, 3, 2))[op]
+    a = np.ascontiguousarray(a, np.uint64 if op == 2 else np.float64).reshape(-1, a_cols)
+    if b_cols:
+        b = np.ascontiguousarray(b, np.float64).reshape(-1, b_cols)
+        if len(a) != len(b):
+            raise ValueError("a and b differ in length")
+    out = np.zeros((len(a), out_cols), np.float64)
+    _check(_rt().rt_debug_short_forms(op, len(a), a.ctypes.data, b.ctypes.data if b_cols else None, out.ctypes.data))
+    return out[:, 0].copy() if out_cols == 1 else out
+
+
 def debug_light_pdf(b: SceneBuilder, origins: np.ndarray, dirs: np.ndarray) -> np.ndarray:
     """rt_debug_light_pdf (needs a GPU): the scene's `lights` pdf_value (HittableList::pdf_value, nested lists included) for n
     (origin, direction) pairs, computed on the device by the function the all-features kernel with object leaves runs."""
