@@ -497,6 +497,10 @@ int rt_debug_room_hit(uint32_t n, double rect_m, const double* boxes, const doub
  * material.  Host pointers.  What the room form's order argument rests on is tested through this: rays that start ON planes, with zero
  * direction components (0 / 0 plane distances), non-finite rays. */
 int rt_debug_list_hit(rt_scene*, uint32_t n, const double* rays, const double* t_min, double* out);
+/* The same through the search as the lean f64 kernel's primary pass runs it: top-level objects whose bit of `mask` is clear are not
+ * searched — except by a wave (64 consecutive rays of the array) in which some ray has a zero, denormal or non-finite direction component
+ * or a non-finite origin: that wave searches the list as the reference has it, in full.  Arguments and out as rt_debug_list_hit. */
+int rt_debug_list_hit_masked(rt_scene*, uint32_t n, const double* rays, const double* t_min, uint32_t mask, double* out);
 /* Known-answer access to the scene's `lights` pdf_value (HittableList::pdf_value, hit.rs:90-92, nested lists included) on the device, through
  * the function the all-features kernel with object leaves runs (the instantiation every scene with a list inside `lights` gets).  origins,
  * dirs: n x 3; out: n.  Host pointers. */
@@ -512,6 +516,16 @@ int rt_debug_onb(rt_scene*, uint32_t n, const double* rects, const double* norma
  * slots_out[48 i + 6 s ..] = {v[3], u[3]} for the sign bits s = sx | sy << 1 | sz << 2.  Either pointer may be NULL.  Returns the number
  * of rect records, *n_valid_out the number of valid entries; -1 on error. */
 int rt_debug_onb_table(rt_scene*, uint64_t* mag_out, double* slots_out, uint32_t max_rects, uint32_t* n_valid_out);
+/* The pixel classifier of the lean f64 list-scene kernel's primary pass (csrc/rt_primary.h): the kernel runs the first level of the camera
+ * paths of a refill together and does not search top-level objects that every ray it can generate for their pixel provably misses.  For
+ * n pixels (pixels: n x (i, j), j counted from the bottom row) out_masks[p] has bit k set when object k of the flattened top-level list may
+ * be hit (a clear bit is a proof; a list of more than 32 objects gives all ones).  rt_debug_primary_mask runs the kernel that writes a
+ * frame's masks before its launch, one thread per pixel (needs a GPU); rt_debug_primary_mask_host is its host twin (no GPU).  Host
+ * pointers.  Environment, read once per launch like RT_NO_SHORT_DIV (A/B runs, tests): RT_NO_PRIMARY_PASS renders without the pass — the
+ * 104-byte queue refilled with camera paths; samples are the same 64-bit words, but the frame is about 2.5 % slower than before the pass
+ * existed, so it is no timing stand-in for an earlier build; RT_NO_PRIMARY_MASK keeps the pass and treats every object as a candidate. */
+int rt_debug_primary_mask(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint32_t* out_masks);
+int rt_debug_primary_mask_host(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint32_t* out_masks);
 /* Known-answer access to the exact short forms of the lean f64 list-scene kernel (csrc/rt_short.h; rt_kernel.hip div_pi_pair, div_frame,
  * rng_u01_of, rect_absdot: the device functions its sites call) on n caller operands, one per lane, waves of 64 — the guards vote per wave.
  * op 0, the Lambertian arm's two divisions by pi: a = n cosines, b = n values of max(dot, 0); out = n x 3: cosine > 0 ? cosine / pi : 0,

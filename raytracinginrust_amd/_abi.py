@@ -153,10 +153,13 @@ SIGNATURES = {
     "debug_cube_hit": (_int, _HITS + [_ptr]),
     "debug_room_hit": (_int, _HITS + [_ptr, _ptr]),
     "debug_list_hit": (_int, [_ptr, _u32, _ptr, _ptr, _ptr]),
+    "debug_list_hit_masked": (_int, [_ptr, _u32, _ptr, _ptr, _u32, _ptr]),
     "debug_light_pdf": (_int, [_ptr, _u32, _ptr, _ptr, _ptr]),
     "debug_onb": (_int, [_ptr, _u32, _ptr, _ptr, _ptr]),
     "debug_onb_table": (_int, [_ptr, _ptr, _ptr, _u32, c_u32_p]),
     "debug_short_forms": (_int, [_u32, _u32, _ptr, _ptr, _ptr]),
+    "debug_primary_mask": (_int, [_ptr, _cam_p, _u32, _u32, _ptr, _u32, _ptr]),
+    "debug_primary_mask_host": (_int, [_ptr, _cam_p, _u32, _u32, _ptr, _u32, _ptr]),
     "debug_trace_path": (_int, [_ptr, C.c_longlong, C.c_longlong]),
     "debug_get_trace": (_int, [_ptr, _ptr, _u32]),
 }

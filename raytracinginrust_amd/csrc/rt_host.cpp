@@ -14,6 +14,7 @@
 #include "rt_scene.h"
 #include "rt_launch.h"
 #include "rt_short.h"
+#include "rt_primary.h"
 #include "rt_device.h"
 #include "rt_resolve.h"
 #include "rt_query.h"
@@ -104,7 +105,7 @@ void rt_scene_destroy(rt_scene* sc) {
         free_device_scene(c->dev32);
         for (Scene::LaunchSlot& l : c->slots) {
             if (l.recorded) (void)hipEventSynchronize((hipEvent_t)l.ev_stop);
-            free_dev(l.d_queue); free_dev(l.d_stats);
+            free_dev(l.d_queue); free_dev(l.d_stats); free_dev(l.d_park); free_dev(l.d_pmask);
             if (l.ev_start) (void)hipEventDestroy((hipEvent_t)l.ev_start);
             if (l.ev_stop) (void)hipEventDestroy((hipEvent_t)l.ev_stop);
         }
@@ -676,6 +677,14 @@ template <typename T> uint32_t tables_are_tame(const HostFlat& f) {
     return tame ? 1u : 0u;
 }
 
+// The launch shape of precision T: the kernel family's, with the lean f64 kernel's queue (rt_launch.h lean_f64_queue)
+template <typename T> static bool is_lean_f64(const HostFlat& f, uint32_t effective) { return sizeof(T) == 8u && pathtrace_feats(f.feats, effective) == 0u; }
+template <typename T> static LaunchShape shape_for(const HostFlat& f, uint32_t effective) {
+    LaunchShape g = pathtrace_shape(f.feats, effective);
+    if (is_lean_f64<T>(f, effective)) lean_f64_queue(g);
+    return g;
+}
+
 // f<float> or f<double>, as the caller's flags ask
 #define BY_PRECISION(flags, f, ...) (((flags) & RT_F32) ? f<float>(__VA_ARGS__) : f<double>(__VA_ARGS__))
 
@@ -724,7 +733,7 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     P.out = (double*)d_out; P.samples_out = (double*)d_samples;
 
     hipDeviceProp_t prop; HIP_OK(hipGetDeviceProperties(&prop, c.device));
-    LaunchShape shape = pathtrace_shape(f.feats, P.flags);
+    LaunchShape shape = shape_for<T>(f, P.flags);
     P.n_cached = cached_nodes<T>(shape, f, prop, P.stack_depth, P.flags);
     // the camera-path queue: the kernel family's minimum, widened (refills at full lane occupancy) while every node still fits
     for (uint32_t q = 64u; q > shape.queue_entries; q >>= 1) {
@@ -741,7 +750,7 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     }
     if (const char* v = std::getenv("RT_QUEUE_ENTRIES")) {       // A/B runs only: the queue first, the node cache gets what is left
         const long n = std::strtol(v, nullptr, 10);
-        if (n == 16 || n == 32 || n == 64) { shape.queue_entries = (uint32_t)n; P.n_cached = cached_nodes<T>(shape, f, prop, P.stack_depth, P.flags); }
+        if ((n == 16 || n == 32 || n == 64) && !is_lean_f64<T>(f, P.flags)) { shape.queue_entries = (uint32_t)n; P.n_cached = cached_nodes<T>(shape, f, prop, P.stack_depth, P.flags); }
     }
     P.queue_entries = shape.queue_entries;
     size_t shmem = pathtrace_lds_bytes(shape, P.stack_depth, P.n_cached, lds_node_bytes<T>(P.flags));
@@ -786,10 +795,37 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
         HIP_OK(hipMemsetAsync(s.d_trace, 0, bytes, stream));
         P.trace_out = (double*)s.d_trace; P.trace_px = (uint32_t)s.trace_px; P.trace_s = (uint32_t)s.trace_s;
     }
+    // the primary pass's parking slots, one per wave of this launch (RT_NO_PRIMARY_PASS: A/B runs and tests — camera paths are queued as in
+    // the other kernels).  The slot's earlier launch has finished (acquire_slot), so a buffer that has to grow is free to go.
+    bool want_masks = false;
+    if (is_lean_f64<T>(f, P.flags) && !std::getenv("RT_NO_PRIMARY_PASS")) {
+        const size_t need = (size_t)n_blocks * waves_per_block * RT_PARK_BYTES_PER_WAVE;
+        if (slot->park_bytes < need) {
+            free_dev(slot->d_park); slot->park_bytes = 0;
+            HIP_OK(hipMalloc(&slot->d_park, need));
+            slot->park_bytes = need;
+        }
+        P.park = (unsigned char*)slot->d_park;
+        // the object masks of this launch's pixels, from 64 samples per pixel on.  The threshold is a SUPPOSITION, not a measurement: below
+        // it a refill spans several pixels, the OR of their masks clears less, and the mask kernel's time is a larger share of a shorter
+        // frame.  RT_NO_PRIMARY_MASK (A/B runs): the pass alone.
+        if (f.n_top <= 32u && spp >= 64u && !std::getenv("RT_NO_PRIMARY_MASK")) {
+            const size_t mneed = (size_t)n_local_px * sizeof(uint32_t);
+            if (slot->pmask_bytes < mneed) {
+                free_dev(slot->d_pmask); slot->pmask_bytes = 0;
+                HIP_OK(hipMalloc(&slot->d_pmask, mneed));
+                slot->pmask_bytes = mneed;
+            }
+            P.pmask = (const uint32_t*)slot->d_pmask; want_masks = true;
+        }
+    }
     HIP_OK(hipMemsetAsync(slot->d_queue, 0, 64, stream));
     HIP_OK(hipMemsetAsync(slot->d_stats, 0, RT_STATS_BYTES, stream));
     if (!accumulate) HIP_OK(hipMemsetAsync(d_out, 0, (size_t)n_local_px * 3 * sizeof(double), stream));      // (a pass of a progressive frame adds to what is there)
     HIP_OK(hipEventRecord((hipEvent_t)slot->ev_start, stream));
+    if constexpr (sizeof(T) == 8u) {                 // (inside the timed span: the masks are part of what the frame costs)
+        if (want_masks) HIP_OK(launch_primary_masks(P, (uint32_t)n_local_px, nullptr, (uint32_t*)slot->d_pmask, stream));
+    }
     HIP_OK(launch_pathtrace<T>(P, f.feats, (uint32_t)n_blocks, shmem, stream));
     HIP_OK(hipEventRecord((hipEvent_t)slot->ev_stop, stream));
     slot->recorded = true; slot->timed = false; slot->seq = ++s.launch_seq; slot->group = s.frame_group; slot->harvested = false;
@@ -973,7 +1009,7 @@ template <typename T> static int prepare_device_as(Scene& s, Scene::DeviceCtx& c
     if (ensure_uploaded<T>(s, dev_of<T>(c))) return -1;
     for (Scene::LaunchSlot& l : c.slots) HIP_OK(ensure_slot_resources(l));
     const uint32_t eff = effective_flags(s.flat, flags, s.loop_how == 4 ? s.loop_choice : -1);
-    const LaunchShape shape = pathtrace_shape(s.flat.feats, eff);
+    const LaunchShape shape = shape_for<T>(s.flat, eff);
     hipDeviceProp_t prop; HIP_OK(hipGetDeviceProperties(&prop, c.device));
     const uint32_t sd = stack_depth_of(s.flat, eff);
     const size_t shmem = pathtrace_lds_bytes(shape, sd, cached_nodes<T>(shape, s.flat, prop, sd, eff), lds_node_bytes<T>(eff));
@@ -1084,7 +1120,7 @@ int rt_debug_section_cycles(rt_scene* sc, unsigned long long out[8]) {
 // A known-answer launch (rt_launch.h) on the calling thread's device: zeroed launch parameters with the scene's f64 tables bound in, two
 // host arrays of n records in (a_rec, b_rec bytes per record), one out.
 typedef hipError_t (*KatLaunch)(const KParams<double>&, uint32_t, const double*, const double*, double*, hipStream_t);
-static int run_kat(Scene& s, KatLaunch launch, uint32_t n, const double* a, size_t a_rec, const double* b, size_t b_rec, double* out, size_t out_rec) {
+static int run_kat(Scene& s, KatLaunch launch, uint32_t n, const double* a, size_t a_rec, const double* b, size_t b_rec, double* out, size_t out_rec, uint32_t flags = 0u) {
     Scene::DeviceCtx* cp = nullptr;
     if (current_ctx(s, &cp)) return -1;
     DeviceScene<double>& d = dev_of<double>(*cp);
@@ -1092,6 +1128,7 @@ static int run_kat(Scene& s, KatLaunch launch, uint32_t n, const double* a, size
     KParams<double> P;
     std::memset((void*)&P, 0, sizeof(P));
     bind_tables(P, d, s.flat);
+    P.flags = flags;
     DeviceBuffer d_a, d_b, d_out;
     HIP_OK(d_a.alloc(n * a_rec)); HIP_OK(d_b.alloc(n * b_rec)); HIP_OK(d_out.alloc(n * out_rec));
     HIP_OK(hipMemcpy(d_a.get(), a, n * a_rec, hipMemcpyHostToDevice));
@@ -1113,6 +1150,17 @@ int rt_debug_list_hit(rt_scene* sc, uint32_t n, const double* rays, const double
     if (s.flat.feats != 0u) return set_err("rt_debug_list_hit serves list scenes only (no BVH, sphere, triangle, medium, texture, dielectric or PBR)");
     return run_kat(s, launch_list_hit_kat, n, rays, 48u, t_min, 8u, out, 96u);
 }
+// The same search as the lean f64 kernel's primary pass runs it (world_hit_list<double, true>): top-level objects whose bit of `mask` is
+// clear are left out — except by a wave (64 consecutive rays) in which some ray takes the NaN-guard route: that wave searches the list as
+// the reference has it, in full, whatever the mask says.
+int rt_debug_list_hit_masked(rt_scene* sc, uint32_t n, const double* rays, const double* t_min, uint32_t mask, double* out) {
+    if (!sc || !rays || !t_min || !out) return set_err("null argument");
+    if (n == 0) return 0;
+    Scene& s = sc->s;
+    if (!flatten_for_render(s)) return -1;
+    if (s.flat.feats != 0u) return set_err("rt_debug_list_hit_masked serves list scenes only (no BVH, sphere, triangle, medium, texture, dielectric or PBR)");
+    return run_kat(s, launch_list_hit_masked_kat, n, rays, 48u, t_min, 8u, out, 96u, mask);
+}
 // Known-answer access to HittableList::pdf_value of the scene's `lights` (hit.rs:90-92, nested lists included) on the device, through the
 // function the F_ALL | F_NESTED kernels run (rt_kernel.hip lights_pdf_tree).  origins, dirs: n x 3; out: n.  Host pointers.
 int rt_debug_light_pdf(rt_scene* sc, uint32_t n, const double* origins, const double* dirs, double* out) {
@@ -1133,6 +1181,46 @@ int rt_debug_onb(rt_scene* sc, uint32_t n, const double* rects, const double* no
     for (uint32_t i = 0; i < n; i++)
         if (!(rects[i] >= 0.0 && rects[i] < (double)s.flat.rects.size() && rects[i] == std::floor(rects[i]))) return set_err("rt_debug_onb: rect index out of range");
     return run_kat(s, launch_onb_kat, n, rects, 8u, normals, 24u, out, 56u);
+}
+// The primary pass's pixel classifier (csrc/rt_primary.h) for n pixels (pixels: n x (i, j), j counted from the bottom row): bit k of
+// out_masks[p] set = top-level object k may be hit by a camera ray of that pixel.  The host twin needs no GPU; the device form runs
+// primary_mask_kernel — the kernel that writes a frame's masks before its launch —, one thread per pixel.  Host pointers.
+static int primary_mask_args(rt_scene* sc, const rt_camera* camp, uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint32_t* out_masks, DCamera<double>& cam) {
+    if (!sc || !camp || (n != 0u && (!pixels || !out_masks))) return set_err("null argument");
+    if (W == 0u || H == 0u || (uint64_t)W * H > 0x7FFFFFFFull) return set_err("rt_debug_primary_mask: W and H must be >= 1 and W*H <= 2^31 - 1");
+    for (uint32_t p = 0; p < n; p++) if (pixels[2u * p] >= W || pixels[2u * p + 1u] >= H) return set_err("rt_debug_primary_mask: pixel (i, j) outside the W x H frame");
+    if (!flatten_for_render(sc->s)) return -1;
+    rt_camera_args ca; std::memcpy(&ca, camp, sizeof(ca));
+    camera_new(ca, cam);
+    return 0;
+}
+int rt_debug_primary_mask_host(rt_scene* sc, const rt_camera* camp, uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint32_t* out_masks) {
+    DCamera<double> cam;
+    if (primary_mask_args(sc, camp, W, H, pixels, n, out_masks, cam)) return -1;
+    const HostFlat& f = sc->s.flat;
+    for (uint32_t p = 0; p < n; p++)
+        out_masks[p] = pm_mask(cam, pixels[2u * p], pixels[2u * p + 1u], W, H, f.objects.data(), f.n_top, f.ops.data(), f.rects.data(), (uint32_t)f.rects.size());
+    return 0;
+}
+int rt_debug_primary_mask(rt_scene* sc, const rt_camera* camp, uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint32_t* out_masks) {
+    DCamera<double> cam;
+    if (primary_mask_args(sc, camp, W, H, pixels, n, out_masks, cam)) return -1;
+    if (n == 0u) return 0;
+    Scene& s = sc->s;
+    Scene::DeviceCtx* cp = nullptr;
+    if (current_ctx(s, &cp)) return -1;
+    DeviceScene<double>& d = dev_of<double>(*cp);
+    if (ensure_uploaded<double>(s, d)) return -1;
+    KParams<double> P;
+    std::memset((void*)&P, 0, sizeof(P));
+    bind_tables(P, d, s.flat);
+    P.cam = cam; P.W = W; P.H = H;
+    DeviceBuffer d_px, d_out;
+    HIP_OK(d_px.alloc((size_t)n * 8u)); HIP_OK(d_out.alloc((size_t)n * 4u));
+    HIP_OK(hipMemcpy(d_px.get(), pixels, (size_t)n * 8u, hipMemcpyHostToDevice));
+    HIP_OK(launch_primary_masks(P, n, (const uint32_t*)d_px.get(), (uint32_t*)d_out.get(), nullptr));
+    HIP_OK(hipMemcpy(out_masks, d_out.get(), (size_t)n * 4u, hipMemcpyDeviceToHost));
+    return 0;
 }
 int rt_debug_trace_path(rt_scene* sc, long long local_pixel, long long sample) {
     if (!sc) return set_err("null argument");

@@ -30,6 +30,7 @@
 #include "rt_ir.h"
 #include "rt_rng.h"
 #include "rt_short.h"
+#include "rt_primary.h"
 #include "rt_launch.h"
 
 // The kernels are built as two translation units from this one source (csrc/Makefile): RT_TU == 1 holds the lean (list-scene)
@@ -441,7 +442,11 @@ DEV bool cube_hit(const KParams<double>& P, uint32_t first, uint32_t count, uint
     const DRect<double> f0 = ld_rect(P.rects + box_at);                 // XY face at z = max.z: a = x range, b = y range (cube.rs:17)
     const double mnz = cl(&P.rects[box_at + 1u].k);                     // XY face at z = min.z (cube.rs:18)
     uint32_t face = 0u; bool hit = false, clear;
-    if (!cube_fast<true, SITE>(P.rect_m, f0.a0, f0.a1, f0.b0, f0.b1, mnz, f0.k, ray, t_min, t_max, t_out, face, hit, clear, room >> 8)) return false;
+    float rect_m = P.rect_m;
+    // (lean unit: the margin's factor 2^-40 rect_m is formed at each test.  Hoisted in front of the bounce loop — what the compiler does once the
+    // primary pass has grown the loop — it is the one value spilled there and reloaded from scratch inside every Cube test.)
+    if constexpr (RT_TU == 1) asm volatile("" : "+s"(rect_m));
+    if (!cube_fast<true, SITE>(rect_m, f0.a0, f0.a1, f0.b0, f0.b1, mnz, f0.k, ray, t_min, t_max, t_out, face, hit, clear, room >> 8)) return false;
     if (hit) { any = true; prim_out = (G_RECT << 28) | (first + face); }
     return true;
 }
@@ -989,16 +994,25 @@ DEV void object_hit(const KParams<T>& P, uint32_t oi, const DObject& ob, const R
 template <typename T> DEV bool risky_component(T x, bool origin);
 template <> DEV bool risky_component<double>(double x, bool origin) { return origin ? __builtin_amdgcn_class(x, 0x207) : __builtin_amdgcn_class(x, 0x2F7); }     // NaN, inf (| zero, denormal)
 template <> DEV bool risky_component<float>(float x, bool origin) { return origin ? __builtin_amdgcn_classf(x, 0x207) : __builtin_amdgcn_classf(x, 0x2F7); }
-template <typename T>
-DEV bool world_hit_list(const KParams<T>& P, const RayT<T>& ray, T t_min, Rng& rng, T& t_hit, HitId& id) {
+// MASKED (the lean f64 kernel's primary pass, trace_lockstep): `mask` is wave-uniform, bit k clear = object k of [0, n_objects) is proven
+// missed by every ray of this wave (rt_primary.h) and is not searched; a missed object returns no hit whatever it is offered, so the
+// running closest hit, the tie rule and the list order are what they would be with it.  The alt list is searched in full.
+template <typename T, bool MASKED = false>
+DEV bool world_hit_list(const KParams<T>& P, const RayT<T>& ray, T t_min, Rng& rng, T& t_hit, HitId& id, uint32_t mask = 0xFFFFFFFFu) {
     T closest = Lim<T>::inf();
     bool any = false;
     uint32_t oi = 0u, oi_last = P.n_objects;
     if (P.n_objects_alt != 0u) {
         const bool risk = risky_component(ray.d.x, false) || risky_component(ray.d.y, false) || risky_component(ray.d.z, false) ||
                           risky_component(ray.o.x, true) || risky_component(ray.o.y, true) || risky_component(ray.o.z, true);
-        if (__ballot(risk) != 0ull) { oi = oi_last; oi_last += P.n_objects_alt; }
+        if (__ballot(risk) != 0ull) { oi = oi_last; oi_last += P.n_objects_alt; if constexpr (MASKED) mask = 0xFFFFFFFFu; }
     }
+    if constexpr (MASKED) {
+        for (; oi < oi_last; oi++) {
+            if (mask != 0xFFFFFFFFu && !((mask >> (oi & 31u)) & 1u)) continue;
+            object_hit<T, 0u>(P, oi, ld_obj(P.objects + oi), ray, t_min, rng, closest, id, any, nullptr);
+        }
+    } else
     for (; oi < oi_last; oi++) object_hit<T, 0u>(P, oi, ld_obj(P.objects + oi), ray, t_min, rng, closest, id, any, nullptr);      // wave-uniform: scalar loads
     t_hit = closest;
     return any;
@@ -1732,6 +1746,159 @@ DEV bool take_new_paths(const KParams<T>& P, WaveWork& w, uint32_t lane, T* q_re
     return got_new;
 }
 
+// ------------------------------------------------------------------ the lean f64 kernel's primary pass (trace_lockstep)
+// The camera rays of one refill are consecutive samples of one pixel (of a few, when spp is no multiple of 64): a bundle that starts on
+// the lens disk and passes through one pixel's footprint.  Searched next to forty secondary rays they pay for every object of the list;
+// searched TOGETHER they skip the objects the whole bundle provably misses (rt_primary.h: a wave-uniform mask).  So this kernel does not
+// only generate when its queue runs dry: it parks the 64 lanes' live paths in the wave's own slot of KParams::park, generates the camera
+// paths into the LANES, runs one ordinary iteration of the bounce loop for them — the same code, the mask handed to world_hit_list —,
+// queues the survivors (ray, beta, rng, pixel, sample: 104 B; depth_left is max_depth - 1 for all of them) and takes its paths back.
+// Per path nothing changes: the same draws in the same order, the same operations on the same values; a path's first level runs
+// earlier, beside its pixel-mates.  park == nullptr (RT_NO_PRIMARY_PASS): the queue is refilled with camera paths (beta = 1) as in the
+// other kernels.
+template <typename T, uint32_t FEATS> struct PrimaryPass { static constexpr bool on = RT_TU != 2 && FEATS == 0u && sizeof(T) == 8u; };
+static constexpr uint32_t regen_bytes_pp(uint32_t qn) { return 10u * qn * 8u + 6u * qn * 4u; }     // [10][QN] f64: o d time beta, [6][QN] u32
+static constexpr uint32_t PARK_BYTES = RT_PARK_BYTES_PER_WAVE;                                       // per wave: [10][64] f64, [8][64] u32
+
+// The object mask of the cursor's pixel (wave-uniform; rt_primary.h): one word per local pixel, written before the launch by
+// primary_mask_kernel (below) — the classifier itself stays out of this kernel: inlined here it cost the bounce loop its register
+// allocation (*measured*, profiles/r10_primary_pass_step0.log: 95.8 ms against 82.8 ms without it).  Null: every object is a candidate.
+template <typename T> DEV uint32_t pixel_mask(const KParams<T>& P, const WaveWork& w) {
+    COLD_K;
+    const uint32_t* const pm = PK(pmask);
+    return pm ? cl(pm + w.cur_px) : 0xFFFFFFFFu;
+}
+// The next (up to) 64 samples of the cursor as camera paths in the lanes: refill_queue's cursor walk and camera arithmetic, expression
+// for expression (a copy, so that the other kernels' code is what it was).  Returns the number generated (0: the global queue is
+// exhausted); `have` lanes hold one.  mask: the OR of the cursor pixels' object masks.
+template <typename T>
+DEV uint32_t gen_camera_paths(const KParams<T>& P, WaveWork& w, uint32_t lane, bool want_mask, bool& have, RayT<T>& ray, Rng& rng, uint32_t& px, uint32_t& smp, uint32_t& mask) {
+    COLD_K;
+    const uint32_t n_px = PK(W) * PK(H);
+    have = false; mask = 0u;
+    uint32_t g_gp = 0, g_i = 0, g_j = 0, n_gen = 0;
+    while (n_gen < 64u) {
+        if (w.cur_px == w.end_px) {
+            uint32_t c = 0;
+            if (lane == 0) c = atomicAdd(PK(queue), 1u);
+            c = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
+            if (c >= PK(n_chunks)) { w.queue_done = true; break; }
+            take_chunk(P, w, c);
+        }
+        if (w.cur_gp >= n_px || w.s_lo >= w.s_hi) { w.cur_px++; w.cur_s = w.s_lo; if (w.cur_px != w.end_px) locate(P, w); continue; }
+        uint32_t avail = w.s_hi - w.cur_s;
+        uint32_t room = 64u - n_gen;
+        uint32_t take = room < avail ? room : avail;
+        if (lane >= n_gen && lane < n_gen + take) { have = true; px = w.cur_px; smp = w.cur_s + (lane - n_gen); g_gp = w.cur_gp; g_i = w.cur_i; g_j = w.cur_j; }
+        if (want_mask) mask |= pixel_mask(P, w);
+        n_gen += take;
+        w.cur_s += take;
+        if (w.cur_s == w.s_hi) { w.cur_px++; w.cur_s = w.s_lo; if (w.cur_px != w.end_px) locate(P, w); }
+    }
+    if (have) {
+        Rng g = rng_for_path(PK(seed), g_gp, smp);
+        T random_u = cam_u01<T>(g);
+        T random_v = cam_u01<T>(g);
+        T u, v;
+        if constexpr (SHORT_DIV && sizeof(T) == 8u) {
+            u = (T)div_frame(T(g_i) + random_u, T(PK(W) - 1u), PK(rcp_wm1));
+            v = (T)div_frame(T(g_j) + random_v, T(PK(H) - 1u), PK(rcp_hm1));
+        } else {
+        u = (T(g_i) + random_u) / T(PK(W) - 1u);
+        v = (T(g_j) + random_v) / T(PK(H) - 1u);
+        }
+        T da, db;
+        for (;;) {
+            da = rng_range(g, T(-1.0), T(1.0));
+            db = rng_range(g, T(-1.0), T(1.0));
+            V3<T> pd = mk<T>(da, db, T(0));
+            if (dot(pd, pd) < T(1.0)) break;
+        }
+        V3<T> rd = PK(cam.lens_radius) * mk<T>(da, db, T(0));
+        V3<T> offset = cl3(K->cam.cu) * rd.x + cl3(K->cam.cv) * rd.y;
+        ray.tm = PK(cam.time0) + cam_u01<T>(g) * (PK(cam.time1) - PK(cam.time0));
+        ray.o = cl3(K->cam.origin) + offset;
+        ray.d = cl3(K->cam.lower_left_corner) + u * cl3(K->cam.horizontal) + v * cl3(K->cam.vertical) - (cl3(K->cam.origin) + offset);
+        rng = g;
+    }
+    return n_gen;
+}
+// One queue entry of the 104-byte form
+template <typename T>
+DEV void queue_put(T* q_real, uint32_t* q_u32, uint32_t e, const RayT<T>& ray, V3<T> beta, const Rng& rng, uint32_t px, uint32_t smp) {
+    q_real[0u * 64u + e] = ray.o.x; q_real[1u * 64u + e] = ray.o.y; q_real[2u * 64u + e] = ray.o.z;
+    q_real[3u * 64u + e] = ray.d.x; q_real[4u * 64u + e] = ray.d.y; q_real[5u * 64u + e] = ray.d.z;
+    q_real[6u * 64u + e] = ray.tm;
+    q_real[7u * 64u + e] = beta.x; q_real[8u * 64u + e] = beta.y; q_real[9u * 64u + e] = beta.z;
+    q_u32[0u * 64u + e] = rng.s0; q_u32[1u * 64u + e] = rng.s1; q_u32[2u * 64u + e] = rng.s2; q_u32[3u * 64u + e] = rng.s3;
+    q_u32[4u * 64u + e] = px; q_u32[5u * 64u + e] = smp;
+}
+// take_new_paths for the 104-byte queue: `dead` lanes pop what the queue holds.  With the pass on the queue is never refilled here (the
+// caller runs a pass when it is empty and lanes still want); with it off, camera paths with beta = 1 are generated into it.
+template <typename T>
+DEV bool take_new_paths_pp(const KParams<T>& P, WaveWork& w, uint32_t lane, T* q_real, uint32_t* q_u32, bool dead, bool pass_on,
+                           RayT<T>& ray, V3<T>& beta, Rng& rng, uint32_t& new_px, uint32_t& path_s) {
+    bool got_new = false;
+    for (;;) {
+        unsigned long long want = __ballot(dead && !got_new);
+        if (want == 0) break;
+        if (w.q_count == 0) {
+            if (w.queue_done || pass_on) break;
+            bool have; RayT<T> r; Rng g; uint32_t px = 0, smp = 0, mask;
+            const uint32_t n_gen = gen_camera_paths(P, w, lane, false, have, r, g, px, smp, mask);
+            if (n_gen == 0) break;
+            if (have) queue_put(q_real, q_u32, lane, r, mk<T>(T(1.0), T(1.0), T(1.0)), g, px, smp);
+            w.q_head = 0; w.q_count = n_gen;
+            __builtin_amdgcn_wave_barrier();
+        }
+        uint32_t n_want = (uint32_t)__popcll(want);
+        uint32_t take = n_want < w.q_count ? n_want : w.q_count;
+        uint32_t rank = lane_rank(want);
+        if (dead && !got_new && rank < take) {
+            const uint32_t e = w.q_head + rank;
+            got_new = true;
+            ray.o = mk<T>(q_real[0u * 64u + e], q_real[1u * 64u + e], q_real[2u * 64u + e]);
+            ray.d = mk<T>(q_real[3u * 64u + e], q_real[4u * 64u + e], q_real[5u * 64u + e]);
+            ray.tm = q_real[6u * 64u + e];
+            beta = mk<T>(q_real[7u * 64u + e], q_real[8u * 64u + e], q_real[9u * 64u + e]);
+            rng.s0 = q_u32[0u * 64u + e]; rng.s1 = q_u32[1u * 64u + e]; rng.s2 = q_u32[2u * 64u + e]; rng.s3 = q_u32[3u * 64u + e];
+            new_px = q_u32[4u * 64u + e]; path_s = q_u32[5u * 64u + e];
+        }
+        w.q_head += take; w.q_count -= take;
+    }
+    return got_new;
+}
+// A wave's parked paths: [10][64] f64 then [8][64] u32 in its own slot, every access one lane's own word (ordinary vector stores and
+// loads, 256 or 512 contiguous bytes per instruction; a lane reads back only what it wrote itself, in program order).
+// The slot's address is formed where it is used, from the kernel argument and a lane index the compiler cannot see through: formed in
+// front of the bounce loop, the lanes' eighteen addresses stay in vector registers through every iteration (*seen*: 14 VGPRs held and
+// five more pairs spilled and reloaded per iteration).
+template <typename T> DEV double* park_slot(uint32_t wave_slot, uint32_t& lane) {
+    COLD_K;
+    asm volatile("" : "+v"(lane));
+    return (double*)(PK(park) + (size_t)wave_slot * PARK_BYTES);
+}
+template <typename T>
+DEV void park_paths(double* pr, uint32_t lane, const RayT<T>& ray, V3<T> beta, const Rng& rng, uint32_t depth_left, uint32_t path_s, uint32_t acc_px, bool alive) {
+    uint32_t* pu = (uint32_t*)(pr + 10u * 64u);
+    pr[0u * 64u + lane] = ray.o.x; pr[1u * 64u + lane] = ray.o.y; pr[2u * 64u + lane] = ray.o.z;
+    pr[3u * 64u + lane] = ray.d.x; pr[4u * 64u + lane] = ray.d.y; pr[5u * 64u + lane] = ray.d.z;
+    pr[6u * 64u + lane] = ray.tm;
+    pr[7u * 64u + lane] = beta.x; pr[8u * 64u + lane] = beta.y; pr[9u * 64u + lane] = beta.z;
+    pu[0u * 64u + lane] = rng.s0; pu[1u * 64u + lane] = rng.s1; pu[2u * 64u + lane] = rng.s2; pu[3u * 64u + lane] = rng.s3;
+    pu[4u * 64u + lane] = depth_left; pu[5u * 64u + lane] = path_s; pu[6u * 64u + lane] = acc_px; pu[7u * 64u + lane] = alive ? 1u : 0u;
+}
+template <typename T>
+DEV void unpark_paths(const double* pr, uint32_t lane, RayT<T>& ray, V3<T>& beta, Rng& rng, uint32_t& depth_left, uint32_t& path_s, uint32_t& acc_px, bool& alive) {
+    const uint32_t* pu = (const uint32_t*)(pr + 10u * 64u);
+    ray.o = mk<T>(pr[0u * 64u + lane], pr[1u * 64u + lane], pr[2u * 64u + lane]);
+    ray.d = mk<T>(pr[3u * 64u + lane], pr[4u * 64u + lane], pr[5u * 64u + lane]);
+    ray.tm = pr[6u * 64u + lane];
+    beta = mk<T>(pr[7u * 64u + lane], pr[8u * 64u + lane], pr[9u * 64u + lane]);
+    rng.s0 = pu[0u * 64u + lane]; rng.s1 = pu[1u * 64u + lane]; rng.s2 = pu[2u * 64u + lane]; rng.s3 = pu[3u * 64u + lane];
+    depth_left = pu[4u * 64u + lane]; path_s = pu[5u * 64u + lane]; acc_px = pu[6u * 64u + lane]; alive = pu[7u * 64u + lane] != 0u;
+}
+
 // The colour of a Lambertian / DiffuseLight material.  The lean kernels (constant textures only) take it from the material record they
 // hold — rt_flatten.cpp copies a constant texture's colour there — instead of gathering the texture record behind it (*measured* +1.4 %
 // on the Cornell box; no gain in the BVH kernels, which keep the texture walk).
@@ -2007,13 +2174,24 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
     uint32_t n_nonfinite = 0, n_flush = 0;
     unsigned long long n_iters = 0, n_active = 0;
     DIAG_DECL
+    // the primary pass (above: PrimaryPass): this wave's parking slot, and the depth a queued path starts at
+    constexpr bool PP = PrimaryPass<T, FEATS>::on;
+    bool pass_on = false; uint32_t depth_new = 0u, wave_slot = 0u;
+    if constexpr (PP) {
+        COLD_K;
+        pass_on = PK(park) != nullptr;
+        wave_slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * Shape<FEATS>::WAVES + (threadIdx.x >> 6)));
+        depth_new = P.max_depth - (pass_on ? 1u : 0u);      // (max_depth 0 with the pass on: every path ends in the pass, nothing is queued)
+    }
 
     for (;;) {
         DIAG_T0();
         // ---- lanes whose path has ended take the next camera path from the wave's queue
         uint32_t new_px = 0;
-        const bool got_new = take_new_paths(P, w, lane, q_real, q_u32, !alive, ray, rng, new_px, path_s);
-        if (__ballot(alive || got_new) == 0) break;     // queue empty and every path finished
+        bool got_new;
+        if constexpr (PP) got_new = take_new_paths_pp(P, w, lane, q_real, q_u32, !alive, pass_on, ray, beta, rng, new_px, path_s);
+        else got_new = take_new_paths(P, w, lane, q_real, q_u32, !alive, ray, rng, new_px, path_s);
+        if constexpr (!PP) if (__ballot(alive || got_new) == 0) break;     // queue empty and every path finished
         DIAG_ADD(0);
 
         // ---- lanes moving on to another pixel hand in their partial sum
@@ -2021,9 +2199,26 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
 
         if (got_new) {
             if (acc_px != new_px) { acc_px = new_px; acc.set(0, 0.0); acc.set(1, 0.0); acc.set(2, 0.0); }
-            beta = mk<T>(T(1.0), T(1.0), T(1.0));
-            depth_left = P.max_depth;
+            if constexpr (!PP) beta = mk<T>(T(1.0), T(1.0), T(1.0));       // (PP: the queue entry's — 1 for a camera path)
+            depth_left = PP ? depth_new : P.max_depth;
             alive = true;
+        }
+
+        // ---- the queue is empty and lanes still want a path: the primary pass — park, generate into the lanes, and let this iteration be theirs
+        bool primary = false;
+        uint32_t obj_mask = 0xFFFFFFFFu;
+        if constexpr (PP) {
+            if (pass_on && w.q_count == 0u && !w.queue_done && __ballot(!alive) != 0ull) {
+                uint32_t pl = lane;
+                double* const park = park_slot<T>(wave_slot, pl);
+                park_paths(park, pl, ray, beta, rng, depth_left, path_s, acc_px, alive);
+                bool have;
+                if (gen_camera_paths(P, w, lane, true, have, ray, rng, acc_px, path_s, obj_mask) != 0u) {
+                    primary = true;
+                    alive = have; beta = mk<T>(T(1.0), T(1.0), T(1.0)); depth_left = P.max_depth;
+                } else { unpark_paths(park, pl, ray, beta, rng, depth_left, path_s, acc_px, alive); obj_mask = 0xFFFFFFFFu; }      // (nothing left to generate: an ordinary iteration)
+            }
+            if (__ballot(alive) == 0) break;            // queue empty and every path finished
         }
 
         n_iters++;
@@ -2031,6 +2226,8 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
         DIAG_ADD(1);
 
         // ---- one level of ray_color (main.rs:41-120) for every live lane
+        [[maybe_unused]] bool ended = false;                                     // (PP, in a pass) this lane's path ended: pacc holds its radiance
+        [[maybe_unused]] typename Shape<FEATS>::Acc pacc; if constexpr (PP) { pacc.set(0, 0.0); pacc.set(1, 0.0); pacc.set(2, 0.0); }
         if (alive) {
             bool done = false;
             V3<T> e = mk<T>(T(0), T(0), T(0));          // terminal radiance of this path (times beta)
@@ -2039,7 +2236,8 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
             } else {
                 T t_hit; HitId id; id.obj = 0; id.prim = 0;
                 bool any_hit;                                                                            // main.rs:48
-                if constexpr (FEATS == 0u) any_hit = world_hit_list<T>(P, ray, TMin<T>::v(), rng, t_hit, id);
+                if constexpr (PP) any_hit = world_hit_list<T, true>(P, ray, TMin<T>::v(), rng, t_hit, id, obj_mask);
+                else if constexpr (FEATS == 0u) any_hit = world_hit_list<T>(P, ray, TMin<T>::v(), rng, t_hit, id);
                 else any_hit = world_hit<T, FEATS>(P, ray, TMin<T>::v(), rng, t_hit, id, stack);
                 DIAG_ADD(2);
                 if (!any_hit) {
@@ -2063,10 +2261,30 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
             }
             DIAG_ADD(4);
             if (done) {
+                if constexpr (PP) {
+                    // a path that ends in the pass (the light seen directly, a miss, max_depth <= 1, Metal's absorbed ray) goes into a sum of
+                    // its own, not into the parked lane's
+                    if (primary) { ended = true; add_radiance(P, beta * e, pacc, n_nonfinite, path_px, path_s); }
+                    else add_radiance(P, beta * e, acc, n_nonfinite, path_px, path_s);
+                } else
                 add_radiance(P, beta * e, acc, n_nonfinite, path_px, path_s);
                 alive = false;
             }
             DIAG_ADD(5);
+        }
+        if constexpr (PP) {
+            if (primary) {
+                // ---- the end of the pass: what ended is handed in per pixel (one butterfly and three atomics, as for any other
+                // partial sum), the survivors are queued in lane order, and the wave takes its parked paths back
+                flush_acc<T, typename Shape<FEATS>::Acc, false>(P, ended, acc_px, pacc, lane, n_flush);
+                const unsigned long long sv = __ballot(alive);
+                if (alive) queue_put(q_real, q_u32, lane_rank(sv), ray, beta, rng, acc_px, path_s);
+                w.q_head = 0u; w.q_count = (uint32_t)__popcll(sv);
+                __builtin_amdgcn_wave_barrier();          // one wave: LDS writes above are ordered before the reads of the pops
+                uint32_t pl = lane;
+                double* const park = park_slot<T>(wave_slot, pl);
+                unpark_paths(park, pl, ray, beta, rng, depth_left, path_s, acc_px, alive);
+            }
         }
     }
     // ---- the queue is empty: hand in what is left
@@ -2369,6 +2587,11 @@ __global__ void __launch_bounds__(Shape<FEATS>::THREADS, Shape<FEATS>::WAVES_PER
         __syncthreads();
     }
     const uint32_t QN = P.queue_entries;
+    if constexpr (PrimaryPass<T, FEATS>::on) {                     // 64 entries of 104 B: [10][64] f64 (... beta), [6][64] u32 (rt_launch.h sizes it so)
+        unsigned char* regen = lds_raw + wave_in_block * regen_bytes_pp(64u);
+        trace_lockstep<T, FEATS>(P, lane, (T*)regen, (uint32_t*)(regen + 10u * 64u * sizeof(T)), nullptr);
+        return;
+    }
     unsigned char* regen = lds_raw + nodes_bytes + wave_in_block * regen_bytes(QN);
     T* q_real = (T*)regen;                                         // [7][QN]: o.x o.y o.z d.x d.y d.z time
     uint32_t* q_u32 = (uint32_t*)(regen + 7u * QN * sizeof(T));    // [6][QN]: rng s0..s3, local pixel, sample
@@ -2399,7 +2622,7 @@ static int occupancy_one(size_t shmem) {
     if (Shape<FEATS>::ONE_PER_CU && nb > 1) nb = 1;       // the register budget is set for exactly one such workgroup per CU
     return nb;
 }
-template <uint32_t FEATS> static LaunchShape shape_one() { LaunchShape g; g.threads = Shape<FEATS>::THREADS; g.queue_entries = Shape<FEATS>::QN_MIN; g.one_per_cu = Shape<FEATS>::ONE_PER_CU; return g; }
+template <uint32_t FEATS> static LaunchShape shape_one() { LaunchShape g; g.threads = Shape<FEATS>::THREADS; g.queue_entries = Shape<FEATS>::QN_MIN; g.entry_bytes = 80u; g.one_per_cu = Shape<FEATS>::ONE_PER_CU; return g; }
 
 // Instantiations per arithmetic type, leanest first: rects + instances + Lambertian/Metal/DiffuseLight (everything the
 // Cornell box needs; 5 waves/SIMD), the same plus BVH + triangles (mesh scenes such as the teapot room; 3 waves/SIMD),
@@ -2423,13 +2646,19 @@ template int occupancy_lean<float>(size_t);
 // Known-answer access to the list-scene kernels' closest-hit search (rt_debug_list_hit): world.hit (main.rs:48) + the hit record for
 // given rays — world_hit<double, 0> and finalize_hit<double, 0>, the code the frames run, one ray per lane, waves of 64 (the search
 // votes).  out[12 i ..] = hit (0 / 1), t, position[3], normal[3], front_face, object, primitive, material.
+// MASKED (rt_debug_list_hit_masked): the search as the primary pass runs it, objects whose bit of P.flags is clear left out — except
+// in a wave that takes the NaN-guard route, which searches the list as the reference has it in full.  (The KAT's launch parameters carry
+// no render flags: the field is free to hold the mask.)
+template <bool MASKED>
 __global__ void list_hit_kat_kernel(const KParams<double> P, uint32_t n, const double* rays, const double* tlim, double* out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t j = i < n ? i : n - 1u;                           // (a partial last wave repeats the last ray: every lane takes part in the votes)
     RayT<double> ray; ray.o = mk<double>(rays[j * 6], rays[j * 6 + 1], rays[j * 6 + 2]); ray.d = mk<double>(rays[j * 6 + 3], rays[j * 6 + 4], rays[j * 6 + 5]); ray.tm = 0.0;
     Rng rng = rng_for_path(0ull, 0u, 0u);
     double t_hit; HitId id; id.obj = 0u; id.prim = 0u;
-    const bool any = world_hit_list<double>(P, ray, tlim[j], rng, t_hit, id);
+    bool any;
+    if constexpr (MASKED) any = world_hit_list<double, true>(P, ray, tlim[j], rng, t_hit, id, P.flags);
+    else any = world_hit_list<double>(P, ray, tlim[j], rng, t_hit, id);
     Rec<double> rec; rec.p = mk<double>(0.0, 0.0, 0.0); rec.n = rec.p; rec.t = 0.0; rec.u = rec.v = 0.0; rec.front = false; rec.mat = 0u;
     if (any) finalize_hit<double, 0u>(P, ray, t_hit, id, true, rec);
     if (i < n) {
@@ -2455,7 +2684,33 @@ hipError_t launch_onb_kat(const KParams<double>& P, uint32_t n, const double* d_
     return hipGetLastError();
 }
 hipError_t launch_list_hit_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream) {
-    hipLaunchKernelGGL(list_hit_kat_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_rays, d_tlim, d_out);
+    hipLaunchKernelGGL(list_hit_kat_kernel<false>, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_rays, d_tlim, d_out);
+    return hipGetLastError();
+}
+hipError_t launch_list_hit_masked_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream) {
+    hipLaunchKernelGGL(list_hit_kat_kernel<true>, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_rays, d_tlim, d_out);
+    return hipGetLastError();
+}
+// The primary pass's object masks (rt_primary.h pm_mask), one thread per pixel.  pixels == nullptr: the launch's n local pixels in
+// locate()'s order -> out[local pixel] (a padding pixel: all ones), what KParams::pmask points at.  Otherwise (rt_debug_primary_mask)
+// the n pixels (i, j) the caller lists.  P carries the tables, the camera, the frame size and the tiling.
+__global__ void __launch_bounds__(256) primary_mask_kernel(const KParams<double> P, uint32_t n, const uint32_t* pixels, uint32_t* out) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    uint32_t i, j;
+    if (pixels) { i = pixels[2u * p]; j = pixels[2u * p + 1u]; }
+    else {
+        const uint32_t q = p / P.tile_px, kk = p - q * P.tile_px;
+        const uint64_t gp = ((uint64_t)P.rank + (uint64_t)q * P.world) * P.tile_px + kk;
+        if (gp >= (uint64_t)P.W * P.H) { out[p] = 0xFFFFFFFFu; return; }
+        const uint32_t row = (uint32_t)(gp / P.W);
+        i = (uint32_t)(gp - (uint64_t)row * P.W); j = P.H - 1u - row;
+    }
+    out[p] = pm_mask(P.cam, i, j, P.W, P.H, P.objects, P.n_objects, P.ops, P.rects, 0xFFFFFFFFu);      // (the flattener's ranges lie inside its tables)
+}
+hipError_t launch_primary_masks(const KParams<double>& P, uint32_t n, const uint32_t* d_pixels, uint32_t* d_out, hipStream_t stream) {
+    if (n == 0u) return hipSuccess;
+    hipLaunchKernelGGL(primary_mask_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, P, n, d_pixels, d_out);
     return hipGetLastError();
 }
 // Known-answer access to the short forms as the lean f64 kernel runs them (rt_debug_short_forms): the device functions its sites call, on

@@ -91,6 +91,7 @@ struct Scene {
     static const int N_SLOTS = 4;
     struct LaunchSlot {
         void* d_queue = nullptr; void* d_stats = nullptr;
+        void* d_park = nullptr; size_t park_bytes = 0; void* d_pmask = nullptr; size_t pmask_bytes = 0;          // the lean f64 kernel's parking slots (KParams::park) and per-pixel object masks (KParams::pmask): grown to the largest launch's wave / local pixel count
         void* ev_start = nullptr; void* ev_stop = nullptr;
         void* stream = nullptr; bool recorded = false, timed = true; unsigned long long seq = 0;
         unsigned long long group = 0; bool harvested = true;   // the frame this launch is a share of; its counters have joined Scene::acc_stats

@@ -105,6 +105,32 @@ def debug_onb(b: SceneBuilder, rects: np.ndarray, normals: np.ndarray):
     return out[:, 0] != 0.0, out[:, 1:4].copy(), out[:, 4:7].copy()
 
 
+def debug_list_hit(b: SceneBuilder, rays: np.ndarray, t_min: float = 0.001, mask: int | None = None) -> np.ndarray:
+    """rt_debug_list_hit / rt_debug_list_hit_masked (needs a GPU; list scenes): world.hit and the hit record for n rays (origin[3],
+    direction[3]) through the lean kernels' own search -> (n, 12): hit, t, position[3], normal[3], front_face, object, primitive,
+    material.  With a mask: the search as the primary pass runs it — objects whose bit is clear are left out, except by a wave (64
+    consecutive rays) that takes the NaN-guard route."""
+    r = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    tm = np.full(len(r), float(t_min))
+    out = np.zeros((len(r), 12), np.float64)
+    if mask is None:
+        _check(_rt().rt_debug_list_hit(b.h, len(r), r.ctypes.data, tm.ctypes.data, out.ctypes.data))
+    else:
+        _check(_rt().rt_debug_list_hit_masked(b.h, len(r), r.ctypes.data, tm.ctypes.data, int(mask), out.ctypes.data))
+    return out
+
+
+def debug_primary_mask(b: SceneBuilder, cam: CameraParams, W: int, H: int, pixels: np.ndarray, host: bool = False) -> np.ndarray:
+    """rt_debug_primary_mask (needs a GPU) / rt_debug_primary_mask_host (host=True, no GPU): the primary pass's pixel classifier
+    (csrc/rt_primary.h) for n pixels (i, j), j counted from the bottom row: per pixel a uint32 whose bit k is set when top-level object
+    k may be hit by a camera ray of that pixel (a clear bit is a proof)."""
+    px = np.ascontiguousarray(pixels, np.uint32).reshape(-1, 2)
+    out = np.zeros(len(px), np.uint32)
+    fn = _rt().rt_debug_primary_mask_host if host else _rt().rt_debug_primary_mask
+    _check(fn(b.h, C.byref(cam), W, H, px.ctypes.data, len(px), out.ctypes.data))
+    return out
+
+
 def debug_short_forms(op: int, a: np.ndarray, b: np.ndarray | None = None) -> np.ndarray:
     """rt_debug_short_forms (needs a GPU): the lean f64 kernel's exact short forms (csrc/rt_short.h) on caller operands, one record per
     lane, waves of 64.  op 0: a (n,) cosines, b (n,) max(dot, 0) -> (n, 3) pdf, sc, wave took the short form; op 1: a (n,) numerators,
