@@ -522,8 +522,8 @@ int rt_debug_onb_table(rt_scene*, uint64_t* mag_out, double* slots_out, uint32_t
  * be hit (a clear bit is a proof; a list of more than 32 objects gives all ones).  rt_debug_primary_mask runs the kernel that writes a
  * frame's masks before its launch, one thread per pixel (needs a GPU); rt_debug_primary_mask_host is its host twin (no GPU).  Host
  * pointers.  Environment, read once per launch like RT_NO_SHORT_DIV (A/B runs, tests): RT_NO_PRIMARY_PASS renders without the pass — the
- * 104-byte queue refilled with camera paths; samples are the same 64-bit words, but the frame is about 2.5 % slower than before the pass
- * existed, so it is no timing stand-in for an earlier build; RT_NO_PRIMARY_MASK keeps the pass and treats every object as a candidate. */
+ * other list kernels' loop, its queue refilled with camera paths; samples are the same 64-bit words; it is a switch for comparing
+ * samples, no timing stand-in for an earlier build; RT_NO_PRIMARY_MASK keeps the pass and treats every object as a candidate. */
 int rt_debug_primary_mask(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint32_t* out_masks);
 int rt_debug_primary_mask_host(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint32_t* out_masks);
 /* Known-answer access to the exact short forms of the lean f64 list-scene kernel (csrc/rt_short.h; rt_kernel.hip div_pi_pair, div_frame,

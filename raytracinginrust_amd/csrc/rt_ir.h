@@ -168,7 +168,7 @@ template <typename T> struct KParams {
     // RN(1 / (W - 1)) and RN(1 / (H - 1)) where the three-instruction form is proven to equal `/`, 0 where it is not (a divisor of 0,
     // 2^53 |zh C - 1| >= 1/2, RT_NO_SHORT_DIV): the kernel then divides.  Always f64; zero in every launch that is not a frame.
     double rcp_wm1, rcp_hm1;
-    // Primary pass (rt_kernel.hip PrimaryPass; lean f64 kernel only): one slot of 7168 B per wave of the launch, where a wave parks its 64
+    // Primary pass (rt_kernel.hip PrimaryPass; lean f64 kernel only): one slot of 6400 B per wave of the launch, where a wave parks its 64
     // live paths while the camera paths of a refill run their first level together.  Owned by the launch slot (rt_device.h), sized from
     // the launch's wave count.  Null (RT_NO_PRIMARY_PASS, every other kernel, every launch that is not a frame): no pass.
     unsigned char* park;

@@ -1751,14 +1751,14 @@ DEV bool take_new_paths(const KParams<T>& P, WaveWork& w, uint32_t lane, T* q_re
 // the lens disk and passes through one pixel's footprint.  Searched next to forty secondary rays they pay for every object of the list;
 // searched TOGETHER they skip the objects the whole bundle provably misses (rt_primary.h: a wave-uniform mask).  So this kernel does not
 // only generate when its queue runs dry: it parks the 64 lanes' live paths in the wave's own slot of KParams::park, generates the camera
-// paths into the LANES, runs one ordinary iteration of the bounce loop for them — the same code, the mask handed to world_hit_list —,
-// queues the survivors (ray, beta, rng, pixel, sample: 104 B; depth_left is max_depth - 1 for all of them) and takes its paths back.
-// Per path nothing changes: the same draws in the same order, the same operations on the same values; a path's first level runs
-// earlier, beside its pixel-mates.  park == nullptr (RT_NO_PRIMARY_PASS): the queue is refilled with camera paths (beta = 1) as in the
+// paths into the LANES, runs the first half of an iteration of the bounce loop for them — the same code, the mask handed to
+// world_hit_list —, queues the survivors as first-hit records (trace_shade_fill, below: 104 B) and takes its paths back.
+// Per path nothing changes: the same draws in the same order, the same operations on the same values; a path's first search runs
+// earlier, beside its pixel-mates.  park == nullptr (RT_NO_PRIMARY_PASS): trace_lockstep, the queue refilled with camera paths as in the
 // other kernels.
 template <typename T, uint32_t FEATS> struct PrimaryPass { static constexpr bool on = RT_TU != 2 && FEATS == 0u && sizeof(T) == 8u; };
-static constexpr uint32_t regen_bytes_pp(uint32_t qn) { return 10u * qn * 8u + 6u * qn * 4u; }     // [10][QN] f64: o d time beta, [6][QN] u32
-static constexpr uint32_t PARK_BYTES = RT_PARK_BYTES_PER_WAVE;                                       // per wave: [10][64] f64, [8][64] u32
+static constexpr uint32_t regen_bytes_pp(uint32_t qn) { return 9u * qn * 8u + 8u * qn * 4u; }      // [9][QN] f64: p n d, [8][QN] u32 (hit_queue_put)
+static constexpr uint32_t PARK_BYTES = RT_PARK_BYTES_PER_WAVE;                                       // per wave: [9][64] f64, [7][64] u32
 
 // The object mask of the cursor's pixel (wave-uniform; rt_primary.h): one word per local pixel, written before the launch by
 // primary_mask_kernel (below) — the classifier itself stays out of this kernel: inlined here it cost the bounce loop its register
@@ -1768,16 +1768,16 @@ template <typename T> DEV uint32_t pixel_mask(const KParams<T>& P, const WaveWor
     const uint32_t* const pm = PK(pmask);
     return pm ? cl(pm + w.cur_px) : 0xFFFFFFFFu;
 }
-// The next (up to) 64 samples of the cursor as camera paths in the lanes: refill_queue's cursor walk and camera arithmetic, expression
+// The next (up to) `limit` <= 64 samples of the cursor as camera paths in the lanes: refill_queue's cursor walk and camera arithmetic, expression
 // for expression (a copy, so that the other kernels' code is what it was).  Returns the number generated (0: the global queue is
 // exhausted); `have` lanes hold one.  mask: the OR of the cursor pixels' object masks.
 template <typename T>
-DEV uint32_t gen_camera_paths(const KParams<T>& P, WaveWork& w, uint32_t lane, bool want_mask, bool& have, RayT<T>& ray, Rng& rng, uint32_t& px, uint32_t& smp, uint32_t& mask) {
+DEV uint32_t gen_camera_paths(const KParams<T>& P, WaveWork& w, uint32_t lane, uint32_t limit, bool want_mask, bool& have, RayT<T>& ray, Rng& rng, uint32_t& px, uint32_t& smp, uint32_t& mask) {
     COLD_K;
     const uint32_t n_px = PK(W) * PK(H);
     have = false; mask = 0u;
     uint32_t g_gp = 0, g_i = 0, g_j = 0, n_gen = 0;
-    while (n_gen < 64u) {
+    while (n_gen < limit) {
         if (w.cur_px == w.end_px) {
             uint32_t c = 0;
             if (lane == 0) c = atomicAdd(PK(queue), 1u);
@@ -1787,7 +1787,7 @@ DEV uint32_t gen_camera_paths(const KParams<T>& P, WaveWork& w, uint32_t lane, b
         }
         if (w.cur_gp >= n_px || w.s_lo >= w.s_hi) { w.cur_px++; w.cur_s = w.s_lo; if (w.cur_px != w.end_px) locate(P, w); continue; }
         uint32_t avail = w.s_hi - w.cur_s;
-        uint32_t room = 64u - n_gen;
+        uint32_t room = limit - n_gen;
         uint32_t take = room < avail ? room : avail;
         if (lane >= n_gen && lane < n_gen + take) { have = true; px = w.cur_px; smp = w.cur_s + (lane - n_gen); g_gp = w.cur_gp; g_i = w.cur_i; g_j = w.cur_j; }
         if (want_mask) mask |= pixel_mask(P, w);
@@ -1823,53 +1823,10 @@ DEV uint32_t gen_camera_paths(const KParams<T>& P, WaveWork& w, uint32_t lane, b
     }
     return n_gen;
 }
-// One queue entry of the 104-byte form
-template <typename T>
-DEV void queue_put(T* q_real, uint32_t* q_u32, uint32_t e, const RayT<T>& ray, V3<T> beta, const Rng& rng, uint32_t px, uint32_t smp) {
-    q_real[0u * 64u + e] = ray.o.x; q_real[1u * 64u + e] = ray.o.y; q_real[2u * 64u + e] = ray.o.z;
-    q_real[3u * 64u + e] = ray.d.x; q_real[4u * 64u + e] = ray.d.y; q_real[5u * 64u + e] = ray.d.z;
-    q_real[6u * 64u + e] = ray.tm;
-    q_real[7u * 64u + e] = beta.x; q_real[8u * 64u + e] = beta.y; q_real[9u * 64u + e] = beta.z;
-    q_u32[0u * 64u + e] = rng.s0; q_u32[1u * 64u + e] = rng.s1; q_u32[2u * 64u + e] = rng.s2; q_u32[3u * 64u + e] = rng.s3;
-    q_u32[4u * 64u + e] = px; q_u32[5u * 64u + e] = smp;
-}
-// take_new_paths for the 104-byte queue: `dead` lanes pop what the queue holds.  With the pass on the queue is never refilled here (the
-// caller runs a pass when it is empty and lanes still want); with it off, camera paths with beta = 1 are generated into it.
-template <typename T>
-DEV bool take_new_paths_pp(const KParams<T>& P, WaveWork& w, uint32_t lane, T* q_real, uint32_t* q_u32, bool dead, bool pass_on,
-                           RayT<T>& ray, V3<T>& beta, Rng& rng, uint32_t& new_px, uint32_t& path_s) {
-    bool got_new = false;
-    for (;;) {
-        unsigned long long want = __ballot(dead && !got_new);
-        if (want == 0) break;
-        if (w.q_count == 0) {
-            if (w.queue_done || pass_on) break;
-            bool have; RayT<T> r; Rng g; uint32_t px = 0, smp = 0, mask;
-            const uint32_t n_gen = gen_camera_paths(P, w, lane, false, have, r, g, px, smp, mask);
-            if (n_gen == 0) break;
-            if (have) queue_put(q_real, q_u32, lane, r, mk<T>(T(1.0), T(1.0), T(1.0)), g, px, smp);
-            w.q_head = 0; w.q_count = n_gen;
-            __builtin_amdgcn_wave_barrier();
-        }
-        uint32_t n_want = (uint32_t)__popcll(want);
-        uint32_t take = n_want < w.q_count ? n_want : w.q_count;
-        uint32_t rank = lane_rank(want);
-        if (dead && !got_new && rank < take) {
-            const uint32_t e = w.q_head + rank;
-            got_new = true;
-            ray.o = mk<T>(q_real[0u * 64u + e], q_real[1u * 64u + e], q_real[2u * 64u + e]);
-            ray.d = mk<T>(q_real[3u * 64u + e], q_real[4u * 64u + e], q_real[5u * 64u + e]);
-            ray.tm = q_real[6u * 64u + e];
-            beta = mk<T>(q_real[7u * 64u + e], q_real[8u * 64u + e], q_real[9u * 64u + e]);
-            rng.s0 = q_u32[0u * 64u + e]; rng.s1 = q_u32[1u * 64u + e]; rng.s2 = q_u32[2u * 64u + e]; rng.s3 = q_u32[3u * 64u + e];
-            new_px = q_u32[4u * 64u + e]; path_s = q_u32[5u * 64u + e];
-        }
-        w.q_head += take; w.q_count -= take;
-    }
-    return got_new;
-}
-// A wave's parked paths: [10][64] f64 then [8][64] u32 in its own slot, every access one lane's own word (ordinary vector stores and
-// loads, 256 or 512 contiguous bytes per instruction; a lane reads back only what it wrote itself, in program order).
+// A wave's parked paths: [9][64] f64 (o d beta) then [7][64] u32 (rng, depth_left, sample, alive) in its own slot — the ray's time is
+// not parked (this kernel's scenes never read it) and neither is the accumulator's pixel (the sum stays in its registers through the
+// pass) —, every access one lane's own word (ordinary vector stores and loads, 256 or 512 contiguous bytes per instruction; a lane reads
+// back only what it wrote itself, in program order).
 // The slot's address is formed where it is used, from the kernel argument and a lane index the compiler cannot see through: formed in
 // front of the bounce loop, the lanes' eighteen addresses stay in vector registers through every iteration (*seen*: 14 VGPRs held and
 // five more pairs spilled and reloaded per iteration).
@@ -1879,24 +1836,22 @@ template <typename T> DEV double* park_slot(uint32_t wave_slot, uint32_t& lane) 
     return (double*)(PK(park) + (size_t)wave_slot * PARK_BYTES);
 }
 template <typename T>
-DEV void park_paths(double* pr, uint32_t lane, const RayT<T>& ray, V3<T> beta, const Rng& rng, uint32_t depth_left, uint32_t path_s, uint32_t acc_px, bool alive) {
-    uint32_t* pu = (uint32_t*)(pr + 10u * 64u);
+DEV void park_paths(double* pr, uint32_t lane, const RayT<T>& ray, V3<T> beta, const Rng& rng, uint32_t depth_left, uint32_t path_s, bool alive) {
+    uint32_t* pu = (uint32_t*)(pr + 9u * 64u);
     pr[0u * 64u + lane] = ray.o.x; pr[1u * 64u + lane] = ray.o.y; pr[2u * 64u + lane] = ray.o.z;
     pr[3u * 64u + lane] = ray.d.x; pr[4u * 64u + lane] = ray.d.y; pr[5u * 64u + lane] = ray.d.z;
-    pr[6u * 64u + lane] = ray.tm;
-    pr[7u * 64u + lane] = beta.x; pr[8u * 64u + lane] = beta.y; pr[9u * 64u + lane] = beta.z;
+    pr[6u * 64u + lane] = beta.x; pr[7u * 64u + lane] = beta.y; pr[8u * 64u + lane] = beta.z;
     pu[0u * 64u + lane] = rng.s0; pu[1u * 64u + lane] = rng.s1; pu[2u * 64u + lane] = rng.s2; pu[3u * 64u + lane] = rng.s3;
-    pu[4u * 64u + lane] = depth_left; pu[5u * 64u + lane] = path_s; pu[6u * 64u + lane] = acc_px; pu[7u * 64u + lane] = alive ? 1u : 0u;
+    pu[4u * 64u + lane] = depth_left; pu[5u * 64u + lane] = path_s; pu[6u * 64u + lane] = alive ? 1u : 0u;
 }
 template <typename T>
-DEV void unpark_paths(const double* pr, uint32_t lane, RayT<T>& ray, V3<T>& beta, Rng& rng, uint32_t& depth_left, uint32_t& path_s, uint32_t& acc_px, bool& alive) {
-    const uint32_t* pu = (const uint32_t*)(pr + 10u * 64u);
+DEV void unpark_paths(const double* pr, uint32_t lane, RayT<T>& ray, V3<T>& beta, Rng& rng, uint32_t& depth_left, uint32_t& path_s, bool& alive) {
+    const uint32_t* pu = (const uint32_t*)(pr + 9u * 64u);
     ray.o = mk<T>(pr[0u * 64u + lane], pr[1u * 64u + lane], pr[2u * 64u + lane]);
     ray.d = mk<T>(pr[3u * 64u + lane], pr[4u * 64u + lane], pr[5u * 64u + lane]);
-    ray.tm = pr[6u * 64u + lane];
-    beta = mk<T>(pr[7u * 64u + lane], pr[8u * 64u + lane], pr[9u * 64u + lane]);
+    beta = mk<T>(pr[6u * 64u + lane], pr[7u * 64u + lane], pr[8u * 64u + lane]);
     rng.s0 = pu[0u * 64u + lane]; rng.s1 = pu[1u * 64u + lane]; rng.s2 = pu[2u * 64u + lane]; rng.s3 = pu[3u * 64u + lane];
-    depth_left = pu[4u * 64u + lane]; path_s = pu[5u * 64u + lane]; acc_px = pu[6u * 64u + lane]; alive = pu[7u * 64u + lane] != 0u;
+    depth_left = pu[4u * 64u + lane]; path_s = pu[5u * 64u + lane]; alive = pu[6u * 64u + lane] != 0u;
 }
 
 // The colour of a Lambertian / DiffuseLight material.  The lean kernels (constant textures only) take it from the material record they
@@ -2174,24 +2129,13 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
     uint32_t n_nonfinite = 0, n_flush = 0;
     unsigned long long n_iters = 0, n_active = 0;
     DIAG_DECL
-    // the primary pass (above: PrimaryPass): this wave's parking slot, and the depth a queued path starts at
-    constexpr bool PP = PrimaryPass<T, FEATS>::on;
-    bool pass_on = false; uint32_t depth_new = 0u, wave_slot = 0u;
-    if constexpr (PP) {
-        COLD_K;
-        pass_on = PK(park) != nullptr;
-        wave_slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * Shape<FEATS>::WAVES + (threadIdx.x >> 6)));
-        depth_new = P.max_depth - (pass_on ? 1u : 0u);      // (max_depth 0 with the pass on: every path ends in the pass, nothing is queued)
-    }
 
     for (;;) {
         DIAG_T0();
         // ---- lanes whose path has ended take the next camera path from the wave's queue
         uint32_t new_px = 0;
-        bool got_new;
-        if constexpr (PP) got_new = take_new_paths_pp(P, w, lane, q_real, q_u32, !alive, pass_on, ray, beta, rng, new_px, path_s);
-        else got_new = take_new_paths(P, w, lane, q_real, q_u32, !alive, ray, rng, new_px, path_s);
-        if constexpr (!PP) if (__ballot(alive || got_new) == 0) break;     // queue empty and every path finished
+        const bool got_new = take_new_paths(P, w, lane, q_real, q_u32, !alive, ray, rng, new_px, path_s);
+        if (__ballot(alive || got_new) == 0) break;     // queue empty and every path finished
         DIAG_ADD(0);
 
         // ---- lanes moving on to another pixel hand in their partial sum
@@ -2199,26 +2143,9 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
 
         if (got_new) {
             if (acc_px != new_px) { acc_px = new_px; acc.set(0, 0.0); acc.set(1, 0.0); acc.set(2, 0.0); }
-            if constexpr (!PP) beta = mk<T>(T(1.0), T(1.0), T(1.0));       // (PP: the queue entry's — 1 for a camera path)
-            depth_left = PP ? depth_new : P.max_depth;
+            beta = mk<T>(T(1.0), T(1.0), T(1.0));
+            depth_left = P.max_depth;
             alive = true;
-        }
-
-        // ---- the queue is empty and lanes still want a path: the primary pass — park, generate into the lanes, and let this iteration be theirs
-        bool primary = false;
-        uint32_t obj_mask = 0xFFFFFFFFu;
-        if constexpr (PP) {
-            if (pass_on && w.q_count == 0u && !w.queue_done && __ballot(!alive) != 0ull) {
-                uint32_t pl = lane;
-                double* const park = park_slot<T>(wave_slot, pl);
-                park_paths(park, pl, ray, beta, rng, depth_left, path_s, acc_px, alive);
-                bool have;
-                if (gen_camera_paths(P, w, lane, true, have, ray, rng, acc_px, path_s, obj_mask) != 0u) {
-                    primary = true;
-                    alive = have; beta = mk<T>(T(1.0), T(1.0), T(1.0)); depth_left = P.max_depth;
-                } else { unpark_paths(park, pl, ray, beta, rng, depth_left, path_s, acc_px, alive); obj_mask = 0xFFFFFFFFu; }      // (nothing left to generate: an ordinary iteration)
-            }
-            if (__ballot(alive) == 0) break;            // queue empty and every path finished
         }
 
         n_iters++;
@@ -2226,8 +2153,6 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
         DIAG_ADD(1);
 
         // ---- one level of ray_color (main.rs:41-120) for every live lane
-        [[maybe_unused]] bool ended = false;                                     // (PP, in a pass) this lane's path ended: pacc holds its radiance
-        [[maybe_unused]] typename Shape<FEATS>::Acc pacc; if constexpr (PP) { pacc.set(0, 0.0); pacc.set(1, 0.0); pacc.set(2, 0.0); }
         if (alive) {
             bool done = false;
             V3<T> e = mk<T>(T(0), T(0), T(0));          // terminal radiance of this path (times beta)
@@ -2236,8 +2161,7 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
             } else {
                 T t_hit; HitId id; id.obj = 0; id.prim = 0;
                 bool any_hit;                                                                            // main.rs:48
-                if constexpr (PP) any_hit = world_hit_list<T, true>(P, ray, TMin<T>::v(), rng, t_hit, id, obj_mask);
-                else if constexpr (FEATS == 0u) any_hit = world_hit_list<T>(P, ray, TMin<T>::v(), rng, t_hit, id);
+                if constexpr (FEATS == 0u) any_hit = world_hit_list<T>(P, ray, TMin<T>::v(), rng, t_hit, id);
                 else any_hit = world_hit<T, FEATS>(P, ray, TMin<T>::v(), rng, t_hit, id, stack);
                 DIAG_ADD(2);
                 if (!any_hit) {
@@ -2261,30 +2185,10 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
             }
             DIAG_ADD(4);
             if (done) {
-                if constexpr (PP) {
-                    // a path that ends in the pass (the light seen directly, a miss, max_depth <= 1, Metal's absorbed ray) goes into a sum of
-                    // its own, not into the parked lane's
-                    if (primary) { ended = true; add_radiance(P, beta * e, pacc, n_nonfinite, path_px, path_s); }
-                    else add_radiance(P, beta * e, acc, n_nonfinite, path_px, path_s);
-                } else
                 add_radiance(P, beta * e, acc, n_nonfinite, path_px, path_s);
                 alive = false;
             }
             DIAG_ADD(5);
-        }
-        if constexpr (PP) {
-            if (primary) {
-                // ---- the end of the pass: what ended is handed in per pixel (one butterfly and three atomics, as for any other
-                // partial sum), the survivors are queued in lane order, and the wave takes its parked paths back
-                flush_acc<T, typename Shape<FEATS>::Acc, false>(P, ended, acc_px, pacc, lane, n_flush);
-                const unsigned long long sv = __ballot(alive);
-                if (alive) queue_put(q_real, q_u32, lane_rank(sv), ray, beta, rng, acc_px, path_s);
-                w.q_head = 0u; w.q_count = (uint32_t)__popcll(sv);
-                __builtin_amdgcn_wave_barrier();          // one wave: LDS writes above are ordered before the reads of the pops
-                uint32_t pl = lane;
-                double* const park = park_slot<T>(wave_slot, pl);
-                unpark_paths(park, pl, ray, beta, rng, depth_left, path_s, acc_px, alive);
-            }
         }
     }
     // ---- the queue is empty: hand in what is left
@@ -2298,6 +2202,210 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
 }
 
 #undef path_px
+
+// ------------------------------------------------------------------ the lean f64 kernel: lock-step bounce loop with shade fill
+// The primary pass (above: PrimaryPass) stopping one stage earlier.  36 % of a wave's lanes end at their hit (the light, a miss) and used
+// to idle through shade_hit, a third of the iteration, before taking a queued path at the next top.  Here the pass ends after
+// finalize_hit: the camera paths that hit a scattering surface are queued as FIRST-HIT RECORDS (p, n, d, mat, rect | front << 31, rng,
+// pixel, sample — 104 B; beta is 1, depth_left is max_depth, the origin and the time are not read again), and in an ordinary iteration
+// the lanes whose path has just ended, or that had none, pop one BETWEEN the hit record and the material section and are shaded with the
+// wave.  A lane that finds the queue dry idles through that shade and through the next search and pops after it.  For that the decision
+// of shade_hit (does the path end at this hit?) is taken before its work: a DiffuseLight's `emitted` (mat.rs:395-401) is evaluated on
+// the ending lanes, and shade_hit sees scattering lanes only.  Per path nothing changes: the same draws in the same order, the same
+// operations on the same values.
+// The loop body is written material section first — shade what the last iteration left, then search, then pop —, so that the popped
+// records reach shade_hit as ordinary loop-carried values: with the pop in the middle of the body the compiler copied the whole path
+// state on every way into the material section and spilled 60 to 100 VGPRs (*seen*, measured 117 ms against the parent's 78).
+// The queue is a ring of 64 and the pass runs when fewer than FILL_AT records are left, for as many camera paths as the ring has room
+// for: waiting for an empty queue leaves the lanes that found it dry without a path through the next search (*measured*, Cornell box
+// 800 x 800 x 1024: FILL_AT 1 77.81 ms, 16 76.21, 24 76.43, 32 79.26; the parent 77.84).
+// A lane that pops a path of another pixel keeps its old pixel's sum (acc, acc_px) until the flush, where it has always stood; should the
+// new path end in the very shade it was popped for (Metal's absorbed ray, max_depth 1), its radiance goes to its own pixel with three
+// atomics of the lane's own (rare: flush_acc's PER_LANE form).
+// RT_NO_PRIMARY_PASS (park == nullptr) does not come here: pathtrace_kernel runs trace_lockstep, camera paths through the queue.
+template <typename T>
+DEV void hit_queue_put(T* q_real, uint32_t e, const Rec<T>& rec, V3<T> d, const Rng& rng, uint32_t px, uint32_t smp, uint32_t rect_front) {
+    uint32_t* q_u32 = (uint32_t*)(q_real + 9u * 64u);                 // [9][64] f64: p n d, [8][64] u32
+    q_real[0u * 64u + e] = rec.p.x; q_real[1u * 64u + e] = rec.p.y; q_real[2u * 64u + e] = rec.p.z;
+    q_real[3u * 64u + e] = rec.n.x; q_real[4u * 64u + e] = rec.n.y; q_real[5u * 64u + e] = rec.n.z;
+    q_real[6u * 64u + e] = d.x; q_real[7u * 64u + e] = d.y; q_real[8u * 64u + e] = d.z;
+    q_u32[0u * 64u + e] = rng.s0; q_u32[1u * 64u + e] = rng.s1; q_u32[2u * 64u + e] = rng.s2; q_u32[3u * 64u + e] = rng.s3;
+    q_u32[4u * 64u + e] = px; q_u32[5u * 64u + e] = smp; q_u32[6u * 64u + e] = rec.mat; q_u32[7u * 64u + e] = rect_front;
+}
+// `dead` lanes pop what the ring holds, in lane order.  True for the lanes that got a first-hit record.  One divergent branch and no
+// wave-uniform one ("nobody wants", "queue empty"): every further way to the material section is another set of copies of the path state.
+template <typename T>
+DEV bool hit_queue_pop(WaveWork& w, const T* q_real, bool dead, V3<T>& p, V3<T>& n, V3<T>& d, Rng& rng, uint32_t& px, uint32_t& smp, uint32_t& mat, uint32_t& rect_front) {
+    const unsigned long long want = __ballot(dead);
+    const uint32_t* q_u32 = (const uint32_t*)(q_real + 9u * 64u);
+    const uint32_t n_want = (uint32_t)__popcll(want);
+    const uint32_t take = n_want < w.q_count ? n_want : w.q_count;
+    const uint32_t rank = lane_rank(want);
+    const bool got = dead && rank < take;
+    if (got) {
+        const uint32_t e = (w.q_head + rank) & 63u;
+        p = mk<T>(q_real[0u * 64u + e], q_real[1u * 64u + e], q_real[2u * 64u + e]);
+        n = mk<T>(q_real[3u * 64u + e], q_real[4u * 64u + e], q_real[5u * 64u + e]);
+        d = mk<T>(q_real[6u * 64u + e], q_real[7u * 64u + e], q_real[8u * 64u + e]);
+        rng.s0 = q_u32[0u * 64u + e]; rng.s1 = q_u32[1u * 64u + e]; rng.s2 = q_u32[2u * 64u + e]; rng.s3 = q_u32[3u * 64u + e];
+        px = q_u32[4u * 64u + e]; smp = q_u32[5u * 64u + e]; mat = q_u32[6u * 64u + e]; rect_front = q_u32[7u * 64u + e];
+    }
+    w.q_head = (w.q_head + take) & 63u; w.q_count -= take;
+    return got;
+}
+// The pass runs when fewer than FILL_AT records are queued, for as many camera paths as the ring has room for (at least 64 - FILL_AT + 1).
+// *Measured* on the Cornell box, 800 x 800 x 1024: 1 (only when the queue is empty) 77.81 ms, 16 76.21, 24 76.43, 32 79.26; nothing between.
+static constexpr uint32_t FILL_AT = 16u;
+template <typename T, uint32_t FEATS>
+DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
+    static_assert(PrimaryPass<T, FEATS>::on, "the lean f64 kernel only");
+    typedef typename Shape<FEATS>::Acc Acc;
+    WaveWork w; w.cur_px = w.end_px = w.cur_s = w.s_lo = w.s_hi = w.cur_gp = w.cur_i = w.cur_j = w.q_head = w.q_count = 0; w.queue_done = false;
+    // per-lane path state
+    bool alive = false;
+    RayT<T> ray; ray.o = mk<T>(T(0), T(0), T(0)); ray.d = ray.o; ray.tm = T(0);
+    V3<T> beta = mk<T>(T(0), T(0), T(0));
+    uint32_t depth_left = 0, path_s = 0, path_px = NONE_PX;
+    Rng rng; rng.s0 = rng.s1 = rng.s2 = rng.s3 = 0;
+    // per-lane accumulator for one local pixel: the path's own (acc_px == path_px) from the top of the iteration after the one it was popped in
+    uint32_t acc_px = NONE_PX;
+    Acc acc;
+    acc.set(0, 0.0); acc.set(1, 0.0); acc.set(2, 0.0);
+    uint32_t n_nonfinite = 0, n_flush = 0;
+    unsigned long long n_iters = 0, n_active = 0;
+    DIAG_DECL
+    const uint32_t wave_slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * Shape<FEATS>::WAVES + (threadIdx.x >> 6)));    // its parking slot
+
+    // the hit record a live lane carries to the material section: ray.o is its p; n, mat, rect | front << 31 beside it
+    Rec<T> rec; rec.p = ray.o; rec.n = ray.o; rec.t = rec.u = rec.v = T(0); rec.front = false; rec.mat = 0u;
+    uint32_t rect_front = 0u;
+    bool unshaded = true;                     // wave-uniform: the live lanes hold hit records (false right after a pass: they hold rays)
+    for (;;) {
+        DIAG_T0();
+        // ---- the second half of a level of ray_color (main.rs:85-116), the material, for every lane with a hit record: the survivors of the
+        // last search and the lanes that popped a first-hit record after it
+        if (unshaded && alive) {
+            bool done = false;
+            V3<T> e = mk<T>(T(0), T(0), T(0));
+            rec.p = ray.o; rec.front = (rect_front >> 31) != 0u;
+            shade_hit<T, FEATS>(P, rec, ray, beta, rng, depth_left, done, e, rect_front & 0x7FFFFFFFu);
+            if (done) {
+                if (path_px == acc_px) add_radiance(P, beta * e, acc, n_nonfinite, path_px, path_s);
+                else {                                  // popped into another pixel and ended at once: its own three atomics
+                    Acc one; one.set(0, 0.0); one.set(1, 0.0); one.set(2, 0.0);
+                    add_radiance(P, beta * e, one, n_nonfinite, path_px, path_s);
+                    flush_acc<T, Acc, true>(P, true, path_px, one, lane, n_flush);
+                }
+                alive = false;
+            }
+        }
+        DIAG_ADD(5);
+        DIAG_ADD(0);
+
+        // ---- lanes that have moved on to another pixel hand in their partial sum
+        {
+            const bool moved = alive && acc_px != path_px;
+            flush_acc<T, Acc, false>(P, moved && acc_px != NONE_PX, acc_px, acc, lane, n_flush);
+            if (moved) { acc_px = path_px; acc.set(0, 0.0); acc.set(1, 0.0); acc.set(2, 0.0); }
+            path_px = acc_px;                       // (a lane without a path: one value for both until it pops)
+        }
+
+        // ---- fewer than FILL_AT records are queued: the primary pass — park, generate into the lanes, and let this iteration's search be theirs
+        bool primary = false;
+        uint32_t obj_mask = 0xFFFFFFFFu;
+        if (w.q_count < FILL_AT && !w.queue_done) {
+            uint32_t pl = lane;
+            double* const park = park_slot<T>(wave_slot, pl);
+            park_paths(park, pl, ray, beta, rng, depth_left, path_s, alive);
+            bool have;
+            if (gen_camera_paths(P, w, lane, 64u - w.q_count, true, have, ray, rng, path_px, path_s, obj_mask) != 0u) {
+                primary = true;
+                alive = have; beta = mk<T>(T(1.0), T(1.0), T(1.0)); depth_left = P.max_depth;
+            } else { unpark_paths(park, pl, ray, beta, rng, depth_left, path_s, alive); path_px = acc_px; obj_mask = 0xFFFFFFFFu; }      // (nothing left to generate: an ordinary iteration)
+        }
+        if (__ballot(alive) == 0ull && w.q_count == 0u) break;            // nothing queued and every path finished
+
+        n_iters++;
+        n_active += (unsigned long long)__popcll(__ballot(alive));         // lanes live at the search
+        DIAG_ADD(1);
+
+        // ---- the first half of a level of ray_color (main.rs:41-84) for every live lane: the search, the hit record, and the paths that end here
+        Acc pacc; pacc.set(0, 0.0); pacc.set(1, 0.0); pacc.set(2, 0.0);        // (in a pass) the radiance of the camera paths that ended
+        bool ended = false;
+        Rec<T> hr; hr.p = rec.n; hr.n = rec.n; hr.t = hr.u = hr.v = T(0); hr.front = false; hr.mat = 0u;     // (lanes without a hit: any defined value)
+        uint32_t hrect = 0u;
+        if (alive) {
+            bool done = false;
+            V3<T> e = mk<T>(T(0), T(0), T(0));          // terminal radiance of this path (times beta)
+            if (depth_left == 0) {
+                done = true;                            // main.rs:42-45
+            } else {
+                T t_hit; HitId id; id.obj = 0; id.prim = 0;
+                const bool any_hit = world_hit_list<T, true>(P, ray, TMin<T>::v(), rng, t_hit, id, obj_mask);   // main.rs:48
+                DIAG_ADD(2);
+                if (!any_hit) {
+                    e = ld3(P.background); done = true;                                     // main.rs:118
+                } else {
+                    finalize_hit<T, FEATS>(P, ray, t_hit, id, true, hr);
+                    hrect = id.prim & 0x0FFFFFFFu;
+                    DIAG_ADD(3);
+#ifdef RT_TRACE_PATH    // debugging build only (tools/fuzz_probe.py): the hits of one path, level by level, for comparison with the oracle's orc_trace_path
+                    if (P.trace_out && path_px == P.trace_px && path_s == P.trace_s && depth_left <= P.max_depth) {
+                        double* o = P.trace_out + 16u * (P.max_depth - depth_left);
+                        o[0] = (double)hr.t; o[1] = (double)hr.p.x; o[2] = (double)hr.p.y; o[3] = (double)hr.p.z;
+                        o[4] = (double)hr.n.x; o[5] = (double)hr.n.y; o[6] = (double)hr.n.z; o[7] = hr.front ? 1.0 : 0.0;
+                        o[8] = (double)id.obj; o[9] = (double)(id.prim >> 28); o[10] = (double)(id.prim & 0x0FFFFFFFu); o[11] = (double)hr.mat;
+                        o[12] = (double)ray.d.x; o[13] = (double)ray.d.y; o[14] = (double)ray.d.z; o[15] = 1.0;
+                    }
+#endif
+                    // shade_hit's decision: only Lambertian and Metal scatter (its other arms are not in this kernel); a DiffuseLight emits
+                    // from its front face and every other material absorbs
+                    const DMaterial<T>* const mp = P.materials + hr.mat;
+                    const uint32_t kind = cl(&mp->kind) & MAT_KIND_MASK;
+                    if (kind != M_LAMBERTIAN && kind != M_METAL) {
+                        if (kind == M_DIFFUSE_LIGHT && hr.front) e = cl3(mp->albedo);
+                        done = true;
+                    }
+                }
+            }
+            if (done) {
+                // a camera path that ends in the pass (the light seen directly, a miss, max_depth 0) goes into a sum of its own, not into the parked lane's
+                if (primary) { ended = true; add_radiance(P, beta * e, pacc, n_nonfinite, path_px, path_s); }
+                else add_radiance(P, beta * e, acc, n_nonfinite, path_px, path_s);
+                alive = false;
+            }
+        }
+        DIAG_ADD(4);
+        // the hit point is the next origin already (what shade_hit leaves there when the path goes on), on every lane: the old origin is dead
+        // from the hit record on, not carried through the material section
+        hrect |= hr.front ? 0x80000000u : 0u;
+        if (primary) {
+            // ---- the end of the pass: what ended is handed in per pixel (one butterfly and three atomics, as for any other partial sum),
+            // the first-hit records are queued in lane order, and the wave takes its parked paths back; its dead lanes pop after the next search
+            flush_acc<T, Acc, false>(P, ended, path_px, pacc, lane, n_flush);
+            const unsigned long long sv = __ballot(alive);
+            if (alive) hit_queue_put(q_real, (w.q_head + w.q_count + lane_rank(sv)) & 63u, hr, ray.d, rng, path_px, path_s, hrect);
+            w.q_count += (uint32_t)__popcll(sv);               // (a ring of 64: at most 64 - q_count were generated)
+            __builtin_amdgcn_wave_barrier();          // one wave: LDS writes above are ordered before the reads of the pops
+            uint32_t pl = lane;
+            double* const park = park_slot<T>(wave_slot, pl);
+            unpark_paths(park, pl, ray, beta, rng, depth_left, path_s, alive); path_px = acc_px;
+            unshaded = false;
+        } else {
+            // ---- the lanes without a path take a first-hit record and join the others at the material section
+            ray.o = hr.p; rec.n = hr.n; rec.mat = hr.mat; rect_front = hrect;
+            if (hit_queue_pop(w, q_real, !alive, ray.o, rec.n, ray.d, rng, path_px, path_s, rec.mat, rect_front)) { beta = mk<T>(T(1.0), T(1.0), T(1.0)); depth_left = P.max_depth; alive = true; }
+            unshaded = true;
+        }
+    }
+    // ---- the queue is empty: hand in what is left
+    flush_acc<T, Acc, false>(P, acc_px != NONE_PX, acc_px, acc, lane, n_flush);
+    unsigned long long* st; { COLD_K; st = stats_row(PK(stats)); }
+    write_stats(st, lane, n_nonfinite, n_iters, n_active, n_flush);
+#ifdef RT_DIAG
+    if (st && lane == 0) for (int k = 0; k < 6; k++) atomicAdd(&st[3 + k], dg_sum[k]);
+#endif
+}
 // ------------------------------------------------------------------ BVH scenes: resumable closest-hit search, persistent traversal
 // With a BVH in the scene the cost of `world.hit` differs wildly between lanes (a ray that misses the root box is done
 // after one node, its neighbour walks a hundred), and in lock-step every lane waits for the slowest one: *measured* VALU
@@ -2587,17 +2695,20 @@ __global__ void __launch_bounds__(Shape<FEATS>::THREADS, Shape<FEATS>::WAVES_PER
         __syncthreads();
     }
     const uint32_t QN = P.queue_entries;
-    if constexpr (PrimaryPass<T, FEATS>::on) {                     // 64 entries of 104 B: [10][64] f64 (... beta), [6][64] u32 (rt_launch.h sizes it so)
+    if constexpr (PrimaryPass<T, FEATS>::on) {                     // 64 entries of 104 B: [9][64] f64, [8][64] u32 (rt_launch.h sizes it so)
         unsigned char* regen = lds_raw + wave_in_block * regen_bytes_pp(64u);
-        trace_lockstep<T, FEATS>(P, lane, (T*)regen, (uint32_t*)(regen + 10u * 64u * sizeof(T)), nullptr);
+        bool pass_on; { COLD_K; pass_on = PK(park) != nullptr; }
+        if (pass_on) trace_shade_fill<T, FEATS>(P, lane, (T*)regen);
+        else trace_lockstep<T, FEATS>(P, lane, (T*)regen, (uint32_t*)(regen + 7u * 64u * sizeof(T)), nullptr);     // RT_NO_PRIMARY_PASS: camera paths through the queue, [7][64] f64 [6][64] u32 of the same 104 B
         return;
-    }
+    } else {
     unsigned char* regen = lds_raw + nodes_bytes + wave_in_block * regen_bytes(QN);
     T* q_real = (T*)regen;                                         // [7][QN]: o.x o.y o.z d.x d.y d.z time
     uint32_t* q_u32 = (uint32_t*)(regen + 7u * QN * sizeof(T));    // [6][QN]: rng s0..s3, local pixel, sample
     uint32_t* stack = (uint32_t*)(lds_raw + nodes_bytes + S::WAVES * regen_bytes(QN)) + wave_in_block * (P.stack_depth * 64u) + lane;
     if (FEATS & F_PERSIST) trace_resumable<T, FEATS>(P, lane, q_real, q_u32, stack);
     else trace_lockstep<T, FEATS>(P, lane, q_real, q_u32, stack);
+    }
 }
 
 #if RT_TU != 3      // (RT_TU == 3: csrc/rt_query.hip includes this file for the device functions above and brings its own kernels and launch code)

@@ -9,7 +9,7 @@ namespace rt {
 // CU's LDS then holds one copy of the top of the BVH, KParams::n_cached nodes).
 struct LaunchShape { uint32_t threads, queue_entries, entry_bytes; bool one_per_cu; };
 // The lean f64 kernel's queue (rt_kernel.hip PrimaryPass): always 64 entries of 104 B.  Every other shape is left as it is.
-static const uint32_t RT_PARK_BYTES_PER_WAVE = 64u * (10u * 8u + 8u * 4u);
+static const uint32_t RT_PARK_BYTES_PER_WAVE = 64u * (9u * 8u + 7u * 4u);
 inline void lean_f64_queue(LaunchShape& g) { g.queue_entries = 64u; g.entry_bytes = 104u; }
 LaunchShape pathtrace_shape(uint32_t scene_feats, uint32_t flags);
 uint32_t pathtrace_feats(uint32_t scene_feats, uint32_t flags);      // the instantiation's FEATS template argument (its name: rt::pathtrace_kernel<T, FEATSu>)
