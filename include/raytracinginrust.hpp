@@ -240,6 +240,36 @@ inline std::vector<double> denoise_host(const std::vector<double>& rgb_sum, uint
     return out;
 }
 
+// Albedo queries (rt_query_albedo, rt_query_camera_albedo): the reflectance at the closest hit — the texture value under a Lambertian, PBR
+// or ConstantMedium hit, a Metal's albedo, (1, 1, 1) for glass, emitters and misses.  query_albedo: n x 3 doubles for caller rays (hits_out,
+// optional, receives the hits of query_hits for the same rays and seed).  query_camera_albedo: W*H*3 doubles in output order, per pixel the
+// SUM over samples [first_sample, first_sample + n_samples) of the albedo under that sample's camera ray — what `denoise_albedo` divides by.
+inline std::vector<double> query_albedo(Scene& s, const std::vector<Ray>& rays, double t_min = 0.00001, uint64_t seed = 0, std::vector<Hit>* hits_out = nullptr) {
+    std::vector<double> in(rays.size() * 7), out(rays.size() * 3), rec(hits_out ? rays.size() * 16 : 0);
+    for (size_t k = 0; k < rays.size(); k++) {
+        for (int a = 0; a < 3; a++) { in[k * 7 + a] = rays[k].origin.e[a]; in[k * 7 + 3 + a] = rays[k].direction.e[a]; }
+        in[k * 7 + 6] = rays[k].time;
+    }
+    if (rt_query_albedo(s.raw(), (uint32_t)rays.size(), in.data(), t_min, seed, 0, out.data(), hits_out ? rec.data() : nullptr) != 0) throw Error(rt_last_error());
+    if (hits_out) { hits_out->resize(rays.size()); for (size_t k = 0; k < rays.size(); k++) (*hits_out)[k] = Hit::from_record(&rec[k * 16]); }
+    return out;
+}
+inline std::vector<double> query_camera_albedo(Scene& s, const Camera& cam, uint32_t W, uint32_t H, uint32_t first_sample = 0, uint32_t n_samples = 1,
+                                               uint64_t seed = 0x5EED) {
+    std::vector<double> out((size_t)W * H * 3);
+    if (rt_query_camera_albedo(s.raw(), &cam.c, W, H, first_sample, n_samples, seed, 0, out.data()) != 0) throw Error(rt_last_error());
+    return out;
+}
+// `denoise` on rgb_sum / albedo, multiplied back (rt_denoise_albedo): textures are not colour the filter has to preserve.  albedo_sum as
+// query_camera_albedo returns it, holding albedo_samples samples per pixel.
+inline std::vector<double> denoise_albedo(const std::vector<double>& rgb_sum, uint64_t samples, const std::vector<double>& albedo_sum, uint64_t albedo_samples,
+                                          const std::vector<double>& hit_records, uint32_t W, uint32_t H, const DenoiseSettings& d = DenoiseSettings()) {
+    if (rgb_sum.size() != (size_t)W * H * 3 || albedo_sum.size() != rgb_sum.size() || hit_records.size() != (size_t)W * H * 16) throw Error("denoise_albedo: frame, albedo or records of another size");
+    std::vector<double> out(rgb_sum.size());
+    if (rt_denoise_albedo(rgb_sum.data(), samples, albedo_sum.data(), albedo_samples, hit_records.data(), W, H, d.iterations, d.sigma, d.flags, out.data()) != 0) throw Error(rt_last_error());
+    return out;
+}
+
 // ray_color (src/main.rs:41-120) along rays the caller chooses (rt_query_radiance), samples_per_ray samples of each: per ray the SUM over
 // its samples, n x 3, as render() returns per pixel — another projection than Camera's, a light probe, a baked light map.  Sample s of ray k
 // draws from the stream of rt_rng_path(seed, k, s).  samples_out (optional) receives every sample, ray-major; nonfinite_out (optional) the
@@ -287,6 +317,10 @@ public:
     // the frame as it is now through `denoise` and format_color on the device (the frame builds and keeps its own guide); rgb8 and its count are untouched
     std::vector<uint8_t> rgb8_denoised(const DenoiseSettings& d = DenoiseSettings()) {
         std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_denoised_rgb8(p_, d.iterations, d.sigma, d.flags, out.data())); return out;
+    }
+    // the same with albedo demodulation (`denoise_albedo`): the frame builds the albedo sums of samples [0, albedo_samples) itself and keeps them
+    std::vector<uint8_t> rgb8_denoised_albedo(uint32_t albedo_samples = 16, const DenoiseSettings& d = DenoiseSettings()) {
+        std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_denoised_albedo_rgb8(p_, albedo_samples, d.iterations, d.sigma, d.flags, out.data())); return out;
     }
     std::vector<double> sum() const { std::vector<double> out(n_px_ * 3); chk(rt_progressive_read_sum(p_, out.data())); return out; }
     void load(const std::vector<double>& rgb_sum, uint64_t samples_done) {

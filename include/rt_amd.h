@@ -273,6 +273,32 @@ int rt_query_camera_device(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, 
                            void* d_rays_out, void* d_hits_out, size_t d_hits_bytes, void* hip_stream);
 int rt_last_query_ms(rt_scene*, float* ms_out);   /* HIP events around the most recent query kernel of this scene (ray or radiance query); waits */
 
+/* ---- albedo queries: the reflectance at the closest hit, for rays the caller chooses or summed over a range of samples of every pixel's
+ *      camera ray — the albedo frame a denoiser divides a textured frame by (rt_denoise_albedo* below), or a compositor's base-colour pass.
+ *      The closest hit is found exactly as rt_query_hits / rt_query_camera find it (the same search, stream and record) and its albedo is
+ *      (csrc/rt_albedo.h, the definition; csrc/rt_albedo.hip, the kernels):
+ *        Lambertian: Texture::mapping(u, v, p) of its texture, the frames' own texture walk on the record (constant, checker, Perlin noise,
+ *        image); PBR: the same of its base-colour texture; a ConstantMedium hit (handle -1): the same of the medium's texture; Metal: its
+ *        albedo; Dielectric, DiffuseLight and a miss: (1, 1, 1) — radiance of emitters and of the background is not reflectance and stays
+ *        un-demodulated.  Specular chains are NOT followed to the first diffuse surface: the albedo is the first hit's.
+ * rt_query_albedo: albedo_out = n x 3 doubles; hits_out: NULL, or n x 16 — the very words rt_query_hits writes for these rays and this seed.
+ * rt_query_camera_albedo: albedo_sum_out = W*H*3 doubles in output order, per pixel the SUM over samples first_sample .. first_sample +
+ * n_samples - 1 of the albedo under that sample's camera ray (the ray of rt_query_camera(sample)), added in ascending order into
+ * accumulators that start at +0.0 — one pixel per lane, no atomics: the same call gives the same words, and the sum of single-sample calls
+ * restates it exactly.  Divide by n_samples for the mean.  n_samples >= 1 and first_sample + n_samples <= 2^32 - 1.
+ * Everything else — flags = 0, f64, errors, n = 0, the _device forms (DEVICE pointers: rays and hits 16-byte aligned, albedo 8-byte; they only
+ * enqueue on hip_stream and never wait or allocate), rt_last_query_ms — is as for the ray queries above. */
+int rt_query_albedo(rt_scene*, uint32_t n, const double* rays, double t_min, uint64_t seed, uint32_t flags, double* albedo_out, double* hits_out);
+int rt_query_albedo_device(rt_scene*, uint32_t n, const void* d_rays, double t_min, uint64_t seed, uint32_t flags,
+                           void* d_albedo_out, size_t d_albedo_bytes, void* d_hits_out, size_t d_hits_bytes, void* hip_stream);
+int rt_query_camera_albedo(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
+                           uint64_t seed, uint32_t flags, double* albedo_sum_out);
+int rt_query_camera_albedo_device(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
+                                  uint64_t seed, uint32_t flags, void* d_albedo_sum, size_t d_albedo_sum_bytes, void* hip_stream);
+/* What a material handle stands for (host only, no GPU): kind_texture_out[0] = the kind (0 Lambertian, 1 Metal, 2 Dielectric, 3 DiffuseLight,
+ * 4 Isotropic, 5 PBR), [1] = its texture handle (-1 for Metal and Dielectric); albedo_out = Metal's albedo (0 otherwise).  A bad handle is an error. */
+int rt_material_info(rt_scene*, int material, int32_t kind_texture_out[2], double albedo_out[3]);
+
 /* ---- radiance queries: the reference's `ray_color(r, background, world, lights, depth)` (src/main.rs:41-120) as a function of its own — the
  *      radiance along rays the caller chooses, samples_per_ray samples of each: another projection than camera.rs's (360-degree panorama,
  *      orthographic, fisheye, a measured lens), a light or irradiance probe at a point, a baked light map over a surface, "how bright is it
@@ -318,8 +344,8 @@ int rt_query_radiance_device(rt_scene*, uint32_t n, const void* d_rays, const do
  * and NaN are errors); flags: RT_DENOISE_SAME_MATERIAL or 0.  rgb_sum_out: W*H*3 doubles, the filtered frame in SUM units again (mean times
  * samples), so that rt_write_ppm, rt_format_color and the resolve apply to it unchanged; it may be rgb_sum itself.  W, H >= 1, W*H <= 2^31 - 1.
  * Non-finite input pixels are left out as neighbours and, as centres, take their neighbours' values: the filter repairs NaN pixels.
- * Not done: guides beyond sample 0's camera ray (no averaging over the lens or the pixel), albedo demodulation (textured surfaces rely on
- * sigma_c).  Errors (non-zero, a message for rt_last_error, nothing written): null arguments and everything outside the ranges above. */
+ * Not done: guides beyond sample 0's camera ray (no averaging over the lens or the pixel).  Textured surfaces: this filter sees a texture as
+ * colour and only sigma_c protects it — use the albedo-demodulated forms below (rt_denoise_albedo*).  Errors (non-zero, a message for rt_last_error, nothing written): null arguments and everything outside the ranges above. */
 enum { RT_DENOISE_SAME_MATERIAL = 1 /* pixels are neighbours only if their hits have the same material handle (default: only hit beside hit, miss beside miss) */ };
 /* The host twin: the specification as plain C++; needs no device. */
 int rt_denoise_host(const double* rgb_sum, uint64_t samples, const double* hits, uint32_t W, uint32_t H, uint32_t iterations,
@@ -343,6 +369,32 @@ int rt_denoise_device(const void* d_rgb_sum, uint64_t samples, const void* d_hit
  * be interleaved freely.  Waits for every pass enqueued so far.  Errors: the arguments of rt_denoise; a frame of 0 samples; a scene that is
  * gone, or has changed, while the frame holds no guide (with a guide the frame still resolves after its scene is destroyed). */
 int rt_progressive_resolve_denoised_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out);
+
+/* ---- albedo-demodulated denoising: the filter above applied to rgb_sum / albedo and multiplied back, so that a texture — checker, image,
+ *      Perlin noise — is not "colour" the filter has to preserve: it filters irradiance.  An exact specification again (csrc/rt_albedo.h:
+ *      only + - * / and comparisons, a fixed order).  Per pixel and channel, eps = 2^-8 (one output code value of format_color per unit of
+ *      irradiance):  a = albedo_sum / albedo_samples;  m = a finite ? a : 1;  d = m >= eps ? m : eps;  x = rgb_sum / d;
+ *      y = rt_denoise(x, ...);  out = y * m.  A black channel stays black whatever its neighbours hold; a non-finite albedo demodulates nothing.
+ * albedo_sum: W*H*3 doubles, as rt_query_camera_albedo returns them; albedo_samples >= 1: how many samples they hold.  The other arguments,
+ * the errors (plus albedo_samples = 0 and a null albedo) and the three forms are those of rt_denoise_host / rt_denoise / rt_denoise_device;
+ * RT_DENOISE_SAME_MATERIAL is the only flag.  The device form wraps two element-wise kernels (csrc/rt_albedo.hip) around the unchanged
+ * filter and needs rt_denoise_albedo_workspace_bytes(W, H) = 152 bytes per pixel; d_albedo_sum is 8-byte aligned and is only read. */
+int rt_denoise_albedo_host(const double* rgb_sum, uint64_t samples, const double* albedo_sum, uint64_t albedo_samples, const double* hits,
+                           uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3], uint32_t flags, double* rgb_sum_out);
+int rt_denoise_albedo(const double* rgb_sum, uint64_t samples, const double* albedo_sum, uint64_t albedo_samples, const double* hits,
+                      uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3], uint32_t flags, double* rgb_sum_out);
+size_t rt_denoise_albedo_workspace_bytes(uint32_t W, uint32_t H);
+int rt_denoise_albedo_device(const void* d_rgb_sum, uint64_t samples, const void* d_albedo_sum, uint64_t albedo_samples, const void* d_hits,
+                             uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3], uint32_t flags, void* d_rgb_sum_out,
+                             void* d_workspace, size_t workspace_bytes, void* hip_stream);
+/* rt_progressive_resolve_denoised_rgb8 with demodulation: byte for byte rt_format_color of rt_denoise_albedo_host(rt_progressive_read_sum,
+ * rt_progressive_samples, rt_query_camera_albedo(first_sample 0, albedo_samples, the frame's seed), albedo_samples, rt_query_camera(sample 0,
+ * the frame's seed)).  The frame builds its albedo sums itself (rt_query_camera_albedo_device on its device; rt_last_query_ms reports that
+ * launch then) and keeps them beside the guide until rt_progressive_reset or until another albedo_samples is asked for (48 more bytes per
+ * pixel).  The accumulated sums and what the other two resolves own are untouched; the three may be interleaved freely.
+ * rt_progressive_albedo_info: the albedo_samples the frame holds sums for (0: none) and how many times it has built them. */
+int rt_progressive_resolve_denoised_albedo_rgb8(void* frame, uint32_t albedo_samples, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out);
+int rt_progressive_albedo_info(void* frame, uint32_t* albedo_samples_out, uint64_t* builds_out);
 
 /* The whole frame on several GPUs of this node from ONE call: what a host that owns the node's GPUs itself (the reference's `main`,
  * src/main.rs:767-835) calls instead of rt_render.  device_mask: bit d selects HIP device d (0 = every visible device).  The scene
@@ -444,6 +496,10 @@ int rt_debug_section_cycles(rt_scene*, unsigned long long out8[8]);
  * launches: ms_out[0] = the pack kernel, ms_out[1 + i] = iteration i (iterations + 1 floats). */
 int rt_debug_denoise_ms(const void* d_rgb_sum, uint64_t samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
                         const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, float* ms_out);
+/* Measuring aid (tools/denoise_probe.py): the two element-wise kernels of rt_denoise_albedo_device on the null stream, synchronously, once to
+ * warm up and once with HIP events between them: ms_out[0] = demodulate (d_rgb_sum, d_albedo_sum -> d_x), ms_out[1] = remodulate (d_x in place).
+ * DEVICE pointers of n_doubles doubles (3 per pixel), 8-byte aligned. */
+int rt_debug_albedo_modulate_ms(const void* d_rgb_sum, const void* d_albedo_sum, uint64_t albedo_samples, void* d_x, uint64_t n_doubles, float ms_out[2]);
 /* Test aid (host only, no GPU): what rt_scene_calibrate does to the filter tree of a world that is ONE bare BVH — inner nodes leave it by
  * their estimated pass rate for the view instead of by box areas (rt_flatten.cpp tune_filter_tree; scheduling only: any conservative
  * hierarchy over the leaves gives the same samples) — without touching a device copy.  1: rebuilt, 0: not that kind of scene, -1: error. */

@@ -111,12 +111,24 @@ SIGNATURES = {
     "query_camera": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u64, _u32, _ptr, _ptr]),
     "query_camera_device": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u64, _u32, _ptr, _ptr, C.c_size_t, _ptr]),
     "last_query_ms": (_int, [_ptr, c_float_p]),
+    # albedo queries
+    "query_albedo": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _ptr, _ptr]),
+    "query_albedo_device": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _ptr, C.c_size_t, _ptr, C.c_size_t, _ptr]),
+    "query_camera_albedo": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u32, _u64, _u32, _ptr]),
+    "query_camera_albedo_device": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u32, _u64, _u32, _ptr, C.c_size_t, _ptr]),
+    "material_info": (_int, [_ptr, _int, C.POINTER(C.c_int32), c_double_p]),
     # denoising
     "denoise_host": (_int, [_ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr]),
     "denoise": (_int, [_ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr]),
     "denoise_workspace_bytes": (C.c_size_t, [_u32, _u32]),
     "denoise_device": (_int, [_ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, C.c_size_t, _ptr]),
     "progressive_resolve_denoised_rgb8": (_int, [_ptr, _u32, c_double_p, _u32, _ptr]),
+    "denoise_albedo_host": (_int, [_ptr, _u64, _ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr]),
+    "denoise_albedo": (_int, [_ptr, _u64, _ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr]),
+    "denoise_albedo_workspace_bytes": (C.c_size_t, [_u32, _u32]),
+    "denoise_albedo_device": (_int, [_ptr, _u64, _ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, C.c_size_t, _ptr]),
+    "progressive_resolve_denoised_albedo_rgb8": (_int, [_ptr, _u32, _u32, c_double_p, _u32, _ptr]),
+    "progressive_albedo_info": (_int, [_ptr, c_u32_p, c_u64_p]),
     # radiance queries
     "query_radiance": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _ptr, _ptr, c_u64_p]),
     "query_radiance_device": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _u32, _int, _ptr, C.c_size_t, _ptr, _ptr, _ptr]),
@@ -144,6 +156,7 @@ SIGNATURES = {
     "last_leaf_steps": (_int, [_ptr, c_ull_p]),
     # test and diagnostic hooks
     "debug_denoise_ms": (_int, [_ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, C.c_size_t, c_float_p]),
+    "debug_albedo_modulate_ms": (_int, [_ptr, _ptr, _u64, _ptr, _u64, c_float_p]),
     "debug_section_cycles": (_int, [_ptr, c_ull_p]),
     "debug_tune_filter": (_int, [_ptr, _ptr]),
     "debug_objects": (_int, [_ptr, _ptr, _u32, c_u32_p]),

@@ -20,6 +20,8 @@
 #include "rt_query.h"
 #include "rt_radiance.h"
 #include "rt_denoise.h"
+#define RT_ALBEDO_QUERIES
+#include "rt_albedo.h"
 
 using namespace rt;
 
@@ -48,6 +50,11 @@ struct Progressive {
     // 0's camera hits of this view, keyed for guide_flags — is built once and kept until rt_progressive_reset.
     void* d_dn_ws = nullptr; void* d_dn_sum = nullptr; void* d_dn_rgb8 = nullptr; void* d_dn_changed = nullptr;
     bool guide_valid = false; uint32_t guide_flags = 0;
+    // rt_progressive_resolve_denoised_albedo_rgb8's own, beside the above: the albedo sums of samples [0, albedo_samples) of this view under
+    // the frame's seed (rt_query_camera_albedo_device), built when first asked for and kept until rt_progressive_reset or another
+    // albedo_samples, and the demodulated frame of a run (24 + 24 bytes per pixel).  albedo_builds counts the launches that built d_alb_sum.
+    void* d_alb_sum = nullptr; void* d_alb_x = nullptr;
+    uint32_t albedo_samples = 0; uint64_t albedo_builds = 0;
     size_t n_px() const { return (size_t)W * H; }
 };
 
@@ -1320,8 +1327,13 @@ static int query_events(Scene& s, int device) {
 }
 // One query launch on the calling thread's current device, enqueued on `stream`: the scene's f64 tables bound into zeroed launch
 // parameters, as a known-answer launch does it, plus what the walks need — bvh_tame, and the LDS node cache: the filter tree, staged by
-// every workgroup when all of it fits the share of the CU's LDS that keeps the workgroups the registers allow resident.
-static int query_launch(Scene& s, const rt_camera* camp, uint32_t W, uint32_t H, QueryArgs Q, hipStream_t stream) {
+// every workgroup when all of it fits the share of the CU's LDS that keeps the workgroups the registers allow resident.  The kernel family
+// (ray queries, albedo queries) comes as its two seams: occupancy(scene feats, camera mode, LDS bytes) and launch(P, scene feats, camera
+// mode, workgroups, LDS bytes, stream); n lanes' worth of work.
+extern "C++" {
+template <typename Occ, typename Launch>
+static int query_launch_as(Scene& s, const rt_camera* camp, uint32_t W, uint32_t H, uint64_t seed, uint32_t n, const char* kernel,
+                           Occ&& occupancy, Launch&& launch, hipStream_t stream) {
     Scene::DeviceCtx* cp = nullptr;
     if (current_ctx(s, &cp)) return -1;
     Scene::DeviceCtx& c = *cp;
@@ -1336,20 +1348,26 @@ static int query_launch(Scene& s, const rt_camera* camp, uint32_t W, uint32_t H,
     if (camera) {
         rt_camera_args ca; std::memcpy(&ca, camp, sizeof(ca));
         camera_new(ca, P.cam);
-        P.W = W; P.H = H; P.spp = 1u; P.seed = Q.seed;
+        P.W = W; P.H = H; P.spp = 1u; P.seed = seed;
     }
     hipDeviceProp_t prop; HIP_OK(hipGetDeviceProperties(&prop, c.device));
     int bpc = 0; size_t shmem = 0;
-    if (query_node_cache(f, prop, [&](size_t lds) { return query_blocks_per_cu(f.feats, camera, lds); }, "ray-query", P, shmem, bpc)) return -1;
+    if (query_node_cache(f, prop, [&](size_t lds) { return occupancy(f.feats, camera, lds); }, kernel, P, shmem, bpc)) return -1;
     uint64_t n_blocks = (uint64_t)prop.multiProcessorCount * (uint64_t)bpc;
-    const uint64_t blocks_needed = ((uint64_t)Q.n + QUERY_THREADS - 1u) / QUERY_THREADS;
+    const uint64_t blocks_needed = ((uint64_t)n + QUERY_THREADS - 1u) / QUERY_THREADS;
     if (n_blocks > blocks_needed) n_blocks = blocks_needed;
     if (query_events(s, c.device)) return -1;
     HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[0], stream));
-    HIP_OK(launch_query(P, Q, f.feats, camera, (uint32_t)n_blocks, shmem, stream));
+    HIP_OK(launch(P, f.feats, camera, (uint32_t)n_blocks, shmem, stream));
     HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[1], stream));
     s.q_recorded = true;
     return 0;
+}
+}
+static int query_launch(Scene& s, const rt_camera* camp, uint32_t W, uint32_t H, QueryArgs Q, hipStream_t stream) {
+    return query_launch_as(s, camp, W, H, Q.seed, Q.n, "ray-query", query_blocks_per_cu,
+                           [&](const KParams<double>& P, uint32_t feats, bool camera, uint32_t n_blocks, size_t shmem, hipStream_t st) {
+                               return launch_query(P, Q, feats, camera, n_blocks, shmem, st); }, stream);
 }
 
 int rt_query_hits_device(rt_scene* sc, uint32_t n, const void* d_rays, double t_min, uint64_t seed, uint32_t flags,
@@ -1412,6 +1430,81 @@ int rt_last_query_ms(rt_scene* sc, float* ms_out) {
     DeviceGuard guard(sc->s.q_device);
     HIP_OK(hipEventSynchronize((hipEvent_t)sc->s.q_ev[1]));
     HIP_OK(hipEventElapsedTime(ms_out, (hipEvent_t)sc->s.q_ev[0], (hipEvent_t)sc->s.q_ev[1]));
+    return 0;
+}
+
+// ---------------------------------------------------------------- albedo queries (csrc/rt_albedo.h: the definition; rt_albedo.hip: the kernels)
+int rt_material_info(rt_scene* sc, int material, int32_t kind_texture_out[2], double albedo_out[3]) {
+    if (!sc || !kind_texture_out || !albedo_out) return set_err("null argument");
+    if (!mat_ok(sc, material)) return set_err("rt_material_info: bad material handle");
+    const DMaterial<double>& m = sc->s.materials[(size_t)material];
+    const uint32_t kind = m.kind & MAT_KIND_MASK;
+    const bool textured = kind != M_METAL && kind != M_DIELECTRIC;
+    kind_texture_out[0] = (int32_t)kind; kind_texture_out[1] = textured ? (int32_t)m.tex : -1;
+    for (int k = 0; k < 3; k++) albedo_out[k] = kind == M_METAL ? m.albedo[k] : 0.0;
+    return 0;
+}
+// One albedo launch: query_launch with the albedo kernels in the query kernels' place
+static int albedo_launch(Scene& s, const rt_camera* camp, uint32_t W, uint32_t H, AlbedoArgs A, hipStream_t stream) {
+    return query_launch_as(s, camp, W, H, A.seed, A.n, "albedo-query", albedo_blocks_per_cu,
+                           [&](const KParams<double>& P, uint32_t feats, bool camera, uint32_t n_blocks, size_t shmem, hipStream_t st) {
+                               return launch_albedo(P, A, feats, camera, n_blocks, shmem, st); }, stream);
+}
+int rt_query_albedo_device(rt_scene* sc, uint32_t n, const void* d_rays, double t_min, uint64_t seed, uint32_t flags,
+                           void* d_albedo_out, size_t d_albedo_bytes, void* d_hits_out, size_t d_hits_bytes, void* hip_stream) {
+    if (!sc || !d_rays || !d_albedo_out) return set_err("null argument");
+    if (query_flags(flags)) return -1;
+    if (n == 0) return 0;
+    if (d_albedo_bytes < (size_t)n * 3u * sizeof(double)) return set_err("albedo buffer too small for n * 3 doubles (24 bytes per ray)");
+    if (d_hits_out && d_hits_bytes < (size_t)n * QUERY_HIT_DOUBLES * sizeof(double)) return set_err("hit buffer too small for n * 16 doubles (128 bytes per ray)");
+    if (query_aligned(d_rays, "d_rays") || (d_hits_out && query_aligned(d_hits_out, "d_hits_out"))) return -1;
+    if (((uintptr_t)d_albedo_out & 7u) != 0u) return set_err("d_albedo_out must be 8-byte aligned");
+    if (need_device_and_flat(sc->s)) return -1;
+    AlbedoArgs A; A.rays = (const double*)d_rays; A.albedo = (double*)d_albedo_out; A.hits = (double*)d_hits_out; A.n = n; A.first_sample = 0u; A.n_samples = 1u;
+    A.t_min = t_min; A.seed = seed;
+    return albedo_launch(sc->s, nullptr, 0u, 0u, A, (hipStream_t)hip_stream);
+}
+int rt_query_albedo(rt_scene* sc, uint32_t n, const double* rays, double t_min, uint64_t seed, uint32_t flags, double* albedo_out, double* hits_out) {
+    if (!sc || !rays || !albedo_out) return set_err("null argument");
+    if (query_flags(flags)) return -1;
+    if (n == 0) return 0;
+    if (need_device_and_flat(sc->s)) return -1;
+    const size_t ray_bytes = (size_t)n * QUERY_RAY_DOUBLES * sizeof(double), alb_bytes = (size_t)n * 3u * sizeof(double), hit_bytes = (size_t)n * QUERY_HIT_DOUBLES * sizeof(double);
+    DeviceBuffer d_rays, d_alb, d_hits;
+    HIP_OK(d_rays.alloc(ray_bytes)); HIP_OK(d_alb.alloc(alb_bytes));
+    if (hits_out) HIP_OK(d_hits.alloc(hit_bytes));
+    HIP_OK(hipMemcpy(d_rays.get(), rays, ray_bytes, hipMemcpyHostToDevice));
+    if (rt_query_albedo_device(sc, n, d_rays.get(), t_min, seed, flags, d_alb.get(), alb_bytes, d_hits.get(), hit_bytes, nullptr)) return -1;
+    HIP_OK(hipMemcpy(albedo_out, d_alb.get(), alb_bytes, hipMemcpyDeviceToHost));       // (waits for the kernel: the null stream)
+    if (hits_out) HIP_OK(hipMemcpy(hits_out, d_hits.get(), hit_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+static int query_camera_albedo_args(rt_scene* sc, const rt_camera* cam, const void* out, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples, uint32_t flags) {
+    if (query_camera_args(sc, cam, out, W, H, flags)) return -1;
+    if (n_samples == 0u) return set_err("n_samples must be >= 1");
+    if ((uint64_t)first_sample + n_samples > 0xFFFFFFFFull) return set_err("first_sample + n_samples must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
+    return 0;
+}
+int rt_query_camera_albedo_device(rt_scene* sc, const rt_camera* cam, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
+                                  uint64_t seed, uint32_t flags, void* d_albedo_sum, size_t d_albedo_sum_bytes, void* hip_stream) {
+    if (query_camera_albedo_args(sc, cam, d_albedo_sum, W, H, first_sample, n_samples, flags)) return -1;
+    const uint32_t n = W * H;
+    if (d_albedo_sum_bytes < (size_t)n * 3u * sizeof(double)) return set_err("albedo buffer too small for W * H * 3 doubles (24 bytes per pixel)");
+    if (((uintptr_t)d_albedo_sum & 7u) != 0u) return set_err("d_albedo_sum must be 8-byte aligned");
+    if (need_device_and_flat(sc->s)) return -1;
+    AlbedoArgs A; A.rays = nullptr; A.albedo = (double*)d_albedo_sum; A.hits = nullptr; A.n = n; A.first_sample = first_sample; A.n_samples = n_samples;
+    A.t_min = 0.00001; A.seed = seed;
+    return albedo_launch(sc->s, cam, W, H, A, (hipStream_t)hip_stream);
+}
+int rt_query_camera_albedo(rt_scene* sc, const rt_camera* cam, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
+                           uint64_t seed, uint32_t flags, double* albedo_sum_out) {
+    if (query_camera_albedo_args(sc, cam, albedo_sum_out, W, H, first_sample, n_samples, flags)) return -1;
+    if (need_device_and_flat(sc->s)) return -1;
+    const size_t alb_bytes = (size_t)W * H * 3u * sizeof(double);
+    DeviceBuffer d_alb;
+    HIP_OK(d_alb.alloc(alb_bytes));
+    if (rt_query_camera_albedo_device(sc, cam, W, H, first_sample, n_samples, seed, flags, d_alb.get(), alb_bytes, nullptr)) return -1;
+    HIP_OK(hipMemcpy(albedo_sum_out, d_alb.get(), alb_bytes, hipMemcpyDeviceToHost));   // (waits for the kernel: the null stream)
     return 0;
 }
 
@@ -1504,6 +1597,7 @@ static void progressive_free(Progressive* p) {
     (void)hipDeviceSynchronize();                   // passes and resolves may still be in flight on the caller's streams
     free_dev(p->d_sum); free_dev(p->d_rgb8[0]); free_dev(p->d_rgb8[1]); free_dev(p->d_changed);
     free_dev(p->d_dn_ws); free_dev(p->d_dn_sum); free_dev(p->d_dn_rgb8); free_dev(p->d_dn_changed);
+    free_dev(p->d_alb_sum); free_dev(p->d_alb_x);
 }
 void* rt_progressive_create(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t max_depth,
                             uint64_t seed, uint32_t flags) {
@@ -1642,6 +1736,7 @@ int rt_progressive_reset(void* frame) {
     if (!p) return set_err("null argument");
     if (p->sc) p->scene_version = p->sc->s.version;     // a new frame, of the scene as it is now
     p->guide_valid = false;                             // ... and so is its denoising guide, rebuilt when it is next needed
+    p->albedo_samples = 0;                              // ... and its albedo sums
     return progressive_restart(p, nullptr, 0);
 }
 
@@ -1715,14 +1810,12 @@ int rt_debug_denoise_ms(const void* d_rgb_sum, uint64_t samples, const void* d_h
     for (uint32_t k = 0; k < n_marks; k++) if (marks[k]) (void)hipEventDestroy(marks[k]);
     return rc;
 }
-// The frame's sums filtered and resolved, into buffers of the frame's own: d_sum, the plain resolve's two images and its count stay as they are.
-int rt_progressive_resolve_denoised_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !sigma || !rgb8_out) return set_err("null argument");
+// What both denoised resolves do before they filter: the checks, the frame's own buffers, and the packed guide — sample 0's camera hits of
+// this view, keyed for `flags` — in its place in the workspace.
+static int progressive_denoise_prepare(Progressive* p, uint32_t iterations, const double sigma[3], uint32_t flags) {
     const std::string problem = denoise_check(p->done ? p->done : 1u, p->W, p->H, iterations, sigma, flags);
     if (!problem.empty()) return set_err(problem);
     if (p->done == 0) return set_err("nothing to resolve: the frame holds 0 samples (format_color divides by the sample count, src/vec.rs:126)");
-    DeviceGuard guard(p->device);
     HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the image
     const size_t n = p->n_px();
     if (!p->guide_valid || p->guide_flags != flags) {
@@ -1743,10 +1836,115 @@ int rt_progressive_resolve_denoised_rgb8(void* frame, uint32_t iterations, const
         HIP_OK(hipStreamSynchronize(nullptr));
         p->guide_valid = true; p->guide_flags = flags;
     }
-    if (denoise_enqueue((const double*)p->d_sum, p->done, nullptr, p->W, p->H, iterations, sigma, flags, (double*)p->d_dn_sum, p->d_dn_ws, nullptr)) return -1;
+    return 0;
+}
+// ... and after: the filtered sums in d_dn_sum resolved and copied out
+static int progressive_denoise_finish(Progressive* p, uint8_t* rgb8_out) {
+    const size_t n = p->n_px();
     HIP_OK(hipMemsetAsync(p->d_dn_changed, 0, sizeof(unsigned long long), nullptr));
     HIP_OK(launch_resolve_rgb8((const double*)p->d_dn_sum, p->done, nullptr, (uint8_t*)p->d_dn_rgb8, (unsigned long long*)p->d_dn_changed, (uint32_t)n, nullptr));
     HIP_OK(hipMemcpy(rgb8_out, p->d_dn_rgb8, n * 3, hipMemcpyDeviceToHost));             // (waits for the kernels: the null stream)
+    return 0;
+}
+// The frame's sums filtered and resolved, into buffers of the frame's own: d_sum, the plain resolve's two images and its count stay as they are.
+int rt_progressive_resolve_denoised_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !sigma || !rgb8_out) return set_err("null argument");
+    DeviceGuard guard(p->device);
+    if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
+    if (denoise_enqueue((const double*)p->d_sum, p->done, nullptr, p->W, p->H, iterations, sigma, flags, (double*)p->d_dn_sum, p->d_dn_ws, nullptr)) return -1;
+    return progressive_denoise_finish(p, rgb8_out);
+}
+
+// ---------------------------------------------------------------- albedo-demodulated denoising (csrc/rt_albedo.h (2))
+size_t rt_denoise_albedo_workspace_bytes(uint32_t W, uint32_t H) { return (size_t)W * H * DENOISE_ALBEDO_WORKSPACE_BYTES_PER_PX; }
+
+// The launches of one run on `stream`: demodulate into d_x, the filter's own launches from d_x to d_out, remodulate d_out in place.
+// d_out may be d_sum: the demodulate kernel has read it by the time anything is written there (stream order).
+static int denoise_albedo_enqueue(const double* d_sum, uint64_t samples, const double* d_albedo_sum, uint64_t albedo_samples, const double* d_hits,
+                                  uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3], uint32_t flags, double* d_out,
+                                  void* d_workspace, double* d_x, hipStream_t stream) {
+    const uint64_t n = (uint64_t)W * H * 3u;
+    HIP_OK((hipError_t)launch_albedo_demodulate(d_sum, d_albedo_sum, albedo_samples, d_x, n, stream));
+    if (denoise_enqueue(d_x, samples, d_hits, W, H, iterations, sigma, flags, d_out, d_workspace, stream)) return -1;
+    HIP_OK((hipError_t)launch_albedo_remodulate(d_out, d_albedo_sum, albedo_samples, n, stream));
+    return 0;
+}
+int rt_denoise_albedo_device(const void* d_rgb_sum, uint64_t samples, const void* d_albedo_sum, uint64_t albedo_samples, const void* d_hits,
+                             uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3], uint32_t flags, void* d_rgb_sum_out,
+                             void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!d_rgb_sum || !d_albedo_sum || !d_hits || !sigma || !d_rgb_sum_out || !d_workspace) return set_err("null argument");
+    const std::string problem = denoise_albedo_check(samples, albedo_samples, W, H, iterations, sigma, flags);
+    if (!problem.empty()) return set_err(problem);
+    if (workspace_bytes < rt_denoise_albedo_workspace_bytes(W, H)) return set_err("denoise: workspace too small: rt_denoise_albedo_workspace_bytes(W, H) = 152 bytes per pixel are needed");
+    if (query_aligned(d_hits, "d_hits") || query_aligned(d_workspace, "d_workspace")) return -1;
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_rgb_sum_out | (uintptr_t)d_albedo_sum) & 7u) != 0u) return set_err("d_rgb_sum, d_albedo_sum and d_rgb_sum_out must be 8-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    double* d_x = (double*)((unsigned char*)d_workspace + rt_denoise_workspace_bytes(W, H));
+    return denoise_albedo_enqueue((const double*)d_rgb_sum, samples, (const double*)d_albedo_sum, albedo_samples, (const double*)d_hits, W, H, iterations,
+                                  sigma, flags, (double*)d_rgb_sum_out, d_workspace, d_x, (hipStream_t)hip_stream);
+}
+int rt_denoise_albedo(const double* rgb_sum, uint64_t samples, const double* albedo_sum, uint64_t albedo_samples, const double* hits,
+                      uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3], uint32_t flags, double* rgb_sum_out) {
+    if (!rgb_sum || !albedo_sum || !hits || !sigma || !rgb_sum_out) return set_err("null argument");
+    const std::string problem = denoise_albedo_check(samples, albedo_samples, W, H, iterations, sigma, flags);
+    if (!problem.empty()) return set_err(problem);
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
+    const size_t ws_bytes = rt_denoise_albedo_workspace_bytes(W, H);
+    DeviceBuffer d_sum, d_alb, d_hits, d_ws;
+    HIP_OK(d_sum.alloc(sum_bytes)); HIP_OK(d_alb.alloc(sum_bytes)); HIP_OK(d_hits.alloc(hit_bytes)); HIP_OK(d_ws.alloc(ws_bytes));
+    HIP_OK(hipMemcpy(d_sum.get(), rgb_sum, sum_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_alb.get(), albedo_sum, sum_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_hits.get(), hits, hit_bytes, hipMemcpyHostToDevice));
+    if (rt_denoise_albedo_device(d_sum.get(), samples, d_alb.get(), albedo_samples, d_hits.get(), W, H, iterations, sigma, flags, d_sum.get(), d_ws.get(), ws_bytes, nullptr)) return -1;
+    HIP_OK(hipMemcpy(rgb_sum_out, d_sum.get(), sum_bytes, hipMemcpyDeviceToHost));       // (waits for the kernels: the null stream)
+    return 0;
+}
+// The frame's sums demodulated by its own albedo frame, filtered, remodulated and resolved; everything the other resolves own stays as it is.
+int rt_progressive_resolve_denoised_albedo_rgb8(void* frame, uint32_t albedo_samples, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !sigma || !rgb8_out) return set_err("null argument");
+    if (albedo_samples == 0u) return set_err("denoise: albedo_samples must be >= 1 (the frame is demodulated by albedo_sum / albedo_samples)");
+    DeviceGuard guard(p->device);
+    if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
+    const size_t n = p->n_px(), sum_bytes = n * 3 * sizeof(double);
+    if (p->albedo_samples != albedo_samples) {
+        if (!p->sc) return set_err("the scene of this progressive frame has been destroyed and the frame holds no albedo sums for this albedo_samples: they are built from the scene (rt_query_camera_albedo_device)");
+        if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
+    }
+    if (!p->d_alb_sum) HIP_OK(hipMalloc(&p->d_alb_sum, sum_bytes));
+    if (!p->d_alb_x) HIP_OK(hipMalloc(&p->d_alb_x, sum_bytes));
+    if (p->albedo_samples != albedo_samples) {
+        p->albedo_samples = 0;
+        if (rt_query_camera_albedo_device(p->sc, &p->cam, p->W, p->H, 0u, albedo_samples, p->seed, 0u, p->d_alb_sum, sum_bytes, nullptr)) return -1;
+        p->albedo_samples = albedo_samples; p->albedo_builds++;
+    }
+    if (denoise_albedo_enqueue((const double*)p->d_sum, p->done, (const double*)p->d_alb_sum, albedo_samples, nullptr, p->W, p->H, iterations, sigma, flags,
+                               (double*)p->d_dn_sum, p->d_dn_ws, (double*)p->d_alb_x, nullptr)) return -1;
+    return progressive_denoise_finish(p, rgb8_out);
+}
+int rt_debug_albedo_modulate_ms(const void* d_rgb_sum, const void* d_albedo_sum, uint64_t albedo_samples, void* d_x, uint64_t n_doubles, float ms_out[2]) {
+    if (!d_rgb_sum || !d_albedo_sum || !d_x || !ms_out) return set_err("null argument");
+    if (albedo_samples == 0u || n_doubles == 0u || n_doubles > 3ull * 0x7FFFFFFFull) return set_err("albedo_samples and n_doubles must be >= 1 (n_doubles <= 3 (2^31 - 1))");
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_albedo_sum | (uintptr_t)d_x) & 7u) != 0u) return set_err("the buffers must be 8-byte aligned");
+    hipEvent_t marks[3] = {};
+    int rc = 0;
+    for (int k = 0; k < 3 && rc == 0; k++) if (hipEventCreate(&marks[k]) != hipSuccess) rc = set_err("hipEventCreate failed");
+    for (int pass = 0; pass < 2 && rc == 0; pass++) {             // a warm run, then the one that is timed
+        if (hipEventRecord(marks[0], nullptr) != hipSuccess || launch_albedo_demodulate((const double*)d_rgb_sum, (const double*)d_albedo_sum, albedo_samples, (double*)d_x, n_doubles, nullptr) != 0 ||
+            hipEventRecord(marks[1], nullptr) != hipSuccess || launch_albedo_remodulate((double*)d_x, (const double*)d_albedo_sum, albedo_samples, n_doubles, nullptr) != 0 ||
+            hipEventRecord(marks[2], nullptr) != hipSuccess) rc = set_err("rt_debug_albedo_modulate_ms: a launch failed");
+    }
+    if (rc == 0 && hipEventSynchronize(marks[2]) != hipSuccess) rc = set_err("hipEventSynchronize failed");
+    for (int k = 0; k < 2 && rc == 0; k++) if (hipEventElapsedTime(&ms_out[k], marks[k], marks[k + 1]) != hipSuccess) rc = set_err("hipEventElapsedTime failed");
+    for (int k = 0; k < 3; k++) if (marks[k]) (void)hipEventDestroy(marks[k]);
+    return rc;
+}
+int rt_progressive_albedo_info(void* frame, uint32_t* albedo_samples_out, uint64_t* builds_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !albedo_samples_out || !builds_out) return set_err("null argument");
+    *albedo_samples_out = p->albedo_samples; *builds_out = p->albedo_builds;
     return 0;
 }
 

@@ -4,11 +4,13 @@
 // (same constructor names and argument order).  Usage mirrors `cargo run --release > image.ppm` (README.md:4):
 //
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
-//              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material FILE] [--panorama FILE]
-//              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] > image.ppm
+//              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material|albedo FILE] [--panorama FILE]
+//              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] [--denoise-albedo N] > image.ppm
 //
 // --denoise K[,c,n,p] (opt-in): the frame through the edge-avoiding a-trous filter before it is written (rt_denoise: K iterations, guided by
 // sample 0's camera hits of this --seed); with --progressive the frame resolves itself denoised on the device (rt_progressive_resolve_denoised_rgb8).
+// --denoise-albedo N (with --denoise): the filter runs on the frame divided by its first-hit albedo — the mean over samples [0, N) of this --seed,
+// rt_query_camera_albedo — and the result is multiplied back (rt_denoise_albedo*): what a textured scene needs.
 //
 // --progressive N (opt-in, one GPU): the frame in passes of N samples per pixel (rt_progressive_*), the reference's style of progress on
 // stderr (main.rs:772-775), and the same PPM bytes at the end, built from the image the device resolved.
@@ -228,15 +230,25 @@ static bool read_image(const std::string& path, std::vector<uint8_t>& data, uint
 }
 
 static const char* AOV_HELP =
-    "  --aov normal|depth|material FILE   write a feature frame instead of the image: the closest hit of the camera ray of sample 0 of\n"
+    "  --aov normal|depth|material|albedo FILE   write a feature frame instead of the image: the closest hit of the camera ray of sample 0 of\n"
     "                                     every pixel (the ray the frame with this --seed traces), as a P3 PPM in FILE (- = stdout):\n"
     "      normal    r g b = 0.5 * (n + 1) * 255.999 truncated, per component of the hit's normal (a miss has the zero normal: 127 127 127)\n"
     "      depth     grey, linear in the hit's t between the frame's smallest finite t (255) and its largest (0): (max - t) / (max - min) *\n"
     "                255.999 truncated; a miss is 0\n"
-    "      material  grey, the hit's material handle mod 256 (a miss or a ConstantMedium hit, handle -1: 255)\n";
+    "      material  grey, the hit's material handle mod 256 (a miss or a ConstantMedium hit, handle -1: 255)\n"
+    "      albedo    r g b = the first hit's albedo held to [0, 1], times 255.999, truncated (no gamma); the mean over the samples [0, N) of\n"
+    "                --denoise-albedo N when that is given, else sample 0's (a miss, glass and emitters: 255 255 255)\n";
 
 // One channel value of the mappings above (a NaN gives 0)
 static unsigned aov_level(double x) { return x >= 0.0 ? (x > 255.0 ? 255u : (unsigned)x) : 0u; }
+static void write_albedo_aov(const std::string& path, const std::vector<double>& albedo_sum, uint32_t n_samples, uint32_t W, uint32_t H) {
+    std::vector<uint8_t> img(albedo_sum.size());
+    for (size_t i = 0; i < albedo_sum.size(); i++) {
+        const double a = albedo_sum[i] / (double)n_samples;
+        img[i] = (uint8_t)aov_level((a >= 0.0 ? (a > 1.0 ? 1.0 : a) : 0.0) * 255.999);
+    }
+    write_ppm_rgb8(path.c_str(), img, W, H);
+}
 static void write_aov(const std::string& kind, const std::string& path, const std::vector<Hit>& hits, uint32_t W, uint32_t H) {
     double lo = 0.0, hi = 0.0; bool have = false;
     for (const Hit& h : hits) if (h.hit && h.t - h.t == 0.0) { lo = have ? std::min(lo, h.t) : h.t; hi = have ? std::max(hi, h.t) : h.t; have = true; }
@@ -264,6 +276,7 @@ int main(int argc, char** argv) {
     std::string aov_kind, aov_path;                                         // --aov KIND FILE: a feature frame instead of the image
     std::string panorama_path;                                              // --panorama FILE: the equirectangular image around lookfrom instead
     bool want_denoise = false; DenoiseSettings dn;                          // --denoise K[,sigma_c,sigma_n,sigma_p]: filter the frame before it is written
+    uint32_t albedo_samples = 0;                                            // --denoise-albedo N: demodulate by the albedo of samples [0, N) (0: the plain filter)
     uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
     int gpus = 1;                                                           // --gpus N: the first N devices (0 = all) through rt_render_multi
     std::string obj_path = "teapot.obj", earth_path = "earthmap.jpg";       // the reference's asset names (main.rs:248,491)
@@ -290,7 +303,7 @@ int main(int argc, char** argv) {
         else if (a == "--progressive") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--progressive needs a pass size >= 1\n"); return 2; } progressive = (uint32_t)n; }
         else if (a == "--aov") {
             aov_kind = next(); aov_path = next();
-            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material") { std::fprintf(stderr, "--aov needs normal, depth or material\n%s", AOV_HELP); return 2; }
+            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material" && aov_kind != "albedo") { std::fprintf(stderr, "--aov needs normal, depth, material or albedo\n%s", AOV_HELP); return 2; }
         }
         else if (a == "--panorama") panorama_path = next();
         else if (a == "--denoise") {
@@ -300,11 +313,14 @@ int main(int argc, char** argv) {
             if (got != 1 && got != 4) { std::fprintf(stderr, "--denoise needs K or K,SIGMA_C,SIGMA_N,SIGMA_P\n"); return 2; }
             want_denoise = true; dn.iterations = k; dn.sigma[0] = c; dn.sigma[1] = n; dn.sigma[2] = p;
         }
+        else if (a == "--denoise-albedo") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--denoise-albedo needs a sample count >= 1\n"); return 2; } albedo_samples = (uint32_t)n; }
         else if (a == "--help" || a == "-h") {
             std::printf("rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N]\n"
                         "         [--depth D] [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] > image.ppm\n%s"
                         "  --denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]  write the frame through K (1 .. 8) iterations of the edge-avoiding a-trous filter, guided by\n"
                         "                                     the camera hits of sample 0 (default sigmas 4, 0.5, 0.02; inf switches a stop off); also with --progressive\n"
+                        "  --denoise-albedo N                 with --denoise: filter the frame divided by its first-hit albedo (the mean over samples 0 .. N-1)\n"
+                        "                                     and multiply back: textures are kept (textured scenes need it); also with --progressive\n"
                         "  --panorama FILE                    write the 2:1 equirectangular image (width x width/2) of everything around the scene's\n"
                         "                                     lookfrom instead of the image: --spp samples per ray, --depth, the scene's background\n", AOV_HELP);
             return 0;
@@ -313,6 +329,7 @@ int main(int argc, char** argv) {
         else if (a == "--fast-bvh") { fast_bvh = true; flags |= RT_NEAR_FIRST_BVH; }      // opt-in, not the reference's tree / visiting order
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
+    if (albedo_samples != 0u && !want_denoise && aov_kind != "albedo") { std::fprintf(stderr, "--denoise-albedo goes with --denoise K (or --aov albedo)\n"); return 2; }
     const double aspect_ratio = (double)image_width / (double)image_height;
     try {
         Scene s;
@@ -379,6 +396,10 @@ int main(int argc, char** argv) {
         }
         if (!aov_kind.empty()) {
             if (flags & RT_F32) throw Error("--aov runs in f64");
+            if (aov_kind == "albedo") {
+                const uint32_t n = albedo_samples ? albedo_samples : 1u;
+                write_albedo_aov(aov_path, query_camera_albedo(s, camera, image_width, image_height, 0u, n, seed), n, image_width, image_height);
+            } else
             write_aov(aov_kind, aov_path, query_camera(s, camera, image_width, image_height, 0u, seed), image_width, image_height);
             std::fprintf(stderr, "Done.\n");
             return 0;
@@ -402,7 +423,7 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "\rSamples: %llu / %u", (unsigned long long)frame.samples(), samples_per_pixel);    // main.rs:772-775
             }
             std::fprintf(stderr, "\n");
-            write_ppm_rgb8("-", want_denoise ? frame.rgb8_denoised(dn) : frame.rgb8(), image_width, image_height);     // main.rs:767-769,832
+            write_ppm_rgb8("-", want_denoise ? (albedo_samples ? frame.rgb8_denoised_albedo(albedo_samples, dn) : frame.rgb8_denoised(dn)) : frame.rgb8(), image_width, image_height);     // main.rs:767-769,832
             std::fprintf(stderr, "Done.\n");                                                    // main.rs:835
             return 0;
         }
@@ -416,7 +437,10 @@ int main(int argc, char** argv) {
             double ms[4]; rt_last_multi_ms(s.raw(), ms);
             std::fprintf(stderr, "rt_render_multi: slowest kernel %.2f ms, gather %.3f ms, un-permute %.3f ms, call %.2f ms\n", ms[0], ms[1], ms[2], ms[3]);
         }
-        if (want_denoise) pixel_sums = denoise(pixel_sums, samples_per_pixel, query_camera_records(s, camera, image_width, image_height, 0u, seed), image_width, image_height, dn);
+        if (want_denoise && albedo_samples)
+            pixel_sums = denoise_albedo(pixel_sums, samples_per_pixel, query_camera_albedo(s, camera, image_width, image_height, 0u, albedo_samples, seed), albedo_samples,
+                                        query_camera_records(s, camera, image_width, image_height, 0u, seed), image_width, image_height, dn);
+        else if (want_denoise) pixel_sums = denoise(pixel_sums, samples_per_pixel, query_camera_records(s, camera, image_width, image_height, 0u, seed), image_width, image_height, dn);
         write_ppm("-", pixel_sums, image_width, image_height, samples_per_pixel);              // main.rs:767-769,832
         std::fprintf(stderr, "Done.\n");                                                      // main.rs:835
     } catch (const Error& e) {

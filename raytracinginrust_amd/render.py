@@ -355,6 +355,21 @@ class Progressive:
         _check(self._lib.rt_progressive_resolve_denoised_rgb8(self._h, k, sg, flags, out.ctypes.data))
         return out
 
+    def rgb8_denoised_albedo(self, albedo_samples: int = 16, iterations: int = None, sigma=None, flags: int = 0) -> np.ndarray:
+        """rt_progressive_resolve_denoised_albedo_rgb8: `rgb8_denoised` on the frame divided by its first-hit albedo and multiplied back
+        (`denoise_albedo`), so that textures are not smoothed -> (H, W, 3) uint8.  The frame builds the albedo sums of samples
+        [0, albedo_samples) itself at the first call and keeps them until reset or another albedo_samples."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        k, sg = _denoise_settings(iterations, sigma)
+        _check(self._lib.rt_progressive_resolve_denoised_albedo_rgb8(self._h, int(albedo_samples), k, sg, flags, out.ctypes.data))
+        return out
+
+    def albedo_info(self):
+        """(the albedo_samples the frame holds albedo sums for — 0: none —, how many times it has built them)."""
+        n, builds = C.c_uint32(), C.c_uint64()
+        _check(self._lib.rt_progressive_albedo_info(self._h, C.byref(n), C.byref(builds)))
+        return int(n.value), int(builds.value)
+
     def sum(self) -> np.ndarray:
         """The accumulated per-pixel sums, (H, W, 3) f64 as `render` returns them; with `samples`, a checkpoint."""
         out = np.zeros((self.H, self.W, 3), dtype=np.float64)
@@ -597,6 +612,71 @@ def equirect_rays(origin, W: int, H: int, time: float = 0.0) -> np.ndarray:
     return rays.reshape(H * W, RAY_DOUBLES)
 
 
+# ---- albedo queries (rt_query_albedo*, rt_query_camera_albedo*): the reflectance at the closest hit, csrc/rt_albedo.h
+MATERIAL_KINDS = ("lambertian", "metal", "dielectric", "diffuse_light", "isotropic", "pbr")
+
+
+def query_albedo(b: SceneBuilder, rays, t_min: float = 1e-5, seed: int = 0, want_hits: bool = False):
+    """rt_query_albedo: the albedo at the closest hit of n rays, (n, 7) f64 -> (n, 3); with want_hits also the (n, 16) records, the words
+    `query_hits` returns for the same rays and seed.  Misses, emitters and dielectrics are (1, 1, 1)."""
+    r = np.ascontiguousarray(rays, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] != RAY_DOUBLES:
+        raise ValueError(f"rays of shape {r.shape}: want (n, {RAY_DOUBLES})")
+    out = np.zeros((len(r), 3), dtype=np.float64)
+    hits = np.zeros((len(r), HIT_DOUBLES), dtype=np.float64) if want_hits else None
+    _check(_rt().rt_query_albedo(b.h, len(r), r.ctypes.data, float(t_min), seed, 0, out.ctypes.data, hits.ctypes.data if want_hits else None))
+    return (out, hits) if want_hits else out
+
+
+def query_albedo_device(b: SceneBuilder, n: int, d_rays, d_albedo, d_hits=None, t_min: float = 1e-5, seed: int = 0, stream: int = 0,
+                        d_albedo_bytes=None, d_hits_bytes=None) -> None:
+    """rt_query_albedo_device: the same for buffers in device memory (torch tensors of f64, or raw pointers with their sizes), enqueued on
+    `stream`; never waits.  d_rays and d_hits 16-byte aligned."""
+    rays_ptr, _ = _device_buffer(d_rays)
+    alb_ptr, abytes = _device_buffer(d_albedo)
+    abytes = abytes if d_albedo_bytes is None else int(d_albedo_bytes)
+    hits_ptr, hbytes = (None, 0) if d_hits is None else _device_buffer(d_hits)
+    hbytes = hbytes if d_hits_bytes is None else int(d_hits_bytes)
+    if abytes is None or hbytes is None:
+        raise ValueError("d_albedo_bytes / d_hits_bytes are needed with raw pointers")
+    _check(_rt().rt_query_albedo_device(b.h, n, C.c_void_p(rays_ptr), float(t_min), seed, 0, C.c_void_p(alb_ptr), abytes, C.c_void_p(hits_ptr), hbytes,
+                                        C.c_void_p(stream)))
+
+
+def query_camera_albedo(b: SceneBuilder, cam: CameraParams, W: int, H: int, first_sample: int = 0, n_samples: int = 1,
+                        seed: int = DEFAULT_SEED) -> np.ndarray:
+    """rt_query_camera_albedo: per pixel the sum over samples [first_sample, first_sample + n_samples) of the albedo under that sample's
+    camera ray -> (H, W, 3) f64, row 0 = top; divide by n_samples for the mean."""
+    out = np.zeros((H, W, 3), dtype=np.float64)
+    _check(_rt().rt_query_camera_albedo(b.h, C.byref(cam), W, H, first_sample, n_samples, seed, 0, out.ctypes.data))
+    return out
+
+
+def query_camera_albedo_device(b: SceneBuilder, cam: CameraParams, W: int, H: int, d_albedo_sum, first_sample: int = 0, n_samples: int = 1,
+                               seed: int = DEFAULT_SEED, stream: int = 0, d_albedo_sum_bytes=None) -> None:
+    """rt_query_camera_albedo_device: the W*H*3 sums into device memory, enqueued on `stream`; never waits."""
+    ptr, nbytes = _device_buffer(d_albedo_sum)
+    nbytes = nbytes if d_albedo_sum_bytes is None else int(d_albedo_sum_bytes)
+    if nbytes is None:
+        raise ValueError("d_albedo_sum_bytes is needed with a raw pointer")
+    _check(_rt().rt_query_camera_albedo_device(b.h, C.byref(cam), W, H, first_sample, n_samples, seed, 0, C.c_void_p(ptr), nbytes, C.c_void_p(stream)))
+
+
+def material_info(b: SceneBuilder, material: int) -> dict:
+    """rt_material_info (host only): {"kind": index into MATERIAL_KINDS, "texture": handle or -1, "albedo": (3,) — Metal's, else zeros}."""
+    kt = (C.c_int32 * 2)()
+    alb = (C.c_double * 3)()
+    _check(_rt().rt_material_info(b.h, int(material), kt, alb))
+    return {"kind": int(kt[0]), "texture": int(kt[1]), "albedo": np.array(alb, dtype=np.float64)}
+
+
+def albedo_image(albedo_sum: np.ndarray, n_samples: int) -> np.ndarray:
+    """An (H, W, 3) 8-bit image of an albedo frame, as `rtrender --aov albedo` writes it: the mean held to [0, 1], times 255.999, truncated
+    (no gamma: an albedo is data, not radiance)."""
+    a = np.asarray(albedo_sum, dtype=np.float64) / float(n_samples)
+    return (np.clip(np.nan_to_num(a, nan=0.0), 0.0, 1.0) * 255.999).astype(np.uint8)
+
+
 def last_query_ms(b: SceneBuilder) -> float:
     """Milliseconds of the most recent query kernel of this scene (HIP events; waits for it)."""
     ms = C.c_float()
@@ -698,6 +778,53 @@ def denoise_device(d_rgb_sum, samples: int, d_hits, W: int, H: int, d_rgb_sum_ou
     k, sg = _denoise_settings(iterations, sigma)
     _check(_rt().rt_denoise_device(C.c_void_p(sum_ptr), int(samples), C.c_void_p(hits_ptr), W, H, k, sg, flags, C.c_void_p(out_ptr),
                                    C.c_void_p(ws_ptr), nbytes, C.c_void_p(stream)))
+    return d_workspace
+
+
+# ---- albedo-demodulated denoising (rt_denoise_albedo*, csrc/rt_albedo.h): the same filter on rgb_sum / albedo, multiplied back
+def _denoise_albedo_call(fn, rgb_sum, samples, albedo_sum, albedo_samples, hits, iterations, sigma, flags):
+    a, g = _denoise_frames(rgb_sum, hits)
+    al = np.ascontiguousarray(albedo_sum, dtype=np.float64)
+    if al.shape != a.shape:
+        raise ValueError(f"albedo_sum of shape {al.shape} for a frame of {a.shape}")
+    k, sg = _denoise_settings(iterations, sigma)
+    out = np.zeros_like(a)
+    _check(fn(a.ctypes.data, int(samples), al.ctypes.data, int(albedo_samples), g.ctypes.data, a.shape[1], a.shape[0], k, sg, flags, out.ctypes.data))
+    return out
+
+
+def denoise_albedo_host(rgb_sum, samples: int, albedo_sum, albedo_samples: int, hits, iterations: int = None, sigma=None, flags: int = 0) -> np.ndarray:
+    """rt_denoise_albedo_host (no GPU): the demodulated filter's specification as plain C++.  albedo_sum (H, W, 3) as query_camera_albedo
+    returns it, holding albedo_samples samples per pixel; the rest as `denoise_host`."""
+    return _denoise_albedo_call(_rt().rt_denoise_albedo_host, rgb_sum, samples, albedo_sum, albedo_samples, hits, iterations, sigma, flags)
+
+
+def denoise_albedo(rgb_sum, samples: int, albedo_sum, albedo_samples: int, hits, iterations: int = None, sigma=None, flags: int = 0) -> np.ndarray:
+    """rt_denoise_albedo: the same call computed by the HIP kernels on the current device — the same words as denoise_albedo_host."""
+    return _denoise_albedo_call(_rt().rt_denoise_albedo, rgb_sum, samples, albedo_sum, albedo_samples, hits, iterations, sigma, flags)
+
+
+def denoise_albedo_workspace_bytes(W: int, H: int) -> int:
+    return int(_rt().rt_denoise_albedo_workspace_bytes(W, H))
+
+
+def denoise_albedo_device(d_rgb_sum, samples: int, d_albedo_sum, albedo_samples: int, d_hits, W: int, H: int, d_rgb_sum_out=None, d_workspace=None,
+                          iterations: int = None, sigma=None, flags: int = 0, stream: int = 0, workspace_bytes=None):
+    """rt_denoise_albedo_device: `denoise_device` with demodulation; the workspace is denoise_albedo_workspace_bytes(W, H) bytes."""
+    sum_ptr, _ = _device_buffer(d_rgb_sum)
+    alb_ptr, _ = _device_buffer(d_albedo_sum)
+    hits_ptr, _ = _device_buffer(d_hits)
+    out_ptr = sum_ptr if d_rgb_sum_out is None else _device_buffer(d_rgb_sum_out)[0]
+    if d_workspace is None:
+        import torch
+        d_workspace = torch.empty(denoise_albedo_workspace_bytes(W, H), dtype=torch.uint8, device=d_rgb_sum.device)
+    ws_ptr, nbytes = _device_buffer(d_workspace)
+    nbytes = nbytes if workspace_bytes is None else int(workspace_bytes)
+    if nbytes is None:
+        raise ValueError("workspace_bytes is needed with a raw pointer")
+    k, sg = _denoise_settings(iterations, sigma)
+    _check(_rt().rt_denoise_albedo_device(C.c_void_p(sum_ptr), int(samples), C.c_void_p(alb_ptr), int(albedo_samples), C.c_void_p(hits_ptr), W, H, k, sg,
+                                          flags, C.c_void_p(out_ptr), C.c_void_p(ws_ptr), nbytes, C.c_void_p(stream)))
     return d_workspace
 
 

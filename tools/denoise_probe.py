@@ -5,8 +5,13 @@ each launch (pack: 152 B in, 96 B out per pixel; an iteration: 96 B in, 32 B out
 synthetic (a smooth colour field plus noise over a guide of a few planes): the kernels' time depends on the frame's size and, through the
 skipped taps, on how many neighbours share a key, not on what the scene is.  Part 2: the clipped mean squared error against a converged
 frame (tests/denoise_cases.py clipped_mse) of raw and denoised frames at 16 and 64 samples per pixel for K = 1 .. 5 on the four preview
-scenes at reduced size, with the Python defaults' sigmas: what render.DENOISE_ITERATIONS is chosen from.
-usage: python tools/denoise_probe.py [timing] [errors] > profiles/denoise.log"""
+scenes at reduced size, with the Python defaults' sigmas: what render.DENOISE_ITERATIONS is chosen from — the plain filter and, beside it,
+the albedo-demodulated one (rt_denoise_albedo, albedo of ALBEDO_SAMPLES samples).  Part 3: the albedo query's kernel time
+(rt_query_camera_albedo_device, rt_last_query_ms) at 1, 16 and 64 samples per pixel on the Cornell box at 800 x 800 and the random spheres
+at 1200 x 675, beside the time of a path-tracing pass of the same number of samples from the same run, and the two element-wise kernels of
+rt_denoise_albedo_device (rt_debug_albedo_modulate_ms) at 800 x 800 and 3840 x 2160 beside the pack kernel.
+usage: python tools/denoise_probe.py [timing] [errors] > profiles/denoise.log
+       python tools/denoise_probe.py albedo errors > profiles/denoise_albedo.log"""
 import ctypes as C
 import os
 import sys
@@ -23,6 +28,7 @@ from raytracinginrust_amd import render as R  # noqa: E402
 REPS = 5
 K = 5
 HBM_ACHIEVABLE = 6.3e12
+ALBEDO_SAMPLES = 16
 
 
 def synthetic(W, H, dev):
@@ -92,24 +98,85 @@ def errors():
     be = _lib.load()
     earth = scenes.load_earthmap()
     depth, truth_spp = 20, 4096
-    print(f"# clipped MSE against {truth_spp} spp (seed 99), depth {depth}, sigma = {R.DENOISE_SIGMA}, flags 0: raw, then K = 1 .. 5 (ratio to raw)")
+    print(f"# clipped MSE against {truth_spp} spp (seed 99), depth {depth}, sigma = {R.DENOISE_SIGMA}, flags 0: raw, then K = 1 .. 5 (ratio to raw);")
+    print(f"# 'plain' rt_denoise, 'demod' rt_denoise_albedo with the albedo of samples 0 .. {ALBEDO_SAMPLES - 1} of the noisy frame's seed")
     for name, (W, H) in (("cornell", (100, 100)), ("random", (160, 90)), ("final", (100, 100)), ("teapot", (160, 90))):
         b, cam, bg = build_scene(name, be, earth)
         truth = R.render(b, cam, bg, W, H, truth_spp, depth, 99)
         hits = R.query_camera(b, cam, W, H, 0, 7)
+        alb = R.query_camera_albedo(b, cam, W, H, 0, ALBEDO_SAMPLES, 7)
         for spp in (16, 64):
             noisy = R.render(b, cam, bg, W, H, spp, depth, 7)
             raw = clipped_mse(noisy, spp, truth, truth_spp)
-            row = []
+            row, row_demod = [], []
             for k in range(1, 6):
                 e = clipped_mse(R.denoise(noisy, spp, hits, k, R.DENOISE_SIGMA, 0), spp, truth, truth_spp)
                 row.append(f"{e:.5f} ({e / raw:.2f})")
-            print(f"{name} {W}x{H} {spp} spp  raw {raw:.5f}  " + "  ".join(row), flush=True)
+                e = clipped_mse(R.denoise_albedo(noisy, spp, alb, ALBEDO_SAMPLES, hits, k, R.DENOISE_SIGMA, 0), spp, truth, truth_spp)
+                row_demod.append(f"{e:.5f} ({e / raw:.2f})")
+            print(f"{name} {W}x{H} {spp} spp  raw {raw:.5f}  plain  " + "  ".join(row), flush=True)
+            print(f"{name} {W}x{H} {spp} spp  raw {raw:.5f}  demod  " + "  ".join(row_demod), flush=True)
+
+
+def albedo():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import build_scene
+    be = _lib.load()
+    lib = be.lib
+    dev = torch.device("cuda", torch.cuda.current_device())
+    print(f"# rt_query_camera_albedo_device: kernel ms (rt_last_query_ms), warm, best of {REPS}; beside it a path-tracing pass of the same number of")
+    print("# samples per pixel of the same view (rt_progressive_add, rt_last_kernel_ms), depth 50, from the same run")
+    print("# scene frame  n_samples  albedo ms  Mrays/s  pass ms  albedo / pass")
+    for name, (W, H) in (("cornell", (800, 800)), ("random", (1200, 675))):
+        b, cam, bg = build_scene(name, be, None)
+        d_alb = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
+        for n in (1, 16, 64):
+            best = 1e30
+            for rep in range(REPS + 1):                           # the first run warms up (upload, code object)
+                R.query_camera_albedo_device(b, cam, W, H, d_alb, 0, n, 7)
+                ms = R.last_query_ms(b)
+                if rep:
+                    best = min(best, ms)
+            best_pass = 1e30
+            with R.Progressive(b, cam, bg, W, H, 50, 7) as frame:
+                for rep in range(REPS + 1):
+                    frame.add(n)
+                    if rep:
+                        best_pass = min(best_pass, R.last_kernel_ms(b))
+            print(f"{name} {W}x{H}  {n}  {best:.4f}  {W * H * n / best / 1e3:.0f}  {best_pass:.4f}  {best / best_pass:.3f}", flush=True)
+        del d_alb
+    print(f"# the two element-wise kernels of rt_denoise_albedo_device (rt_debug_albedo_modulate_ms), HIP events, warm, best of {REPS}; floors: demodulate")
+    print("# 48 B in + 24 B out per pixel, remodulate 48 B in + 24 B out; the pack kernel of the same frame (152 B in, 96 B out) beside them")
+    print("# frame  kernel  ms  floor bytes  achieved TB/s")
+    sigma = (C.c_double * 3)(*R.DENOISE_SIGMA)
+    for W, H in ((800, 800), (3840, 2160)):
+        rgb, hits = synthetic(W, H, dev)
+        alb = (torch.rand((H, W, 3), device=dev, dtype=torch.float64) * ALBEDO_SAMPLES).contiguous()
+        x = torch.empty_like(rgb)
+        need = R.denoise_workspace_bytes(W, H)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        best = np.full(2, 1e30); best_pack = 1e30
+        for _ in range(REPS):
+            ms = (C.c_float * 2)()
+            if lib.rt_debug_albedo_modulate_ms(C.c_void_p(rgb.data_ptr()), C.c_void_p(alb.data_ptr()), ALBEDO_SAMPLES, C.c_void_p(x.data_ptr()), W * H * 3, ms) != 0:
+                raise RuntimeError(lib.rt_last_error().decode())
+            best = np.minimum(best, np.array(ms[:]))
+            pk = (C.c_float * 2)()
+            if lib.rt_debug_denoise_ms(C.c_void_p(rgb.data_ptr()), 16, C.c_void_p(hits.data_ptr()), W, H, 1, sigma, 0, C.c_void_p(x.data_ptr()), C.c_void_p(ws.data_ptr()), need, pk) != 0:
+                raise RuntimeError(lib.rt_last_error().decode())
+            best_pack = min(best_pack, pk[0])
+        n = W * H
+        for kname, ms, floor in (("demodulate", best[0], n * 72), ("remodulate", best[1], n * 72), ("pack", best_pack, n * 248)):
+            print(f"{W}x{H}  {kname}  {ms:.4f}  {floor}  {floor / (ms * 1e-3) / 1e12:.3f}", flush=True)
+        del rgb, hits, alb, x, ws
 
 
 if __name__ == "__main__":
     what = sys.argv[1:] or ["timing", "errors"]
     if "timing" in what:
         timing()
+    if "albedo" in what:
+        albedo()
     if "errors" in what:
         errors()
