@@ -301,6 +301,23 @@ inline std::vector<Ray> equirect_rays(Point3 origin, uint32_t W, uint32_t H, dou
     return rays;
 }
 
+// The per-pixel error estimate of a frame of passes (rt_moments_*, csrc/rt_moments.h).  ErrorStats: the pixels whose standard error in display
+// units (1/256 = one code value) is <= tau / > tau / not finite, and the largest finite e2 (a squared standard error).
+struct ErrorStats {
+    uint64_t converged = 0, unconverged = 0, nonfinite = 0; double max_e2 = 0.0;
+    static ErrorStats from_words(const uint64_t w[4]) { ErrorStats s; s.converged = w[0]; s.unconverged = w[1]; s.nonfinite = w[2]; std::memcpy(&s.max_e2, &w[3], sizeof(double)); return s; }
+};
+// e2 of every pixel (W*H doubles, output order) from sums and second moments of `passes` passes holding `samples` samples per pixel — the host
+// form: no device needed.  stats (optional) receives the statistics for tau.
+inline std::vector<double> moments_error(const std::vector<double>& rgb_sum, const std::vector<double>& sq_sum, uint64_t samples, uint64_t passes,
+                                         uint32_t W, uint32_t H, double tau = 1.0 / 256.0, ErrorStats* stats = nullptr) {
+    if (rgb_sum.size() != (size_t)W * H * 3 || sq_sum.size() != rgb_sum.size()) throw Error("moments_error: frames of another size");
+    std::vector<double> e2((size_t)W * H);
+    if (rt_moments_error_host(rgb_sum.data(), sq_sum.data(), samples, passes, W, H, e2.data()) != 0) throw Error(rt_last_error());
+    if (stats) { uint64_t w[4]; if (rt_moments_stats_host(e2.data(), e2.size(), tau, w) != 0) throw Error(rt_last_error()); *stats = ErrorStats::from_words(w); }
+    return e2;
+}
+
 // A progressive frame (rt_progressive_*): the same loop in passes of samples that accumulate on the device, with the reference's
 // format_color (src/vec.rs:125-131) resolved there too — progress, preview, stop half-way, "another 1000 samples", save and resume.
 class Progressive {
@@ -328,6 +345,17 @@ public:
         chk(rt_progressive_load_sum(p_, rgb_sum.data(), samples_done));
     }
     void reset() { chk(rt_progressive_reset(p_)); }
+    // moments (rt_progressive_enable_moments): only while the frame holds 0 samples; from then on every pass is also merged into the second
+    // moment of the pass sums, and once two passes are in error_map / error_stats estimate every pixel's standard error
+    void enable_moments() { chk(rt_progressive_enable_moments(p_)); }
+    uint64_t passes() const { uint64_t n = 0; chk(rt_progressive_passes(p_, &n)); return n; }
+    std::vector<double> sq_sum() const { std::vector<double> out(n_px_ * 3); chk(rt_progressive_read_moments(p_, out.data())); return out; }
+    void load(const std::vector<double>& rgb_sum, const std::vector<double>& sq_sum, uint64_t samples_done, uint64_t passes) {
+        if (rgb_sum.size() != n_px_ * 3 || sq_sum.size() != n_px_ * 3) throw Error("checkpoint of another frame size");
+        chk(rt_progressive_load_moments(p_, rgb_sum.data(), sq_sum.data(), samples_done, passes));
+    }
+    std::vector<double> error_map() { std::vector<double> out(n_px_); chk(rt_progressive_error_map(p_, out.data())); return out; }      // e2, W*H doubles
+    ErrorStats error_stats(double tau) { uint64_t w[4]; chk(rt_progressive_error_stats(p_, tau, w)); return ErrorStats::from_words(w); }
 private:
     static void chk(int rc) { if (rc != 0) throw Error(rt_last_error()); }
     void* p_; size_t n_px_;

@@ -239,6 +239,58 @@ int rt_progressive_load_sum(void* frame, const double* rgb_sum, uint64_t samples
 int rt_progressive_reset(void* frame);
 void rt_progressive_destroy(void* frame);                                  /* waits for the frame's work; the scene may be gone already */
 
+/* ---- moments: the per-pixel error estimate of a frame that accumulates passes, and a statistical stop.  The changed-pixel count of a
+ *      resolve depends on the pass size and on when the caller resolves, and says nothing per pixel; a standard error does.  The path-tracing
+ *      kernels gather no second moment.  It is taken BETWEEN passes, from the pass frames themselves (batch means): a pass of n_b samples is
+ *      rendered into a pass frame p of its own and merged,   S += p,   Q += p*p / n_b   (per pixel and channel),   and for B >= 2 passes and
+ *      N samples the between-pass sum of squares  ssb = max(Q - S*S/N, 0)  estimates (B - 1) sigma^2 — for unequal n_b too — so that
+ *      V = ssb / (B - 1) / N is the variance of the mean m = S / N, and  e2 = V / (4 max(m, 2^-8))  the squared standard error of what
+ *      format_color shows, sqrt(m), in display units (1/256 = one code value); a channel whose mean lies three standard errors above the
+ *      clamp counts as 0; a pixel's e2 is the largest of its three channels'.  csrc/rt_moments.h is the exact specification — + - * / and
+ *      comparisons in a fixed order — and the host forms, the HIP kernels (csrc/rt_moments.hip) and the NumPy restatement of
+ *      tests/moments_cases.py give the same 64-bit words.
+ * The building blocks, for one-process-per-GPU callers of rt_render_device_pass too.  n_doubles = 3 * pixels; every frame 8-byte aligned.
+ * rt_moments_merge_host merges pass_sum into rgb_sum and sq_sum and leaves pass_sum as it is.  rt_moments_merge_device does the same for
+ * DEVICE pointers (three distinct buffers; 16-byte accesses when all are 16-byte aligned) on hip_stream (a hipStream_t, may be NULL), never
+ * waits, never allocates, and sets d_pass_sum to +0.0: the pass frame is ready for the next rt_render_device_pass(accumulate = 1), so a pass
+ * costs no memset of its own.  Errors (non-zero, a message for rt_last_error, nothing written or launched): null pointers, n_samples = 0. */
+int rt_moments_merge_host(const double* pass_sum, uint64_t n_samples, double* rgb_sum, double* sq_sum, uint64_t n_doubles);
+int rt_moments_merge_device(void* d_pass_sum, uint64_t n_samples, void* d_rgb_sum, void* d_sq_sum, uint64_t n_doubles, void* hip_stream);
+/* e2 of every pixel (W*H doubles, output order) from the sums of `passes` passes holding `samples` samples per pixel.  Errors: null
+ * pointers, passes < 2, samples = 0, W*H = 0 or > 2^31 - 1. */
+int rt_moments_error_host(const double* rgb_sum, const double* sq_sum, uint64_t samples, uint64_t passes, uint32_t W, uint32_t H, double* e2_out);
+/* The statistics of an error map for a threshold tau (a standard error in display units): stats_out[0] = converged, the pixels with e2 finite
+ * and e2 <= tau*tau; [1] = unconverged, e2 finite and > tau*tau; [2] = nonfinite, the rest; [3] = the bit pattern of the largest finite e2
+ * (+0.0 when there is none).  All four are exact, whatever the order of the pixels.  Errors: null pointers, tau negative or NaN. */
+int rt_moments_stats_host(const double* e2, uint64_t n_px, double tau, uint64_t stats_out[4]);
+/* Both on the device, enqueued on hip_stream; never waits, never allocates.  d_e2_out (W*H doubles) and d_stats_out (four 64-bit words,
+ * zeroed in stream order by this call) may each be NULL; tau is looked at only with d_stats_out. */
+int rt_moments_error_device(const void* d_rgb_sum, const void* d_sq_sum, uint64_t samples, uint64_t passes, uint32_t W, uint32_t H,
+                            void* d_e2_out, double tau, void* d_stats_out, void* hip_stream);
+/* A progressive frame with moments.  Allowed only while the frame holds 0 samples (an error otherwise); allocates the second-moment frame
+ * and the pass frame, zeroed (48 more bytes per pixel).  From then on a pass renders into the pass frame and is followed by the merge kernel on
+ * the same stream: the frame's sums are the merge-order sum of the pass frames — still within the any-order bound rt_progressive_read_sum
+ * states — and resolve, read_sum, both denoised resolves and samples_out work unchanged.  Passes of rt_progressive_add_async on different
+ * streams share the pass frame: the frame records an event behind every merge and makes the next pass's stream wait for it
+ * (hipStreamWaitEvent), so the host still never waits and the passes SERIALISE on the device instead of overlapping.  A frame that never
+ * enables moments takes exactly the path it took before.  rt_progressive_reset zeroes the second moments and the pass count and keeps
+ * moments enabled.  rt_progressive_load_sum keeps working and marks the moments INVALID (the sums would hold samples the second moments do
+ * not): the error calls then fail with a message until rt_progressive_reset or rt_progressive_load_moments. */
+int rt_progressive_enable_moments(void* frame);
+int rt_progressive_passes(void* frame, uint64_t* passes_out);             /* passes merged so far (enqueued ones included); 0 without moments */
+/* The second moments, W*H*3 doubles (waits for the passes enqueued so far): with rt_progressive_read_sum, rt_progressive_samples and
+ * rt_progressive_passes, a checkpoint — which rt_progressive_load_moments resumes from (samples_done <= 2^32 - 1; 0 samples or 0 passes only
+ * with frames that are all zero, and with each other). */
+int rt_progressive_read_moments(void* frame, double* sq_sum_out);
+int rt_progressive_load_moments(void* frame, const double* rgb_sum, const double* sq_sum, uint64_t samples_done, uint64_t passes);
+/* rt_moments_error_device on the frame's own sums.  error_map: e2 of every pixel to host memory (W*H doubles); error_map_device: enqueued
+ * on hip_stream, never waits, *d_e2_out receives the DEVICE address of the W*H doubles, a buffer owned by the frame and allocated at the
+ * first call; error_stats: the four words of rt_moments_stats_host for tau.  error_map and error_stats wait for every pass enqueued so
+ * far, as rt_progressive_resolve_rgb8 does.  Errors: a frame without moments, moments invalid, fewer than 2 passes, tau negative or NaN. */
+int rt_progressive_error_map(void* frame, double* e2_out);
+int rt_progressive_error_map_device(void* frame, void** d_e2_out, void* hip_stream);
+int rt_progressive_error_stats(void* frame, double tau, uint64_t stats_out[4]);
+
 /* ---- ray queries: the reference's `world.hit(r, 0.00001, f64::INFINITY)` (src/main.rs:48, Hittable::hit) as a function of its own — the
  *      closest hit of rays the caller chooses, or of the camera rays of one sample of every pixel: which object is under pixel (i, j), how far
  *      away it is (auto-focus), depth / normal / material-id frames for a denoiser or a compositor, visibility probes.  The search and the

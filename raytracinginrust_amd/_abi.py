@@ -104,6 +104,19 @@ SIGNATURES = {
     "progressive_load_sum": (_int, [_ptr, _ptr, _u64]),
     "progressive_reset": (_int, [_ptr]),
     "progressive_destroy": (None, [_ptr]),
+    # moments: the per-pixel error estimate of a progressive frame
+    "moments_merge_host": (_int, [_ptr, _u64, _ptr, _ptr, _u64]),
+    "moments_merge_device": (_int, [_ptr, _u64, _ptr, _ptr, _u64, _ptr]),
+    "moments_error_host": (_int, [_ptr, _ptr, _u64, _u64, _u32, _u32, _ptr]),
+    "moments_stats_host": (_int, [_ptr, _u64, _f64, c_u64_p]),
+    "moments_error_device": (_int, [_ptr, _ptr, _u64, _u64, _u32, _u32, _ptr, _f64, _ptr, _ptr]),
+    "progressive_enable_moments": (_int, [_ptr]),
+    "progressive_passes": (_int, [_ptr, c_u64_p]),
+    "progressive_read_moments": (_int, [_ptr, _ptr]),
+    "progressive_load_moments": (_int, [_ptr, _ptr, _ptr, _u64, _u64]),
+    "progressive_error_map": (_int, [_ptr, _ptr]),
+    "progressive_error_map_device": (_int, [_ptr, c_void_pp, _ptr]),
+    "progressive_error_stats": (_int, [_ptr, _f64, c_u64_p]),
     # ray queries
     "camera_ray": (_int, [_cam_p, _u32, _u32, _u32, _u32, _u64, _u32, c_double_p]),
     "query_hits": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _ptr]),

@@ -22,6 +22,7 @@
 #include "rt_denoise.h"
 #define RT_ALBEDO_QUERIES
 #include "rt_albedo.h"
+#include "rt_moments.h"
 
 using namespace rt;
 
@@ -55,6 +56,14 @@ struct Progressive {
     // albedo_samples, and the demodulated frame of a run (24 + 24 bytes per pixel).  albedo_builds counts the launches that built d_alb_sum.
     void* d_alb_sum = nullptr; void* d_alb_x = nullptr;
     uint32_t albedo_samples = 0; uint64_t albedo_builds = 0;
+    // rt_progressive_enable_moments (rt_moments.h): the second moments Q (d_sq) and the pass frame a pass renders into before the merge
+    // kernel adds it to d_sum and d_sq and zeroes it again (24 + 24 bytes per pixel); `passes` merges so far; moments_valid: d_sq describes
+    // the samples d_sum holds (rt_progressive_load_sum breaks that).  ev_merged is recorded behind every merge: the next pass's stream waits
+    // for it, because passes on different streams share d_pass.  d_e2 (rt_progressive_error_map*, allocated at the first call) and the
+    // four statistics words.
+    bool moments = false, moments_valid = false, merge_recorded = false; uint64_t passes = 0;
+    void* d_sq = nullptr; void* d_pass = nullptr; void* d_e2 = nullptr; void* d_mstats = nullptr;
+    hipEvent_t ev_merged = nullptr;
     size_t n_px() const { return (size_t)W * H; }
 };
 
@@ -1598,6 +1607,8 @@ static void progressive_free(Progressive* p) {
     free_dev(p->d_sum); free_dev(p->d_rgb8[0]); free_dev(p->d_rgb8[1]); free_dev(p->d_changed);
     free_dev(p->d_dn_ws); free_dev(p->d_dn_sum); free_dev(p->d_dn_rgb8); free_dev(p->d_dn_changed);
     free_dev(p->d_alb_sum); free_dev(p->d_alb_x);
+    free_dev(p->d_sq); free_dev(p->d_pass); free_dev(p->d_e2); free_dev(p->d_mstats);
+    if (p->ev_merged) { (void)hipEventDestroy(p->ev_merged); p->ev_merged = nullptr; }
 }
 void* rt_progressive_create(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t max_depth,
                             uint64_t seed, uint32_t flags) {
@@ -1640,6 +1651,17 @@ static int progressive_pass_args(Progressive* p, uint32_t n) {
 }
 static int progressive_pass(Progressive* p, uint32_t n, void* d_samples, hipStream_t stream, bool may_calibrate) {
     const size_t n_px = p->n_px();
+    if (p->moments) {
+        // the pass frame is shared: this pass starts behind the merge of the one before it, whatever stream that was on (the host does not wait)
+        if (p->merge_recorded) HIP_OK(hipStreamWaitEvent(stream, p->ev_merged, 0));
+        if (render_any(p->sc, &p->cam, p->bg, p->W, p->H, n, p->max_depth, p->seed, p->flags, (uint32_t)n_px, 0, 1, p->d_pass, n_px * 3 * sizeof(double),
+                       d_samples, stream, may_calibrate, (uint32_t)p->done, true)) return -1;
+        HIP_OK((hipError_t)launch_moments_merge((double*)p->d_pass, n, (double*)p->d_sum, (double*)p->d_sq, (uint64_t)n_px * 3u, stream));
+        HIP_OK(hipEventRecord(p->ev_merged, stream));
+        p->merge_recorded = true;
+        p->done += n; p->passes++;
+        return 0;
+    }
     if (render_any(p->sc, &p->cam, p->bg, p->W, p->H, n, p->max_depth, p->seed, p->flags, (uint32_t)n_px, 0, 1, p->d_sum, n_px * 3 * sizeof(double),
                    d_samples, stream, may_calibrate, (uint32_t)p->done, true)) return -1;
     p->done += n;
@@ -1718,6 +1740,15 @@ static int progressive_restart(Progressive* p, const double* rgb_sum, uint64_t s
     if (rgb_sum) HIP_OK(hipMemcpy(p->d_sum, rgb_sum, p->n_px() * 3 * sizeof(double), hipMemcpyHostToDevice));
     else { HIP_OK(hipMemsetAsync(p->d_sum, 0, p->n_px() * 3 * sizeof(double), nullptr)); HIP_OK(hipStreamSynchronize(nullptr)); }
     p->done = samples_done; p->have_prev = false; p->resolved = false;       // the next resolve is a first one: every pixel counts as changed
+    if (p->moments) {
+        // a frame of sums alone (rt_progressive_load_sum) holds samples the second moments know nothing of: they are invalid until a reset
+        // or rt_progressive_load_moments; a reset starts them again.  The pass frame is +0.0 either way (a pass that failed half-way too).
+        p->moments_valid = rgb_sum == nullptr;
+        p->passes = 0;
+        HIP_OK(hipMemsetAsync(p->d_sq, 0, p->n_px() * 3 * sizeof(double), nullptr));
+        HIP_OK(hipMemsetAsync(p->d_pass, 0, p->n_px() * 3 * sizeof(double), nullptr));
+        HIP_OK(hipStreamSynchronize(nullptr));
+    }
     return 0;
 }
 int rt_progressive_load_sum(void* frame, const double* rgb_sum, uint64_t samples_done) {
@@ -1738,6 +1769,134 @@ int rt_progressive_reset(void* frame) {
     p->guide_valid = false;                             // ... and so is its denoising guide, rebuilt when it is next needed
     p->albedo_samples = 0;                              // ... and its albedo sums
     return progressive_restart(p, nullptr, 0);
+}
+
+// ---------------------------------------------------------------- moments (csrc/rt_moments.h: the specification; rt_moments.hip: the kernels)
+int rt_moments_merge_device(void* d_pass_sum, uint64_t n_samples, void* d_rgb_sum, void* d_sq_sum, uint64_t n_doubles, void* hip_stream) {
+    if (!d_pass_sum || !d_rgb_sum || !d_sq_sum) return set_err("null argument");
+    const std::string problem = moments_merge_check(n_samples);
+    if (!problem.empty()) return set_err(problem);
+    if ((((uintptr_t)d_pass_sum | (uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum) & 7u) != 0u) return set_err("d_pass_sum, d_rgb_sum and d_sq_sum must be 8-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    HIP_OK((hipError_t)launch_moments_merge((double*)d_pass_sum, n_samples, (double*)d_rgb_sum, (double*)d_sq_sum, n_doubles, hip_stream));
+    return 0;
+}
+int rt_moments_error_device(const void* d_rgb_sum, const void* d_sq_sum, uint64_t samples, uint64_t passes, uint32_t W, uint32_t H,
+                            void* d_e2_out, double tau, void* d_stats_out, void* hip_stream) {
+    if (!d_rgb_sum || !d_sq_sum) return set_err("null argument");
+    std::string problem = moments_error_check(samples, passes, W, H);
+    if (problem.empty() && d_stats_out) problem = moments_tau_check(tau);
+    if (!problem.empty()) return set_err(problem);
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum | (uintptr_t)d_e2_out | (uintptr_t)d_stats_out) & 7u) != 0u) return set_err("d_rgb_sum, d_sq_sum, d_e2_out and d_stats_out must be 8-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    if (!d_e2_out && !d_stats_out) return 0;                    // nothing asked for
+    if (d_stats_out) HIP_OK(hipMemsetAsync(d_stats_out, 0, MOMENTS_STATS_WORDS * sizeof(uint64_t), (hipStream_t)hip_stream));
+    HIP_OK((hipError_t)launch_moments_error((const double*)d_rgb_sum, (const double*)d_sq_sum, samples, passes, W * H, (double*)d_e2_out, tau * tau,
+                                            (unsigned long long*)d_stats_out, hip_stream));
+    return 0;
+}
+int rt_progressive_enable_moments(void* frame) {
+    Progressive* p = (Progressive*)frame;
+    if (!p) return set_err("null argument");
+    if (p->moments) return 0;
+    if (p->done != 0) return set_err("moments can only be enabled while the frame holds 0 samples (the second moments must cover every sample of the sums): rt_progressive_reset first");
+    DeviceGuard guard(p->device);
+    const size_t bytes = p->n_px() * 3 * sizeof(double);
+    hipError_t e = hipMalloc(&p->d_sq, bytes);
+    if (e == hipSuccess) e = hipMalloc(&p->d_pass, bytes);
+    if (e == hipSuccess) e = hipMalloc(&p->d_mstats, MOMENTS_STATS_WORDS * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_merged, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_sq, 0, bytes, nullptr);
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_pass, 0, bytes, nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        free_dev(p->d_sq); free_dev(p->d_pass); free_dev(p->d_mstats);
+        if (p->ev_merged) { (void)hipEventDestroy(p->ev_merged); p->ev_merged = nullptr; }
+        return set_err(std::string("rt_progressive_enable_moments: ") + hipGetErrorString(e));
+    }
+    p->moments = true; p->moments_valid = true; p->merge_recorded = false; p->passes = 0;
+    return 0;
+}
+static int moments_frame(Progressive* p) {
+    if (!p) return set_err("null argument");
+    if (!p->moments) return set_err("this progressive frame has no moments (rt_progressive_enable_moments, while it holds 0 samples)");
+    return 0;
+}
+// what the three error calls check: moments that describe the sums, and two passes
+static int moments_error_ready(Progressive* p) {
+    if (moments_frame(p)) return -1;
+    if (!p->moments_valid) return set_err("the moments of this frame are invalid: rt_progressive_load_sum loaded sums whose second moments are unknown (rt_progressive_reset or rt_progressive_load_moments)");
+    const std::string problem = moments_error_check(p->done, p->passes, p->W, p->H);
+    return problem.empty() ? 0 : set_err(problem);
+}
+int rt_progressive_passes(void* frame, uint64_t* passes_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !passes_out) return set_err("null argument");
+    *passes_out = p->moments ? p->passes : 0u;
+    return 0;
+}
+int rt_progressive_read_moments(void* frame, double* sq_sum_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!sq_sum_out) return set_err("null argument");
+    if (moments_frame(p)) return -1;
+    if (!p->moments_valid) return set_err("the moments of this frame are invalid: rt_progressive_load_sum loaded sums whose second moments are unknown (rt_progressive_reset or rt_progressive_load_moments)");
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(sq_sum_out, p->d_sq, p->n_px() * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+int rt_progressive_load_moments(void* frame, const double* rgb_sum, const double* sq_sum, uint64_t samples_done, uint64_t passes) {
+    Progressive* p = (Progressive*)frame;
+    if (!rgb_sum || !sq_sum) return set_err("null argument");
+    if (moments_frame(p)) return -1;
+    if (samples_done > 0xFFFFFFFFull) return set_err("samples_done must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
+    if (passes > samples_done) return set_err("passes must be <= samples_done: a pass holds at least one sample");
+    if ((samples_done == 0) != (passes == 0)) return set_err("samples_done = 0 and passes = 0 go together: a checkpoint is the sums, the second moments, the sample count AND the pass count");
+    if (samples_done == 0) {
+        const size_t n = p->n_px() * 3;
+        for (size_t i = 0; i < n; i++) {
+            uint64_t w, v; std::memcpy(&w, rgb_sum + i, sizeof(w)); std::memcpy(&v, sq_sum + i, sizeof(v));
+            if ((w | v) != 0) return set_err("samples_done = 0 with a non-zero frame: a checkpoint is the sums, the second moments, the sample count AND the pass count");
+        }
+    }
+    if (progressive_restart(p, rgb_sum, samples_done)) return -1;
+    DeviceGuard guard(p->device);
+    HIP_OK(hipMemcpy(p->d_sq, sq_sum, p->n_px() * 3 * sizeof(double), hipMemcpyHostToDevice));
+    p->passes = passes; p->moments_valid = true;
+    return 0;
+}
+int rt_progressive_error_map_device(void* frame, void** d_e2_out, void* hip_stream) {
+    Progressive* p = (Progressive*)frame;
+    if (moments_error_ready(p)) return -1;
+    DeviceGuard guard(p->device);
+    if (!p->d_e2) HIP_OK(hipMalloc(&p->d_e2, p->n_px() * sizeof(double)));
+    HIP_OK((hipError_t)launch_moments_error((const double*)p->d_sum, (const double*)p->d_sq, p->done, p->passes, (uint32_t)p->n_px(), (double*)p->d_e2, 0.0, nullptr, hip_stream));
+    if (d_e2_out) *d_e2_out = p->d_e2;
+    return 0;
+}
+int rt_progressive_error_map(void* frame, double* e2_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!e2_out) return set_err("null argument");
+    if (moments_error_ready(p)) return -1;
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the estimate
+    if (rt_progressive_error_map_device(frame, nullptr, nullptr)) return -1;
+    HIP_OK(hipMemcpy(e2_out, p->d_e2, p->n_px() * sizeof(double), hipMemcpyDeviceToHost));      // (waits for the kernel: the null stream)
+    return 0;
+}
+int rt_progressive_error_stats(void* frame, double tau, uint64_t stats_out[4]) {
+    Progressive* p = (Progressive*)frame;
+    if (!stats_out) return set_err("null argument");
+    if (moments_error_ready(p)) return -1;
+    const std::string problem = moments_tau_check(tau);
+    if (!problem.empty()) return set_err(problem);
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemsetAsync(p->d_mstats, 0, MOMENTS_STATS_WORDS * sizeof(uint64_t), nullptr));
+    HIP_OK((hipError_t)launch_moments_error((const double*)p->d_sum, (const double*)p->d_sq, p->done, p->passes, (uint32_t)p->n_px(), nullptr, tau * tau,
+                                            (unsigned long long*)p->d_mstats, nullptr));
+    HIP_OK(hipMemcpy(stats_out, p->d_mstats, MOMENTS_STATS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // ---------------------------------------------------------------- denoiser (csrc/rt_denoise.h: the specification; rt_denoise.hip: the kernels)

@@ -5,7 +5,7 @@
 //
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
 //              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material|albedo FILE] [--panorama FILE]
-//              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] [--denoise-albedo N] > image.ppm
+//              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] [--denoise-albedo N] [--until-error TAU] [--max-samples M] [--aov error FILE] > image.ppm
 //
 // --denoise K[,c,n,p] (opt-in): the frame through the edge-avoiding a-trous filter before it is written (rt_denoise: K iterations, guided by
 // sample 0's camera hits of this --seed); with --progressive the frame resolves itself denoised on the device (rt_progressive_resolve_denoised_rgb8).
@@ -14,6 +14,11 @@
 //
 // --progressive N (opt-in, one GPU): the frame in passes of N samples per pixel (rt_progressive_*), the reference's style of progress on
 // stderr (main.rs:772-775), and the same PPM bytes at the end, built from the image the device resolved.
+//
+// --until-error TAU [--max-samples M] (with --progressive N): the frame keeps moments (rt_progressive_enable_moments) and stops at the first
+// pass — the second at the earliest — after which no pixel's estimated standard error exceeds TAU display units (1/256 = 0.00390625 is one code
+// value), at the latest after M samples per pixel (default: --spp); the progress line carries the three pixel counts.
+// --aov error FILE (with --progressive N, beside the frame): the frame's error map when it ends (rt_progressive_error_map).
 //
 // --aov KIND FILE (opt-in, one GPU, instead of the frame): a feature frame for a denoiser or a compositor — the closest hit of sample 0's
 // camera ray of every pixel (rt_query_camera: the ray the frame traces for that sample) as a P3 PPM in FILE ("-": stdout); AOV_HELP has the mappings.
@@ -237,7 +242,9 @@ static const char* AOV_HELP =
     "                255.999 truncated; a miss is 0\n"
     "      material  grey, the hit's material handle mod 256 (a miss or a ConstantMedium hit, handle -1: 255)\n"
     "      albedo    r g b = the first hit's albedo held to [0, 1], times 255.999, truncated (no gamma); the mean over the samples [0, N) of\n"
-    "                --denoise-albedo N when that is given, else sample 0's (a miss, glass and emitters: 255 255 255)\n";
+    "                --denoise-albedo N when that is given, else sample 0's (a miss, glass and emitters: 255 255 255)\n"
+    "      error     (with --progressive N, written BESIDE the image when the frame ends) grey, the estimated standard error of the pixel in\n"
+    "                display units: sqrt(e2) * 256 * 8 truncated, held to 255 — one code value of standard error is grey 8; not finite: 255\n";
 
 // One channel value of the mappings above (a NaN gives 0)
 static unsigned aov_level(double x) { return x >= 0.0 ? (x > 255.0 ? 255u : (unsigned)x) : 0u; }
@@ -246,6 +253,14 @@ static void write_albedo_aov(const std::string& path, const std::vector<double>&
     for (size_t i = 0; i < albedo_sum.size(); i++) {
         const double a = albedo_sum[i] / (double)n_samples;
         img[i] = (uint8_t)aov_level((a >= 0.0 ? (a > 1.0 ? 1.0 : a) : 0.0) * 255.999);
+    }
+    write_ppm_rgb8(path.c_str(), img, W, H);
+}
+static void write_error_aov(const std::string& path, const std::vector<double>& e2, uint32_t W, uint32_t H) {
+    std::vector<uint8_t> img(e2.size() * 3);
+    for (size_t p = 0; p < e2.size(); p++) {
+        const uint8_t g = (uint8_t)(e2[p] - e2[p] == 0.0 ? aov_level(std::sqrt(e2[p]) * 256.0 * 8.0) : 255u);
+        img[p * 3] = img[p * 3 + 1] = img[p * 3 + 2] = g;
     }
     write_ppm_rgb8(path.c_str(), img, W, H);
 }
@@ -278,6 +293,7 @@ int main(int argc, char** argv) {
     bool want_denoise = false; DenoiseSettings dn;                          // --denoise K[,sigma_c,sigma_n,sigma_p]: filter the frame before it is written
     uint32_t albedo_samples = 0;                                            // --denoise-albedo N: demodulate by the albedo of samples [0, N) (0: the plain filter)
     uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
+    double until_error = -1.0; uint32_t max_samples = 0;                    // --until-error TAU [--max-samples M]: stop when no pixel's standard error exceeds TAU
     int gpus = 1;                                                           // --gpus N: the first N devices (0 = all) through rt_render_multi
     std::string obj_path = "teapot.obj", earth_path = "earthmap.jpg";       // the reference's asset names (main.rs:248,491)
     for (int i = 1; i < argc; i++) {
@@ -303,9 +319,11 @@ int main(int argc, char** argv) {
         else if (a == "--progressive") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--progressive needs a pass size >= 1\n"); return 2; } progressive = (uint32_t)n; }
         else if (a == "--aov") {
             aov_kind = next(); aov_path = next();
-            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material" && aov_kind != "albedo") { std::fprintf(stderr, "--aov needs normal, depth, material or albedo\n%s", AOV_HELP); return 2; }
+            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material" && aov_kind != "albedo" && aov_kind != "error") { std::fprintf(stderr, "--aov needs normal, depth, material, albedo or error\n%s", AOV_HELP); return 2; }
         }
         else if (a == "--panorama") panorama_path = next();
+        else if (a == "--until-error") { until_error = std::atof(next()); if (!(until_error >= 0.0)) { std::fprintf(stderr, "--until-error needs a standard error >= 0 in display units (0.00390625 is one code value)\n"); return 2; } }
+        else if (a == "--max-samples") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--max-samples needs a sample count >= 1\n"); return 2; } max_samples = (uint32_t)n; }
         else if (a == "--denoise") {
             const std::string v = next();
             unsigned k = 0; double c = dn.sigma[0], n = dn.sigma[1], p = dn.sigma[2];
@@ -321,6 +339,8 @@ int main(int argc, char** argv) {
                         "                                     the camera hits of sample 0 (default sigmas 4, 0.5, 0.02; inf switches a stop off); also with --progressive\n"
                         "  --denoise-albedo N                 with --denoise: filter the frame divided by its first-hit albedo (the mean over samples 0 .. N-1)\n"
                         "                                     and multiply back: textures are kept (textured scenes need it); also with --progressive\n"
+                        "  --until-error TAU [--max-samples M]  with --progressive N: stop at the first pass after which no pixel's estimated standard error\n"
+                        "                                     exceeds TAU display units (0.00390625 = one code value), at the latest after M samples (default --spp)\n"
                         "  --panorama FILE                    write the 2:1 equirectangular image (width x width/2) of everything around the scene's\n"
                         "                                     lookfrom instead of the image: --spp samples per ray, --depth, the scene's background\n", AOV_HELP);
             return 0;
@@ -329,6 +349,8 @@ int main(int argc, char** argv) {
         else if (a == "--fast-bvh") { fast_bvh = true; flags |= RT_NEAR_FIRST_BVH; }      // opt-in, not the reference's tree / visiting order
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
+    if ((until_error >= 0.0 || max_samples != 0u || aov_kind == "error") && progressive == 0u) { std::fprintf(stderr, "--until-error, --max-samples and --aov error go with --progressive N\n"); return 2; }
+    if (max_samples != 0u && until_error < 0.0) { std::fprintf(stderr, "--max-samples goes with --until-error TAU\n"); return 2; }
     if (albedo_samples != 0u && !want_denoise && aov_kind != "albedo") { std::fprintf(stderr, "--denoise-albedo goes with --denoise K (or --aov albedo)\n"); return 2; }
     const double aspect_ratio = (double)image_width / (double)image_height;
     try {
@@ -394,7 +416,7 @@ int main(int argc, char** argv) {
             break;
         }
         }
-        if (!aov_kind.empty()) {
+        if (!aov_kind.empty() && aov_kind != "error") {
             if (flags & RT_F32) throw Error("--aov runs in f64");
             if (aov_kind == "albedo") {
                 const uint32_t n = albedo_samples ? albedo_samples : 1u;
@@ -418,11 +440,23 @@ int main(int argc, char** argv) {
         if (progressive) {
             if (gpus != 1 || (flags & RT_MULTI_COLLECTIVE)) throw Error("--progressive renders on one GPU");
             Progressive frame(s, camera, background, image_width, image_height, max_depth, seed, flags);
-            while (frame.samples() < samples_per_pixel) {
-                frame.add((uint32_t)std::min<uint64_t>(progressive, samples_per_pixel - frame.samples()));
-                std::fprintf(stderr, "\rSamples: %llu / %u", (unsigned long long)frame.samples(), samples_per_pixel);    // main.rs:772-775
+            const bool want_moments = until_error >= 0.0 || aov_kind == "error";
+            if (want_moments) frame.enable_moments();
+            const uint32_t limit = until_error >= 0.0 && max_samples ? max_samples : samples_per_pixel;
+            while (frame.samples() < limit) {
+                frame.add((uint32_t)std::min<uint64_t>(progressive, limit - frame.samples()));
+                std::fprintf(stderr, "\rSamples: %llu / %u", (unsigned long long)frame.samples(), limit);    // main.rs:772-775
+                if (until_error >= 0.0 && frame.passes() >= 2) {
+                    const ErrorStats st = frame.error_stats(until_error);
+                    std::fprintf(stderr, "  converged %llu  unconverged %llu  nonfinite %llu", (unsigned long long)st.converged, (unsigned long long)st.unconverged, (unsigned long long)st.nonfinite);
+                    if (st.unconverged == 0) break;
+                }
             }
             std::fprintf(stderr, "\n");
+            if (aov_kind == "error") {
+                if (frame.passes() < 2) throw Error("--aov error needs at least two passes: --spp must be more than the pass size of --progressive");
+                write_error_aov(aov_path, frame.error_map(), image_width, image_height);
+            }
             write_ppm_rgb8("-", want_denoise ? (albedo_samples ? frame.rgb8_denoised_albedo(albedo_samples, dn) : frame.rgb8_denoised(dn)) : frame.rgb8(), image_width, image_height);     // main.rs:767-769,832
             std::fprintf(stderr, "Done.\n");                                                    // main.rs:835
             return 0;

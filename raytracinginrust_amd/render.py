@@ -299,9 +299,17 @@ class Progressive:
             while frame.samples < 1024:
                 frame.add(64)
                 image, changed = frame.rgb8()        # (H, W, 3) uint8 and the pixels that differ from the previous resolve
+
+    moments=True (rt_progressive_enable_moments) also keeps the second moment of the pass sums, from which `error_map` and `error_stats`
+    estimate every pixel's standard error in display units once two passes are in (csrc/rt_moments.h):
+
+        with Progressive(b, cam, bg, W, H, max_depth, moments=True) as frame:
+            while frame.passes < 2 or frame.error_stats(1 / 256)["unconverged"]:
+                frame.add(64)
     """
 
-    def __init__(self, b: SceneBuilder, cam: CameraParams, background, W: int, H: int, max_depth: int, seed: int = 0x5EED, flags: int = RT_F64):
+    def __init__(self, b: SceneBuilder, cam: CameraParams, background, W: int, H: int, max_depth: int, seed: int = 0x5EED, flags: int = RT_F64,
+                 moments: bool = False):
         self._lib = _rt()
         self.W, self.H = int(W), int(H)
         bg = (C.c_double * 3)(*[float(x) for x in background])
@@ -309,6 +317,60 @@ class Progressive:
         if not self._h:
             raise RenderError(_err())
         self._builder = b              # the scene stays alive at least as long as the frame
+        self.has_moments = False
+        if moments:
+            self.enable_moments()
+
+    def enable_moments(self) -> None:
+        """rt_progressive_enable_moments: only while the frame holds 0 samples; 48 more bytes per pixel."""
+        _check(self._lib.rt_progressive_enable_moments(self._h))
+        self.has_moments = True
+
+    @property
+    def passes(self) -> int:
+        """Passes merged so far (0 on a frame without moments)."""
+        n = C.c_uint64()
+        _check(self._lib.rt_progressive_passes(self._h, C.byref(n)))
+        return int(n.value)
+
+    def sq_sum(self) -> np.ndarray:
+        """The second moments of the pass sums, (H, W, 3) f64 (rt_progressive_read_moments)."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.float64)
+        _check(self._lib.rt_progressive_read_moments(self._h, out.ctypes.data))
+        return out
+
+    def error_map(self) -> np.ndarray:
+        """e2 of every pixel, (H, W) f64: the squared standard error of the displayed value sqrt(mean), the largest of the three channels
+        (csrc/rt_moments.h); needs two passes."""
+        out = np.zeros((self.H, self.W), dtype=np.float64)
+        _check(self._lib.rt_progressive_error_map(self._h, out.ctypes.data))
+        return out
+
+    def error_map_device(self, stream: int = 0) -> int:
+        """Enqueue the error kernel on a HIP stream; returns the DEVICE address of the W*H doubles (owned by the frame)."""
+        ptr = C.c_void_p()
+        _check(self._lib.rt_progressive_error_map_device(self._h, C.byref(ptr), C.c_void_p(stream)))
+        return int(ptr.value or 0)
+
+    def error_stats(self, tau: float) -> dict:
+        """Pixels whose standard error is <= tau / > tau / not finite, and the largest finite e2 (see `moments_stats`)."""
+        words = (C.c_uint64 * 4)()
+        _check(self._lib.rt_progressive_error_stats(self._h, float(tau), words))
+        return moments_stats(words, tau)
+
+    def checkpoint(self) -> dict:
+        """Everything `restore` needs: the sums, the sample count and — with moments — the second moments and the pass count."""
+        return {"rgb_sum": self.sum(), "samples": self.samples, "passes": self.passes, "sq_sum": self.sq_sum() if self.has_moments else None}
+
+    def restore(self, ck: dict) -> None:
+        """Resume from `checkpoint()`: with second moments into a frame with moments (rt_progressive_load_moments), else the sums alone."""
+        if ck.get("sq_sum") is None:
+            return self.load(ck["rgb_sum"], ck["samples"])
+        a = np.ascontiguousarray(ck["rgb_sum"], dtype=np.float64)
+        q = np.ascontiguousarray(ck["sq_sum"], dtype=np.float64)
+        if a.shape != (self.H, self.W, 3) or q.shape != a.shape:
+            raise ValueError(f"checkpoint of shapes {a.shape}, {q.shape} for a frame of {(self.H, self.W, 3)}")
+        _check(self._lib.rt_progressive_load_moments(self._h, a.ctypes.data, q.ctypes.data, int(ck["samples"]), int(ck["passes"])))
 
     def add(self, n: int, want_samples: bool = False):
         """One synchronous pass of n samples per pixel; with want_samples returns them, (H, W, n, 3) as `render` lays them out."""
@@ -407,10 +469,19 @@ DEFAULT_PASS_SPP = 64
 
 
 def render_progressive(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, spp: int, max_depth: int, passes=None,
-                       seed: int = 0x5EED, flags: int = RT_F64):
+                       seed: int = 0x5EED, flags: int = RT_F64, until_error=None, min_passes: int = 2, max_samples=None):
     """Generator: renders `spp` samples per pixel in passes and yields (samples_done, rgb8, changed_px) after each; the last item is the
     full frame — the image `format_image(render(..., spp), spp)` gives.  passes: None (passes of DEFAULT_PASS_SPP), an int (that many
-    passes of equal size, the remainder in the first ones), or a sequence of pass sizes that sums to spp."""
+    passes of equal size, the remainder in the first ones), or a sequence of pass sizes that sums to spp.
+
+    until_error=tau: a frame with moments that stops at the first pass — not before min_passes (>= 2) — after which no pixel's estimated
+    standard error exceeds tau (display units: 1/256 is one code value), at the latest after max_samples (default: spp, which `passes`
+    then divides) samples.  Every item is then (samples_done, rgb8, changed_px, stats): the dict of `Progressive.error_stats(tau)`, None
+    while the frame holds fewer than two passes."""
+    if until_error is not None:
+        if min_passes < 2:
+            raise ValueError("min_passes must be >= 2: the error is estimated from the spread between passes")
+        spp = spp if max_samples is None else int(max_samples)
     if passes is None:
         sizes = [DEFAULT_PASS_SPP] * (spp // DEFAULT_PASS_SPP) + ([spp % DEFAULT_PASS_SPP] if spp % DEFAULT_PASS_SPP else [])
     elif isinstance(passes, int):
@@ -421,11 +492,17 @@ def render_progressive(b: SceneBuilder, cam: CameraParams, background, W: int, H
         sizes = [int(n) for n in passes]
         if sum(sizes) != spp or min(sizes, default=0) < 1:
             raise ValueError("pass sizes must be >= 1 and sum to spp")
-    with Progressive(b, cam, background, W, H, max_depth, seed, flags) as frame:
+    with Progressive(b, cam, background, W, H, max_depth, seed, flags, moments=until_error is not None) as frame:
         for n in sizes:
             frame.add(n)
             image, changed = frame.rgb8()
-            yield frame.samples, image, changed
+            if until_error is None:
+                yield frame.samples, image, changed
+                continue
+            stats = frame.error_stats(until_error) if frame.passes >= 2 else None
+            yield frame.samples, image, changed, stats
+            if stats is not None and frame.passes >= min_passes and stats["unconverged"] == 0:
+                return
 
 
 def render_multi(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, spp: int, max_depth: int, device_mask: int = 0,
@@ -826,6 +903,71 @@ def denoise_albedo_device(d_rgb_sum, samples: int, d_albedo_sum, albedo_samples:
     _check(_rt().rt_denoise_albedo_device(C.c_void_p(sum_ptr), int(samples), C.c_void_p(alb_ptr), int(albedo_samples), C.c_void_p(hits_ptr), W, H, k, sg,
                                           flags, C.c_void_p(out_ptr), C.c_void_p(ws_ptr), nbytes, C.c_void_p(stream)))
     return d_workspace
+
+
+# ---- moments (rt_moments_*, csrc/rt_moments.h): the second moment of pass sums and the per-pixel error estimate of a frame of passes
+def moments_stats(words, tau: float) -> dict:
+    """The four words of rt_moments_stats_host / rt_moments_error_device / rt_progressive_error_stats as a dict: the three pixel counts,
+    max_e2 (the largest finite e2, a float), max_error = sqrt(max_e2) in display units, and tau."""
+    w = [int(x) for x in words]
+    max_e2 = float(np.array([w[3]], dtype=np.uint64).view(np.float64)[0])
+    return {"converged": w[0], "unconverged": w[1], "nonfinite": w[2], "max_e2": max_e2, "max_error": math.sqrt(max_e2), "tau": float(tau)}
+
+
+def moments_merge_host(pass_sum, n_samples: int, rgb_sum: np.ndarray, sq_sum: np.ndarray) -> None:
+    """rt_moments_merge_host (no GPU): merges the pass frame `pass_sum` of n_samples samples per pixel into rgb_sum and sq_sum IN PLACE
+    (C-contiguous f64 arrays of pass_sum's size): S += p, Q += p * p / n_samples."""
+    p = np.ascontiguousarray(pass_sum, dtype=np.float64)
+    for a in (rgb_sum, sq_sum):
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous and a.size == p.size):
+            raise ValueError("rgb_sum and sq_sum are merged in place: C-contiguous float64 arrays of pass_sum's size")
+    _check(_rt().rt_moments_merge_host(p.ctypes.data, int(n_samples), rgb_sum.ctypes.data, sq_sum.ctypes.data, p.size))
+
+
+def _moments_frames(rgb_sum, sq_sum):
+    s = np.ascontiguousarray(rgb_sum, dtype=np.float64)
+    q = np.ascontiguousarray(sq_sum, dtype=np.float64)
+    if s.ndim != 3 or s.shape[2] != 3 or q.shape != s.shape:
+        raise ValueError(f"rgb_sum of shape {s.shape} and sq_sum of shape {q.shape}: want (H, W, 3) twice")
+    return s, q
+
+
+def moments_error_host(rgb_sum, sq_sum, samples: int, passes: int) -> np.ndarray:
+    """rt_moments_error_host (no GPU): e2 of every pixel, (H, W), from (H, W, 3) sums and second moments of `passes` passes holding
+    `samples` samples per pixel."""
+    s, q = _moments_frames(rgb_sum, sq_sum)
+    out = np.zeros(s.shape[:2], dtype=np.float64)
+    _check(_rt().rt_moments_error_host(s.ctypes.data, q.ctypes.data, int(samples), int(passes), s.shape[1], s.shape[0], out.ctypes.data))
+    return out
+
+
+def moments_stats_host(e2, tau: float) -> dict:
+    """rt_moments_stats_host (no GPU): `moments_stats` of an error map for the threshold tau."""
+    e = np.ascontiguousarray(e2, dtype=np.float64)
+    words = (C.c_uint64 * 4)()
+    _check(_rt().rt_moments_stats_host(e.ctypes.data, e.size, float(tau), words))
+    return moments_stats(words, tau)
+
+
+def moments_merge_device(d_pass_sum, n_samples: int, d_rgb_sum, d_sq_sum, n_doubles=None, stream: int = 0) -> None:
+    """rt_moments_merge_device: the merge for frames in device memory (torch tensors of f64, or raw pointers with n_doubles), enqueued on
+    `stream`; never waits; d_pass_sum is all +0.0 afterwards."""
+    p_ptr, nbytes = _device_buffer(d_pass_sum)
+    n = nbytes // 8 if n_doubles is None and nbytes is not None else n_doubles
+    if n is None:
+        raise ValueError("n_doubles is needed with a raw pointer")
+    _check(_rt().rt_moments_merge_device(C.c_void_p(p_ptr), int(n_samples), C.c_void_p(_device_buffer(d_rgb_sum)[0]),
+                                         C.c_void_p(_device_buffer(d_sq_sum)[0]), int(n), C.c_void_p(stream)))
+
+
+def moments_error_device(d_rgb_sum, d_sq_sum, samples: int, passes: int, W: int, H: int, d_e2_out=None, tau: float = 0.0, d_stats_out=None,
+                         stream: int = 0) -> None:
+    """rt_moments_error_device: the error map (d_e2_out, W*H f64) and / or the four statistics words for tau (d_stats_out, 4 x int64 /
+    uint64; read them with `moments_stats`), for frames in device memory, enqueued on `stream`; never waits."""
+    e2_ptr = None if d_e2_out is None else _device_buffer(d_e2_out)[0]
+    st_ptr = None if d_stats_out is None else _device_buffer(d_stats_out)[0]
+    _check(_rt().rt_moments_error_device(C.c_void_p(_device_buffer(d_rgb_sum)[0]), C.c_void_p(_device_buffer(d_sq_sum)[0]), int(samples), int(passes),
+                                         W, H, C.c_void_p(e2_ptr), float(tau), C.c_void_p(st_ptr), C.c_void_p(stream)))
 
 
 def kernel_time_total(b: SceneBuilder, reset: bool = False):
