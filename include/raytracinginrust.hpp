@@ -317,6 +317,29 @@ inline std::vector<double> moments_error(const std::vector<double>& rgb_sum, con
     if (stats) { uint64_t w[4]; if (rt_moments_stats_host(e2.data(), e2.size(), tau, w) != 0) throw Error(rt_last_error()); *stats = ErrorStats::from_words(w); }
     return e2;
 }
+// The variance of the mean of every pixel and channel (W*H*3 doubles; rt_moments_variance_host, csrc/rt_moments.h (4)): the V that e2 is
+// computed from, and what `denoise_variance` takes as its input.  The host form: no device needed.
+inline std::vector<double> moments_variance(const std::vector<double>& rgb_sum, const std::vector<double>& sq_sum, uint64_t samples, uint64_t passes,
+                                            uint32_t W, uint32_t H) {
+    if (rgb_sum.size() != (size_t)W * H * 3 || sq_sum.size() != rgb_sum.size()) throw Error("moments_variance: frames of another size");
+    std::vector<double> var(rgb_sum.size());
+    if (rt_moments_variance_host(rgb_sum.data(), sq_sum.data(), samples, passes, W, H, var.data()) != 0) throw Error(rt_last_error());
+    return var;
+}
+// Variance-guided denoising (rt_denoise_variance, csrc/rt_denoise_var.h): `denoise` with its colour stop measured in standard deviations of
+// the two pixels a tap compares, from `var` (moments_variance, Progressive::variance).  sigma = {sigma_v, sigma_n, sigma_p}; the default
+// sigma_v is render.py's.  var_out (optional): the filtered variance, W*H doubles.
+struct DenoiseVarianceSettings {
+    uint32_t iterations = 2; double sigma[3] = {3.0, 0.5, 0.02}; uint32_t flags = 0;
+};
+inline std::vector<double> denoise_variance(const std::vector<double>& rgb_sum, uint64_t samples, const std::vector<double>& var, const std::vector<double>& hit_records,
+                                            uint32_t W, uint32_t H, const DenoiseVarianceSettings& d = DenoiseVarianceSettings(), std::vector<double>* var_out = nullptr) {
+    if (rgb_sum.size() != (size_t)W * H * 3 || var.size() != rgb_sum.size() || hit_records.size() != (size_t)W * H * 16) throw Error("denoise_variance: frame, variance or records of another size");
+    std::vector<double> out(rgb_sum.size());
+    if (var_out) var_out->resize((size_t)W * H);
+    if (rt_denoise_variance(rgb_sum.data(), samples, var.data(), hit_records.data(), W, H, d.iterations, d.sigma, d.flags, out.data(), var_out ? var_out->data() : nullptr) != 0) throw Error(rt_last_error());
+    return out;
+}
 
 // A progressive frame (rt_progressive_*): the same loop in passes of samples that accumulate on the device, with the reference's
 // format_color (src/vec.rs:125-131) resolved there too — progress, preview, stop half-way, "another 1000 samples", save and resume.
@@ -356,6 +379,11 @@ public:
     }
     std::vector<double> error_map() { std::vector<double> out(n_px_); chk(rt_progressive_error_map(p_, out.data())); return out; }      // e2, W*H doubles
     ErrorStats error_stats(double tau) { uint64_t w[4]; chk(rt_progressive_error_stats(p_, tau, w)); return ErrorStats::from_words(w); }
+    std::vector<double> variance() { std::vector<double> out(n_px_ * 3); chk(rt_progressive_variance(p_, out.data())); return out; }    // the variance of the mean, W*H*3 doubles
+    // the frame as it is now through `denoise_variance`, guided by its own variance, and format_color, all on the device; needs moments and two passes
+    std::vector<uint8_t> rgb8_denoised_variance(const DenoiseVarianceSettings& d = DenoiseVarianceSettings()) {
+        std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_denoised_variance_rgb8(p_, d.iterations, d.sigma, d.flags, out.data())); return out;
+    }
 private:
     static void chk(int rc) { if (rc != 0) throw Error(rt_last_error()); }
     void* p_; size_t n_px_;

@@ -290,6 +290,16 @@ int rt_progressive_load_moments(void* frame, const double* rgb_sum, const double
 int rt_progressive_error_map(void* frame, double* e2_out);
 int rt_progressive_error_map_device(void* frame, void** d_e2_out, void* hip_stream);
 int rt_progressive_error_stats(void* frame, double tau, uint64_t stats_out[4]);
+/* The variance of the mean of every pixel and channel, V above, as a frame of its own (W*H*3 doubles, output order; csrc/rt_moments.h (4)) —
+ * what the variance-guided denoiser below (rt_denoise_variance*) takes as its input.  e2 is computed from this very V.  A channel whose
+ * state is not finite has V = 0, except for a +inf in Q, which gives +inf.  The host form needs no device; the device form only enqueues
+ * on hip_stream (8-byte aligned buffers, d_var_out neither input; 16-byte accesses when all three are 16-byte aligned), never waits, never
+ * allocates; rt_progressive_variance is the device form on the frame's own sums, into a buffer of the frame's own (24 more bytes per pixel,
+ * allocated at the first call), copied out; it waits for every pass enqueued so far.  Errors: those of the error calls above. */
+int rt_moments_variance_host(const double* rgb_sum, const double* sq_sum, uint64_t samples, uint64_t passes, uint32_t W, uint32_t H, double* var_out);
+int rt_moments_variance_device(const void* d_rgb_sum, const void* d_sq_sum, uint64_t samples, uint64_t passes, uint32_t W, uint32_t H,
+                               void* d_var_out, void* hip_stream);
+int rt_progressive_variance(void* frame, double* var_out);
 
 /* ---- ray queries: the reference's `world.hit(r, 0.00001, f64::INFINITY)` (src/main.rs:48, Hittable::hit) as a function of its own — the
  *      closest hit of rays the caller chooses, or of the camera rays of one sample of every pixel: which object is under pixel (i, j), how far
@@ -448,6 +458,37 @@ int rt_denoise_albedo_device(const void* d_rgb_sum, uint64_t samples, const void
 int rt_progressive_resolve_denoised_albedo_rgb8(void* frame, uint32_t albedo_samples, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out);
 int rt_progressive_albedo_info(void* frame, uint32_t* albedo_samples_out, uint64_t* builds_out);
 
+/* ---- variance-guided denoising: the filter of rt_denoise with a colour stop measured in standard deviations of the two pixels it compares
+ *      (the variance-guided a-trous filter of SVGF, Schied et al. 2017), so that no sigma_c has to be tuned per scene or per sample count.
+ *      var: W*H*3 doubles, the variance of the mean of every pixel and channel (rt_moments_variance*); the filter uses their sum v per pixel
+ *      (a NaN, an infinity, a negative or a zero sum counts as 0), smooths it once over 3 x 3 pixels of the same key, and in every iteration
+ *      weights a tap by  wc = max(1 - |c_q - c_p|^2 / (sigma_v^2 (v_p + v_q + 2^-16)), 0)^2  beside the unchanged normal, plane and key
+ *      stops, and filters v along with the colour (sum of w^2 v over the square of the sum of w): the stop tightens as the picture gets
+ *      cleaner, and there is no 4^i schedule.  csrc/rt_denoise_var.h is the exact specification — + - * / and comparisons in a fixed order —
+ *      which the HIP kernels (csrc/rt_denoise_var.hip) and the host twin satisfy bit for bit.
+ * sigma = {sigma_v, sigma_n, sigma_p}: sigma_v is dimensionless (standard deviations); +inf switches a stop off, and with sigma_v = +inf the
+ * filtered colours are the words of rt_denoise with sigma_c = +inf.  var_out: W*H doubles or NULL, the filtered v — the variance of the
+ * filtered mean, were the taps independent.  The other arguments, the errors (plus a null var) and the three forms are those of
+ * rt_denoise_host / rt_denoise / rt_denoise_device; the workspace is rt_denoise_variance_workspace_bytes(W, H) = 128 bytes per pixel;
+ * d_var and d_var_out are 8-byte aligned, d_var is only read.
+ * Not done: the combination with albedo demodulation (per-channel V / albedo^2 — which is why var is per channel), temporal accumulation,
+ * variance gathered inside the path-tracing kernels, rt_render_multi. */
+int rt_denoise_variance_host(const double* rgb_sum, uint64_t samples, const double* var, const double* hits, uint32_t W, uint32_t H,
+                             uint32_t iterations, const double sigma[3], uint32_t flags, double* rgb_sum_out, double* var_out);
+int rt_denoise_variance(const double* rgb_sum, uint64_t samples, const double* var, const double* hits, uint32_t W, uint32_t H,
+                        uint32_t iterations, const double sigma[3], uint32_t flags, double* rgb_sum_out, double* var_out);
+size_t rt_denoise_variance_workspace_bytes(uint32_t W, uint32_t H);
+int rt_denoise_variance_device(const void* d_rgb_sum, uint64_t samples, const void* d_var, const void* d_hits, uint32_t W, uint32_t H,
+                               uint32_t iterations, const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_var_out,
+                               void* d_workspace, size_t workspace_bytes, void* hip_stream);
+/* rt_progressive_resolve_denoised_rgb8 with the frame's own variance: byte for byte rt_format_color of rt_denoise_variance_host(
+ * rt_progressive_read_sum, rt_progressive_samples, rt_moments_variance_host(the sums, rt_progressive_read_moments, samples, passes),
+ * rt_query_camera(sample 0, the frame's seed)).  The variance, the filter and the resolve run on the device; the guide is the one the frame
+ * packs once for all its denoised resolves.  The accumulated sums, the second moments, the pass count and what the other resolves own are
+ * untouched.  Errors: those of rt_progressive_resolve_denoised_rgb8, and a frame without moments, with invalid moments or with fewer than
+ * two passes. */
+int rt_progressive_resolve_denoised_variance_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out);
+
 /* The whole frame on several GPUs of this node from ONE call: what a host that owns the node's GPUs itself (the reference's `main`,
  * src/main.rs:767-835) calls instead of rt_render.  device_mask: bit d selects HIP device d (0 = every visible device).  The scene
  * is replicated on each selected device; tiles of tile_px output-order pixels (0 = the default, 67) are dealt round-robin, each
@@ -548,6 +589,10 @@ int rt_debug_section_cycles(rt_scene*, unsigned long long out8[8]);
  * launches: ms_out[0] = the pack kernel, ms_out[1 + i] = iteration i (iterations + 1 floats). */
 int rt_debug_denoise_ms(const void* d_rgb_sum, uint64_t samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
                         const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, float* ms_out);
+/* The same for rt_denoise_variance_device (d_var_out NULL): ms_out[0] = the guide and colour packs, ms_out[1] = the 3 x 3 prefilter of v,
+ * ms_out[2 + i] = iteration i (iterations + 2 floats). */
+int rt_debug_denoise_variance_ms(const void* d_rgb_sum, uint64_t samples, const void* d_var, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
+                                 const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, float* ms_out);
 /* Measuring aid (tools/denoise_probe.py): the two element-wise kernels of rt_denoise_albedo_device on the null stream, synchronously, once to
  * warm up and once with HIP events between them: ms_out[0] = demodulate (d_rgb_sum, d_albedo_sum -> d_x), ms_out[1] = remodulate (d_x in place).
  * DEVICE pointers of n_doubles doubles (3 per pixel), 8-byte aligned. */

@@ -117,6 +117,9 @@ SIGNATURES = {
     "progressive_error_map": (_int, [_ptr, _ptr]),
     "progressive_error_map_device": (_int, [_ptr, c_void_pp, _ptr]),
     "progressive_error_stats": (_int, [_ptr, _f64, c_u64_p]),
+    "moments_variance_host": (_int, [_ptr, _ptr, _u64, _u64, _u32, _u32, _ptr]),
+    "moments_variance_device": (_int, [_ptr, _ptr, _u64, _u64, _u32, _u32, _ptr, _ptr]),
+    "progressive_variance": (_int, [_ptr, _ptr]),
     # ray queries
     "camera_ray": (_int, [_cam_p, _u32, _u32, _u32, _u32, _u64, _u32, c_double_p]),
     "query_hits": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _ptr]),
@@ -142,6 +145,11 @@ SIGNATURES = {
     "denoise_albedo_device": (_int, [_ptr, _u64, _ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, C.c_size_t, _ptr]),
     "progressive_resolve_denoised_albedo_rgb8": (_int, [_ptr, _u32, _u32, c_double_p, _u32, _ptr]),
     "progressive_albedo_info": (_int, [_ptr, c_u32_p, c_u64_p]),
+    "denoise_variance_host": (_int, [_ptr, _u64, _ptr, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr]),
+    "denoise_variance": (_int, [_ptr, _u64, _ptr, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr]),
+    "denoise_variance_workspace_bytes": (C.c_size_t, [_u32, _u32]),
+    "denoise_variance_device": (_int, [_ptr, _u64, _ptr, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, _ptr, C.c_size_t, _ptr]),
+    "progressive_resolve_denoised_variance_rgb8": (_int, [_ptr, _u32, c_double_p, _u32, _ptr]),
     # radiance queries
     "query_radiance": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _ptr, _ptr, c_u64_p]),
     "query_radiance_device": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _u32, _int, _ptr, C.c_size_t, _ptr, _ptr, _ptr]),
@@ -169,6 +177,7 @@ SIGNATURES = {
     "last_leaf_steps": (_int, [_ptr, c_ull_p]),
     # test and diagnostic hooks
     "debug_denoise_ms": (_int, [_ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, C.c_size_t, c_float_p]),
+    "debug_denoise_variance_ms": (_int, [_ptr, _u64, _ptr, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, C.c_size_t, c_float_p]),
     "debug_albedo_modulate_ms": (_int, [_ptr, _ptr, _u64, _ptr, _u64, c_float_p]),
     "debug_section_cycles": (_int, [_ptr, c_ull_p]),
     "debug_tune_filter": (_int, [_ptr, _ptr]),

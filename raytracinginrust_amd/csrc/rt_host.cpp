@@ -23,6 +23,7 @@
 #define RT_ALBEDO_QUERIES
 #include "rt_albedo.h"
 #include "rt_moments.h"
+#include "rt_denoise_var.h"
 
 using namespace rt;
 
@@ -64,6 +65,9 @@ struct Progressive {
     bool moments = false, moments_valid = false, merge_recorded = false; uint64_t passes = 0;
     void* d_sq = nullptr; void* d_pass = nullptr; void* d_e2 = nullptr; void* d_mstats = nullptr;
     hipEvent_t ev_merged = nullptr;
+    // rt_progressive_variance / rt_progressive_resolve_denoised_variance_rgb8: the per-channel variance frame (rt_moments.h (4)) of the sums
+    // as they are at that call, allocated at the first one (24 bytes per pixel)
+    void* d_var = nullptr;
     size_t n_px() const { return (size_t)W * H; }
 };
 
@@ -1607,7 +1611,7 @@ static void progressive_free(Progressive* p) {
     free_dev(p->d_sum); free_dev(p->d_rgb8[0]); free_dev(p->d_rgb8[1]); free_dev(p->d_changed);
     free_dev(p->d_dn_ws); free_dev(p->d_dn_sum); free_dev(p->d_dn_rgb8); free_dev(p->d_dn_changed);
     free_dev(p->d_alb_sum); free_dev(p->d_alb_x);
-    free_dev(p->d_sq); free_dev(p->d_pass); free_dev(p->d_e2); free_dev(p->d_mstats);
+    free_dev(p->d_sq); free_dev(p->d_pass); free_dev(p->d_e2); free_dev(p->d_mstats); free_dev(p->d_var);
     if (p->ev_merged) { (void)hipEventDestroy(p->ev_merged); p->ev_merged = nullptr; }
 }
 void* rt_progressive_create(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t max_depth,
@@ -1898,6 +1902,32 @@ int rt_progressive_error_stats(void* frame, double tau, uint64_t stats_out[4]) {
     HIP_OK(hipMemcpy(stats_out, p->d_mstats, MOMENTS_STATS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return 0;
 }
+// (4) of rt_moments.h
+int rt_moments_variance_device(const void* d_rgb_sum, const void* d_sq_sum, uint64_t samples, uint64_t passes, uint32_t W, uint32_t H, void* d_var_out, void* hip_stream) {
+    if (!d_rgb_sum || !d_sq_sum || !d_var_out) return set_err("null argument");
+    const std::string problem = moments_error_check(samples, passes, W, H);
+    if (!problem.empty()) return set_err(problem);
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum | (uintptr_t)d_var_out) & 7u) != 0u) return set_err("d_rgb_sum, d_sq_sum and d_var_out must be 8-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    HIP_OK((hipError_t)launch_moments_variance((const double*)d_rgb_sum, (const double*)d_sq_sum, samples, passes, (uint64_t)W * H * 3u, (double*)d_var_out, hip_stream));
+    return 0;
+}
+// ... on the frame's own sums, into the frame's own variance frame, on `stream`
+static int progressive_variance_enqueue(Progressive* p, hipStream_t stream) {
+    if (!p->d_var) HIP_OK(hipMalloc(&p->d_var, p->n_px() * 3 * sizeof(double)));
+    HIP_OK((hipError_t)launch_moments_variance((const double*)p->d_sum, (const double*)p->d_sq, p->done, p->passes, (uint64_t)p->n_px() * 3u, (double*)p->d_var, stream));
+    return 0;
+}
+int rt_progressive_variance(void* frame, double* var_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!var_out) return set_err("null argument");
+    if (moments_error_ready(p)) return -1;
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the estimate
+    if (progressive_variance_enqueue(p, nullptr)) return -1;
+    HIP_OK(hipMemcpy(var_out, p->d_var, p->n_px() * 3 * sizeof(double), hipMemcpyDeviceToHost));      // (waits for the kernel: the null stream)
+    return 0;
+}
 
 // ---------------------------------------------------------------- denoiser (csrc/rt_denoise.h: the specification; rt_denoise.hip: the kernels)
 size_t rt_denoise_workspace_bytes(uint32_t W, uint32_t H) { return (size_t)W * H * DENOISE_WORKSPACE_BYTES_PER_PX; }
@@ -2012,6 +2042,100 @@ int rt_progressive_resolve_denoised_rgb8(void* frame, uint32_t iterations, const
     DeviceGuard guard(p->device);
     if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
     if (denoise_enqueue((const double*)p->d_sum, p->done, nullptr, p->W, p->H, iterations, sigma, flags, (double*)p->d_dn_sum, p->d_dn_ws, nullptr)) return -1;
+    return progressive_denoise_finish(p, rgb8_out);
+}
+
+// ---------------------------------------------------------------- variance-guided denoising (csrc/rt_denoise_var.h: the specification; rt_denoise_var.hip: the kernels)
+size_t rt_denoise_variance_workspace_bytes(uint32_t W, uint32_t H) { return rt_denoise_workspace_bytes(W, H); }
+
+// The launches of one run on `stream`, in denoise_enqueue's workspace {colour A, colour B, guide}: the guide when d_hits is given, the pack
+// into B, the prefilter of v from B to A, then the iterations alternating from A, the last one writing sums to d_out and v to d_var_out.
+static int denoise_variance_enqueue(const double* d_sum, uint64_t samples, const double* d_var, const double* d_hits, uint32_t W, uint32_t H,
+                                    uint32_t iterations, const double sigma[3], uint32_t flags, double* d_out, double* d_var_out, void* d_workspace,
+                                    hipStream_t stream, hipEvent_t* marks = nullptr) {
+    const size_t n = (size_t)W * H;
+    double* color[2] = {(double*)d_workspace, (double*)d_workspace + n * DENOISE_COLOR_DOUBLES};
+    double* guide = (double*)d_workspace + 2u * n * DENOISE_COLOR_DOUBLES;
+    double inv[3];
+    denoise_inverse_squares(sigma, inv);
+    const double kv = sigma[0] * sigma[0];
+    if (marks) HIP_OK(hipEventRecord(marks[0], stream));
+    if (d_hits) HIP_OK((hipError_t)launch_denoise_pack(nullptr, samples, d_hits, flags, nullptr, guide, (uint32_t)n, stream));
+    HIP_OK((hipError_t)launch_denoise_var_pack(d_sum, samples, d_var, color[1], (uint32_t)n, stream));
+    if (marks) HIP_OK(hipEventRecord(marks[1], stream));
+    HIP_OK((hipError_t)launch_denoise_var_prefilter(color[1], guide, color[0], W, H, stream));
+    for (uint32_t i = 0; i < iterations; i++) {
+        const bool last = i + 1u == iterations;
+        if (marks) HIP_OK(hipEventRecord(marks[i + 2u], stream));
+        HIP_OK((hipError_t)launch_denoise_var_filter(color[i & 1u], guide, last ? nullptr : color[(i + 1u) & 1u], last ? d_out : nullptr, last ? d_var_out : nullptr,
+                                                     W, H, 1u << i, kv, inv[1], inv[2], samples, stream));
+    }
+    if (marks) HIP_OK(hipEventRecord(marks[iterations + 2u], stream));
+    return 0;
+}
+int rt_denoise_variance_device(const void* d_rgb_sum, uint64_t samples, const void* d_var, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
+                               const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_var_out, void* d_workspace, size_t workspace_bytes,
+                               void* hip_stream) {
+    if (!d_rgb_sum || !d_var || !d_hits || !sigma || !d_rgb_sum_out || !d_workspace) return set_err("null argument");
+    const std::string problem = denoise_variance_check(samples, W, H, iterations, sigma, flags);
+    if (!problem.empty()) return set_err(problem);
+    if (workspace_bytes < rt_denoise_variance_workspace_bytes(W, H)) return set_err("denoise: workspace too small: rt_denoise_variance_workspace_bytes(W, H) = 128 bytes per pixel are needed");
+    if (query_aligned(d_hits, "d_hits") || query_aligned(d_workspace, "d_workspace")) return -1;
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_rgb_sum_out | (uintptr_t)d_var | (uintptr_t)d_var_out) & 7u) != 0u) return set_err("d_rgb_sum, d_var, d_rgb_sum_out and d_var_out must be 8-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    return denoise_variance_enqueue((const double*)d_rgb_sum, samples, (const double*)d_var, (const double*)d_hits, W, H, iterations, sigma, flags,
+                                    (double*)d_rgb_sum_out, (double*)d_var_out, d_workspace, (hipStream_t)hip_stream);
+}
+int rt_denoise_variance(const double* rgb_sum, uint64_t samples, const double* var, const double* hits, uint32_t W, uint32_t H, uint32_t iterations,
+                        const double sigma[3], uint32_t flags, double* rgb_sum_out, double* var_out) {
+    if (!rgb_sum || !var || !hits || !sigma || !rgb_sum_out) return set_err("null argument");
+    const std::string problem = denoise_variance_check(samples, W, H, iterations, sigma, flags);
+    if (!problem.empty()) return set_err(problem);
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
+    const size_t ws_bytes = rt_denoise_variance_workspace_bytes(W, H);
+    DeviceBuffer d_sum, d_var, d_hits, d_ws, d_vout;
+    HIP_OK(d_sum.alloc(sum_bytes)); HIP_OK(d_var.alloc(sum_bytes)); HIP_OK(d_hits.alloc(hit_bytes)); HIP_OK(d_ws.alloc(ws_bytes));
+    if (var_out) HIP_OK(d_vout.alloc(n * sizeof(double)));
+    HIP_OK(hipMemcpy(d_sum.get(), rgb_sum, sum_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_var.get(), var, sum_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_hits.get(), hits, hit_bytes, hipMemcpyHostToDevice));
+    if (rt_denoise_variance_device(d_sum.get(), samples, d_var.get(), d_hits.get(), W, H, iterations, sigma, flags, d_sum.get(), var_out ? d_vout.get() : nullptr,
+                                   d_ws.get(), ws_bytes, nullptr)) return -1;
+    HIP_OK(hipMemcpy(rgb_sum_out, d_sum.get(), sum_bytes, hipMemcpyDeviceToHost));       // (waits for the kernels: the null stream)
+    if (var_out) HIP_OK(hipMemcpy(var_out, d_vout.get(), n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+int rt_debug_denoise_variance_ms(const void* d_rgb_sum, uint64_t samples, const void* d_var, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
+                                 const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, float* ms_out) {
+    if (!ms_out) return set_err("null argument");
+    hipEvent_t marks[DENOISE_MAX_ITERATIONS + 3u] = {};
+    const uint32_t n_marks = (iterations <= DENOISE_MAX_ITERATIONS ? iterations : 0u) + 3u;
+    int rc = 0;
+    for (uint32_t k = 0; k < n_marks && rc == 0; k++) if (hipEventCreate(&marks[k]) != hipSuccess) rc = set_err("hipEventCreate failed");
+    // (the arguments are rt_denoise_variance_device's and are checked there; nothing is recorded for a refused call)
+    if (rc == 0) {
+        if (rt_denoise_variance_device(d_rgb_sum, samples, d_var, d_hits, W, H, iterations, sigma, flags, d_rgb_sum_out, nullptr, d_workspace, workspace_bytes, nullptr)) rc = -1;     // the checks, and a warm run
+        else rc = denoise_variance_enqueue((const double*)d_rgb_sum, samples, (const double*)d_var, (const double*)d_hits, W, H, iterations, sigma, flags,
+                                           (double*)d_rgb_sum_out, nullptr, d_workspace, nullptr, marks);
+    }
+    if (rc == 0 && hipEventSynchronize(marks[iterations + 2u]) != hipSuccess) rc = set_err("hipEventSynchronize failed");
+    for (uint32_t k = 0; k <= iterations + 1u && rc == 0; k++) if (hipEventElapsedTime(&ms_out[k], marks[k], marks[k + 1u]) != hipSuccess) rc = set_err("hipEventElapsedTime failed");
+    for (uint32_t k = 0; k < n_marks; k++) if (marks[k]) (void)hipEventDestroy(marks[k]);
+    return rc;
+}
+// The frame's sums filtered under the guidance of the frame's own variance, and resolved; everything the other resolves own stays as it is.
+int rt_progressive_resolve_denoised_variance_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !sigma || !rgb8_out) return set_err("null argument");
+    if (moments_error_ready(p)) return -1;
+    const std::string problem = denoise_variance_check(p->done, p->W, p->H, iterations, sigma, flags);
+    if (!problem.empty()) return set_err(problem);
+    DeviceGuard guard(p->device);
+    if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
+    if (progressive_variance_enqueue(p, nullptr)) return -1;
+    if (denoise_variance_enqueue((const double*)p->d_sum, p->done, (const double*)p->d_var, nullptr, p->W, p->H, iterations, sigma, flags, (double*)p->d_dn_sum,
+                                 nullptr, p->d_dn_ws, nullptr)) return -1;
     return progressive_denoise_finish(p, rgb8_out);
 }
 

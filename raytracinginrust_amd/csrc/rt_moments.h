@@ -41,6 +41,12 @@
 //         [2] nonfinite    the rest
 //         [3] max_e2       the bit pattern of the largest finite e2: starts at +0.0 and is replaced by a finite e2 that is > it
 //     Positive doubles order as their bit patterns do, so all four words are independent of the order in which pixels are visited: exact.
+//
+// (4) VARIANCE, for B >= 2: the intermediate V of (2) as a frame of its own, three doubles per pixel — the variance of the mean of every
+//     channel, which the variance-guided denoiser (rt_denoise_var.h) takes as its input:
+//         ssb = Q - (S * S) / Nd;   ssb = ssb > 0 ? ssb : 0;   V = (ssb / Bm1) / Nd
+//     (2) computes its V with this very function, so e2 = V / (4 * den) holds word for word.  A non-finite state gives what (2) says: 0, or
+//     +inf from a +inf in Q.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -64,13 +70,17 @@ RT_MOMENTS_FN void moments_merge(double p, double nb, double& S, double& Q) {
     Q = Q + pp / nb;
 }
 RT_MOMENTS_FN bool moments_finite(double v) { return v - v == 0.0; }
-// (2), one channel
-RT_MOMENTS_FN double moments_channel_e2(double S, double Q, double Nd, double Bm1) {
-    const double m = S / Nd;
+// (4), one channel: the variance of the mean
+RT_MOMENTS_FN double moments_channel_variance(double S, double Q, double Nd, double Bm1) {
     const double ss = S * S;
     double ssb = Q - ss / Nd;
     ssb = ssb > 0.0 ? ssb : 0.0;
-    const double V = (ssb / Bm1) / Nd;
+    return (ssb / Bm1) / Nd;
+}
+// (2), one channel
+RT_MOMENTS_FN double moments_channel_e2(double S, double Q, double Nd, double Bm1) {
+    const double m = S / Nd;
+    const double V = moments_channel_variance(S, Q, Nd, Bm1);
     const double den = m >= MOMENTS_DELTA ? m : MOMENTS_DELTA;
     double e2 = V / (4.0 * den);
     if (m >= 1.0) {
@@ -99,6 +109,7 @@ std::string moments_tau_check(double tau);
 void moments_merge_host(const double* pass_sum, uint64_t n_samples, double* rgb_sum, double* sq_sum, uint64_t n_doubles);
 void moments_error_host(const double* rgb_sum, const double* sq_sum, uint64_t samples, uint64_t passes, uint64_t n_px, double* e2_out);
 void moments_stats_host(const double* e2, uint64_t n_px, double tau, uint64_t stats_out[4]);
+void moments_variance_host(const double* rgb_sum, const double* sq_sum, uint64_t samples, uint64_t passes, uint64_t n_doubles, double* var_out);
 
 // ---- the kernels (rt_moments.hip).  DEVICE pointers, 8-byte aligned, the three of a merge distinct buffers; asynchronous on `stream` (a
 // hipStream_t); the return value is the hipError_t of the launch.
@@ -108,5 +119,8 @@ int launch_moments_merge(double* d_pass_sum, uint64_t n_samples, double* d_rgb_s
 // are each written when given.
 int launch_moments_error(const double* d_rgb_sum, const double* d_sq_sum, uint64_t samples, uint64_t passes, uint32_t n_px, double* d_e2_out,
                          double tau2, unsigned long long* d_stats, void* stream);
+// (4) over n doubles (rt_denoise_var.hip: a unit of its own, so that rt_moments.hip's code object does not change).  16-byte accesses when all
+// three buffers are 16-byte aligned; d_var_out may be neither input.
+int launch_moments_variance(const double* d_rgb_sum, const double* d_sq_sum, uint64_t samples, uint64_t passes, uint64_t n, double* d_var_out, void* stream);
 
 } // namespace rt

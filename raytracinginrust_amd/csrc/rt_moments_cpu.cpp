@@ -1,5 +1,5 @@
 // csrc/rt_moments_cpu.cpp — the host twin of the moments of a progressive frame: the specification of rt_moments.h as plain C++ (no HIP, no
-// device), the argument checks every entry point shares, and rt_moments_merge_host / rt_moments_error_host / rt_moments_stats_host of
+// device), the argument checks every entry point shares, and rt_moments_merge_host / rt_moments_error_host / rt_moments_variance_host / rt_moments_stats_host of
 // include/rt_amd.h.  Built with -ffp-contract=off like the rest of the library: every operation rounds once, which is what makes its words
 // the ones the HIP kernels (rt_moments.hip) produce.
 #include <cstring>
@@ -34,6 +34,10 @@ void moments_error_host(const double* rgb_sum, const double* sq_sum, uint64_t sa
     const double Nd = (double)samples, Bm1 = (double)(passes - 1u);
     for (uint64_t p = 0; p < n_px; p++) e2_out[p] = moments_pixel_e2(rgb_sum + 3u * p, sq_sum + 3u * p, Nd, Bm1);
 }
+void moments_variance_host(const double* rgb_sum, const double* sq_sum, uint64_t samples, uint64_t passes, uint64_t n_doubles, double* var_out) {
+    const double Nd = (double)samples, Bm1 = (double)(passes - 1u);
+    for (uint64_t i = 0; i < n_doubles; i++) var_out[i] = moments_channel_variance(rgb_sum[i], sq_sum[i], Nd, Bm1);
+}
 void moments_stats_host(const double* e2, uint64_t n_px, double tau, uint64_t stats_out[4]) {
     const double tau2 = tau * tau;
     uint64_t conv = 0, unconv = 0, nonfinite = 0;
@@ -64,6 +68,13 @@ int rt_moments_error_host(const double* rgb_sum, const double* sq_sum, uint64_t 
     const std::string problem = rt::moments_error_check(samples, passes, W, H);
     if (!problem.empty()) return rt::set_error(problem);
     rt::moments_error_host(rgb_sum, sq_sum, samples, passes, (uint64_t)W * H, e2_out);
+    return 0;
+}
+int rt_moments_variance_host(const double* rgb_sum, const double* sq_sum, uint64_t samples, uint64_t passes, uint32_t W, uint32_t H, double* var_out) {
+    if (!rgb_sum || !sq_sum || !var_out) return rt::set_error("null argument");
+    const std::string problem = rt::moments_error_check(samples, passes, W, H);
+    if (!problem.empty()) return rt::set_error(problem);
+    rt::moments_variance_host(rgb_sum, sq_sum, samples, passes, (uint64_t)W * H * 3u, var_out);
     return 0;
 }
 int rt_moments_stats_host(const double* e2, uint64_t n_px, double tau, uint64_t stats_out[4]) {

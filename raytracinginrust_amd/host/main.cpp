@@ -5,12 +5,14 @@
 //
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
 //              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material|albedo FILE] [--panorama FILE]
-//              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] [--denoise-albedo N] [--until-error TAU] [--max-samples M] [--aov error FILE] > image.ppm
+//              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] [--denoise-albedo N] [--denoise-variance SIGMA_V] [--until-error TAU] [--max-samples M] [--aov error FILE] > image.ppm
 //
 // --denoise K[,c,n,p] (opt-in): the frame through the edge-avoiding a-trous filter before it is written (rt_denoise: K iterations, guided by
 // sample 0's camera hits of this --seed); with --progressive the frame resolves itself denoised on the device (rt_progressive_resolve_denoised_rgb8).
 // --denoise-albedo N (with --denoise): the filter runs on the frame divided by its first-hit albedo — the mean over samples [0, N) of this --seed,
 // rt_query_camera_albedo — and the result is multiplied back (rt_denoise_albedo*): what a textured scene needs.
+// --denoise-variance SIGMA_V (with --progressive N and --denoise K): the colour stop is SIGMA_V standard deviations of the frame's own
+// per-pixel variance instead of SIGMA_C (rt_progressive_resolve_denoised_variance_rgb8); the frame keeps moments and needs at least two passes.
 //
 // --progressive N (opt-in, one GPU): the frame in passes of N samples per pixel (rt_progressive_*), the reference's style of progress on
 // stderr (main.rs:772-775), and the same PPM bytes at the end, built from the image the device resolved.
@@ -292,6 +294,7 @@ int main(int argc, char** argv) {
     std::string panorama_path;                                              // --panorama FILE: the equirectangular image around lookfrom instead
     bool want_denoise = false; DenoiseSettings dn;                          // --denoise K[,sigma_c,sigma_n,sigma_p]: filter the frame before it is written
     uint32_t albedo_samples = 0;                                            // --denoise-albedo N: demodulate by the albedo of samples [0, N) (0: the plain filter)
+    double sigma_v = 0.0;                                                   // --denoise-variance SIGMA_V: the variance-guided colour stop (0: the plain filter)
     uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
     double until_error = -1.0; uint32_t max_samples = 0;                    // --until-error TAU [--max-samples M]: stop when no pixel's standard error exceeds TAU
     int gpus = 1;                                                           // --gpus N: the first N devices (0 = all) through rt_render_multi
@@ -332,6 +335,7 @@ int main(int argc, char** argv) {
             want_denoise = true; dn.iterations = k; dn.sigma[0] = c; dn.sigma[1] = n; dn.sigma[2] = p;
         }
         else if (a == "--denoise-albedo") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--denoise-albedo needs a sample count >= 1\n"); return 2; } albedo_samples = (uint32_t)n; }
+        else if (a == "--denoise-variance") { sigma_v = std::atof(next()); if (!(sigma_v > 0.0)) { std::fprintf(stderr, "--denoise-variance needs a colour stop > 0 in standard deviations (inf switches it off)\n"); return 2; } }
         else if (a == "--help" || a == "-h") {
             std::printf("rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N]\n"
                         "         [--depth D] [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] > image.ppm\n%s"
@@ -339,6 +343,8 @@ int main(int argc, char** argv) {
                         "                                     the camera hits of sample 0 (default sigmas 4, 0.5, 0.02; inf switches a stop off); also with --progressive\n"
                         "  --denoise-albedo N                 with --denoise: filter the frame divided by its first-hit albedo (the mean over samples 0 .. N-1)\n"
                         "                                     and multiply back: textures are kept (textured scenes need it); also with --progressive\n"
+                        "  --denoise-variance SIGMA_V         with --progressive N and --denoise K: the colour stop in standard deviations of the frame's own\n"
+                        "                                     per-pixel variance instead of SIGMA_C; needs at least two passes (--spp more than N)\n"
                         "  --until-error TAU [--max-samples M]  with --progressive N: stop at the first pass after which no pixel's estimated standard error\n"
                         "                                     exceeds TAU display units (0.00390625 = one code value), at the latest after M samples (default --spp)\n"
                         "  --panorama FILE                    write the 2:1 equirectangular image (width x width/2) of everything around the scene's\n"
@@ -352,6 +358,7 @@ int main(int argc, char** argv) {
     if ((until_error >= 0.0 || max_samples != 0u || aov_kind == "error") && progressive == 0u) { std::fprintf(stderr, "--until-error, --max-samples and --aov error go with --progressive N\n"); return 2; }
     if (max_samples != 0u && until_error < 0.0) { std::fprintf(stderr, "--max-samples goes with --until-error TAU\n"); return 2; }
     if (albedo_samples != 0u && !want_denoise && aov_kind != "albedo") { std::fprintf(stderr, "--denoise-albedo goes with --denoise K (or --aov albedo)\n"); return 2; }
+    if (sigma_v != 0.0 && (!want_denoise || progressive == 0u || albedo_samples != 0u)) { std::fprintf(stderr, "--denoise-variance goes with --progressive N and --denoise K, and without --denoise-albedo\n"); return 2; }
     const double aspect_ratio = (double)image_width / (double)image_height;
     try {
         Scene s;
@@ -440,7 +447,7 @@ int main(int argc, char** argv) {
         if (progressive) {
             if (gpus != 1 || (flags & RT_MULTI_COLLECTIVE)) throw Error("--progressive renders on one GPU");
             Progressive frame(s, camera, background, image_width, image_height, max_depth, seed, flags);
-            const bool want_moments = until_error >= 0.0 || aov_kind == "error";
+            const bool want_moments = until_error >= 0.0 || aov_kind == "error" || sigma_v != 0.0;
             if (want_moments) frame.enable_moments();
             const uint32_t limit = until_error >= 0.0 && max_samples ? max_samples : samples_per_pixel;
             while (frame.samples() < limit) {
@@ -456,6 +463,14 @@ int main(int argc, char** argv) {
             if (aov_kind == "error") {
                 if (frame.passes() < 2) throw Error("--aov error needs at least two passes: --spp must be more than the pass size of --progressive");
                 write_error_aov(aov_path, frame.error_map(), image_width, image_height);
+            }
+            if (sigma_v != 0.0) {
+                if (frame.passes() < 2) throw Error("--denoise-variance needs at least two passes: --spp must be more than the pass size of --progressive");
+                DenoiseVarianceSettings dv;
+                dv.iterations = dn.iterations; dv.sigma[0] = sigma_v; dv.sigma[1] = dn.sigma[1]; dv.sigma[2] = dn.sigma[2];
+                write_ppm_rgb8("-", frame.rgb8_denoised_variance(dv), image_width, image_height);
+                std::fprintf(stderr, "Done.\n");
+                return 0;
             }
             write_ppm_rgb8("-", want_denoise ? (albedo_samples ? frame.rgb8_denoised_albedo(albedo_samples, dn) : frame.rgb8_denoised(dn)) : frame.rgb8(), image_width, image_height);     // main.rs:767-769,832
             std::fprintf(stderr, "Done.\n");                                                    // main.rs:835

@@ -426,6 +426,23 @@ class Progressive:
         _check(self._lib.rt_progressive_resolve_denoised_albedo_rgb8(self._h, int(albedo_samples), k, sg, flags, out.ctypes.data))
         return out
 
+    def variance(self) -> np.ndarray:
+        """rt_progressive_variance: the variance of the mean of every pixel and channel, (H, W, 3) f64 (csrc/rt_moments.h (4)), computed on
+        the device from the frame's sums and second moments; needs two passes."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.float64)
+        _check(self._lib.rt_progressive_variance(self._h, out.ctypes.data))
+        return out
+
+    def rgb8_denoised_variance(self, iterations: int = None, sigma=None, flags: int = 0) -> np.ndarray:
+        """rt_progressive_resolve_denoised_variance_rgb8: `rgb8_denoised` with the colour stop measured in standard deviations of the
+        frame's own per-pixel variance (`denoise_variance`) -> (H, W, 3) uint8.  sigma = (sigma_v, sigma_n, sigma_p).  Needs moments and
+        two passes; the variance, the filter and the resolve run on the device, and `sum`, `sq_sum`, `passes`, `rgb8` and its changed-pixel
+        count are untouched."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        k, sg = _denoise_variance_settings(iterations, sigma)
+        _check(self._lib.rt_progressive_resolve_denoised_variance_rgb8(self._h, k, sg, flags, out.ctypes.data))
+        return out
+
     def albedo_info(self):
         """(the albedo_samples the frame holds albedo sums for — 0: none —, how many times it has built them)."""
         n, builds = C.c_uint32(), C.c_uint64()
@@ -905,6 +922,66 @@ def denoise_albedo_device(d_rgb_sum, samples: int, d_albedo_sum, albedo_samples:
     return d_workspace
 
 
+# ---- variance-guided denoising (rt_denoise_variance*, csrc/rt_denoise_var.h): the colour stop in standard deviations of the frame's own noise.
+# The default sigma_v: DESIGN.md ("Variance-guided denoising") has the errors by sigma_v and K that it was chosen from.
+DENOISE_VARIANCE_SIGMA = (3.0, 0.5, 0.02)
+
+
+def _denoise_variance_settings(iterations, sigma):
+    return _denoise_settings(iterations, DENOISE_VARIANCE_SIGMA if sigma is None else sigma)
+
+
+def _denoise_variance_call(fn, rgb_sum, samples, var, hits, iterations, sigma, flags, want_var):
+    a, g = _denoise_frames(rgb_sum, hits)
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if v.shape != a.shape:
+        raise ValueError(f"var of shape {v.shape} for a frame of {a.shape}: the variance of the mean per pixel and channel")
+    k, sg = _denoise_variance_settings(iterations, sigma)
+    out = np.zeros_like(a)
+    v_out = np.zeros(a.shape[:2], dtype=np.float64) if want_var else None
+    _check(fn(a.ctypes.data, int(samples), v.ctypes.data, g.ctypes.data, a.shape[1], a.shape[0], k, sg, flags, out.ctypes.data,
+              v_out.ctypes.data if want_var else None))
+    return (out, v_out) if want_var else out
+
+
+def denoise_variance_host(rgb_sum, samples: int, var, hits, iterations: int = None, sigma=None, flags: int = 0, want_var: bool = False):
+    """rt_denoise_variance_host (no GPU): the variance-guided filter's specification as plain C++.  var (H, W, 3): the variance of the mean
+    of every pixel and channel, as `moments_variance_host` / `Progressive.variance` return it; sigma = (sigma_v, sigma_n, sigma_p), sigma_v
+    in standard deviations; the rest as `denoise_host`.  want_var: also the filtered variance, (H, W)."""
+    return _denoise_variance_call(_rt().rt_denoise_variance_host, rgb_sum, samples, var, hits, iterations, sigma, flags, want_var)
+
+
+def denoise_variance(rgb_sum, samples: int, var, hits, iterations: int = None, sigma=None, flags: int = 0, want_var: bool = False):
+    """rt_denoise_variance: the same call computed by the HIP kernels on the current device — the same words as denoise_variance_host."""
+    return _denoise_variance_call(_rt().rt_denoise_variance, rgb_sum, samples, var, hits, iterations, sigma, flags, want_var)
+
+
+def denoise_variance_workspace_bytes(W: int, H: int) -> int:
+    return int(_rt().rt_denoise_variance_workspace_bytes(W, H))
+
+
+def denoise_variance_device(d_rgb_sum, samples: int, d_var, d_hits, W: int, H: int, d_rgb_sum_out=None, d_var_out=None, d_workspace=None,
+                            iterations: int = None, sigma=None, flags: int = 0, stream: int = 0, workspace_bytes=None):
+    """rt_denoise_variance_device: `denoise_device` with the per-channel variance frame d_var (W*H*3 f64 in device memory); d_var_out: None,
+    or W*H f64 that receive the filtered variance.  The workspace is denoise_variance_workspace_bytes(W, H) bytes."""
+    sum_ptr, _ = _device_buffer(d_rgb_sum)
+    var_ptr, _ = _device_buffer(d_var)
+    hits_ptr, _ = _device_buffer(d_hits)
+    out_ptr = sum_ptr if d_rgb_sum_out is None else _device_buffer(d_rgb_sum_out)[0]
+    vout_ptr = None if d_var_out is None else _device_buffer(d_var_out)[0]
+    if d_workspace is None:
+        import torch
+        d_workspace = torch.empty(denoise_variance_workspace_bytes(W, H), dtype=torch.uint8, device=d_rgb_sum.device)
+    ws_ptr, nbytes = _device_buffer(d_workspace)
+    nbytes = nbytes if workspace_bytes is None else int(workspace_bytes)
+    if nbytes is None:
+        raise ValueError("workspace_bytes is needed with a raw pointer")
+    k, sg = _denoise_variance_settings(iterations, sigma)
+    _check(_rt().rt_denoise_variance_device(C.c_void_p(sum_ptr), int(samples), C.c_void_p(var_ptr), C.c_void_p(hits_ptr), W, H, k, sg, flags,
+                                            C.c_void_p(out_ptr), C.c_void_p(vout_ptr), C.c_void_p(ws_ptr), nbytes, C.c_void_p(stream)))
+    return d_workspace
+
+
 # ---- moments (rt_moments_*, csrc/rt_moments.h): the second moment of pass sums and the per-pixel error estimate of a frame of passes
 def moments_stats(words, tau: float) -> dict:
     """The four words of rt_moments_stats_host / rt_moments_error_device / rt_progressive_error_stats as a dict: the three pixel counts,
@@ -939,6 +1016,31 @@ def moments_error_host(rgb_sum, sq_sum, samples: int, passes: int) -> np.ndarray
     out = np.zeros(s.shape[:2], dtype=np.float64)
     _check(_rt().rt_moments_error_host(s.ctypes.data, q.ctypes.data, int(samples), int(passes), s.shape[1], s.shape[0], out.ctypes.data))
     return out
+
+
+def moments_variance_host(rgb_sum, sq_sum, samples: int, passes: int) -> np.ndarray:
+    """rt_moments_variance_host (no GPU): the variance of the mean of every pixel and channel, (H, W, 3) — the V that e2 is computed from
+    (csrc/rt_moments.h (4)), and the input of `denoise_variance`."""
+    s, q = _moments_frames(rgb_sum, sq_sum)
+    out = np.zeros_like(s)
+    _check(_rt().rt_moments_variance_host(s.ctypes.data, q.ctypes.data, int(samples), int(passes), s.shape[1], s.shape[0], out.ctypes.data))
+    return out
+
+
+def moments_variance(rgb_sum, sq_sum, samples: int, passes: int) -> np.ndarray:
+    """`moments_variance_host`'s words computed by the HIP kernel on the current device (through torch tensors)."""
+    import torch
+    s, q = _moments_frames(rgb_sum, sq_sum)
+    d_s, d_q = torch.from_numpy(s.copy()).cuda(), torch.from_numpy(q.copy()).cuda()      # (a copy: the caller's arrays may be read-only)
+    d_v = torch.empty_like(d_s)
+    moments_variance_device(d_s, d_q, samples, passes, s.shape[1], s.shape[0], d_v, stream=torch.cuda.current_stream().cuda_stream)
+    return d_v.cpu().numpy()
+
+
+def moments_variance_device(d_rgb_sum, d_sq_sum, samples: int, passes: int, W: int, H: int, d_var_out, stream: int = 0) -> None:
+    """rt_moments_variance_device: the variance frame (d_var_out, W*H*3 f64) for frames in device memory, enqueued on `stream`; never waits."""
+    _check(_rt().rt_moments_variance_device(C.c_void_p(_device_buffer(d_rgb_sum)[0]), C.c_void_p(_device_buffer(d_sq_sum)[0]), int(samples), int(passes),
+                                            W, H, C.c_void_p(_device_buffer(d_var_out)[0]), C.c_void_p(stream)))
 
 
 def moments_stats_host(e2, tau: float) -> dict:

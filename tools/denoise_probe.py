@@ -10,8 +10,13 @@ the albedo-demodulated one (rt_denoise_albedo, albedo of ALBEDO_SAMPLES samples)
 (rt_query_camera_albedo_device, rt_last_query_ms) at 1, 16 and 64 samples per pixel on the Cornell box at 800 x 800 and the random spheres
 at 1200 x 675, beside the time of a path-tracing pass of the same number of samples from the same run, and the two element-wise kernels of
 rt_denoise_albedo_device (rt_debug_albedo_modulate_ms) at 800 x 800 and 3840 x 2160 beside the pack kernel.
+Part 4, `variance`: the variance-guided filter (rt_denoise_variance*) — its kernels' times beside the plain filter's from the same
+run, as shipped and with RT_DENOISE_NO_LDS=1, and the variance kernel's; the whole denoised resolves of a progressive frame of C2's view
+beside one 64-sample pass; and the error table above with columns for the variance-guided filter, moments from 4 passes, plus the
+three-texture scene of §15.
 usage: python tools/denoise_probe.py [timing] [errors] > profiles/denoise.log
-       python tools/denoise_probe.py albedo errors > profiles/denoise_albedo.log"""
+       python tools/denoise_probe.py albedo errors > profiles/denoise_albedo.log
+       python tools/denoise_probe.py variance > profiles/denoise_variance.log"""
 import ctypes as C
 import os
 import sys
@@ -172,11 +177,130 @@ def albedo():
         del rgb, hits, alb, x, ws
 
 
+VARIANCE_SIGMA_VS = (2.0, 3.0, 4.0)
+
+
+def _variance_timing():
+    lib = _lib.load().lib
+    dev = torch.device("cuda", torch.cuda.current_device())
+    sigma = (C.c_double * 3)(*R.DENOISE_VARIANCE_SIGMA)
+    print(f"# variance-guided denoiser kernel times, K = {K}, sigma = {R.DENOISE_VARIANCE_SIGMA}, flags 0; HIP events, warm, best of {REPS}")
+    print("# frame  kernel  ms  floor bytes  achieved TB/s  share of the 6.3 TB/s achievable HBM rate")
+    for W, H in ((800, 800), (3840, 2160)):
+        rgb, hits = synthetic(W, H, dev)
+        # a variance on the scale of the synthetic noise: 0.3 * uniform per sample mean has variance 0.0075 per channel
+        var = (0.0075 * (0.5 + torch.rand((H, W, 3), device=dev, dtype=torch.float64))).contiguous()
+        sq = (rgb * rgb / 16.0 + 16.0 * 3.0 * var).contiguous()
+        out = torch.empty_like(rgb)
+        need = R.denoise_variance_workspace_bytes(W, H)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        best = np.full(K + 2, 1e30)
+        for _ in range(REPS):
+            ms = (C.c_float * (K + 2))()
+            rc = lib.rt_debug_denoise_variance_ms(C.c_void_p(rgb.data_ptr()), 16, C.c_void_p(var.data_ptr()), C.c_void_p(hits.data_ptr()), W, H, K, sigma, 0,
+                                                  C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), need, ms)
+            if rc != 0:
+                raise RuntimeError(lib.rt_last_error().decode())
+            best = np.minimum(best, np.array(ms[:]))
+        n = W * H
+        floors = [n * (152 + 24 + 96)] + [n * (32 + 16 + 32)] + [n * (96 + 32)] * (K - 1) + [n * (96 + 24)]
+        for k in range(K + 2):
+            name = "guide pack + colour pack" if k == 0 else "prefilter of v" if k == 1 else f"iteration {k - 2} (step {1 << (k - 2)})"
+            rate = floors[k] / (best[k] * 1e-3)
+            print(f"{W}x{H}  {name}  {best[k]:.4f}  {floors[k]}  {rate / 1e12:.3f}  {rate / HBM_ACHIEVABLE:.2f}", flush=True)
+        print(f"{W}x{H}  all {K + 3} launches  {best.sum():.4f} ms", flush=True)
+        # the variance kernel: 48 B in, 24 B out per pixel
+        v_out = torch.empty_like(rgb)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        best_v = 1e30
+        for rep in range(REPS + 1):
+            ev[0].record()
+            R.moments_variance_device(rgb, sq, 16, 4, W, H, v_out, stream=torch.cuda.current_stream().cuda_stream)
+            ev[1].record(); ev[1].synchronize()
+            if rep:
+                best_v = min(best_v, ev[0].elapsed_time(ev[1]))
+        print(f"{W}x{H}  moments variance  {best_v:.4f}  {n * 72}  {n * 72 / (best_v * 1e-3) / 1e12:.3f}  {n * 72 / (best_v * 1e-3) / HBM_ACHIEVABLE:.2f}", flush=True)
+        del rgb, hits, var, sq, out, ws, v_out
+
+
+def _variance_resolve():
+    import time
+    from raytracinginrust_amd import workloads
+    be = _lib.load()
+    w = workloads.WORKLOADS["C2"]
+    b, cam, bg = workloads.build(w, be, None)
+    print(f"# a progressive frame of C2's view ({w.scene}, {w.W}x{w.H}, depth {w.max_depth}) with moments, two passes of 64 samples: host time of each resolve call")
+    print(f"# (it ends with the copy of the image to the host), warm, best of {REPS}; the pass: rt_last_kernel_ms of a 64-sample pass plus its merge, host time")
+    with R.Progressive(b, cam, bg, w.W, w.H, w.max_depth, 7, moments=True) as frame:
+        best_pass = 1e30
+        for _ in range(3):
+            t0 = time.perf_counter(); frame.add(64); best_pass = min(best_pass, (time.perf_counter() - t0) * 1e3)
+        print(f"pass of 64 samples (kernel {R.last_kernel_ms(b):.3f} ms)  {best_pass:.3f} ms")
+        for name, fn in (("rgb8", lambda: frame.rgb8()), ("rgb8_denoised K = 2", lambda: frame.rgb8_denoised()), ("rgb8_denoised_variance K = 2", lambda: frame.rgb8_denoised_variance())):
+            best = 1e30
+            for rep in range(REPS + 1):
+                t0 = time.perf_counter(); fn(); dt = (time.perf_counter() - t0) * 1e3
+                if rep:
+                    best = min(best, dt)
+            print(f"{name}  {best:.3f} ms  ({best / best_pass:.3f} of the pass)", flush=True)
+
+
+def _variance_errors():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import build_scene
+    from denoise_cases import clipped_mse
+    from test_denoise_albedo_gpu import textured_scene
+    be = _lib.load()
+    earth = scenes.load_earthmap()
+    depth, truth_spp, n_passes = 20, 4096, 4
+    print(f"# clipped MSE against {truth_spp} spp (seed 99), depth {depth}, flags 0: raw, then K = 1 .. 5 (ratio to raw); the noisy frame is a progressive")
+    print(f"# frame of {n_passes} equal passes (seed 7) with moments; 'plain' rt_denoise with sigma = {R.DENOISE_SIGMA}; 'var s' rt_denoise_variance with sigma_v = s and")
+    print(f"# sigma_n, sigma_p = {R.DENOISE_VARIANCE_SIGMA[1:]}; the default sigma_v is {R.DENOISE_VARIANCE_SIGMA[0]:g}")
+    cases = [(name, size, lambda name=name: build_scene(name, be, earth)) for name, size in (("cornell", (100, 100)), ("random", (160, 90)), ("final", (100, 100)), ("teapot", (160, 90)))]
+    cases.append(("textured", (100, 100), lambda: textured_scene(be)))
+    for name, (W, H), make in cases:
+        b, cam, bg = make()
+        truth = R.render(b, cam, bg, W, H, truth_spp, depth, 99)
+        hits = R.query_camera(b, cam, W, H, 0, 7)
+        for spp in (16, 64):
+            with R.Progressive(b, cam, bg, W, H, depth, 7, moments=True) as frame:
+                for _ in range(n_passes):
+                    frame.add(spp // n_passes)
+                noisy, var = frame.sum(), frame.variance()
+            raw = clipped_mse(noisy, spp, truth, truth_spp)
+            rows = {"plain": []}
+            for k in range(1, 6):
+                e = clipped_mse(R.denoise(noisy, spp, hits, k, R.DENOISE_SIGMA, 0), spp, truth, truth_spp)
+                rows["plain"].append(f"{e:.5f} ({e / raw:.2f})")
+                for sv in VARIANCE_SIGMA_VS:
+                    e = clipped_mse(R.denoise_variance(noisy, spp, var, hits, k, (sv,) + tuple(R.DENOISE_VARIANCE_SIGMA[1:]), 0), spp, truth, truth_spp)
+                    rows.setdefault(f"var {sv:g}", []).append(f"{e:.5f} ({e / raw:.2f})")
+            for label, row in rows.items():
+                print(f"{name} {W}x{H} {spp} spp  raw {raw:.5f}  {label}  " + "  ".join(row), flush=True)
+
+
+def variance():
+    for no_lds in (False, True):
+        if no_lds:
+            os.environ["RT_DENOISE_NO_LDS"] = "1"
+        else:
+            os.environ.pop("RT_DENOISE_NO_LDS", None)
+        print("# ---- " + ("RT_DENOISE_NO_LDS=1: every iteration reads its taps from global memory" if no_lds else "as shipped: steps 1 and 2 from LDS tiles"))
+        _timing()
+        _variance_timing()
+    os.environ.pop("RT_DENOISE_NO_LDS", None)
+    _variance_resolve()
+    _variance_errors()
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["timing", "errors"]
     if "timing" in what:
         timing()
     if "albedo" in what:
         albedo()
+    if "variance" in what:
+        variance()
     if "errors" in what:
         errors()
