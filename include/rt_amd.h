@@ -690,6 +690,31 @@ int rt_debug_primary_mask_host(rt_scene*, const rt_camera*, uint32_t W, uint32_t
  *       pdf, and 1 if the record's wave took |v_k| for |dot(v, n)| (0: the two dot products).
  * Host pointers; no scene.  Returns 0, -1 on a bad argument or a device error. */
 int rt_debug_short_forms(uint32_t op, uint32_t n, const double* a, const double* b, double* out);
+/* Known-answer access to the arithmetic of the SHADING side (csrc/rt_kat.hip over rt_kernel.hip's device functions): one device function per
+ * lane on n caller operands, f64.  The two units the frames are built from compile the shared source in two code shapes; op selects the
+ * lean (list-scene) unit's, op | RT_KAT_REST_SHAPE the other unit's.  Doubles per record of a / b / out:
+ *   0 sincos_0_2pi(phi): 1 / 0 / 2 (sin, cos);  1 sin, 2 cos, 3 tan, 4 atan, 6 acos, 7 log, 8 log2: 1 / 0 / 1;  5 atan2(a, b), 9 pow(a, b): 1 / 1 / 1;
+ *   10 Vec3 / f64: 3 / 1 / 4 (the quotients, then 1 if the lane took the shared-denominator form, 0 for the three plain divisions);
+ *   11 onb_from_w(n): 3 / 0 / 9 (u, v, w);  12 GTR_1(n_dot_h, a): 1 / 1 / 1;  13 GTR_2_aniso(n_dot_h, h_dot_x, h_dot_y; ax, ay): 3 / 2 / 1;
+ *   14 smithG_GGX(n_dot_v, alphaG): 1 / 1 / 1;  15 smithG_GGX_aniso(n_dot_v, v_dot_x, v_dot_y; ax, ay): 3 / 2 / 1;  16 schlick_fresnel(u): 1 / 0 / 1.
+ * b may be NULL where its record is empty.  Host pointers; no scene.  Returns 0, -1 on a bad argument or a device error. */
+#define RT_KAT_REST_SHAPE 0x100u
+int rt_debug_math(uint32_t op, uint32_t n, const double* a, const double* b, double* out);
+/* Material::brdf (mat.rs:133-195) and PDF::BRDF value (pdf.rs:97-130, on ONB::build_from_w(normal)) of one PBR material of the scene, on the
+ * device through the functions shade_hit's principled arm calls (pbr_brdf, brdf_pdf_value), for n caller records.  r_in, r_out, normal,
+ * base (the base colour the texture would give): n x 3 each; out: n x 4 = brdf[3], pdf value.  shape: 0 or RT_KAT_REST_SHAPE, as above.
+ * Host pointers. */
+int rt_debug_brdf(rt_scene*, uint32_t n, int material, const double* r_in, const double* r_out, const double* normal, const double* base, double* out, uint32_t shape);
+/* ONE level of ray_color after the hit (main.rs:50-116) per record, through the function the frames' bounce loops call (rt_kernel.hip shade_hit).
+ * records: n x 16 in rt_query_hits' layout (every one a hit; in a list scene the primitive index names the rect whose ONB memo entry the
+ * Lambertian arm probes); rays: n x 7, the incoming rays; beta: the throughput every lane starts with; record k draws from
+ * rt_rng_path(seed, k, 0); depth_left >= 1.  flags: RT_STOP_ON_ZERO, RT_ISOTROPIC_SCATTER; RT_KAT_REST_SHAPE — the all-features instantiation
+ * under the other unit's code shape (with object leaves and nested light lists where the scene has them) instead of the lean one (list scenes
+ * only); RT_KAT_NO_ONB_TABLE — the lean one without the ONB memo.  out: n x 19 = the ray afterwards (7), beta[3], e[3] (the terminal radiance
+ * beta multiplies), done (0 / 1), depth_left, the stream's four state words afterwards.  Host pointers. */
+#define RT_KAT_NO_ONB_TABLE 0x200u
+int rt_debug_shade(rt_scene*, uint32_t n, const double* records, const double* rays, const double beta[3], uint64_t seed, uint32_t depth_left,
+                   uint32_t flags, double* out);
 /* Debugging aid for parity work: the hits of ONE camera path, level by level.  rt_debug_trace_path chooses the path (local pixel index =
  * output-order pixel for an unsharded render, sample index; -1 switches it off); the following renders record, per level of ray_color
  * that found a hit, 16 doubles at out[16 * level]: t, position[3], normal[3], front_face, object, primitive kind, primitive index,

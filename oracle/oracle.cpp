@@ -95,6 +95,22 @@ struct Counters {
     }
 };
 
+// orc_shade_batch's margin: while it runs one level of ray_color, every comparison whose operands depend on a libm result — the cosine
+// and half-vector tests of the pdfs and the BRDF, the lights' hit tests inside pdf_value — notes how far, scaled, its operand lies from
+// its threshold; the smallest is reported, and a caller comparing with another libm knows which inputs may legitimately take the other
+// branch.  Off (a null pointer) everywhere else; compiled out of the timed build and of the op-counting build.
+#if defined(ORC_NO_COUNTERS) || defined(ORC_COUNT_OPS)
+#define ORC_MARGIN(x, thr, scale) ((void)0)
+#else
+static thread_local double* g_margin = nullptr;
+static inline void margin_note(double x, double thr, double scale) {
+    if (!g_margin) return;
+    const double m = std::fabs(x - thr) / scale;
+    if (m < *g_margin) *g_margin = m;                                  // (NaN: not noted)
+}
+#define ORC_MARGIN(x, thr, scale) margin_note(x, thr, scale)
+#endif
+
 // thread_rng() stand-in + counters, threaded through every call that draws in the reference.
 #ifdef ORC_COUNT_OPS
 // the draws of orc_rng.h work on plain f64; their arithmetic is tallied here: u01 = one conversion and one multiply,
@@ -525,6 +541,7 @@ struct PDF {                                                           // pdf.rs
         switch (kind) {
         case BRDF: {                                                   // pdf.rs:97-130
             double cosine = r_out.normalized().dot(uvw.w());
+            ORC_MARGIN(cosine, 0.0, 1.0);
             if (cosine <= 0.0) return 0.0;
             double diffuse_pdf = cosine / PI;
             Vec3 l = r_in.normalized() * (-1.0);
@@ -533,6 +550,7 @@ struct PDF {                                                           // pdf.rs
             double n_dot_l = n.dot(l);
             Vec3 h = (l + v).normalized();
             double n_dot_h = n.dot(h);
+            ORC_MARGIN(n_dot_h, 0.0, 1.0);
             if (n_dot_h <= 0.0) return 0.0;
             double aspect = std::sqrt(1.0 - anisotropic * 0.9);
             double ax = f_max(roughness * roughness / aspect, 0.001);
@@ -543,6 +561,7 @@ struct PDF {                                                           // pdf.rs
         }
         case Cosine: {
             double cosine = r_out.normalized().dot(uvw.w());
+            ORC_MARGIN(cosine, 0.0, 1.0);
             return (cosine > 0.0) ? cosine / PI : 0.0;
         }
         case HittableK: return hittable->pdf_value(origin, r_out, s);
@@ -593,6 +612,7 @@ struct PBR : Material {                                                // mat.rs
         Vec3 n = onb.w(), x = onb.u(), y = onb.v();
         double n_dot_v = n.dot(v);
         double n_dot_l = n.dot(l);
+        ORC_MARGIN(n_dot_l, 0.0, 1.0); ORC_MARGIN(n_dot_v, 0.0, 1.0);
         if (n_dot_l < 0.0 || n_dot_v < 0.0) return Vec3(0.0, 0.0, 0.0);
         Vec3 h = (l + v).normalized();
         double n_dot_h = n.dot(h);
@@ -727,11 +747,14 @@ static bool sphere_hit_body(const Point3& center, double radius, const Material*
     double half_b = oc.dot(r.direction());
     double c = sq_of_len(oc) - radius * radius;
     double discriminant = half_b * half_b - a * c;
+    ORC_MARGIN(discriminant, 0.0, f_max(half_b * half_b, std::fabs(a * c)));
     if (discriminant < 0.0) return false;
     double sqrt_d = std::sqrt(discriminant);
     double root = (-half_b - sqrt_d) / a;
+    ORC_MARGIN(root, t_min, f_max(std::fabs(root), std::fabs(t_min)));
     if (root < t_min || root > t_max) {
         root = (-half_b + sqrt_d) / a;
+        ORC_MARGIN(root, t_min, f_max(std::fabs(root), std::fabs(t_min)));
         if (root < t_min || root > t_max) return false;
     }
     rec.position = r.at(root);
@@ -806,9 +829,12 @@ struct AARect : Hittable {
         int ki, ai, bi;
         plane_axes(plane, ki, ai, bi);
         double t = (k - r.origin()[ki]) / r.direction()[ki];
+        ORC_MARGIN(t, t_min, f_max(std::fabs(t), std::fabs(t_min)));
         if (t < t_min || t > t_max) return false;
         double a = r.origin()[ai] + t * r.direction()[ai];
         double b = r.origin()[bi] + t * r.direction()[bi];
+        ORC_MARGIN(a, a0, f_max(std::fabs(a0), std::fabs(a1))); ORC_MARGIN(a, a1, f_max(std::fabs(a0), std::fabs(a1)));
+        ORC_MARGIN(b, b0, f_max(std::fabs(b0), std::fabs(b1))); ORC_MARGIN(b, b1, f_max(std::fabs(b0), std::fabs(b1)));
         if (a < a0 || a > a1 || b < b0 || b > b1) return false;
         rec.u = (a - a0) / (a1 - a0);
         rec.v = (b - b0) / (b1 - b0);
@@ -1090,6 +1116,44 @@ struct Camera {
 };
 
 // ---------------------------------------------------------------- src/main.rs:41-120  ray_color
+// One level after the hit (main.rs:62-110): the emitted term, scatter_mc_method, the specular arm or the mixture / BRDF pdf arm, and what
+// multiplies the child's colour.  False: no scatter (the level returns `emitted`).  ray_color and orc_shade_batch both run this.
+struct Level {
+    Color emitted;
+    ScatterRecord::Kind kind;
+    Color a;                 // Specular: attenuation; Scatter: attenuation * scattering_pdf; Microfacet: brdf
+    double pdf_value;
+    Ray child;
+    Color weigh(const Color& c) const { return kind == ScatterRecord::Specular ? a * c : a * c / pdf_value; }
+    Color combine(const Color& c) const { return kind == ScatterRecord::Specular ? weigh(c) : emitted + weigh(c); }   // main.rs:89-91 / :97, :104
+};
+static bool ray_color_level(const Ray& ray, const HitRecord& rec, const HittableList* lights, Sampler& s, Level& L) {
+    L.emitted = rec.material->emitted(rec, s);                                                       // main.rs:62
+    ScatterRecord srec;
+    if (!rec.material->scatter_mc_method(ray, rec, s, srec)) return false;                           // main.rs:86
+    ORC_COUNT(s.c.bounces++);
+    L.kind = srec.kind;
+    if (srec.kind == ScatterRecord::Specular) {                                                      // main.rs:89-91
+        L.a = srec.attenuation; L.pdf_value = 1.0; L.child = srec.specular_ray;
+        return true;
+    }
+    // ScatterRecord::Scatter, main.rs:92-98; ScatterRecord::Microfacet, main.rs:99-105 (same sampling, brdf() weight)
+    Vec3 dir; double pdf_value;
+    if (lights->list.empty()) {                                                                      // deviation D2
+        dir = srec.pdf.generate(s);
+        pdf_value = srec.pdf.value(dir, s);
+    } else {
+        PDF hittable_pdf = PDF::hittable_pdf(rec.position, lights);
+        PDF mixture_pdf = PDF::mixture_pdf(&hittable_pdf, &srec.pdf);
+        dir = mixture_pdf.generate(s);
+        pdf_value = mixture_pdf.value(dir, s);
+    }
+    L.child = Ray(rec.position, dir, ray.time());
+    L.pdf_value = pdf_value;
+    L.a = (srec.kind == ScatterRecord::Microfacet) ? rec.material->brdf(ray, L.child, rec, s)
+                                                   : srec.attenuation * rec.material->scattering_pdf(ray, rec, L.child);
+    return true;
+}
 static Color ray_color(const Ray& ray, const Color& background, const Hittable* world, const HittableList* lights, uint64_t depth, Sampler& s) {
     if (depth <= 0) return Color(0.0, 0.0, 0.0);                                                     // main.rs:42-45
     ORC_COUNT(s.c.world_hits++);
@@ -1103,31 +1167,10 @@ static Color ray_color(const Ray& ray, const Color& background, const Hittable* 
     }
     if (any_hit) {
         ORC_COUNT(s.c.shades++);
-        Color emitted = rec.material->emitted(rec, s);                                               // main.rs:62
-        ScatterRecord srec;
-        if (rec.material->scatter_mc_method(ray, rec, s, srec)) {                                    // main.rs:86
-            ORC_COUNT(s.c.bounces++);
-            if (srec.kind == ScatterRecord::Specular) {                                              // main.rs:89-91
-                return srec.attenuation * ray_color(srec.specular_ray, background, world, lights, depth - 1, s);
-            }
-            // ScatterRecord::Scatter, main.rs:92-98; ScatterRecord::Microfacet, main.rs:99-105 (same sampling, brdf() weight)
-            Vec3 dir; double pdf_value;
-            if (lights->list.empty()) {                                                              // deviation D2
-                dir = srec.pdf.generate(s);
-                pdf_value = srec.pdf.value(dir, s);
-            } else {
-                PDF hittable_pdf = PDF::hittable_pdf(rec.position, lights);
-                PDF mixture_pdf = PDF::mixture_pdf(&hittable_pdf, &srec.pdf);
-                dir = mixture_pdf.generate(s);
-                pdf_value = mixture_pdf.value(dir, s);
-            }
-            Ray scattered(rec.position, dir, ray.time());
-            if (srec.kind == ScatterRecord::Microfacet)
-                return emitted + rec.material->brdf(ray, scattered, rec, s) * ray_color(scattered, background, world, lights, depth - 1, s) / pdf_value;
-            return emitted + srec.attenuation * rec.material->scattering_pdf(ray, rec, scattered) *
-                                 ray_color(scattered, background, world, lights, depth - 1, s) / pdf_value;
-        }
-        return emitted;                                                                              // main.rs:108-110
+        Level L;
+        if (ray_color_level(ray, rec, lights, s, L))
+            return L.combine(ray_color(L.child, background, world, lights, depth - 1, s));
+        return L.emitted;                                                                            // main.rs:108-110
     }
     return background;                                                                               // main.rs:118
 }
@@ -1502,6 +1545,96 @@ void orc_camera_ray(const orc_camera* c, uint32_t W, uint32_t H, uint32_t i, uin
 void orc_ray_color(void* s, const double* o, const double* d, double time, const double* bg, uint64_t depth, void* rng, double* out3) {
     Color c = ray_color(Ray(V(o), V(d), time), V(bg), SC->world, &SC->lights, depth, *(Sampler*)rng);
     for (int i = 0; i < 3; i++) out3[i] = c[i];
+}
+// ray_color on an explicit ray with the stream of a camera path, Rng::for_path(seed, pixel, sample): what orc_shade_batch's record `pixel` draws from
+void orc_ray_color_path(void* s, const double* o, const double* d, double time, const double* bg, uint64_t depth, uint64_t seed, uint32_t pixel,
+                        uint32_t sample, double* out3) {
+    Sampler smp; smp.rng = Rng::for_path(seed, pixel, sample);
+    Color c = ray_color(Ray(V(o), V(d), time), V(bg), SC->world, &SC->lights, depth, smp);
+    for (int i = 0; i < 3; i++) out3[i] = c[i];
+}
+// world.hit(ray, 0.00001, +inf) for n rays (n x 7), written in the product's rt_query_hits layout (n x 16): hit, t, position[3], normal[3],
+// front_face, u, v, the material's handle; the object and primitive fields, which only the product knows, are -1.  Ray k draws from
+// Rng::for_stream(seed, k) where a ConstantMedium needs a number.
+void orc_hit_records(void* s, uint32_t n, const double* rays, uint64_t seed, double* out) {
+    for (uint32_t k = 0; k < n; k++) {
+        const double* ry = rays + 7 * (size_t)k; double* o = out + 16 * (size_t)k;
+        Sampler smp; smp.rng = Rng::for_stream(seed, k);
+        HitRecord rec;
+        const bool any = SC->world->hit(Ray(V(ry), V(ry + 3), ry[6]), 0.00001, F64_INF, smp, rec);
+        for (int i = 0; i < 16; i++) o[i] = 0.0;
+        o[11] = o[12] = o[13] = o[14] = -1.0;
+        if (!any) continue;
+        o[0] = 1.0; o[1] = rec.t; o[8] = rec.front_face ? 1.0 : 0.0; o[9] = rec.u; o[10] = rec.v;
+        for (int i = 0; i < 3; i++) { o[2 + i] = rec.position[i]; o[5 + i] = rec.normal[i]; }
+        for (size_t m = 0; m < SC->materials.size(); m++) if (SC->materials[m].get() == rec.material) o[11] = (double)m;
+    }
+}
+// The libm this restatement is linked with, on n caller operands: op 1 sin, 2 cos, 3 tan, 4 atan, 5 atan2(a, b), 6 acos, 7 log, 8 log2,
+// 9 pow(a, b) (the product's rt_debug_math numbering; b is read by 5 and 9 only).  What tests/test_shade_kat_host.py measures.
+void orc_libm(uint32_t op, uint32_t n, const double* a, const double* b, double* out) {
+    for (uint32_t i = 0; i < n; i++) {
+        switch (op) {
+        case 1: out[i] = std::sin(a[i]); break;
+        case 2: out[i] = std::cos(a[i]); break;
+        case 3: out[i] = std::tan(a[i]); break;
+        case 4: out[i] = std::atan(a[i]); break;
+        case 5: out[i] = std::atan2(a[i], b[i]); break;
+        case 6: out[i] = std::acos(a[i]); break;
+        case 7: out[i] = std::log(a[i]); break;
+        case 8: out[i] = std::log2(a[i]); break;
+        case 9: out[i] = std::pow(a[i], b[i]); break;
+        default: out[i] = 0.0; break;
+        }
+    }
+}
+// One level of ray_color after the hit (ray_color_level: the code ray_color runs) for n caller hit records, the counterpart of the product's
+// rt_debug_shade: records n x 16 (hit, t, position[3], normal[3], front_face, u, v, material handle, ...), rays n x 7, record k on the
+// stream Rng::for_path(seed, k, 0).  flags: 2 = the product's RT_STOP_ON_ZERO rule on the outgoing beta, 4 = Isotropic scatters.  out: n x 19
+// = the ray afterwards (the incoming one where nothing scatters), beta * weight, e (the emitted term where the path ends), done,
+// depth_left, the stream's four words afterwards.  margin_out (may be null): per record the smallest scaled distance to its threshold
+// of any libm-dependent comparison (ORC_MARGIN; +inf: none was made).  -1: a record without a material of this scene.
+int orc_shade_batch(void* s, uint32_t n, const double* records, const double* rays, const double* beta, uint64_t seed, uint32_t depth_left,
+                    uint32_t flags, double* out, double* margin_out) {
+    const bool iso_before = SC->isotropic_scatters;
+    SC->isotropic_scatters = (flags & 4u) != 0u;
+    int rc = 0;
+    for (uint32_t k = 0; k < n; k++) {
+        const double* r = records + 16 * (size_t)k; const double* ry = rays + 7 * (size_t)k; double* o = out + 19 * (size_t)k;
+        const int64_t mat = (int64_t)r[11];
+        if (mat < 0 || (size_t)mat >= SC->materials.size()) { rc = -1; break; }
+        HitRecord rec;
+        rec.t = r[1]; rec.position = V(r + 2); rec.normal = V(r + 5); rec.front_face = r[8] != 0.0; rec.u = r[9]; rec.v = r[10];
+        rec.material = MAT((size_t)mat);
+        const Ray ray(V(ry), V(ry + 3), ry[6]);
+        Sampler smp; smp.rng = Rng::for_path(seed, k, 0);
+        double margin = F64_INF;
+#if !defined(ORC_NO_COUNTERS) && !defined(ORC_COUNT_OPS)
+        g_margin = &margin;
+#endif
+        Level L;
+        const bool scattered = ray_color_level(ray, rec, &SC->lights, smp, L);
+#if !defined(ORC_NO_COUNTERS) && !defined(ORC_COUNT_OPS)
+        g_margin = nullptr;
+#endif
+        Color b = V(beta), e(0.0, 0.0, 0.0);
+        Ray after = ray;
+        bool done = !scattered;
+        uint32_t left = depth_left;
+        if (scattered) {
+            after = L.child;
+            b = b * L.weigh(Color(1.0, 1.0, 1.0));
+            left--;
+            if (left == 0) done = true;                                                                // the child call returns 0, main.rs:42-45
+            if ((flags & 2u) && b[0] == 0.0 && b[1] == 0.0 && b[2] == 0.0) done = true;
+        } else e = L.emitted;
+        for (int i = 0; i < 3; i++) { o[i] = after.orig[i]; o[3 + i] = after.dir[i]; o[7 + i] = b[i]; o[10 + i] = e[i]; }
+        o[6] = after.tm; o[13] = done ? 1.0 : 0.0; o[14] = (double)left;
+        for (int i = 0; i < 4; i++) o[15 + i] = (double)smp.rng.s[i];
+        if (margin_out) margin_out[k] = margin;
+    }
+    SC->isotropic_scatters = iso_before;
+    return rc;
 }
 
 } // extern "C"

@@ -131,6 +131,15 @@ def _declare(lib) -> Backend:
     lib.orc_brdf_pdf_value.argtypes = [C.c_void_p, C.c_int, d3, d3, d3]
     lib.orc_brdf_pdf_generate.argtypes = [C.c_void_p, C.c_int, d3, d3, C.c_void_p, d3]
     lib.orc_ray_color.argtypes = [C.c_void_p, d3, d3, C.c_double, d3, C.c_uint64, C.c_void_p, d3]
+    lib.orc_ray_color_path.restype = None
+    lib.orc_ray_color_path.argtypes = [C.c_void_p, d3, d3, C.c_double, d3, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, d3]
+    lib.orc_hit_records.restype = None
+    lib.orc_hit_records.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.orc_libm.restype = None
+    lib.orc_libm.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.orc_shade_batch.restype = C.c_int
+    lib.orc_shade_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                    C.c_void_p, C.c_void_p]
     return be
 
 
@@ -217,3 +226,50 @@ def brdf_pdf_value(b, mat, r_in, r_out, normal):
 
 def brdf_pdf_generate(b, mat, r_in, normal, rng):
     out = _d(0, 0, 0); load().lib.orc_brdf_pdf_generate(b.h, mat.id, _d(*r_in), _d(*normal), rng.h, out); return list(out)
+
+
+def ray_color_path(b, o, d, time_, background, depth, seed, pixel, sample=0):
+    """orc_ray_color_path: ray_color along one ray on the stream rng_path(seed, pixel, sample)."""
+    out = _d(0, 0, 0)
+    load().lib.orc_ray_color_path(b.h, _d(*o), _d(*d), time_, _d(*background), depth, seed, pixel, sample, out)
+    return list(out)
+
+
+def hit_records(b, rays, seed=0):
+    """orc_hit_records: world.hit for n rays (n, 7) -> (n, 16) records in the product's query_hits layout (object and primitive fields -1)."""
+    ry = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+    out = np.zeros((len(ry), 16), np.float64)
+    load().lib.orc_hit_records(b.h, len(ry), ry.ctypes.data, int(seed), out.ctypes.data)
+    return out
+
+
+LIBM_OPS = ("", "sin", "cos", "tan", "atan", "atan2", "acos", "log", "log2", "pow")
+
+
+def libm(op, a, b=None):
+    """orc_libm: the libm the oracle is linked with (glibc) on arrays — op: a name of LIBM_OPS; b for atan2(a, b) and pow(a, b)."""
+    a = np.ascontiguousarray(a, np.float64).reshape(-1)
+    b = np.ascontiguousarray(a if b is None else b, np.float64).reshape(-1)
+    if len(a) != len(b):
+        raise ValueError("a and b differ in length")
+    out = np.zeros(len(a), np.float64)
+    load().lib.orc_libm(LIBM_OPS.index(op), len(a), a.ctypes.data, b.ctypes.data, out.ctypes.data)
+    return out
+
+
+def shade_batch(b, records, rays, beta=(1.0, 1.0, 1.0), seed=0, depth_left=50, flags=0):
+    """orc_shade_batch: one level of ray_color after the hit (the code ray_color runs) for n hit records (n, 16) in the product's
+    query_hits layout and their incoming rays (n, 7), record k on the stream rng_path(seed, k, 0) — the counterpart of the product's
+    rt_debug_shade, same (n, 19) columns — and per record the margin: the smallest scaled distance to its threshold of any comparison
+    whose operands depend on a libm result (inf: none).  flags: 2 stop on a zero beta, 4 Isotropic scatters."""
+    rec = np.ascontiguousarray(records, np.float64).reshape(-1, 16)
+    ry = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+    if len(rec) != len(ry):
+        raise ValueError("records and rays differ in length")
+    bt = np.ascontiguousarray(beta, np.float64).reshape(3)
+    out = np.zeros((len(rec), 19), np.float64)
+    margin = np.zeros(len(rec), np.float64)
+    if load().lib.orc_shade_batch(b.h, len(rec), rec.ctypes.data, ry.ctypes.data, bt.ctypes.data, int(seed), int(depth_left), int(flags),
+                                  out.ctypes.data, margin.ctypes.data) != 0:
+        raise RuntimeError("orc_shade_batch: a record names no material of this scene")
+    return out, margin

@@ -193,6 +193,9 @@ SIGNATURES = {
     "debug_onb": (_int, [_ptr, _u32, _ptr, _ptr, _ptr]),
     "debug_onb_table": (_int, [_ptr, _ptr, _ptr, _u32, c_u32_p]),
     "debug_short_forms": (_int, [_u32, _u32, _ptr, _ptr, _ptr]),
+    "debug_math": (_int, [_u32, _u32, _ptr, _ptr, _ptr]),
+    "debug_brdf": (_int, [_ptr, _u32, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _u32]),
+    "debug_shade": (_int, [_ptr, _u32, _ptr, _ptr, _ptr, _u64, _u32, _u32, _ptr]),
     "debug_primary_mask": (_int, [_ptr, _cam_p, _u32, _u32, _ptr, _u32, _ptr]),
     "debug_primary_mask_host": (_int, [_ptr, _cam_p, _u32, _u32, _ptr, _u32, _ptr]),
     "debug_trace_path": (_int, [_ptr, C.c_longlong, C.c_longlong]),

@@ -24,6 +24,7 @@
 #include "rt_albedo.h"
 #include "rt_moments.h"
 #include "rt_denoise_var.h"
+#include "rt_kat.h"
 
 using namespace rt;
 
@@ -1201,6 +1202,109 @@ int rt_debug_onb(rt_scene* sc, uint32_t n, const double* rects, const double* no
     for (uint32_t i = 0; i < n; i++)
         if (!(rects[i] >= 0.0 && rects[i] < (double)s.flat.rects.size() && rects[i] == std::floor(rects[i]))) return set_err("rt_debug_onb: rect index out of range");
     return run_kat(s, launch_onb_kat, n, rects, 8u, normals, 24u, out, 56u);
+}
+// Known-answer access to the shading side's arithmetic (csrc/rt_kat.hip): one device function per lane on caller operands, under either
+// code shape.  No scene.  Records per op: rt_kat.h KAT_RECORDS.  Host pointers.
+int rt_debug_math(uint32_t op, uint32_t n, const double* a, const double* b, double* out) {
+    const bool rest = (op & RT_KAT_REST_SHAPE) != 0u;
+    op &= ~(uint32_t)RT_KAT_REST_SHAPE;
+    if (op >= KAT_N_OPS) return set_err("rt_debug_math: no such op");
+    const uint32_t* rec = KAT_RECORDS[op];
+    if (!a || !out || (!b && rec[1] != 0u)) return set_err("null argument");
+    if (n == 0) return 0;
+    DeviceBuffer d_a, d_b, d_out;
+    const size_t na = (size_t)n * rec[0] * 8u, nb = (size_t)n * rec[1] * 8u, no = (size_t)n * rec[2] * 8u;
+    HIP_OK(d_a.alloc(na)); HIP_OK(d_out.alloc(no));
+    HIP_OK(hipMemcpy(d_a.get(), a, na, hipMemcpyHostToDevice));
+    if (nb) { HIP_OK(d_b.alloc(nb)); HIP_OK(hipMemcpy(d_b.get(), b, nb, hipMemcpyHostToDevice)); }
+    HIP_OK((rest ? launch_math_kat_rest : launch_math_kat_lean)(op, n, (const double*)d_a.get(), nb ? (const double*)d_b.get() : nullptr, (double*)d_out.get(), nullptr));
+    HIP_OK(hipMemcpy(out, d_out.get(), no, hipMemcpyDeviceToHost));
+    return 0;
+}
+// Material::brdf and PDF::BRDF value of one PBR material of the scene on the device (pbr_brdf, brdf_pdf_value: the functions shade_hit's
+// principled arm calls) for n caller (r_in, r_out, normal, base colour).  out: n x 4 = brdf[3], pdf value.  Host pointers.
+int rt_debug_brdf(rt_scene* sc, uint32_t n, int material, const double* r_in, const double* r_out, const double* normal, const double* base, double* out, uint32_t shape) {
+    if (!sc || !r_in || !r_out || !normal || !base || !out) return set_err("null argument");
+    if (shape != 0u && shape != RT_KAT_REST_SHAPE) return set_err("rt_debug_brdf: shape is 0 or RT_KAT_REST_SHAPE");
+    if (n == 0) return 0;
+    Scene& s = sc->s;
+    if (!flatten_for_render(s)) return -1;
+    if (material < 0 || (size_t)material >= s.flat.materials.size() || (s.flat.materials[(size_t)material].kind & MAT_KIND_MASK) != M_PBR)
+        return set_err("rt_debug_brdf: not a PBR material of this scene");
+    const double pidx = s.flat.materials[(size_t)material].albedo[0];
+    if (!(pidx >= 0.0 && pidx < (double)s.pbr.size())) return set_err("rt_debug_brdf: the material's parameter record is out of range");
+    std::vector<double> in((size_t)n * KAT_BRDF_IN);
+    for (size_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) { in[i * 12u + k] = r_in[i * 3u + k]; in[i * 12u + 3 + k] = r_out[i * 3u + k]; in[i * 12u + 6 + k] = normal[i * 3u + k]; in[i * 12u + 9 + k] = base[i * 3u + k]; }
+    Scene::DeviceCtx* cp = nullptr;
+    if (current_ctx(s, &cp)) return -1;
+    DeviceScene<double>& d = dev_of<double>(*cp);
+    if (ensure_uploaded<double>(s, d)) return -1;
+    KParams<double> P;
+    std::memset((void*)&P, 0, sizeof(P));
+    bind_tables(P, d, s.flat);
+    DeviceBuffer d_in, d_out;
+    HIP_OK(d_in.alloc(in.size() * 8u)); HIP_OK(d_out.alloc((size_t)n * KAT_BRDF_OUT * 8u));
+    HIP_OK(hipMemcpy(d_in.get(), in.data(), in.size() * 8u, hipMemcpyHostToDevice));
+    HIP_OK((shape ? launch_brdf_kat_rest : launch_brdf_kat_lean)(P, n, (uint32_t)pidx, (const double*)d_in.get(), (double*)d_out.get(), nullptr));
+    HIP_OK(hipMemcpy(out, d_out.get(), (size_t)n * KAT_BRDF_OUT * 8u, hipMemcpyDeviceToHost));
+    return 0;
+}
+// ONE call of shade_hit per record (csrc/rt_kat.hip): records in rt_query_hits' layout, rays n x 7.  Every index a record carries is checked
+// against the scene's tables here, before the launch.
+int rt_debug_shade(rt_scene* sc, uint32_t n, const double* records, const double* rays, const double beta[3], uint64_t seed, uint32_t depth_left,
+                   uint32_t flags, double* out) {
+    if (!sc || !records || !rays || !beta || !out) return set_err("null argument");
+    if (flags & ~(uint32_t)(RT_STOP_ON_ZERO | RT_ISOTROPIC_SCATTER | RT_KAT_REST_SHAPE | RT_KAT_NO_ONB_TABLE))
+        return set_err("rt_debug_shade takes RT_STOP_ON_ZERO, RT_ISOTROPIC_SCATTER, RT_KAT_REST_SHAPE and RT_KAT_NO_ONB_TABLE only");
+    if (n > 0x7FFFFFFFu) return set_err("too many records: n must be <= 2^31 - 1 (per-path RNG keys, csrc/rt_rng.h)");
+    if (depth_left == 0u) return set_err("rt_debug_shade: depth_left must be >= 1 (a path with no level left does not reach shade_hit)");
+    if (n == 0) return 0;
+    Scene& s = sc->s;
+    if (!flatten_for_render(s)) return -1;
+    const HostFlat& f = s.flat;
+    const bool rest = (flags & RT_KAT_REST_SHAPE) != 0u;
+    if (!rest && f.feats != 0u) return set_err("rt_debug_shade: the lean shape serves list scenes only (no feature bit); pass RT_KAT_REST_SHAPE");
+    std::vector<double> in((size_t)n * KAT_SHADE_IN, 0.0);
+    for (size_t i = 0; i < n; i++) {
+        const double* r = records + 16u * i; double* p = in.data() + KAT_SHADE_IN * i;
+        if (r[0] == 0.0) return set_err("rt_debug_shade: record " + std::to_string(i) + " is no hit");
+        double mat = r[11];
+        if (mat < 0.0) {                                           // a ConstantMedium's hit: its Isotropic was appended by the flattener
+            const double obj = r[12];
+            if (!(obj >= 0.0 && obj < (double)f.objects.size()) || f.objects[(size_t)obj].medium < 0 || (size_t)f.objects[(size_t)obj].medium >= f.media.size())
+                return set_err("rt_debug_shade: record " + std::to_string(i) + " names no material and no medium");
+            mat = (double)f.media[(size_t)f.objects[(size_t)obj].medium].mat;
+        }
+        if (!(mat >= 0.0 && mat < (double)f.materials.size() && mat == std::floor(mat))) return set_err("rt_debug_shade: record " + std::to_string(i) + ": material out of range");
+        double rect = 0.0;
+        if (!rest) {                                               // a list scene: every hit is a rect's, and its index names the ONB memo's entry
+            rect = r[14];
+            if (!(rect >= 0.0 && rect < (double)f.rects.size() && rect == std::floor(rect))) return set_err("rt_debug_shade: record " + std::to_string(i) + ": rect index out of range");
+        }
+        p[0] = r[2]; p[1] = r[3]; p[2] = r[4]; p[3] = r[5]; p[4] = r[6]; p[5] = r[7]; p[6] = r[1]; p[7] = r[9]; p[8] = r[10]; p[9] = r[8];
+        p[10] = mat; p[11] = rect;
+        for (int k = 0; k < 7; k++) p[12 + k] = rays[7u * i + k];
+    }
+    Scene::DeviceCtx* cp = nullptr;
+    if (current_ctx(s, &cp)) return -1;
+    DeviceScene<double>& d = dev_of<double>(*cp);
+    if (ensure_uploaded<double>(s, d)) return -1;
+    KParams<double> P;
+    std::memset((void*)&P, 0, sizeof(P));
+    bind_tables(P, d, f);
+    P.flags = flags & (uint32_t)(RT_STOP_ON_ZERO | RT_ISOTROPIC_SCATTER);
+    if (flags & RT_KAT_NO_ONB_TABLE) P.onb = nullptr;
+    DeviceBuffer d_in, d_out;
+    HIP_OK(d_in.alloc(in.size() * 8u)); HIP_OK(d_out.alloc((size_t)n * KAT_SHADE_OUT * 8u));
+    HIP_OK(hipMemcpy(d_in.get(), in.data(), in.size() * 8u, hipMemcpyHostToDevice));
+    ShadeKatArgs A;
+    A.n = n; A.in = (const double*)d_in.get(); A.out = (double*)d_out.get(); A.seed = seed; A.depth_left = depth_left;
+    for (int k = 0; k < 3; k++) A.beta[k] = beta[k];
+    if (rest) HIP_OK(launch_shade_kat_rest(P, A, (f.feats & F_NESTED) != 0u, nullptr));
+    else HIP_OK(launch_shade_kat_lean(P, A, nullptr));
+    HIP_OK(hipMemcpy(out, d_out.get(), (size_t)n * KAT_SHADE_OUT * 8u, hipMemcpyDeviceToHost));
+    return 0;
 }
 // The primary pass's pixel classifier (csrc/rt_primary.h) for n pixels (pixels: n x (i, j), j counted from the bottom row): bit k of
 // out_masks[p] set = top-level object k may be hit by a camera ray of that pixel.  The host twin needs no GPU; the device form runs

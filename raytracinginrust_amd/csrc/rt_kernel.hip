@@ -40,6 +40,11 @@
 #ifndef RT_TU
 #define RT_TU 0
 #endif
+// RT_SHAPE: which unit's code-generation choices (below) the device functions are compiled with.  It is the unit itself everywhere but in
+// the known-answer unit (csrc/rt_kat.hip, RT_TU == 4), which is compiled once per shape so that both can be run on caller operands.
+#ifndef RT_SHAPE
+#define RT_SHAPE RT_TU
+#endif
 // Minimum resident waves per SIMD the register allocation is held to (512 VGPRs / waves, in steps of 8), per kernel family.
 // *Measured* (round 2, A/B in one process, with -disable-machine-licm): the lock-step BVH kernels are faster at 4 waves with a few
 // dozen spilled registers than at 3 without (random spheres +6.6 %, final scene +10 %); the persistent-traversal mesh kernel is not
@@ -65,8 +70,8 @@ static constexpr int BOX_STEPS_PERSIST = 8;     // ... persistent loop (round 5,
 static constexpr uint32_t WW_NUM = 5u, WW_DEN = 8u;       // leaf step once 5/8 of the lanes still in a walk hold a pending leaf (3/8 until round 5)
 static constexpr uint32_t SPEC_NUM = 5u, SPEC_DEN = 8u;   // ... in the walk-ahead form (one-BVH worlds)
 // The kernels are two translation units (RT_TU, above) so that these two code-generation choices can differ between them:
-static constexpr bool SHARED_DIV3 = RT_TU == 2;  // shared-denominator Vec3 division: +3.8 % teapot room, +1.7 % final scene; -1.2 % Cornell box
-static constexpr bool MERGE_ARMS = RT_TU == 1;   // shade_hit: Lambertian's two sampling arms and Metal share their common instruction runs (round 4,
+static constexpr bool SHARED_DIV3 = RT_SHAPE == 2;  // shared-denominator Vec3 division: +3.8 % teapot room, +1.7 % final scene; -1.2 % Cornell box
+static constexpr bool MERGE_ARMS = RT_SHAPE == 1;  // shade_hit: Lambertian's two sampling arms and Metal share their common instruction runs (round 4,
                                                  // samples bit-identical): Cornell box +2.5 %; in the BVH kernels -3 ... -7 % (register allocation)
 // rt_short.h: exact short forms for f64 operations on constants of the scene or the frame, in the lean f64 kernel only (the sites test
 // sizeof(T) too: the lean f32 kernel keeps its instructions); samples bit-identical.  RT_SHORT_PARTS (A/B builds): bit 0 division by pi and
@@ -74,7 +79,7 @@ static constexpr bool MERGE_ARMS = RT_TU == 1;   // shade_hit: Lambertian's two 
 #ifndef RT_SHORT_PARTS
 #define RT_SHORT_PARTS 7
 #endif
-static constexpr bool SHORT_DIV = RT_TU == 1 && (RT_SHORT_PARTS & 1), SHORT_U01 = RT_TU == 1 && (RT_SHORT_PARTS & 2), SHORT_LPDF = RT_TU == 1 && (RT_SHORT_PARTS & 4);
+static constexpr bool SHORT_DIV = RT_SHAPE == 1 && (RT_SHORT_PARTS & 1), SHORT_U01 = RT_SHAPE == 1 && (RT_SHORT_PARTS & 2), SHORT_LPDF = RT_SHAPE == 1 && (RT_SHORT_PARTS & 4);
 
 // ------------------------------------------------------------------ small vector algebra (src/vec.rs)
 template <typename T> struct V3 { T x, y, z; };
@@ -91,13 +96,16 @@ template <typename T> DEV V3<T> operator*(T s, V3<T> a) { return mk<T>(s * a.x, 
 // three numerators (it rescales only at the ends of the exponent range).  Then it is computed once and each quotient
 // finishes with its own numerator: the same instructions on the same values, bit for bit the three separate divisions.
 // Otherwise (checked) the three plain divisions run.
-DEV V3<double> operator/(V3<double> a, double d) {
+// div3 (also called by the known-answer unit, csrc/rt_kat.hip): `shared` says which form the lane took.
+DEV V3<double> div3(V3<double> a, double d, bool& shared) {
+    shared = false;
     if (!SHARED_DIV3) return mk<double>(a.x / d, a.y / d, a.z / d);
     bool fx, fy, fz, unused;
     const double d0 = __builtin_amdgcn_div_scale(a.x, d, false, &unused);
     const double d1 = __builtin_amdgcn_div_scale(a.y, d, false, &unused);
     const double d2 = __builtin_amdgcn_div_scale(a.z, d, false, &unused);
     if (__double_as_longlong(d0) == __double_as_longlong(d1) && __double_as_longlong(d0) == __double_as_longlong(d2)) {
+        shared = true;
         const double nd = -d0;
         double r = __builtin_amdgcn_rcp(d0);
         r = __builtin_fma(r, __builtin_fma(nd, r, 1.0), r);
@@ -114,6 +122,7 @@ DEV V3<double> operator/(V3<double> a, double d) {
     }
     return mk<double>(a.x / d, a.y / d, a.z / d);
 }
+DEV V3<double> operator/(V3<double> a, double d) { bool shared; return div3(a, d, shared); }
 DEV V3<float> operator/(V3<float> a, float s) { return mk<float>(a.x / s, a.y / s, a.z / s); }
 template <typename T> DEV T dot(V3<T> a, V3<T> b) { return a.x * b.x + a.y * b.y + a.z * b.z; }                  // vec.rs:38-40
 template <typename T> DEV V3<T> cross(V3<T> a, V3<T> b) { return mk<T>(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }   // vec.rs:46-54
@@ -179,8 +188,9 @@ DEV void m_sincos(float x, float& sn, float& cs) { ::sincosf(x, &sn, &cs); }
 // of its ~150 instructions on argument reduction for arbitrary magnitudes; here the range is known, so: k = nearest
 // integer to phi * 2/pi (0..4), r = phi - k*pi/2 with a two-word pi/2 (Cody-Waite, exact products via fma), then the
 // classic minimax kernels on [-pi/4, pi/4] (coefficients of the fdlibm __kernel_sin/__kernel_cos polynomials).  Measured
-// on the host against long double over 2e7 arguments: max error 0.78 ulp, 96.9 % of results bit-equal to glibc — the same
-// class as the device libm (neither is correctly rounded); f64 only.
+// on the device against mpmath (tests/test_shade_kat_gpu.py: phi = 2 pi r1 for 8 000 random r1 and every quadrant boundary
+// +- 3 ulp): max error 0.754 ulp (sin), 0.682 ulp (cos), signs exact at the boundaries — the same class as the device libm
+// (sin 0.71, cos 0.78 ulp on their own sets; neither is correctly rounded); f64 only.
 DEV void sincos_0_2pi(double phi, double& sn, double& cs) {
     const double two_over_pi = 6.36619772367581382433e-01;
     const double pio2_hi = 1.57079632673412561417e+00;     // first 33 bits of pi/2
@@ -2711,7 +2721,7 @@ __global__ void __launch_bounds__(Shape<FEATS>::THREADS, Shape<FEATS>::WAVES_PER
     }
 }
 
-#if RT_TU != 3      // (RT_TU == 3: csrc/rt_query.hip includes this file for the device functions above and brings its own kernels and launch code)
+#if RT_TU != 3 && RT_TU != 4      // (RT_TU == 3: csrc/rt_query.hip includes this file for the device functions above and brings its own kernels and launch code; 4: csrc/rt_kat.hip)
 // ------------------------------------------------------------------ launch
 template <typename T, uint32_t FEATS>
 static hipError_t allow_lds(size_t shmem) {            // more than the default 64 KB of dynamic LDS needs to be asked for
@@ -2890,11 +2900,11 @@ template hipError_t launch_pathtrace<float>(const KParams<float>&, uint32_t, uin
 template int pathtrace_blocks_per_cu<double>(uint32_t, uint32_t, size_t);
 template int pathtrace_blocks_per_cu<float>(uint32_t, uint32_t, size_t);
 #endif
-#endif      // RT_TU != 3
+#endif      // RT_TU != 3 && RT_TU != 4
 
 } // namespace rt
 
-#if RT_TU != 1 && RT_TU != 3
+#if RT_TU != 1 && RT_TU != 3 && RT_TU != 4
 // ------------------------------------------------------------------ known-answer access to AABB::hit on the device (tests only)
 namespace rt {
 __global__ void aabb_kat_kernel(uint32_t n, const double* boxes, const double* rays, const double* tlim, int* out) {
@@ -3042,7 +3052,7 @@ extern "C" int rt_debug_cube_hit(uint32_t n, double rect_m, const double* boxes,
 }
 #endif
 
-#if RT_TU != 2 && RT_TU != 3
+#if RT_TU != 2 && RT_TU != 3 && RT_TU != 4
 // Known-answer access to the short forms of the lean f64 kernel (rt::short_forms_kat_kernel above says what each op computes).  Records of
 // doubles per operand: op 0: a 1, b 1, out 3; op 1: a 1, b 2, out 1; op 2: a 1 (the u64's bits), b unused (may be null), out 1; op 3: a 3, b 3,
 // out 2.  Host pointers.

@@ -147,6 +147,61 @@ def debug_short_forms(op: int, a: np.ndarray, b: np.ndarray | None = None) -> np
     return out[:, 0].copy() if out_cols == 1 else out
 
 
+KAT_OPS = ("sincos_0_2pi", "sin", "cos", "tan", "atan", "atan2", "acos", "log", "log2", "pow", "div3", "onb_from_w",
+           "GTR_1", "GTR_2_aniso", "smithG_GGX", "smithG_GGX_aniso", "schlick_fresnel")
+KAT_RECORDS = ((1, 0, 2), (1, 0, 1), (1, 0, 1), (1, 0, 1), (1, 0, 1), (1, 1, 1), (1, 0, 1), (1, 0, 1), (1, 0, 1), (1, 1, 1),
+               (3, 1, 4), (3, 0, 9), (1, 1, 1), (3, 2, 1), (1, 1, 1), (3, 2, 1), (1, 0, 1))
+KAT_SHAPES = {"lean": 0, "rest": 0x100}
+
+
+def debug_math(op: str, a: np.ndarray, b: np.ndarray | None = None, shape: str = "lean") -> np.ndarray:
+    """rt_debug_math (needs a GPU): one shading-side device function of rt_kernel.hip per lane on caller operands, f64, under the code
+    shape of the lean unit or of the rest (KAT_SHAPES).  op: a name of KAT_OPS; a, b: (n, cols) as KAT_RECORDS says; -> (n, out cols),
+    or (n,) where the op gives one value.  div3: the three quotients, then 1.0 where the lane took the shared-denominator form."""
+    k = KAT_OPS.index(op)
+    a_cols, b_cols, out_cols = KAT_RECORDS[k]
+    a = np.ascontiguousarray(a, np.float64).reshape(-1, a_cols)
+    if b_cols:
+        b = np.ascontiguousarray(b, np.float64).reshape(-1, b_cols)
+        if len(a) != len(b):
+            raise ValueError("a and b differ in length")
+    out = np.zeros((len(a), out_cols), np.float64)
+    _check(_rt().rt_debug_math(k | KAT_SHAPES[shape], len(a), a.ctypes.data, b.ctypes.data if b_cols else None, out.ctypes.data))
+    return out[:, 0].copy() if out_cols == 1 else out
+
+
+def debug_brdf(b: SceneBuilder, material: int, r_in: np.ndarray, r_out: np.ndarray, normal: np.ndarray, base: np.ndarray,
+               shape: str = "lean") -> np.ndarray:
+    """rt_debug_brdf (needs a GPU): Material::brdf and PDF::BRDF value of a PBR material of the scene on the device, for n records of
+    (r_in, r_out, normal, base colour), each (n, 3) -> (n, 4): brdf[3], pdf value."""
+    arrs = [np.ascontiguousarray(x, np.float64).reshape(-1, 3) for x in (r_in, r_out, normal, base)]
+    if len({len(x) for x in arrs}) != 1:
+        raise ValueError("r_in, r_out, normal and base differ in length")
+    out = np.zeros((len(arrs[0]), 4), np.float64)
+    _check(_rt().rt_debug_brdf(b.h, len(out), int(material), *[x.ctypes.data for x in arrs], out.ctypes.data, KAT_SHAPES[shape]))
+    return out
+
+
+RT_KAT_REST_SHAPE, RT_KAT_NO_ONB_TABLE = 0x100, 0x200
+SHADE_FIELDS = {"ray": slice(0, 7), "beta": slice(7, 10), "e": slice(10, 13), "done": 13, "depth_left": 14, "state": slice(15, 19)}
+
+
+def debug_shade(b: SceneBuilder, records: np.ndarray, rays: np.ndarray, beta=(1.0, 1.0, 1.0), seed: int = 0, depth_left: int = 50,
+                flags: int = 0, shape: str = "lean", onb_table: bool = True) -> np.ndarray:
+    """rt_debug_shade (needs a GPU): ONE call of the kernels' shade_hit per record — records (n, 16) as query_hits gives them, rays (n, 7),
+    record k on the stream rt_rng_path(seed, k, 0) — under the lean instantiation and code shape (list scenes; onb_table=False: without
+    the ONB memo) or the all-features one (shape="rest").  flags: RT_STOP_ON_ZERO, RT_ISOTROPIC_SCATTER.  -> (n, 19), columns SHADE_FIELDS."""
+    rec = np.ascontiguousarray(records, np.float64).reshape(-1, 16)
+    ry = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+    if len(rec) != len(ry):
+        raise ValueError("records and rays differ in length")
+    bt = np.ascontiguousarray(beta, np.float64).reshape(3)
+    out = np.zeros((len(rec), 19), np.float64)
+    fl = int(flags) | KAT_SHAPES[shape] | (0 if onb_table else RT_KAT_NO_ONB_TABLE)
+    _check(_rt().rt_debug_shade(b.h, len(rec), rec.ctypes.data, ry.ctypes.data, bt.ctypes.data, int(seed), int(depth_left), fl, out.ctypes.data))
+    return out
+
+
 def debug_light_pdf(b: SceneBuilder, origins: np.ndarray, dirs: np.ndarray) -> np.ndarray:
     """rt_debug_light_pdf (needs a GPU): the scene's `lights` pdf_value (HittableList::pdf_value, nested lists included) for n
     (origin, direction) pairs, computed on the device by the function the all-features kernel with object leaves runs."""
