@@ -384,6 +384,15 @@ public:
     std::vector<uint8_t> rgb8_denoised_variance(const DenoiseVarianceSettings& d = DenoiseVarianceSettings()) {
         std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_denoised_variance_rgb8(p_, d.iterations, d.sigma, d.flags, out.data())); return out;
     }
+    // adaptive sampling (rt_progressive_enable_adaptive): per-pixel sample counts on a frame with moments, only while it holds 0 samples.
+    // add_adaptive: one pass of n_samples over the pixels whose estimated standard error exceeds tau (spread = 1: and their 8 neighbours)
+    // and that stay within max_samples (0: 2^32 - 1); listed == 0 is the stop condition, nothing was rendered
+    struct AdaptiveInfo { uint64_t listed, samples, total, kernel; };      // pixels sampled, samples rendered, the sum of all counts, 0 the frames' / 1 the list kernel
+    void enable_adaptive() { chk(rt_progressive_enable_adaptive(p_)); }
+    AdaptiveInfo add_adaptive(uint32_t n_samples, double tau, uint64_t max_samples = 0, uint32_t spread = 1) {
+        uint64_t w[4]; chk(rt_progressive_add_adaptive(p_, n_samples, tau, max_samples, spread, w)); return AdaptiveInfo{w[0], w[1], w[2], w[3]};
+    }
+    std::vector<uint32_t> counts() const { std::vector<uint32_t> out(n_px_); chk(rt_progressive_read_counts(p_, out.data(), nullptr)); return out; }      // n[p], W*H
 private:
     static void chk(int rc) { if (rc != 0) throw Error(rt_last_error()); }
     void* p_; size_t n_px_;

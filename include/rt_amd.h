@@ -301,6 +301,78 @@ int rt_moments_variance_device(const void* d_rgb_sum, const void* d_sq_sum, uint
                                void* d_var_out, void* hip_stream);
 int rt_progressive_variance(void* frame, double* var_out);
 
+/* ---- adaptive frames: a progressive frame with moments knows, pixel by pixel, which pixels are finished; an ADAPTIVE frame stops sampling
+ *      them.  THE INVARIANT: pixel p of an adaptive frame with count n[p] holds exactly samples 0 .. n[p] - 1 of the streams
+ *      rt_rng_path(seed, p, s) — the very samples rt_render with the same view and seed holds at those indices.  A pass has ONE size n_b:
+ *      a listed pixel receives samples [n[p], n[p] + n_b); no seed folding, the kernel reads the pixel's own first sample.  Per pixel,
+ *      beside the sums S and the second moments Q: n[p] (uint32) the samples done, b[p] (uint32) the passes the pixel took part in.
+ *      csrc/rt_adaptive.h is the exact specification — (A) the error with counts: e2 of rt_moments_error_* with (n[p], b[p]) in the frame's
+ *      counts' place, +inf while b[p] < 2; (B) the selection: need = b < 2 or e2 finite and > tau*tau; with spread = 1 also the pixels with
+ *      a needing neighbour (8-neighbourhood inside the frame: a pixel whose passes held no bright path yet looks converged, its neighbours
+ *      know better); active = needed and n + n_b <= max_samples; the LIST is the active pixels' output-order indices in ASCENDING order;
+ *      (C) the list merge: rt_moments_merge_* for the listed pixels, pass frame zeroed, n += n_b, b += 1, nothing else read or written;
+ *      (D) the resolve: rt_format_color(S[p], n[p]), 0 where n[p] = 0 — and the host forms, the HIP kernels (csrc/rt_adaptive.hip) and the
+ *      NumPy restatement of tests/adaptive_cases.py give the same words.
+ * The path-tracing building block: n_samples samples of every pixel of d_list (n_list output-order indices, uint32, DEVICE memory) of the
+ * W x H view, ADDED to d_out (W*H*3 doubles, output order, 8-byte aligned: a pass frame): pixel p receives samples [d_counts[p], + n_samples)
+ * (d_counts: W*H uint32 in DEVICE memory, or NULL for first sample 0 everywhere).  f64 and the reference's traversal order only: flags may
+ * hold RT_STOP_ON_ZERO and RT_ISOTROPIC_SCATTER.  Enqueued on hip_stream, never waits, never allocates; a scene not yet on the device is
+ * uploaded first (rt_scene_prepare).  n_list = 0 is a no-op.  A list entry that is not a pixel of the frame, or whose count + n_samples
+ * would pass 2^32 - 1 (the sample field of a path's RNG key), is skipped on the device: nothing is traced or written for it — rt_adaptive_select_*
+ * never lists such a pixel, and the frame calls below refuse such a pass on the host.  rt_last_query_ms reports the kernel. */
+int rt_render_pixels_device(rt_scene*, const rt_camera*, const double background[3], uint32_t W, uint32_t H,
+                            uint32_t n_samples, uint32_t max_depth, uint64_t seed, uint32_t flags,
+                            const void* d_list, uint32_t n_list, const void* d_counts, void* d_out, size_t d_out_bytes, void* hip_stream);
+/* (A): e2_out (W*H doubles) and stats_out (the four words of rt_moments_stats_host for tau) may each be NULL.  The host form needs no
+ * device; the device form only enqueues (d_stats_out is zeroed in stream order by the call).  Errors: null pointers, W*H = 0 or > 2^31 - 1,
+ * tau negative or NaN (looked at only with stats). */
+int rt_adaptive_error_host(const double* rgb_sum, const double* sq_sum, const uint32_t* counts, const uint32_t* passes, uint32_t W, uint32_t H,
+                           double* e2_out, double tau, uint64_t stats_out[4]);
+int rt_adaptive_error_device(const void* d_rgb_sum, const void* d_sq_sum, const void* d_counts, const void* d_passes, uint32_t W, uint32_t H,
+                             void* d_e2_out, double tau, void* d_stats_out, void* hip_stream);
+/* (B): the list (room for W*H uint32) and its length.  The device form needs rt_adaptive_select_workspace_bytes(W, H) bytes of 16-byte
+ * aligned DEVICE memory (about 2 bytes per pixel) and writes the length to d_n_list_out (one uint32, DEVICE memory): count, scan, scatter,
+ * four launches, no wait.  Errors: null pointers, the frame as above, n_samples = 0, tau negative or NaN, max_samples > 2^32 - 1, spread > 1. */
+int rt_adaptive_select_host(const double* rgb_sum, const double* sq_sum, const uint32_t* counts, const uint32_t* passes, uint32_t W, uint32_t H,
+                            uint32_t n_samples, double tau, uint64_t max_samples, uint32_t spread, uint32_t* list_out, uint32_t* n_list_out);
+size_t rt_adaptive_select_workspace_bytes(uint32_t W, uint32_t H);
+int rt_adaptive_select_device(const void* d_rgb_sum, const void* d_sq_sum, const void* d_counts, const void* d_passes, uint32_t W, uint32_t H,
+                              uint32_t n_samples, double tau, uint64_t max_samples, uint32_t spread, void* d_list_out, void* d_n_list_out,
+                              void* d_workspace, size_t workspace_bytes, void* hip_stream);
+/* (C).  The host form checks its list (ascending, inside the frame, count + n_samples <= 2^32 - 1) before it writes anything; the device
+ * form cannot and relies on a list of rt_adaptive_select_device's making. */
+int rt_adaptive_merge_host(double* pass_sum, uint32_t n_samples, double* rgb_sum, double* sq_sum, uint32_t* counts, uint32_t* passes,
+                           const uint32_t* list, uint32_t n_list, uint32_t W, uint32_t H);
+int rt_adaptive_merge_device(void* d_pass_sum, uint32_t n_samples, void* d_rgb_sum, void* d_sq_sum, void* d_counts, void* d_passes,
+                             const void* d_list, uint32_t n_list, void* hip_stream);
+/* (D): rgb8_out (W*H*3 bytes) and the number of pixels whose triple differs from rgb8_prev's (NULL: every pixel counts).  The device form
+ * ADDS that number to *d_changed_px_out (one 64-bit word, may be NULL; the caller zeroes it in stream order). */
+int rt_adaptive_resolve_rgb8_host(const double* rgb_sum, const uint32_t* counts, uint32_t W, uint32_t H, const uint8_t* rgb8_prev, uint8_t* rgb8_out,
+                                  uint64_t* changed_px_out);
+int rt_adaptive_resolve_rgb8_device(const void* d_rgb_sum, const void* d_counts, uint32_t W, uint32_t H, const void* d_rgb8_prev, void* d_rgb8_out,
+                                    void* d_changed_px_out, void* hip_stream);
+/* A progressive frame with moments becomes adaptive: allowed only while it holds 0 samples; allocates the counts, the list and the selection's
+ * workspace (about 14 more bytes per pixel).  An error without moments, and when the frame's flags hold anything but RT_STOP_ON_ZERO and
+ * RT_ISOTROPIC_SCATTER (the list kernel runs f64 and the reference's traversal order only).  From then on:
+ *   rt_progressive_add is a pass over ALL pixels; rt_progressive_add_async is an error; rt_progressive_samples returns the largest n[p];
+ *   rt_progressive_resolve_rgb8* use (D); error_map, error_map_device and error_stats use (A) (they need two passes of the frame, not of every pixel);
+ *   rt_progressive_reset zeroes the counts; rt_progressive_read_sum / read_moments work as before;
+ *   rt_progressive_variance, the three denoised resolves, rt_progressive_load_sum and rt_progressive_load_moments are errors while the counts
+ *   are not uniform (all n[p] equal and all b[p] equal, which the host tracks), and behave as before while they are.
+ * While every pixel is listed and the frame is uniform a pass goes through the launch rt_progressive_add uses — the frames' own kernels are
+ * the fast ones — followed by (C) over all pixels; otherwise through rt_render_pixels_device and the list merge. */
+int rt_progressive_enable_adaptive(void* frame);
+/* Select (B) with (n_samples, tau, max_samples, spread), render the listed pixels, merge (C), wait.  info_out: [0] the listed pixels, [1] the
+ * samples rendered by this pass (listed * n_samples), [2] the sum of n[p] over the frame afterwards, [3] the kernel used: 0 = the frames'
+ * kernel, 1 = the list kernel.  With nothing listed it renders nothing and returns 0 with info_out[0] = 0: the stop condition.  max_samples =
+ * 0 means 2^32 - 1.  Errors, nothing launched: not an adaptive frame, n_samples = 0, tau negative or NaN, max_samples > 2^32 - 1, spread > 1,
+ * the scene destroyed or changed. */
+int rt_progressive_add_adaptive(void* frame, uint32_t n_samples, double tau, uint64_t max_samples, uint32_t spread, uint64_t info_out[4]);
+/* The counts (W*H uint32 each; either may be NULL; waits): with read_sum and read_moments, a checkpoint — which rt_progressive_load_adaptive
+ * resumes from.  Errors of the load: not an adaptive frame, b[p] > n[p], n[p] = 0 with a pixel that is not all zero. */
+int rt_progressive_read_counts(void* frame, uint32_t* counts_out, uint32_t* passes_out);
+int rt_progressive_load_adaptive(void* frame, const double* rgb_sum, const double* sq_sum, const uint32_t* counts, const uint32_t* passes);
+
 /* ---- ray queries: the reference's `world.hit(r, 0.00001, f64::INFINITY)` (src/main.rs:48, Hittable::hit) as a function of its own — the
  *      closest hit of rays the caller chooses, or of the camera rays of one sample of every pixel: which object is under pixel (i, j), how far
  *      away it is (auto-focus), depth / normal / material-id frames for a denoiser or a compositor, visibility probes.  The search and the

@@ -120,6 +120,21 @@ SIGNATURES = {
     "moments_variance_host": (_int, [_ptr, _ptr, _u64, _u64, _u32, _u32, _ptr]),
     "moments_variance_device": (_int, [_ptr, _ptr, _u64, _u64, _u32, _u32, _ptr, _ptr]),
     "progressive_variance": (_int, [_ptr, _ptr]),
+    # adaptive frames: per-pixel sample counts, the pixel-list kernel
+    "render_pixels_device": (_int, _FRAME + [_ptr, _u32, _ptr, _ptr, C.c_size_t, _ptr]),
+    "adaptive_error_host": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _f64, c_u64_p]),
+    "adaptive_error_device": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _f64, _ptr, _ptr]),
+    "adaptive_select_host": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _f64, _u64, _u32, _ptr, c_u32_p]),
+    "adaptive_select_workspace_bytes": (C.c_size_t, [_u32, _u32]),
+    "adaptive_select_device": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _f64, _u64, _u32, _ptr, _ptr, _ptr, C.c_size_t, _ptr]),
+    "adaptive_merge_host": (_int, [_ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32]),
+    "adaptive_merge_device": (_int, [_ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr]),
+    "adaptive_resolve_rgb8_host": (_int, [_ptr, _ptr, _u32, _u32, _ptr, _ptr, c_u64_p]),
+    "adaptive_resolve_rgb8_device": (_int, [_ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr, _ptr]),
+    "progressive_enable_adaptive": (_int, [_ptr]),
+    "progressive_add_adaptive": (_int, [_ptr, _u32, _f64, _u64, _u32, c_u64_p]),
+    "progressive_read_counts": (_int, [_ptr, _ptr, _ptr]),
+    "progressive_load_adaptive": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr]),
     # ray queries
     "camera_ray": (_int, [_cam_p, _u32, _u32, _u32, _u32, _u64, _u32, c_double_p]),
     "query_hits": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _ptr]),

@@ -24,6 +24,8 @@
 #include "rt_albedo.h"
 #include "rt_moments.h"
 #include "rt_denoise_var.h"
+#include "rt_adaptive.h"
+#include "rt_pixels.h"
 #include "rt_kat.h"
 
 using namespace rt;
@@ -69,6 +71,12 @@ struct Progressive {
     // rt_progressive_variance / rt_progressive_resolve_denoised_variance_rgb8: the per-channel variance frame (rt_moments.h (4)) of the sums
     // as they are at that call, allocated at the first one (24 bytes per pixel)
     void* d_var = nullptr;
+    // rt_progressive_enable_adaptive (rt_adaptive.h): per-pixel counts n (d_cnt) and b (d_pas), the pixel list of a pass with its length and
+    // the largest count behind a list merge (d_words: two uint32), and the selection's workspace.  `uniform`: every n[p] equals `done` and
+    // every b[p] equals `passes` — true until the first pass over a proper subset; from then on `done` is the largest n[p] and `passes` the
+    // passes of the frame.  total: the sum of n[p].
+    bool adaptive = false, uniform = true; uint64_t total = 0;
+    void* d_cnt = nullptr; void* d_pas = nullptr; void* d_list = nullptr; void* d_words = nullptr; void* d_sel_ws = nullptr;
     size_t n_px() const { return (size_t)W * H; }
 };
 
@@ -1709,6 +1717,12 @@ int rt_query_radiance(rt_scene* sc, uint32_t n, const double* rays, const double
 // ---------------------------------------------------------------- progressive frames
 // (the reference's loop prints `Scanlines remaining` while it works, src/main.rs:772-775, and formats each pixel as it is finished,
 // src/main.rs:832: a frame that accumulates passes of samples and can be resolved to the 8-bit image at any time is that, per pass)
+// what a call that knows one sample count for the whole frame checks first on an adaptive frame
+static int adaptive_needs_uniform(const Progressive* p, const char* what) {
+    if (p && p->adaptive && !p->uniform)
+        return set_err(std::string(what) + ": the pixels of this adaptive frame hold different sample counts, and this call knows one count for the whole frame (rt_progressive_read_counts has them; denoising frames with non-uniform counts is not supported)");
+    return 0;
+}
 static void progressive_free(Progressive* p) {
     DeviceGuard guard(p->device);
     (void)hipDeviceSynchronize();                   // passes and resolves may still be in flight on the caller's streams
@@ -1716,6 +1730,7 @@ static void progressive_free(Progressive* p) {
     free_dev(p->d_dn_ws); free_dev(p->d_dn_sum); free_dev(p->d_dn_rgb8); free_dev(p->d_dn_changed);
     free_dev(p->d_alb_sum); free_dev(p->d_alb_x);
     free_dev(p->d_sq); free_dev(p->d_pass); free_dev(p->d_e2); free_dev(p->d_mstats); free_dev(p->d_var);
+    free_dev(p->d_cnt); free_dev(p->d_pas); free_dev(p->d_list); free_dev(p->d_words); free_dev(p->d_sel_ws);
     if (p->ev_merged) { (void)hipEventDestroy(p->ev_merged); p->ev_merged = nullptr; }
 }
 void* rt_progressive_create(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t max_depth,
@@ -1765,6 +1780,8 @@ static int progressive_pass(Progressive* p, uint32_t n, void* d_samples, hipStre
         if (render_any(p->sc, &p->cam, p->bg, p->W, p->H, n, p->max_depth, p->seed, p->flags, (uint32_t)n_px, 0, 1, p->d_pass, n_px * 3 * sizeof(double),
                        d_samples, stream, may_calibrate, (uint32_t)p->done, true)) return -1;
         HIP_OK((hipError_t)launch_moments_merge((double*)p->d_pass, n, (double*)p->d_sum, (double*)p->d_sq, (uint64_t)n_px * 3u, stream));
+        // (an adaptive frame comes here only while it is uniform: (C) over all pixels is the merge above and the counts)
+        if (p->adaptive) { HIP_OK((hipError_t)launch_adaptive_bump((uint32_t*)p->d_cnt, (uint32_t*)p->d_pas, n, (uint32_t)n_px, stream)); p->total += (uint64_t)n_px * n; }
         HIP_OK(hipEventRecord(p->ev_merged, stream));
         p->merge_recorded = true;
         p->done += n; p->passes++;
@@ -1775,9 +1792,11 @@ static int progressive_pass(Progressive* p, uint32_t n, void* d_samples, hipStre
     p->done += n;
     return 0;
 }
+static int adaptive_pass_over_all(Progressive* p, uint32_t n, double* samples_out);
 int rt_progressive_add(void* frame, uint32_t n, double* samples_out) {
     Progressive* p = (Progressive*)frame;
     if (progressive_pass_args(p, n)) return -1;
+    if (p->adaptive && !p->uniform) return adaptive_pass_over_all(p, n, samples_out);
     DeviceGuard guard(p->device);
     DeviceBuffer d_samples;
     const size_t sample_bytes = p->n_px() * n * 3 * sizeof(double);
@@ -1790,6 +1809,7 @@ int rt_progressive_add(void* frame, uint32_t n, double* samples_out) {
 int rt_progressive_add_async(void* frame, uint32_t n, void* hip_stream) {
     Progressive* p = (Progressive*)frame;
     if (progressive_pass_args(p, n)) return -1;
+    if (p->adaptive) return set_err("rt_progressive_add_async: not available on an adaptive frame (a pass selects, renders, merges and waits: rt_progressive_add, rt_progressive_add_adaptive)");
     DeviceGuard guard(p->device);
     return progressive_pass(p, n, nullptr, (hipStream_t)hip_stream, false);
 }
@@ -1807,8 +1827,12 @@ int rt_progressive_resolve_rgb8_device(void* frame, void** d_rgb8_out, void* hip
     hipStream_t stream = (hipStream_t)hip_stream;
     const int next = 1 - p->cur;
     HIP_OK(hipMemsetAsync(p->d_changed, 0, sizeof(unsigned long long), stream));
-    HIP_OK(launch_resolve_rgb8((const double*)p->d_sum, p->done, p->have_prev ? (const uint8_t*)p->d_rgb8[p->cur] : nullptr, (uint8_t*)p->d_rgb8[next],
-                               (unsigned long long*)p->d_changed, (uint32_t)p->n_px(), stream));
+    if (p->adaptive)
+        HIP_OK((hipError_t)launch_adaptive_resolve((const double*)p->d_sum, (const uint32_t*)p->d_cnt, p->have_prev ? (const uint8_t*)p->d_rgb8[p->cur] : nullptr,
+                                                   (uint8_t*)p->d_rgb8[next], (unsigned long long*)p->d_changed, (uint32_t)p->n_px(), stream));
+    else
+        HIP_OK(launch_resolve_rgb8((const double*)p->d_sum, p->done, p->have_prev ? (const uint8_t*)p->d_rgb8[p->cur] : nullptr, (uint8_t*)p->d_rgb8[next],
+                                   (unsigned long long*)p->d_changed, (uint32_t)p->n_px(), stream));
     p->cur = next; p->have_prev = true; p->resolved = true;
     if (d_rgb8_out) *d_rgb8_out = p->d_rgb8[next];
     return 0;
@@ -1855,6 +1879,11 @@ static int progressive_restart(Progressive* p, const double* rgb_sum, uint64_t s
         p->passes = 0;
         HIP_OK(hipMemsetAsync(p->d_sq, 0, p->n_px() * 3 * sizeof(double), nullptr));
         HIP_OK(hipMemsetAsync(p->d_pass, 0, p->n_px() * 3 * sizeof(double), nullptr));
+        if (p->adaptive) {                              // every pixel holds samples_done samples of 0 passes (the loads set the passes afterwards)
+            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)p->d_cnt, (int)(uint32_t)samples_done, p->n_px(), nullptr));
+            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)p->d_pas, 0, p->n_px(), nullptr));
+            p->uniform = true; p->total = (uint64_t)p->n_px() * samples_done;
+        }
         HIP_OK(hipStreamSynchronize(nullptr));
     }
     return 0;
@@ -1864,6 +1893,7 @@ int rt_progressive_load_sum(void* frame, const double* rgb_sum, uint64_t samples
     if (!rgb_sum) return set_err("null argument");
     if (samples_done > 0xFFFFFFFFull) return set_err("samples_done must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
     if (!p) return set_err("null argument");
+    if (adaptive_needs_uniform(p, "rt_progressive_load_sum")) return -1;
     if (samples_done == 0) {                        // 0 samples is the empty frame and nothing else (-0.0 is not empty either: its bits are a checkpoint's)
         const size_t n = p->n_px() * 3;
         for (size_t i = 0; i < n; i++) { uint64_t w; std::memcpy(&w, rgb_sum + i, sizeof(w)); if (w != 0) return set_err("samples_done = 0 with a non-zero frame: a checkpoint is a sum AND its sample count"); }
@@ -1957,6 +1987,7 @@ int rt_progressive_load_moments(void* frame, const double* rgb_sum, const double
     Progressive* p = (Progressive*)frame;
     if (!rgb_sum || !sq_sum) return set_err("null argument");
     if (moments_frame(p)) return -1;
+    if (adaptive_needs_uniform(p, "rt_progressive_load_moments")) return -1;
     if (samples_done > 0xFFFFFFFFull) return set_err("samples_done must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
     if (passes > samples_done) return set_err("passes must be <= samples_done: a pass holds at least one sample");
     if ((samples_done == 0) != (passes == 0)) return set_err("samples_done = 0 and passes = 0 go together: a checkpoint is the sums, the second moments, the sample count AND the pass count");
@@ -1970,6 +2001,7 @@ int rt_progressive_load_moments(void* frame, const double* rgb_sum, const double
     if (progressive_restart(p, rgb_sum, samples_done)) return -1;
     DeviceGuard guard(p->device);
     HIP_OK(hipMemcpy(p->d_sq, sq_sum, p->n_px() * 3 * sizeof(double), hipMemcpyHostToDevice));
+    if (p->adaptive) { HIP_OK(hipMemsetD32Async((hipDeviceptr_t)p->d_pas, (int)(uint32_t)passes, p->n_px(), nullptr)); HIP_OK(hipStreamSynchronize(nullptr)); }
     p->passes = passes; p->moments_valid = true;
     return 0;
 }
@@ -1978,7 +2010,11 @@ int rt_progressive_error_map_device(void* frame, void** d_e2_out, void* hip_stre
     if (moments_error_ready(p)) return -1;
     DeviceGuard guard(p->device);
     if (!p->d_e2) HIP_OK(hipMalloc(&p->d_e2, p->n_px() * sizeof(double)));
-    HIP_OK((hipError_t)launch_moments_error((const double*)p->d_sum, (const double*)p->d_sq, p->done, p->passes, (uint32_t)p->n_px(), (double*)p->d_e2, 0.0, nullptr, hip_stream));
+    if (p->adaptive)
+        HIP_OK((hipError_t)launch_adaptive_error((const double*)p->d_sum, (const double*)p->d_sq, (const uint32_t*)p->d_cnt, (const uint32_t*)p->d_pas, (uint32_t)p->n_px(),
+                                                 (double*)p->d_e2, 0.0, nullptr, hip_stream));
+    else
+        HIP_OK((hipError_t)launch_moments_error((const double*)p->d_sum, (const double*)p->d_sq, p->done, p->passes, (uint32_t)p->n_px(), (double*)p->d_e2, 0.0, nullptr, hip_stream));
     if (d_e2_out) *d_e2_out = p->d_e2;
     return 0;
 }
@@ -2001,8 +2037,12 @@ int rt_progressive_error_stats(void* frame, double tau, uint64_t stats_out[4]) {
     DeviceGuard guard(p->device);
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemsetAsync(p->d_mstats, 0, MOMENTS_STATS_WORDS * sizeof(uint64_t), nullptr));
-    HIP_OK((hipError_t)launch_moments_error((const double*)p->d_sum, (const double*)p->d_sq, p->done, p->passes, (uint32_t)p->n_px(), nullptr, tau * tau,
-                                            (unsigned long long*)p->d_mstats, nullptr));
+    if (p->adaptive)
+        HIP_OK((hipError_t)launch_adaptive_error((const double*)p->d_sum, (const double*)p->d_sq, (const uint32_t*)p->d_cnt, (const uint32_t*)p->d_pas, (uint32_t)p->n_px(),
+                                                 nullptr, tau * tau, (unsigned long long*)p->d_mstats, nullptr));
+    else
+        HIP_OK((hipError_t)launch_moments_error((const double*)p->d_sum, (const double*)p->d_sq, p->done, p->passes, (uint32_t)p->n_px(), nullptr, tau * tau,
+                                                (unsigned long long*)p->d_mstats, nullptr));
     HIP_OK(hipMemcpy(stats_out, p->d_mstats, MOMENTS_STATS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -2025,11 +2065,250 @@ static int progressive_variance_enqueue(Progressive* p, hipStream_t stream) {
 int rt_progressive_variance(void* frame, double* var_out) {
     Progressive* p = (Progressive*)frame;
     if (!var_out) return set_err("null argument");
+    if (adaptive_needs_uniform(p, "rt_progressive_variance")) return -1;
     if (moments_error_ready(p)) return -1;
     DeviceGuard guard(p->device);
     HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the estimate
     if (progressive_variance_enqueue(p, nullptr)) return -1;
     HIP_OK(hipMemcpy(var_out, p->d_var, p->n_px() * 3 * sizeof(double), hipMemcpyDeviceToHost));      // (waits for the kernel: the null stream)
+    return 0;
+}
+
+// ---------------------------------------------------------------- adaptive frames (csrc/rt_adaptive.h: the specification; rt_adaptive.hip: the kernels)
+static int pixels_args(rt_scene* sc, const rt_camera* cam, const double* bg, uint32_t W, uint32_t H, uint32_t n_samples, uint32_t flags) {
+    if (!sc || !cam || !bg) return set_err("null argument");
+    if (W < 2 || H < 2) return set_err("W and H must be >= 2 (u,v divide by W-1 and H-1, src/main.rs:817-818)");
+    if ((uint64_t)W * H > 0x7FFFFFFFull) return set_err("frame too large: W*H must be <= 2^31 - 1 (per-path RNG keys, csrc/rt_rng.h)");
+    if (n_samples == 0) return set_err("n_samples must be >= 1");
+    if (flags & ~(uint32_t)(RT_STOP_ON_ZERO | RT_ISOTROPIC_SCATTER))
+        return set_err("pixel-list passes take RT_STOP_ON_ZERO and RT_ISOTROPIC_SCATTER only: they run in f64 and in the reference's traversal order (RT_F32 and every other flag: not supported)");
+    return 0;
+}
+int rt_render_pixels_device(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t n_samples, uint32_t max_depth,
+                            uint64_t seed, uint32_t flags, const void* d_list, uint32_t n_list, const void* d_counts, void* d_out, size_t d_out_bytes,
+                            void* hip_stream) {
+    if (pixels_args(sc, cam, bg, W, H, n_samples, flags)) return -1;
+    if (!d_out || (!d_list && n_list)) return set_err("null argument");
+    if (n_list > W * H) return set_err("n_list must be <= W * H: the list names each pixel at most once");
+    if (d_out_bytes < (size_t)W * H * 3u * sizeof(double)) return set_err("output buffer too small for W * H * 3 doubles (24 bytes per pixel)");
+    if (((uintptr_t)d_out & 7u) || ((uintptr_t)d_list & 3u) || ((uintptr_t)d_counts & 3u)) return set_err("d_out must be 8-byte aligned, d_list and d_counts 4-byte aligned");
+    Scene& s = sc->s;
+    if (need_device_and_flat(s)) return -1;
+    if (n_list == 0) return 0;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    Scene::DeviceCtx* cp = nullptr;
+    if (current_ctx(s, &cp)) return -1;
+    Scene::DeviceCtx& c = *cp;
+    DeviceScene<double>& d = dev_of<double>(c);
+    if (ensure_uploaded<double>(s, d)) return -1;
+    const HostFlat& f = s.flat;
+    KParams<double> P;
+    std::memset((void*)&P, 0, sizeof(P));
+    bind_tables(P, d, f);
+    P.bvh_tame = tables_are_tame<double>(f);
+    rt_camera_args ca; std::memcpy(&ca, cam, sizeof(ca));
+    camera_new(ca, P.cam);
+    for (int k = 0; k < 3; k++) P.background[k] = bg[k];
+    P.W = W; P.H = H; P.spp = n_samples; P.max_depth = max_depth; P.flags = flags; P.seed = seed;
+    P.out = (double*)d_out; P.samples_out = nullptr;
+    PixelsArgs X;
+    X.list = (const uint32_t*)d_list; X.counts = (const uint32_t*)d_counts; X.nonfinite = nullptr; X.n_px = W * H;
+    X.chunk = PIXELS_CHUNK;
+    // RT_PIXELS_CHUNK (A/B runs, tools/adaptive_probe.py): paths per chunk of the static dealing — same samples with any value
+    if (const char* v = std::getenv("RT_PIXELS_CHUNK")) { const long m = std::strtol(v, nullptr, 10); if (m >= 1 && m <= 65536) X.chunk = (uint32_t)m; }
+    X.n_paths = (uint64_t)n_list * n_samples;
+    X.n_chunks = (X.n_paths + X.chunk - 1u) / X.chunk;
+    hipDeviceProp_t prop; HIP_OK(hipGetDeviceProperties(&prop, c.device));
+    int bpc = 0; size_t shmem = 0;
+    if (query_node_cache(f, prop, [&](size_t lds) { return pixels_blocks_per_cu(f.feats, lds); }, "pixel-list", P, shmem, bpc)) return -1;
+    uint64_t n_blocks = (uint64_t)prop.multiProcessorCount * (uint64_t)bpc;
+    const uint64_t waves_per_block = PIXELS_THREADS / 64u;
+    const uint64_t blocks_needed = (X.n_chunks + waves_per_block - 1u) / waves_per_block;      // a chunk per wave at least
+    if (n_blocks > blocks_needed) n_blocks = blocks_needed;
+    if (query_events(s, c.device)) return -1;
+    HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[0], stream));
+    HIP_OK(launch_pixels(P, X, f.feats, (uint32_t)n_blocks, shmem, stream));
+    HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[1], stream));
+    s.q_recorded = true;
+    return 0;
+}
+int rt_adaptive_error_device(const void* d_rgb_sum, const void* d_sq_sum, const void* d_counts, const void* d_passes, uint32_t W, uint32_t H,
+                             void* d_e2_out, double tau, void* d_stats_out, void* hip_stream) {
+    if (!d_rgb_sum || !d_sq_sum || !d_counts || !d_passes) return set_err("null argument");
+    std::string problem = adaptive_frame_check(W, H);
+    if (problem.empty() && d_stats_out) problem = moments_tau_check(tau);
+    if (!problem.empty()) return set_err(problem);
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum | (uintptr_t)d_e2_out | (uintptr_t)d_stats_out) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_passes) & 3u) != 0u)
+        return set_err("d_rgb_sum, d_sq_sum, d_e2_out and d_stats_out must be 8-byte aligned, d_counts and d_passes 4-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    if (!d_e2_out && !d_stats_out) return 0;                    // nothing asked for
+    if (d_stats_out) HIP_OK(hipMemsetAsync(d_stats_out, 0, MOMENTS_STATS_WORDS * sizeof(uint64_t), (hipStream_t)hip_stream));
+    HIP_OK((hipError_t)launch_adaptive_error((const double*)d_rgb_sum, (const double*)d_sq_sum, (const uint32_t*)d_counts, (const uint32_t*)d_passes, W * H,
+                                             (double*)d_e2_out, tau * tau, (unsigned long long*)d_stats_out, hip_stream));
+    return 0;
+}
+size_t rt_adaptive_select_workspace_bytes(uint32_t W, uint32_t H) { return adaptive_select_workspace_bytes((uint64_t)W * H); }
+int rt_adaptive_select_device(const void* d_rgb_sum, const void* d_sq_sum, const void* d_counts, const void* d_passes, uint32_t W, uint32_t H,
+                              uint32_t n_samples, double tau, uint64_t max_samples, uint32_t spread, void* d_list_out, void* d_n_list_out,
+                              void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!d_rgb_sum || !d_sq_sum || !d_counts || !d_passes || !d_list_out || !d_n_list_out || !d_workspace) return set_err("null argument");
+    const std::string problem = adaptive_select_check(W, H, n_samples, tau, max_samples, spread);
+    if (!problem.empty()) return set_err(problem);
+    if (workspace_bytes < rt_adaptive_select_workspace_bytes(W, H)) return set_err("adaptive: workspace too small: rt_adaptive_select_workspace_bytes(W, H) bytes are needed");
+    if (query_aligned(d_workspace, "d_workspace")) return -1;
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_passes | (uintptr_t)d_list_out | (uintptr_t)d_n_list_out) & 3u) != 0u)
+        return set_err("d_rgb_sum and d_sq_sum must be 8-byte aligned, d_counts, d_passes, d_list_out and d_n_list_out 4-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    HIP_OK((hipError_t)launch_adaptive_select((const double*)d_rgb_sum, (const double*)d_sq_sum, (const uint32_t*)d_counts, (const uint32_t*)d_passes, W, H, n_samples,
+                                              tau * tau, max_samples, spread, (uint32_t*)d_list_out, (uint32_t*)d_n_list_out, d_workspace, hip_stream));
+    return 0;
+}
+int rt_adaptive_merge_device(void* d_pass_sum, uint32_t n_samples, void* d_rgb_sum, void* d_sq_sum, void* d_counts, void* d_passes, const void* d_list,
+                             uint32_t n_list, void* hip_stream) {
+    if (!d_pass_sum || !d_rgb_sum || !d_sq_sum || !d_counts || !d_passes || (!d_list && n_list)) return set_err("null argument");
+    if (n_samples == 0u) return set_err("adaptive: n_samples must be >= 1 (a pass's square is divided by its sample count)");
+    if (n_list > 0x7FFFFFFFu) return set_err("adaptive: n_list must be <= 2^31 - 1");
+    if ((((uintptr_t)d_pass_sum | (uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_passes | (uintptr_t)d_list) & 3u) != 0u)
+        return set_err("d_pass_sum, d_rgb_sum and d_sq_sum must be 8-byte aligned, d_counts, d_passes and d_list 4-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    HIP_OK((hipError_t)launch_adaptive_merge((double*)d_pass_sum, n_samples, (double*)d_rgb_sum, (double*)d_sq_sum, (uint32_t*)d_counts, (uint32_t*)d_passes,
+                                             (const uint32_t*)d_list, n_list, nullptr, hip_stream));
+    return 0;
+}
+int rt_adaptive_resolve_rgb8_device(const void* d_rgb_sum, const void* d_counts, uint32_t W, uint32_t H, const void* d_rgb8_prev, void* d_rgb8_out,
+                                    void* d_changed_px_out, void* hip_stream) {
+    if (!d_rgb_sum || !d_counts || !d_rgb8_out) return set_err("null argument");
+    const std::string problem = adaptive_frame_check(W, H);
+    if (!problem.empty()) return set_err(problem);
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_changed_px_out) & 7u) != 0u || ((uintptr_t)d_counts & 3u) != 0u) return set_err("d_rgb_sum and d_changed_px_out must be 8-byte aligned, d_counts 4-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    HIP_OK((hipError_t)launch_adaptive_resolve((const double*)d_rgb_sum, (const uint32_t*)d_counts, (const uint8_t*)d_rgb8_prev, (uint8_t*)d_rgb8_out,
+                                               (unsigned long long*)d_changed_px_out, W * H, hip_stream));
+    return 0;
+}
+
+static int adaptive_frame(Progressive* p) {
+    if (!p) return set_err("null argument");
+    if (!p->adaptive) return set_err("this progressive frame is not adaptive (rt_progressive_enable_adaptive, on a frame with moments while it holds 0 samples)");
+    return 0;
+}
+int rt_progressive_enable_adaptive(void* frame) {
+    Progressive* p = (Progressive*)frame;
+    if (moments_frame(p)) return -1;
+    if (p->adaptive) return 0;
+    if (p->done != 0) return set_err("adaptive sampling can only be enabled while the frame holds 0 samples (the counts must cover every sample of the sums): rt_progressive_reset first");
+    if (p->flags & ~(uint32_t)(RT_STOP_ON_ZERO | RT_ISOTROPIC_SCATTER))
+        return set_err("adaptive frames take RT_STOP_ON_ZERO and RT_ISOTROPIC_SCATTER only: the pixel-list kernel runs in f64 and in the reference's traversal order (RT_F32 and every other flag: not supported)");
+    DeviceGuard guard(p->device);
+    const size_t n = p->n_px();
+    hipError_t e = hipMalloc(&p->d_cnt, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&p->d_pas, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&p->d_list, n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&p->d_words, 2 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&p->d_sel_ws, rt_adaptive_select_workspace_bytes(p->W, p->H));
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_cnt, 0, n * sizeof(uint32_t), nullptr);
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_pas, 0, n * sizeof(uint32_t), nullptr);
+    if (e == hipSuccess) e = hipMemsetAsync(p->d_words, 0, 2 * sizeof(uint32_t), nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        free_dev(p->d_cnt); free_dev(p->d_pas); free_dev(p->d_list); free_dev(p->d_words); free_dev(p->d_sel_ws);
+        return set_err(std::string("rt_progressive_enable_adaptive: ") + hipGetErrorString(e));
+    }
+    p->adaptive = true; p->uniform = true; p->total = 0;
+    return 0;
+}
+// one pass of n samples over the n_list pixels of the frame's list (already in d_list) through the list kernel, merged, waited for
+static int adaptive_list_pass(Progressive* p, uint32_t n, uint32_t n_list) {
+    const size_t n_px = p->n_px();
+    uint32_t* words = (uint32_t*)p->d_words;                    // [0] the list's length, [1] the largest count behind the merge
+    if (p->merge_recorded) HIP_OK(hipStreamWaitEvent(nullptr, p->ev_merged, 0));
+    if (rt_render_pixels_device(p->sc, &p->cam, p->bg, p->W, p->H, n, p->max_depth, p->seed, p->flags, p->d_list, n_list, p->d_cnt, p->d_pass,
+                                n_px * 3 * sizeof(double), nullptr)) return -1;
+    HIP_OK(hipMemsetAsync(words + 1, 0, sizeof(uint32_t), nullptr));
+    HIP_OK((hipError_t)launch_adaptive_merge((double*)p->d_pass, n, (double*)p->d_sum, (double*)p->d_sq, (uint32_t*)p->d_cnt, (uint32_t*)p->d_pas,
+                                             (const uint32_t*)p->d_list, n_list, words + 1, nullptr));
+    HIP_OK(hipEventRecord(p->ev_merged, nullptr));
+    p->merge_recorded = true;
+    uint32_t largest = 0;
+    HIP_OK(hipMemcpy(&largest, words + 1, sizeof(largest), hipMemcpyDeviceToHost));       // (waits for the pass: the null stream)
+    if (n_list != n_px) p->uniform = false;
+    if (largest > p->done) p->done = largest;
+    p->passes++; p->total += (uint64_t)n_list * n;
+    return 0;
+}
+// rt_progressive_add on an adaptive frame whose counts differ: a pass over all pixels through the list kernel
+static int adaptive_pass_over_all(Progressive* p, uint32_t n, double* samples_out) {
+    if (samples_out) return set_err("rt_progressive_add: samples_out is not available on an adaptive frame whose pixels hold different sample counts");
+    DeviceGuard guard(p->device);
+    const size_t n_px = p->n_px();
+    std::vector<uint32_t> all(n_px);
+    for (size_t i = 0; i < n_px; i++) all[i] = (uint32_t)i;
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(p->d_list, all.data(), n_px * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return adaptive_list_pass(p, n, (uint32_t)n_px);
+}
+int rt_progressive_add_adaptive(void* frame, uint32_t n, double tau, uint64_t max_samples, uint32_t spread, uint64_t info_out[4]) {
+    Progressive* p = (Progressive*)frame;
+    if (!info_out) return set_err("null argument");
+    if (adaptive_frame(p)) return -1;
+    if (max_samples == 0u) max_samples = ADAPTIVE_MAX_SAMPLES;
+    const std::string problem = adaptive_select_check(p->W, p->H, n, tau, max_samples, spread);
+    if (!problem.empty()) return set_err(problem);
+    if (!p->sc) return set_err("the scene of this progressive frame has been destroyed");
+    if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
+    if (!p->moments_valid) return set_err("the moments of this frame are invalid: rt_progressive_load_sum loaded sums whose second moments are unknown (rt_progressive_reset or rt_progressive_load_adaptive)");
+    DeviceGuard guard(p->device);
+    const size_t n_px = p->n_px();
+    uint32_t* words = (uint32_t*)p->d_words;
+    HIP_OK((hipError_t)launch_adaptive_select((const double*)p->d_sum, (const double*)p->d_sq, (const uint32_t*)p->d_cnt, (const uint32_t*)p->d_pas, p->W, p->H, n,
+                                              tau * tau, max_samples, spread, (uint32_t*)p->d_list, words, p->d_sel_ws, nullptr));
+    uint32_t n_list = 0;
+    HIP_OK(hipMemcpy(&n_list, words, sizeof(n_list), hipMemcpyDeviceToHost));             // (waits for the selection: the null stream)
+    info_out[0] = n_list; info_out[1] = (uint64_t)n_list * n; info_out[2] = p->total; info_out[3] = 0;
+    if (n_list == 0u) return 0;                                  // nothing listed: the stop condition
+    if (n_list == n_px && p->uniform) {                          // still a uniform frame: the frames' own kernels are the fast ones
+        if (progressive_pass(p, n, nullptr, nullptr, true)) return -1;
+        HIP_OK(hipStreamSynchronize(nullptr));
+    } else {
+        if (adaptive_list_pass(p, n, n_list)) return -1;
+        info_out[3] = 1;
+    }
+    info_out[2] = p->total;
+    return 0;
+}
+int rt_progressive_read_counts(void* frame, uint32_t* counts_out, uint32_t* passes_out) {
+    Progressive* p = (Progressive*)frame;
+    if (adaptive_frame(p)) return -1;
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());
+    if (counts_out) HIP_OK(hipMemcpy(counts_out, p->d_cnt, p->n_px() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (passes_out) HIP_OK(hipMemcpy(passes_out, p->d_pas, p->n_px() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+int rt_progressive_load_adaptive(void* frame, const double* rgb_sum, const double* sq_sum, const uint32_t* counts, const uint32_t* passes) {
+    Progressive* p = (Progressive*)frame;
+    if (!rgb_sum || !sq_sum || !counts || !passes) return set_err("null argument");
+    if (adaptive_frame(p)) return -1;
+    const size_t n_px = p->n_px();
+    uint32_t most = 0, most_b = 0; uint64_t total = 0; bool uniform = true;
+    for (size_t i = 0; i < n_px; i++) {
+        if (passes[i] > counts[i]) return set_err("passes must be <= counts for every pixel: a pass holds at least one sample");
+        if (counts[i] == 0u)
+            for (size_t k = 0; k < 3; k++) {
+                uint64_t w, v; std::memcpy(&w, rgb_sum + 3 * i + k, sizeof(w)); std::memcpy(&v, sq_sum + 3 * i + k, sizeof(v));
+                if ((w | v) != 0) return set_err("a pixel with count 0 that is not all zero: a checkpoint is the sums, the second moments AND the counts");
+            }
+        if (counts[i] != counts[0] || passes[i] != passes[0]) uniform = false;
+        if (counts[i] > most) most = counts[i];
+        if (passes[i] > most_b) most_b = passes[i];
+        total += counts[i];
+    }
+    if (progressive_restart(p, rgb_sum, most)) return -1;
+    DeviceGuard guard(p->device);
+    HIP_OK(hipMemcpy(p->d_sq, sq_sum, n_px * 3 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(p->d_cnt, counts, n_px * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(p->d_pas, passes, n_px * sizeof(uint32_t), hipMemcpyHostToDevice));
+    p->passes = most_b; p->moments_valid = true; p->uniform = uniform; p->total = total;
     return 0;
 }
 
@@ -2143,6 +2422,7 @@ static int progressive_denoise_finish(Progressive* p, uint8_t* rgb8_out) {
 int rt_progressive_resolve_denoised_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
     Progressive* p = (Progressive*)frame;
     if (!p || !sigma || !rgb8_out) return set_err("null argument");
+    if (adaptive_needs_uniform(p, "rt_progressive_resolve_denoised_rgb8")) return -1;
     DeviceGuard guard(p->device);
     if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
     if (denoise_enqueue((const double*)p->d_sum, p->done, nullptr, p->W, p->H, iterations, sigma, flags, (double*)p->d_dn_sum, p->d_dn_ws, nullptr)) return -1;
@@ -2232,6 +2512,7 @@ int rt_debug_denoise_variance_ms(const void* d_rgb_sum, uint64_t samples, const 
 int rt_progressive_resolve_denoised_variance_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
     Progressive* p = (Progressive*)frame;
     if (!p || !sigma || !rgb8_out) return set_err("null argument");
+    if (adaptive_needs_uniform(p, "rt_progressive_resolve_denoised_variance_rgb8")) return -1;
     if (moments_error_ready(p)) return -1;
     const std::string problem = denoise_variance_check(p->done, p->W, p->H, iterations, sigma, flags);
     if (!problem.empty()) return set_err(problem);
@@ -2293,6 +2574,7 @@ int rt_progressive_resolve_denoised_albedo_rgb8(void* frame, uint32_t albedo_sam
     Progressive* p = (Progressive*)frame;
     if (!p || !sigma || !rgb8_out) return set_err("null argument");
     if (albedo_samples == 0u) return set_err("denoise: albedo_samples must be >= 1 (the frame is demodulated by albedo_sum / albedo_samples)");
+    if (adaptive_needs_uniform(p, "rt_progressive_resolve_denoised_albedo_rgb8")) return -1;
     DeviceGuard guard(p->device);
     if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
     const size_t n = p->n_px(), sum_bytes = n * 3 * sizeof(double);

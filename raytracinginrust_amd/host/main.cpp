@@ -5,7 +5,8 @@
 //
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
 //              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material|albedo FILE] [--panorama FILE]
-//              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] [--denoise-albedo N] [--denoise-variance SIGMA_V] [--until-error TAU] [--max-samples M] [--aov error FILE] > image.ppm
+//              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] [--denoise-albedo N] [--denoise-variance SIGMA_V] [--until-error TAU] [--max-samples M] [--aov error FILE]
+//              [--adaptive] [--aov samples FILE] > image.ppm
 //
 // --denoise K[,c,n,p] (opt-in): the frame through the edge-avoiding a-trous filter before it is written (rt_denoise: K iterations, guided by
 // sample 0's camera hits of this --seed); with --progressive the frame resolves itself denoised on the device (rt_progressive_resolve_denoised_rgb8).
@@ -20,6 +21,9 @@
 // --until-error TAU [--max-samples M] (with --progressive N): the frame keeps moments (rt_progressive_enable_moments) and stops at the first
 // pass — the second at the earliest — after which no pixel's estimated standard error exceeds TAU display units (1/256 = 0.00390625 is one code
 // value), at the latest after M samples per pixel (default: --spp); the progress line carries the three pixel counts.
+// --adaptive (with --progressive N and --until-error TAU): an adaptive frame (rt_progressive_enable_adaptive) — every pass samples only the pixels
+// whose estimated standard error still exceeds TAU, and their neighbours, no pixel beyond --max-samples (default: --spp); the frame ends with the
+// pass that lists no pixel.  --aov samples FILE (with --adaptive, beside the frame): the per-pixel sample counts when it ends.
 // --aov error FILE (with --progressive N, beside the frame): the frame's error map when it ends (rt_progressive_error_map).
 //
 // --aov KIND FILE (opt-in, one GPU, instead of the frame): a feature frame for a denoiser or a compositor — the closest hit of sample 0's
@@ -246,7 +250,8 @@ static const char* AOV_HELP =
     "      albedo    r g b = the first hit's albedo held to [0, 1], times 255.999, truncated (no gamma); the mean over the samples [0, N) of\n"
     "                --denoise-albedo N when that is given, else sample 0's (a miss, glass and emitters: 255 255 255)\n"
     "      error     (with --progressive N, written BESIDE the image when the frame ends) grey, the estimated standard error of the pixel in\n"
-    "                display units: sqrt(e2) * 256 * 8 truncated, held to 255 — one code value of standard error is grey 8; not finite: 255\n";
+    "                display units: sqrt(e2) * 256 * 8 truncated, held to 255 — one code value of standard error is grey 8; not finite: 255\n"
+    "      samples   (with --adaptive, written BESIDE the image when the frame ends) grey, the samples the pixel holds: 255 * n / the largest n, truncated\n";
 
 // One channel value of the mappings above (a NaN gives 0)
 static unsigned aov_level(double x) { return x >= 0.0 ? (x > 255.0 ? 255u : (unsigned)x) : 0u; }
@@ -264,6 +269,13 @@ static void write_error_aov(const std::string& path, const std::vector<double>& 
         const uint8_t g = (uint8_t)(e2[p] - e2[p] == 0.0 ? aov_level(std::sqrt(e2[p]) * 256.0 * 8.0) : 255u);
         img[p * 3] = img[p * 3 + 1] = img[p * 3 + 2] = g;
     }
+    write_ppm_rgb8(path.c_str(), img, W, H);
+}
+static void write_samples_aov(const std::string& path, const std::vector<uint32_t>& counts, uint32_t W, uint32_t H) {
+    uint32_t most = 1u;
+    for (uint32_t n : counts) most = std::max(most, n);
+    std::vector<uint8_t> img(counts.size() * 3);
+    for (size_t p = 0; p < counts.size(); p++) img[p * 3] = img[p * 3 + 1] = img[p * 3 + 2] = (uint8_t)((uint64_t)counts[p] * 255u / most);
     write_ppm_rgb8(path.c_str(), img, W, H);
 }
 static void write_aov(const std::string& kind, const std::string& path, const std::vector<Hit>& hits, uint32_t W, uint32_t H) {
@@ -296,6 +308,7 @@ int main(int argc, char** argv) {
     uint32_t albedo_samples = 0;                                            // --denoise-albedo N: demodulate by the albedo of samples [0, N) (0: the plain filter)
     double sigma_v = 0.0;                                                   // --denoise-variance SIGMA_V: the variance-guided colour stop (0: the plain filter)
     uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
+    bool adaptive = false;                                                  // --adaptive: sample only the pixels whose estimated error still exceeds --until-error
     double until_error = -1.0; uint32_t max_samples = 0;                    // --until-error TAU [--max-samples M]: stop when no pixel's standard error exceeds TAU
     int gpus = 1;                                                           // --gpus N: the first N devices (0 = all) through rt_render_multi
     std::string obj_path = "teapot.obj", earth_path = "earthmap.jpg";       // the reference's asset names (main.rs:248,491)
@@ -322,10 +335,11 @@ int main(int argc, char** argv) {
         else if (a == "--progressive") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--progressive needs a pass size >= 1\n"); return 2; } progressive = (uint32_t)n; }
         else if (a == "--aov") {
             aov_kind = next(); aov_path = next();
-            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material" && aov_kind != "albedo" && aov_kind != "error") { std::fprintf(stderr, "--aov needs normal, depth, material, albedo or error\n%s", AOV_HELP); return 2; }
+            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material" && aov_kind != "albedo" && aov_kind != "error" && aov_kind != "samples") { std::fprintf(stderr, "--aov needs normal, depth, material, albedo, error or samples\n%s", AOV_HELP); return 2; }
         }
         else if (a == "--panorama") panorama_path = next();
         else if (a == "--until-error") { until_error = std::atof(next()); if (!(until_error >= 0.0)) { std::fprintf(stderr, "--until-error needs a standard error >= 0 in display units (0.00390625 is one code value)\n"); return 2; } }
+        else if (a == "--adaptive") adaptive = true;
         else if (a == "--max-samples") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--max-samples needs a sample count >= 1\n"); return 2; } max_samples = (uint32_t)n; }
         else if (a == "--denoise") {
             const std::string v = next();
@@ -347,6 +361,8 @@ int main(int argc, char** argv) {
                         "                                     per-pixel variance instead of SIGMA_C; needs at least two passes (--spp more than N)\n"
                         "  --until-error TAU [--max-samples M]  with --progressive N: stop at the first pass after which no pixel's estimated standard error\n"
                         "                                     exceeds TAU display units (0.00390625 = one code value), at the latest after M samples (default --spp)\n"
+                        "  --adaptive                         with --progressive N and --until-error TAU: every pass samples only the pixels whose estimated standard\n"
+                        "                                     error still exceeds TAU (and their neighbours), none beyond M samples; ends when no pixel is left\n"
                         "  --panorama FILE                    write the 2:1 equirectangular image (width x width/2) of everything around the scene's\n"
                         "                                     lookfrom instead of the image: --spp samples per ray, --depth, the scene's background\n", AOV_HELP);
             return 0;
@@ -356,6 +372,8 @@ int main(int argc, char** argv) {
         else { std::fprintf(stderr, "unknown flag %s\n", a.c_str()); return 2; }
     }
     if ((until_error >= 0.0 || max_samples != 0u || aov_kind == "error") && progressive == 0u) { std::fprintf(stderr, "--until-error, --max-samples and --aov error go with --progressive N\n"); return 2; }
+    if (adaptive && (progressive == 0u || until_error < 0.0)) { std::fprintf(stderr, "--adaptive goes with --progressive N and --until-error TAU\n"); return 2; }
+    if (aov_kind == "samples" && !adaptive) { std::fprintf(stderr, "--aov samples goes with --adaptive\n"); return 2; }
     if (max_samples != 0u && until_error < 0.0) { std::fprintf(stderr, "--max-samples goes with --until-error TAU\n"); return 2; }
     if (albedo_samples != 0u && !want_denoise && aov_kind != "albedo") { std::fprintf(stderr, "--denoise-albedo goes with --denoise K (or --aov albedo)\n"); return 2; }
     if (sigma_v != 0.0 && (!want_denoise || progressive == 0u || albedo_samples != 0u)) { std::fprintf(stderr, "--denoise-variance goes with --progressive N and --denoise K, and without --denoise-albedo\n"); return 2; }
@@ -423,7 +441,7 @@ int main(int argc, char** argv) {
             break;
         }
         }
-        if (!aov_kind.empty() && aov_kind != "error") {
+        if (!aov_kind.empty() && aov_kind != "error" && aov_kind != "samples") {
             if (flags & RT_F32) throw Error("--aov runs in f64");
             if (aov_kind == "albedo") {
                 const uint32_t n = albedo_samples ? albedo_samples : 1u;
@@ -450,7 +468,17 @@ int main(int argc, char** argv) {
             const bool want_moments = until_error >= 0.0 || aov_kind == "error" || sigma_v != 0.0;
             if (want_moments) frame.enable_moments();
             const uint32_t limit = until_error >= 0.0 && max_samples ? max_samples : samples_per_pixel;
-            while (frame.samples() < limit) {
+            if (adaptive) {
+                frame.enable_adaptive();
+                for (;;) {
+                    const Progressive::AdaptiveInfo info = frame.add_adaptive(progressive, until_error, limit);
+                    if (info.listed == 0) break;
+                    std::fprintf(stderr, "\rSamples: up to %llu / %u  pixels sampled %llu  mean samples %.1f", (unsigned long long)frame.samples(), limit,
+                                 (unsigned long long)info.listed, (double)info.total / ((double)image_width * image_height));
+                }
+                if (aov_kind == "samples") write_samples_aov(aov_path, frame.counts(), image_width, image_height);
+            }
+            while (!adaptive && frame.samples() < limit) {
                 frame.add((uint32_t)std::min<uint64_t>(progressive, limit - frame.samples()));
                 std::fprintf(stderr, "\rSamples: %llu / %u", (unsigned long long)frame.samples(), limit);    // main.rs:772-775
                 if (until_error >= 0.0 && frame.passes() >= 2) {

@@ -364,7 +364,7 @@ class Progressive:
     """
 
     def __init__(self, b: SceneBuilder, cam: CameraParams, background, W: int, H: int, max_depth: int, seed: int = 0x5EED, flags: int = RT_F64,
-                 moments: bool = False):
+                 moments: bool = False, adaptive: bool = False):
         self._lib = _rt()
         self.W, self.H = int(W), int(H)
         bg = (C.c_double * 3)(*[float(x) for x in background])
@@ -373,8 +373,31 @@ class Progressive:
             raise RenderError(_err())
         self._builder = b              # the scene stays alive at least as long as the frame
         self.has_moments = False
-        if moments:
+        self.is_adaptive = False
+        if moments or adaptive:
             self.enable_moments()
+        if adaptive:
+            self.enable_adaptive()
+
+    def enable_adaptive(self) -> None:
+        """rt_progressive_enable_adaptive: per-pixel sample counts on a frame with moments, only while it holds 0 samples (csrc/rt_adaptive.h)."""
+        _check(self._lib.rt_progressive_enable_adaptive(self._h))
+        self.is_adaptive = True
+
+    def add_adaptive(self, n: int, tau: float, max_samples=None, spread: int = 1) -> dict:
+        """rt_progressive_add_adaptive: one pass of n samples over the pixels whose estimated standard error exceeds tau (display units; with
+        spread=1 also their 8 neighbours) and that hold at most max_samples - n samples.  -> {"listed": pixels sampled, "samples": samples
+        rendered by this pass, "total": the sum of all counts, "kernel": 0 the frames' kernel / 1 the pixel-list kernel}; listed == 0 is the
+        stop condition: nothing was rendered."""
+        info = (C.c_uint64 * 4)()
+        _check(self._lib.rt_progressive_add_adaptive(self._h, int(n), float(tau), 0 if max_samples is None else int(max_samples), int(spread), info))
+        return {"listed": int(info[0]), "samples": int(info[1]), "total": int(info[2]), "kernel": int(info[3])}
+
+    def counts(self):
+        """(n, b): the samples every pixel holds and the passes it took part in, (H, W) uint32 each (rt_progressive_read_counts)."""
+        n = np.zeros((self.H, self.W), dtype=np.uint32); b = np.zeros((self.H, self.W), dtype=np.uint32)
+        _check(self._lib.rt_progressive_read_counts(self._h, n.ctypes.data, b.ctypes.data))
+        return n, b
 
     def enable_moments(self) -> None:
         """rt_progressive_enable_moments: only while the frame holds 0 samples; 48 more bytes per pixel."""
@@ -415,10 +438,20 @@ class Progressive:
 
     def checkpoint(self) -> dict:
         """Everything `restore` needs: the sums, the sample count and — with moments — the second moments and the pass count."""
-        return {"rgb_sum": self.sum(), "samples": self.samples, "passes": self.passes, "sq_sum": self.sq_sum() if self.has_moments else None}
+        ck = {"rgb_sum": self.sum(), "samples": self.samples, "passes": self.passes, "sq_sum": self.sq_sum() if self.has_moments else None}
+        if self.is_adaptive:
+            ck["counts"], ck["pixel_passes"] = self.counts()
+        return ck
 
     def restore(self, ck: dict) -> None:
-        """Resume from `checkpoint()`: with second moments into a frame with moments (rt_progressive_load_moments), else the sums alone."""
+        """Resume from `checkpoint()`: with second moments into a frame with moments (rt_progressive_load_moments), with counts into an
+        adaptive frame (rt_progressive_load_adaptive), else the sums alone."""
+        if ck.get("counts") is not None:
+            a = np.ascontiguousarray(ck["rgb_sum"], dtype=np.float64); q = np.ascontiguousarray(ck["sq_sum"], dtype=np.float64)
+            n = np.ascontiguousarray(ck["counts"], dtype=np.uint32); nb = np.ascontiguousarray(ck["pixel_passes"], dtype=np.uint32)
+            if a.shape != (self.H, self.W, 3) or q.shape != a.shape or n.shape != a.shape[:2] or nb.shape != n.shape:
+                raise ValueError(f"checkpoint of shapes {a.shape}, {q.shape}, {n.shape}, {nb.shape} for a frame of {(self.H, self.W, 3)}")
+            return _check(self._lib.rt_progressive_load_adaptive(self._h, a.ctypes.data, q.ctypes.data, n.ctypes.data, nb.ctypes.data))
         if ck.get("sq_sum") is None:
             return self.load(ck["rgb_sum"], ck["samples"])
         a = np.ascontiguousarray(ck["rgb_sum"], dtype=np.float64)
@@ -541,7 +574,8 @@ DEFAULT_PASS_SPP = 64
 
 
 def render_progressive(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, spp: int, max_depth: int, passes=None,
-                       seed: int = 0x5EED, flags: int = RT_F64, until_error=None, min_passes: int = 2, max_samples=None):
+                       seed: int = 0x5EED, flags: int = RT_F64, until_error=None, min_passes: int = 2, max_samples=None, adaptive: bool = False,
+                       spread: int = 1):
     """Generator: renders `spp` samples per pixel in passes and yields (samples_done, rgb8, changed_px) after each; the last item is the
     full frame — the image `format_image(render(..., spp), spp)` gives.  passes: None (passes of DEFAULT_PASS_SPP), an int (that many
     passes of equal size, the remainder in the first ones), or a sequence of pass sizes that sums to spp.
@@ -549,7 +583,13 @@ def render_progressive(b: SceneBuilder, cam: CameraParams, background, W: int, H
     until_error=tau: a frame with moments that stops at the first pass — not before min_passes (>= 2) — after which no pixel's estimated
     standard error exceeds tau (display units: 1/256 is one code value), at the latest after max_samples (default: spp, which `passes`
     then divides) samples.  Every item is then (samples_done, rgb8, changed_px, stats): the dict of `Progressive.error_stats(tau)`, None
-    while the frame holds fewer than two passes."""
+    while the frame holds fewer than two passes.
+
+    adaptive=True (with until_error): an adaptive frame — every pass samples only the pixels whose estimated standard error still exceeds tau
+    (`Progressive.add_adaptive`, with `spread`), no pixel beyond max_samples, and the generator ends with the pass that lists no pixel.
+    samples_done is then the LARGEST per-pixel count, and stats carries "listed", "samples" and "total" of the pass beside the error words."""
+    if adaptive and until_error is None:
+        raise ValueError("adaptive=True needs until_error: the pixels to sample are chosen by their estimated error")
     if until_error is not None:
         if min_passes < 2:
             raise ValueError("min_passes must be >= 2: the error is estimated from the spread between passes")
@@ -564,8 +604,16 @@ def render_progressive(b: SceneBuilder, cam: CameraParams, background, W: int, H
         sizes = [int(n) for n in passes]
         if sum(sizes) != spp or min(sizes, default=0) < 1:
             raise ValueError("pass sizes must be >= 1 and sum to spp")
-    with Progressive(b, cam, background, W, H, max_depth, seed, flags, moments=until_error is not None) as frame:
+    with Progressive(b, cam, background, W, H, max_depth, seed, flags, moments=until_error is not None, adaptive=adaptive) as frame:
         for n in sizes:
+            if adaptive:
+                info = frame.add_adaptive(n, until_error, max_samples=spp, spread=spread)
+                if info["listed"] == 0:
+                    return
+                image, changed = frame.rgb8()
+                stats = frame.error_stats(until_error) if frame.passes >= 2 else None
+                yield frame.samples, image, changed, None if stats is None else {**stats, **info}
+                continue
             frame.add(n)
             image, changed = frame.rgb8()
             if until_error is None:
@@ -1125,6 +1173,120 @@ def moments_error_device(d_rgb_sum, d_sq_sum, samples: int, passes: int, W: int,
     st_ptr = None if d_stats_out is None else _device_buffer(d_stats_out)[0]
     _check(_rt().rt_moments_error_device(C.c_void_p(_device_buffer(d_rgb_sum)[0]), C.c_void_p(_device_buffer(d_sq_sum)[0]), int(samples), int(passes),
                                          W, H, C.c_void_p(e2_ptr), float(tau), C.c_void_p(st_ptr), C.c_void_p(stream)))
+
+
+# ---- adaptive frames (rt_adaptive_*, rt_render_pixels_device; csrc/rt_adaptive.h): per-pixel sample counts through error, selection, merge, resolve
+ADAPTIVE_MAX_SAMPLES = 2 ** 32 - 1
+
+
+def _adaptive_state(rgb_sum, sq_sum, counts, passes):
+    s, q = _moments_frames(rgb_sum, sq_sum)
+    n = np.ascontiguousarray(counts, dtype=np.uint32); b = np.ascontiguousarray(passes, dtype=np.uint32)
+    if n.shape != s.shape[:2] or b.shape != n.shape:
+        raise ValueError(f"counts of shape {n.shape} and passes of shape {b.shape} for frames of shape {s.shape}: want (H, W) twice")
+    return s, q, n, b
+
+
+def adaptive_error_host(rgb_sum, sq_sum, counts, passes, tau=None):
+    """rt_adaptive_error_host (no GPU): e2 of every pixel, (H, W), from (H, W, 3) sums and second moments and (H, W) uint32 per-pixel sample
+    and pass counts; +inf where a pixel has fewer than two passes.  With tau: (e2, `moments_stats` of the map)."""
+    s, q, n, b = _adaptive_state(rgb_sum, sq_sum, counts, passes)
+    out = np.zeros(n.shape, dtype=np.float64)
+    words = (C.c_uint64 * 4)()
+    _check(_rt().rt_adaptive_error_host(s.ctypes.data, q.ctypes.data, n.ctypes.data, b.ctypes.data, s.shape[1], s.shape[0], out.ctypes.data,
+                                        0.0 if tau is None else float(tau), None if tau is None else words))
+    return out if tau is None else (out, moments_stats(words, tau))
+
+
+def adaptive_select_host(rgb_sum, sq_sum, counts, passes, n_samples: int, tau: float, max_samples: int = ADAPTIVE_MAX_SAMPLES, spread: int = 1) -> np.ndarray:
+    """rt_adaptive_select_host (no GPU): the ascending output-order indices (uint32) of the pixels a pass of n_samples would sample."""
+    s, q, n, b = _adaptive_state(rgb_sum, sq_sum, counts, passes)
+    out = np.zeros(n.size, dtype=np.uint32)
+    count = C.c_uint32()
+    _check(_rt().rt_adaptive_select_host(s.ctypes.data, q.ctypes.data, n.ctypes.data, b.ctypes.data, s.shape[1], s.shape[0], int(n_samples), float(tau),
+                                         int(max_samples), int(spread), out.ctypes.data, C.byref(count)))
+    return out[:count.value].copy()
+
+
+def adaptive_merge_host(pass_sum: np.ndarray, n_samples: int, rgb_sum: np.ndarray, sq_sum: np.ndarray, counts: np.ndarray, passes: np.ndarray, pixels) -> None:
+    """rt_adaptive_merge_host (no GPU): merges the listed pixels of the pass frame IN PLACE into rgb_sum, sq_sum, counts and passes and zeroes
+    them in pass_sum; every other pixel is left alone.  All five are C-contiguous arrays, (H, W, 3) float64 / (H, W) uint32."""
+    for a, dt in ((pass_sum, np.float64), (rgb_sum, np.float64), (sq_sum, np.float64), (counts, np.uint32), (passes, np.uint32)):
+        if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous and a.flags.writeable):
+            raise ValueError("the frames are merged in place: writeable C-contiguous float64 (frames) and uint32 (counts) arrays")
+    if rgb_sum.ndim != 3 or rgb_sum.shape[2] != 3 or pass_sum.shape != rgb_sum.shape or sq_sum.shape != rgb_sum.shape or counts.shape != rgb_sum.shape[:2] or passes.shape != counts.shape:
+        raise ValueError("want (H, W, 3) frames and (H, W) counts of one size")
+    px = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+    _check(_rt().rt_adaptive_merge_host(pass_sum.ctypes.data, int(n_samples), rgb_sum.ctypes.data, sq_sum.ctypes.data, counts.ctypes.data, passes.ctypes.data,
+                                        px.ctypes.data if px.size else None, px.size, rgb_sum.shape[1], rgb_sum.shape[0]))
+
+
+def adaptive_resolve_rgb8_host(rgb_sum, counts, rgb8_prev=None):
+    """rt_adaptive_resolve_rgb8_host (no GPU): format_color with every pixel's own count -> ((H, W, 3) uint8, pixels that differ from rgb8_prev)."""
+    s = np.ascontiguousarray(rgb_sum, dtype=np.float64); n = np.ascontiguousarray(counts, dtype=np.uint32)
+    if s.ndim != 3 or s.shape[2] != 3 or n.shape != s.shape[:2]:
+        raise ValueError(f"rgb_sum of shape {s.shape} and counts of shape {n.shape}: want (H, W, 3) and (H, W)")
+    prev = None if rgb8_prev is None else np.ascontiguousarray(rgb8_prev, dtype=np.uint8)
+    if prev is not None and prev.shape != s.shape:
+        raise ValueError("rgb8_prev must have the frame's shape")
+    out = np.zeros(s.shape, dtype=np.uint8)
+    changed = C.c_uint64()
+    _check(_rt().rt_adaptive_resolve_rgb8_host(s.ctypes.data, n.ctypes.data, s.shape[1], s.shape[0], None if prev is None else prev.ctypes.data, out.ctypes.data,
+                                               C.byref(changed)))
+    return out, int(changed.value)
+
+
+def _ptr_or_none(x):
+    return C.c_void_p(None if x is None else _device_buffer(x)[0])
+
+
+def adaptive_error_device(d_rgb_sum, d_sq_sum, d_counts, d_passes, W: int, H: int, d_e2_out=None, tau: float = 0.0, d_stats_out=None, stream: int = 0) -> None:
+    """rt_adaptive_error_device: `adaptive_error_host` for frames in device memory, enqueued on `stream`; never waits."""
+    _check(_rt().rt_adaptive_error_device(_ptr_or_none(d_rgb_sum), _ptr_or_none(d_sq_sum), _ptr_or_none(d_counts), _ptr_or_none(d_passes), W, H,
+                                          _ptr_or_none(d_e2_out), float(tau), _ptr_or_none(d_stats_out), C.c_void_p(stream)))
+
+
+def adaptive_select_workspace_bytes(W: int, H: int) -> int:
+    return int(_rt().rt_adaptive_select_workspace_bytes(W, H))
+
+
+def adaptive_select_device(d_rgb_sum, d_sq_sum, d_counts, d_passes, W: int, H: int, n_samples: int, tau: float, d_list_out, d_n_list_out, d_workspace,
+                           max_samples: int = ADAPTIVE_MAX_SAMPLES, spread: int = 1, stream: int = 0, workspace_bytes=None) -> None:
+    """rt_adaptive_select_device: the list (room for W*H uint32 / int32) and its length (one word) in device memory; the workspace is
+    `adaptive_select_workspace_bytes(W, H)` bytes, 16-byte aligned.  Enqueued on `stream`; never waits."""
+    ws_ptr, nbytes = _device_buffer(d_workspace)
+    nbytes = nbytes if workspace_bytes is None else int(workspace_bytes)
+    if nbytes is None:
+        raise ValueError("workspace_bytes is needed with a raw pointer")
+    _check(_rt().rt_adaptive_select_device(_ptr_or_none(d_rgb_sum), _ptr_or_none(d_sq_sum), _ptr_or_none(d_counts), _ptr_or_none(d_passes), W, H, int(n_samples),
+                                           float(tau), int(max_samples), int(spread), _ptr_or_none(d_list_out), _ptr_or_none(d_n_list_out), C.c_void_p(ws_ptr), nbytes,
+                                           C.c_void_p(stream)))
+
+
+def adaptive_merge_device(d_pass_sum, n_samples: int, d_rgb_sum, d_sq_sum, d_counts, d_passes, d_list, n_list: int, stream: int = 0) -> None:
+    """rt_adaptive_merge_device: the list merge for frames in device memory, enqueued on `stream`; never waits."""
+    _check(_rt().rt_adaptive_merge_device(_ptr_or_none(d_pass_sum), int(n_samples), _ptr_or_none(d_rgb_sum), _ptr_or_none(d_sq_sum), _ptr_or_none(d_counts),
+                                          _ptr_or_none(d_passes), _ptr_or_none(d_list), int(n_list), C.c_void_p(stream)))
+
+
+def adaptive_resolve_rgb8_device(d_rgb_sum, d_counts, W: int, H: int, d_rgb8_out, d_rgb8_prev=None, d_changed=None, stream: int = 0) -> None:
+    """rt_adaptive_resolve_rgb8_device: the resolve with counts for frames in device memory; the changed-pixel count is ADDED to d_changed."""
+    _check(_rt().rt_adaptive_resolve_rgb8_device(_ptr_or_none(d_rgb_sum), _ptr_or_none(d_counts), W, H, _ptr_or_none(d_rgb8_prev), _ptr_or_none(d_rgb8_out),
+                                                 _ptr_or_none(d_changed), C.c_void_p(stream)))
+
+
+def render_pixels_device(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, n_samples: int, max_depth: int, d_list, n_list: int, d_out,
+                         d_counts=None, seed: int = DEFAULT_SEED, flags: int = 0, stream: int = 0, d_out_bytes=None) -> None:
+    """rt_render_pixels_device: n_samples samples of every pixel of d_list (n_list ascending output-order indices, uint32 / int32 in device
+    memory) ADDED to the W*H*3 f64 frame d_out; pixel p receives samples [d_counts[p], d_counts[p] + n_samples) of the frame `render` with
+    the same view and seed would hold (d_counts None: from sample 0).  Enqueued on `stream`; never waits."""
+    out_ptr, nbytes = _device_buffer(d_out)
+    nbytes = nbytes if d_out_bytes is None else int(d_out_bytes)
+    if nbytes is None:
+        raise ValueError("d_out_bytes is needed with a raw pointer")
+    bg = (C.c_double * 3)(*[float(x) for x in background])
+    _check(_rt().rt_render_pixels_device(b.h, C.byref(cam), bg, W, H, int(n_samples), max_depth, seed, flags, _ptr_or_none(d_list), int(n_list),
+                                         _ptr_or_none(d_counts), C.c_void_p(out_ptr), nbytes, C.c_void_p(stream)))
 
 
 def kernel_time_total(b: SceneBuilder, reset: bool = False):

@@ -1,0 +1,533 @@
+"""Adaptive progressive frames on the GPU (csrc/rt_adaptive.hip, rt_progressive_enable_adaptive, rt_render_pixels_device).
+
+What is compared with what:
+  1. the element-wise kernels on torch tensors against rt_adaptive_*_host (which tests/test_adaptive_host.py holds to the NumPy restatement):
+     every word equal, and the device list == np.flatnonzero(active) — one pixel, odd sizes, more than one sweep of the grid, buffers at
+     16-byte alignment and 8 bytes off it, lists that cross every block boundary of the compaction;
+  2. the pixel-list kernel against the frames' own samples (rt_render_samples of the existing kernels): a listed pixel with count n[p] must
+     receive samples [n[p], n[p] + n_b) of the frame of the same view and seed, an unlisted pixel keeps every word;
+  3. adaptive frames (Cornell box, 16 x 16) against the host twin's selection and against their own samples.
+
+The bound on a sum of N samples x_i added in any order (f64 atomic adds) against NumPy's sum of the frames' samples: 2 gamma_N sum|x_i| —
+each of the two sums is within gamma_{N-1} sum|x_i| of the exact one — plus N * 1e-10, the project's per-sample parity figure (two kernels
+tracing the same path may round a free-flight distance differently).  Where the kernel adds into a pre-filled buffer, the value that was
+there is one more term of the sum.  gamma_n = n u / (1 - n u), u = 2^-53.  At most MAX_BAD = 2 pixels per case may fall outside (a path
+whose free-flight distance lands one ulp across a boundary takes another way); on the list scene none may."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+from raytracinginrust_amd import render as R
+
+import adaptive_cases as AC
+import moments_cases as MC
+from moments_cases import differing_words, gamma
+
+pytestmark = pytest.mark.gpu
+
+W = H = 16
+N_PX = W * H
+DEPTH = 8
+SEED = 0xADA7
+MAX_BAD = 2
+PARITY = 1e-10
+
+
+def _shifted(a, off, dtype=np.float64):
+    """A device copy of `a` whose address is 8 * off bytes behind a fresh allocation (torch allocations are at least 256-byte aligned).
+    uint32 arrays travel as int32 tensors."""
+    import torch
+    flat = np.array(a, dtype=dtype, copy=True).reshape(-1)
+    per = 8 // flat.itemsize
+    if flat.dtype == np.uint32:
+        flat = flat.view(np.int32)
+    buf = torch.zeros(flat.size + off * per, dtype=torch.from_numpy(flat[:0]).dtype, device="cuda")
+    view = buf[off * per:]
+    view.copy_(torch.from_numpy(flat))
+    assert view.data_ptr() % 16 == (8 * off) % 16
+    return view
+
+
+def _u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+# ---------------------------------------------------------------- 1. the element-wise kernels against the host twin
+# (H, W): one pixel; 165 pixels (odd, not a multiple of 4); 192; 90000 (88 blocks of the compaction, the last one partial); 614400 pixels =
+# more than one sweep of the error kernel's 1024 x 256 lanes and of the need kernel's 2048 x 256, and 600 blocks of the compaction
+DEVICE_SHAPES = AC.SHAPES + ((600, 1024),)
+IDS = dict(ids=lambda s: f"{s[1]}x{s[0]}")
+
+
+def _device_select(dS, dQ, dn, db, shape, n_b, tau, cap, spread):
+    import torch
+    n_px = shape[0] * shape[1]
+    d_list = torch.full((n_px,), -7, dtype=torch.int32, device="cuda")
+    d_count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+    ws = torch.zeros(R.adaptive_select_workspace_bytes(shape[1], shape[0]), dtype=torch.uint8, device="cuda")
+    R.adaptive_select_device(dS, dQ, dn, db, shape[1], shape[0], n_b, tau, d_list, d_count, ws, cap, spread)
+    count = int(_u32(d_count)[0])
+    full = _u32(d_list)
+    assert (full[count:].view(np.int32) == -7).all()              # nothing is written past the list's end
+    return full[:count]
+
+
+@pytest.mark.parametrize("off", [0, 1], ids=["aligned16", "off8"])
+@pytest.mark.parametrize("shape", DEVICE_SHAPES, **IDS)
+def test_error_select_and_resolve_equal_the_host_twin(shape, off):
+    import torch
+    S, Q, n, b = AC.state(shape)
+    n_px = shape[0] * shape[1]
+    dS, dQ = _shifted(S, off), _shifted(Q, off)
+    dn, db = _shifted(n, off, np.uint32), _shifted(b, off, np.uint32)
+    # (A)
+    want = R.adaptive_error_host(S, Q, n, b)
+    for tau in (1.0 / 256.0, 0.05):
+        d_e2 = torch.full((n_px,), -1.0, dtype=torch.float64, device="cuda")
+        d_st = torch.full((4,), 77, dtype=torch.int64, device="cuda")              # the launcher zeroes the words
+        R.adaptive_error_device(dS, dQ, dn, db, shape[1], shape[0], d_e2, tau, d_st)
+        assert differing_words(d_e2.cpu().numpy().reshape(shape), want) == 0
+        st = R.moments_stats(d_st.cpu().numpy().view(np.uint64), tau)
+        assert st == R.moments_stats_host(want, tau) and st["converged"] + st["unconverged"] + st["nonfinite"] == n_px
+        d_st2 = torch.full((4,), 77, dtype=torch.int64, device="cuda")
+        R.adaptive_error_device(dS, dQ, dn, db, shape[1], shape[0], None, tau, d_st2)
+        assert torch.equal(d_st2, d_st)
+    # (B)
+    sizes = set()
+    for tau, spread, cap in ((0.0, 0, AC.MAX_SAMPLES), (1.0 / 256.0, 1, AC.MAX_SAMPLES), (0.05, 0, AC.CAP), (0.05, 1, AC.CAP), (0.05, 1, 40), (1e30, 0, AC.MAX_SAMPLES)):
+        got = _device_select(dS, dQ, dn, db, shape, AC.N_B, tau, cap, spread)
+        assert np.array_equal(got, R.adaptive_select_host(S, Q, n, b, AC.N_B, tau, cap, spread)), (tau, spread, cap)
+        assert np.array_equal(got, np.flatnonzero(AC.numpy_active(S, Q, n, b, AC.N_B, tau, cap, spread))), (tau, spread, cap)
+        sizes.add(len(got))
+    assert n_px < 33 or len(sizes) > 3
+    # (D)
+    want_img, _ = R.adaptive_resolve_rgb8_host(S, n)
+    prev = want_img.copy(); prev.reshape(-1, 3)[::3, 1] ^= 1
+    for p_host in (None, prev):
+        d_img = torch.full((n_px * 3 + 4,), 9, dtype=torch.uint8, device="cuda")
+        d_chg = torch.zeros(1, dtype=torch.int64, device="cuda")
+        d_prev = None if p_host is None else torch.from_numpy(p_host.reshape(-1).copy()).cuda()
+        R.adaptive_resolve_rgb8_device(dS, dn, shape[1], shape[0], d_img, d_prev, d_chg)
+        out = d_img.cpu().numpy()
+        assert np.array_equal(out[:n_px * 3].reshape(want_img.shape), want_img) and (out[n_px * 3:] == 9).all()
+        assert int(d_chg.cpu()[0]) == R.adaptive_resolve_rgb8_host(S, n, p_host)[1]
+    if off == 0 and n_px > 1:                                   # an image one byte off dword alignment: the byte-wise kernel
+        d_img = torch.full((n_px * 3 + 4,), 9, dtype=torch.uint8, device="cuda")
+        d_chg = torch.zeros(1, dtype=torch.int64, device="cuda")
+        R.adaptive_resolve_rgb8_device(dS, dn, shape[1], shape[0], d_img[1:], None, d_chg)
+        out = d_img.cpu().numpy()
+        assert np.array_equal(out[1:1 + n_px * 3].reshape(want_img.shape), want_img) and out[0] == 9 and (out[1 + n_px * 3:] == 9).all() and int(d_chg.cpu()[0]) == n_px
+
+
+def _flag_state(shape, pixels):
+    """A state whose selection (spread 0) is exactly `pixels`: they hold one pass, every other pixel is finished beyond doubt."""
+    S = np.full(shape + (3,), 16.0); Q = np.zeros(shape + (3,)); n = np.full(shape, 32, np.uint32); b = np.full(shape, 4, np.uint32)
+    b.reshape(-1)[pixels.astype(np.int64)] = 1
+    return S, Q, n, b
+
+
+@pytest.mark.parametrize("off", [0, 1], ids=["aligned16", "off8"])
+@pytest.mark.parametrize("shape", DEVICE_SHAPES, **IDS)
+def test_lists_and_the_list_merge_equal_the_host_twin(shape, off):
+    n_px = shape[0] * shape[1]
+    S, Q, n, b = AC.state(shape)
+    p = AC.pass_frame(shape) if shape in AC.SHAPES else np.random.RandomState(5).uniform(0.0, 8.0, shape + (3,))
+    lists = dict(AC.lists_for(n_px), selected=AC.numpy_select(S, Q, n, b, AC.N_B, 0.05, AC.CAP, 1))
+    for name, pixels in lists.items():
+        # the compaction makes this very list
+        fS, fQ, fn, fb = _flag_state(shape, pixels) if name != "selected" else (S, Q, n, b)
+        tau, cap, spread = (0.01, AC.MAX_SAMPLES, 0) if name != "selected" else (0.05, AC.CAP, 1)
+        got = _device_select(_shifted(fS, off), _shifted(fQ, off), _shifted(fn, off, np.uint32), _shifted(fb, off, np.uint32), shape, AC.N_B, tau, cap, spread)
+        assert np.array_equal(got, pixels), name
+        # ... and the merge over it equals the host twin's
+        host = [a.copy() for a in (p, S, Q, n, b)]
+        R.adaptive_merge_host(host[0], AC.N_B, host[1], host[2], host[3], host[4], pixels)
+        dev = [_shifted(p, off), _shifted(S, off), _shifted(Q, off), _shifted(n, off, np.uint32), _shifted(b, off, np.uint32)]
+        d_list = _shifted(pixels if len(pixels) else np.zeros(2, np.uint32), 0, np.uint32)
+        R.adaptive_merge_device(dev[0], AC.N_B, dev[1], dev[2], dev[3], dev[4], d_list, len(pixels))
+        for g, w in zip(dev[:3], host[:3]):
+            assert differing_words(g.cpu().numpy().reshape(w.shape), w) == 0, name
+        assert np.array_equal(_u32(dev[3]).reshape(shape), host[3]) and np.array_equal(_u32(dev[4]).reshape(shape), host[4]), name
+
+
+# ---------------------------------------------------------------- 2. the list kernel against the frames' own samples
+# one scene of every instantiation of pixels_kernel: list scene, one BVH, mesh, all features (the principled material), object leaves —
+# tests/test_radiance_query_gpu.py's scenes
+SCENE_CLASSES = ("cornell", "random", "teapot", "pbr", "medium_bvh")
+N_B = 6
+SPP_REF = 70 + N_B
+SPP_CORNELL = 70 + 1000
+
+
+@functools.lru_cache(maxsize=None)
+def _scene(name):
+    from test_radiance_query_gpu import _scene as scene_of
+    pb, _, cam, bg = scene_of(name)
+    return pb, cam, bg
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(name):
+    """The frames' own samples, (H, W, spp, 3): rt_render_samples of the existing kernels, once per scene, read-only."""
+    pb, cam, bg = _scene(name)
+    _, samples = R.render(pb, cam, bg, W, H, SPP_CORNELL if name == "cornell" else SPP_REF, DEPTH, seed=SEED, want_samples=True)
+    samples.setflags(write=False)
+    return samples
+
+
+def _sentinel():
+    px = np.arange(N_PX, dtype=np.float64)[:, None]
+    return (0.25 * (px % 7.0) + 0.125 * np.arange(3.0)[None, :] + 0.5).reshape(H, W, 3)      # exact in binary, positive, different per pixel and channel
+
+
+def _render_pixels(name, pixels, counts, n_b, seed=SEED, flags=0):
+    import torch
+    pb, cam, bg = _scene(name)
+    d_out = torch.from_numpy(_sentinel().copy()).cuda()
+    d_list = torch.from_numpy(np.ascontiguousarray(pixels, np.uint32).view(np.int32).copy() if len(pixels) else np.zeros(1, np.int32)).cuda()
+    d_counts = None if counts is None else torch.from_numpy(np.ascontiguousarray(counts, np.uint32).reshape(-1).view(np.int32).copy()).cuda()
+    R.render_pixels_device(pb, cam, bg, W, H, n_b, DEPTH, d_list, len(pixels), d_out, d_counts, seed=seed, flags=flags)
+    torch.cuda.synchronize()
+    return d_out.cpu().numpy()
+
+
+def _check_pixels(name, out, pixels, counts, n_b, cap):
+    """Unlisted pixels keep every word; listed ones hold the sentinel plus samples [n[p], n[p] + n_b) of the frame.  -> pixels outside the bound"""
+    ref = _reference(name)
+    sent = _sentinel()
+    listed = np.zeros(N_PX, bool); listed[np.asarray(pixels, np.int64)] = True
+    assert differing_words(out.reshape(-1, 3)[~listed], sent.reshape(-1, 3)[~listed]) == 0
+    first = np.zeros(N_PX, np.int64) if counts is None else np.asarray(counts, np.int64).reshape(-1)
+    bad = 0
+    for p in np.flatnonzero(listed):
+        x = ref.reshape(N_PX, -1, 3)[p, first[p]:first[p] + n_b]
+        assert len(x) == n_b
+        got = out.reshape(-1, 3)[p]
+        if not np.isfinite(x).all():
+            assert MC_masks_equal(got, sent.reshape(-1, 3)[p] + x.sum(axis=0))
+            continue
+        terms = np.abs(x).sum(axis=0) + np.abs(sent.reshape(-1, 3)[p])
+        bound = 2.0 * gamma(n_b + 1) * terms + n_b * PARITY
+        if not (np.abs(got - (sent.reshape(-1, 3)[p] + x.sum(axis=0))) <= bound).all():
+            bad += 1
+    print(f"{name}: {int(listed.sum())} listed pixels x {n_b} samples, {bad} outside the bound (cap {cap})")
+    assert bad <= cap
+    return bad
+
+
+def MC_masks_equal(a, b):
+    return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(np.isposinf(a), np.isposinf(b)) and np.array_equal(np.isneginf(a), np.isneginf(b))
+
+
+@pytest.mark.parametrize("name", SCENE_CLASSES)
+def test_listed_pixels_receive_the_frames_own_samples(name):
+    rs = np.random.RandomState(40 + SCENE_CLASSES.index(name))
+    counts = rs.choice(np.array([0, 3, 70], np.uint32), size=N_PX)
+    pixels = np.flatnonzero(rs.rand(N_PX) < 0.45).astype(np.uint32)
+    assert 0 < len(pixels) < N_PX and len(set(counts[pixels].tolist())) == 3
+    out = _render_pixels(name, pixels, counts, N_B)
+    _check_pixels(name, out, pixels, counts, N_B, 0 if name == "cornell" else MAX_BAD)
+
+
+@pytest.mark.parametrize("pixels,n_b", [((37,), 1), ((200,), 1000), (tuple(range(90, 155)), 1), (tuple(range(0, 256, 5)), 5), (tuple(range(3, 256, 7)), 64)],
+                         ids=["one_pixel_one_sample", "one_pixel_1000_samples", "65_pixels_cross_a_wave", "n_b_5", "n_b_64"])
+def test_small_shapes_of_the_list_kernel(pixels, n_b):
+    pixels = np.array(pixels, np.uint32)
+    counts = np.random.RandomState(len(pixels) + n_b).choice(np.array([0, 3, 70], np.uint32), size=N_PX)
+    _check_pixels("cornell", _render_pixels("cornell", pixels, counts, n_b), pixels, counts, n_b, 0)
+    if n_b == 1:                                                  # no counts: first sample 0 everywhere
+        _check_pixels("cornell", _render_pixels("cornell", pixels, None, n_b), pixels, None, n_b, 0)
+
+
+def test_an_empty_list_is_a_no_op_and_bad_entries_are_skipped():
+    sent = _sentinel()
+    assert differing_words(_render_pixels("cornell", np.zeros(0, np.uint32), None, 4), sent) == 0
+    # an entry that is not a pixel of the frame is dropped on the device; its neighbours in the list are rendered
+    pixels = np.array([5, N_PX, 9, 0xFFFFFFFF], np.uint32)
+    out = _render_pixels("cornell", pixels, None, 3)
+    _check_pixels("cornell", out, pixels[[0, 2]], None, 3, 0)
+
+
+def test_the_last_sample_index_is_accepted_and_one_more_is_not(pbe):
+    """n[p] + n_b = 2^32 - 1 is the last pass a pixel can take (the sample field of a path's RNG key is 32 bits).  The frames' own kernel
+    renders the same sample through a plain progressive frame loaded at that count."""
+    pb, cam, bg = _scene("cornell")
+    last = 2 ** 32 - 2                                            # the sample index of a pass of 1 that ends at 2^32 - 1
+    with R.Progressive(pb, cam, bg, W, H, DEPTH, seed=SEED) as plain:
+        plain.load(np.zeros((H, W, 3)), last)
+        ref = plain.add(1, want_samples=True)[:, :, 0, :]
+        with pytest.raises(R.RenderError, match="2\\^32 - 1"):
+            plain.add(1)
+    counts = np.full(N_PX, 3, np.uint32); counts[[10, 11]] = last; counts[12] = last + 1
+    out = _render_pixels("cornell", np.array([10, 11, 12, 13], np.uint32), counts, 1)
+    sent = _sentinel().reshape(-1, 3); got = out.reshape(-1, 3)
+    for p in (10, 11):
+        x = ref.reshape(-1, 3)[p]
+        assert (np.abs(got[p] - (sent[p] + x)) <= 2.0 * gamma(2) * (np.abs(x) + sent[p]) + PARITY).all()
+    assert differing_words(got[12], sent[12]) == 0               # one more: the pixel is skipped, nothing is written
+    x = _reference("cornell").reshape(N_PX, -1, 3)[13, 3]        # ... and the entry behind it is rendered: sample 3 of pixel 13
+    assert (np.abs(got[13] - (sent[13] + x)) <= 2.0 * gamma(2) * (np.abs(x) + sent[13]) + PARITY).all()
+    # a frame refuses such a pass on the host, nothing launched
+    with R.Progressive(pb, cam, bg, W, H, DEPTH, seed=SEED, adaptive=True) as frame:
+        n = np.full((H, W), 8, np.uint32); b = np.full((H, W), 2, np.uint32); n.reshape(-1)[7] = last
+        S = np.full((H, W, 3), 4.0); Q = np.full((H, W, 3), 9.0)
+        frame.restore({"rgb_sum": S, "sq_sum": Q, "counts": n, "pixel_passes": b})
+        assert frame.samples == last
+        stats = R.last_stats(pb)
+        with pytest.raises(R.RenderError, match="2\\^32 - 1"):
+            frame.add(2)
+        assert R.last_stats(pb) == stats and np.array_equal(frame.counts()[0], n)
+        info = frame.add_adaptive(2, 0.0)                          # the selection leaves the pixel out
+        after = frame.counts()[0]
+        assert info["listed"] == N_PX - 1 and after.reshape(-1)[7] == last and (np.delete(after.reshape(-1), 7) == 10).all()
+        info = frame.add_adaptive(1, 0.0)                          # ... and takes it for the one sample that is left
+        assert info["listed"] == N_PX and frame.counts()[0].reshape(-1)[7] == last + 1 == frame.samples
+
+
+# ---------------------------------------------------------------- 3. frames
+N_PASS = 4
+MAX_SAMPLES = 40
+
+
+def _sum_ok(S, n, ref):
+    """The pixels whose sums are NOT within the bound of samples [0, n[p]) of the frame -> count"""
+    bad = 0
+    flat_ref = ref.reshape(N_PX, -1, 3)
+    for p in range(N_PX):
+        k = int(n.reshape(-1)[p])
+        x = flat_ref[p, :k]
+        if not np.isfinite(x).all():
+            continue
+        bound = 2.0 * gamma(max(k, 1)) * np.abs(x).sum(axis=0) + k * PARITY
+        if not (np.abs(S.reshape(-1, 3)[p] - x.sum(axis=0)) <= bound).all():
+            bad += 1
+    return bad
+
+
+def _frame(adaptive=True, moments=True):
+    pb, cam, bg = _scene("cornell")
+    return R.Progressive(pb, cam, bg, W, H, DEPTH, seed=SEED, moments=moments, adaptive=adaptive)
+
+
+def _two_uniform_passes(frame):
+    for _ in range(2):
+        info = frame.add_adaptive(N_PASS, 1.0)                    # b < 2: every pixel is needed whatever tau says
+        assert info["listed"] == N_PX and info["kernel"] == 0 and info["samples"] == N_PX * N_PASS
+    return float(np.median(frame.error_map())) ** 0.5
+
+
+def test_adaptive_passes_sample_what_the_host_twin_selects():
+    ref = _reference("cornell")
+    with _frame() as frame:
+        tau = _two_uniform_passes(frame)
+        assert tau > 0.0
+        rendered = 2 * N_PX * N_PASS
+        first = True
+        for _ in range(MAX_SAMPLES // N_PASS):
+            S0, Q0 = frame.sum(), frame.sq_sum()
+            n0, b0 = frame.counts()
+            want = R.adaptive_select_host(S0, Q0, n0, b0, N_PASS, tau, MAX_SAMPLES, 0)
+            if first:
+                assert 0 < len(want) < N_PX                       # the precondition of everything below: a proper subset
+            info = frame.add_adaptive(N_PASS, tau, MAX_SAMPLES, 0)
+            S1, Q1 = frame.sum(), frame.sq_sum()
+            n1, b1 = frame.counts()
+            assert info["listed"] == len(want) and info["samples"] == len(want) * N_PASS and info["kernel"] == (1 if len(want) else 0)
+            listed = np.zeros(N_PX, bool); listed[want.astype(np.int64)] = True
+            assert np.array_equal(n1.reshape(-1), n0.reshape(-1) + N_PASS * listed) and np.array_equal(b1.reshape(-1), b0.reshape(-1) + listed)
+            assert differing_words(S1.reshape(-1, 3)[~listed], S0.reshape(-1, 3)[~listed]) == 0
+            assert differing_words(Q1.reshape(-1, 3)[~listed], Q0.reshape(-1, 3)[~listed]) == 0
+            rendered += info["samples"]
+            assert info["total"] == rendered == int(n1.sum(dtype=np.uint64))
+            bad = _sum_ok(S1, n1, ref)
+            print(f"pass over {len(want)} pixels: {bad} sums outside the bound")
+            assert bad == 0
+            assert frame.samples == int(n1.max())
+            first = False
+            if info["listed"] == 0:
+                assert differing_words(S1, S0) == 0 and np.array_equal(n1, n0)
+                break
+        assert int(n1.max()) <= MAX_SAMPLES and len(np.unique(n1)) > 1
+        # the image is rt_format_color(S[p], n[p]) byte for byte, on the device as on the host
+        image, changed = frame.rgb8()
+        assert np.array_equal(image, R.adaptive_resolve_rgb8_host(S1, n1)[0]) and changed == N_PX
+        out3 = (C.c_uint64 * 3)()
+        for p in range(N_PX):
+            R._rt().rt_format_color(np.ascontiguousarray(S1.reshape(-1, 3)[p]).ctypes.data_as(C.POINTER(C.c_double)), int(n1.reshape(-1)[p]), out3)
+            assert list(out3) == list(image.reshape(-1, 3)[p])
+        assert frame.rgb8()[1] == 0
+        # the error map and statistics are (A)'s on the state read back
+        e2 = frame.error_map()
+        assert differing_words(e2, R.adaptive_error_host(S1, Q1, n1, b1)) == 0
+        assert frame.error_stats(tau) == R.adaptive_error_host(S1, Q1, n1, b1, tau=tau)[1]
+        # a pass over all pixels of a frame whose counts differ goes through the list kernel and keeps the invariant
+        frame.add(3)
+        n2, b2 = frame.counts()
+        assert np.array_equal(n2, n1 + 3) and np.array_equal(b2, b1 + 1) and _sum_ok(frame.sum(), n2, ref) == 0 and frame.samples == int(n2.max())
+
+
+def test_tau_zero_stays_on_the_frames_kernel_and_equals_a_plain_moments_frame():
+    ref = _reference("cornell")
+    with _frame() as frame, _frame(adaptive=False) as plain:
+        for _ in range(3):
+            info = frame.add_adaptive(N_PASS, 0.0)
+            assert info["kernel"] == 0 and info["listed"] == N_PX
+            plain.add(N_PASS)
+        n, b = frame.counts()
+        assert (n == 3 * N_PASS).all() and (b == 3).all() and frame.samples == plain.samples == 12 and frame.passes == plain.passes == 3
+        assert _sum_ok(frame.sum(), n, ref) == 0 and _sum_ok(plain.sum(), n, ref) == 0
+        # while the counts are uniform everything that knows one count for the frame works as it does on a plain frame
+        assert differing_words(frame.error_map(), R.moments_error_host(frame.sum(), frame.sq_sum(), 12, 3)) == 0
+        assert frame.variance().shape == (H, W, 3) and frame.rgb8_denoised_variance().shape == (H, W, 3)
+        assert np.array_equal(frame.rgb8()[0], R.format_image(frame.sum(), 12))
+
+
+def test_a_huge_tau_lists_nothing_and_renders_nothing():
+    pb = _scene("cornell")[0]
+    with _frame() as frame:
+        _two_uniform_passes(frame)
+        S, Q = frame.sum(), frame.sq_sum()
+        n, b = frame.counts()
+        stats, ms = R.last_stats(pb), R.last_kernel_ms(pb)
+        info = frame.add_adaptive(N_PASS, 1e30)
+        assert info == {"listed": 0, "samples": 0, "total": 2 * N_PX * N_PASS, "kernel": 0}
+        assert R.last_stats(pb) == stats and R.last_kernel_ms(pb) == ms
+        assert differing_words(frame.sum(), S) == 0 and differing_words(frame.sq_sum(), Q) == 0
+        assert np.array_equal(frame.counts()[0], n) and np.array_equal(frame.counts()[1], b) and frame.samples == 2 * N_PASS
+
+
+def test_spread_lists_the_dilated_need_map_restricted_by_the_cap():
+    with _frame() as frame:
+        tau = _two_uniform_passes(frame)
+        S, Q = frame.sum(), frame.sq_sum()
+        n, b = frame.counts()
+        need = AC.numpy_need(S, Q, n, b, tau)
+        assert 0 < need.sum() < N_PX
+        ck = frame.checkpoint()
+        lists = {}
+        for spread in (0, 1):
+            frame.restore(ck)
+            frame.add_adaptive(N_PASS, tau, None, spread)
+            lists[spread] = np.flatnonzero(frame.counts()[0].reshape(-1) > 2 * N_PASS)
+        assert np.array_equal(lists[0], np.flatnonzero(need)) and np.array_equal(lists[1], np.flatnonzero(AC.dilate3(need)))
+        assert len(lists[1]) > len(lists[0])
+        # the cap: with max_samples = 2 N_PASS + N_PASS - 1 no pixel has room for another pass
+        frame.restore(ck)
+        assert frame.add_adaptive(N_PASS, tau, 3 * N_PASS - 1, 1)["listed"] == 0
+        assert frame.add_adaptive(N_PASS, tau, 3 * N_PASS, 1)["listed"] == len(lists[1])
+
+
+def test_checkpoint_restore_and_reset():
+    ref = _reference("cornell")
+    with _frame() as frame, _frame() as other:
+        tau = _two_uniform_passes(frame)
+        frame.add_adaptive(N_PASS, tau, None, 0)
+        ck = frame.checkpoint()
+        assert len(np.unique(ck["counts"])) == 2
+        other.restore(ck)
+        assert differing_words(other.sum(), ck["rgb_sum"]) == 0 and differing_words(other.sq_sum(), ck["sq_sum"]) == 0
+        assert np.array_equal(other.counts()[0], ck["counts"]) and np.array_equal(other.counts()[1], ck["pixel_passes"])
+        assert other.samples == frame.samples == 3 * N_PASS and other.passes == 3
+        a, c = frame.add_adaptive(N_PASS, tau), other.add_adaptive(N_PASS, tau)
+        assert a == c and np.array_equal(frame.counts()[0], other.counts()[0]) and _sum_ok(other.sum(), other.counts()[0], ref) == 0
+        # a checkpoint that cannot be one
+        bad = dict(ck); bad["pixel_passes"] = ck["counts"] + 1
+        with pytest.raises(R.RenderError, match="passes must be <= counts"):
+            other.restore(bad)
+        y, x = np.unravel_index(int(np.argmax(ck["rgb_sum"][:, :, 0])), (H, W))      # a pixel that does hold something
+        bad = dict(ck); bad["counts"] = ck["counts"].copy(); bad["counts"][y, x] = 0; bad["pixel_passes"] = ck["pixel_passes"].copy(); bad["pixel_passes"][y, x] = 0
+        with pytest.raises(R.RenderError, match="count 0"):
+            other.restore(bad)
+        # reset: back to nothing, still adaptive
+        other.reset()
+        assert other.samples == 0 and other.passes == 0 and not other.counts()[0].any() and not other.counts()[1].any() and not other.sum().any()
+        info = other.add_adaptive(N_PASS, tau)
+        assert info == {"listed": N_PX, "samples": N_PX * N_PASS, "total": N_PX * N_PASS, "kernel": 0}
+        assert _sum_ok(other.sum(), other.counts()[0], ref) == 0
+
+
+def test_what_an_adaptive_frame_refuses(pbe):
+    import torch
+    pb, cam, bg = _scene("cornell")
+    with _frame(adaptive=False, moments=False) as plain:
+        with pytest.raises(R.RenderError, match="no moments"):
+            plain.enable_adaptive()
+        with pytest.raises(R.RenderError, match="not adaptive"):
+            plain.add_adaptive(4, 0.1)
+        with pytest.raises(R.RenderError, match="not adaptive"):
+            plain.counts()
+    with _frame(adaptive=False) as late:
+        late.add(4)
+        with pytest.raises(R.RenderError, match="0 samples"):
+            late.enable_adaptive()
+    for flags in (R.RT_F32, R.RT_NEAR_FIRST_BVH, R.RT_STOP_ON_ZERO | R.RT_LOCKSTEP_BVH):
+        with R.Progressive(pb, cam, bg, W, H, DEPTH, seed=SEED, flags=flags, moments=True) as f:
+            with pytest.raises(R.RenderError, match="RT_STOP_ON_ZERO and RT_ISOTROPIC_SCATTER only"):
+                f.enable_adaptive()
+    with R.Progressive(pb, cam, bg, W, H, DEPTH, seed=SEED, flags=R.RT_STOP_ON_ZERO | R.RT_ISOTROPIC_SCATTER, adaptive=True) as f:
+        assert f.add_adaptive(2, 0.1)["listed"] == N_PX
+    with _frame() as frame:
+        for bad in ((0, 0.1, None, 1), (4, -0.1, None, 1), (4, float("nan"), None, 1), (4, 0.1, 2 ** 32, 1), (4, 0.1, None, 2)):
+            with pytest.raises(R.RenderError, match="adaptive:"):
+                frame.add_adaptive(*bad)
+        with pytest.raises(R.RenderError, match="not available on an adaptive frame"):
+            frame.add_async(4, torch.cuda.current_stream().cuda_stream)
+        assert frame.samples == 0
+        tau = _two_uniform_passes(frame)
+        frame.variance(); frame.rgb8_denoised(); frame.rgb8_denoised_albedo(4); frame.rgb8_denoised_variance()      # uniform: as on any frame
+        assert frame.add_adaptive(N_PASS, tau, None, 0)["kernel"] == 1
+        S, Q = frame.sum(), frame.sq_sum()
+        for call in (frame.variance, frame.rgb8_denoised, lambda: frame.rgb8_denoised_albedo(4), frame.rgb8_denoised_variance,
+                     lambda: frame.load(S, 12), lambda: frame.restore({"rgb_sum": S, "sq_sum": Q, "samples": 12, "passes": 3}),
+                     lambda: frame.add(2, want_samples=True)):
+            with pytest.raises(R.RenderError, match="different sample counts"):
+                call()
+        assert differing_words(frame.sum(), S) == 0               # none of them touched the frame
+
+
+# ---------------------------------------------------------------- 4. the generator and the command line
+# passes of ONE sample: a pass frame then holds exactly that sample (0.0 + x) and the merges come in pass order, so two runs give the same
+# words, the same lists and the same image
+def _one_sample_passes(b, cam, bg, size, depth, tau, cap, max_passes=None, spread=1, **kw):
+    with R.Progressive(b, cam, bg, size, size, depth, adaptive=True, **kw) as frame:
+        listed = []
+        while max_passes is None or len(listed) < max_passes:
+            info = frame.add_adaptive(1, tau, cap, spread)
+            if info["listed"] == 0:
+                break
+            listed.append(info["listed"])
+        return frame.rgb8()[0], frame.counts()[0], listed
+
+
+def test_render_progressive_adaptive():
+    pb, cam, bg = _scene("cornell")
+    image, n, listed = _one_sample_passes(pb, cam, bg, W, DEPTH, 0.1, 12, max_passes=12, spread=0, seed=SEED)
+    assert listed[0] == listed[1] == N_PX and listed[-1] < N_PX and len(np.unique(n)) > 1 and int(n.max()) <= 12
+    items = list(R.render_progressive(pb, cam, bg, W, H, 12, DEPTH, passes=12, seed=SEED, until_error=0.1, adaptive=True, spread=0))
+    assert [it[3]["listed"] for it in items[1:]] == listed[1:] and items[0][3] is None and len(items) == len(listed)
+    assert np.array_equal(items[-1][1], image) and items[-1][0] == int(n.max()) and items[-1][3]["total"] == int(n.sum())
+
+
+def test_rtrender_adaptive_writes_what_the_python_path_yields(pbe, tmp_path):
+    import os
+    import subprocess
+    from raytracinginrust_amd import _lib, scenes
+    exe = os.path.join(os.path.dirname(_lib.LIB_PATH), "..", "host", "rtrender")
+    assert os.path.exists(exe), "host/rtrender missing: run make -C raytracinginrust_amd/csrc"
+    size, depth, cap, tau = 24, 8, 12, 0.05
+    aov = str(tmp_path / "samples.ppm")
+    common = [exe, "--scene", "cornell", "--width", str(size), "--height", str(size), "--spp", str(cap), "--depth", str(depth)]
+    run = subprocess.run(common + ["--progressive", "1", "--until-error", str(tau), "--adaptive", "--aov", "samples", aov], check=True, capture_output=True, timeout=120)
+    b, cam, bg = scenes.cornell_box(pbe)
+    image, n, listed = _one_sample_passes(b, cam, bg, size, depth, tau, cap)
+    assert len(np.unique(n)) > 1
+    ppm = lambda img: f"P3\n{size} {size}\n255\n" + "".join(f"{p[0]} {p[1]} {p[2]}\n" for p in img.reshape(-1, 3))
+    assert run.stdout == ppm(image).encode()
+    grey = (n.astype(np.uint64) * 255 // int(n.max())).astype(np.uint8)
+    assert open(aov).read() == ppm(np.repeat(grey.reshape(-1, 1), 3, axis=1))
+    alone = subprocess.run(common + ["--progressive", "1", "--adaptive"], capture_output=True, timeout=120)
+    assert alone.returncode == 2 and b"--until-error" in alone.stderr
+    no_frame = subprocess.run(common + ["--progressive", "1", "--until-error", str(tau), "--aov", "samples", aov], capture_output=True, timeout=120)
+    assert no_frame.returncode == 2 and b"--adaptive" in no_frame.stderr
