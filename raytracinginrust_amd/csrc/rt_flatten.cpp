@@ -593,19 +593,17 @@ struct Flattener {
             f.objects.insert(f.objects.end(), subs.begin(), subs.end());
             for (DObject& o : f.objects) if (o.geom_kind == G_OBJ) o.geom_first += f.n_top;     // media with a boundary run (emit_boundary)
         }
-        // which materials' textures read (u, v): ImageTexture, possibly under CheckTextures (texture.rs:45-54)
+        // which materials' textures read (u, v): ImageTexture, under any number of CheckTextures (texture.rs:45-54).  A CheckTexture is
+        // made from textures that exist (rt_texture_check), so its children have smaller handles: one pass in handle order, no recursion
+        // and no depth limit — a chain of any length is seen through
         {
-            std::vector<int> uv(f.textures.size(), -1);          // -1 unknown, 0 / 1 known
-            std::function<bool(uint32_t, int)> reads_uv = [&](uint32_t t, int depth) -> bool {
-                if (t >= f.textures.size() || depth > 64) return false;
-                if (uv[t] >= 0) return uv[t] != 0;
+            std::vector<char> uv(f.textures.size(), 0);
+            for (size_t t = 0; t < f.textures.size(); t++) {
                 const auto& tx = f.textures[t];
-                bool r = tx.kind == T_IMAGE || (tx.kind == T_CHECK && (reads_uv(tx.a, depth + 1) || reads_uv(tx.b, depth + 1)));
-                uv[t] = r ? 1 : 0;
-                return r;
-            };
+                uv[t] = tx.kind == T_IMAGE || (tx.kind == T_CHECK && ((tx.a < t && uv[tx.a]) || (tx.b < t && uv[tx.b])));
+            }
             for (auto& m : f.materials)
-                if ((m.kind == M_LAMBERTIAN || m.kind == M_DIFFUSE_LIGHT || m.kind == M_ISOTROPIC || m.kind == M_PBR) && reads_uv(m.tex, 0)) m.kind |= MAT_NEEDS_UV;
+                if ((m.kind == M_LAMBERTIAN || m.kind == M_DIFFUSE_LIGHT || m.kind == M_ISOTROPIC || m.kind == M_PBR) && m.tex < uv.size() && uv[m.tex]) m.kind |= MAT_NEEDS_UV;
         }
         // lights: a HittableList of FlipNormal(..) / AARect / Sphere / HittableList (hit.rs:90-96, 125-132; rect.rs:91-111;
         // sphere.rs:104-119); anything else has the trait defaults pdf_value = 0, random = (1,0,0) (hit.rs:29-30) — Translate, Rotate,

@@ -406,3 +406,28 @@ def test_medium_in_medium_boundary_still_refused(pbe, where):
     b.set_scene(b.ConstantMedium(l, 0.1, tex), [])
     with pytest.raises(R.RenderError, match="nested ConstantMedium"):
         R.flatten(b)
+
+
+# ---------------------------------------------------------------- which materials read (u, v)
+def test_needs_uv_sees_an_image_behind_any_number_of_checkers(tmp_path):
+    """MAT_NEEDS_UV (rt_flatten.cpp) decides whether finalize_hit computes u, v at all; without it an ImageTexture is sampled at (0, 0).  The
+    flag used to be found by a recursion that gave up 65 levels down and memoised the answer, so an image under more than 64 CheckTextures
+    lost it (on the device: tests/test_texture_walk_gpu.py::test_image_behind_a_chain_of_checkers_on_a_sphere).  No C-ABI call shows a
+    flattened material, so tests/reads_uv_main.cpp reads the flattened scene behind the handle: every chain over an image has the flag —
+    as both children, as the odd one, as the even one, under Lambertian, DiffuseLight, Isotropic and PBR — and no chain over a constant."""
+    import os
+    import subprocess
+    from conftest import ROOT
+    from raytracinginrust_amd import _lib
+    if os.environ.get("RT_SANITIZER_RUN") == "1":      # (the library in use is the sanitizer build: a program without its runtime cannot load it)
+        return
+    exe = str(tmp_path / "reads_uv")
+    libdir = os.path.dirname(os.path.abspath(_lib.LIB_PATH))
+    subprocess.run(["g++", "-std=c++17", "-O1", "-ffp-contract=off", os.path.join(ROOT, "tests", "reads_uv_main.cpp"), "-o", exe,
+                    "-L" + libdir, "-lrt_amd", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=300)
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stdout + run.stderr
+    flags = dict(line.split() for line in run.stdout.splitlines())
+    assert len(flags) == 4 * 9 + 1
+    wrong = sorted(name for name, f in flags.items() if f != ("0" if name.startswith("constant") else "1"))
+    assert not wrong, f"MAT_NEEDS_UV wrong for {wrong}"
