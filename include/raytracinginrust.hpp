@@ -340,6 +340,35 @@ inline std::vector<double> denoise_variance(const std::vector<double>& rgb_sum, 
     if (rt_denoise_variance(rgb_sum.data(), samples, var.data(), hit_records.data(), W, H, d.iterations, d.sigma, d.flags, out.data(), var_out ? var_out->data() : nullptr) != 0) throw Error(rt_last_error());
     return out;
 }
+// The variance frame of a frame with per-pixel counts (rt_adaptive_variance_host, csrc/rt_denoise_frame.h (E)): `moments_variance` with
+// every pixel's own sample and pass counts; +inf where a pixel has fewer than two passes.  The host form: no device needed.
+inline std::vector<double> adaptive_variance(const std::vector<double>& rgb_sum, const std::vector<double>& sq_sum, const std::vector<uint32_t>& counts,
+                                             const std::vector<uint32_t>& passes, uint32_t W, uint32_t H) {
+    if (rgb_sum.size() != (size_t)W * H * 3 || sq_sum.size() != rgb_sum.size() || counts.size() != (size_t)W * H || passes.size() != counts.size())
+        throw Error("adaptive_variance: frames of another size");
+    std::vector<double> var(rgb_sum.size());
+    if (rt_adaptive_variance_host(rgb_sum.data(), sq_sum.data(), counts.data(), passes.data(), W, H, var.data()) != 0) throw Error(rt_last_error());
+    return var;
+}
+// Denoising a frame as it is (rt_denoise_frame, csrc/rt_denoise_frame.h): `denoise`, `denoise_albedo` and `denoise_variance` composed, for one
+// sample count or a count per pixel.  counts: null, or W*H per-pixel sample counts (then `samples` is ignored); var: null (the colour stop,
+// sigma[0] = sigma_c), or W*H*3 variances (the variance stop, sigma[0] = sigma_v); albedo_sum: null, or W*H*3 sums of albedo_samples samples.
+struct DenoiseFrameSettings {
+    bool variance = false; uint32_t albedo_samples = 0;          // what Progressive::rgb8_denoised_frame uses of the frame's own
+    uint32_t iterations = 2; double sigma[3] = {4.0, 0.5, 0.02}; uint32_t flags = 0;
+    static DenoiseFrameSettings with_variance(uint32_t albedo_samples = 0) { DenoiseFrameSettings d; d.variance = true; d.albedo_samples = albedo_samples; d.sigma[0] = 3.0; return d; }
+};
+inline std::vector<double> denoise_frame(const std::vector<double>& rgb_sum, const std::vector<uint32_t>* counts, uint64_t samples, const std::vector<double>* var,
+                                         const std::vector<double>* albedo_sum, uint64_t albedo_samples, const std::vector<double>& hit_records, uint32_t W, uint32_t H,
+                                         const DenoiseFrameSettings& d = DenoiseFrameSettings(), std::vector<double>* var_out = nullptr) {
+    if (rgb_sum.size() != (size_t)W * H * 3 || hit_records.size() != (size_t)W * H * 16 || (counts && counts->size() != (size_t)W * H) || (var && var->size() != rgb_sum.size()) ||
+        (albedo_sum && albedo_sum->size() != rgb_sum.size())) throw Error("denoise_frame: frame, counts, variance, albedo or records of another size");
+    std::vector<double> out(rgb_sum.size());
+    if (var_out) var_out->resize((size_t)W * H);
+    if (rt_denoise_frame(rgb_sum.data(), counts ? counts->data() : nullptr, samples, var ? var->data() : nullptr, albedo_sum ? albedo_sum->data() : nullptr, albedo_samples,
+                         hit_records.data(), W, H, d.iterations, d.sigma, d.flags, out.data(), var_out ? var_out->data() : nullptr) != 0) throw Error(rt_last_error());
+    return out;
+}
 
 // A progressive frame (rt_progressive_*): the same loop in passes of samples that accumulate on the device, with the reference's
 // format_color (src/vec.rs:125-131) resolved there too — progress, preview, stop half-way, "another 1000 samples", save and resume.
@@ -393,6 +422,15 @@ public:
         uint64_t w[4]; chk(rt_progressive_add_adaptive(p_, n_samples, tau, max_samples, spread, w)); return AdaptiveInfo{w[0], w[1], w[2], w[3]};
     }
     std::vector<uint32_t> counts() const { std::vector<uint32_t> out(n_px_); chk(rt_progressive_read_counts(p_, out.data(), nullptr)); return out; }      // n[p], W*H
+    // `variance` for any frame with moments: on an adaptive frame from every pixel's own counts (+inf where a pixel has fewer than two passes)
+    std::vector<double> variance_counts() { std::vector<double> out(n_px_ * 3); chk(rt_progressive_variance_counts(p_, out.data())); return out; }
+    // the denoised resolve of the frame as it is (`denoise_frame`): works on adaptive frames whose counts differ, and combines the variance stop
+    // (d.variance; needs moments) with albedo demodulation (d.albedo_samples >= 1)
+    std::vector<uint8_t> rgb8_denoised_frame(const DenoiseFrameSettings& d = DenoiseFrameSettings()) {
+        std::vector<uint8_t> out(n_px_ * 3);
+        chk(rt_progressive_resolve_denoised_frame_rgb8(p_, d.variance ? RT_DENOISE_STOP_VARIANCE : RT_DENOISE_STOP_COLOUR, d.albedo_samples, d.iterations, d.sigma, d.flags, out.data()));
+        return out;
+    }
 private:
     static void chk(int rc) { if (rc != 0) throw Error(rt_last_error()); }
     void* p_; size_t n_px_;

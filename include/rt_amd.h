@@ -358,7 +358,8 @@ int rt_adaptive_resolve_rgb8_device(const void* d_rgb_sum, const void* d_counts,
  *   rt_progressive_resolve_rgb8* use (D); error_map, error_map_device and error_stats use (A) (they need two passes of the frame, not of every pixel);
  *   rt_progressive_reset zeroes the counts; rt_progressive_read_sum / read_moments work as before;
  *   rt_progressive_variance, the three denoised resolves, rt_progressive_load_sum and rt_progressive_load_moments are errors while the counts
- *   are not uniform (all n[p] equal and all b[p] equal, which the host tracks), and behave as before while they are.
+ *   are not uniform (all n[p] equal and all b[p] equal, which the host tracks), and behave as before while they are;
+ *   rt_progressive_variance_counts and rt_progressive_resolve_denoised_frame_rgb8 (below) take the frame as it is.
  * While every pixel is listed and the frame is uniform a pass goes through the launch rt_progressive_add uses — the frames' own kernels are
  * the fast ones — followed by (C) over all pixels; otherwise through rt_render_pixels_device and the list merge. */
 int rt_progressive_enable_adaptive(void* frame);
@@ -560,6 +561,54 @@ int rt_denoise_variance_device(const void* d_rgb_sum, uint64_t samples, const vo
  * untouched.  Errors: those of rt_progressive_resolve_denoised_rgb8, and a frame without moments, with invalid moments or with fewer than
  * two passes. */
 int rt_progressive_resolve_denoised_variance_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out);
+
+/* ---- denoising a frame as it is: one sample count for the frame or a count per pixel (an adaptive frame), with or without a variance
+ *      frame, with or without albedo sums — the three filters above composed, and the only denoised form an adaptive frame with differing
+ *      counts has.  csrc/rt_denoise_frame.h is the exact specification: per pixel and channel, N = counts ? counts[p] : samples; m and d as in
+ *      rt_denoise_albedo (m = d = 1 without albedo_sum);  c = (rgb_sum / d) / N;  Vd = (var / d) / d;  y = rt_denoise(c, samples = 1, ...) or,
+ *      with var, rt_denoise_variance(c, samples = 1, Vd, ...);  out = ((N > 0 ? y * N : +0.0)) * m.  The filters in the middle are the ones
+ *      above, unchanged; with equal counts every word is the one rt_denoise*, rt_denoise_albedo* and rt_denoise_variance* give.  A pixel with
+ *      count 0 is left out as a neighbour, as a non-finite pixel is, and comes out 0.
+ *
+ * The variance frame of a frame with counts, (E) of that header: per pixel and channel, V = passes[p] >= 2 ? the V of rt_moments_variance
+ * with counts[p] samples and passes[p] passes : +inf (which the variance-guided filter counts as "no information").  counts, passes: W*H
+ * uint32; var_out: W*H*3 doubles.  The device form takes device pointers (doubles 8-byte aligned, counts 4-byte), never waits, never
+ * allocates; var_out may be neither input. */
+int rt_adaptive_variance_host(const double* rgb_sum, const double* sq_sum, const uint32_t* counts, const uint32_t* passes, uint32_t W, uint32_t H,
+                              double* var_out);
+int rt_adaptive_variance_device(const void* d_rgb_sum, const void* d_sq_sum, const void* d_counts, const void* d_passes, uint32_t W, uint32_t H,
+                                void* d_var_out, void* hip_stream);
+/* counts: W*H uint32 or NULL (then `samples` is the frame's count; with counts `samples` is ignored); var: W*H*3 doubles or NULL (NULL: the
+ * colour stop of rt_denoise, sigma[0] = sigma_c; else the variance stop of rt_denoise_variance, sigma[0] = sigma_v); albedo_sum: W*H*3 doubles
+ * or NULL (then albedo_samples is ignored); var_out: W*H doubles or NULL, the filtered v of rt_denoise_variance — of the DEMODULATED frame when
+ * albedo_sum is given — and an error without var.  Everything else, the errors and the three forms are those of rt_denoise_host / rt_denoise /
+ * rt_denoise_device.  The device form wraps two element-wise kernels (csrc/rt_denoise_frame.hip) around the unchanged filter and needs
+ * rt_denoise_frame_workspace_bytes(W, H) (the filter's 128 bytes per pixel and two frames of 24); d_counts is 4-byte aligned; d_rgb_sum_out
+ * may be d_rgb_sum. */
+int rt_denoise_frame_host(const double* rgb_sum, const uint32_t* counts, uint64_t samples, const double* var, const double* albedo_sum,
+                          uint64_t albedo_samples, const double* hits, uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3],
+                          uint32_t flags, double* rgb_sum_out, double* var_out);
+int rt_denoise_frame(const double* rgb_sum, const uint32_t* counts, uint64_t samples, const double* var, const double* albedo_sum,
+                     uint64_t albedo_samples, const double* hits, uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3],
+                     uint32_t flags, double* rgb_sum_out, double* var_out);
+size_t rt_denoise_frame_workspace_bytes(uint32_t W, uint32_t H);
+int rt_denoise_frame_device(const void* d_rgb_sum, const void* d_counts, uint64_t samples, const void* d_var, const void* d_albedo_sum,
+                            uint64_t albedo_samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3],
+                            uint32_t flags, void* d_rgb_sum_out, void* d_var_out, void* d_workspace, size_t workspace_bytes, void* hip_stream);
+/* rt_progressive_variance for any frame with moments: (E) with the frame's own counts on an adaptive frame (uniform or not; a pixel with
+ * fewer than two passes holds +inf), rt_progressive_variance itself on any other. */
+int rt_progressive_variance_counts(void* frame, double* var_out);
+/* The denoised resolve of any progressive frame, adaptive frames with differing counts included: byte for byte the resolve of
+ * rt_denoise_frame_host(rt_progressive_read_sum, the frame's counts or its sample count, stop = RT_DENOISE_STOP_VARIANCE ?
+ * rt_progressive_variance_counts : NULL, albedo_samples ? the albedo sums of rt_progressive_resolve_denoised_albedo_rgb8 : NULL,
+ * rt_query_camera(sample 0, the frame's seed)) — rt_format_color with the frame's sample count, or rt_adaptive_resolve_rgb8_host with its
+ * counts on an adaptive frame.  On a frame without counts the three modes that have a predecessor give that predecessor's bytes.  The
+ * sums, moments, counts, what the other resolves own and rt_progressive_albedo_info's behaviour are untouched.  Errors: those of
+ * rt_progressive_resolve_denoised_rgb8; an unknown stop; the variance stop on a frame without (valid) moments, or — a frame without
+ * counts — with fewer than two passes. */
+enum { RT_DENOISE_STOP_COLOUR = 0, RT_DENOISE_STOP_VARIANCE = 1 };
+int rt_progressive_resolve_denoised_frame_rgb8(void* frame, uint32_t stop, uint32_t albedo_samples, uint32_t iterations, const double sigma[3],
+                                               uint32_t flags, uint8_t* rgb8_out);
 
 /* The whole frame on several GPUs of this node from ONE call: what a host that owns the node's GPUs itself (the reference's `main`,
  * src/main.rs:767-835) calls instead of rt_render.  device_mask: bit d selects HIP device d (0 = every visible device).  The scene

@@ -165,6 +165,15 @@ SIGNATURES = {
     "denoise_variance_workspace_bytes": (C.c_size_t, [_u32, _u32]),
     "denoise_variance_device": (_int, [_ptr, _u64, _ptr, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, _ptr, C.c_size_t, _ptr]),
     "progressive_resolve_denoised_variance_rgb8": (_int, [_ptr, _u32, c_double_p, _u32, _ptr]),
+    # denoising a frame as it is: per-pixel counts, variance and albedo around the same filters
+    "adaptive_variance_host": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr]),
+    "adaptive_variance_device": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr]),
+    "denoise_frame_host": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr]),
+    "denoise_frame": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr]),
+    "denoise_frame_workspace_bytes": (C.c_size_t, [_u32, _u32]),
+    "denoise_frame_device": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, _ptr, C.c_size_t, _ptr]),
+    "progressive_variance_counts": (_int, [_ptr, _ptr]),
+    "progressive_resolve_denoised_frame_rgb8": (_int, [_ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr]),
     # radiance queries
     "query_radiance": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _ptr, _ptr, c_u64_p]),
     "query_radiance_device": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _u32, _int, _ptr, C.c_size_t, _ptr, _ptr, _ptr]),

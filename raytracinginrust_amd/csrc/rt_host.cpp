@@ -25,6 +25,7 @@
 #include "rt_moments.h"
 #include "rt_denoise_var.h"
 #include "rt_adaptive.h"
+#include "rt_denoise_frame.h"
 #include "rt_pixels.h"
 #include "rt_kat.h"
 
@@ -77,6 +78,9 @@ struct Progressive {
     // passes of the frame.  total: the sum of n[p].
     bool adaptive = false, uniform = true; uint64_t total = 0;
     void* d_cnt = nullptr; void* d_pas = nullptr; void* d_list = nullptr; void* d_words = nullptr; void* d_sel_ws = nullptr;
+    // rt_progressive_resolve_denoised_frame_rgb8's own, beside the denoised resolves': the per-pixel means c and the demodulated variance Vd
+    // of a run (rt_denoise_frame.h (F): two frames of 24 bytes per pixel, each padded to 16), allocated at its first call
+    void* d_fr_planes = nullptr;
     size_t n_px() const { return (size_t)W * H; }
 };
 
@@ -1720,7 +1724,7 @@ int rt_query_radiance(rt_scene* sc, uint32_t n, const double* rays, const double
 // what a call that knows one sample count for the whole frame checks first on an adaptive frame
 static int adaptive_needs_uniform(const Progressive* p, const char* what) {
     if (p && p->adaptive && !p->uniform)
-        return set_err(std::string(what) + ": the pixels of this adaptive frame hold different sample counts, and this call knows one count for the whole frame (rt_progressive_read_counts has them; denoising frames with non-uniform counts is not supported)");
+        return set_err(std::string(what) + ": the pixels of this adaptive frame hold different sample counts, and this call knows one count for the whole frame (rt_progressive_read_counts has them; rt_progressive_variance_counts and rt_progressive_resolve_denoised_frame_rgb8 take the frame as it is)");
     return 0;
 }
 static void progressive_free(Progressive* p) {
@@ -1731,6 +1735,7 @@ static void progressive_free(Progressive* p) {
     free_dev(p->d_alb_sum); free_dev(p->d_alb_x);
     free_dev(p->d_sq); free_dev(p->d_pass); free_dev(p->d_e2); free_dev(p->d_mstats); free_dev(p->d_var);
     free_dev(p->d_cnt); free_dev(p->d_pas); free_dev(p->d_list); free_dev(p->d_words); free_dev(p->d_sel_ws);
+    free_dev(p->d_fr_planes);
     if (p->ev_merged) { (void)hipEventDestroy(p->ev_merged); p->ev_merged = nullptr; }
 }
 void* rt_progressive_create(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t max_depth,
@@ -2614,6 +2619,144 @@ int rt_progressive_albedo_info(void* frame, uint32_t* albedo_samples_out, uint64
     Progressive* p = (Progressive*)frame;
     if (!p || !albedo_samples_out || !builds_out) return set_err("null argument");
     *albedo_samples_out = p->albedo_samples; *builds_out = p->albedo_builds;
+    return 0;
+}
+
+// ---------------------------------------------------------------- denoising a frame as it is (csrc/rt_denoise_frame.h: the specification; rt_denoise_frame.hip: the kernels)
+int rt_adaptive_variance_device(const void* d_rgb_sum, const void* d_sq_sum, const void* d_counts, const void* d_passes, uint32_t W, uint32_t H,
+                                void* d_var_out, void* hip_stream) {
+    if (!d_rgb_sum || !d_sq_sum || !d_counts || !d_passes || !d_var_out) return set_err("null argument");
+    const std::string problem = adaptive_frame_check(W, H);
+    if (!problem.empty()) return set_err(problem);
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum | (uintptr_t)d_var_out) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_passes) & 3u) != 0u)
+        return set_err("d_rgb_sum, d_sq_sum and d_var_out must be 8-byte aligned, d_counts and d_passes 4-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    HIP_OK((hipError_t)launch_frame_variance((const double*)d_rgb_sum, (const double*)d_sq_sum, (const uint32_t*)d_counts, (const uint32_t*)d_passes, W * H,
+                                             (double*)d_var_out, hip_stream));
+    return 0;
+}
+size_t rt_denoise_frame_workspace_bytes(uint32_t W, uint32_t H) { return denoise_frame_workspace_bytes((uint64_t)W * H); }
+
+// The launches of one run on `stream`: prepare (c into d_c; Vd into d_vd when there are both a variance frame and albedo sums), the filter's
+// own launches from d_c with samples = 1 to d_out, finish on d_out in place.  d_out may be d_sum: prepare has read it by the time anything
+// is written there (stream order).
+static int denoise_frame_enqueue(const double* d_sum, const uint32_t* d_counts, uint64_t samples, const double* d_var, const double* d_albedo_sum,
+                                 uint64_t albedo_samples, const double* d_hits, uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3],
+                                 uint32_t flags, double* d_out, double* d_var_out, void* d_workspace, double* d_c, double* d_vd, hipStream_t stream) {
+    const uint32_t n_px = W * H;
+    HIP_OK((hipError_t)launch_frame_prepare(d_sum, d_counts, samples, d_var, d_albedo_sum, albedo_samples, d_c, d_vd, n_px, stream));
+    if (d_var) {
+        if (denoise_variance_enqueue(d_c, 1u, d_albedo_sum ? d_vd : d_var, d_hits, W, H, iterations, sigma, flags, d_out, d_var_out, d_workspace, stream)) return -1;
+    } else if (denoise_enqueue(d_c, 1u, d_hits, W, H, iterations, sigma, flags, d_out, d_workspace, stream)) return -1;
+    HIP_OK((hipError_t)launch_frame_finish(d_out, d_counts, samples, d_albedo_sum, albedo_samples, n_px, stream));
+    return 0;
+}
+int rt_denoise_frame_device(const void* d_rgb_sum, const void* d_counts, uint64_t samples, const void* d_var, const void* d_albedo_sum,
+                            uint64_t albedo_samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3],
+                            uint32_t flags, void* d_rgb_sum_out, void* d_var_out, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!d_rgb_sum || !d_hits || !sigma || !d_rgb_sum_out || !d_workspace) return set_err("null argument");
+    const std::string problem = denoise_frame_check(d_counts != nullptr, samples, d_var != nullptr, d_albedo_sum != nullptr, albedo_samples, W, H, iterations, sigma,
+                                                    flags, d_var_out != nullptr);
+    if (!problem.empty()) return set_err(problem);
+    if (workspace_bytes < rt_denoise_frame_workspace_bytes(W, H))
+        return set_err("denoise: workspace too small: rt_denoise_frame_workspace_bytes(W, H) — the filter's 128 bytes per pixel and two frames of 24 — are needed");
+    if (query_aligned(d_hits, "d_hits") || query_aligned(d_workspace, "d_workspace")) return -1;
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_rgb_sum_out | (uintptr_t)d_var | (uintptr_t)d_var_out | (uintptr_t)d_albedo_sum) & 7u) != 0u || ((uintptr_t)d_counts & 3u) != 0u)
+        return set_err("d_rgb_sum, d_var, d_albedo_sum, d_rgb_sum_out and d_var_out must be 8-byte aligned, d_counts 4-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    const uint64_t n_px = (uint64_t)W * H;
+    unsigned char* planes = (unsigned char*)d_workspace + rt_denoise_workspace_bytes(W, H);
+    return denoise_frame_enqueue((const double*)d_rgb_sum, (const uint32_t*)d_counts, samples, (const double*)d_var, (const double*)d_albedo_sum, albedo_samples,
+                                 (const double*)d_hits, W, H, iterations, sigma, flags, (double*)d_rgb_sum_out, (double*)d_var_out, d_workspace,
+                                 (double*)planes, (double*)(planes + denoise_frame_plane_bytes(n_px)), (hipStream_t)hip_stream);
+}
+int rt_denoise_frame(const double* rgb_sum, const uint32_t* counts, uint64_t samples, const double* var, const double* albedo_sum,
+                     uint64_t albedo_samples, const double* hits, uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3],
+                     uint32_t flags, double* rgb_sum_out, double* var_out) {
+    if (!rgb_sum || !hits || !sigma || !rgb_sum_out) return set_err("null argument");
+    const std::string problem = denoise_frame_check(counts != nullptr, samples, var != nullptr, albedo_sum != nullptr, albedo_samples, W, H, iterations, sigma,
+                                                    flags, var_out != nullptr);
+    if (!problem.empty()) return set_err(problem);
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
+    const size_t ws_bytes = rt_denoise_frame_workspace_bytes(W, H);
+    DeviceBuffer d_sum, d_cnt, d_var, d_alb, d_hits, d_ws, d_vout;
+    HIP_OK(d_sum.alloc(sum_bytes)); HIP_OK(d_hits.alloc(hit_bytes)); HIP_OK(d_ws.alloc(ws_bytes));
+    if (counts) { HIP_OK(d_cnt.alloc(n * sizeof(uint32_t))); HIP_OK(hipMemcpy(d_cnt.get(), counts, n * sizeof(uint32_t), hipMemcpyHostToDevice)); }
+    if (var) { HIP_OK(d_var.alloc(sum_bytes)); HIP_OK(hipMemcpy(d_var.get(), var, sum_bytes, hipMemcpyHostToDevice)); }
+    if (albedo_sum) { HIP_OK(d_alb.alloc(sum_bytes)); HIP_OK(hipMemcpy(d_alb.get(), albedo_sum, sum_bytes, hipMemcpyHostToDevice)); }
+    if (var_out) HIP_OK(d_vout.alloc(n * sizeof(double)));
+    HIP_OK(hipMemcpy(d_sum.get(), rgb_sum, sum_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_hits.get(), hits, hit_bytes, hipMemcpyHostToDevice));
+    if (rt_denoise_frame_device(d_sum.get(), counts ? d_cnt.get() : nullptr, samples, var ? d_var.get() : nullptr, albedo_sum ? d_alb.get() : nullptr, albedo_samples,
+                                d_hits.get(), W, H, iterations, sigma, flags, d_sum.get(), var_out ? d_vout.get() : nullptr, d_ws.get(), ws_bytes, nullptr)) return -1;
+    HIP_OK(hipMemcpy(rgb_sum_out, d_sum.get(), sum_bytes, hipMemcpyDeviceToHost));       // (waits for the kernels: the null stream)
+    if (var_out) HIP_OK(hipMemcpy(var_out, d_vout.get(), n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+// what the variance of a frame with counts needs: moments that describe the sums (two passes are every pixel's own matter, (E))
+static int frame_variance_ready(Progressive* p) {
+    if (!p->adaptive) return moments_error_ready(p);
+    if (!p->moments_valid) return set_err("the moments of this frame are invalid: rt_progressive_load_sum loaded sums whose second moments are unknown (rt_progressive_reset or rt_progressive_load_moments)");
+    return 0;
+}
+// (E) on an adaptive frame, (4) on any other: into the frame's own variance frame, on `stream`
+static int frame_variance_enqueue(Progressive* p, hipStream_t stream) {
+    if (!p->adaptive) return progressive_variance_enqueue(p, stream);
+    if (!p->d_var) HIP_OK(hipMalloc(&p->d_var, p->n_px() * 3 * sizeof(double)));
+    HIP_OK((hipError_t)launch_frame_variance((const double*)p->d_sum, (const double*)p->d_sq, (const uint32_t*)p->d_cnt, (const uint32_t*)p->d_pas, (uint32_t)p->n_px(),
+                                             (double*)p->d_var, stream));
+    return 0;
+}
+int rt_progressive_variance_counts(void* frame, double* var_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!var_out) return set_err("null argument");
+    if (moments_frame(p) || frame_variance_ready(p)) return -1;
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the estimate
+    if (frame_variance_enqueue(p, nullptr)) return -1;
+    HIP_OK(hipMemcpy(var_out, p->d_var, p->n_px() * 3 * sizeof(double), hipMemcpyDeviceToHost));      // (waits for the kernel: the null stream)
+    return 0;
+}
+// The frame as it is — its counts when it has them, its variance under the variance stop, its albedo sums when asked for — filtered and
+// resolved; everything the other resolves own stays as it is.
+int rt_progressive_resolve_denoised_frame_rgb8(void* frame, uint32_t stop, uint32_t albedo_samples, uint32_t iterations, const double sigma[3],
+                                               uint32_t flags, uint8_t* rgb8_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !sigma || !rgb8_out) return set_err("null argument");
+    if (stop > (uint32_t)RT_DENOISE_STOP_VARIANCE) return set_err("denoise: stop must be RT_DENOISE_STOP_COLOUR = 0 or RT_DENOISE_STOP_VARIANCE = 1");
+    const bool variance = stop == (uint32_t)RT_DENOISE_STOP_VARIANCE;
+    if (variance) {
+        if (moments_frame(p) || frame_variance_ready(p)) return -1;
+        const std::string problem = denoise_variance_check(p->done ? p->done : 1u, p->W, p->H, iterations, sigma, flags);
+        if (!problem.empty()) return set_err(problem);
+    }
+    DeviceGuard guard(p->device);
+    if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
+    const size_t n = p->n_px(), sum_bytes = n * 3 * sizeof(double);
+    if (albedo_samples) {                                       // the albedo sums rt_progressive_resolve_denoised_albedo_rgb8 keeps, built as it builds them
+        if (p->albedo_samples != albedo_samples) {
+            if (!p->sc) return set_err("the scene of this progressive frame has been destroyed and the frame holds no albedo sums for this albedo_samples: they are built from the scene (rt_query_camera_albedo_device)");
+            if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
+        }
+        if (!p->d_alb_sum) HIP_OK(hipMalloc(&p->d_alb_sum, sum_bytes));
+        if (p->albedo_samples != albedo_samples) {
+            p->albedo_samples = 0;
+            if (rt_query_camera_albedo_device(p->sc, &p->cam, p->W, p->H, 0u, albedo_samples, p->seed, 0u, p->d_alb_sum, sum_bytes, nullptr)) return -1;
+            p->albedo_samples = albedo_samples; p->albedo_builds++;
+        }
+    }
+    const size_t plane = denoise_frame_plane_bytes(n);
+    if (!p->d_fr_planes) HIP_OK(hipMalloc(&p->d_fr_planes, 2u * plane));
+    if (variance && frame_variance_enqueue(p, nullptr)) return -1;
+    if (denoise_frame_enqueue((const double*)p->d_sum, p->adaptive ? (const uint32_t*)p->d_cnt : nullptr, p->done, variance ? (const double*)p->d_var : nullptr,
+                              albedo_samples ? (const double*)p->d_alb_sum : nullptr, albedo_samples, nullptr, p->W, p->H, iterations, sigma, flags,
+                              (double*)p->d_dn_sum, nullptr, p->d_dn_ws, (double*)p->d_fr_planes, (double*)((unsigned char*)p->d_fr_planes + plane), nullptr)) return -1;
+    if (!p->adaptive) return progressive_denoise_finish(p, rgb8_out);
+    HIP_OK(hipMemsetAsync(p->d_dn_changed, 0, sizeof(unsigned long long), nullptr));
+    HIP_OK((hipError_t)launch_adaptive_resolve((const double*)p->d_dn_sum, (const uint32_t*)p->d_cnt, nullptr, (uint8_t*)p->d_dn_rgb8, (unsigned long long*)p->d_dn_changed,
+                                               (uint32_t)n, nullptr));
+    HIP_OK(hipMemcpy(rgb8_out, p->d_dn_rgb8, n * 3, hipMemcpyDeviceToHost));             // (waits for the kernels: the null stream)
     return 0;
 }
 

@@ -14,6 +14,8 @@
 // rt_query_camera_albedo — and the result is multiplied back (rt_denoise_albedo*): what a textured scene needs.
 // --denoise-variance SIGMA_V (with --progressive N and --denoise K): the colour stop is SIGMA_V standard deviations of the frame's own
 // per-pixel variance instead of SIGMA_C (rt_progressive_resolve_denoised_variance_rgb8); the frame keeps moments and needs at least two passes.
+// With --denoise-albedo as well, and on an --adaptive frame with any of the three, the frame is denoised as it is — per-pixel counts, its
+// variance divided by the albedo squared — by rt_progressive_resolve_denoised_frame_rgb8; every other combination takes the call named above.
 //
 // --progressive N (opt-in, one GPU): the frame in passes of N samples per pixel (rt_progressive_*), the reference's style of progress on
 // stderr (main.rs:772-775), and the same PPM bytes at the end, built from the image the device resolved.
@@ -358,7 +360,8 @@ int main(int argc, char** argv) {
                         "  --denoise-albedo N                 with --denoise: filter the frame divided by its first-hit albedo (the mean over samples 0 .. N-1)\n"
                         "                                     and multiply back: textures are kept (textured scenes need it); also with --progressive\n"
                         "  --denoise-variance SIGMA_V         with --progressive N and --denoise K: the colour stop in standard deviations of the frame's own\n"
-                        "                                     per-pixel variance instead of SIGMA_C; needs at least two passes (--spp more than N)\n"
+                        "                                     per-pixel variance instead of SIGMA_C; needs at least two passes (--spp more than N);\n"
+                        "                                     also with --denoise-albedo, and all three also with --adaptive\n"
                         "  --until-error TAU [--max-samples M]  with --progressive N: stop at the first pass after which no pixel's estimated standard error\n"
                         "                                     exceeds TAU display units (0.00390625 = one code value), at the latest after M samples (default --spp)\n"
                         "  --adaptive                         with --progressive N and --until-error TAU: every pass samples only the pixels whose estimated standard\n"
@@ -376,7 +379,7 @@ int main(int argc, char** argv) {
     if (aov_kind == "samples" && !adaptive) { std::fprintf(stderr, "--aov samples goes with --adaptive\n"); return 2; }
     if (max_samples != 0u && until_error < 0.0) { std::fprintf(stderr, "--max-samples goes with --until-error TAU\n"); return 2; }
     if (albedo_samples != 0u && !want_denoise && aov_kind != "albedo") { std::fprintf(stderr, "--denoise-albedo goes with --denoise K (or --aov albedo)\n"); return 2; }
-    if (sigma_v != 0.0 && (!want_denoise || progressive == 0u || albedo_samples != 0u)) { std::fprintf(stderr, "--denoise-variance goes with --progressive N and --denoise K, and without --denoise-albedo\n"); return 2; }
+    if (sigma_v != 0.0 && (!want_denoise || progressive == 0u)) { std::fprintf(stderr, "--denoise-variance goes with --progressive N and --denoise K\n"); return 2; }
     const double aspect_ratio = (double)image_width / (double)image_height;
     try {
         Scene s;
@@ -491,6 +494,16 @@ int main(int argc, char** argv) {
             if (aov_kind == "error") {
                 if (frame.passes() < 2) throw Error("--aov error needs at least two passes: --spp must be more than the pass size of --progressive");
                 write_error_aov(aov_path, frame.error_map(), image_width, image_height);
+            }
+            if (want_denoise && (adaptive || (sigma_v != 0.0 && albedo_samples != 0u))) {
+                // the frame as it is: per-pixel counts, and the variance stop together with demodulation (rt_progressive_resolve_denoised_frame_rgb8)
+                if (sigma_v != 0.0 && !adaptive && frame.passes() < 2) throw Error("--denoise-variance needs at least two passes: --spp must be more than the pass size of --progressive");
+                DenoiseFrameSettings df;
+                df.variance = sigma_v != 0.0; df.albedo_samples = albedo_samples;
+                df.iterations = dn.iterations; df.sigma[0] = df.variance ? sigma_v : dn.sigma[0]; df.sigma[1] = dn.sigma[1]; df.sigma[2] = dn.sigma[2];
+                write_ppm_rgb8("-", frame.rgb8_denoised_frame(df), image_width, image_height);
+                std::fprintf(stderr, "Done.\n");
+                return 0;
             }
             if (sigma_v != 0.0) {
                 if (frame.passes() < 2) throw Error("--denoise-variance needs at least two passes: --spp must be more than the pass size of --progressive");

@@ -531,6 +531,26 @@ class Progressive:
         _check(self._lib.rt_progressive_resolve_denoised_variance_rgb8(self._h, k, sg, flags, out.ctypes.data))
         return out
 
+    def variance_counts(self) -> np.ndarray:
+        """rt_progressive_variance_counts: `variance` for any frame with moments, (H, W, 3) f64 — on an adaptive frame every pixel's variance
+        from its own sample and pass counts (`adaptive_variance_host`; +inf where a pixel has fewer than two passes), whether the counts
+        differ or not."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.float64)
+        _check(self._lib.rt_progressive_variance_counts(self._h, out.ctypes.data))
+        return out
+
+    def rgb8_denoised_frame(self, iterations: int = None, sigma=None, flags: int = 0, variance: bool = False, albedo_samples: int = 0) -> np.ndarray:
+        """rt_progressive_resolve_denoised_frame_rgb8: the denoised resolve of the frame as it is (`denoise_frame`) -> (H, W, 3) uint8.  Works
+        on adaptive frames whose counts differ, which the three resolves above refuse, and combines the variance stop (variance=True:
+        sigma = (sigma_v, sigma_n, sigma_p), default DENOISE_VARIANCE_SIGMA; needs moments) with albedo demodulation (albedo_samples >= 1).
+        On a frame without counts the three modes `rgb8_denoised`, `rgb8_denoised_albedo` and `rgb8_denoised_variance` cover give their bytes.
+        `sum`, `sq_sum`, `counts`, `rgb8` and its changed-pixel count are untouched."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        k, sg = _denoise_variance_settings(iterations, sigma) if variance else _denoise_settings(iterations, sigma)
+        _check(self._lib.rt_progressive_resolve_denoised_frame_rgb8(self._h, DENOISE_STOP_VARIANCE if variance else DENOISE_STOP_COLOUR, int(albedo_samples), k, sg,
+                                                                    flags, out.ctypes.data))
+        return out
+
     def albedo_info(self):
         """(the albedo_samples the frame holds albedo sums for — 0: none —, how many times it has built them)."""
         n, builds = C.c_uint32(), C.c_uint64()
@@ -1287,6 +1307,98 @@ def render_pixels_device(b: SceneBuilder, cam: CameraParams, background, W: int,
     bg = (C.c_double * 3)(*[float(x) for x in background])
     _check(_rt().rt_render_pixels_device(b.h, C.byref(cam), bg, W, H, int(n_samples), max_depth, seed, flags, _ptr_or_none(d_list), int(n_list),
                                          _ptr_or_none(d_counts), C.c_void_p(out_ptr), nbytes, C.c_void_p(stream)))
+
+
+# ---- denoising a frame as it is (rt_adaptive_variance*, rt_denoise_frame*; csrc/rt_denoise_frame.h): one sample count or a count per pixel,
+# with or without a variance frame, with or without albedo sums, around the unchanged filters
+DENOISE_STOP_COLOUR = 0
+DENOISE_STOP_VARIANCE = 1
+
+
+def adaptive_variance_host(rgb_sum, sq_sum, counts, passes) -> np.ndarray:
+    """rt_adaptive_variance_host (no GPU): the variance of the mean of every pixel and channel, (H, W, 3), from every pixel's own sample and
+    pass counts ((H, W) uint32); +inf where a pixel has fewer than two passes.  With equal counts: `moments_variance_host`."""
+    s, q, n, b = _adaptive_state(rgb_sum, sq_sum, counts, passes)
+    out = np.zeros(s.shape, dtype=np.float64)
+    _check(_rt().rt_adaptive_variance_host(s.ctypes.data, q.ctypes.data, n.ctypes.data, b.ctypes.data, s.shape[1], s.shape[0], out.ctypes.data))
+    return out
+
+
+def adaptive_variance(rgb_sum, sq_sum, counts, passes) -> np.ndarray:
+    """The same frame computed by the HIP kernel on the current device (rt_adaptive_variance_device on torch tensors) — the same words."""
+    import torch
+    s, q, n, b = _adaptive_state(rgb_sum, sq_sum, counts, passes)
+    d_s, d_q = torch.from_numpy(s.copy()).cuda(), torch.from_numpy(q.copy()).cuda()
+    d_n, d_b = torch.from_numpy(n.view(np.int32).copy()).cuda(), torch.from_numpy(b.view(np.int32).copy()).cuda()
+    d_v = torch.empty_like(d_s)
+    adaptive_variance_device(d_s, d_q, d_n, d_b, s.shape[1], s.shape[0], d_v)
+    torch.cuda.synchronize()
+    return d_v.cpu().numpy()
+
+
+def adaptive_variance_device(d_rgb_sum, d_sq_sum, d_counts, d_passes, W: int, H: int, d_var_out, stream: int = 0) -> None:
+    """rt_adaptive_variance_device: `adaptive_variance_host` for frames in device memory, enqueued on `stream`; never waits."""
+    _check(_rt().rt_adaptive_variance_device(_ptr_or_none(d_rgb_sum), _ptr_or_none(d_sq_sum), _ptr_or_none(d_counts), _ptr_or_none(d_passes), W, H,
+                                             _ptr_or_none(d_var_out), C.c_void_p(stream)))
+
+
+def _denoise_frame_call(fn, rgb_sum, hits, counts, samples, var, albedo_sum, albedo_samples, iterations, sigma, flags, want_var):
+    a, g = _denoise_frames(rgb_sum, hits)
+    n = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    if n is not None and n.shape != a.shape[:2]:
+        raise ValueError(f"counts of shape {n.shape} for a frame of {a.shape}: want (H, W)")
+    v = None if var is None else np.ascontiguousarray(var, dtype=np.float64)
+    al = None if albedo_sum is None else np.ascontiguousarray(albedo_sum, dtype=np.float64)
+    for name, x in (("var", v), ("albedo_sum", al)):
+        if x is not None and x.shape != a.shape:
+            raise ValueError(f"{name} of shape {x.shape} for a frame of {a.shape}")
+    k, sg = _denoise_settings(iterations, sigma) if v is None else _denoise_variance_settings(iterations, sigma)
+    out = np.zeros_like(a)
+    v_out = np.zeros(a.shape[:2], dtype=np.float64) if want_var else None
+    _check(fn(a.ctypes.data, None if n is None else n.ctypes.data, int(samples), None if v is None else v.ctypes.data,
+              None if al is None else al.ctypes.data, int(albedo_samples), g.ctypes.data, a.shape[1], a.shape[0], k, sg, flags, out.ctypes.data,
+              v_out.ctypes.data if want_var else None))
+    return (out, v_out) if want_var else out
+
+
+def denoise_frame_host(rgb_sum, hits, counts=None, samples: int = 1, var=None, albedo_sum=None, albedo_samples: int = 1, iterations: int = None, sigma=None,
+                       flags: int = 0, want_var: bool = False):
+    """rt_denoise_frame_host (no GPU): the frame denoise of csrc/rt_denoise_frame.h as plain C++.  counts (H, W) uint32 or None (then `samples`
+    is the frame's count); var (H, W, 3) or None (None: the colour stop of `denoise_host`, else the variance stop of `denoise_variance_host`
+    and its default sigma); albedo_sum (H, W, 3) holding albedo_samples samples, or None.  -> the filtered frame in sum units, (H, W, 3);
+    want_var (needs var): also the filtered variance, (H, W) — of the demodulated frame when albedo_sum is given."""
+    return _denoise_frame_call(_rt().rt_denoise_frame_host, rgb_sum, hits, counts, samples, var, albedo_sum, albedo_samples, iterations, sigma, flags, want_var)
+
+
+def denoise_frame(rgb_sum, hits, counts=None, samples: int = 1, var=None, albedo_sum=None, albedo_samples: int = 1, iterations: int = None, sigma=None,
+                  flags: int = 0, want_var: bool = False):
+    """rt_denoise_frame: the same call computed by the HIP kernels on the current device — the same words as denoise_frame_host."""
+    return _denoise_frame_call(_rt().rt_denoise_frame, rgb_sum, hits, counts, samples, var, albedo_sum, albedo_samples, iterations, sigma, flags, want_var)
+
+
+def denoise_frame_workspace_bytes(W: int, H: int) -> int:
+    return int(_rt().rt_denoise_frame_workspace_bytes(W, H))
+
+
+def denoise_frame_device(d_rgb_sum, d_hits, W: int, H: int, d_counts=None, samples: int = 1, d_var=None, d_albedo_sum=None, albedo_samples: int = 1,
+                         d_rgb_sum_out=None, d_var_out=None, d_workspace=None, iterations: int = None, sigma=None, flags: int = 0, stream: int = 0,
+                         workspace_bytes=None):
+    """rt_denoise_frame_device: `denoise_device` for a frame as it is — d_counts (W*H uint32 / int32), d_var and d_albedo_sum (W*H*3 f64) in
+    device memory, each optional; d_var_out: None, or W*H f64.  The workspace is denoise_frame_workspace_bytes(W, H) bytes."""
+    sum_ptr, _ = _device_buffer(d_rgb_sum)
+    out_ptr = sum_ptr if d_rgb_sum_out is None else _device_buffer(d_rgb_sum_out)[0]
+    if d_workspace is None:
+        import torch
+        d_workspace = torch.empty(denoise_frame_workspace_bytes(W, H), dtype=torch.uint8, device=d_rgb_sum.device)
+    ws_ptr, nbytes = _device_buffer(d_workspace)
+    nbytes = nbytes if workspace_bytes is None else int(workspace_bytes)
+    if nbytes is None:
+        raise ValueError("workspace_bytes is needed with a raw pointer")
+    k, sg = _denoise_settings(iterations, sigma) if d_var is None else _denoise_variance_settings(iterations, sigma)
+    _check(_rt().rt_denoise_frame_device(C.c_void_p(sum_ptr), _ptr_or_none(d_counts), int(samples), _ptr_or_none(d_var), _ptr_or_none(d_albedo_sum),
+                                         int(albedo_samples), _ptr_or_none(d_hits), W, H, k, sg, flags, C.c_void_p(out_ptr), _ptr_or_none(d_var_out),
+                                         C.c_void_p(ws_ptr), nbytes, C.c_void_p(stream)))
+    return d_workspace
 
 
 def kernel_time_total(b: SceneBuilder, reset: bool = False):
