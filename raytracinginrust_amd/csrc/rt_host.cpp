@@ -710,7 +710,7 @@ template <typename T> uint32_t tables_are_tame(const HostFlat& f) {
     return tame ? 1u : 0u;
 }
 
-// The launch shape of precision T: the kernel family's, with the lean f64 kernel's queue (rt_launch.h lean_f64_queue)
+// The launch shape of precision T: the kernel family's, with the lean f64 kernel's queue (rt_launch.h lean_f64_queue: HIT_RING_QN entries)
 template <typename T> static bool is_lean_f64(const HostFlat& f, uint32_t effective) { return sizeof(T) == 8u && pathtrace_feats(f.feats, effective) == 0u; }
 template <typename T> static LaunchShape shape_for(const HostFlat& f, uint32_t effective) {
     LaunchShape g = pathtrace_shape(f.feats, effective);
@@ -785,7 +785,9 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
         const long n = std::strtol(v, nullptr, 10);
         if ((n == 16 || n == 32 || n == 64) && !is_lean_f64<T>(f, P.flags)) { shape.queue_entries = (uint32_t)n; P.n_cached = cached_nodes<T>(shape, f, prop, P.stack_depth, P.flags); }
     }
-    P.queue_entries = shape.queue_entries;
+    // (the lean f64 kernel: the shape's entries are its first-hit ring's, which the kernel knows as a constant; the field keeps the 64 camera
+    // paths per refill of its RT_NO_PRIMARY_PASS route)
+    P.queue_entries = is_lean_f64<T>(f, P.flags) ? LEAN_F64_CAMERA_QN : shape.queue_entries;
     size_t shmem = pathtrace_lds_bytes(shape, P.stack_depth, P.n_cached, lds_node_bytes<T>(P.flags));
     int bpc = pathtrace_blocks_per_cu<T>(f.feats, P.flags, shmem);
     if (bpc <= 0) return set_err("occupancy query failed for the path-tracing kernel (LDS: " + std::to_string(shmem) + " bytes per workgroup)");

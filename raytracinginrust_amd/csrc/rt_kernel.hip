@@ -2226,46 +2226,52 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
 // The loop body is written material section first — shade what the last iteration left, then search, then pop —, so that the popped
 // records reach shade_hit as ordinary loop-carried values: with the pop in the middle of the body the compiler copied the whole path
 // state on every way into the material section and spilled 60 to 100 VGPRs (*seen*, measured 117 ms against the parent's 78).
-// The queue is a ring of 64 and the pass runs when fewer than FILL_AT records are left, for as many camera paths as the ring has room
-// for: waiting for an empty queue leaves the lanes that found it dry without a path through the next search (*measured*, Cornell box
-// 800 x 800 x 1024: FILL_AT 1 77.81 ms, 16 76.21, 24 76.43, 32 79.26; the parent 77.84).
+// The queue is a ring of HIT_RING_QN = 76 records (rt_launch.h: what five workgroups per CU leave room for) and the pass runs when fewer
+// than FILL_AT records are left, for as many camera paths as the ring has room for, 64 at the most: waiting for an empty queue leaves the
+// lanes that found it dry without a path through the next search (*measured* with a ring of 64, Cornell box 800 x 800 x 1024: FILL_AT 1
+// 77.81 ms, 16 76.21, 24 76.43, 32 79.26; the parent 77.84), and a ring of 64 that is refilled early has room for 48 ... 64 camera paths
+// only (*measured*: 60.66 lanes live at a search, 3.019 iterations per 64 samples; 76 entries refilled below 26: 62.29, 2.940).
 // A lane that pops a path of another pixel keeps its old pixel's sum (acc, acc_px) until the flush, where it has always stood; should the
 // new path end in the very shade it was popped for (Metal's absorbed ray, max_depth 1), its radiance goes to its own pixel with three
 // atomics of the lane's own (rare: flush_acc's PER_LANE form).
 // RT_NO_PRIMARY_PASS (park == nullptr) does not come here: pathtrace_kernel runs trace_lockstep, camera paths through the queue.
 template <typename T>
 DEV void hit_queue_put(T* q_real, uint32_t e, const Rec<T>& rec, V3<T> d, const Rng& rng, uint32_t px, uint32_t smp, uint32_t rect_front) {
-    uint32_t* q_u32 = (uint32_t*)(q_real + 9u * 64u);                 // [9][64] f64: p n d, [8][64] u32
-    q_real[0u * 64u + e] = rec.p.x; q_real[1u * 64u + e] = rec.p.y; q_real[2u * 64u + e] = rec.p.z;
-    q_real[3u * 64u + e] = rec.n.x; q_real[4u * 64u + e] = rec.n.y; q_real[5u * 64u + e] = rec.n.z;
-    q_real[6u * 64u + e] = d.x; q_real[7u * 64u + e] = d.y; q_real[8u * 64u + e] = d.z;
-    q_u32[0u * 64u + e] = rng.s0; q_u32[1u * 64u + e] = rng.s1; q_u32[2u * 64u + e] = rng.s2; q_u32[3u * 64u + e] = rng.s3;
-    q_u32[4u * 64u + e] = px; q_u32[5u * 64u + e] = smp; q_u32[6u * 64u + e] = rec.mat; q_u32[7u * 64u + e] = rect_front;
+    constexpr uint32_t QN = HIT_RING_QN;
+    uint32_t* q_u32 = (uint32_t*)(q_real + 9u * QN);                  // [9][QN] f64: p n d, [8][QN] u32
+    q_real[0u * QN + e] = rec.p.x; q_real[1u * QN + e] = rec.p.y; q_real[2u * QN + e] = rec.p.z;
+    q_real[3u * QN + e] = rec.n.x; q_real[4u * QN + e] = rec.n.y; q_real[5u * QN + e] = rec.n.z;
+    q_real[6u * QN + e] = d.x; q_real[7u * QN + e] = d.y; q_real[8u * QN + e] = d.z;
+    q_u32[0u * QN + e] = rng.s0; q_u32[1u * QN + e] = rng.s1; q_u32[2u * QN + e] = rng.s2; q_u32[3u * QN + e] = rng.s3;
+    q_u32[4u * QN + e] = px; q_u32[5u * QN + e] = smp; q_u32[6u * QN + e] = rec.mat; q_u32[7u * QN + e] = rect_front;
 }
 // `dead` lanes pop what the ring holds, in lane order.  True for the lanes that got a first-hit record.  One divergent branch and no
 // wave-uniform one ("nobody wants", "queue empty"): every further way to the material section is another set of copies of the path state.
 template <typename T>
 DEV bool hit_queue_pop(WaveWork& w, const T* q_real, bool dead, V3<T>& p, V3<T>& n, V3<T>& d, Rng& rng, uint32_t& px, uint32_t& smp, uint32_t& mat, uint32_t& rect_front) {
     const unsigned long long want = __ballot(dead);
-    const uint32_t* q_u32 = (const uint32_t*)(q_real + 9u * 64u);
+    constexpr uint32_t QN = HIT_RING_QN;
+    const uint32_t* q_u32 = (const uint32_t*)(q_real + 9u * QN);
     const uint32_t n_want = (uint32_t)__popcll(want);
     const uint32_t take = n_want < w.q_count ? n_want : w.q_count;
     const uint32_t rank = lane_rank(want);
     const bool got = dead && rank < take;
     if (got) {
-        const uint32_t e = (w.q_head + rank) & 63u;
-        p = mk<T>(q_real[0u * 64u + e], q_real[1u * 64u + e], q_real[2u * 64u + e]);
-        n = mk<T>(q_real[3u * 64u + e], q_real[4u * 64u + e], q_real[5u * 64u + e]);
-        d = mk<T>(q_real[6u * 64u + e], q_real[7u * 64u + e], q_real[8u * 64u + e]);
-        rng.s0 = q_u32[0u * 64u + e]; rng.s1 = q_u32[1u * 64u + e]; rng.s2 = q_u32[2u * 64u + e]; rng.s3 = q_u32[3u * 64u + e];
-        px = q_u32[4u * 64u + e]; smp = q_u32[5u * 64u + e]; mat = q_u32[6u * 64u + e]; rect_front = q_u32[7u * 64u + e];
+        const uint32_t e = hit_ring_slot(w.q_head, rank);          // (rank < take <= q_count <= QN)
+        p = mk<T>(q_real[0u * QN + e], q_real[1u * QN + e], q_real[2u * QN + e]);
+        n = mk<T>(q_real[3u * QN + e], q_real[4u * QN + e], q_real[5u * QN + e]);
+        d = mk<T>(q_real[6u * QN + e], q_real[7u * QN + e], q_real[8u * QN + e]);
+        rng.s0 = q_u32[0u * QN + e]; rng.s1 = q_u32[1u * QN + e]; rng.s2 = q_u32[2u * QN + e]; rng.s3 = q_u32[3u * QN + e];
+        px = q_u32[4u * QN + e]; smp = q_u32[5u * QN + e]; mat = q_u32[6u * QN + e]; rect_front = q_u32[7u * QN + e];
     }
-    w.q_head = (w.q_head + take) & 63u; w.q_count -= take;
+    w.q_head = hit_ring_slot(w.q_head, take); w.q_count -= take;
     return got;
 }
-// The pass runs when fewer than FILL_AT records are queued, for as many camera paths as the ring has room for (at least 64 - FILL_AT + 1).
-// *Measured* on the Cornell box, 800 x 800 x 1024: 1 (only when the queue is empty) 77.81 ms, 16 76.21, 24 76.43, 32 79.26; nothing between.
-static constexpr uint32_t FILL_AT = 16u;
+// The pass runs when fewer than FILL_AT records are queued, for as many camera paths as the ring has room for (at least HIT_RING_QN -
+// FILL_AT + 1, at most 64).  The value and what it was measured against: rt_launch.h HIT_RING_FILL_AT.
+static constexpr uint32_t FILL_AT = HIT_RING_FILL_AT;
+// Camera paths of a pass that finds `queued` records in the ring: a lane each, as far as the ring has room for their records
+DEV uint32_t pass_limit(uint32_t queued) { return HIT_RING_QN - queued < 64u ? HIT_RING_QN - queued : 64u; }
 template <typename T, uint32_t FEATS>
 DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
     static_assert(PrimaryPass<T, FEATS>::on, "the lean f64 kernel only");
@@ -2328,7 +2334,7 @@ DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
             double* const park = park_slot<T>(wave_slot, pl);
             park_paths(park, pl, ray, beta, rng, depth_left, path_s, alive);
             bool have;
-            if (gen_camera_paths(P, w, lane, 64u - w.q_count, true, have, ray, rng, path_px, path_s, obj_mask) != 0u) {
+            if (gen_camera_paths(P, w, lane, pass_limit(w.q_count), true, have, ray, rng, path_px, path_s, obj_mask) != 0u) {
                 primary = true;
                 alive = have; beta = mk<T>(T(1.0), T(1.0), T(1.0)); depth_left = P.max_depth;
             } else { unpark_paths(park, pl, ray, beta, rng, depth_left, path_s, alive); path_px = acc_px; obj_mask = 0xFFFFFFFFu; }      // (nothing left to generate: an ordinary iteration)
@@ -2394,8 +2400,8 @@ DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
             // the first-hit records are queued in lane order, and the wave takes its parked paths back; its dead lanes pop after the next search
             flush_acc<T, Acc, false>(P, ended, path_px, pacc, lane, n_flush);
             const unsigned long long sv = __ballot(alive);
-            if (alive) hit_queue_put(q_real, (w.q_head + w.q_count + lane_rank(sv)) & 63u, hr, ray.d, rng, path_px, path_s, hrect);
-            w.q_count += (uint32_t)__popcll(sv);               // (a ring of 64: at most 64 - q_count were generated)
+            if (alive) hit_queue_put(q_real, hit_ring_slot(w.q_head, w.q_count + lane_rank(sv)), hr, ray.d, rng, path_px, path_s, hrect);
+            w.q_count += (uint32_t)__popcll(sv);               // (a ring of HIT_RING_QN: at most HIT_RING_QN - q_count were generated)
             __builtin_amdgcn_wave_barrier();          // one wave: LDS writes above are ordered before the reads of the pops
             uint32_t pl = lane;
             double* const park = park_slot<T>(wave_slot, pl);
@@ -2704,12 +2710,12 @@ __global__ void __launch_bounds__(Shape<FEATS>::THREADS, Shape<FEATS>::WAVES_PER
         for (uint32_t i = threadIdx.x; i < nodes_bytes / 16u; i += S::THREADS) dst[i] = src[i];
         __syncthreads();
     }
-    const uint32_t QN = P.queue_entries;
-    if constexpr (PrimaryPass<T, FEATS>::on) {                     // 64 entries of 104 B: [9][64] f64, [8][64] u32 (rt_launch.h sizes it so)
-        unsigned char* regen = lds_raw + wave_in_block * regen_bytes_pp(64u);
+    const uint32_t QN = P.queue_entries;                           // (the other kernels' queue; the lean f64 kernel's ring below is HIT_RING_QN entries, a constant)
+    if constexpr (PrimaryPass<T, FEATS>::on) {                     // HIT_RING_QN entries of 104 B: [9][QN] f64, [8][QN] u32 (rt_launch.h sizes it so)
+        unsigned char* regen = lds_raw + wave_in_block * regen_bytes_pp(HIT_RING_QN);
         bool pass_on; { COLD_K; pass_on = PK(park) != nullptr; }
         if (pass_on) trace_shade_fill<T, FEATS>(P, lane, (T*)regen);
-        else trace_lockstep<T, FEATS>(P, lane, (T*)regen, (uint32_t*)(regen + 7u * 64u * sizeof(T)), nullptr);     // RT_NO_PRIMARY_PASS: camera paths through the queue, [7][64] f64 [6][64] u32 of the same 104 B
+        else trace_lockstep<T, FEATS>(P, lane, (T*)regen, (uint32_t*)(regen + 7u * LEAN_F64_CAMERA_QN * sizeof(T)), nullptr);     // RT_NO_PRIMARY_PASS: camera paths through the queue, [7][64] f64 [6][64] u32 at the front of the same region (KParams::queue_entries is 64)
         return;
     } else {
     unsigned char* regen = lds_raw + nodes_bytes + wave_in_block * regen_bytes(QN);
@@ -2758,6 +2764,8 @@ template <typename T> hipError_t launch_lean(const KParams<T>& P, uint32_t n_blo
 template <typename T> int occupancy_lean(size_t shmem);
 static LaunchShape shape_lean() { return shape_one<FEATS_LEAN>(); }
 #if RT_TU != 2
+void lean_f64_queue(LaunchShape& g) { g.queue_entries = HIT_RING_QN; g.entry_bytes = HIT_RING_ENTRY_BYTES; }
+static_assert(regen_bytes_pp(1u) == HIT_RING_ENTRY_BYTES && regen_bytes_pp(HIT_RING_QN) >= regen_bytes(LEAN_F64_CAMERA_QN), "the host sizes the LDS by the entry; the camera-path view fits in it");
 template <typename T> hipError_t launch_lean(const KParams<T>& P, uint32_t n_blocks, size_t shmem, hipStream_t stream) { return launch_one<T, FEATS_LEAN>(P, n_blocks, shmem, stream); }
 template <typename T> int occupancy_lean(size_t shmem) { return occupancy_one<T, FEATS_LEAN>(shmem); }
 template hipError_t launch_lean<double>(const KParams<double>&, uint32_t, size_t, hipStream_t);

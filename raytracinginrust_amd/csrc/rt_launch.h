@@ -8,9 +8,35 @@ namespace rt {
 // in the lean f64 kernel, whose entries carry beta: lean_f64_queue below), and whether it runs as ONE workgroup per CU (BVH kernels: the
 // CU's LDS then holds one copy of the top of the BVH, KParams::n_cached nodes).
 struct LaunchShape { uint32_t threads, queue_entries, entry_bytes; bool one_per_cu; };
-// The lean f64 kernel's queue (rt_kernel.hip PrimaryPass): always 64 entries of 104 B.  Every other shape is left as it is.
+// The lean f64 kernel's queue (rt_kernel.hip PrimaryPass, trace_shade_fill): a ring of HIT_RING_QN first-hit records of 104 B per wave.
+// The primary pass runs when fewer than HIT_RING_FILL_AT records are queued and generates min(64, HIT_RING_QN - queued) camera paths.
+// The one definition of both, for the kernel, for the LDS the host asks for and for lean_f64_queue; -DRT_HIT_RING_QN /
+// -DRT_HIT_RING_FILL_AT: measurement builds of the lean unit (tools/ring_sweep.py).
+// The constraint on the size: five workgroups per CU.  76 x 104 B x 4 waves = 31 616 B per workgroup keeps them; the frame time says
+// that 77 entries (32 032 B) do not, although the occupancy query still answers 5 — which is what an LDS allocation granule of 1280 B
+// would give; the granule itself was not read from anywhere.  The threshold trades popping lanes left dry (low) against short passes
+// (high) and was timed on the final build.  Both with their measurements: docs/history.md, profiles/r12_ring_step0.log.
+#ifndef RT_HIT_RING_QN
+#define RT_HIT_RING_QN 76
+#endif
+#ifndef RT_HIT_RING_FILL_AT
+#define RT_HIT_RING_FILL_AT 26
+#endif
+static constexpr uint32_t HIT_RING_QN = RT_HIT_RING_QN, HIT_RING_FILL_AT = RT_HIT_RING_FILL_AT;
+static constexpr uint32_t HIT_RING_ENTRY_BYTES = 9u * 8u + 8u * 4u;      // p n d as f64; rng, pixel, sample, material, rect | front << 31
+static_assert(HIT_RING_QN >= 64u && HIT_RING_FILL_AT >= 1u && HIT_RING_FILL_AT <= HIT_RING_QN, "a pass must find room for at least one path");
+// Slot k behind `head` (head < HIT_RING_QN, k <= HIT_RING_QN): add, compare, subtract — the capacity need be no power of two
+constexpr uint32_t hit_ring_slot(uint32_t head, uint32_t k) { return head + k >= HIT_RING_QN ? head + k - HIT_RING_QN : head + k; }
+constexpr bool hit_ring_slot_ok() {
+    for (uint32_t h = 0u; h < HIT_RING_QN; h++) for (uint32_t k = 0u; k <= HIT_RING_QN; k++) if (hit_ring_slot(h, k) != (h + k) % HIT_RING_QN) return false;
+    return true;
+}
+static_assert(hit_ring_slot_ok(), "hit_ring_slot is (head + k) mod HIT_RING_QN for every head and k");
+// Camera paths per refill with RT_NO_PRIMARY_PASS (trace_lockstep's [7][64] f64, [6][64] u32 view of the same LDS): KParams::queue_entries
+static constexpr uint32_t LEAN_F64_CAMERA_QN = 64u;
 static const uint32_t RT_PARK_BYTES_PER_WAVE = 64u * (9u * 8u + 7u * 4u);
-inline void lean_f64_queue(LaunchShape& g) { g.queue_entries = 64u; g.entry_bytes = 104u; }
+// Defined in the lean translation unit, so that a measurement build of that unit alone brings its own ring size to the host's LDS request
+void lean_f64_queue(LaunchShape& g);
 LaunchShape pathtrace_shape(uint32_t scene_feats, uint32_t flags);
 uint32_t pathtrace_feats(uint32_t scene_feats, uint32_t flags);      // the instantiation's FEATS template argument (its name: rt::pathtrace_kernel<T, FEATSu>)
 // Dynamic LDS of one workgroup: [n_cached nodes][waves x queue][waves x stack_depth x 64 dwords]
