@@ -1570,6 +1570,27 @@ void orc_hit_records(void* s, uint32_t n, const double* rays, uint64_t seed, dou
         for (size_t m = 0; m < SC->materials.size(); m++) if (SC->materials[m].get() == rec.material) o[11] = (double)m;
     }
 }
+// The same for ANY hittable handle and per-ray limits: HIT(h)->hit(ray k, tlim[2 k], tlim[2 k + 1]), records in the layout above, ray k on
+// Rng::for_stream(seed, k).  What tests/medium_cases.py walks a list with, item by item (an item's t_max is the closest hit so far), and
+// asks a ConstantMedium's boundary its two hits of medium.rs:29-30 with.
+void orc_hit_batch(void* s, int h, uint32_t n, const double* rays, const double* tlim, uint64_t seed, double* out) {
+    for (uint32_t k = 0; k < n; k++) {
+        const double* ry = rays + 7 * (size_t)k; double* o = out + 16 * (size_t)k;
+        Sampler smp; smp.rng = Rng::for_stream(seed, k);
+        HitRecord rec;
+        const bool any = HIT(h)->hit(Ray(V(ry), V(ry + 3), ry[6]), tlim[2 * (size_t)k], tlim[2 * (size_t)k + 1], smp, rec);
+        for (int i = 0; i < 16; i++) o[i] = 0.0;
+        o[11] = o[12] = o[13] = o[14] = -1.0;
+        if (!any) continue;
+        o[0] = 1.0; o[1] = rec.t; o[8] = rec.front_face ? 1.0 : 0.0; o[9] = rec.u; o[10] = rec.v;
+        for (int i = 0; i < 3; i++) { o[2 + i] = rec.position[i]; o[5 + i] = rec.normal[i]; }
+        for (size_t m = 0; m < SC->materials.size(); m++) if (SC->materials[m].get() == rec.material) o[11] = (double)m;
+    }
+}
+// sin and cos as Rotate::new takes them (orc_sincos: ONE sincos call for the pair): out[2 i] = sin a[i], out[2 i + 1] = cos a[i]
+void orc_sincos_batch(uint32_t n, const double* a, double* out) {
+    for (uint32_t i = 0; i < n; i++) { double sn, cs; orc_sincos(a[i], sn, cs); out[2 * (size_t)i] = sn; out[2 * (size_t)i + 1] = cs; }
+}
 // The libm this restatement is linked with, on n caller operands: op 1 sin, 2 cos, 3 tan, 4 atan, 5 atan2(a, b), 6 acos, 7 log, 8 log2,
 // 9 pow(a, b) (the product's rt_debug_math numbering; b is read by 5 and 9 only).  What tests/test_shade_kat_host.py measures.
 void orc_libm(uint32_t op, uint32_t n, const double* a, const double* b, double* out) {

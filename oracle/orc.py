@@ -135,6 +135,10 @@ def _declare(lib) -> Backend:
     lib.orc_ray_color_path.argtypes = [C.c_void_p, d3, d3, C.c_double, d3, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, d3]
     lib.orc_hit_records.restype = None
     lib.orc_hit_records.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.orc_hit_batch.restype = None
+    lib.orc_hit_batch.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    lib.orc_sincos_batch.restype = None
+    lib.orc_sincos_batch.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
     lib.orc_libm.restype = None
     lib.orc_libm.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.orc_shade_batch.restype = C.c_int
@@ -241,6 +245,25 @@ def hit_records(b, rays, seed=0):
     out = np.zeros((len(ry), 16), np.float64)
     load().lib.orc_hit_records(b.h, len(ry), ry.ctypes.data, int(seed), out.ctypes.data)
     return out
+
+
+def hit_batch(b, h, rays, t_min, t_max, seed=0):
+    """orc_hit_batch: h.hit(ray k, t_min[k], t_max[k]) of ANY hittable handle for n rays (n, 7) -> (n, 16) records in hit_records' layout;
+    t_min, t_max: one value each, or one per ray.  Ray k draws from Rng(seed, k) where a ConstantMedium needs a number."""
+    ry = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+    tlim = np.empty((len(ry), 2), np.float64)
+    tlim[:, 0] = t_min; tlim[:, 1] = t_max
+    out = np.zeros((len(ry), 16), np.float64)
+    load().lib.orc_hit_batch(b.h, h.id, len(ry), ry.ctypes.data, tlim.ctypes.data, int(seed), out.ctypes.data)
+    return out
+
+
+def sincos(a):
+    """orc_sincos_batch: (sin a, cos a) from ONE sincos call per operand, as Rotate::new takes its pair."""
+    a = np.ascontiguousarray(a, np.float64).reshape(-1)
+    out = np.zeros((len(a), 2), np.float64)
+    load().lib.orc_sincos_batch(len(a), a.ctypes.data, out.ctypes.data)
+    return out[:, 0].copy(), out[:, 1].copy()
 
 
 LIBM_OPS = ("", "sin", "cos", "tan", "atan", "atan2", "acos", "log", "log2", "pow")
