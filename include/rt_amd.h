@@ -695,6 +695,10 @@ int rt_last_stats(rt_scene*, unsigned long long out3[3]);
 /* Geometry of the most recent launch: [0] workgroups, [1] threads per workgroup, [2] dynamic LDS bytes per workgroup, [3] BVH nodes
  * staged in LDS by each workgroup (the top levels of the trees), [4] BVH nodes in the scene, [5] resident workgroups per CU. */
 int rt_last_launch_info(rt_scene*, uint32_t out6[6]);
+/* The first-hit ring of the most recent launch (the lean f64 list-scene kernels): [0] entries per wave, [1] bytes per entry
+ * (98 x 80: the compact form, 76 x 104: the wide one; both 0 for every other kernel), [2] 1 when the launch ran the lean f64 kernel with
+ * the wide ring, whose symbol is rt::pathtrace_wide_ring_kernel<double> and not the instantiation rt_last_loop_info names, 0 otherwise. */
+int rt_last_ring_info(rt_scene*, uint32_t out3[3]);
 /* Per-pixel accumulator flushes of the most recent finished launch; each is three f64 atomic adds to the frame — the
  * kernel's only global write traffic (used to calibrate the WRITE_SIZE counter). */
 int rt_last_flush_count(rt_scene*, unsigned long long* out);
@@ -790,6 +794,16 @@ int rt_debug_onb(rt_scene*, uint32_t n, const double* rects, const double* norma
  * slots_out[48 i + 6 s ..] = {v[3], u[3]} for the sign bits s = sx | sy << 1 | sz << 2.  Either pointer may be NULL.  Returns the number
  * of rect records, *n_valid_out the number of valid entries; -1 on error. */
 int rt_debug_onb_table(rt_scene*, uint64_t* mag_out, double* slots_out, uint32_t max_rects, uint32_t* n_valid_out);
+/* Test aid (host only, no GPU): the form of the first-hit ring this scene's frames get from the lean f64 kernels: *entries_out per wave of
+ * *entry_bytes_out each.  98 x 80, the compact form, where every rect record has a valid ONB-table entry (the normal of a queued hit is then
+ * three sign bits: the table holds its magnitudes); 76 x 104, the wide form, for every other list scene and under RT_NO_PRIMARY_PASS; 0 x 0
+ * where those kernels do not run (a scene with a feature bit, RT_F32 in flags).  Returns 1 for the compact form, 0 otherwise, -1 on error. */
+int rt_debug_ring_form(rt_scene*, uint32_t flags, uint32_t* entries_out, uint32_t* entry_bytes_out);
+/* Known-answer access to the normal of a compact first-hit record (rt_kernel.hip ring_pack_signs / ring_normal, the device functions the
+ * lean f64 kernel's loop calls): world.hit and the hit record for n given rays, the record's normal packed into three sign bits and rebuilt
+ * from the ONB table.  rays: n x (origin[3], direction[3]); t_min: n; out: n x 8 = hit (0 / 1), rect index (-1 on a miss), the hit record's
+ * normal[3], the rebuilt normal[3] (zeros on a miss).  Only for scenes whose ring is compact (rt_debug_ring_form).  Host pointers. */
+int rt_debug_ring_normal(rt_scene*, uint32_t n, const double* rays, const double* t_min, double* out);
 /* The pixel classifier of the lean f64 list-scene kernel's primary pass (csrc/rt_primary.h): the kernel runs the first level of the camera
  * paths of a refill together and does not search top-level objects that every ray it can generate for their pixel provably misses.  For
  * n pixels (pixels: n x (i, j), j counted from the bottom row) out_masks[p] has bit k set when object k of the flattened top-level list may

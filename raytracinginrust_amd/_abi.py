@@ -196,6 +196,7 @@ SIGNATURES = {
     "kernel_time_total": (_int, [_ptr, c_double_p, c_ull_p, _int]),
     "last_stats": (_int, [_ptr, c_ull_p]),
     "last_launch_info": (_int, [_ptr, c_u32_p]),
+    "last_ring_info": (_int, [_ptr, c_u32_p]),
     "last_flush_count": (_int, [_ptr, c_ull_p]),
     "last_traversal_stats": (_int, [_ptr, c_ull_p]),
     "last_leaf_steps": (_int, [_ptr, c_ull_p]),
@@ -216,6 +217,8 @@ SIGNATURES = {
     "debug_light_pdf": (_int, [_ptr, _u32, _ptr, _ptr, _ptr]),
     "debug_onb": (_int, [_ptr, _u32, _ptr, _ptr, _ptr]),
     "debug_onb_table": (_int, [_ptr, _ptr, _ptr, _u32, c_u32_p]),
+    "debug_ring_form": (_int, [_ptr, _u32, c_u32_p, c_u32_p]),
+    "debug_ring_normal": (_int, [_ptr, _u32, _ptr, _ptr, _ptr]),
     "debug_short_forms": (_int, [_u32, _u32, _ptr, _ptr, _ptr]),
     "debug_math": (_int, [_u32, _u32, _ptr, _ptr, _ptr]),
     "debug_brdf": (_int, [_ptr, _u32, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _u32]),

@@ -751,7 +751,7 @@ void build_onb_table(HostFlat& f) {
     DOnbEntry none; std::memset((void*)&none, 0, sizeof(none));
     for (int k = 0; k < 3; k++) none.mag[k] = ONB_MAG_INVALID;
     f.onb.assign(f.rects.size(), none);
-    f.onb_any = false;
+    f.onb_any = false; f.onb_all = false;
     if (f.feats != 0u || std::getenv("RT_NO_ONB_TABLE")) return;
     // per rect: the chain it is reached through — 0 none yet, 1 no rotation (bare / FlipNormals only), 2 + first_op the fused idiom,
     // ~0 more than one chain or any other chain (invalid)
@@ -788,6 +788,15 @@ void build_onb_table(HostFlat& f) {
         }
         f.onb_any = true;
     }
+    // every rect an object owns has its entry, and there is one: a hit's normal is then the entry's magnitudes and three sign bits,
+    // whichever rect it is on (rt_kernel.hip: Lemma N), which is what the compact first-hit ring needs.  (A record no object's range
+    // holds — the two box records behind a room's walls, form_room — is never tested and never hit.)
+    bool owned = false, all = true;
+    for (size_t i = 0; i < f.rects.size(); i++) {
+        if (how[i] == 0ull) continue;
+        owned = true; all = all && f.onb[i].mag[0] != ONB_MAG_INVALID;
+    }
+    f.onb_all = owned && all;
 }
 
 } // namespace

@@ -710,12 +710,21 @@ template <typename T> uint32_t tables_are_tame(const HostFlat& f) {
     return tame ? 1u : 0u;
 }
 
-// The launch shape of precision T: the kernel family's, with the lean f64 kernel's queue (rt_launch.h lean_f64_queue: HIT_RING_QN entries)
+// The launch shape of precision T: the kernel family's, with the lean f64 kernels' queue (rt_launch.h lean_f64_queue: the first-hit ring
+// in its compact or its wide form)
 template <typename T> static bool is_lean_f64(const HostFlat& f, uint32_t effective) { return sizeof(T) == 8u && pathtrace_feats(f.feats, effective) == 0u; }
+// Which of the two lean f64 kernels serves the scene: the compact ring where every rect has its entry in the ONB table (the kernel rebuilds
+// a hit's normal from it), the wide one everywhere else and without the pass (RT_NO_PRIMARY_PASS: A/B runs and tests)
+static bool lean_f64_compact(const HostFlat& f) { return f.onb_all && !std::getenv("RT_NO_PRIMARY_PASS"); }
 template <typename T> static LaunchShape shape_for(const HostFlat& f, uint32_t effective) {
     LaunchShape g = pathtrace_shape(f.feats, effective);
-    if (is_lean_f64<T>(f, effective)) lean_f64_queue(g);
+    if (is_lean_f64<T>(f, effective)) lean_f64_queue(g, lean_f64_compact(f));
     return g;
+}
+// resident workgroups per CU of the kernel that serves the scene — of the two lean f64 kernels, the one that will run
+template <typename T> static int blocks_per_cu_for(const HostFlat& f, uint32_t effective, size_t shmem) {
+    if (is_lean_f64<T>(f, effective)) return occupancy_lean_f64(lean_f64_compact(f), shmem);
+    return pathtrace_blocks_per_cu<T>(f.feats, effective, shmem);
 }
 
 // f<float> or f<double>, as the caller's flags ask
@@ -789,7 +798,7 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     // paths per refill of its RT_NO_PRIMARY_PASS route)
     P.queue_entries = is_lean_f64<T>(f, P.flags) ? LEAN_F64_CAMERA_QN : shape.queue_entries;
     size_t shmem = pathtrace_lds_bytes(shape, P.stack_depth, P.n_cached, lds_node_bytes<T>(P.flags));
-    int bpc = pathtrace_blocks_per_cu<T>(f.feats, P.flags, shmem);
+    int bpc = blocks_per_cu_for<T>(f, P.flags, shmem);
     if (bpc <= 0) return set_err("occupancy query failed for the path-tracing kernel (LDS: " + std::to_string(shmem) + " bytes per workgroup)");
     const uint64_t waves_per_block = shape.threads / 64u;
     uint64_t waves_needed = (n_local_px * spp + 63) / 64;
@@ -861,7 +870,11 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     if constexpr (sizeof(T) == 8u) {                 // (inside the timed span: the masks are part of what the frame costs)
         if (want_masks) HIP_OK(launch_primary_masks(P, (uint32_t)n_local_px, nullptr, (uint32_t*)slot->d_pmask, stream));
     }
-    HIP_OK(launch_pathtrace<T>(P, f.feats, (uint32_t)n_blocks, shmem, stream));
+    const bool lean_f64 = is_lean_f64<T>(f, P.flags), compact = lean_f64 && lean_f64_compact(f);
+    if constexpr (sizeof(T) == 8u) {
+        if (lean_f64) HIP_OK(launch_lean_f64(P, compact, (uint32_t)n_blocks, shmem, stream));
+        else HIP_OK(launch_pathtrace<T>(P, f.feats, (uint32_t)n_blocks, shmem, stream));
+    } else HIP_OK(launch_pathtrace<T>(P, f.feats, (uint32_t)n_blocks, shmem, stream));
     HIP_OK(hipEventRecord((hipEvent_t)slot->ev_stop, stream));
     slot->recorded = true; slot->timed = false; slot->seq = ++s.launch_seq; slot->group = s.frame_group; slot->harvested = false;
     c.last_slot = (int)(slot - c.slots);
@@ -871,6 +884,7 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     s.last_loop[1] = (int)pathtrace_feats(f.feats, P.flags);
     s.last_loop[0] = !(f.feats & F_BVH) ? 0 : ((s.last_loop[1] & (int)F_PERSIST) ? 2 : 1);
     s.last_loop[2] = (f.feats & F_BVH) ? loop_how : 0; s.last_loop[3] = sizeof(T) == 4 ? 1 : 0;
+    s.last_ring[0] = lean_f64 ? shape.queue_entries : 0u; s.last_ring[1] = lean_f64 ? shape.entry_bytes : 0u; s.last_ring[2] = lean_f64 && !compact ? 1u : 0u;
     return 0;
 }
 
@@ -1048,7 +1062,7 @@ template <typename T> static int prepare_device_as(Scene& s, Scene::DeviceCtx& c
     hipDeviceProp_t prop; HIP_OK(hipGetDeviceProperties(&prop, c.device));
     const uint32_t sd = stack_depth_of(s.flat, eff);
     const size_t shmem = pathtrace_lds_bytes(shape, sd, cached_nodes<T>(shape, s.flat, prop, sd, eff), lds_node_bytes<T>(eff));
-    if (pathtrace_blocks_per_cu<T>(s.flat.feats, eff, shmem) <= 0) return set_err("occupancy query failed for the path-tracing kernel");
+    if (blocks_per_cu_for<T>(s.flat, eff, shmem) <= 0) return set_err("occupancy query failed for the path-tracing kernel");
     HIP_OK(hipDeviceSynchronize());
     return 0;
 }
@@ -1105,6 +1119,28 @@ static int read_stats(rt_scene* sc, unsigned long long h[RT_STATS_SLOTS]) {
         for (Scene::LaunchSlot& l : c->slots) if (l.recorded && l.group == group && harvest_slot(s, l)) return -1;
     }
     for (uint32_t k = 0; k < RT_STATS_SLOTS; k++) h[k] = s.acc_group == group ? s.acc_stats[k] : 0ull;
+    return 0;
+}
+// Test aid (host only): the form of the lean f64 kernels' first-hit ring this scene's frames get (rt_launch.h): entries per wave and bytes
+// per entry — 98 x 80 (compact) where every rect has its entry in the ONB table, 76 x 104 (wide) otherwise and under RT_NO_PRIMARY_PASS;
+// 0 x 0 for a scene the lean f64 kernels do not serve (a feature bit, RT_F32 in `flags`).  Returns 1 for the compact form, 0 otherwise; -1 on error.
+int rt_debug_ring_form(rt_scene* sc, uint32_t flags, uint32_t* entries_out, uint32_t* entry_bytes_out) {
+    if (!sc) return set_err("null argument");
+    if (!flatten_for_render(sc->s)) return -1;
+    const HostFlat& f = sc->s.flat;
+    const bool lean = !(flags & RT_F32) && f.feats == 0u, compact = lean && lean_f64_compact(f);
+    LaunchShape g; g.threads = 0u; g.queue_entries = 0u; g.entry_bytes = 0u; g.one_per_cu = false;
+    if (lean) lean_f64_queue(g, compact);
+    if (entries_out) *entries_out = g.queue_entries;
+    if (entry_bytes_out) *entry_bytes_out = g.entry_bytes;
+    return compact ? 1 : 0;
+}
+// The first-hit ring of the most recent launch: [0] entries per wave, [1] bytes per entry (both 0: not one of the lean f64 kernels),
+// [2] 1 when the launch ran rt::pathtrace_wide_ring_kernel<double>, the lean f64 kernel with the wide ring, and not the instantiation
+// rt_last_loop_info names
+int rt_last_ring_info(rt_scene* sc, uint32_t out3[3]) {
+    if (!sc || !out3) return set_err("null argument");
+    for (int k = 0; k < 3; k++) out3[k] = sc->s.last_ring[k];
     return 0;
 }
 // Geometry of the most recent launch: [0] workgroups, [1] threads per workgroup, [2] dynamic LDS bytes per workgroup, [3] BVH nodes
@@ -1216,6 +1252,18 @@ int rt_debug_onb(rt_scene* sc, uint32_t n, const double* rects, const double* no
     for (uint32_t i = 0; i < n; i++)
         if (!(rects[i] >= 0.0 && rects[i] < (double)s.flat.rects.size() && rects[i] == std::floor(rects[i]))) return set_err("rt_debug_onb: rect index out of range");
     return run_kat(s, launch_onb_kat, n, rects, 8u, normals, 24u, out, 56u);
+}
+// Known-answer access to the normal of the lean f64 kernel's compact first-hit record (rt_kernel.hip ring_pack_signs / ring_normal, the
+// functions its loop calls): world.hit and the hit record for n given rays, the normal packed into its three sign bits and rebuilt from
+// the ONB table.  rays: n x (origin[3], direction[3]); t_min: n; out: n x 8 = hit (0 / 1), rect index (-1 on a miss), the hit record's
+// normal[3], the rebuilt normal[3] (zeros on a miss).  Serves the scenes that get the compact ring only (rt_debug_ring_form).  Host pointers.
+int rt_debug_ring_normal(rt_scene* sc, uint32_t n, const double* rays, const double* t_min, double* out) {
+    if (!sc || !rays || !t_min || !out) return set_err("null argument");
+    if (n == 0) return 0;
+    Scene& s = sc->s;
+    if (!flatten_for_render(s)) return -1;
+    if (s.flat.feats != 0u || !s.flat.onb_all) return set_err("rt_debug_ring_normal serves scenes with the compact first-hit ring only (a list scene in which every rect has a valid ONB-table entry)");
+    return run_kat(s, launch_ring_normal_kat, n, rays, 48u, t_min, 8u, out, 64u);
 }
 // Known-answer access to the shading side's arithmetic (csrc/rt_kat.hip): one device function per lane on caller operands, under either
 // code shape.  No scene.  Records per op: rt_kat.h KAT_RECORDS.  Host pointers.

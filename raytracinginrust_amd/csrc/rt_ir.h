@@ -124,7 +124,7 @@ template <typename T> struct KParams {
     const uint8_t* image_bytes;
     uint32_t stack_depth;          // per-lane BVH stack entries staged in LDS: 0 in the reference's traversal order (skip links), the tree depth for near-first
     uint32_t queue_entries;        // camera paths each wave's LDS queue holds (16, 32 or 64; 80 B each).  The lean f64 kernel: always 64, read only by
-                                   // its RT_NO_PRIMARY_PASS route; the size of its first-hit ring is the constant HIT_RING_QN (rt_launch.h), not this field
+                                   // its RT_NO_PRIMARY_PASS route; the size of its first-hit ring is a constant of rt_launch.h (HIT_RING_QN, HIT_RING_QN_COMPACT), not this field
     uint32_t n_cached;             // BVH nodes [0, n_cached) are copied into LDS by every workgroup at launch (depth order: the top levels)
     uint32_t bvh_tame;             // every BVH box is finite, below 1e300 in magnitude and has min <= max: rays that are tame too may
                                    // take the NaN-free form of AABB::hit (rt_kernel.hip: box_inside_tame) — same answers

@@ -1768,6 +1768,7 @@ DEV bool take_new_paths(const KParams<T>& P, WaveWork& w, uint32_t lane, T* q_re
 // other kernels.
 template <typename T, uint32_t FEATS> struct PrimaryPass { static constexpr bool on = RT_TU != 2 && FEATS == 0u && sizeof(T) == 8u; };
 static constexpr uint32_t regen_bytes_pp(uint32_t qn) { return 9u * qn * 8u + 8u * qn * 4u; }      // [9][QN] f64: p n d, [8][QN] u32 (hit_queue_put)
+static constexpr uint32_t regen_bytes_pp_compact(uint32_t qn) { return 6u * qn * 8u + 8u * qn * 4u; }      // [6][QN] f64: p d, [8][QN] u32 (hit_queue_put, compact form)
 static constexpr uint32_t PARK_BYTES = RT_PARK_BYTES_PER_WAVE;                                       // per wave: [9][64] f64, [7][64] u32
 
 // The object mask of the cursor's pixel (wave-uniform; rt_primary.h): one word per local pixel, written before the launch by
@@ -2213,11 +2214,12 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
 
 #undef path_px
 
-// ------------------------------------------------------------------ the lean f64 kernel: lock-step bounce loop with shade fill
+// ------------------------------------------------------------------ the lean f64 kernels: lock-step bounce loop with shade fill
 // The primary pass (above: PrimaryPass) stopping one stage earlier.  36 % of a wave's lanes end at their hit (the light, a miss) and used
 // to idle through shade_hit, a third of the iteration, before taking a queued path at the next top.  Here the pass ends after
 // finalize_hit: the camera paths that hit a scattering surface are queued as FIRST-HIT RECORDS (p, n, d, mat, rect | front << 31, rng,
-// pixel, sample — 104 B; beta is 1, depth_left is max_depth, the origin and the time are not read again), and in an ordinary iteration
+// pixel, sample — 104 B, or 80 B without n in the compact form, below; beta is 1, depth_left is max_depth, the origin and the time are
+// not read again), and in an ordinary iteration
 // the lanes whose path has just ended, or that had none, pop one BETWEEN the hit record and the material section and are shaded with the
 // wave.  A lane that finds the queue dry idles through that shade and through the next search and pops after it.  For that the decision
 // of shade_hit (does the path end at this hit?) is taken before its work: a DiffuseLight's `emitted` (mat.rs:395-401) is evaluated on
@@ -2226,56 +2228,84 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
 // The loop body is written material section first — shade what the last iteration left, then search, then pop —, so that the popped
 // records reach shade_hit as ordinary loop-carried values: with the pop in the middle of the body the compiler copied the whole path
 // state on every way into the material section and spilled 60 to 100 VGPRs (*seen*, measured 117 ms against the parent's 78).
-// The queue is a ring of HIT_RING_QN = 76 records (rt_launch.h: what five workgroups per CU leave room for) and the pass runs when fewer
+// The queue is a ring of QN records (rt_launch.h: what five workgroups per CU leave room for — 76 of 104 B refilled below 26, or 98 of 80 B
+// refilled below 36 in the compact form) and the pass runs when fewer
 // than FILL_AT records are left, for as many camera paths as the ring has room for, 64 at the most: waiting for an empty queue leaves the
 // lanes that found it dry without a path through the next search (*measured* with a ring of 64, Cornell box 800 x 800 x 1024: FILL_AT 1
 // 77.81 ms, 16 76.21, 24 76.43, 32 79.26; the parent 77.84), and a ring of 64 that is refilled early has room for 48 ... 64 camera paths
-// only (*measured*: 60.66 lanes live at a search, 3.019 iterations per 64 samples; 76 entries refilled below 26: 62.29, 2.940).
+// only (*measured*: 60.66 lanes live at a search, 3.019 iterations per 64 samples; 76 entries refilled below 26: 62.29, 2.940; 98 entries
+// refilled below 36: 63.77, 2.872 — the paths need 2.861).
 // A lane that pops a path of another pixel keeps its old pixel's sum (acc, acc_px) until the flush, where it has always stood; should the
 // new path end in the very shade it was popped for (Metal's absorbed ray, max_depth 1), its radiance goes to its own pixel with three
 // atomics of the lane's own (rare: flush_acc's PER_LANE form).
-// RT_NO_PRIMARY_PASS (park == nullptr) does not come here: pathtrace_kernel runs trace_lockstep, camera paths through the queue.
-template <typename T>
+// RT_NO_PRIMARY_PASS (park == nullptr) does not come here: the kernel runs trace_lockstep, camera paths through the queue.
+//
+// The COMPACT form (rt_launch.h; pathtrace_kernel<double, 0u>, the scenes with HostFlat::onb_all) leaves the normal out of the record:
+// 80 B, and 98 of them where 76 fit.  It rests on
+// LEMMA N.  For a rect with a valid entry in the per-face ONB table, the three sign-masked words of the normal finalize_hit gives a hit on
+// it equal that entry's mag[0..2], for every ray.  finalize_hit builds the normal from the rect's axis unit vector by set_face_normal
+// (negates or leaves), for the fused Translate(RotateY) idiom one rot_back by the op's constants, whose products have a factor +-0 or +-1
+// and are exact, and set_face_normal again; a NaN dot product gives front = false, a negation.  The ray decides sign bits only, and
+// rt_flatten.cpp build_onb_table fills mag by these very operations.  (On the device: tests/test_compact_ring_gpu.py, rt_debug_ring_normal.)
+// So the normal is its three sign bits — bits 28..30 of the rect word, which a 28-bit primitive index leaves clear — and the entry the
+// merged Lambertian arm's probe loads anyway.  The compact kernel carries every lane's normal that way, popped or not: it is rebuilt at
+// the top of the material section and is not a loop-carried value at all.
+DEV uint32_t ring_pack_signs(uint32_t rect_front, V3<double> n) {
+    const uint32_t sx = (uint32_t)((unsigned long long)__double_as_longlong(n.x) >> 63), sy = (uint32_t)((unsigned long long)__double_as_longlong(n.y) >> 63),
+                   sz = (uint32_t)((unsigned long long)__double_as_longlong(n.z) >> 63);
+    return rect_front | sx << HIT_RING_SIGN_SHIFT | sy << (HIT_RING_SIGN_SHIFT + 1u) | sz << (HIT_RING_SIGN_SHIFT + 2u);
+}
+DEV V3<double> ring_normal(const DOnbEntry* tab, uint32_t rect_signs) {
+    const DOnbEntry* e = tab + (rect_signs & HIT_RING_RECT_MASK);
+    typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
+    const ull2 m01 = *(const CAS ull2*)&e->mag[0];
+    const unsigned long long m2 = cl((const unsigned long long*)&e->mag[2]);
+    const unsigned long long s = rect_signs;
+    return mk<double>(__longlong_as_double((long long)(m01.x | ((s >> HIT_RING_SIGN_SHIFT) & 1ull) << 63)),
+                      __longlong_as_double((long long)(m01.y | ((s >> (HIT_RING_SIGN_SHIFT + 1u)) & 1ull) << 63)),
+                      __longlong_as_double((long long)(m2 | ((s >> (HIT_RING_SIGN_SHIFT + 2u)) & 1ull) << 63)));
+}
+template <typename T, bool COMPACT>
 DEV void hit_queue_put(T* q_real, uint32_t e, const Rec<T>& rec, V3<T> d, const Rng& rng, uint32_t px, uint32_t smp, uint32_t rect_front) {
-    constexpr uint32_t QN = HIT_RING_QN;
-    uint32_t* q_u32 = (uint32_t*)(q_real + 9u * QN);                  // [9][QN] f64: p n d, [8][QN] u32
+    constexpr uint32_t QN = hit_ring_qn(COMPACT), ND = COMPACT ? 3u : 6u;
+    uint32_t* q_u32 = (uint32_t*)(q_real + (ND + 3u) * QN);           // [9][QN] f64: p n d (compact: [6][QN], p d), [8][QN] u32
     q_real[0u * QN + e] = rec.p.x; q_real[1u * QN + e] = rec.p.y; q_real[2u * QN + e] = rec.p.z;
-    q_real[3u * QN + e] = rec.n.x; q_real[4u * QN + e] = rec.n.y; q_real[5u * QN + e] = rec.n.z;
-    q_real[6u * QN + e] = d.x; q_real[7u * QN + e] = d.y; q_real[8u * QN + e] = d.z;
+    if constexpr (!COMPACT) { q_real[3u * QN + e] = rec.n.x; q_real[4u * QN + e] = rec.n.y; q_real[5u * QN + e] = rec.n.z; }
+    q_real[ND * QN + e] = d.x; q_real[(ND + 1u) * QN + e] = d.y; q_real[(ND + 2u) * QN + e] = d.z;
     q_u32[0u * QN + e] = rng.s0; q_u32[1u * QN + e] = rng.s1; q_u32[2u * QN + e] = rng.s2; q_u32[3u * QN + e] = rng.s3;
-    q_u32[4u * QN + e] = px; q_u32[5u * QN + e] = smp; q_u32[6u * QN + e] = rec.mat; q_u32[7u * QN + e] = rect_front;
+    q_u32[4u * QN + e] = px; q_u32[5u * QN + e] = smp; q_u32[6u * QN + e] = rec.mat; q_u32[7u * QN + e] = rect_front;      // (compact: the signs of n are in the word already)
 }
 // `dead` lanes pop what the ring holds, in lane order.  True for the lanes that got a first-hit record.  One divergent branch and no
 // wave-uniform one ("nobody wants", "queue empty"): every further way to the material section is another set of copies of the path state.
-template <typename T>
+template <typename T, bool COMPACT>
 DEV bool hit_queue_pop(WaveWork& w, const T* q_real, bool dead, V3<T>& p, V3<T>& n, V3<T>& d, Rng& rng, uint32_t& px, uint32_t& smp, uint32_t& mat, uint32_t& rect_front) {
     const unsigned long long want = __ballot(dead);
-    constexpr uint32_t QN = HIT_RING_QN;
-    const uint32_t* q_u32 = (const uint32_t*)(q_real + 9u * QN);
+    constexpr uint32_t QN = hit_ring_qn(COMPACT), ND = COMPACT ? 3u : 6u;
+    const uint32_t* q_u32 = (const uint32_t*)(q_real + (ND + 3u) * QN);
     const uint32_t n_want = (uint32_t)__popcll(want);
     const uint32_t take = n_want < w.q_count ? n_want : w.q_count;
     const uint32_t rank = lane_rank(want);
     const bool got = dead && rank < take;
     if (got) {
-        const uint32_t e = hit_ring_slot(w.q_head, rank);          // (rank < take <= q_count <= QN)
+        const uint32_t e = hit_ring_slot<QN>(w.q_head, rank);      // (rank < take <= q_count <= QN)
         p = mk<T>(q_real[0u * QN + e], q_real[1u * QN + e], q_real[2u * QN + e]);
-        n = mk<T>(q_real[3u * QN + e], q_real[4u * QN + e], q_real[5u * QN + e]);
-        d = mk<T>(q_real[6u * QN + e], q_real[7u * QN + e], q_real[8u * QN + e]);
+        if constexpr (!COMPACT) n = mk<T>(q_real[3u * QN + e], q_real[4u * QN + e], q_real[5u * QN + e]);      // (compact: `n` is not touched)
+        d = mk<T>(q_real[ND * QN + e], q_real[(ND + 1u) * QN + e], q_real[(ND + 2u) * QN + e]);
         rng.s0 = q_u32[0u * QN + e]; rng.s1 = q_u32[1u * QN + e]; rng.s2 = q_u32[2u * QN + e]; rng.s3 = q_u32[3u * QN + e];
         px = q_u32[4u * QN + e]; smp = q_u32[5u * QN + e]; mat = q_u32[6u * QN + e]; rect_front = q_u32[7u * QN + e];
     }
-    w.q_head = hit_ring_slot(w.q_head, take); w.q_count -= take;
+    w.q_head = hit_ring_slot<QN>(w.q_head, take); w.q_count -= take;
     return got;
 }
-// The pass runs when fewer than FILL_AT records are queued, for as many camera paths as the ring has room for (at least HIT_RING_QN -
-// FILL_AT + 1, at most 64).  The value and what it was measured against: rt_launch.h HIT_RING_FILL_AT.
-static constexpr uint32_t FILL_AT = HIT_RING_FILL_AT;
+// The pass runs when fewer than FILL_AT records are queued, for as many camera paths as the ring has room for (at least QN - FILL_AT + 1,
+// at most 64).  The values and what they were measured against: rt_launch.h HIT_RING_FILL_AT, HIT_RING_FILL_AT_COMPACT.
 // Camera paths of a pass that finds `queued` records in the ring: a lane each, as far as the ring has room for their records
-DEV uint32_t pass_limit(uint32_t queued) { return HIT_RING_QN - queued < 64u ? HIT_RING_QN - queued : 64u; }
-template <typename T, uint32_t FEATS>
+template <bool COMPACT> DEV uint32_t pass_limit(uint32_t queued) { return hit_ring_qn(COMPACT) - queued < 64u ? hit_ring_qn(COMPACT) - queued : 64u; }
+template <typename T, uint32_t FEATS, bool COMPACT>
 DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
-    static_assert(PrimaryPass<T, FEATS>::on, "the lean f64 kernel only");
+    static_assert(PrimaryPass<T, FEATS>::on, "the lean f64 kernels only");
     typedef typename Shape<FEATS>::Acc Acc;
+    constexpr uint32_t QN = hit_ring_qn(COMPACT), FILL_AT = hit_ring_fill_at(COMPACT);
     WaveWork w; w.cur_px = w.end_px = w.cur_s = w.s_lo = w.s_hi = w.cur_gp = w.cur_i = w.cur_j = w.q_head = w.q_count = 0; w.queue_done = false;
     // per-lane path state
     bool alive = false;
@@ -2304,7 +2334,8 @@ DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
             bool done = false;
             V3<T> e = mk<T>(T(0), T(0), T(0));
             rec.p = ray.o; rec.front = (rect_front >> 31) != 0u;
-            shade_hit<T, FEATS>(P, rec, ray, beta, rng, depth_left, done, e, rect_front & 0x7FFFFFFFu);
+            if constexpr (COMPACT) rec.n = ring_normal(P.onb, rect_front);      // Lemma N: every lane's normal, popped or not
+            shade_hit<T, FEATS>(P, rec, ray, beta, rng, depth_left, done, e, rect_front & (COMPACT ? HIT_RING_RECT_MASK : 0x7FFFFFFFu));
             if (done) {
                 if (path_px == acc_px) add_radiance(P, beta * e, acc, n_nonfinite, path_px, path_s);
                 else {                                  // popped into another pixel and ended at once: its own three atomics
@@ -2334,7 +2365,7 @@ DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
             double* const park = park_slot<T>(wave_slot, pl);
             park_paths(park, pl, ray, beta, rng, depth_left, path_s, alive);
             bool have;
-            if (gen_camera_paths(P, w, lane, pass_limit(w.q_count), true, have, ray, rng, path_px, path_s, obj_mask) != 0u) {
+            if (gen_camera_paths(P, w, lane, pass_limit<COMPACT>(w.q_count), true, have, ray, rng, path_px, path_s, obj_mask) != 0u) {
                 primary = true;
                 alive = have; beta = mk<T>(T(1.0), T(1.0), T(1.0)); depth_left = P.max_depth;
             } else { unpark_paths(park, pl, ray, beta, rng, depth_left, path_s, alive); path_px = acc_px; obj_mask = 0xFFFFFFFFu; }      // (nothing left to generate: an ordinary iteration)
@@ -2348,7 +2379,8 @@ DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
         // ---- the first half of a level of ray_color (main.rs:41-84) for every live lane: the search, the hit record, and the paths that end here
         Acc pacc; pacc.set(0, 0.0); pacc.set(1, 0.0); pacc.set(2, 0.0);        // (in a pass) the radiance of the camera paths that ended
         bool ended = false;
-        Rec<T> hr; hr.p = rec.n; hr.n = rec.n; hr.t = hr.u = hr.v = T(0); hr.front = false; hr.mat = 0u;     // (lanes without a hit: any defined value)
+        Rec<T> hr; hr.t = hr.u = hr.v = T(0); hr.front = false; hr.mat = 0u;     // (lanes without a hit: any defined value)
+        if constexpr (COMPACT) { hr.p = ray.o; hr.n = ray.o; } else { hr.p = rec.n; hr.n = rec.n; }
         uint32_t hrect = 0u;
         if (alive) {
             bool done = false;
@@ -2395,13 +2427,14 @@ DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
         // the hit point is the next origin already (what shade_hit leaves there when the path goes on), on every lane: the old origin is dead
         // from the hit record on, not carried through the material section
         hrect |= hr.front ? 0x80000000u : 0u;
+        if constexpr (COMPACT) hrect = ring_pack_signs(hrect, hr.n);
         if (primary) {
             // ---- the end of the pass: what ended is handed in per pixel (one butterfly and three atomics, as for any other partial sum),
             // the first-hit records are queued in lane order, and the wave takes its parked paths back; its dead lanes pop after the next search
             flush_acc<T, Acc, false>(P, ended, path_px, pacc, lane, n_flush);
             const unsigned long long sv = __ballot(alive);
-            if (alive) hit_queue_put(q_real, hit_ring_slot(w.q_head, w.q_count + lane_rank(sv)), hr, ray.d, rng, path_px, path_s, hrect);
-            w.q_count += (uint32_t)__popcll(sv);               // (a ring of HIT_RING_QN: at most HIT_RING_QN - q_count were generated)
+            if (alive) hit_queue_put<T, COMPACT>(q_real, hit_ring_slot<QN>(w.q_head, w.q_count + lane_rank(sv)), hr, ray.d, rng, path_px, path_s, hrect);
+            w.q_count += (uint32_t)__popcll(sv);               // (a ring of QN: at most QN - q_count were generated)
             __builtin_amdgcn_wave_barrier();          // one wave: LDS writes above are ordered before the reads of the pops
             uint32_t pl = lane;
             double* const park = park_slot<T>(wave_slot, pl);
@@ -2409,8 +2442,9 @@ DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
             unshaded = false;
         } else {
             // ---- the lanes without a path take a first-hit record and join the others at the material section
-            ray.o = hr.p; rec.n = hr.n; rec.mat = hr.mat; rect_front = hrect;
-            if (hit_queue_pop(w, q_real, !alive, ray.o, rec.n, ray.d, rng, path_px, path_s, rec.mat, rect_front)) { beta = mk<T>(T(1.0), T(1.0), T(1.0)); depth_left = P.max_depth; alive = true; }
+            ray.o = hr.p; rec.mat = hr.mat; rect_front = hrect;
+            if constexpr (!COMPACT) rec.n = hr.n;
+            if (hit_queue_pop<T, COMPACT>(w, q_real, !alive, ray.o, rec.n, ray.d, rng, path_px, path_s, rec.mat, rect_front)) { beta = mk<T>(T(1.0), T(1.0), T(1.0)); depth_left = P.max_depth; alive = true; }
             unshaded = true;
         }
     }
@@ -2711,11 +2745,11 @@ __global__ void __launch_bounds__(Shape<FEATS>::THREADS, Shape<FEATS>::WAVES_PER
         __syncthreads();
     }
     const uint32_t QN = P.queue_entries;                           // (the other kernels' queue; the lean f64 kernel's ring below is HIT_RING_QN entries, a constant)
-    if constexpr (PrimaryPass<T, FEATS>::on) {                     // HIT_RING_QN entries of 104 B: [9][QN] f64, [8][QN] u32 (rt_launch.h sizes it so)
-        unsigned char* regen = lds_raw + wave_in_block * regen_bytes_pp(HIT_RING_QN);
+    if constexpr (PrimaryPass<T, FEATS>::on) {                     // the COMPACT ring: HIT_RING_QN_COMPACT entries of 80 B, [6][QN] f64, [8][QN] u32 (rt_launch.h sizes it so); the wide one: pathtrace_wide_ring_kernel below
+        unsigned char* regen = lds_raw + wave_in_block * regen_bytes_pp_compact(HIT_RING_QN_COMPACT);
         bool pass_on; { COLD_K; pass_on = PK(park) != nullptr; }
-        if (pass_on) trace_shade_fill<T, FEATS>(P, lane, (T*)regen);
-        else trace_lockstep<T, FEATS>(P, lane, (T*)regen, (uint32_t*)(regen + 7u * LEAN_F64_CAMERA_QN * sizeof(T)), nullptr);     // RT_NO_PRIMARY_PASS: camera paths through the queue, [7][64] f64 [6][64] u32 at the front of the same region (KParams::queue_entries is 64)
+        if (pass_on) trace_shade_fill<T, FEATS, true>(P, lane, (T*)regen);
+        else trace_lockstep<T, FEATS>(P, lane, (T*)regen, (uint32_t*)(regen + 7u * LEAN_F64_CAMERA_QN * sizeof(T)), nullptr);     // no pass (the host sends RT_NO_PRIMARY_PASS to the wide kernel; here for a null `park` all the same): camera paths through the queue, [7][64] f64 [6][64] u32 at the front of the same region (KParams::queue_entries is 64)
         return;
     } else {
     unsigned char* regen = lds_raw + nodes_bytes + wave_in_block * regen_bytes(QN);
@@ -2726,6 +2760,21 @@ __global__ void __launch_bounds__(Shape<FEATS>::THREADS, Shape<FEATS>::WAVES_PER
     else trace_lockstep<T, FEATS>(P, lane, q_real, q_u32, stack);
     }
 }
+
+#if RT_TU == 1
+// The lean f64 kernel with the WIDE first-hit ring (rt_launch.h): HIT_RING_QN entries of 104 B, [9][QN] f64, [8][QN] u32 — the scenes
+// without HostFlat::onb_all, and RT_NO_PRIMARY_PASS.  The same loop as pathtrace_kernel<double, 0u>'s over the other record: a kernel of
+// its own, not a second loop in that one (which cost 13 to 22 spilled VGPRs when it was tried).
+template <typename T>
+__global__ void __launch_bounds__(Shape<0u>::THREADS, Shape<0u>::WAVES_PER_SIMD) pathtrace_wide_ring_kernel(const KParams<T> P) {
+    static_assert(PrimaryPass<T, 0u>::on, "the lean f64 kernels only");
+    const uint32_t lane = threadIdx.x & 63u, wave_in_block = threadIdx.x >> 6;
+    unsigned char* regen = lds_raw + wave_in_block * regen_bytes_pp(HIT_RING_QN);
+    bool pass_on; { COLD_K; pass_on = PK(park) != nullptr; }
+    if (pass_on) trace_shade_fill<T, 0u, false>(P, lane, (T*)regen);
+    else trace_lockstep<T, 0u>(P, lane, (T*)regen, (uint32_t*)(regen + 7u * LEAN_F64_CAMERA_QN * sizeof(T)), nullptr);     // RT_NO_PRIMARY_PASS: camera paths through the queue, [7][64] f64 [6][64] u32 at the front of the same region (KParams::queue_entries is 64)
+}
+#endif
 
 #if RT_TU != 3 && RT_TU != 4      // (RT_TU == 3: csrc/rt_query.hip includes this file for the device functions above and brings its own kernels and launch code; 4: csrc/rt_kat.hip)
 // ------------------------------------------------------------------ launch
@@ -2764,8 +2813,22 @@ template <typename T> hipError_t launch_lean(const KParams<T>& P, uint32_t n_blo
 template <typename T> int occupancy_lean(size_t shmem);
 static LaunchShape shape_lean() { return shape_one<FEATS_LEAN>(); }
 #if RT_TU != 2
-void lean_f64_queue(LaunchShape& g) { g.queue_entries = HIT_RING_QN; g.entry_bytes = HIT_RING_ENTRY_BYTES; }
+void lean_f64_queue(LaunchShape& g, bool compact) { g.queue_entries = hit_ring_qn(compact); g.entry_bytes = hit_ring_entry_bytes(compact); }
 static_assert(regen_bytes_pp(1u) == HIT_RING_ENTRY_BYTES && regen_bytes_pp(HIT_RING_QN) >= regen_bytes(LEAN_F64_CAMERA_QN), "the host sizes the LDS by the entry; the camera-path view fits in it");
+static_assert(regen_bytes_pp_compact(1u) == HIT_RING_ENTRY_BYTES_COMPACT && regen_bytes_pp_compact(HIT_RING_QN_COMPACT) >= regen_bytes(LEAN_F64_CAMERA_QN), "the same for the compact ring");
+// the lean f64 kernel of either ring form (rt_launch.h): launched and queried by the name that runs
+hipError_t launch_lean_f64(const KParams<double>& P, bool compact, uint32_t n_blocks, size_t shmem, hipStream_t stream) {
+    if (compact) return launch_one<double, FEATS_LEAN>(P, n_blocks, shmem, stream);
+    if (shmem > 65536u) return hipErrorInvalidValue;               // (a ring is 31 616 B at the most)
+    hipLaunchKernelGGL((pathtrace_wide_ring_kernel<double>), dim3(n_blocks), dim3(Shape<FEATS_LEAN>::THREADS), shmem, stream, P);
+    return hipGetLastError();
+}
+int occupancy_lean_f64(bool compact, size_t shmem) {
+    if (compact) return occupancy_one<double, FEATS_LEAN>(shmem);
+    int nb = 0;
+    if (shmem > 65536u || hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pathtrace_wide_ring_kernel<double>, (int)Shape<FEATS_LEAN>::THREADS, shmem) != hipSuccess) return 0;
+    return nb;
+}
 template <typename T> hipError_t launch_lean(const KParams<T>& P, uint32_t n_blocks, size_t shmem, hipStream_t stream) { return launch_one<T, FEATS_LEAN>(P, n_blocks, shmem, stream); }
 template <typename T> int occupancy_lean(size_t shmem) { return occupancy_one<T, FEATS_LEAN>(shmem); }
 template hipError_t launch_lean<double>(const KParams<double>&, uint32_t, size_t, hipStream_t);
@@ -2807,6 +2870,33 @@ __global__ void onb_kat_kernel(const KParams<double> P, uint32_t n, const double
     if (hit) onb_memo_load(slot, v, u);
     double* o = out + 7ull * i;
     o[0] = hit ? 1.0 : 0.0; o[1] = v.x; o[2] = v.y; o[3] = v.z; o[4] = u.x; o[5] = u.y; o[6] = u.z;
+}
+// Known-answer access to the compact first-hit record's normal (rt_debug_ring_normal; Lemma N above hit_queue_put): world.hit and the hit
+// record for given rays as in list_hit_kat_kernel, then the record's rect word packed as the primary pass packs it (ring_pack_signs) and
+// the normal rebuilt from it as the material section rebuilds it (ring_normal).  out[8 i ..] = hit (0 / 1), the rect index,
+// finalize_hit's normal[3], the rebuilt normal[3].  P.onb is not null (the host serves scenes with HostFlat::onb_all only).
+__global__ void ring_normal_kat_kernel(const KParams<double> P, uint32_t n, const double* rays, const double* tlim, double* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t j = i < n ? i : n - 1u;                           // (a partial last wave repeats the last ray: every lane takes part in the votes)
+    RayT<double> ray; ray.o = mk<double>(rays[j * 6], rays[j * 6 + 1], rays[j * 6 + 2]); ray.d = mk<double>(rays[j * 6 + 3], rays[j * 6 + 4], rays[j * 6 + 5]); ray.tm = 0.0;
+    Rng rng = rng_for_path(0ull, 0u, 0u);
+    double t_hit; HitId id; id.obj = 0u; id.prim = 0u;
+    const bool any = world_hit_list<double>(P, ray, tlim[j], rng, t_hit, id);
+    Rec<double> rec; rec.p = mk<double>(0.0, 0.0, 0.0); rec.n = rec.p; rec.t = 0.0; rec.u = rec.v = 0.0; rec.front = false; rec.mat = 0u;
+    V3<double> back = rec.p;
+    if (any) {
+        finalize_hit<double, 0u>(P, ray, t_hit, id, true, rec);
+        const uint32_t word = ring_pack_signs((id.prim & 0x0FFFFFFFu) | (rec.front ? 0x80000000u : 0u), rec.n);
+        back = ring_normal(P.onb, word);
+    }
+    if (i < n) {
+        double* o = out + 8ull * i;
+        o[0] = any ? 1.0 : 0.0; o[1] = any ? (double)(id.prim & 0x0FFFFFFFu) : -1.0; o[2] = rec.n.x; o[3] = rec.n.y; o[4] = rec.n.z; o[5] = back.x; o[6] = back.y; o[7] = back.z;
+    }
+}
+hipError_t launch_ring_normal_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream) {
+    hipLaunchKernelGGL(ring_normal_kat_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_rays, d_tlim, d_out);
+    return hipGetLastError();
 }
 hipError_t launch_onb_kat(const KParams<double>& P, uint32_t n, const double* d_rects, const double* d_normals, double* d_out, hipStream_t stream) {
     hipLaunchKernelGGL(onb_kat_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_rects, d_normals, d_out);

@@ -8,35 +8,65 @@ namespace rt {
 // in the lean f64 kernel, whose entries carry beta: lean_f64_queue below), and whether it runs as ONE workgroup per CU (BVH kernels: the
 // CU's LDS then holds one copy of the top of the BVH, KParams::n_cached nodes).
 struct LaunchShape { uint32_t threads, queue_entries, entry_bytes; bool one_per_cu; };
-// The lean f64 kernel's queue (rt_kernel.hip PrimaryPass, trace_shade_fill): a ring of HIT_RING_QN first-hit records of 104 B per wave.
-// The primary pass runs when fewer than HIT_RING_FILL_AT records are queued and generates min(64, HIT_RING_QN - queued) camera paths.
-// The one definition of both, for the kernel, for the LDS the host asks for and for lean_f64_queue; -DRT_HIT_RING_QN /
-// -DRT_HIT_RING_FILL_AT: measurement builds of the lean unit (tools/ring_sweep.py).
+// The lean f64 kernels' queue (rt_kernel.hip PrimaryPass, trace_shade_fill): a ring of first-hit records per wave, in one of two forms.
+// The primary pass runs when fewer than FILL_AT records are queued and generates min(64, QN - queued) camera paths.
+// WIDE: 104 B a record — p, n, d as f64; rng, pixel, sample, material, rect | front << 31 —, HIT_RING_QN = 76 records refilled below
+// HIT_RING_FILL_AT = 26.  COMPACT: 80 B — the same without n, whose three sign bits ride in bits 28..30 of the rect word —,
+// HIT_RING_QN_COMPACT records refilled below HIT_RING_FILL_AT_COMPACT.  The compact form serves the scenes in which every rect has a valid
+// entry in the per-face ONB table (HostFlat::onb_all): there the sign-masked words of a hit's normal are the entry's mag[0..2] for every
+// ray (rt_kernel.hip: Lemma N above trace_shade_fill), so the normal is rebuilt from the table and three bits.  Every other scene, and
+// RT_NO_PRIMARY_PASS, runs the wide kernel.
+// The one definition of the constants, for the kernels, for the LDS the host asks for and for lean_f64_queue; -DRT_HIT_RING_QN /
+// -DRT_HIT_RING_FILL_AT / -DRT_HIT_RING_QN_COMPACT / -DRT_HIT_RING_FILL_AT_COMPACT: measurement builds of the lean unit
+// (tools/ring_sweep.py).
 // The constraint on the size: five workgroups per CU.  76 x 104 B x 4 waves = 31 616 B per workgroup keeps them; the frame time says
 // that 77 entries (32 032 B) do not, although the occupancy query still answers 5 — which is what an LDS allocation granule of 1280 B
-// would give; the granule itself was not read from anywhere.  The threshold trades popping lanes left dry (low) against short passes
-// (high) and was timed on the final build.  Both with their measurements: docs/history.md, profiles/r12_ring_step0.log.
+// would give; the granule itself was not read from anywhere.  98 x 80 B x 4 waves = 31 360 B.  The threshold trades popping lanes left
+// dry (low) against short passes (high) and was timed on the final build.  Both with their measurements: docs/history.md,
+// profiles/r12_ring_step0.log, profiles/r13_ring_step0.log.
 #ifndef RT_HIT_RING_QN
 #define RT_HIT_RING_QN 76
 #endif
 #ifndef RT_HIT_RING_FILL_AT
 #define RT_HIT_RING_FILL_AT 26
 #endif
+#ifndef RT_HIT_RING_QN_COMPACT
+#define RT_HIT_RING_QN_COMPACT 98
+#endif
+#ifndef RT_HIT_RING_FILL_AT_COMPACT
+#define RT_HIT_RING_FILL_AT_COMPACT 36
+#endif
 static constexpr uint32_t HIT_RING_QN = RT_HIT_RING_QN, HIT_RING_FILL_AT = RT_HIT_RING_FILL_AT;
+static constexpr uint32_t HIT_RING_QN_COMPACT = RT_HIT_RING_QN_COMPACT, HIT_RING_FILL_AT_COMPACT = RT_HIT_RING_FILL_AT_COMPACT;
 static constexpr uint32_t HIT_RING_ENTRY_BYTES = 9u * 8u + 8u * 4u;      // p n d as f64; rng, pixel, sample, material, rect | front << 31
+static constexpr uint32_t HIT_RING_ENTRY_BYTES_COMPACT = 6u * 8u + 8u * 4u;      // p d as f64; rng, pixel, sample, material, rect | signs of n << 28 | front << 31
+static constexpr uint32_t HIT_RING_SIGN_SHIFT = 28u, HIT_RING_RECT_MASK = 0x0FFFFFFFu;      // (a primitive index has 28 bits: rt_kernel.hip HitId)
+static constexpr uint32_t hit_ring_qn(bool compact) { return compact ? HIT_RING_QN_COMPACT : HIT_RING_QN; }
+static constexpr uint32_t hit_ring_fill_at(bool compact) { return compact ? HIT_RING_FILL_AT_COMPACT : HIT_RING_FILL_AT; }
+static constexpr uint32_t hit_ring_entry_bytes(bool compact) { return compact ? HIT_RING_ENTRY_BYTES_COMPACT : HIT_RING_ENTRY_BYTES; }
 static_assert(HIT_RING_QN >= 64u && HIT_RING_FILL_AT >= 1u && HIT_RING_FILL_AT <= HIT_RING_QN, "a pass must find room for at least one path");
-// Slot k behind `head` (head < HIT_RING_QN, k <= HIT_RING_QN): add, compare, subtract — the capacity need be no power of two
-constexpr uint32_t hit_ring_slot(uint32_t head, uint32_t k) { return head + k >= HIT_RING_QN ? head + k - HIT_RING_QN : head + k; }
-constexpr bool hit_ring_slot_ok() {
-    for (uint32_t h = 0u; h < HIT_RING_QN; h++) for (uint32_t k = 0u; k <= HIT_RING_QN; k++) if (hit_ring_slot(h, k) != (h + k) % HIT_RING_QN) return false;
+static_assert(HIT_RING_QN_COMPACT >= 64u && HIT_RING_FILL_AT_COMPACT >= 1u && HIT_RING_FILL_AT_COMPACT <= HIT_RING_QN_COMPACT, "a pass must find room for at least one path");
+#ifndef RT_HIT_RING_ANY_SIZE      // (measurement builds that give up the fifth workgroup on purpose: tools/ring_sweep.py's counter runs)
+static_assert(HIT_RING_QN * HIT_RING_ENTRY_BYTES * 4u <= 31616u && HIT_RING_QN_COMPACT * HIT_RING_ENTRY_BYTES_COMPACT * 4u <= 31616u,
+              "a workgroup's four rings stay within what five workgroups per CU leave");
+#endif
+// Slot k behind `head` (head < QN, k <= QN): add, compare, subtract — the capacity need be no power of two
+template <uint32_t QN = HIT_RING_QN> constexpr uint32_t hit_ring_slot(uint32_t head, uint32_t k) { return head + k >= QN ? head + k - QN : head + k; }
+template <uint32_t QN> constexpr bool hit_ring_slot_ok() {
+    for (uint32_t h = 0u; h < QN; h++) for (uint32_t k = 0u; k <= QN; k++) if (hit_ring_slot<QN>(h, k) != (h + k) % QN) return false;
     return true;
 }
-static_assert(hit_ring_slot_ok(), "hit_ring_slot is (head + k) mod HIT_RING_QN for every head and k");
+static_assert(hit_ring_slot_ok<HIT_RING_QN>() && hit_ring_slot_ok<HIT_RING_QN_COMPACT>(), "hit_ring_slot is (head + k) mod QN for every head and k, at both capacities");
 // Camera paths per refill with RT_NO_PRIMARY_PASS (trace_lockstep's [7][64] f64, [6][64] u32 view of the same LDS): KParams::queue_entries
 static constexpr uint32_t LEAN_F64_CAMERA_QN = 64u;
 static const uint32_t RT_PARK_BYTES_PER_WAVE = 64u * (9u * 8u + 7u * 4u);
-// Defined in the lean translation unit, so that a measurement build of that unit alone brings its own ring size to the host's LDS request
-void lean_f64_queue(LaunchShape& g);
+// Defined in the lean translation unit, so that a measurement build of that unit alone brings its own ring sizes to the host's LDS request
+void lean_f64_queue(LaunchShape& g, bool compact);
+// The two lean f64 kernels (the lean translation unit): pathtrace_kernel<double, 0u> runs the compact ring, pathtrace_wide_ring_kernel<double>
+// the wide one — the same loop over another record; two kernels and not two loops in one, which costs spilled registers.  The host
+// chooses (rt_host.cpp lean_f64_compact), launches and queries the one it chose.
+hipError_t launch_lean_f64(const KParams<double>& P, bool compact, uint32_t n_blocks, size_t shmem, hipStream_t stream);
+int occupancy_lean_f64(bool compact, size_t shmem);
 LaunchShape pathtrace_shape(uint32_t scene_feats, uint32_t flags);
 uint32_t pathtrace_feats(uint32_t scene_feats, uint32_t flags);      // the instantiation's FEATS template argument (its name: rt::pathtrace_kernel<T, FEATSu>)
 // Dynamic LDS of one workgroup: [n_cached nodes][waves x queue][waves x stack_depth x 64 dwords]
@@ -58,6 +88,8 @@ hipError_t launch_list_hit_kat(const KParams<double>& P, uint32_t n, const doubl
 hipError_t launch_list_hit_masked_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream);
 // Known-answer access to the per-face ONB memo as the lean f64 kernel's Lambertian arm reads it (rt_debug_onb; the lean translation unit)
 hipError_t launch_onb_kat(const KParams<double>& P, uint32_t n, const double* d_rects, const double* d_normals, double* d_out, hipStream_t stream);
+// Known-answer access to the compact first-hit record's normal, packed and rebuilt as the lean f64 kernel does it (rt_debug_ring_normal; the lean translation unit)
+hipError_t launch_ring_normal_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream);
 // The primary pass's object masks (csrc/rt_primary.h; the kernel lives in the lean translation unit): d_pixels == nullptr — one word per
 // local pixel of the launch P describes (camera, frame size, tiling), what KParams::pmask points at; otherwise the n pixels (i, j) listed
 // (rt_debug_primary_mask)

@@ -43,6 +43,7 @@ struct HostFlat {             // canonical f64 flattening
     bool bvh_tame = true;          // all BVH boxes finite, |.| < 1e300 (1e30 matters for the f32 variant: checked there too), min <= max
     std::vector<DOnbEntry> onb;    // per-face ONB memo, one entry per rect (rt_flatten.cpp build_onb_table); onb_any: some entry is valid
     bool onb_any = false;
+    bool onb_all = false;          // ... and every rect's is, in a scene with a rect: the lean f64 kernel's compact first-hit ring (rt_launch.h)
 };
 
 template <typename T> struct DeviceScene {   // device copies of HostFlat for one arithmetic type
@@ -76,6 +77,7 @@ struct Scene {
     // FEATS template argument of the instantiation, [2] how the shape was chosen (0 the scene leaves no choice, 1 size rule, 2 calibration,
     // 3 the caller's RT_PERSISTENT_BVH / RT_LOCKSTEP_BVH flag, 4 rt_scene_set_loop_shape), [3] precision (0 f64, 1 f32)
     int last_loop[4] = {0, 0, 0, 0};
+    uint32_t last_ring[3] = {0, 0, 0};                 // rt_last_ring_info: the lean f64 kernels' first-hit ring of that launch
     // Worlds that are ONE bare BVH: the view whose estimated pass rates the filter tree's contraction was last tuned for (0: the area
     // rule's tree as flattened) — rt_flatten.cpp tune_filter_tree, rt_host.cpp tune_for_view; any tree gives the same samples
     unsigned long long filter_key = 0;

@@ -93,6 +93,28 @@ def debug_onb_table(b: SceneBuilder):
     return mag[:n], slots[:n], int(n_valid.value)
 
 
+def debug_ring_form(b: SceneBuilder, flags: int = 0) -> dict:
+    """rt_debug_ring_form (host only): the first-hit ring this scene's frames get from the lean f64 kernels — compact (98 entries of 80 B)
+    where every rect has a valid ONB-table entry, wide (76 of 104 B) otherwise; entries 0 where those kernels do not serve the scene."""
+    n, nb = C.c_uint32(0), C.c_uint32(0)
+    rc = _rt().rt_debug_ring_form(b.h, flags, C.byref(n), C.byref(nb))
+    if rc < 0:
+        raise RenderError(_err())
+    return {"compact": rc == 1, "entries": int(n.value), "entry_bytes": int(nb.value)}
+
+
+def debug_ring_normal(b: SceneBuilder, rays: np.ndarray, t_min: np.ndarray):
+    """rt_debug_ring_normal (needs a GPU): for n rays (n, 6) the closest hit's normal as finalize_hit gives it and as the compact first-hit
+    record carries it (three sign bits, rebuilt from the ONB table): (hit (n,) bool, rect (n,) int, normal (n, 3), rebuilt (n, 3))."""
+    r = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    t = np.ascontiguousarray(t_min, np.float64).reshape(-1)
+    if len(r) != len(t):
+        raise ValueError("rays and t_min differ in length")
+    out = np.zeros((len(r), 8), np.float64)
+    _check(_rt().rt_debug_ring_normal(b.h, len(r), r.ctypes.data, t.ctypes.data, out.ctypes.data))
+    return out[:, 0] != 0.0, out[:, 1].astype(np.int64), out[:, 2:5].copy(), out[:, 5:8].copy()
+
+
 def debug_onb(b: SceneBuilder, rects: np.ndarray, normals: np.ndarray):
     """rt_debug_onb (needs a GPU): the memo as the kernel's Lambertian arm reads it, for n pairs of (rect index, normal):
     (hit (n,) bool, v (n, 3), u (n, 3)); v and u are zero on a miss."""
@@ -323,9 +345,20 @@ def last_loop_info(b: SceneBuilder) -> dict:
     out = (C.c_int32 * 4)(); ms = (C.c_float * 2)()
     _check(_rt().rt_last_loop_info(b.h, out, ms))
     t = "float" if out[3] else "double"
+    # (`kernel` is the symbol that ran, but for a list scene the lean f64 kernel serves with its WIDE first-hit ring: last_ring_info)
     return {"shape": LOOP_SHAPES[out[0]], "feats": int(out[1]), "kernel": f"rt::pathtrace_kernel<{t}, {int(out[1])}u>",
             "chosen_by": LOOP_CHOSEN_BY[out[2]],
             "calibration_ms": {"lock-step": float(ms[0]), "persistent": float(ms[1])} if ms[0] > 0 or ms[1] > 0 else None}
+
+
+def last_ring_info(b: SceneBuilder) -> dict:
+    """rt_last_ring_info: the first-hit ring of the most recent launch — entries per wave, bytes per entry, `form` "compact", "wide" or None
+    (not one of the lean f64 kernels) — and `symbol`, the kernel that ran as a rocprofv3 trace names it: last_loop_info's `kernel`, but for
+    the lean f64 kernel with the wide ring, which is a kernel of its own."""
+    ring = (C.c_uint32 * 3)()
+    _check(_rt().rt_last_ring_info(b.h, ring))
+    return {"entries": int(ring[0]), "entry_bytes": int(ring[1]), "form": ("wide" if ring[2] else "compact") if ring[0] else None,
+            "symbol": "rt::pathtrace_wide_ring_kernel<double>" if ring[2] else last_loop_info(b)["kernel"]}
 
 
 def render(b: SceneBuilder, cam: CameraParams, background, W: int, H: int, spp: int, max_depth: int,

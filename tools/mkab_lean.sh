@@ -2,7 +2,8 @@
 # Like tools/mkab.sh for a variant of the LEAN translation unit only (the list-scene kernels: C2 / C5): compiles that unit from `src` with
 # extra flags and links it with the product build's other objects -> csrc/abx/<name>.so.  ~40 s instead of ~3 min.
 # usage: tools/mkab_lean.sh <name> "<extra flags>" [kernel source (default rt_kernel.hip)]
-# (the lean unit defines lean_f64_queue: a variant with -DRT_HIT_RING_QN=n brings its ring size to the product build's host code)
+# (the lean unit defines lean_f64_queue: a variant with -DRT_HIT_RING_QN=n or -DRT_HIT_RING_QN_COMPACT=n brings its ring sizes to the product
+# build's host code; -DRT_HIT_RING_ANY_SIZE lifts the header's bound on a workgroup's LDS for builds that are run for their counters)
 set -e
 cd "$(dirname "$0")/../raytracinginrust_amd/csrc"
 name=$1; f1=$2; src=${3:-rt_kernel.hip}

@@ -1,5 +1,8 @@
-"""The lean f64 kernel's first-hit ring (csrc/rt_launch.h HIT_RING_QN, HIT_RING_FILL_AT) swept over builds of the lean unit
-(tools/mkab_lean.sh qnQ_fF "-DRT_HIT_RING_QN=Q -DRT_HIT_RING_FILL_AT=F"): one 800 x 800 x spp frame of C2's scene and view per library,
+"""The lean f64 kernels' first-hit ring (csrc/rt_launch.h HIT_RING_QN, HIT_RING_FILL_AT and their _COMPACT twins) swept over builds of the
+lean unit (tools/mkab_lean.sh qnQ_fF "-DRT_HIT_RING_QN=Q -DRT_HIT_RING_FILL_AT=F" for the wide form, cqQ_fF "-DRT_HIT_RING_QN_COMPACT=Q
+-DRT_HIT_RING_FILL_AT_COMPACT=F" for the compact one, which is what the Cornell box runs; add -DRT_HIT_RING_ANY_SIZE for a size that gives
+up the fifth workgroup per CU — its counters still count; --wide: RT_NO_ONB_TABLE for the whole run, so that the Cornell box runs the
+wide form): one 800 x 800 x spp frame of C2's scene and view per library,
 and per library the loop counters, which depend on the per-wave logic only (not on occupancy or clocks): wave iterations per 64 samples
 and lanes live at a search; beside them the LDS of a workgroup and what the runtime answers for resident workgroups per CU.
 usage: python tools/ring_sweep.py [--spp 128] name=lib.so ..."""
@@ -9,7 +12,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.ins
 import torch  # noqa: F401  (one HIP runtime in the process)
 from raytracinginrust_amd import _lib, scenes
 ap = argparse.ArgumentParser(); ap.add_argument('--spp', type=int, default=128); ap.add_argument('--size', type=int, default=800); ap.add_argument('libs', nargs='+')
+ap.add_argument('--wide', action='store_true')
 a = ap.parse_args()
+if a.wide: os.environ['RT_NO_ONB_TABLE'] = '1'      # (read when a scene is flattened: no valid entry, the wide ring)
 W = H = a.size
 ref = None
 print(f'# Cornell box {W} x {H} x {a.spp}, max_depth 50, f64')
