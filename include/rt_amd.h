@@ -804,6 +804,16 @@ int rt_debug_ring_form(rt_scene*, uint32_t flags, uint32_t* entries_out, uint32_
  * from the ONB table.  rays: n x (origin[3], direction[3]); t_min: n; out: n x 8 = hit (0 / 1), rect index (-1 on a miss), the hit record's
  * normal[3], the rebuilt normal[3] (zeros on a miss).  Only for scenes whose ring is compact (rt_debug_ring_form).  Host pointers. */
 int rt_debug_ring_normal(rt_scene*, uint32_t n, const double* rays, const double* t_min, double* out);
+/* Test aid (host only, no GPU): the ONB table's companion records, one per rect record: wmag_out[3 i ..] = the bit patterns of
+ * |w.x|, |w.y|, |w.z| of w = normalized(n) (onb.rs:10) for the hit normal n the rect's owner produces — the normalisation sees no sign, so
+ * these are constants of the rect as rt_debug_onb_table's mag are; all ones exactly where that entry is invalid.  wmag_out may be NULL.
+ * Returns the number of rect records; -1 on error. */
+int rt_debug_onb_table_w(rt_scene*, uint64_t* wmag_out, uint32_t max_rects);
+/* Known-answer access to w as the compact lean f64 kernel's material section takes it from those records (rt_kernel.hip ring_w): world.hit
+ * and the hit record for n given rays, then normalized(the record's normal) by the kernel's own normalisation, and the table's magnitudes
+ * with the normal's sign bits.  rays, t_min as rt_debug_ring_normal; out: n x 8 = hit (0 / 1), rect index (-1 on a miss),
+ * normalized(normal)[3], the table's w[3] (zeros on a miss).  Only for scenes whose ring is compact.  Host pointers. */
+int rt_debug_ring_w(rt_scene*, uint32_t n, const double* rays, const double* t_min, double* out);
 /* The pixel classifier of the lean f64 list-scene kernel's primary pass (csrc/rt_primary.h): the kernel runs the first level of the camera
  * paths of a refill together and does not search top-level objects that every ray it can generate for their pixel provably misses.  For
  * n pixels (pixels: n x (i, j), j counted from the bottom row) out_masks[p] has bit k set when object k of the flattened top-level list may

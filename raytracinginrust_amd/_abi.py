@@ -219,6 +219,8 @@ SIGNATURES = {
     "debug_onb_table": (_int, [_ptr, _ptr, _ptr, _u32, c_u32_p]),
     "debug_ring_form": (_int, [_ptr, _u32, c_u32_p, c_u32_p]),
     "debug_ring_normal": (_int, [_ptr, _u32, _ptr, _ptr, _ptr]),
+    "debug_onb_table_w": (_int, [_ptr, _ptr, _u32]),
+    "debug_ring_w": (_int, [_ptr, _u32, _ptr, _ptr, _ptr]),
     "debug_short_forms": (_int, [_u32, _u32, _ptr, _ptr, _ptr]),
     "debug_math": (_int, [_u32, _u32, _ptr, _ptr, _ptr]),
     "debug_brdf": (_int, [_ptr, _u32, _int, _ptr, _ptr, _ptr, _ptr, _ptr, _u32]),

@@ -737,8 +737,11 @@ void make_filter_nodes(HostFlat& f, const std::vector<unsigned char>* take_out =
 // those very bits: which entries are valid decides how often the memo hits, never what a sample is.  This translation unit is compiled
 // with -ffp-contract=off (Makefile) and IEEE divide / sqrt round correctly on host and device: the same facts the per-sample parity
 // with the CPU oracle rests on.  RT_NO_ONB_TABLE (A/B runs, tests): every entry invalid.
+// The entry's companion (rt_ir.h DOnbW) holds |w| of w = normalized(n), from the one normalisation every slot starts with (onb_norm), run
+// once on |n|: no operation of it sees a sign (rt_kernel.hip: Lemma W; tests/test_table_w_host.py runs all eight sign patterns).
+void onb_norm(const double a[3], double o[3]) { const double l = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); for (int k = 0; k < 3; k++) o[k] = a[k] / l; }
 void onb_slot(const double w0[3], double vu[6]) {
-    auto norm = [](const double a[3], double o[3]) { const double l = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); for (int k = 0; k < 3; k++) o[k] = a[k] / l; };
+    auto norm = onb_norm;
     auto cross = [](const double a[3], const double b[3], double o[3]) { o[0] = a[1] * b[2] - a[2] * b[1]; o[1] = a[2] * b[0] - a[0] * b[2]; o[2] = a[0] * b[1] - a[1] * b[0]; };
     double w[3], c[3];
     norm(w0, w);                                                            // onb.rs:10
@@ -751,6 +754,9 @@ void build_onb_table(HostFlat& f) {
     DOnbEntry none; std::memset((void*)&none, 0, sizeof(none));
     for (int k = 0; k < 3; k++) none.mag[k] = ONB_MAG_INVALID;
     f.onb.assign(f.rects.size(), none);
+    DOnbW none_w; for (int k = 0; k < 3; k++) none_w.wmag[k] = ONB_MAG_INVALID;
+    none_w.pad = 0ull;
+    f.onb_w.assign(f.rects.size(), none_w);
     f.onb_any = false; f.onb_all = false;
     if (f.feats != 0u || std::getenv("RT_NO_ONB_TABLE")) return;
     // per rect: the chain it is reached through — 0 none yet, 1 no rotation (bare / FlipNormals only), 2 + first_op the fused idiom,
@@ -786,6 +792,10 @@ void build_onb_table(HostFlat& f) {
             for (int k = 0; k < 3; k++) w[k] = std::copysign(std::fabs(n[k]), ((s >> k) & 1) ? -1.0 : 1.0);
             onb_slot(w, e.slot[s]);
         }
+        double am[3], aw[3];
+        for (int k = 0; k < 3; k++) am[k] = std::fabs(n[k]);
+        onb_norm(am, aw);
+        std::memcpy(f.onb_w[i].wmag, aw, 24);
         f.onb_any = true;
     }
     // every rect an object owns has its entry, and there is one: a hit's normal is then the entry's magnitudes and three sign bits,

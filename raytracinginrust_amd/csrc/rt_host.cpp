@@ -477,6 +477,17 @@ int rt_debug_onb_table(rt_scene* sc, uint64_t* mag_out, double* slots_out, uint3
     return (int)f.onb.size();
 }
 
+// Test aid (host only): the table's companion records (rt_ir.h DOnbW), one per rect record: wmag_out[3*i ..] = the bit patterns of
+// |normalized(n)| (all ones: invalid, exactly where rt_debug_onb_table's entry is).  Returns the number of rects; -1 on error.
+int rt_debug_onb_table_w(rt_scene* sc, uint64_t* wmag_out, uint32_t max_rects) {
+    if (!sc) return set_err("null argument");
+    if (!flatten_for_render(sc->s)) return -1;
+    const HostFlat& f = sc->s.flat;
+    for (size_t i = 0; i < f.onb_w.size() && i < max_rects && wmag_out; i++)
+        for (int k = 0; k < 3; k++) wmag_out[3 * i + k] = f.onb_w[i].wmag[k];
+    return (int)f.onb_w.size();
+}
+
 uint32_t rt_local_tiles(uint32_t W, uint32_t H, uint32_t tile_px, uint32_t rank, uint32_t world) {
     (void)rank;
     if (tile_px == 0 || world == 0) return 0;
@@ -548,7 +559,16 @@ template <typename T> int ensure_uploaded(Scene& s, DeviceScene<T>& d) {
     if (upload_vec<DPbr<T>>(s.pbr, d.pbr)) return -1;
     if (upload_raw(s.image_bytes, d.image)) return -1;
     d.onb = nullptr;                       // the ONB memo: f64 tables only, and only when some entry is valid (the kernel tests the pointer)
-    if (sizeof(T) == 8u && f.onb_any) { std::vector<DOnbEntry> ot(f.onb); ot.push_back(DOnbEntry{}); if (upload_raw(ot, d.onb)) return -1; }
+    // One buffer, laid out as rt_ir.h says beside DOnbW: the DOnbW records in front (onb_w_prefix_bytes, onb_w_index), then the table and
+    // one padding record.  d.onb is the allocation (what is freed); bind_tables hands the kernels the table's address inside it.
+    if (sizeof(T) == 8u && f.onb_any) {
+        const size_t n = f.onb.size();
+        std::vector<unsigned char> ot(onb_w_prefix_bytes(n) + (n + 1u) * sizeof(DOnbEntry), (unsigned char)0);
+        unsigned char* const table = ot.data() + onb_w_prefix_bytes(n);
+        for (size_t i = 0; i < n; i++) std::memcpy((DOnbW*)table + onb_w_index(i), &f.onb_w[i], sizeof(DOnbW));
+        std::memcpy(table, f.onb.data(), n * sizeof(DOnbEntry));
+        if (upload_raw(ot, d.onb)) return -1;
+    }
     d.valid = true;
     return 0;
 }
@@ -695,7 +715,8 @@ template <typename T> void bind_tables(KParams<T>& P, const DeviceScene<T>& d, c
     P.ops = (const DOp<T>*)d.ops; P.rects = (const DRect<T>*)d.rects; P.spheres = (const DSphere<T>*)d.spheres;
     P.mspheres = (const DMSphere<T>*)d.mspheres; P.tris = (const DTri<T>*)d.tris; P.bvh = (const DBvhNode<T>*)d.bvh;
     P.n_bvh = (uint32_t)f.bvh.size();
-    P.bvh_f = (const DFNode*)d.bvh_f; P.filter_m = f.filter_m; P.rect_m = f.rect_m; P.onb = (const DOnbEntry*)d.onb;
+    P.bvh_f = (const DFNode*)d.bvh_f; P.filter_m = f.filter_m; P.rect_m = f.rect_m;
+    P.onb = d.onb ? (const DOnbEntry*)((const unsigned char*)d.onb + onb_w_prefix_bytes(f.onb.size())) : nullptr;  // (the table, behind the DOnbW records: rt_ir.h, ensure_uploaded)
     P.materials = (const DMaterial<T>*)d.materials; P.textures = (const DTexture<T>*)d.textures; P.media = (const DMedium<T>*)d.media;
     P.lights = (const DLight*)d.lights; P.n_lights = f.n_lights;
     P.perlins = (const DPerlin<T>*)d.perlins; P.pbr = (const DPbr<T>*)d.pbr; P.image_bytes = (const uint8_t*)d.image;
@@ -1264,6 +1285,18 @@ int rt_debug_ring_normal(rt_scene* sc, uint32_t n, const double* rays, const dou
     if (!flatten_for_render(s)) return -1;
     if (s.flat.feats != 0u || !s.flat.onb_all) return set_err("rt_debug_ring_normal serves scenes with the compact first-hit ring only (a list scene in which every rect has a valid ONB-table entry)");
     return run_kat(s, launch_ring_normal_kat, n, rays, 48u, t_min, 8u, out, 64u);
+}
+// Known-answer access to Lemma W (rt_kernel.hip ring_w, the function the compact lean f64 kernel's material section calls): world.hit and
+// the hit record for n given rays, then normalized(the record's normal) by the kernel's own normalisation and w as the table gives it for
+// the record's rect word.  out: n x 8 = hit (0 / 1), rect index (-1 on a miss), normalized(normal)[3], the table's w[3] (zeros on a
+// miss).  Serves the scenes that get the compact ring only.  Host pointers.
+int rt_debug_ring_w(rt_scene* sc, uint32_t n, const double* rays, const double* t_min, double* out) {
+    if (!sc || !rays || !t_min || !out) return set_err("null argument");
+    if (n == 0) return 0;
+    Scene& s = sc->s;
+    if (!flatten_for_render(s)) return -1;
+    if (s.flat.feats != 0u || !s.flat.onb_all) return set_err("rt_debug_ring_w serves scenes with the compact first-hit ring only (a list scene in which every rect has a valid ONB-table entry)");
+    return run_kat(s, launch_ring_w_kat, n, rays, 48u, t_min, 8u, out, 64u);
 }
 // Known-answer access to the shading side's arithmetic (csrc/rt_kat.hip): one device function per lane on caller operands, under either
 // code shape.  No scene.  Records per op: rt_kat.h KAT_RECORDS.  Host pointers.

@@ -20,6 +20,7 @@
 // loads); BVH nodes and leaf primitives with per-lane indices (vector gathers, node = one 64-byte line
 // in f64).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace rt {
@@ -99,6 +100,18 @@ struct DLight { uint32_t kind, index; };
 // bits s = sx | sy << 1 | sz << 2.  416 B, 16-byte aligned pieces.
 struct alignas(16) DOnbEntry { uint64_t mag[3]; uint64_t pad; double slot[8][6]; };
 static const uint64_t ONB_MAG_INVALID = ~0ull;
+// ... and the magnitudes of w = normalized(n) (onb.rs:10) beside it: the squares, the sum and the root of a normalisation do not see
+// signs and IEEE division is sign-symmetric, so |w| is a constant of the rect as |n| is and w's sign bits are n's (rt_kernel.hip: Lemma
+// W).  All ones: no valid entry.  On the device the records stand IN FRONT of the table, rect i's at ((const DOnbW*)onb)[-1 - i]: DOnbEntry,
+// its stride and the kernel arguments stay what every other kernel was compiled for.  Read by the compact lean f64 kernel only.
+struct alignas(16) DOnbW { uint64_t wmag[3]; uint64_t pad; };
+// The layout of that buffer, in one place for whoever uploads it, binds it or reads it (rt_host.cpp ensure_uploaded, bind_tables;
+// rt_kernel.hip ring_w): [DOnbW of rect n-1 .. DOnbW of rect 0][DOnbEntry of rect 0 .. n-1][one padding DOnbEntry].  The allocation starts
+// onb_w_prefix_bytes(n) BEFORE the pointer the kernels receive (KParams::onb), and rect i's DOnbW is ((const DOnbW*)onb)[onb_w_index(i)]
+// (ring_w writes that index out as `- 1 - i`, two steps: the form its machine code was measured in).
+static_assert(sizeof(DOnbW) == 32 && alignof(DOnbW) == 16 && sizeof(DOnbEntry) % 16 == 0, "the DOnbW prefix keeps the table's 16-byte alignment");
+constexpr size_t onb_w_prefix_bytes(size_t n_rects) { return n_rects * sizeof(DOnbW); }
+constexpr ptrdiff_t onb_w_index(size_t rect) { return -1 - (ptrdiff_t)rect; }
 template <typename T> struct DPerlin { T rd_vec[256 * 3]; uint8_t perm_x[256], perm_y[256], perm_z[256]; };   // src/perlin.rs:59-65
 template <typename T> struct DCamera {                                                        // src/camera.rs:6-16
     T origin[3], lower_left_corner[3], horizontal[3], vertical[3], cu[3], cv[3];

@@ -1100,6 +1100,24 @@ DEV void onb_memo_load(const double* slot, V3<double>& v, V3<double>& u) {
     const d2 a = *(const CAS d2*)slot, b = *(const CAS d2*)(slot + 2), c = *(const CAS d2*)(slot + 4);
     v = mk<double>(a.x, a.y, b.x); u = mk<double>(b.y, c.x, c.y);
 }
+// The COMPACT lean f64 kernel (trace_shade_fill; Lemma N there) knows a hit's normal as the rect's entry and three sign bits of the rect
+// word, and takes the whole ONB from the table the same way:
+// LEMMA W.  w = normalized(n) is n_k / sqrt(n.x n.x + n.y n.y + n.z n.z).  The squares, hence the sum and the root, do not see the signs of
+// n, and IEEE division gives |n_k| / l with the sign of n_k (a zero's included; l is positive or NaN).  So for a rect with a valid entry
+// the sign-masked words of w are constants of the rect — rt_flatten.cpp build_onb_table runs that one normalisation on |n| (rt_ir.h
+// DOnbW, in front of the table) — and its sign bits are n's.  v and u are the slot those three bits name: by Lemma N the probe's
+// comparison holds for every hit, so nothing is compared.  (On the device: tests/test_table_w_gpu.py, rt_debug_ring_w.)
+DEV V3<double> ring_w(const DOnbEntry* tab, uint32_t rect_signs) {
+    const DOnbW* e = (const DOnbW*)tab - 1 - (ptrdiff_t)(rect_signs & HIT_RING_RECT_MASK);
+    typedef unsigned long long ull2 __attribute__((ext_vector_type(2)));
+    const ull2 m01 = *(const CAS ull2*)&e->wmag[0];
+    const unsigned long long m2 = cl((const unsigned long long*)&e->wmag[2]);
+    const unsigned long long s = rect_signs;
+    return mk<double>(__longlong_as_double((long long)(m01.x | ((s >> HIT_RING_SIGN_SHIFT) & 1ull) << 63)),
+                      __longlong_as_double((long long)(m01.y | ((s >> (HIT_RING_SIGN_SHIFT + 1u)) & 1ull) << 63)),
+                      __longlong_as_double((long long)(m2 | ((s >> (HIT_RING_SIGN_SHIFT + 2u)) & 1ull) << 63)));
+}
+DEV const double* ring_slot(const DOnbEntry* tab, uint32_t rect_signs) { return tab[rect_signs & HIT_RING_RECT_MASK].slot[(rect_signs >> HIT_RING_SIGN_SHIFT) & 7u]; }
 
 // Rebuild the full HitRecord of the winning (object, primitive, t): the same arithmetic the reference runs
 // eagerly inside every `hit`, run once.  Per-lane gathers: lanes may hold different objects.
@@ -1897,11 +1915,91 @@ DEV bool div_pi_pair(double cosine, double m, double& pdf, double& sc) {
     sc = m / SF_PI;
     return false;
 }
+// shade_hit's merged Lambertian / Metal arm as the COMPACT lean f64 kernel runs it (shade_hit<double, 0u, true>; rect_signs: the rect word
+// with the normal's sign bits, ring_pack_signs).  The ONB comes from the table whole (Lemma W above ring_w): no first normalisation on
+// Lambertian lanes, no probe, no fallback arithmetic.  That leaves each lane ONE normalisation — Lambertian normalized(dir), Metal
+// normalized(reflect(..)) —, and both are one instruction run: it stands after the Lambertian sampling arms have produced dir, Metal
+// forms its reflection just before it and draws the third component of its fuzz vector after it.  Per lane the draws are the merged
+// arm's in the merged arm's order and every f64 operation has the same operands: the same samples bit for bit.  The operand of the
+// run is written by each side in its own branch — no select between two computed vectors —, and every value is defined on every lane.
+DEV void merged_arms_table_w(const KParams<double>& P, const DMaterial<double>& mt, bool lam, const Rec<double>& rec, RayT<double>& ray, V3<double>& beta,
+                             Rng& rng, bool& done, uint32_t rect_signs) {
+    typedef double T;
+    bool to_light = false;
+    DLight L; L.kind = 0xFFFFFFFFu; L.index = 0u;
+    // ray.d is the operand of the normalisation — Lambertian: dir, Metal: the reflection — and the old direction is dead from here on
+    if (!lam) ray.d = ray.d + ((-dot(ray.d, rec.n)) * T(2.0) * rec.n);      // reflect, vec.rs:112-114
+    if (lam) {                                                              // mat.rs:225-249, main.rs:92-98
+        if (P.n_lights != 0u && rng_bool(rng)) {                            // pdf.rs:167-173 (no lights: deviation D2, cosine only)
+            to_light = true;
+            L = ld_light(P.lights + rng_index(rng, P.n_lights));            // hit.rs:94-96
+        }
+    }
+    const bool two = !to_light || L.kind == L_RECT;
+    uint64_t b1 = 0, b2 = 0;
+    if (two) { b1 = rng_u64(rng); b2 = rng_u64(rng); }
+    if (lam) {
+        if (!to_light) {                                                    // random_cosine_direction, pdf.rs:8-18
+            T r1 = rng_u01_of(b1, T(0)), r2 = rng_u01_of(b2, T(0));
+            T z = rsqrt_(T(1.0) - r2);
+            T phi = T(2.0) * PI_T * r1;
+            T sn, cs; sincos_0_2pi(phi, sn, cs);
+            Onb<T> uvw;                                                     // onb.rs:8-20, whole from the table, where it is used
+            uvw.w = ring_w(P.onb, rect_signs);
+            onb_memo_load(ring_slot(P.onb, rect_signs), uvw.v, uvw.u);
+            ray.d = onb_local(uvw, mk<T>(cs * rsqrt_(r2), sn * rsqrt_(r2), z));
+        } else if (L.kind == L_RECT) {                                      // rect.rs:103-111
+            const DRect<T> rc = ld_rect(P.rects + L.index);
+            uint32_t ki, ai, bi; plane_axes(rc.plane, ki, ai, bi);
+            T ra = rng_range_of(b1, rc.a0, rc.a1);
+            T rb = rng_range_of(b2, rc.b0, rc.b1);
+            V3<T> pt;
+            pt.x = ki == 0u ? rc.k : (ai == 0u ? ra : rb);
+            pt.y = ki == 1u ? rc.k : (ai == 1u ? ra : rb);
+            pt.z = ki == 2u ? rc.k : rb;
+            ray.d = pt - rec.p;
+        } else {
+            ray.d = light_random<T, 0u>(P, L, rec.p, rng);
+        }
+    }
+    const V3<T> xn = normalized(ray.d);                                        // pdf.rs:131 and mat.rs:247 / mat.rs:285
+    if (lam) {
+        // w is loaded again here, not kept through the arms and the normalisation (six VGPRs; a load is no VALU slot)
+        T cosine = dot(xn, ring_w(P.onb, rect_signs));                      // pdf.rs:131-139
+        T pdf_value, sc;
+        if constexpr (SHORT_DIV) div_pi_pair(cosine, m_max(dot(rec.n, xn), T(0)), pdf_value, sc);   // both divisions by pi, here
+        else pdf_value = (cosine > T(0)) ? cosine / PI_T : T(0);
+        if (P.n_lights != 0u) {
+            T lsum = T(0);                                                  // hit.rs:90-92
+            for (uint32_t li = 0; li < P.n_lights; li++) lsum += light_pdf_value<T, 0u>(P, ld_light(P.lights + li), rec.p, ray.d);
+            T lpdf = lsum;                                                  // x / 1.0 is x
+            if (P.n_lights != 1u) {
+                // the divisor is converted here: converted in front of the bounce loop (*seen*) it is spilled there and reloaded here
+                uint32_t nl = P.n_lights;
+                asm volatile("" : "+s"(nl));
+                lpdf = lsum / T(nl);
+            }
+            pdf_value = T(0.5) * lpdf + T(0.5) * pdf_value;                 // pdf.rs:143-145
+        }
+        if constexpr (!SHORT_DIV) sc = m_max(dot(rec.n, xn), T(0)) / PI_T;  // scattering_pdf, mat.rs:246-249
+        beta = (beta * (ld3(mt.albedo) * sc)) / pdf_value;                  // main.rs:97 (emitted is the literal zero here)
+        ray.o = rec.p;                                                      // (ray.d is dir already; time unchanged)
+    } else {                                                                // mat.rs:280-293
+        V3<T> fz;                                                           // random_in_unit_sphere, vec.rs:78-85: the first try's a and b are drawn above
+        fz.x = rng_range_of(b1, T(-1.0), T(1.0)); fz.y = rng_range_of(b2, T(-1.0), T(1.0)); fz.z = rng_range(rng, T(-1.0), T(1.0));
+        while (!(dot(fz, fz) < T(1.0))) { T a = rng_range(rng, T(-1.0), T(1.0)), b = rng_range(rng, T(-1.0), T(1.0)), c = rng_range(rng, T(-1.0), T(1.0)); fz = mk<T>(a, b, c); }
+        ray.o = rec.p; ray.d = xn + mt.param * fz;                          // (also where the path ends: a finished lane's ray is not read again)
+        if (dot(ray.d, rec.n) > T(0)) beta = ld3(mt.albedo) * beta;         // main.rs:89-91
+        else done = true;                                                   // None -> emitted = 0, main.rs:108-110
+    }
+}
 // ------------------------------------------------------------------ one level of ray_color after the hit: main.rs:50-116
 // In: the hit record.  In/out: ray (becomes the scattered ray), beta, rng, depth_left.  Out: done (the path ends here) and
 // e, the terminal radiance to be multiplied by beta.  rect: the rect record the hit came from — read by the lean f64 kernel only (every hit
 // of a list scene is a rect's), where it names the hit's entry in the ONB memo; the other callers leave it out.
-template <typename T, uint32_t FEATS>
+// TABLE_W (the compact lean f64 kernel only): the merged arm takes the whole ONB from the table (merged_arms_table_w above), and rect is the
+// rect word with the normal's sign bits.
+template <typename T, uint32_t FEATS, bool TABLE_W = false>
 DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& beta, Rng& rng, uint32_t& depth_left, bool& done, V3<T>& e, uint32_t rect = 0u) {
     const DMaterial<T> mt = ld_mat(P.materials + rec.mat);
     // Lambertian (its two sampling arms) and Metal in one instruction stream where they run the same instructions on their own
@@ -1911,6 +2009,7 @@ DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& 
     constexpr bool MERGE = MERGE_ARMS && sizeof(T) == 8u;               // (the f32 kernels draw one u32 per value)
     const bool lam = mt.kind == M_LAMBERTIAN, met = mt.kind == M_METAL;
     if (MERGE && (lam || met)) { if constexpr (MERGE) {
+        if constexpr (TABLE_W) merged_arms_table_w(P, mt, lam, rec, ray, beta, rng, done, rect); else {
         V3<T> unit0 = rec.n;
         if (met) unit0 = ray.d + ((-dot(ray.d, rec.n)) * T(2.0) * rec.n);  // reflect, vec.rs:112-114
         unit0 = normalized(unit0);
@@ -1985,6 +2084,7 @@ DEV void shade_hit(const KParams<T>& P, const Rec<T>& rec, RayT<T>& ray, V3<T>& 
             V3<T> sd = unit0 + mt.param * fz;
             if (dot(sd, rec.n) > T(0)) { beta = ld3(mt.albedo) * beta; ray.o = rec.p; ray.d = sd; }   // main.rs:89-91
             else done = true;                                               // None -> emitted = 0, main.rs:108-110
+        }
         }
     } } else if (lam) {                                                     // mat.rs:225-249, main.rs:92-98
         V3<T> attenuation = tex_eval<T, FEATS>(P, mt.tex, rec.u, rec.v, rec.p);
@@ -2249,7 +2349,8 @@ DEV void trace_lockstep(const KParams<T>& P, uint32_t lane, T* q_real, uint32_t*
 // rt_flatten.cpp build_onb_table fills mag by these very operations.  (On the device: tests/test_compact_ring_gpu.py, rt_debug_ring_normal.)
 // So the normal is its three sign bits — bits 28..30 of the rect word, which a 28-bit primitive index leaves clear — and the entry the
 // merged Lambertian arm's probe loads anyway.  The compact kernel carries every lane's normal that way, popped or not: it is rebuilt at
-// the top of the material section and is not a loop-carried value at all.
+// the top of the material section and is not a loop-carried value at all.  Its material section takes the ONB of a Lambertian hit from
+// the table whole, by the same three bits (Lemma W above ring_w, merged_arms_table_w): one normalisation per lane and bounce, not two.
 DEV uint32_t ring_pack_signs(uint32_t rect_front, V3<double> n) {
     const uint32_t sx = (uint32_t)((unsigned long long)__double_as_longlong(n.x) >> 63), sy = (uint32_t)((unsigned long long)__double_as_longlong(n.y) >> 63),
                    sz = (uint32_t)((unsigned long long)__double_as_longlong(n.z) >> 63);
@@ -2335,7 +2436,7 @@ DEV void trace_shade_fill(const KParams<T>& P, uint32_t lane, T* q_real) {
             V3<T> e = mk<T>(T(0), T(0), T(0));
             rec.p = ray.o; rec.front = (rect_front >> 31) != 0u;
             if constexpr (COMPACT) rec.n = ring_normal(P.onb, rect_front);      // Lemma N: every lane's normal, popped or not
-            shade_hit<T, FEATS>(P, rec, ray, beta, rng, depth_left, done, e, rect_front & (COMPACT ? HIT_RING_RECT_MASK : 0x7FFFFFFFu));
+            shade_hit<T, FEATS, COMPACT>(P, rec, ray, beta, rng, depth_left, done, e, COMPACT ? rect_front : rect_front & 0x7FFFFFFFu);      // (compact: the ONB from the table, Lemma W)
             if (done) {
                 if (path_px == acc_px) add_radiance(P, beta * e, acc, n_nonfinite, path_px, path_s);
                 else {                                  // popped into another pixel and ended at once: its own three atomics
@@ -2896,6 +2997,32 @@ __global__ void ring_normal_kat_kernel(const KParams<double> P, uint32_t n, cons
 }
 hipError_t launch_ring_normal_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream) {
     hipLaunchKernelGGL(ring_normal_kat_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_rays, d_tlim, d_out);
+    return hipGetLastError();
+}
+// Known-answer access to Lemma W (rt_debug_ring_w; above ring_w): the hit record as in ring_normal_kat_kernel, then normalized(its normal)
+// by the kernels' own normalisation and w as the compact kernel's material section takes it from the table for the packed rect word.
+// out[8 i ..] = hit (0 / 1), the rect index, normalized(normal)[3], the table's w[3].  P.onb is not null (HostFlat::onb_all only).
+__global__ void ring_w_kat_kernel(const KParams<double> P, uint32_t n, const double* rays, const double* tlim, double* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t j = i < n ? i : n - 1u;                           // (a partial last wave repeats the last ray: every lane takes part in the votes)
+    RayT<double> ray; ray.o = mk<double>(rays[j * 6], rays[j * 6 + 1], rays[j * 6 + 2]); ray.d = mk<double>(rays[j * 6 + 3], rays[j * 6 + 4], rays[j * 6 + 5]); ray.tm = 0.0;
+    Rng rng = rng_for_path(0ull, 0u, 0u);
+    double t_hit; HitId id; id.obj = 0u; id.prim = 0u;
+    const bool any = world_hit_list<double>(P, ray, tlim[j], rng, t_hit, id);
+    Rec<double> rec; rec.p = mk<double>(0.0, 0.0, 0.0); rec.n = rec.p; rec.t = 0.0; rec.u = rec.v = 0.0; rec.front = false; rec.mat = 0u;
+    V3<double> wn = rec.p, wt = rec.p;
+    if (any) {
+        finalize_hit<double, 0u>(P, ray, t_hit, id, true, rec);
+        wn = normalized(rec.n);
+        wt = ring_w(P.onb, ring_pack_signs((id.prim & 0x0FFFFFFFu) | (rec.front ? 0x80000000u : 0u), rec.n));
+    }
+    if (i < n) {
+        double* o = out + 8ull * i;
+        o[0] = any ? 1.0 : 0.0; o[1] = any ? (double)(id.prim & 0x0FFFFFFFu) : -1.0; o[2] = wn.x; o[3] = wn.y; o[4] = wn.z; o[5] = wt.x; o[6] = wt.y; o[7] = wt.z;
+    }
+}
+hipError_t launch_ring_w_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream) {
+    hipLaunchKernelGGL(ring_w_kat_kernel, dim3((n + 63u) / 64u), dim3(64), 0, stream, P, n, d_rays, d_tlim, d_out);
     return hipGetLastError();
 }
 hipError_t launch_onb_kat(const KParams<double>& P, uint32_t n, const double* d_rects, const double* d_normals, double* d_out, hipStream_t stream) {

@@ -90,6 +90,8 @@ hipError_t launch_list_hit_masked_kat(const KParams<double>& P, uint32_t n, cons
 hipError_t launch_onb_kat(const KParams<double>& P, uint32_t n, const double* d_rects, const double* d_normals, double* d_out, hipStream_t stream);
 // Known-answer access to the compact first-hit record's normal, packed and rebuilt as the lean f64 kernel does it (rt_debug_ring_normal; the lean translation unit)
 hipError_t launch_ring_normal_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream);
+// ... and to w = normalized(normal) as that kernel takes it from the table's DOnbW records (rt_debug_ring_w; the lean translation unit)
+hipError_t launch_ring_w_kat(const KParams<double>& P, uint32_t n, const double* d_rays, const double* d_tlim, double* d_out, hipStream_t stream);
 // The primary pass's object masks (csrc/rt_primary.h; the kernel lives in the lean translation unit): d_pixels == nullptr — one word per
 // local pixel of the launch P describes (camera, frame size, tiling), what KParams::pmask points at; otherwise the n pixels (i, j) listed
 // (rt_debug_primary_mask)

@@ -42,6 +42,7 @@ struct HostFlat {             // canonical f64 flattening
     uint32_t bvh_depth = 0;
     bool bvh_tame = true;          // all BVH boxes finite, |.| < 1e300 (1e30 matters for the f32 variant: checked there too), min <= max
     std::vector<DOnbEntry> onb;    // per-face ONB memo, one entry per rect (rt_flatten.cpp build_onb_table); onb_any: some entry is valid
+    std::vector<DOnbW> onb_w;      // ... and |normalized(n)| per rect (rt_ir.h DOnbW), same indices, valid where onb's entry is
     bool onb_any = false;
     bool onb_all = false;          // ... and every rect's is, in a scene with a rect: the lean f64 kernel's compact first-hit ring (rt_launch.h)
 };

@@ -115,6 +115,30 @@ def debug_ring_normal(b: SceneBuilder, rays: np.ndarray, t_min: np.ndarray):
     return out[:, 0] != 0.0, out[:, 1].astype(np.int64), out[:, 2:5].copy(), out[:, 5:8].copy()
 
 
+def debug_onb_table_w(b: SceneBuilder):
+    """rt_debug_onb_table_w (host only): the ONB table's companion records, (n, 3) uint64 — the bit patterns of |normalized(n)| per rect
+    record, ONB_MAG_INVALID in all three exactly where debug_onb_table's entry is invalid."""
+    n = _rt().rt_debug_onb_table_w(b.h, None, 0)
+    if n < 0:
+        raise RenderError(_err())
+    wmag = np.zeros((max(n, 1), 3), np.uint64)
+    if _rt().rt_debug_onb_table_w(b.h, wmag.ctypes.data, n) != n:
+        raise RenderError(_err())
+    return wmag[:n]
+
+
+def debug_ring_w(b: SceneBuilder, rays: np.ndarray, t_min: np.ndarray):
+    """rt_debug_ring_w (needs a GPU): for n rays (n, 6) the closest hit's normalized(normal) as the kernel's normalisation gives it and w as
+    the compact lean f64 kernel takes it from the table: (hit (n,) bool, rect (n,) int, normalized (n, 3), from_table (n, 3))."""
+    r = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    t = np.ascontiguousarray(t_min, np.float64).reshape(-1)
+    if len(r) != len(t):
+        raise ValueError("rays and t_min differ in length")
+    out = np.zeros((len(r), 8), np.float64)
+    _check(_rt().rt_debug_ring_w(b.h, len(r), r.ctypes.data, t.ctypes.data, out.ctypes.data))
+    return out[:, 0] != 0.0, out[:, 1].astype(np.int64), out[:, 2:5].copy(), out[:, 5:8].copy()
+
+
 def debug_onb(b: SceneBuilder, rects: np.ndarray, normals: np.ndarray):
     """rt_debug_onb (needs a GPU): the memo as the kernel's Lambertian arm reads it, for n pairs of (rect index, normal):
     (hit (n,) bool, v (n, 3), u (n, 3)); v and u are zero on a miss."""
