@@ -855,9 +855,17 @@ int rt_debug_brdf(rt_scene*, uint32_t n, int material, const double* r_in, const
  * Lambertian arm probes); rays: n x 7, the incoming rays; beta: the throughput every lane starts with; record k draws from
  * rt_rng_path(seed, k, 0); depth_left >= 1.  flags: RT_STOP_ON_ZERO, RT_ISOTROPIC_SCATTER; RT_KAT_REST_SHAPE — the all-features instantiation
  * under the other unit's code shape (with object leaves and nested light lists where the scene has them) instead of the lean one (list scenes
- * only); RT_KAT_NO_ONB_TABLE — the lean one without the ONB memo.  out: n x 19 = the ray afterwards (7), beta[3], e[3] (the terminal radiance
- * beta multiplies), done (0 / 1), depth_left, the stream's four state words afterwards.  Host pointers. */
+ * only); RT_KAT_NO_ONB_TABLE — the lean one without the ONB memo; RT_KAT_TABLE_W — the call as the COMPACT lean f64 kernel's material section
+ * makes it, the one the frames of every scene with the compact first-hit ring run: the rect word packed with `front_face` and the normal's
+ * three sign bits, the normal rebuilt from the ONB table, then the instantiation whose Lambertian / Metal arm takes w, v and u from the
+ * table (rt_kernel.hip ring_pack_signs, ring_normal, shade_hit<double, 0, true>).  It is refused, before any device call and with the
+ * record's number in the message, together with either of the other two RT_KAT_ flags, for a scene whose ring is not compact
+ * (rt_debug_ring_form), for a record whose material is neither Lambertian nor Metal (that kernel ends every other path before the call) and
+ * for a record whose sign-masked normal words are not its rect's magnitudes in the ONB table (the compact record carries the normal as three
+ * sign bits: rt_debug_onb_table).  out: n x 19 = the ray afterwards (7; the incoming ray where nothing scatters), beta[3], e[3] (the terminal
+ * radiance beta multiplies), done (0 / 1), depth_left, the stream's four state words afterwards.  Host pointers. */
 #define RT_KAT_NO_ONB_TABLE 0x200u
+#define RT_KAT_TABLE_W 0x400u
 int rt_debug_shade(rt_scene*, uint32_t n, const double* records, const double* rays, const double beta[3], uint64_t seed, uint32_t depth_left,
                    uint32_t flags, double* out);
 /* Debugging aid for parity work: the hits of ONE camera path, level by level.  rt_debug_trace_path chooses the path (local pixel index =

@@ -78,7 +78,10 @@ struct Rng {
         double v12;
         std::memcpy(&v12, &bits, 8);
         double res = (v12 - 1.0) * (b - a) + a;
-        if (!(res < b)) res = std::nextafter(b, a);
+        // the largest double below b, as the line above says and as the product's rng_range forms it.  (It was nextafter(b, a): the same
+        // value for a < b, but b itself for the EMPTY range a == b — a rect light of zero width, on which rand panics —, where the two
+        // restatements then sampled different points: tests/test_table_w_shade_host.py.)
+        if (!(res < b)) res = std::nextafter(b, -HUGE_VAL);
         return res;
     }
     inline bool boolean() { return (next_u32() >> 31) != 0; }

@@ -1350,8 +1350,11 @@ int rt_debug_brdf(rt_scene* sc, uint32_t n, int material, const double* r_in, co
 int rt_debug_shade(rt_scene* sc, uint32_t n, const double* records, const double* rays, const double beta[3], uint64_t seed, uint32_t depth_left,
                    uint32_t flags, double* out) {
     if (!sc || !records || !rays || !beta || !out) return set_err("null argument");
-    if (flags & ~(uint32_t)(RT_STOP_ON_ZERO | RT_ISOTROPIC_SCATTER | RT_KAT_REST_SHAPE | RT_KAT_NO_ONB_TABLE))
-        return set_err("rt_debug_shade takes RT_STOP_ON_ZERO, RT_ISOTROPIC_SCATTER, RT_KAT_REST_SHAPE and RT_KAT_NO_ONB_TABLE only");
+    if (flags & ~(uint32_t)(RT_STOP_ON_ZERO | RT_ISOTROPIC_SCATTER | RT_KAT_REST_SHAPE | RT_KAT_NO_ONB_TABLE | RT_KAT_TABLE_W))
+        return set_err("rt_debug_shade takes RT_STOP_ON_ZERO, RT_ISOTROPIC_SCATTER, RT_KAT_REST_SHAPE, RT_KAT_NO_ONB_TABLE and RT_KAT_TABLE_W only");
+    const bool table_w = (flags & RT_KAT_TABLE_W) != 0u;
+    if (table_w && (flags & (uint32_t)(RT_KAT_REST_SHAPE | RT_KAT_NO_ONB_TABLE)))
+        return set_err("rt_debug_shade: RT_KAT_TABLE_W is the compact lean f64 kernel's call: it goes with neither RT_KAT_REST_SHAPE nor RT_KAT_NO_ONB_TABLE");
     if (n > 0x7FFFFFFFu) return set_err("too many records: n must be <= 2^31 - 1 (per-path RNG keys, csrc/rt_rng.h)");
     if (depth_left == 0u) return set_err("rt_debug_shade: depth_left must be >= 1 (a path with no level left does not reach shade_hit)");
     if (n == 0) return 0;
@@ -1360,6 +1363,8 @@ int rt_debug_shade(rt_scene* sc, uint32_t n, const double* records, const double
     const HostFlat& f = s.flat;
     const bool rest = (flags & RT_KAT_REST_SHAPE) != 0u;
     if (!rest && f.feats != 0u) return set_err("rt_debug_shade: the lean shape serves list scenes only (no feature bit); pass RT_KAT_REST_SHAPE");
+    if (table_w && !(f.feats == 0u && lean_f64_compact(f)))
+        return set_err("rt_debug_shade: RT_KAT_TABLE_W serves scenes with the compact first-hit ring only (rt_debug_ring_form: a list scene in which every rect has a valid ONB-table entry)");
     std::vector<double> in((size_t)n * KAT_SHADE_IN, 0.0);
     for (size_t i = 0; i < n; i++) {
         const double* r = records + 16u * i; double* p = in.data() + KAT_SHADE_IN * i;
@@ -1376,6 +1381,17 @@ int rt_debug_shade(rt_scene* sc, uint32_t n, const double* records, const double
         if (!rest) {                                               // a list scene: every hit is a rect's, and its index names the ONB memo's entry
             rect = r[14];
             if (!(rect >= 0.0 && rect < (double)f.rects.size() && rect == std::floor(rect))) return set_err("rt_debug_shade: record " + std::to_string(i) + ": rect index out of range");
+        }
+        if (table_w) {                                             // what the compact loop hands its material section, and nothing else
+            const uint32_t kind = f.materials[(size_t)mat].kind & MAT_KIND_MASK;
+            if (kind != M_LAMBERTIAN && kind != M_METAL)
+                return set_err("rt_debug_shade: record " + std::to_string(i) + ": RT_KAT_TABLE_W takes Lambertian and Metal records only (the compact loop ends every other path before shade_hit)");
+            const DOnbEntry& e = f.onb[(size_t)rect];
+            for (int k = 0; k < 3; k++) {
+                uint64_t w; std::memcpy(&w, r + 5 + k, 8);
+                if ((w & 0x7FFFFFFFFFFFFFFFull) != e.mag[k])
+                    return set_err("rt_debug_shade: record " + std::to_string(i) + ": the normal's magnitudes are not those of rect " + std::to_string((size_t)rect) + "'s ONB-table entry (the compact record carries the normal as three sign bits)");
+            }
         }
         p[0] = r[2]; p[1] = r[3]; p[2] = r[4]; p[3] = r[5]; p[4] = r[6]; p[5] = r[7]; p[6] = r[1]; p[7] = r[9]; p[8] = r[10]; p[9] = r[8];
         p[10] = mat; p[11] = rect;
@@ -1397,6 +1413,7 @@ int rt_debug_shade(rt_scene* sc, uint32_t n, const double* records, const double
     A.n = n; A.in = (const double*)d_in.get(); A.out = (double*)d_out.get(); A.seed = seed; A.depth_left = depth_left;
     for (int k = 0; k < 3; k++) A.beta[k] = beta[k];
     if (rest) HIP_OK(launch_shade_kat_rest(P, A, (f.feats & F_NESTED) != 0u, nullptr));
+    else if (table_w) HIP_OK(launch_shade_kat_table_w(P, A, nullptr));
     else HIP_OK(launch_shade_kat_lean(P, A, nullptr));
     HIP_OK(hipMemcpy(out, d_out.get(), (size_t)n * KAT_SHADE_OUT * 8u, hipMemcpyDeviceToHost));
     return 0;

@@ -30,4 +30,7 @@ hipError_t launch_brdf_kat_rest(const KParams<double>& P, uint32_t n, uint32_t p
 // one call of shade_hit per record: shade_hit<double, 0> under the lean shape, <double, F_ALL> or (nested) <double, F_ALL | F_NESTED> under the other
 hipError_t launch_shade_kat_lean(const KParams<double>& P, const ShadeKatArgs& A, hipStream_t stream);
 hipError_t launch_shade_kat_rest(const KParams<double>& P, const ShadeKatArgs& A, bool nested, hipStream_t stream);
+// the call as the compact lean f64 kernel's material section makes it (lean shape): the rect word packed with the normal's sign bits, the normal
+// rebuilt from the ONB table, shade_hit<double, 0, true>.  For scenes with the compact ring and records that satisfy Lemma N's premise only.
+hipError_t launch_shade_kat_table_w(const KParams<double>& P, const ShadeKatArgs& A, hipStream_t stream);
 }

@@ -106,6 +106,43 @@ __global__ void __launch_bounds__(KAT_THREADS) shade_kat_kernel(const KParams<do
 }
 
 #if RT_SHAPE == 1
+// The same call as the COMPACT lean f64 kernel makes it (RT_KAT_TABLE_W; the lean shape only, so the other shape's object is not touched):
+// the top of trace_shade_fill<double, 0u, true>'s material section — the rect word with `front` and the normal's three sign bits, the
+// normal rebuilt from the ONB table, shade_hit<double, 0u, true> on that word (merged_arms_table_w: w, v, u from the table).  Records,
+// stream, columns and the partial last wave are shade_kat_kernel's.  The host has checked that P.onb holds a valid entry for every rect
+// and that each record's normal has its rect's magnitudes (Lemma N's premise) and a Lambertian or Metal material (the loop ends every
+// other path before this call).
+// The columns mean what they mean under the other forms: "the ray afterwards" is the incoming ray where nothing scatters.  The compact arm
+// forms Metal's scattered ray in place before it knows whether the lane is absorbed (the loop does not read a finished lane's ray again),
+// so a record that ends without a scatter — `done` with depth_left untouched — reports the ray it came with.
+__global__ void __launch_bounds__(KAT_THREADS) shade_kat_table_w_kernel(const KParams<double> P, const ShadeKatArgs A) {
+    typedef double T;
+    const uint64_t i64 = (uint64_t)blockIdx.x * KAT_THREADS + threadIdx.x;
+    const bool mine = i64 < A.n;
+    const uint32_t k = mine ? (uint32_t)i64 : A.n - 1u;
+    const double* p = A.in + (uint64_t)KAT_SHADE_IN * k;
+    Rec<T> rec;
+    rec.p = mk<T>(p[0], p[1], p[2]); rec.t = p[6]; rec.u = p[7]; rec.v = p[8]; rec.front = p[9] != 0.0;
+    rec.mat = (uint32_t)p[10];
+    const uint32_t word = ring_pack_signs((uint32_t)p[11] | (rec.front ? 0x80000000u : 0u), mk<T>(p[3], p[4], p[5]));
+    rec.n = ring_normal(P.onb, word);
+    RayT<T> ray; ray.o = mk<T>(p[12], p[13], p[14]); ray.d = mk<T>(p[15], p[16], p[17]); ray.tm = p[18];
+    const RayT<T> came = ray;
+    V3<T> beta = mk<T>(A.beta[0], A.beta[1], A.beta[2]);
+    Rng rng = rng_for_path(A.seed, k, 0u);
+    uint32_t depth_left = A.depth_left;
+    bool done = false;
+    V3<T> e = mk<T>(T(0), T(0), T(0));
+    shade_hit<T, 0u, true>(P, rec, ray, beta, rng, depth_left, done, e, word);
+    if (done && depth_left == A.depth_left) ray = came;
+    if (mine) {
+        double* o = A.out + (uint64_t)KAT_SHADE_OUT * k;
+        o[0] = ray.o.x; o[1] = ray.o.y; o[2] = ray.o.z; o[3] = ray.d.x; o[4] = ray.d.y; o[5] = ray.d.z; o[6] = ray.tm;
+        o[7] = beta.x; o[8] = beta.y; o[9] = beta.z; o[10] = e.x; o[11] = e.y; o[12] = e.z;
+        o[13] = done ? 1.0 : 0.0; o[14] = (double)depth_left;
+        o[15] = (double)rng.s0; o[16] = (double)rng.s1; o[17] = (double)rng.s2; o[18] = (double)rng.s3;
+    }
+}
 #define KAT_NAME(f) f##_lean
 #else
 #define KAT_NAME(f) f##_rest
@@ -124,6 +161,11 @@ hipError_t KAT_NAME(launch_brdf_kat)(const KParams<double>& P, uint32_t n, uint3
 #if RT_SHAPE == 1
 hipError_t launch_shade_kat_lean(const KParams<double>& P, const ShadeKatArgs& A, hipStream_t stream) {
     hipLaunchKernelGGL((shade_kat_kernel<RT_SHAPE, 0u>), dim3((A.n + KAT_THREADS - 1u) / KAT_THREADS), dim3(KAT_THREADS), 0, stream, P, A);
+    return hipGetLastError();
+}
+// ... and the compact kernel's (shade_hit<double, 0u, true>): P.onb is not null and every record's entry is valid (rt_host.cpp rt_debug_shade)
+hipError_t launch_shade_kat_table_w(const KParams<double>& P, const ShadeKatArgs& A, hipStream_t stream) {
+    hipLaunchKernelGGL(shade_kat_table_w_kernel, dim3((A.n + KAT_THREADS - 1u) / KAT_THREADS), dim3(KAT_THREADS), 0, stream, P, A);
     return hipGetLastError();
 }
 #else

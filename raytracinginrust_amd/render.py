@@ -228,22 +228,24 @@ def debug_brdf(b: SceneBuilder, material: int, r_in: np.ndarray, r_out: np.ndarr
     return out
 
 
-RT_KAT_REST_SHAPE, RT_KAT_NO_ONB_TABLE = 0x100, 0x200
+RT_KAT_REST_SHAPE, RT_KAT_NO_ONB_TABLE, RT_KAT_TABLE_W = 0x100, 0x200, 0x400
 SHADE_FIELDS = {"ray": slice(0, 7), "beta": slice(7, 10), "e": slice(10, 13), "done": 13, "depth_left": 14, "state": slice(15, 19)}
 
 
 def debug_shade(b: SceneBuilder, records: np.ndarray, rays: np.ndarray, beta=(1.0, 1.0, 1.0), seed: int = 0, depth_left: int = 50,
-                flags: int = 0, shape: str = "lean", onb_table: bool = True) -> np.ndarray:
+                flags: int = 0, shape: str = "lean", onb_table: bool = True, table_w: bool = False) -> np.ndarray:
     """rt_debug_shade (needs a GPU): ONE call of the kernels' shade_hit per record — records (n, 16) as query_hits gives them, rays (n, 7),
     record k on the stream rt_rng_path(seed, k, 0) — under the lean instantiation and code shape (list scenes; onb_table=False: without
-    the ONB memo) or the all-features one (shape="rest").  flags: RT_STOP_ON_ZERO, RT_ISOTROPIC_SCATTER.  -> (n, 19), columns SHADE_FIELDS."""
+    the ONB memo; table_w=True: the call as the compact lean f64 kernel makes it, w, v and u from the ONB table — scenes with the compact
+    ring, Lambertian and Metal records whose normals have their rects' magnitudes) or the all-features one (shape="rest").
+    flags: RT_STOP_ON_ZERO, RT_ISOTROPIC_SCATTER.  -> (n, 19), columns SHADE_FIELDS.  The arguments are checked before any device call."""
     rec = np.ascontiguousarray(records, np.float64).reshape(-1, 16)
     ry = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
     if len(rec) != len(ry):
         raise ValueError("records and rays differ in length")
     bt = np.ascontiguousarray(beta, np.float64).reshape(3)
     out = np.zeros((len(rec), 19), np.float64)
-    fl = int(flags) | KAT_SHAPES[shape] | (0 if onb_table else RT_KAT_NO_ONB_TABLE)
+    fl = int(flags) | KAT_SHAPES[shape] | (0 if onb_table else RT_KAT_NO_ONB_TABLE) | (RT_KAT_TABLE_W if table_w else 0)
     _check(_rt().rt_debug_shade(b.h, len(rec), rec.ctypes.data, ry.ctypes.data, bt.ctypes.data, int(seed), int(depth_left), fl, out.ctypes.data))
     return out
 
