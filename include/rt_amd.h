@@ -407,6 +407,11 @@ int rt_query_camera(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_
 int rt_query_camera_device(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t sample, uint64_t seed, uint32_t flags,
                            void* d_rays_out, void* d_hits_out, size_t d_hits_bytes, void* hip_stream);
 int rt_last_query_ms(rt_scene*, float* ms_out);   /* HIP events around the most recent query kernel of this scene (ray or radiance query); waits */
+/* Geometry of that kernel's launch — the most recent ray, albedo or radiance query or pixel-list pass (rt_render_pixels_device) of this scene —
+ * as the host computed it: [0] workgroups launched, [1] threads per workgroup, [2] paths per chunk and [3] number of chunks of a radiance query
+ * or pixel-list pass (saturating at 2^32 - 1), both 0 for a ray or albedo query, which have no chunks: n rays with n > [0] * [1] take a lane
+ * through its loop more than once, [3] > [0] * [1] / 64 gives a wave a second chunk.  Read-only, waits for nothing; -1 before the first query. */
+int rt_last_query_launch(rt_scene*, uint32_t out4[4]);
 
 /* ---- albedo queries: the reflectance at the closest hit, for rays the caller chooses or summed over a range of samples of every pixel's
  *      camera ray — the albedo frame a denoiser divides a textured frame by (rt_denoise_albedo* below), or a compositor's base-colour pass.
@@ -710,6 +715,16 @@ int rt_last_leaf_steps(rt_scene*, unsigned long long out2[2]);
 /* Diagnostic builds (-DRT_DIAG) only (zeros in a normal build): [0..5] wave-cycle sums of the six kernel sections, [6] rect tests
  * counted per wavefront, [7] those among them in which no lane's plane distance lay in [t_min, closest] (-DRT_DIAG_RECTS builds). */
 int rt_debug_section_cycles(rt_scene*, unsigned long long out8[8]);
+/* Test aid (host only, no GPU): the compiled-in launch limits of the element-wise kernels, so that a test can choose the smallest frame that takes
+ * a loop into its second trip and can tell that it did.  Writes min(max_words, RT_LOOP_LIMITS_WORDS) words and returns RT_LOOP_LIMITS_WORDS:
+ * [0] [1] workgroups at most / threads of the kernels of rt_denoise_frame_device (a lane takes one PAIR of doubles per trip), [2] [3] the same
+ * for the variance kernels (rt_moments_variance_device), [4] pixels per workgroup of the selection's compaction, [5] workgroup counts its
+ * scan takes per trip (one workgroup of that many lanes), [6] workgroups at most of the error and counts-aware resolve kernels, [7] threads of
+ * the adaptive element-wise kernels (the resolve takes 4 pixels per lane and trip), [8] workgroups at most of the others, [9] [10] [11]
+ * workgroups at most / threads / pixels per lane and trip of rt_progressive_resolve_rgb8, [12] threads of the ray and albedo query kernels,
+ * [13] [14] threads / default paths per chunk of the radiance queries, [15] [16] the same for the pixel-list kernel. */
+#define RT_LOOP_LIMITS_WORDS 17u
+int rt_debug_loop_limits(uint32_t* out, uint32_t max_words);
 /* Measuring aid (tools/denoise_probe.py): rt_denoise_device on the null stream, synchronously, once to warm up and once with HIP events between its
  * launches: ms_out[0] = the pack kernel, ms_out[1 + i] = iteration i (iterations + 1 floats). */
 int rt_debug_denoise_ms(const void* d_rgb_sum, uint64_t samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,

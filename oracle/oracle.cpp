@@ -1553,6 +1553,35 @@ void orc_ray_color_path(void* s, const double* o, const double* d, double time, 
     Color c = ray_color(Ray(V(o), V(d), time), V(bg), SC->world, &SC->lights, depth, smp);
     for (int i = 0; i < 3; i++) out3[i] = c[i];
 }
+// orc_ray_color_path for every path of a batch: samples [first_sample, first_sample + spp) of n caller rays (n x 7), ray k's sample s on
+// Rng::for_path(seed, k, s) — the key of the product's radiance queries.  out: n x spp x 3.  Paths are dealt to nthreads threads 256 at a time
+// (nthreads <= 0: hardware concurrency); a path's value depends on (k, s) alone, so the dealing changes no word.
+void orc_ray_color_paths(void* s, uint32_t n, const double* rays, uint32_t spp, uint32_t first_sample, const double* bg, uint64_t depth, uint64_t seed,
+                         int nthreads, double* out) {
+    if (nthreads <= 0) nthreads = (int)std::thread::hardware_concurrency();
+    if (nthreads <= 0) nthreads = 1;
+    const Scene& sc = *SC;
+    const Color background = V(bg);
+    const uint64_t n_paths = (uint64_t)n * spp;
+    std::atomic<uint64_t> next(0);
+    auto work = [&]() {
+        for (;;) {
+            const uint64_t p0 = next.fetch_add(256);
+            if (p0 >= n_paths) break;
+            for (uint64_t p = p0; p < std::min(n_paths, p0 + 256); p++) {
+                const uint32_t k = (uint32_t)(p / spp), smp_i = (uint32_t)(p - (uint64_t)k * spp);
+                const double* ry = rays + 7 * (size_t)k;
+                Sampler smp; smp.rng = Rng::for_path(seed, k, first_sample + smp_i);
+                Color c = ray_color(Ray(V(ry), V(ry + 3), ry[6]), background, sc.world, &sc.lights, depth, smp);
+                for (int i = 0; i < 3; i++) out[3 * p + (uint64_t)i] = c[i];
+            }
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 1; t < nthreads; t++) th.emplace_back(work);
+    work();
+    for (auto& t : th) t.join();
+}
 // world.hit(ray, 0.00001, +inf) for n rays (n x 7), written in the product's rt_query_hits layout (n x 16): hit, t, position[3], normal[3],
 // front_face, u, v, the material's handle; the object and primitive fields, which only the product knows, are -1.  Ray k draws from
 // Rng::for_stream(seed, k) where a ConstantMedium needs a number.

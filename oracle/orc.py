@@ -133,6 +133,8 @@ def _declare(lib) -> Backend:
     lib.orc_ray_color.argtypes = [C.c_void_p, d3, d3, C.c_double, d3, C.c_uint64, C.c_void_p, d3]
     lib.orc_ray_color_path.restype = None
     lib.orc_ray_color_path.argtypes = [C.c_void_p, d3, d3, C.c_double, d3, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, d3]
+    lib.orc_ray_color_paths.restype = None
+    lib.orc_ray_color_paths.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, d3, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p]
     lib.orc_hit_records.restype = None
     lib.orc_hit_records.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]
     lib.orc_hit_batch.restype = None
@@ -237,6 +239,17 @@ def ray_color_path(b, o, d, time_, background, depth, seed, pixel, sample=0):
     out = _d(0, 0, 0)
     load().lib.orc_ray_color_path(b.h, _d(*o), _d(*d), time_, _d(*background), depth, seed, pixel, sample, out)
     return list(out)
+
+
+def ray_color_paths(b, rays, spp, background, depth, seed, first_sample=0, nthreads=0):
+    """orc_ray_color_paths: ray_color for samples [first_sample, first_sample + spp) of n rays (n, 7) -> (n, spp, 3); ray k's sample s on the
+    stream rng_path(seed, k, s), as ray_color_path computes it one path at a time.  nthreads 0: min(hardware threads, 16)."""
+    ry = np.ascontiguousarray(rays, np.float64).reshape(-1, 7)
+    out = np.zeros((len(ry), int(spp), 3), np.float64)
+    if nthreads <= 0:
+        nthreads = max(1, min(hardware_threads(), 16))
+    load().lib.orc_ray_color_paths(b.h, len(ry), ry.ctypes.data, int(spp), int(first_sample), _d(*background), int(depth), int(seed), int(nthreads), out.ctypes.data)
+    return out
 
 
 def hit_records(b, rays, seed=0):

@@ -142,6 +142,7 @@ SIGNATURES = {
     "query_camera": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u64, _u32, _ptr, _ptr]),
     "query_camera_device": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u64, _u32, _ptr, _ptr, C.c_size_t, _ptr]),
     "last_query_ms": (_int, [_ptr, c_float_p]),
+    "last_query_launch": (_int, [_ptr, c_u32_p]),
     # albedo queries
     "query_albedo": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _ptr, _ptr]),
     "query_albedo_device": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _ptr, C.c_size_t, _ptr, C.c_size_t, _ptr]),
@@ -205,6 +206,7 @@ SIGNATURES = {
     "debug_denoise_variance_ms": (_int, [_ptr, _u64, _ptr, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, C.c_size_t, c_float_p]),
     "debug_albedo_modulate_ms": (_int, [_ptr, _ptr, _u64, _ptr, _u64, c_float_p]),
     "debug_section_cycles": (_int, [_ptr, c_ull_p]),
+    "debug_loop_limits": (_int, [c_u32_p, _u32]),
     "debug_tune_filter": (_int, [_ptr, _ptr]),
     "debug_objects": (_int, [_ptr, _ptr, _u32, c_u32_p]),
     "debug_bvh_links": (_int, [_ptr, c_u32_p, _u32, c_u32_p, _u32, c_u32_p]),

@@ -76,6 +76,12 @@ int launch_adaptive_error(const double* d_S, const double* d_Q, const uint32_t* 
                           unsigned long long* d_stats, void* stream);
 // (B): count, scan, scatter.  The workspace (16-byte aligned, adaptive_select_workspace_bytes) holds the need and active flags and the per-block counts.
 static const uint32_t ADAPTIVE_BLOCK_PX = 1024u;                 // pixels one workgroup of the compaction covers: 256 lanes x 4 consecutive pixels
+// the element-wise kernels' launch (rt_adaptive.hip; here for rt_debug_loop_limits): the scan is ONE workgroup of ADAPTIVE_SCAN_THREADS lanes that
+// walks the workgroup counts that many at a time; the error and resolve kernels launch at most ADAPTIVE_ERROR_MAX_BLOCKS workgroups
+static const uint32_t ADAPTIVE_THREADS = 256u;
+static const uint32_t ADAPTIVE_MAX_BLOCKS = 2048u;            // 8 resident workgroups' worth per CU; grid-stride beyond that
+static const uint32_t ADAPTIVE_ERROR_MAX_BLOCKS = 1024u;      // every workgroup ends with up to four atomics on one cache line (rt_moments.hip)
+static const uint32_t ADAPTIVE_SCAN_THREADS = 1024u;
 inline size_t adaptive_select_workspace_bytes(uint64_t n_px) {
     const uint64_t flags = (n_px + 15u) & ~(uint64_t)15u, blocks = (n_px + ADAPTIVE_BLOCK_PX - 1u) / ADAPTIVE_BLOCK_PX;
     return (size_t)(2u * flags + ((blocks * 4u + 15u) & ~(uint64_t)15u));

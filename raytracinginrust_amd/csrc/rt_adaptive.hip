@@ -216,11 +216,6 @@ hipError_t launch_pixels(const KParams<double>& P, const PixelsArgs& X, uint32_t
 }
 
 // ------------------------------------------------------------------ the element-wise kernels (rt_adaptive.h (A) - (D))
-static const uint32_t ADAPTIVE_THREADS = 256u;
-static const uint32_t ADAPTIVE_MAX_BLOCKS = 2048u;            // 8 resident workgroups' worth per CU; grid-stride beyond that
-static const uint32_t ADAPTIVE_ERROR_MAX_BLOCKS = 1024u;      // every workgroup ends with up to four atomics on one cache line (rt_moments.hip)
-static const uint32_t ADAPTIVE_SCAN_THREADS = 1024u;
-
 // the three doubles of pixel p; A16: `base` is 16-byte aligned
 template <bool A16> DEV void ld3d(const double* base, uint64_t p, double v[3]) {
     const double* q = base + 3u * p;

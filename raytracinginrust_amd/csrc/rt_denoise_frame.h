@@ -39,6 +39,10 @@
 
 namespace rt {
 
+// the element-wise kernels' launch (rt_denoise_frame.hip; here for rt_debug_loop_limits): one pair of doubles per lane and trip
+static const uint32_t DNF_THREADS = 256u;
+static const uint32_t DNF_MAX_BLOCKS = 2048u;                   // 8 resident workgroups' worth per CU; grid-stride beyond that (rt_moments.hip)
+
 // the workspace of one run: the filter's own, then the frames c and Vd (3 doubles per pixel each, each padded to a multiple of 16 bytes so
 // that both start 16-byte aligned in a 16-byte aligned workspace)
 inline size_t denoise_frame_plane_bytes(uint64_t n_px) { return (size_t)((n_px * 3u * sizeof(double) + 15u) & ~(uint64_t)15u); }

@@ -22,9 +22,6 @@ namespace rt {
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-static const uint32_t DNF_THREADS = 256u;
-static const uint32_t DNF_MAX_BLOCKS = 2048u;                   // 8 resident workgroups' worth per CU; grid-stride beyond that (rt_moments.hip)
-
 // the pixels of doubles 2 i and 2 i + 1
 __device__ __forceinline__ void pair_pixels(uint64_t i, uint64_t& p0, uint64_t& p1) {
     const uint64_t i0 = 2u * i;

@@ -51,6 +51,10 @@
 
 namespace rt {
 
+// the element-wise variance kernels' launch (rt_denoise_var.hip; here for rt_debug_loop_limits): one pair of doubles per lane and trip
+static const uint32_t DNV_THREADS = 256u;
+static const uint32_t DNV_MAX_BLOCKS = 2048u;                   // the element-wise variance kernel: grid-stride beyond that (rt_moments.hip)
+
 static const double DENOISE_VAR_EPS = 0.0000152587890625;       // 2^-16
 // the workspace of one run is rt_denoise.h's: two packed colour frames {r, g, b, v} and the packed guide, 128 bytes per pixel
 

@@ -24,8 +24,6 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 
 static const uint32_t DNV_BLOCK_X = 64u, DNV_BLOCK_Y = 4u;       // one wave per row segment, four rows per workgroup
 static const uint32_t DNV_LDS_TILE = 16u;                       // the LDS form: 16 x 16 pixels per workgroup
-static const uint32_t DNV_THREADS = 256u;
-static const uint32_t DNV_MAX_BLOCKS = 2048u;                   // the element-wise variance kernel: grid-stride beyond that (rt_moments.hip)
 
 __device__ __forceinline__ bool dnv_finite(double v) { return v - v == 0.0; }
 __device__ __forceinline__ double dnv_stop(double t) { return t > 0.0 ? t * t : 0.0; }

@@ -1588,6 +1588,7 @@ static int query_launch_as(Scene& s, const rt_camera* camp, uint32_t W, uint32_t
     if (query_events(s, c.device)) return -1;
     HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[0], stream));
     HIP_OK(launch(P, f.feats, camera, (uint32_t)n_blocks, shmem, stream));
+    s.q_launch[0] = (uint32_t)n_blocks; s.q_launch[1] = QUERY_THREADS; s.q_launch[2] = 0u; s.q_launch[3] = 0u;      // (no chunks: one ray per lane and batch)
     HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[1], stream));
     s.q_recorded = true;
     return 0;
@@ -1660,6 +1661,26 @@ int rt_last_query_ms(rt_scene* sc, float* ms_out) {
     HIP_OK(hipEventSynchronize((hipEvent_t)sc->s.q_ev[1]));
     HIP_OK(hipEventElapsedTime(ms_out, (hipEvent_t)sc->s.q_ev[0], (hipEvent_t)sc->s.q_ev[1]));
     return 0;
+}
+// Geometry of the most recent query kernel of this scene (what rt_last_query_ms times): [0] workgroups, [1] threads per workgroup, [2] paths
+// per chunk and [3] chunks (saturating at 2^32 - 1) of a radiance-query or pixel-list kernel, both 0 for a ray or albedo query.  Written
+// by the host where the grid is computed; nothing waits
+int rt_last_query_launch(rt_scene* sc, uint32_t out4[4]) {
+    if (!sc || !out4) return set_err("null argument");
+    if (!sc->s.q_recorded) return set_err("no ray query has been launched for this scene");
+    for (int k = 0; k < 4; k++) out4[k] = sc->s.q_launch[k];
+    return 0;
+}
+// The sizes at which the element-wise kernels' loops turn over, as compiled (include/rt_amd.h names the slots); host only
+int rt_debug_loop_limits(uint32_t* out, uint32_t max_words) {
+    const uint32_t v[RT_LOOP_LIMITS_WORDS] = {
+        DNF_MAX_BLOCKS, DNF_THREADS, DNV_MAX_BLOCKS, DNV_THREADS,
+        ADAPTIVE_BLOCK_PX, ADAPTIVE_SCAN_THREADS, ADAPTIVE_ERROR_MAX_BLOCKS, ADAPTIVE_THREADS, ADAPTIVE_MAX_BLOCKS,
+        RT_RESOLVE_MAX_BLOCKS, RT_RESOLVE_THREADS, RT_RESOLVE_PX_PER_LANE,
+        QUERY_THREADS, RADIANCE_THREADS, RADIANCE_CHUNK, PIXELS_THREADS, PIXELS_CHUNK };
+    if (!out && max_words) return set_err("null argument");
+    for (uint32_t k = 0; k < RT_LOOP_LIMITS_WORDS && k < max_words; k++) out[k] = v[k];
+    return (int)RT_LOOP_LIMITS_WORDS;
 }
 
 // ---------------------------------------------------------------- albedo queries (csrc/rt_albedo.h: the definition; rt_albedo.hip: the kernels)
@@ -1794,6 +1815,7 @@ int rt_query_radiance_device(rt_scene* sc, uint32_t n, const void* d_rays, const
     if (!accumulate) HIP_OK(hipMemsetAsync(d_rgb_sum, 0, (size_t)n * 3u * sizeof(double), stream));
     HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[0], stream));
     HIP_OK(launch_radiance(P, R, f.feats, (uint32_t)n_blocks, shmem, stream));
+    s.q_launch[0] = (uint32_t)n_blocks; s.q_launch[1] = RADIANCE_THREADS; s.q_launch[2] = R.chunk; s.q_launch[3] = (uint32_t)(R.n_chunks > 0xFFFFFFFFull ? 0xFFFFFFFFull : R.n_chunks);
     HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[1], stream));
     s.q_recorded = true;
     return 0;
@@ -2233,6 +2255,7 @@ int rt_render_pixels_device(rt_scene* sc, const rt_camera* cam, const double bg[
     if (query_events(s, c.device)) return -1;
     HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[0], stream));
     HIP_OK(launch_pixels(P, X, f.feats, (uint32_t)n_blocks, shmem, stream));
+    s.q_launch[0] = (uint32_t)n_blocks; s.q_launch[1] = PIXELS_THREADS; s.q_launch[2] = X.chunk; s.q_launch[3] = (uint32_t)(X.n_chunks > 0xFFFFFFFFull ? 0xFFFFFFFFull : X.n_chunks);
     HIP_OK(hipEventRecord((hipEvent_t)s.q_ev[1], stream));
     s.q_recorded = true;
     return 0;

@@ -14,4 +14,8 @@ hipError_t launch_resolve_rgb8(const double* sum, uint64_t samples, const uint8_
                                unsigned long long* changed_px, uint32_t n_px, hipStream_t stream);
 // pixels one lane resolves per step of its grid-stride loop (tests choose frame sizes that are not multiples of it)
 static const uint32_t RT_RESOLVE_PX_PER_LANE = 4u;
+// the launch: workgroups of RT_RESOLVE_THREADS lanes, at most RT_RESOLVE_MAX_BLOCKS of them — 32 resident workgroups' worth per CU; a frame of
+// more than MAX_BLOCKS x THREADS x PX_PER_LANE pixels goes through the kernel's grid-stride loop more than once (rt_debug_loop_limits)
+static const uint32_t RT_RESOLVE_THREADS = 256u;
+static const uint32_t RT_RESOLVE_MAX_BLOCKS = 8192u;
 }

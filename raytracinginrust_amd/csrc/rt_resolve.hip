@@ -65,10 +65,10 @@ __global__ __launch_bounds__(256) void resolve_rgb8_kernel(const double* __restr
 
 hipError_t launch_resolve_rgb8(const double* sum, uint64_t samples, const uint8_t* rgb8_prev, uint8_t* rgb8_out,
                                unsigned long long* changed_px, uint32_t n_px, hipStream_t stream) {
-    const uint32_t threads = 256u;
+    const uint32_t threads = RT_RESOLVE_THREADS;
     const uint64_t n_groups = n_px / RT_RESOLVE_PX_PER_LANE;
     uint64_t blocks = (n_groups + threads - 1u) / threads;
-    if (blocks > 8192u) blocks = 8192u;                          // grid-stride beyond that: 32 resident workgroups' worth per CU
+    if (blocks > RT_RESOLVE_MAX_BLOCKS) blocks = RT_RESOLVE_MAX_BLOCKS;      // grid-stride beyond that (rt_resolve.h)
     if (blocks == 0u) blocks = 1u;
     hipLaunchKernelGGL(resolve_rgb8_kernel, dim3((uint32_t)blocks), dim3(threads), 0, stream, sum, (double)samples, rgb8_prev, rgb8_out, changed_px, n_px);
     return hipGetLastError();

@@ -960,6 +960,33 @@ def last_query_ms(b: SceneBuilder) -> float:
     return float(ms.value)
 
 
+def last_query_launch(b: SceneBuilder) -> dict:
+    """rt_last_query_launch: the launch geometry of the most recent query kernel of this scene (ray, albedo or radiance query, pixel-list
+    pass) as the host computed it — workgroups, threads per workgroup, waves (workgroups x threads / 64), and paths per chunk / chunks
+    of a radiance query or pixel-list pass (0 / 0 for a ray or albedo query).  Waits for nothing; an error before the first query."""
+    out = (C.c_uint32 * 4)()
+    _check(_rt().rt_last_query_launch(b.h, out))
+    wg, th, chunk, n_chunks = (int(x) for x in out)
+    return {"workgroups": wg, "threads": th, "waves": wg * (th // 64), "chunk": chunk, "chunks": n_chunks}
+
+
+LOOP_LIMITS = ("denoise_frame_max_blocks", "denoise_frame_threads", "variance_max_blocks", "variance_threads", "compaction_block_px",
+               "scan_threads", "adaptive_error_max_blocks", "adaptive_threads", "adaptive_max_blocks", "resolve_max_blocks", "resolve_threads",
+               "resolve_px_per_lane", "query_threads", "radiance_threads", "radiance_chunk", "pixels_threads", "pixels_chunk")
+
+
+def debug_loop_limits() -> dict:
+    """rt_debug_loop_limits (host only): the compiled-in launch limits of the element-wise kernels and the workgroup and chunk sizes of the
+    query kernels, by name (include/rt_amd.h has the slots)."""
+    n = _rt().rt_debug_loop_limits(None, 0)
+    if n != len(LOOP_LIMITS):
+        raise RenderError(f"rt_debug_loop_limits reports {n} words, this binding knows {len(LOOP_LIMITS)}")
+    out = (C.c_uint32 * n)()
+    if _rt().rt_debug_loop_limits(out, n) != n:
+        raise RenderError(_err())
+    return dict(zip(LOOP_LIMITS, (int(x) for x in out)))
+
+
 def aov_image(hits: np.ndarray, which: str) -> np.ndarray:
     """An (H, W, 3) 8-bit image of one field of (H, W, 16) hit records, as `rtrender --aov` writes it: "normal" = 0.5 (n + 1) * 255.999
     truncated (a miss: the zero normal, 127); "depth" = t linear between the frame's smallest (255) and largest (0) finite hit t, a miss 0;
