@@ -270,6 +270,26 @@ inline std::vector<double> denoise_albedo(const std::vector<double>& rgb_sum, ui
     return out;
 }
 
+// Averaged denoising guides (rt_query_camera_guide, csrc/rt_guide.h): the first-hit records of samples [first_sample, first_sample +
+// n_samples) of every pixel reduced to one record in the 16-double layout of query_camera's — hit by majority, t / position / normal /
+// front_face as means over the hitting samples, material / object where they agree (else -1), the coverage count in word [15] — which
+// every `hit_records` parameter of the denoise family takes unchanged.  albedo_sum_out (optional) receives the W*H*3 sums of
+// query_camera_albedo for the same samples, from the same searches.
+inline std::vector<double> query_camera_guide(Scene& s, const Camera& cam, uint32_t W, uint32_t H, uint32_t first_sample = 0, uint32_t n_samples = 16,
+                                              uint64_t seed = 0x5EED, std::vector<double>* albedo_sum_out = nullptr) {
+    std::vector<double> out((size_t)W * H * 16);
+    if (albedo_sum_out) albedo_sum_out->assign((size_t)W * H * 3, 0.0);
+    if (rt_query_camera_guide(s.raw(), &cam.c, W, H, first_sample, n_samples, seed, 0, out.data(), albedo_sum_out ? albedo_sum_out->data() : nullptr) != 0) throw Error(rt_last_error());
+    return out;
+}
+// the specification on the host (no device): hit_records = n_samples x n_px x 16 doubles, sample-major -> n_px x 16
+inline std::vector<double> guide_from_hits(const std::vector<double>& hit_records, uint32_t n_samples, uint64_t n_px) {
+    if (n_samples == 0 || hit_records.size() != (size_t)n_samples * n_px * 16) throw Error("guide_from_hits: records of another size");
+    std::vector<double> out((size_t)n_px * 16);
+    if (rt_guide_from_hits_host(hit_records.data(), n_samples, n_px, out.data()) != 0) throw Error(rt_last_error());
+    return out;
+}
+
 // ray_color (src/main.rs:41-120) along rays the caller chooses (rt_query_radiance), samples_per_ray samples of each: per ray the SUM over
 // its samples, n x 3, as render() returns per pixel — another projection than Camera's, a light probe, a baked light map.  Sample s of ray k
 // draws from the stream of rt_rng_path(seed, k, s).  samples_out (optional) receives every sample, ray-major; nonfinite_out (optional) the
@@ -391,6 +411,11 @@ public:
     std::vector<uint8_t> rgb8_denoised_albedo(uint32_t albedo_samples = 16, const DenoiseSettings& d = DenoiseSettings()) {
         std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_denoised_albedo_rgb8(p_, albedo_samples, d.iterations, d.sigma, d.flags, out.data())); return out;
     }
+    // the guide of every denoised resolve: 1 (the default) the camera hits of sample 0, n > 1 `query_camera_guide` over samples [0, n); another
+    // value drops the packed guide and the next denoised resolve builds it.  guide_info: the value in force and the guides built so far
+    void set_guide_samples(uint32_t n_samples) { chk(rt_progressive_set_guide_samples(p_, n_samples)); }
+    struct GuideInfo { uint32_t guide_samples; uint64_t builds; };
+    GuideInfo guide_info() const { GuideInfo g{0u, 0u}; chk(rt_progressive_guide_info(p_, &g.guide_samples, &g.builds)); return g; }
     std::vector<double> sum() const { std::vector<double> out(n_px_ * 3); chk(rt_progressive_read_sum(p_, out.data())); return out; }
     void load(const std::vector<double>& rgb_sum, uint64_t samples_done) {
         if (rgb_sum.size() != n_px_ * 3) throw Error("checkpoint of another frame size");

@@ -435,6 +435,45 @@ int rt_query_camera_albedo(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, 
                            uint64_t seed, uint32_t flags, double* albedo_sum_out);
 int rt_query_camera_albedo_device(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
                                   uint64_t seed, uint32_t flags, void* d_albedo_sum, size_t d_albedo_sum_bytes, void* hip_stream);
+
+/* ---- averaged denoising guides: the first-hit records of n_samples camera samples of every pixel reduced to ONE record in the layout of
+ *      rt_query_camera, so that every `hits` parameter of the denoise family below takes it unchanged — a guide that sees what the lens,
+ *      the shutter and the pixel's area see, where sample 0's record sees one ray.  An exact f64 specification (csrc/rt_guide.h: only + /
+ *      comparisons and integer counts, a fixed order) that the HIP kernel (csrc/rt_guide.hip) and the host twin satisfy bit for bit.
+ * Per pixel, over the records r_s of rt_query_camera(sample = s), s = first_sample .. first_sample + n_samples - 1 ascending: h = the number
+ * with hit != 0, hf = the number of those with front_face != 0; t, position and normal are summed over the hitting records only, in
+ * ascending order, into accumulators that start at +0.0.  The record:
+ *   [0] hit = 1.0 if h >= 1 and 2 h >= n_samples (the majority, a tie counting as hit), else 0.0;  [1] t, [2..4] position, [5..7] normal =
+ *   sum / h (0 when h = 0; the normal is NOT renormalised: an edge pixel's short normal is information);  [8] front_face = hf / h, a
+ *   fraction;  [9], [10] u, v = 0.0;  [11] material, [12] object = the common value over the hitting records (a medium's -1 is a value
+ *   like any other), -1 when they differ or h = 0;  [13], [14] = -1;  [15] hits = (double) h, the coverage count (rt_query_camera writes
+ *   0.0 there and no reader uses it).
+ * n_samples = 1 gives words [0]-[8], [11], [12] of rt_query_camera(first_sample) as values (a -0.0 component becomes +0.0 through the
+ * accumulator).  A pixel whose samples mix materials has material -1: key 1 under RT_DENOISE_SAME_MATERIAL, as a medium, never a miss's 0.
+ * A pixel whose samples mostly miss is a miss to the filters; words [1]-[8] and [15] still carry what the hitting samples saw.
+ * rt_query_camera_guide: guide_out = W*H*16 doubles in output order; albedo_sum_out: NULL, or W*H*3 doubles — the very words
+ * rt_query_camera_albedo(first_sample, n_samples) writes, from the SAME searches (one search per sample instead of two for a caller who
+ * wants both).  n_samples >= 1 and first_sample + n_samples <= 2^32 - 1.  Everything else — flags = 0, f64, errors, the _device form (DEVICE
+ * pointers: d_guide 16-byte aligned, d_albedo_sum 8-byte and may be NULL; it only enqueues on hip_stream and never waits or allocates; a
+ * buffer that is too small is an error and nothing is launched), rt_last_query_ms, rt_last_query_launch — is as for rt_query_camera_albedo*.
+ * rt_guide_from_hits_host: the specification on the host, no GPU: hits = n_samples x n_px x 16 doubles (sample-major: the stacked outputs
+ * of rt_query_camera), guide_out = n_px x 16.  Errors: null arguments, n_samples = 0.
+ * Not done: a coverage or depth-spread stop inside the filters (they read words [0]-[7] and [11] only), following specular chains, f32,
+ * rt_render_multi. */
+int rt_query_camera_guide(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
+                          uint64_t seed, uint32_t flags, double* guide_out, double* albedo_sum_out);
+int rt_query_camera_guide_device(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
+                                 uint64_t seed, uint32_t flags, void* d_guide, size_t d_guide_bytes,
+                                 void* d_albedo_sum, size_t d_albedo_sum_bytes, void* hip_stream);
+int rt_guide_from_hits_host(const double* hits, uint32_t n_samples, uint64_t n_px, double* guide_out);
+/* A progressive frame's denoising guide: guide_samples = 1 (the default) is rt_query_camera(sample 0, the frame's seed); n > 1 is
+ * rt_query_camera_guide(first_sample 0, n, the frame's seed).  Setting another value drops the packed guide; the next denoised resolve of any
+ * kind builds it (rt_query_camera_guide_device on the frame's device; rt_last_query_ms reports that launch then) and keeps it until
+ * rt_progressive_reset or another value.  n = 0 is an error.  rt_progressive_guide_info: the value in force and how many guides the frame
+ * has built so far.  The frame's albedo sums are built as before, by their own launch. */
+int rt_progressive_set_guide_samples(void* frame, uint32_t n_samples);
+int rt_progressive_guide_info(void* frame, uint32_t* guide_samples_out, uint64_t* builds_out);
+
 /* What a material handle stands for (host only, no GPU): kind_texture_out[0] = the kind (0 Lambertian, 1 Metal, 2 Dielectric, 3 DiffuseLight,
  * 4 Isotropic, 5 PBR), [1] = its texture handle (-1 for Metal and Dielectric); albedo_out = Metal's albedo (0 otherwise).  A bad handle is an error. */
 int rt_material_info(rt_scene*, int material, int32_t kind_texture_out[2], double albedo_out[3]);
@@ -480,11 +519,13 @@ int rt_query_radiance_device(rt_scene*, uint32_t n, const void* d_rays, const do
  *      hit distance: sigma_p has no scene scale) and a hit / material key.  The filter is an exact f64 specification (csrc/rt_denoise.h: only
  *      + - * / and comparisons, a fixed order) that the HIP kernels (csrc/rt_denoise.hip) and the host twin below satisfy bit for bit.
  * rgb_sum: W*H*3 doubles in output order, as rt_render returns them; samples >= 1: how many samples they hold; hits: W*H records of 16 doubles,
- * as rt_query_camera returns them; iterations: 1 .. 8; sigma = {sigma_c, sigma_n, sigma_p}: each > 0, +inf switches that stop off (0, negative
+ * as rt_query_camera returns them or — here and for every `hits` / `d_hits` parameter of the denoise family below — the averaged records of
+ * rt_query_camera_guide (the filters read hit, t, position, normal and material only); iterations: 1 .. 8; sigma = {sigma_c, sigma_n, sigma_p}: each > 0, +inf switches that stop off (0, negative
  * and NaN are errors); flags: RT_DENOISE_SAME_MATERIAL or 0.  rgb_sum_out: W*H*3 doubles, the filtered frame in SUM units again (mean times
  * samples), so that rt_write_ppm, rt_format_color and the resolve apply to it unchanged; it may be rgb_sum itself.  W, H >= 1, W*H <= 2^31 - 1.
  * Non-finite input pixels are left out as neighbours and, as centres, take their neighbours' values: the filter repairs NaN pixels.
- * Not done: guides beyond sample 0's camera ray (no averaging over the lens or the pixel).  Textured surfaces: this filter sees a texture as
+ * Guides beyond sample 0's camera ray — averaged over the lens, the shutter and the pixel — are rt_query_camera_guide's records; not done: a
+ * coverage or depth-spread stop that would read their word [15].  Textured surfaces: this filter sees a texture as
  * colour and only sigma_c protects it — use the albedo-demodulated forms below (rt_denoise_albedo*).  Errors (non-zero, a message for rt_last_error, nothing written): null arguments and everything outside the ranges above. */
 enum { RT_DENOISE_SAME_MATERIAL = 1 /* pixels are neighbours only if their hits have the same material handle (default: only hit beside hit, miss beside miss) */ };
 /* The host twin: the specification as plain C++; needs no device. */
@@ -501,8 +542,9 @@ size_t rt_denoise_workspace_bytes(uint32_t W, uint32_t H);
 int rt_denoise_device(const void* d_rgb_sum, uint64_t samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
                       const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, void* hip_stream);
 /* A progressive frame's sums as they are now, filtered and resolved on the device: rgb8_out receives W*H*3 bytes, format_color of the
- * filtered sums — byte for byte rt_format_color of rt_denoise_host(rt_progressive_read_sum, rt_progressive_samples, rt_query_camera(sample 0,
- * the frame's seed)).  The frame builds the packed guide itself at the first call (rt_query_camera_device on its device; what rt_last_query_ms
+ * filtered sums — byte for byte rt_format_color of rt_denoise_host(rt_progressive_read_sum, rt_progressive_samples, the frame's guide):
+ * rt_query_camera(sample 0, the frame's seed), or the averaged record rt_progressive_set_guide_samples asked for.  The frame builds the packed
+ * guide itself at the first call (rt_query_camera_device or rt_query_camera_guide_device on its device; what rt_last_query_ms
  * reports for the scene is that launch then) and keeps it until rt_progressive_reset; another `flags` than the guide was keyed for rebuilds it.
  * Everything happens in buffers of the frame's own, allocated at the first call (155 bytes per pixel) and freed by rt_progressive_destroy:
  * the accumulated sums, the images of rt_progressive_resolve_rgb8* and its changed-pixel count are untouched, and the two kinds of resolve may
@@ -528,8 +570,8 @@ int rt_denoise_albedo_device(const void* d_rgb_sum, uint64_t samples, const void
                              uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3], uint32_t flags, void* d_rgb_sum_out,
                              void* d_workspace, size_t workspace_bytes, void* hip_stream);
 /* rt_progressive_resolve_denoised_rgb8 with demodulation: byte for byte rt_format_color of rt_denoise_albedo_host(rt_progressive_read_sum,
- * rt_progressive_samples, rt_query_camera_albedo(first_sample 0, albedo_samples, the frame's seed), albedo_samples, rt_query_camera(sample 0,
- * the frame's seed)).  The frame builds its albedo sums itself (rt_query_camera_albedo_device on its device; rt_last_query_ms reports that
+ * rt_progressive_samples, rt_query_camera_albedo(first_sample 0, albedo_samples, the frame's seed), albedo_samples, the frame's guide
+ * (rt_progressive_set_guide_samples)).  The frame builds its albedo sums itself (rt_query_camera_albedo_device on its device; rt_last_query_ms reports that
  * launch then) and keeps them beside the guide until rt_progressive_reset or until another albedo_samples is asked for (48 more bytes per
  * pixel).  The accumulated sums and what the other two resolves own are untouched; the three may be interleaved freely.
  * rt_progressive_albedo_info: the albedo_samples the frame holds sums for (0: none) and how many times it has built them. */
@@ -561,7 +603,7 @@ int rt_denoise_variance_device(const void* d_rgb_sum, uint64_t samples, const vo
                                void* d_workspace, size_t workspace_bytes, void* hip_stream);
 /* rt_progressive_resolve_denoised_rgb8 with the frame's own variance: byte for byte rt_format_color of rt_denoise_variance_host(
  * rt_progressive_read_sum, rt_progressive_samples, rt_moments_variance_host(the sums, rt_progressive_read_moments, samples, passes),
- * rt_query_camera(sample 0, the frame's seed)).  The variance, the filter and the resolve run on the device; the guide is the one the frame
+ * the frame's guide (rt_progressive_set_guide_samples)).  The variance, the filter and the resolve run on the device; the guide is the one the frame
  * packs once for all its denoised resolves.  The accumulated sums, the second moments, the pass count and what the other resolves own are
  * untouched.  Errors: those of rt_progressive_resolve_denoised_rgb8, and a frame without moments, with invalid moments or with fewer than
  * two passes. */
@@ -606,7 +648,7 @@ int rt_progressive_variance_counts(void* frame, double* var_out);
 /* The denoised resolve of any progressive frame, adaptive frames with differing counts included: byte for byte the resolve of
  * rt_denoise_frame_host(rt_progressive_read_sum, the frame's counts or its sample count, stop = RT_DENOISE_STOP_VARIANCE ?
  * rt_progressive_variance_counts : NULL, albedo_samples ? the albedo sums of rt_progressive_resolve_denoised_albedo_rgb8 : NULL,
- * rt_query_camera(sample 0, the frame's seed)) — rt_format_color with the frame's sample count, or rt_adaptive_resolve_rgb8_host with its
+ * the frame's guide (rt_progressive_set_guide_samples)) — rt_format_color with the frame's sample count, or rt_adaptive_resolve_rgb8_host with its
  * counts on an adaptive frame.  On a frame without counts the three modes that have a predecessor give that predecessor's bytes.  The
  * sums, moments, counts, what the other resolves own and rt_progressive_albedo_info's behaviour are untouched.  Errors: those of
  * rt_progressive_resolve_denoised_rgb8; an unknown stop; the variance stop on a frame without (valid) moments, or — a frame without

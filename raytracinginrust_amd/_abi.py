@@ -148,6 +148,12 @@ SIGNATURES = {
     "query_albedo_device": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _ptr, C.c_size_t, _ptr, C.c_size_t, _ptr]),
     "query_camera_albedo": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u32, _u64, _u32, _ptr]),
     "query_camera_albedo_device": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u32, _u64, _u32, _ptr, C.c_size_t, _ptr]),
+    # averaged denoising guides
+    "query_camera_guide": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u32, _u64, _u32, _ptr, _ptr]),
+    "query_camera_guide_device": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u32, _u64, _u32, _ptr, C.c_size_t, _ptr, C.c_size_t, _ptr]),
+    "guide_from_hits_host": (_int, [_ptr, _u32, _u64, _ptr]),
+    "progressive_set_guide_samples": (_int, [_ptr, _u32]),
+    "progressive_guide_info": (_int, [_ptr, c_u32_p, c_u64_p]),
     "material_info": (_int, [_ptr, _int, C.POINTER(C.c_int32), c_double_p]),
     # denoising
     "denoise_host": (_int, [_ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr]),

@@ -22,6 +22,8 @@
 #include "rt_denoise.h"
 #define RT_ALBEDO_QUERIES
 #include "rt_albedo.h"
+#define RT_GUIDE_QUERIES
+#include "rt_guide.h"
 #include "rt_moments.h"
 #include "rt_denoise_var.h"
 #include "rt_adaptive.h"
@@ -56,6 +58,9 @@ struct Progressive {
     // 0's camera hits of this view, keyed for guide_flags — is built once and kept until rt_progressive_reset.
     void* d_dn_ws = nullptr; void* d_dn_sum = nullptr; void* d_dn_rgb8 = nullptr; void* d_dn_changed = nullptr;
     bool guide_valid = false; uint32_t guide_flags = 0;
+    // rt_progressive_set_guide_samples: 1 is the guide above; n > 1 builds it from samples [0, n) of this view under the frame's seed instead
+    // (rt_query_camera_guide_device, rt_guide.h).  guide_builds counts the guides built, of either kind.
+    uint32_t guide_samples = 1; uint64_t guide_builds = 0;
     // rt_progressive_resolve_denoised_albedo_rgb8's own, beside the above: the albedo sums of samples [0, albedo_samples) of this view under
     // the frame's seed (rt_query_camera_albedo_device), built when first asked for and kept until rt_progressive_reset or another
     // albedo_samples, and the demodulated frame of a run (24 + 24 bytes per pixel).  albedo_builds counts the launches that built d_alb_sum.
@@ -1758,6 +1763,38 @@ int rt_query_camera_albedo(rt_scene* sc, const rt_camera* cam, uint32_t W, uint3
     return 0;
 }
 
+// ---------------------------------------------------------------- averaged guides (csrc/rt_guide.h: the definition; rt_guide.hip: the kernel)
+int rt_query_camera_guide_device(rt_scene* sc, const rt_camera* cam, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
+                                 uint64_t seed, uint32_t flags, void* d_guide, size_t d_guide_bytes, void* d_albedo_sum, size_t d_albedo_sum_bytes,
+                                 void* hip_stream) {
+    if (query_camera_albedo_args(sc, cam, d_guide, W, H, first_sample, n_samples, flags)) return -1;
+    const uint32_t n = W * H;
+    if (d_guide_bytes < (size_t)n * GUIDE_DOUBLES * sizeof(double)) return set_err("guide buffer too small for W * H * 16 doubles (128 bytes per pixel)");
+    if (query_aligned(d_guide, "d_guide")) return -1;
+    if (d_albedo_sum && d_albedo_sum_bytes < (size_t)n * 3u * sizeof(double)) return set_err("albedo buffer too small for W * H * 3 doubles (24 bytes per pixel)");
+    if (((uintptr_t)d_albedo_sum & 7u) != 0u) return set_err("d_albedo_sum must be 8-byte aligned");
+    if (need_device_and_flat(sc->s)) return -1;
+    GuideArgs A; A.guide = (double*)d_guide; A.albedo = (double*)d_albedo_sum; A.n = n; A.first_sample = first_sample; A.n_samples = n_samples;
+    A.t_min = 0.00001; A.seed = seed;
+    return query_launch_as(sc->s, cam, W, H, seed, n, "guide-query",
+                           [&](uint32_t feats, bool, size_t lds) { return guide_blocks_per_cu(feats, A.albedo != nullptr, lds); },
+                           [&](const KParams<double>& P, uint32_t feats, bool, uint32_t n_blocks, size_t shmem, hipStream_t st) {
+                               return launch_guide(P, A, feats, n_blocks, shmem, st); }, (hipStream_t)hip_stream);
+}
+int rt_query_camera_guide(rt_scene* sc, const rt_camera* cam, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
+                          uint64_t seed, uint32_t flags, double* guide_out, double* albedo_sum_out) {
+    if (query_camera_albedo_args(sc, cam, guide_out, W, H, first_sample, n_samples, flags)) return -1;
+    if (need_device_and_flat(sc->s)) return -1;
+    const size_t guide_bytes = (size_t)W * H * GUIDE_DOUBLES * sizeof(double), alb_bytes = (size_t)W * H * 3u * sizeof(double);
+    DeviceBuffer d_guide, d_alb;
+    HIP_OK(d_guide.alloc(guide_bytes));
+    if (albedo_sum_out) HIP_OK(d_alb.alloc(alb_bytes));
+    if (rt_query_camera_guide_device(sc, cam, W, H, first_sample, n_samples, seed, flags, d_guide.get(), guide_bytes, d_alb.get(), alb_bytes, nullptr)) return -1;
+    HIP_OK(hipMemcpy(guide_out, d_guide.get(), guide_bytes, hipMemcpyDeviceToHost));    // (waits for the kernel: the null stream)
+    if (albedo_sum_out) HIP_OK(hipMemcpy(albedo_sum_out, d_alb.get(), alb_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // ---------------------------------------------------------------- radiance queries
 // ray_color(r, background, world, lights, depth) (main.rs:41-120) for rays the caller chooses (csrc/rt_radiance.hip): the frames' bounce loop
 // behind the caller's rays instead of Camera::get_ray.
@@ -2510,8 +2547,9 @@ int rt_debug_denoise_ms(const void* d_rgb_sum, uint64_t samples, const void* d_h
     for (uint32_t k = 0; k < n_marks; k++) if (marks[k]) (void)hipEventDestroy(marks[k]);
     return rc;
 }
-// What both denoised resolves do before they filter: the checks, the frame's own buffers, and the packed guide — sample 0's camera hits of
-// this view, keyed for `flags` — in its place in the workspace.
+// What every denoised resolve does before it filters: the checks, the frame's own buffers, and the packed guide — sample 0's camera hits of
+// this view or, with guide_samples > 1, the averaged record of samples [0, guide_samples) (rt_guide.h), keyed for `flags` — in its place in
+// the workspace.
 static int progressive_denoise_prepare(Progressive* p, uint32_t iterations, const double sigma[3], uint32_t flags) {
     const std::string problem = denoise_check(p->done ? p->done : 1u, p->W, p->H, iterations, sigma, flags);
     if (!problem.empty()) return set_err(problem);
@@ -2526,16 +2564,30 @@ static int progressive_denoise_prepare(Progressive* p, uint32_t iterations, cons
     if (!p->d_dn_sum) HIP_OK(hipMalloc(&p->d_dn_sum, n * 3 * sizeof(double)));
     if (!p->d_dn_rgb8) HIP_OK(hipMalloc(&p->d_dn_rgb8, n * 3));
     if (!p->d_dn_changed) HIP_OK(hipMalloc(&p->d_dn_changed, sizeof(unsigned long long)));
-    if (!p->guide_valid || p->guide_flags != flags) {           // sample 0's camera hits of this view, packed; the records themselves are not kept
+    if (!p->guide_valid || p->guide_flags != flags) {           // the guide's records of this view, packed; the records themselves are not kept
         const size_t hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
         DeviceBuffer d_hits;
         HIP_OK(d_hits.alloc(hit_bytes));
         p->guide_valid = false;
-        if (rt_query_camera_device(p->sc, &p->cam, p->W, p->H, 0u, p->seed, 0u, nullptr, d_hits.get(), hit_bytes, nullptr)) return -1;
+        if (p->guide_samples == 1u) { if (rt_query_camera_device(p->sc, &p->cam, p->W, p->H, 0u, p->seed, 0u, nullptr, d_hits.get(), hit_bytes, nullptr)) return -1; }
+        else if (rt_query_camera_guide_device(p->sc, &p->cam, p->W, p->H, 0u, p->guide_samples, p->seed, 0u, d_hits.get(), hit_bytes, nullptr, 0u, nullptr)) return -1;
         HIP_OK((hipError_t)launch_denoise_pack(nullptr, 1u, (const double*)d_hits.get(), flags, nullptr, (double*)p->d_dn_ws + 2u * n * DENOISE_COLOR_DOUBLES, (uint32_t)n, nullptr));
         HIP_OK(hipStreamSynchronize(nullptr));
-        p->guide_valid = true; p->guide_flags = flags;
+        p->guide_valid = true; p->guide_flags = flags; p->guide_builds++;
     }
+    return 0;
+}
+int rt_progressive_set_guide_samples(void* frame, uint32_t n_samples) {
+    Progressive* p = (Progressive*)frame;
+    if (!p) return set_err("null argument");
+    if (n_samples == 0u) return set_err("guide_samples must be >= 1 (1: the camera hits of sample 0; n: the averaged record of samples 0 .. n - 1)");
+    if (n_samples != p->guide_samples) { p->guide_samples = n_samples; p->guide_valid = false; }
+    return 0;
+}
+int rt_progressive_guide_info(void* frame, uint32_t* guide_samples_out, uint64_t* builds_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !guide_samples_out || !builds_out) return set_err("null argument");
+    *guide_samples_out = p->guide_samples; *builds_out = p->guide_builds;
     return 0;
 }
 // ... and after: the filtered sums in d_dn_sum resolved and copied out

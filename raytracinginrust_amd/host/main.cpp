@@ -6,12 +6,15 @@
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
 //              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material|albedo FILE] [--panorama FILE]
 //              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] [--denoise-albedo N] [--denoise-variance SIGMA_V] [--until-error TAU] [--max-samples M] [--aov error FILE]
-//              [--adaptive] [--aov samples FILE] > image.ppm
+//              [--adaptive] [--aov samples FILE] [--denoise-guide N] [--aov coverage FILE] > image.ppm
 //
 // --denoise K[,c,n,p] (opt-in): the frame through the edge-avoiding a-trous filter before it is written (rt_denoise: K iterations, guided by
-// sample 0's camera hits of this --seed); with --progressive the frame resolves itself denoised on the device (rt_progressive_resolve_denoised_rgb8).
+// sample 0's camera hits of this --seed, or --denoise-guide's record); with --progressive the frame resolves itself denoised on the device (rt_progressive_resolve_denoised_rgb8).
 // --denoise-albedo N (with --denoise): the filter runs on the frame divided by its first-hit albedo — the mean over samples [0, N) of this --seed,
 // rt_query_camera_albedo — and the result is multiplied back (rt_denoise_albedo*): what a textured scene needs.
+// --denoise-guide N (with --denoise): the filter is guided by the averaged first-hit record of samples [0, N) of this --seed
+// (rt_query_camera_guide: what the lens, the shutter and the pixel's area see) instead of sample 0's; with --progressive the frame builds it
+// (rt_progressive_set_guide_samples).  --aov coverage FILE: that record's hit count / N as a grey image.
 // --denoise-variance SIGMA_V (with --progressive N and --denoise K): the colour stop is SIGMA_V standard deviations of the frame's own
 // per-pixel variance instead of SIGMA_C (rt_progressive_resolve_denoised_variance_rgb8); the frame keeps moments and needs at least two passes.
 // With --denoise-albedo as well, and on an --adaptive frame with any of the three, the frame is denoised as it is — per-pixel counts, its
@@ -251,6 +254,8 @@ static const char* AOV_HELP =
     "      material  grey, the hit's material handle mod 256 (a miss or a ConstantMedium hit, handle -1: 255)\n"
     "      albedo    r g b = the first hit's albedo held to [0, 1], times 255.999, truncated (no gamma); the mean over the samples [0, N) of\n"
     "                --denoise-albedo N when that is given, else sample 0's (a miss, glass and emitters: 255 255 255)\n"
+    "      coverage  grey, the fraction of the samples [0, N) of --denoise-guide N (default 1) whose camera ray hits anything: hits / N * 255.999\n"
+    "                truncated (rt_query_camera_guide's word 15)\n"
     "      error     (with --progressive N, written BESIDE the image when the frame ends) grey, the estimated standard error of the pixel in\n"
     "                display units: sqrt(e2) * 256 * 8 truncated, held to 255 — one code value of standard error is grey 8; not finite: 255\n"
     "      samples   (with --adaptive, written BESIDE the image when the frame ends) grey, the samples the pixel holds: 255 * n / the largest n, truncated\n";
@@ -263,6 +268,11 @@ static void write_albedo_aov(const std::string& path, const std::vector<double>&
         const double a = albedo_sum[i] / (double)n_samples;
         img[i] = (uint8_t)aov_level((a >= 0.0 ? (a > 1.0 ? 1.0 : a) : 0.0) * 255.999);
     }
+    write_ppm_rgb8(path.c_str(), img, W, H);
+}
+static void write_coverage_aov(const std::string& path, const std::vector<double>& guide, uint32_t n_samples, uint32_t W, uint32_t H) {
+    std::vector<uint8_t> img(guide.size() / 16u * 3u);
+    for (size_t p = 0; p < guide.size() / 16u; p++) img[p * 3] = img[p * 3 + 1] = img[p * 3 + 2] = (uint8_t)aov_level(guide[p * 16 + 15] / (double)n_samples * 255.999);
     write_ppm_rgb8(path.c_str(), img, W, H);
 }
 static void write_error_aov(const std::string& path, const std::vector<double>& e2, uint32_t W, uint32_t H) {
@@ -307,6 +317,7 @@ int main(int argc, char** argv) {
     std::string aov_kind, aov_path;                                         // --aov KIND FILE: a feature frame instead of the image
     std::string panorama_path;                                              // --panorama FILE: the equirectangular image around lookfrom instead
     bool want_denoise = false; DenoiseSettings dn;                          // --denoise K[,sigma_c,sigma_n,sigma_p]: filter the frame before it is written
+    uint32_t guide_samples = 0;                                             // --denoise-guide N: guide the filter by the averaged record of samples [0, N) (0: sample 0's)
     uint32_t albedo_samples = 0;                                            // --denoise-albedo N: demodulate by the albedo of samples [0, N) (0: the plain filter)
     double sigma_v = 0.0;                                                   // --denoise-variance SIGMA_V: the variance-guided colour stop (0: the plain filter)
     uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
@@ -337,7 +348,7 @@ int main(int argc, char** argv) {
         else if (a == "--progressive") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--progressive needs a pass size >= 1\n"); return 2; } progressive = (uint32_t)n; }
         else if (a == "--aov") {
             aov_kind = next(); aov_path = next();
-            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material" && aov_kind != "albedo" && aov_kind != "error" && aov_kind != "samples") { std::fprintf(stderr, "--aov needs normal, depth, material, albedo, error or samples\n%s", AOV_HELP); return 2; }
+            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material" && aov_kind != "albedo" && aov_kind != "error" && aov_kind != "samples" && aov_kind != "coverage") { std::fprintf(stderr, "--aov needs normal, depth, material, albedo, coverage, error or samples\n%s", AOV_HELP); return 2; }
         }
         else if (a == "--panorama") panorama_path = next();
         else if (a == "--until-error") { until_error = std::atof(next()); if (!(until_error >= 0.0)) { std::fprintf(stderr, "--until-error needs a standard error >= 0 in display units (0.00390625 is one code value)\n"); return 2; } }
@@ -351,14 +362,17 @@ int main(int argc, char** argv) {
             want_denoise = true; dn.iterations = k; dn.sigma[0] = c; dn.sigma[1] = n; dn.sigma[2] = p;
         }
         else if (a == "--denoise-albedo") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--denoise-albedo needs a sample count >= 1\n"); return 2; } albedo_samples = (uint32_t)n; }
+        else if (a == "--denoise-guide") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--denoise-guide needs a sample count >= 1\n"); return 2; } guide_samples = (uint32_t)n; }
         else if (a == "--denoise-variance") { sigma_v = std::atof(next()); if (!(sigma_v > 0.0)) { std::fprintf(stderr, "--denoise-variance needs a colour stop > 0 in standard deviations (inf switches it off)\n"); return 2; } }
         else if (a == "--help" || a == "-h") {
             std::printf("rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N]\n"
                         "         [--depth D] [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] > image.ppm\n%s"
                         "  --denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]  write the frame through K (1 .. 8) iterations of the edge-avoiding a-trous filter, guided by\n"
-                        "                                     the camera hits of sample 0 (default sigmas 4, 0.5, 0.02; inf switches a stop off); also with --progressive\n"
+                        "                                     the camera hits of sample 0 or of --denoise-guide N (default sigmas 4, 0.5, 0.02; inf switches a stop off); also with --progressive\n"
                         "  --denoise-albedo N                 with --denoise: filter the frame divided by its first-hit albedo (the mean over samples 0 .. N-1)\n"
                         "                                     and multiply back: textures are kept (textured scenes need it); also with --progressive\n"
+                        "  --denoise-guide N                  with --denoise: guide the filter by the averaged first-hit record of samples 0 .. N-1 (lens, shutter and\n"
+                        "                                     pixel area) instead of sample 0's; also with --progressive\n"
                         "  --denoise-variance SIGMA_V         with --progressive N and --denoise K: the colour stop in standard deviations of the frame's own\n"
                         "                                     per-pixel variance instead of SIGMA_C; needs at least two passes (--spp more than N);\n"
                         "                                     also with --denoise-albedo, and all three also with --adaptive\n"
@@ -379,6 +393,7 @@ int main(int argc, char** argv) {
     if (aov_kind == "samples" && !adaptive) { std::fprintf(stderr, "--aov samples goes with --adaptive\n"); return 2; }
     if (max_samples != 0u && until_error < 0.0) { std::fprintf(stderr, "--max-samples goes with --until-error TAU\n"); return 2; }
     if (albedo_samples != 0u && !want_denoise && aov_kind != "albedo") { std::fprintf(stderr, "--denoise-albedo goes with --denoise K (or --aov albedo)\n"); return 2; }
+    if (guide_samples != 0u && !want_denoise && aov_kind != "coverage") { std::fprintf(stderr, "--denoise-guide goes with --denoise K (or --aov coverage)\n"); return 2; }
     if (sigma_v != 0.0 && (!want_denoise || progressive == 0u)) { std::fprintf(stderr, "--denoise-variance goes with --progressive N and --denoise K\n"); return 2; }
     const double aspect_ratio = (double)image_width / (double)image_height;
     try {
@@ -449,6 +464,9 @@ int main(int argc, char** argv) {
             if (aov_kind == "albedo") {
                 const uint32_t n = albedo_samples ? albedo_samples : 1u;
                 write_albedo_aov(aov_path, query_camera_albedo(s, camera, image_width, image_height, 0u, n, seed), n, image_width, image_height);
+            } else if (aov_kind == "coverage") {
+                const uint32_t n = guide_samples ? guide_samples : 1u;
+                write_coverage_aov(aov_path, query_camera_guide(s, camera, image_width, image_height, 0u, n, seed), n, image_width, image_height);
             } else
             write_aov(aov_kind, aov_path, query_camera(s, camera, image_width, image_height, 0u, seed), image_width, image_height);
             std::fprintf(stderr, "Done.\n");
@@ -470,6 +488,7 @@ int main(int argc, char** argv) {
             Progressive frame(s, camera, background, image_width, image_height, max_depth, seed, flags);
             const bool want_moments = until_error >= 0.0 || aov_kind == "error" || sigma_v != 0.0;
             if (want_moments) frame.enable_moments();
+            if (guide_samples) frame.set_guide_samples(guide_samples);
             const uint32_t limit = until_error >= 0.0 && max_samples ? max_samples : samples_per_pixel;
             if (adaptive) {
                 frame.enable_adaptive();
@@ -527,10 +546,13 @@ int main(int argc, char** argv) {
             double ms[4]; rt_last_multi_ms(s.raw(), ms);
             std::fprintf(stderr, "rt_render_multi: slowest kernel %.2f ms, gather %.3f ms, un-permute %.3f ms, call %.2f ms\n", ms[0], ms[1], ms[2], ms[3]);
         }
+        // the guide: sample 0's records, or the averaged records of samples [0, --denoise-guide N)
+        auto guide_records = [&]() { return guide_samples > 1u ? query_camera_guide(s, camera, image_width, image_height, 0u, guide_samples, seed)
+                                                               : query_camera_records(s, camera, image_width, image_height, 0u, seed); };
         if (want_denoise && albedo_samples)
             pixel_sums = denoise_albedo(pixel_sums, samples_per_pixel, query_camera_albedo(s, camera, image_width, image_height, 0u, albedo_samples, seed), albedo_samples,
-                                        query_camera_records(s, camera, image_width, image_height, 0u, seed), image_width, image_height, dn);
-        else if (want_denoise) pixel_sums = denoise(pixel_sums, samples_per_pixel, query_camera_records(s, camera, image_width, image_height, 0u, seed), image_width, image_height, dn);
+                                        guide_records(), image_width, image_height, dn);
+        else if (want_denoise) pixel_sums = denoise(pixel_sums, samples_per_pixel, guide_records(), image_width, image_height, dn);
         write_ppm("-", pixel_sums, image_width, image_height, samples_per_pixel);              // main.rs:767-769,832
         std::fprintf(stderr, "Done.\n");                                                      // main.rs:835
     } catch (const Error& e) {

@@ -423,7 +423,7 @@ class Progressive:
     """
 
     def __init__(self, b: SceneBuilder, cam: CameraParams, background, W: int, H: int, max_depth: int, seed: int = 0x5EED, flags: int = RT_F64,
-                 moments: bool = False, adaptive: bool = False):
+                 moments: bool = False, adaptive: bool = False, guide_samples: int = 1):
         self._lib = _rt()
         self.W, self.H = int(W), int(H)
         bg = (C.c_double * 3)(*[float(x) for x in background])
@@ -437,6 +437,19 @@ class Progressive:
             self.enable_moments()
         if adaptive:
             self.enable_adaptive()
+        if guide_samples != 1:
+            self.set_guide_samples(guide_samples)
+
+    def set_guide_samples(self, n: int) -> None:
+        """rt_progressive_set_guide_samples: the guide of every denoised resolve — 1 (the default): the camera hits of sample 0; n > 1: the
+        averaged record of samples [0, n) (`query_camera_guide`).  Another value drops the packed guide; the next denoised resolve builds it."""
+        _check(self._lib.rt_progressive_set_guide_samples(self._h, int(n)))
+
+    def guide_info(self):
+        """(the guide_samples in force, how many guides the frame has built so far)."""
+        n, builds = C.c_uint32(), C.c_uint64()
+        _check(self._lib.rt_progressive_guide_info(self._h, C.byref(n), C.byref(builds)))
+        return int(n.value), int(builds.value)
 
     def enable_adaptive(self) -> None:
         """rt_progressive_enable_adaptive: per-pixel sample counts on a frame with moments, only while it holds 0 samples (csrc/rt_adaptive.h)."""
@@ -557,8 +570,8 @@ class Progressive:
 
     def rgb8_denoised(self, iterations: int = None, sigma=None, flags: int = 0) -> np.ndarray:
         """rt_progressive_resolve_denoised_rgb8: the frame's sums as they are now through the edge-avoiding a-trous filter (`denoise`) and
-        format_color, all on the device -> (H, W, 3) uint8.  The frame builds its guide (sample 0's camera hits) at the first call and keeps
-        it until reset; `sum`, `rgb8` and its changed-pixel count are untouched."""
+        format_color, all on the device -> (H, W, 3) uint8.  The frame builds its guide (sample 0's camera hits, or the averaged record of
+        `set_guide_samples`) at the first call and keeps it until reset; `sum`, `rgb8` and its changed-pixel count are untouched."""
         out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
         k, sg = _denoise_settings(iterations, sigma)
         _check(self._lib.rt_progressive_resolve_denoised_rgb8(self._h, k, sg, flags, out.ctypes.data))
@@ -936,6 +949,49 @@ def query_camera_albedo_device(b: SceneBuilder, cam: CameraParams, W: int, H: in
     if nbytes is None:
         raise ValueError("d_albedo_sum_bytes is needed with a raw pointer")
     _check(_rt().rt_query_camera_albedo_device(b.h, C.byref(cam), W, H, first_sample, n_samples, seed, 0, C.c_void_p(ptr), nbytes, C.c_void_p(stream)))
+
+
+# ---- averaged denoising guides (rt_query_camera_guide*, rt_guide_from_hits_host): csrc/rt_guide.h
+# the guide record's 16 doubles by name: HIT_FIELDS (t, position, normal, front_face are means over the hitting samples, u, v, prim_kind and
+# prim_index carry nothing) and the coverage count in the last word
+GUIDE_FIELDS = dict(HIT_FIELDS, hits=slice(15, 16))
+
+
+def query_camera_guide(b: SceneBuilder, cam: CameraParams, W: int, H: int, first_sample: int = 0, n_samples: int = 16,
+                       seed: int = DEFAULT_SEED, want_albedo: bool = False):
+    """rt_query_camera_guide: per pixel the first-hit records of samples [first_sample, first_sample + n_samples) reduced to one record
+    every denoiser takes as `hits` -> (H, W, 16) (GUIDE_FIELDS); with want_albedo also (H, W, 3), the words `query_camera_albedo` gives for
+    the same samples, from the same searches."""
+    out = np.zeros((H, W, HIT_DOUBLES), dtype=np.float64)
+    alb = np.zeros((H, W, 3), dtype=np.float64) if want_albedo else None
+    _check(_rt().rt_query_camera_guide(b.h, C.byref(cam), W, H, first_sample, n_samples, seed, 0, out.ctypes.data,
+                                       alb.ctypes.data if want_albedo else None))
+    return (out, alb) if want_albedo else out
+
+
+def query_camera_guide_device(b: SceneBuilder, cam: CameraParams, W: int, H: int, d_guide, d_albedo_sum=None, first_sample: int = 0,
+                              n_samples: int = 16, seed: int = DEFAULT_SEED, stream: int = 0, d_guide_bytes=None, d_albedo_sum_bytes=None) -> None:
+    """rt_query_camera_guide_device: the W*H*16 records (and, with d_albedo_sum, the W*H*3 albedo sums) into device memory (torch tensors of
+    f64, or raw pointers with their sizes), enqueued on `stream`; never waits."""
+    g_ptr, gbytes = _device_buffer(d_guide)
+    gbytes = gbytes if d_guide_bytes is None else int(d_guide_bytes)
+    a_ptr, abytes = _device_buffer(d_albedo_sum) if d_albedo_sum is not None else (None, 0)
+    abytes = abytes if d_albedo_sum_bytes is None else int(d_albedo_sum_bytes)
+    if gbytes is None or abytes is None:
+        raise ValueError("d_guide_bytes / d_albedo_sum_bytes are needed with raw pointers")
+    _check(_rt().rt_query_camera_guide_device(b.h, C.byref(cam), W, H, first_sample, n_samples, seed, 0, C.c_void_p(g_ptr), gbytes,
+                                              C.c_void_p(a_ptr), abytes, C.c_void_p(stream)))
+
+
+def guide_from_hits(hits) -> np.ndarray:
+    """rt_guide_from_hits_host (no GPU): the guide's specification as plain C++ on stacked records, (n_samples, H, W, 16) or
+    (n_samples, n, 16) as n_samples calls of `query_camera` / `query_hits` return them -> (H, W, 16) or (n, 16)."""
+    h = np.ascontiguousarray(hits, dtype=np.float64)
+    if h.ndim not in (3, 4) or h.shape[-1] != HIT_DOUBLES:
+        raise ValueError(f"hits of shape {h.shape}: (n_samples, H, W, 16) or (n_samples, n, 16) is needed")
+    out = np.zeros(h.shape[1:], dtype=np.float64)
+    _check(_rt().rt_guide_from_hits_host(h.ctypes.data, h.shape[0], int(np.prod(h.shape[1:-1])), out.ctypes.data))
+    return out
 
 
 def material_info(b: SceneBuilder, material: int) -> dict:

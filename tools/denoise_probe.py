@@ -14,7 +14,12 @@ Part 4, `variance`: the variance-guided filter (rt_denoise_varianc
 run, as shipped and with RT_DENOISE_NO_LDS=1, and the variance kernel's; the whole denoised resolves of a progressive frame of C2's view
 beside one 64-sample pass; and the error table above with columns for the variance-guided filter, moments from 4 passes, plus the
 three-texture scene of §15.
+Part 5, `guide`: the averaged guide (rt_query_camera_guide*) — the error rows of parts 2 and of tools/denoise_frame_probe.py's
+random spheres with a line per row for a guide of GUIDE_SAMPLES samples beside sample 0's; the 40 x 40 thin-lens scene of
+tests/guide_cases.py on three seeds; and the kernel time of rt_query_camera_guide_device without and with its albedo output at 1, 16 and 64
+samples beside rt_query_camera_albedo_device and, for one sample, rt_query_camera_device, from the same run.
 usage: python tools/denoise_probe.py [timing] [errors] > profiles/denoise.log
+       python tools/denoise_probe.py guide > profiles/denoise_guide.log      (guide-cost: the kernel times alone)
        python tools/denoise_probe.py albedo errors > profiles/denoise_albedo.log
        python tools/denoise_probe.py variance > profiles/denoise_variance.log"""
 import ctypes as C
@@ -294,6 +299,138 @@ def variance():
     _variance_errors()
 
 
+GUIDE_SAMPLES = 16
+
+
+def _guide_errors():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import build_scene
+    from denoise_cases import clipped_mse
+    be = _lib.load()
+    earth = scenes.load_earthmap()
+    depth, truth_spp = 20, 4096
+    print(f"# clipped MSE against {truth_spp} spp (seed 99), depth {depth}, sigma = {R.DENOISE_SIGMA}, flags 0: raw, then K = 1 .. 5 (ratio to raw); part 2's rows,")
+    print(f"# each with the guide of sample 0 (rt_query_camera) and with the averaged guide of samples 0 .. {GUIDE_SAMPLES - 1} (rt_query_camera_guide); the albedo")
+    print(f"# of samples 0 .. {ALBEDO_SAMPLES - 1} comes from the same launch as the averaged guide")
+    for name, (W, H) in (("cornell", (100, 100)), ("random", (160, 90)), ("final", (100, 100)), ("teapot", (160, 90))):
+        b, cam, bg = build_scene(name, be, earth)
+        truth = R.render(b, cam, bg, W, H, truth_spp, depth, 99)
+        hits = R.query_camera(b, cam, W, H, 0, 7)
+        guide, alb = R.query_camera_guide(b, cam, W, H, 0, GUIDE_SAMPLES, 7, want_albedo=True)
+        cov = guide[..., 15]
+        print(f"# {name} {W}x{H}: {int(((cov > 0) & (cov < GUIDE_SAMPLES)).sum())} pixels partly covered, {int(((guide[..., 11] == -1.0) & (cov >= 2) & (hits[..., 11] != -1.0)).sum())} "
+              f"with mixed materials, {int((guide[..., 0] != hits[..., 0]).sum())} whose hit flag differs from sample 0's")
+        for spp in (16, 64):
+            noisy = R.render(b, cam, bg, W, H, spp, depth, 7)
+            raw = clipped_mse(noisy, spp, truth, truth_spp)
+            for label, fn in (("plain", lambda g, k: R.denoise(noisy, spp, g, k, R.DENOISE_SIGMA, 0)),
+                              ("demod", lambda g, k: R.denoise_albedo(noisy, spp, alb, ALBEDO_SAMPLES, g, k, R.DENOISE_SIGMA, 0))):
+                for gname, g in (("guide = sample 0", hits), (f"guide = {GUIDE_SAMPLES} samples", guide)):
+                    row = []
+                    for k in range(1, 6):
+                        e = clipped_mse(fn(g, k), spp, truth, truth_spp)
+                        row.append(f"{e:.5f} ({e / raw:.2f})")
+                    print(f"{name} {W}x{H} {spp} spp  raw {raw:.5f}  {label}  {gname}  " + "  ".join(row), flush=True)
+
+
+def _guide_frame_errors():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import build_scene
+    be = _lib.load()
+    W = H = 40
+    truth_spp, depth = 2048, 20
+
+    def mse(rgb_sum, n):
+        mean = rgb_sum / (n if np.isscalar(n) else np.maximum(n, 1).astype(np.float64)[..., None])
+        return float(np.mean((np.clip(mean, 0.0, 1.0) - np.clip(truth / truth_spp, 0.0, 1.0)) ** 2))
+    print(f"# tools/denoise_frame_probe.py's random-spheres rows ({W}x{H}, depth {depth}, seed 7, truth {truth_spp} spp of seed 99, render.py's sigmas, albedo of 16")
+    print("# samples), ratio to raw: uniform 4 x 4: albedo only / variance only / variance with albedo; adaptive: colour stop / variance stop / variance with albedo")
+    b, cam, bg = build_scene("random", be, None)
+    truth = R.render(b, cam, bg, W, H, truth_spp, depth, 99)
+    hits = R.query_camera(b, cam, W, H, 0, 7)
+    guide, alb = R.query_camera_guide(b, cam, W, H, 0, GUIDE_SAMPLES, 7, want_albedo=True)
+    with R.Progressive(b, cam, bg, W, H, depth, 7, moments=True) as frame:
+        for _ in range(4):
+            frame.add(4)
+        S, N, V = frame.sum(), frame.samples, frame.variance()
+    raw = mse(S, N)
+    for gname, g in (("guide = sample 0", hits), (f"guide = {GUIDE_SAMPLES} samples", guide)):
+        for k in range(1, 6):
+            a = mse(R.denoise_albedo(S, N, alb, 16, g, k, R.DENOISE_SIGMA), N)
+            v = mse(R.denoise_variance(S, N, V, g, k, R.DENOISE_VARIANCE_SIGMA), N)
+            both = mse(R.denoise_frame(S, g, None, N, V, alb, 16, k, R.DENOISE_VARIANCE_SIGMA), N)
+            print(f"random  uniform 4 x 4  {gname}  raw {raw:.6f}  K = {k}  {a / raw:.3f}  {v / raw:.3f}  {both / raw:.3f}", flush=True)
+    with R.Progressive(b, cam, bg, W, H, depth, 7, adaptive=True) as frame:
+        while frame.add_adaptive(4, 1.0 / 64.0, 64)["listed"]:
+            pass
+        S, (n, _), V = frame.sum(), frame.counts(), frame.variance_counts()
+    raw = mse(S, n)
+    for gname, g in (("guide = sample 0", hits), (f"guide = {GUIDE_SAMPLES} samples", guide)):
+        for k in range(1, 6):
+            c = mse(R.denoise_frame(S, g, n, 1, None, None, 1, k, R.DENOISE_SIGMA), n)
+            v = mse(R.denoise_frame(S, g, n, 1, V, None, 1, k, R.DENOISE_VARIANCE_SIGMA), n)
+            both = mse(R.denoise_frame(S, g, n, 1, V, alb, 16, k, R.DENOISE_VARIANCE_SIGMA), n)
+            print(f"random  adaptive tau 1/64 (mean {n.mean():.1f}, {n.min()} .. {n.max()} samples)  {gname}  raw {raw:.6f}  K = {k}  {c / raw:.3f}  {v / raw:.3f}  {both / raw:.3f}", flush=True)
+
+
+def _guide_lens_scene():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import guide_cases as G
+    from denoise_cases import clipped_mse
+    b, cam, bg = G.lens_quality_scene(_lib.load())
+    W, H = G.Q_W, G.Q_H
+    print(f"# the thin-lens scene of tests/guide_cases.py, {W}x{H}, {G.Q_SPP} spp against {G.Q_TRUTH_SPP} spp of another seed, depth {G.Q_DEPTH}, K = {G.Q_ITERATIONS}, sigma = {G.Q_SIGMA},")
+    print(f"# albedo of {G.Q_ALBEDO_SAMPLES} samples: clipped MSE raw / demodulated filter with sample 0's guide / with the guide of {G.Q_GUIDE_SAMPLES} samples, and the ratio of the last two")
+    for seed, truth_seed in G.Q_SEEDS:
+        noisy = R.render(b, cam, bg, W, H, G.Q_SPP, G.Q_DEPTH, seed)
+        truth = R.render(b, cam, bg, W, H, G.Q_TRUTH_SPP, G.Q_DEPTH, truth_seed)
+        hits = R.query_camera(b, cam, W, H, 0, seed)
+        guide, alb = R.query_camera_guide(b, cam, W, H, 0, G.Q_GUIDE_SAMPLES, seed, want_albedo=True)
+        raw = clipped_mse(noisy, G.Q_SPP, truth, G.Q_TRUTH_SPP)
+        e0 = clipped_mse(R.denoise_albedo(noisy, G.Q_SPP, alb, G.Q_ALBEDO_SAMPLES, hits, G.Q_ITERATIONS, G.Q_SIGMA, 0), G.Q_SPP, truth, G.Q_TRUTH_SPP)
+        e16 = clipped_mse(R.denoise_albedo(noisy, G.Q_SPP, alb, G.Q_ALBEDO_SAMPLES, guide, G.Q_ITERATIONS, G.Q_SIGMA, 0), G.Q_SPP, truth, G.Q_TRUTH_SPP)
+        print(f"lens scene  seed {seed}  raw {raw:.6f}  sample 0 {e0:.6f} ({e0 / raw:.3f})  {G.Q_GUIDE_SAMPLES} samples {e16:.6f} ({e16 / raw:.3f})  ratio {e16 / e0:.3f}", flush=True)
+
+
+def _guide_cost():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from conftest import build_scene
+    be = _lib.load()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    print(f"# rt_query_camera_guide_device without and with its albedo output, rt_query_camera_albedo_device and (one sample) rt_query_camera_device: kernel ms")
+    print(f"# (rt_last_query_ms: HIP events around the launch), warm, best of {REPS}, all from this run; Mrays/s = W H n_samples / ms; 'two launches' = guide + albedo query")
+    print("# scene frame  n_samples  guide ms (Mrays/s)  guide+albedo ms (Mrays/s)  albedo query ms (Mrays/s)  two launches ms  fused / two launches  camera query ms")
+    for name, (W, H) in (("cornell", (800, 800)), ("random", (1200, 675)), ("teapot", (1200, 675))):
+        b, cam, bg = build_scene(name, be, None)
+        d_guide = torch.empty((H, W, 16), dtype=torch.float64, device=dev)
+        d_alb = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
+
+        def best_of(call):
+            best = 1e30
+            for rep in range(REPS + 1):                           # the first run warms up (upload, code object)
+                call()
+                ms = R.last_query_ms(b)
+                if rep:
+                    best = min(best, ms)
+            return best
+        for n in (1, 16, 64):
+            g = best_of(lambda: R.query_camera_guide_device(b, cam, W, H, d_guide, None, 0, n, 7))
+            ga = best_of(lambda: R.query_camera_guide_device(b, cam, W, H, d_guide, d_alb, 0, n, 7))
+            a = best_of(lambda: R.query_camera_albedo_device(b, cam, W, H, d_alb, 0, n, 7))
+            q = best_of(lambda: R.query_camera_device(b, cam, W, H, d_guide, 0, 7)) if n == 1 else None
+            rate = lambda ms: W * H * n / ms / 1e3
+            print(f"{name} {W}x{H}  {n}  {g:.4f} ({rate(g):.0f})  {ga:.4f} ({rate(ga):.0f})  {a:.4f} ({rate(a):.0f})  {g + a:.4f}  {ga / (g + a):.3f}  "
+                  + (f"{q:.4f}" if q is not None else "-"), flush=True)
+        del d_guide, d_alb
+
+
+def guide():
+    _guide_cost()
+    _guide_lens_scene()
+    _guide_frame_errors()
+    _guide_errors()
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["timing", "errors"]
     if "timing" in what:
@@ -304,3 +441,7 @@ if __name__ == "__main__":
         variance()
     if "errors" in what:
         errors()
+    if "guide" in what:
+        guide()
+    if "guide-cost" in what:
+        _guide_cost()
