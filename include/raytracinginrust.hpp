@@ -390,6 +390,32 @@ inline std::vector<double> denoise_frame(const std::vector<double>& rgb_sum, con
     return out;
 }
 
+// Temporal accumulation (rt_reproject, csrc/rt_reproject.h): the previous view's frame — prev_sum with prev_counts (null: prev_samples in every
+// pixel) — reprojected into a new view, from the query_camera / query_camera_guide records of the two views.  History: W*H*3 sums and W*H
+// counts, 0 where a pixel has none.  The defaults are render.py's starting values, not tuned.  host = true: the plain-C++ twin, no device.
+struct ReprojectSettings { uint32_t max_history = 64; double sigma[2] = {0.9, 0.01}; };      // sigma = {normal_min, sigma_p}
+struct History { std::vector<double> sum; std::vector<uint32_t> counts; };
+inline History reproject(const std::vector<double>& prev_sum, const std::vector<uint32_t>* prev_counts, uint64_t prev_samples, const std::vector<double>& prev_records,
+                         const Camera& prev_cam, const std::vector<double>& cur_records, uint32_t W, uint32_t H, const ReprojectSettings& r = ReprojectSettings(),
+                         bool host = false) {
+    if (prev_sum.size() != (size_t)W * H * 3 || prev_records.size() != (size_t)W * H * 16 || cur_records.size() != prev_records.size() ||
+        (prev_counts && prev_counts->size() != (size_t)W * H)) throw Error("reproject: frame, counts or records of another size");
+    History h; h.sum.resize(prev_sum.size()); h.counts.resize((size_t)W * H);
+    if ((host ? rt_reproject_host : rt_reproject)(prev_sum.data(), prev_counts ? prev_counts->data() : nullptr, prev_samples, prev_records.data(), &prev_cam.c, cur_records.data(),
+                                                  W, H, r.max_history, r.sigma, 0, h.sum.data(), h.counts.data()) != 0) throw Error(rt_last_error());
+    return h;
+}
+// The blend of a frame with a history (rt_temporal_blend_host; no device): sums added, counts added — a frame with counts, which
+// denoise_frame(counts = ...) takes as it is.
+inline History temporal_blend(const std::vector<double>& rgb_sum, const std::vector<uint32_t>* counts, uint64_t samples, const History& history, uint32_t W, uint32_t H) {
+    if (rgb_sum.size() != (size_t)W * H * 3 || history.sum.size() != rgb_sum.size() || history.counts.size() != (size_t)W * H || (counts && counts->size() != (size_t)W * H))
+        throw Error("temporal_blend: frame, counts or history of another size");
+    History out; out.sum.resize(rgb_sum.size()); out.counts.resize((size_t)W * H);
+    if (rt_temporal_blend_host(rgb_sum.data(), counts ? counts->data() : nullptr, samples, history.sum.data(), history.counts.data(), W, H, out.sum.data(), out.counts.data()) != 0)
+        throw Error(rt_last_error());
+    return out;
+}
+
 // A progressive frame (rt_progressive_*): the same loop in passes of samples that accumulate on the device, with the reference's
 // format_color (src/vec.rs:125-131) resolved there too — progress, preview, stop half-way, "another 1000 samples", save and resume.
 class Progressive {
@@ -421,7 +447,18 @@ public:
         if (rgb_sum.size() != n_px_ * 3) throw Error("checkpoint of another frame size");
         chk(rt_progressive_load_sum(p_, rgb_sum.data(), samples_done));
     }
-    void reset() { chk(rt_progressive_reset(p_)); }
+    void reset() { chk(rt_progressive_reset(p_)); }                                                   // drops the history set_view keeps
+    // Another view of the same scene WITH the frame's history (rt_progressive_set_view): the frame's sums blended with the history it holds are
+    // reprojected into the new view; the frame then holds 0 samples of the new camera and seed.  Give every view a NEW seed (the random
+    // streams are keyed by pixel and sample, so the same seed under a nearby camera repeats the history's noise).  max_history = 0: a plain
+    // change of view.  Not on an adaptive frame.
+    void set_view(const Camera& cam, uint64_t seed, const ReprojectSettings& r = ReprojectSettings()) { chk(rt_progressive_set_view(p_, &cam.c, seed, r.max_history, r.sigma)); }
+    History history() const { History h; h.sum.resize(n_px_ * 3); h.counts.resize(n_px_); chk(rt_progressive_read_history(p_, h.sum.data(), h.counts.data())); return h; }
+    // the resolve of the frame blended with its history, every pixel divided by its own count; iterations >= 1: denoise_frame with the blend's
+    // counts in between.  Works with 0 samples once there is history: the preview right after a camera move
+    std::vector<uint8_t> rgb8_temporal(uint32_t iterations = 0, const DenoiseSettings& d = DenoiseSettings()) {
+        std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_temporal_rgb8(p_, iterations, d.sigma, d.flags, out.data())); return out;
+    }
     // moments (rt_progressive_enable_moments): only while the frame holds 0 samples; from then on every pass is also merged into the second
     // moment of the pass sums, and once two passes are in error_map / error_stats estimate every pixel's standard error
     void enable_moments() { chk(rt_progressive_enable_moments(p_)); }

@@ -591,8 +591,8 @@ int rt_progressive_albedo_info(void* frame, uint32_t* albedo_samples_out, uint64
  * filtered mean, were the taps independent.  The other arguments, the errors (plus a null var) and the three forms are those of
  * rt_denoise_host / rt_denoise / rt_denoise_device; the workspace is rt_denoise_variance_workspace_bytes(W, H) = 128 bytes per pixel;
  * d_var and d_var_out are 8-byte aligned, d_var is only read.
- * Not done: the combination with albedo demodulation (per-channel V / albedo^2 — which is why var is per channel), temporal accumulation,
- * variance gathered inside the path-tracing kernels, rt_render_multi. */
+ * Not done: the combination with albedo demodulation (per-channel V / albedo^2 — which is why var is per channel), temporal accumulation
+ * (now rt_reproject below, for the colour sums only), variance gathered inside the path-tracing kernels, rt_render_multi. */
 int rt_denoise_variance_host(const double* rgb_sum, uint64_t samples, const double* var, const double* hits, uint32_t W, uint32_t H,
                              uint32_t iterations, const double sigma[3], uint32_t flags, double* rgb_sum_out, double* var_out);
 int rt_denoise_variance(const double* rgb_sum, uint64_t samples, const double* var, const double* hits, uint32_t W, uint32_t H,
@@ -656,6 +656,70 @@ int rt_progressive_variance_counts(void* frame, double* var_out);
 enum { RT_DENOISE_STOP_COLOUR = 0, RT_DENOISE_STOP_VARIANCE = 1 };
 int rt_progressive_resolve_denoised_frame_rgb8(void* frame, uint32_t stop, uint32_t albedo_samples, uint32_t iterations, const double sigma[3],
                                                uint32_t flags, uint8_t* rgb8_out);
+
+/* ---- temporal accumulation: a frame's history reprojected into a new view of the same scene (the half of SVGF, Schied et al. 2017, that the
+ *      variance-guided filter leaves out), so that a camera move does not throw every sample away.  For every pixel of the new view whose
+ *      first-hit record (cur_hits) is a hit with an object (word [12] >= 0): its surface point is projected through the previous camera's
+ *      lens centre onto the previous view's pixel grid; the four pixels around that place are the taps of a bilinear footprint; a tap counts
+ *      when the previous record (prev_hits) is a hit of the same object whose normal agrees (n.m > 0 and cos^2 >= normal_min^2), whose point
+ *      lies in the centre's plane within sigma_p times the distance from the previous camera, whose count is not 0 and whose sums are
+ *      finite.  The history is the weighted mean of the taps' MEANS, in sum units with a count of its own:
+ *          hist_counts = floor(min(sum of w * count over the taps, max_history)),   hist_sum = mean * hist_counts
+ *      — the weights are not renormalised in the count, so a footprint that is only partly valid is worth less, and max_history caps what
+ *      the past is worth: n new samples weigh n / (n + hist_counts).  A pixel without history holds +0.0 sums and count 0.
+ *      csrc/rt_reproject.h is the exact specification — + - * /, floor and comparisons in a fixed order — which the HIP kernel
+ *      (csrc/rt_reproject.hip), the host twin and a NumPy restatement (tests/reproject_cases.py) satisfy bit for bit.
+ * prev_sum: W*H*3 doubles, output order; prev_counts: W*H uint32 or NULL (then prev_samples >= 1 is every pixel's count; with counts it is
+ * ignored); prev_hits, cur_hits: W*H records of 16 doubles as rt_query_camera or rt_query_camera_guide write them for the previous and the
+ * new view; prev_cam: the previous view's camera (the new view's is not needed: its records hold world-space points); max_history: 0 .. 2^31 - 1
+ * (0: an empty history); sigma = {normal_min in [0, 1], sigma_p > 0}, +inf as sigma_p switches that stop off; flags: 0.
+ * hist_sum_out: W*H*3 doubles; hist_counts_out: W*H uint32; neither may overlap an input.
+ * Three forms as for rt_denoise: _host is plain C++ (no GPU), rt_reproject copies to the current device and runs the kernel there,
+ * rt_reproject_device takes device pointers (records 16-byte aligned, sums 8-byte, counts 4-byte), only enqueues on hip_stream, never waits
+ * and never allocates.  Errors (non-zero, rt_last_error, nothing written or launched): a null argument, W or H < 2, W*H > 2^31 - 1,
+ * max_history > 2^31 - 1, normal_min outside [0, 1] or NaN, sigma_p <= 0 or NaN, flags != 0, prev_samples = 0 without counts.
+ * Not done: history for pixels that miss (the background), a wider search when all four taps fail, objects that move between the views,
+ * reflections and refractions (a mirror's image is reprojected as if painted on it), second moments or a variance frame, f32. */
+int rt_reproject_host(const double* prev_sum, const uint32_t* prev_counts, uint64_t prev_samples, const double* prev_hits, const rt_camera* prev_cam,
+                      const double* cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2], uint32_t flags,
+                      double* hist_sum_out, uint32_t* hist_counts_out);
+int rt_reproject(const double* prev_sum, const uint32_t* prev_counts, uint64_t prev_samples, const double* prev_hits, const rt_camera* prev_cam,
+                 const double* cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2], uint32_t flags,
+                 double* hist_sum_out, uint32_t* hist_counts_out);
+int rt_reproject_device(const void* d_prev_sum, const void* d_prev_counts, uint64_t prev_samples, const void* d_prev_hits, const rt_camera* prev_cam,
+                        const void* d_cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2], uint32_t flags,
+                        void* d_hist_sum_out, void* d_hist_counts_out, void* hip_stream);
+/* The blend of a frame with a history, element-wise: sum_out = rgb_sum + hist_sum, counts_out = min(N + hist_counts, 2^32 - 1) with
+ * N = counts ? counts[p] : samples (samples = 0 is allowed: a view that has no samples of its own yet).  The result is a frame with counts in
+ * the adaptive frames' layout: rt_adaptive_resolve_rgb8_* and rt_denoise_frame*(counts = ...) take it unchanged.  counts: W*H uint32 or
+ * NULL; sum_out may be rgb_sum and counts_out may be counts; the history may overlap no output.  The device form takes device pointers (sums
+ * 8-byte aligned, counts 4-byte), only enqueues, never waits, never allocates.  Errors: a null argument, W or H < 2, W*H > 2^31 - 1. */
+int rt_temporal_blend_host(const double* rgb_sum, const uint32_t* counts, uint64_t samples, const double* hist_sum, const uint32_t* hist_counts,
+                           uint32_t W, uint32_t H, double* sum_out, uint32_t* counts_out);
+int rt_temporal_blend_device(const void* d_rgb_sum, const void* d_counts, uint64_t samples, const void* d_hist_sum, const void* d_hist_counts,
+                             uint32_t W, uint32_t H, void* d_sum_out, void* d_counts_out, void* hip_stream);
+/* A progressive frame moved to another view WITH its history (rt_progressive_reset moves nothing and drops the history).  Waits for the
+ * passes enqueued so far.  The previous frame is the blend of the frame's sums (rt_progressive_samples samples) with the history it holds, so
+ * history chains from view to view; prev_hits and cur_hits are the frame's guide records — rt_query_camera(sample 0), or
+ * rt_query_camera_guide(0, guide_samples) after rt_progressive_set_guide_samples — of the old view under the old seed and of the new view
+ * under the new seed; the history becomes rt_reproject of that frame (H_sum and H_cnt, 28 more bytes per pixel, allocated at first use).
+ * The frame then holds 0 samples of the new camera and seed, exactly as rt_progressive_reset leaves it (moments, guide, albedo sums, the
+ * first-resolve state), and keeps the history.  Give the new view a NEW SEED: a sample's random stream is keyed by pixel and sample index,
+ * so the same seed under a nearby camera gives the new samples nearly the noise the history already carries, and the two do not average
+ * out.  max_history = 0 is a plain change of view.  Every call that existed before ignores the history.
+ * Errors: those of rt_reproject; an adaptive frame (compose rt_reproject_device and rt_temporal_blend_device instead); a scene that has been
+ * destroyed or changed.
+ * rt_progressive_read_history: H_sum (W*H*3 doubles) and H_cnt (W*H uint32); all zero without a history.
+ * rt_progressive_history_info: out[0] the views taken by rt_progressive_set_view over the frame's life, out[1] the pixels with H_cnt > 0. */
+int rt_progressive_set_view(void* frame, const rt_camera* cam, uint64_t seed, uint32_t max_history, const double sigma[2]);
+int rt_progressive_read_history(void* frame, double* hist_sum_out, uint32_t* hist_counts_out);
+int rt_progressive_history_info(void* frame, uint64_t out[2]);
+/* The resolve of the frame blended with its history.  iterations = 0: byte for byte rt_adaptive_resolve_rgb8_host of rt_temporal_blend_host(
+ * rt_progressive_read_sum, rt_progressive_samples, rt_progressive_read_history); sigma may be NULL.  iterations 1 .. 8: that resolve of
+ * rt_denoise_frame_host(the blend's sums, counts = the blend's counts, no variance, no albedo, the frame's guide, iterations, sigma = {sigma_c,
+ * sigma_n, sigma_p}, flags).  Allowed with 0 samples when a pixel has history — the preview in the instant after a camera move; an error
+ * with neither samples nor history, and on an adaptive frame.  The sums, the history and what the other resolves own are untouched. */
+int rt_progressive_resolve_temporal_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out);
 
 /* The whole frame on several GPUs of this node from ONE call: what a host that owns the node's GPUs itself (the reference's `main`,
  * src/main.rs:767-835) calls instead of rt_render.  device_mask: bit d selects HIP device d (0 = every visible device).  The scene

@@ -181,8 +181,18 @@ SIGNATURES = {
     "denoise_frame_device": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, _ptr, C.c_size_t, _ptr]),
     "progressive_variance_counts": (_int, [_ptr, _ptr]),
     "progressive_resolve_denoised_frame_rgb8": (_int, [_ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr]),
+    # temporal accumulation: a frame's history reprojected into a new view, and the blend with it
+    "reproject_host": (_int, [_ptr, _ptr, _u64, _ptr, _cam_p, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr]),
+    "reproject": (_int, [_ptr, _ptr, _u64, _ptr, _cam_p, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr]),
+    "reproject_device": (_int, [_ptr, _ptr, _u64, _ptr, _cam_p, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, _ptr]),
+    "temporal_blend_host": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _u32, _u32, _ptr, _ptr]),
+    "temporal_blend_device": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr]),
+    "progressive_set_view": (_int, [_ptr, _cam_p, _u64, _u32, c_double_p]),
+    "progressive_read_history": (_int, [_ptr, _ptr, _ptr]),
+    "progressive_history_info": (_int, [_ptr, c_u64_p]),
+    "progressive_resolve_temporal_rgb8": (_int, [_ptr, _u32, c_double_p, _u32, _ptr]),
     # radiance queries
-    "query_radiance": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _ptr, _ptr, c_u64_p]),
+    "query_radiance":(_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _ptr, _ptr, c_u64_p]),
     "query_radiance_device": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _u32, _int, _ptr, C.c_size_t, _ptr, _ptr, _ptr]),
     "render_multi": (_int, _FRAME + [_u32, _u32, _ptr]),
     "render_multi_device": (_int, _FRAME + [_u32, _u32, c_void_pp]),

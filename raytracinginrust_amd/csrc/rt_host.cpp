@@ -28,6 +28,7 @@
 #include "rt_denoise_var.h"
 #include "rt_adaptive.h"
 #include "rt_denoise_frame.h"
+#include "rt_reproject.h"
 #include "rt_pixels.h"
 #include "rt_kat.h"
 
@@ -86,6 +87,11 @@ struct Progressive {
     // rt_progressive_resolve_denoised_frame_rgb8's own, beside the denoised resolves': the per-pixel means c and the demodulated variance Vd
     // of a run (rt_denoise_frame.h (F): two frames of 24 bytes per pixel, each padded to 16), allocated at its first call
     void* d_fr_planes = nullptr;
+    // rt_progressive_set_view (rt_reproject.h): the history H_sum (24 bytes per pixel) and H_cnt (4), allocated at first use; hist_valid: they
+    // hold a history (rt_progressive_reset drops it; an all-zero one is made when one is needed); hist_px: the pixels with H_cnt > 0;
+    // views: the views taken over the frame's life
+    void* d_hist_sum = nullptr; void* d_hist_cnt = nullptr;
+    bool hist_valid = false; uint64_t hist_px = 0, views = 0;
     size_t n_px() const { return (size_t)W * H; }
 };
 
@@ -1895,6 +1901,7 @@ static void progressive_free(Progressive* p) {
     free_dev(p->d_sq); free_dev(p->d_pass); free_dev(p->d_e2); free_dev(p->d_mstats); free_dev(p->d_var);
     free_dev(p->d_cnt); free_dev(p->d_pas); free_dev(p->d_list); free_dev(p->d_words); free_dev(p->d_sel_ws);
     free_dev(p->d_fr_planes);
+    free_dev(p->d_hist_sum); free_dev(p->d_hist_cnt);
     if (p->ev_merged) { (void)hipEventDestroy(p->ev_merged); p->ev_merged = nullptr; }
 }
 void* rt_progressive_create(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t max_depth,
@@ -2070,6 +2077,7 @@ int rt_progressive_reset(void* frame) {
     if (p->sc) p->scene_version = p->sc->s.version;     // a new frame, of the scene as it is now
     p->guide_valid = false;                             // ... and so is its denoising guide, rebuilt when it is next needed
     p->albedo_samples = 0;                              // ... and its albedo sums
+    p->hist_valid = false; p->hist_px = 0;              // ... and the history of the views before it (rt_progressive_set_view keeps it)
     return progressive_restart(p, nullptr, 0);
 }
 
@@ -2549,11 +2557,11 @@ int rt_debug_denoise_ms(const void* d_rgb_sum, uint64_t samples, const void* d_h
 }
 // What every denoised resolve does before it filters: the checks, the frame's own buffers, and the packed guide — sample 0's camera hits of
 // this view or, with guide_samples > 1, the averaged record of samples [0, guide_samples) (rt_guide.h), keyed for `flags` — in its place in
-// the workspace.
-static int progressive_denoise_prepare(Progressive* p, uint32_t iterations, const double sigma[3], uint32_t flags) {
+// the workspace.  allow_no_samples: the temporal resolve's, which has a history to show while the frame holds 0 samples.
+static int progressive_denoise_prepare(Progressive* p, uint32_t iterations, const double sigma[3], uint32_t flags, bool allow_no_samples = false) {
     const std::string problem = denoise_check(p->done ? p->done : 1u, p->W, p->H, iterations, sigma, flags);
     if (!problem.empty()) return set_err(problem);
-    if (p->done == 0) return set_err("nothing to resolve: the frame holds 0 samples (format_color divides by the sample count, src/vec.rs:126)");
+    if (p->done == 0 && !allow_no_samples) return set_err("nothing to resolve: the frame holds 0 samples (format_color divides by the sample count, src/vec.rs:126)");
     HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the image
     const size_t n = p->n_px();
     if (!p->guide_valid || p->guide_flags != flags) {
@@ -2932,6 +2940,164 @@ int rt_progressive_resolve_denoised_frame_rgb8(void* frame, uint32_t stop, uint3
     HIP_OK((hipError_t)launch_adaptive_resolve((const double*)p->d_dn_sum, (const uint32_t*)p->d_cnt, nullptr, (uint8_t*)p->d_dn_rgb8, (unsigned long long*)p->d_dn_changed,
                                                (uint32_t)n, nullptr));
     HIP_OK(hipMemcpy(rgb8_out, p->d_dn_rgb8, n * 3, hipMemcpyDeviceToHost));             // (waits for the kernels: the null stream)
+    return 0;
+}
+
+// ---------------------------------------------------------------- temporal accumulation (csrc/rt_reproject.h: the specification; rt_reproject.hip: the kernels)
+int rt_reproject_device(const void* d_prev_sum, const void* d_prev_counts, uint64_t prev_samples, const void* d_prev_hits, const rt_camera* prev_cam,
+                        const void* d_cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2], uint32_t flags,
+                        void* d_hist_sum_out, void* d_hist_counts_out, void* hip_stream) {
+    if (!d_prev_sum || !d_prev_hits || !prev_cam || !d_cur_hits || !sigma || !d_hist_sum_out || !d_hist_counts_out) return set_err("null argument");
+    const std::string problem = reproject_check(d_prev_counts != nullptr, prev_samples, W, H, max_history, sigma, flags);
+    if (!problem.empty()) return set_err(problem);
+    if (query_aligned(d_prev_hits, "d_prev_hits") || query_aligned(d_cur_hits, "d_cur_hits")) return -1;
+    if ((((uintptr_t)d_prev_sum | (uintptr_t)d_hist_sum_out) & 7u) != 0u || (((uintptr_t)d_prev_counts | (uintptr_t)d_hist_counts_out) & 3u) != 0u)
+        return set_err("d_prev_sum and d_hist_sum_out must be 8-byte aligned, d_prev_counts and d_hist_counts_out 4-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    double fields[21];
+    rt_camera_fields(prev_cam, fields);
+    HIP_OK((hipError_t)launch_reproject(reproject_consts(fields, prev_samples, W, H, max_history, sigma), (const double*)d_prev_sum, (const uint32_t*)d_prev_counts,
+                                        (const double*)d_prev_hits, (const double*)d_cur_hits, (double*)d_hist_sum_out, (uint32_t*)d_hist_counts_out, hip_stream));
+    return 0;
+}
+int rt_reproject(const double* prev_sum, const uint32_t* prev_counts, uint64_t prev_samples, const double* prev_hits, const rt_camera* prev_cam,
+                 const double* cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2], uint32_t flags,
+                 double* hist_sum_out, uint32_t* hist_counts_out) {
+    if (!prev_sum || !prev_hits || !prev_cam || !cur_hits || !sigma || !hist_sum_out || !hist_counts_out) return set_err("null argument");
+    const std::string problem = reproject_check(prev_counts != nullptr, prev_samples, W, H, max_history, sigma, flags);
+    if (!problem.empty()) return set_err(problem);
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), cnt_bytes = n * sizeof(uint32_t), hit_bytes = n * REPROJECT_HIT_DOUBLES * sizeof(double);
+    DeviceBuffer d_sum, d_cnt, d_prev, d_cur, d_hsum, d_hcnt;
+    HIP_OK(d_sum.alloc(sum_bytes)); HIP_OK(d_prev.alloc(hit_bytes)); HIP_OK(d_cur.alloc(hit_bytes)); HIP_OK(d_hsum.alloc(sum_bytes)); HIP_OK(d_hcnt.alloc(cnt_bytes));
+    if (prev_counts) { HIP_OK(d_cnt.alloc(cnt_bytes)); HIP_OK(hipMemcpy(d_cnt.get(), prev_counts, cnt_bytes, hipMemcpyHostToDevice)); }
+    HIP_OK(hipMemcpy(d_sum.get(), prev_sum, sum_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_prev.get(), prev_hits, hit_bytes, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_cur.get(), cur_hits, hit_bytes, hipMemcpyHostToDevice));
+    if (rt_reproject_device(d_sum.get(), prev_counts ? d_cnt.get() : nullptr, prev_samples, d_prev.get(), prev_cam, d_cur.get(), W, H, max_history, sigma, flags,
+                            d_hsum.get(), d_hcnt.get(), nullptr)) return -1;
+    HIP_OK(hipMemcpy(hist_sum_out, d_hsum.get(), sum_bytes, hipMemcpyDeviceToHost));     // (waits for the kernel: the null stream)
+    HIP_OK(hipMemcpy(hist_counts_out, d_hcnt.get(), cnt_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+int rt_temporal_blend_device(const void* d_rgb_sum, const void* d_counts, uint64_t samples, const void* d_hist_sum, const void* d_hist_counts,
+                             uint32_t W, uint32_t H, void* d_sum_out, void* d_counts_out, void* hip_stream) {
+    if (!d_rgb_sum || !d_hist_sum || !d_hist_counts || !d_sum_out || !d_counts_out) return set_err("null argument");
+    const std::string problem = reproject_frame_check(W, H);
+    if (!problem.empty()) return set_err(problem);
+    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_hist_sum | (uintptr_t)d_sum_out) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_hist_counts | (uintptr_t)d_counts_out) & 3u) != 0u)
+        return set_err("d_rgb_sum, d_hist_sum and d_sum_out must be 8-byte aligned, d_counts, d_hist_counts and d_counts_out 4-byte aligned");
+    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
+    HIP_OK((hipError_t)launch_temporal_blend((const double*)d_rgb_sum, (const uint32_t*)d_counts, samples, (const double*)d_hist_sum, (const uint32_t*)d_hist_counts,
+                                             W * H, (double*)d_sum_out, (uint32_t*)d_counts_out, hip_stream));
+    return 0;
+}
+// The history's buffers, allocated at first use; without a history they are made the empty one (all +0.0 and 0), so that every caller blends
+// with something.  On the null stream; nothing waits.
+static int progressive_history_ready(Progressive* p) {
+    const size_t n = p->n_px();
+    if (!p->d_hist_sum) HIP_OK(hipMalloc(&p->d_hist_sum, n * 3 * sizeof(double)));
+    if (!p->d_hist_cnt) HIP_OK(hipMalloc(&p->d_hist_cnt, n * sizeof(uint32_t)));
+    if (!p->hist_valid) {
+        HIP_OK(hipMemsetAsync(p->d_hist_sum, 0, n * 3 * sizeof(double), nullptr));
+        HIP_OK(hipMemsetAsync(p->d_hist_cnt, 0, n * sizeof(uint32_t), nullptr));
+        p->hist_valid = true; p->hist_px = 0;
+    }
+    return 0;
+}
+// the guide records of a view of the frame's scene, as progressive_denoise_prepare builds them: sample 0's, or the averaged record
+static int progressive_view_records(Progressive* p, const rt_camera* cam, uint64_t seed, void* d_hits, size_t hit_bytes) {
+    if (p->guide_samples == 1u) return rt_query_camera_device(p->sc, cam, p->W, p->H, 0u, seed, 0u, nullptr, d_hits, hit_bytes, nullptr);
+    return rt_query_camera_guide_device(p->sc, cam, p->W, p->H, 0u, p->guide_samples, seed, 0u, d_hits, hit_bytes, nullptr, 0u, nullptr);
+}
+int rt_progressive_set_view(void* frame, const rt_camera* cam, uint64_t seed, uint32_t max_history, const double sigma[2]) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !cam || !sigma) return set_err("null argument");
+    if (p->adaptive) return set_err("rt_progressive_set_view: not available on an adaptive frame (rt_reproject_device and rt_temporal_blend_device take per-pixel counts: a caller can compose them)");
+    if (!p->sc) return set_err("the scene of this progressive frame has been destroyed");
+    if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
+    const std::string problem = reproject_check(true, 0u, p->W, p->H, max_history, sigma, 0u);
+    if (!problem.empty()) return set_err(problem);
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the previous frame
+    if (progressive_history_ready(p)) return -1;
+    const size_t n = p->n_px(), sum_bytes = n * 3 * sizeof(double), cnt_bytes = n * sizeof(uint32_t), hit_bytes = n * REPROJECT_HIT_DOUBLES * sizeof(double);
+    if (max_history == 0u || (p->done == 0 && p->hist_px == 0)) {     // nothing is carried over: the empty history, as (R5) gives it
+        HIP_OK(hipMemsetAsync(p->d_hist_sum, 0, sum_bytes, nullptr));
+        HIP_OK(hipMemsetAsync(p->d_hist_cnt, 0, cnt_bytes, nullptr));
+        p->hist_px = 0;
+    } else {
+        DeviceBuffer d_bsum, d_bcnt, d_prev, d_cur;
+        HIP_OK(d_bsum.alloc(sum_bytes)); HIP_OK(d_bcnt.alloc(cnt_bytes)); HIP_OK(d_prev.alloc(hit_bytes)); HIP_OK(d_cur.alloc(hit_bytes));
+        HIP_OK((hipError_t)launch_temporal_blend((const double*)p->d_sum, nullptr, p->done, (const double*)p->d_hist_sum, (const uint32_t*)p->d_hist_cnt, (uint32_t)n,
+                                                 (double*)d_bsum.get(), (uint32_t*)d_bcnt.get(), nullptr));
+        if (progressive_view_records(p, &p->cam, p->seed, d_prev.get(), hit_bytes)) return -1;
+        if (progressive_view_records(p, cam, seed, d_cur.get(), hit_bytes)) return -1;
+        if (rt_reproject_device(d_bsum.get(), d_bcnt.get(), 0u, d_prev.get(), &p->cam, d_cur.get(), p->W, p->H, max_history, sigma, 0u, p->d_hist_sum, p->d_hist_cnt, nullptr)) return -1;
+        std::vector<uint32_t> cnt(n);
+        HIP_OK(hipMemcpy(cnt.data(), p->d_hist_cnt, cnt_bytes, hipMemcpyDeviceToHost));      // (waits for the kernels: the null stream)
+        uint64_t px = 0;
+        for (size_t k = 0; k < n; k++) px += cnt[k] != 0u;
+        p->hist_px = px;
+    }
+    std::memcpy(&p->cam, cam, sizeof(rt_camera)); p->seed = seed;
+    p->guide_valid = false; p->albedo_samples = 0;      // as rt_progressive_reset: a new frame of the new view ...
+    p->views++;
+    return progressive_restart(p, nullptr, 0);          // ... that keeps its history
+}
+int rt_progressive_read_history(void* frame, double* hist_sum_out, uint32_t* hist_counts_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !hist_sum_out || !hist_counts_out) return set_err("null argument");
+    const size_t n = p->n_px();
+    if (!p->hist_valid) {
+        std::memset(hist_sum_out, 0, n * 3 * sizeof(double)); std::memset(hist_counts_out, 0, n * sizeof(uint32_t));
+        return 0;
+    }
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(hist_sum_out, p->d_hist_sum, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(hist_counts_out, p->d_hist_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+int rt_progressive_history_info(void* frame, uint64_t out[2]) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !out) return set_err("null argument");
+    out[0] = p->views; out[1] = p->hist_valid ? p->hist_px : 0u;
+    return 0;
+}
+// The blend of the frame with its history resolved with the blend's counts, with the frame filter in between when iterations >= 1; into
+// the denoised resolves' buffers: d_sum, the history, the plain resolve's two images and its count stay as they are.
+int rt_progressive_resolve_temporal_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !rgb8_out || (iterations && !sigma)) return set_err("null argument");
+    if (p->adaptive) return set_err("rt_progressive_resolve_temporal_rgb8: not available on an adaptive frame (it has no history: rt_progressive_set_view refuses it)");
+    if (iterations > DENOISE_MAX_ITERATIONS) return set_err("denoise: iterations must be 0 .. 8 (0: the resolve of the blend without a filter)");
+    const bool history = p->hist_valid && p->hist_px > 0;
+    if (p->done == 0 && !history) return set_err("nothing to resolve: the frame holds 0 samples and no history (rt_progressive_add, rt_progressive_set_view)");
+    DeviceGuard guard(p->device);
+    const size_t n = p->n_px(), sum_bytes = n * 3 * sizeof(double);
+    if (iterations) { if (progressive_denoise_prepare(p, iterations, sigma, flags, true)) return -1; }
+    else {
+        HIP_OK(hipDeviceSynchronize());             // passes enqueued on the caller's streams belong to the image
+        if (!p->d_dn_rgb8) HIP_OK(hipMalloc(&p->d_dn_rgb8, n * 3));
+        if (!p->d_dn_changed) HIP_OK(hipMalloc(&p->d_dn_changed, sizeof(unsigned long long)));
+    }
+    if (progressive_history_ready(p)) return -1;
+    DeviceBuffer d_bsum, d_bcnt;
+    HIP_OK(d_bsum.alloc(sum_bytes)); HIP_OK(d_bcnt.alloc(n * sizeof(uint32_t)));
+    HIP_OK((hipError_t)launch_temporal_blend((const double*)p->d_sum, nullptr, p->done, (const double*)p->d_hist_sum, (const uint32_t*)p->d_hist_cnt, (uint32_t)n,
+                                             (double*)d_bsum.get(), (uint32_t*)d_bcnt.get(), nullptr));
+    const double* d_resolved = (const double*)d_bsum.get();
+    if (iterations) {
+        const size_t plane = denoise_frame_plane_bytes(n);
+        if (!p->d_fr_planes) HIP_OK(hipMalloc(&p->d_fr_planes, 2u * plane));
+        if (denoise_frame_enqueue((const double*)d_bsum.get(), (const uint32_t*)d_bcnt.get(), 0u, nullptr, nullptr, 0u, nullptr, p->W, p->H, iterations, sigma, flags,
+                                  (double*)p->d_dn_sum, nullptr, p->d_dn_ws, (double*)p->d_fr_planes, (double*)((unsigned char*)p->d_fr_planes + plane), nullptr)) return -1;
+        d_resolved = (const double*)p->d_dn_sum;
+    }
+    HIP_OK(hipMemsetAsync(p->d_dn_changed, 0, sizeof(unsigned long long), nullptr));
+    HIP_OK((hipError_t)launch_adaptive_resolve(d_resolved, (const uint32_t*)d_bcnt.get(), nullptr, (uint8_t*)p->d_dn_rgb8, (unsigned long long*)p->d_dn_changed, (uint32_t)n, nullptr));
+    HIP_OK(hipMemcpy(rgb8_out, p->d_dn_rgb8, n * 3, hipMemcpyDeviceToHost));             // (waits for the kernels, before the blend's buffers go: the null stream)
     return 0;
 }
 

@@ -6,7 +6,7 @@
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
 //              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material|albedo FILE] [--panorama FILE]
 //              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] [--denoise-albedo N] [--denoise-variance SIGMA_V] [--until-error TAU] [--max-samples M] [--aov error FILE]
-//              [--adaptive] [--aov samples FILE] [--denoise-guide N] [--aov coverage FILE] > image.ppm
+//              [--adaptive] [--aov samples FILE] [--denoise-guide N] [--aov coverage FILE] [--orbit FRAMES,DEGREES [--history CAP] [--out FILE]] > image.ppm
 //
 // --denoise K[,c,n,p] (opt-in): the frame through the edge-avoiding a-trous filter before it is written (rt_denoise: K iterations, guided by
 // sample 0's camera hits of this --seed, or --denoise-guide's record); with --progressive the frame resolves itself denoised on the device (rt_progressive_resolve_denoised_rgb8).
@@ -29,6 +29,10 @@
 // --adaptive (with --progressive N and --until-error TAU): an adaptive frame (rt_progressive_enable_adaptive) — every pass samples only the pixels
 // whose estimated standard error still exceeds TAU, and their neighbours, no pixel beyond --max-samples (default: --spp); the frame ends with the
 // pass that lists no pixel.  --aov samples FILE (with --adaptive, beside the frame): the per-pixel sample counts when it ends.
+// --orbit FRAMES,DEGREES [--history CAP] [--out FILE] (with --progressive N; --denoise K[,c,n,p] allowed): FRAMES views on a circle around lookat about
+// vup, DEGREES apart, each with a new seed (--seed + view) and N samples; from the second view on the frame carries its history along
+// (rt_progressive_set_view, at most CAP samples' worth per pixel, default 64; 0: none) and FILE_000.ppm, FILE_001.ppm ... (default orbit) are the
+// temporal resolves (rt_progressive_resolve_temporal_rgb8), through K iterations of the frame filter with --denoise.  Nothing goes to stdout.
 // --aov error FILE (with --progressive N, beside the frame): the frame's error map when it ends (rt_progressive_error_map).
 //
 // --aov KIND FILE (opt-in, one GPU, instead of the frame): a feature frame for a denoiser or a compositor — the closest hit of sample 0's
@@ -323,6 +327,8 @@ int main(int argc, char** argv) {
     uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
     bool adaptive = false;                                                  // --adaptive: sample only the pixels whose estimated error still exceeds --until-error
     double until_error = -1.0; uint32_t max_samples = 0;                    // --until-error TAU [--max-samples M]: stop when no pixel's standard error exceeds TAU
+    uint32_t orbit_frames = 0; double orbit_degrees = 0.0;                  // --orbit FRAMES,DEGREES: views on a circle around lookat, with temporal accumulation
+    ReprojectSettings history; std::string orbit_out = "orbit";             // --history CAP, --out FILE
     int gpus = 1;                                                           // --gpus N: the first N devices (0 = all) through rt_render_multi
     std::string obj_path = "teapot.obj", earth_path = "earthmap.jpg";       // the reference's asset names (main.rs:248,491)
     for (int i = 1; i < argc; i++) {
@@ -364,6 +370,13 @@ int main(int argc, char** argv) {
         else if (a == "--denoise-albedo") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--denoise-albedo needs a sample count >= 1\n"); return 2; } albedo_samples = (uint32_t)n; }
         else if (a == "--denoise-guide") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--denoise-guide needs a sample count >= 1\n"); return 2; } guide_samples = (uint32_t)n; }
         else if (a == "--denoise-variance") { sigma_v = std::atof(next()); if (!(sigma_v > 0.0)) { std::fprintf(stderr, "--denoise-variance needs a colour stop > 0 in standard deviations (inf switches it off)\n"); return 2; } }
+        else if (a == "--orbit") {
+            unsigned n = 0;
+            if (std::sscanf(next(), "%u,%lf", &n, &orbit_degrees) != 2 || n < 1u) { std::fprintf(stderr, "--orbit needs FRAMES,DEGREES with FRAMES >= 1\n"); return 2; }
+            orbit_frames = n;
+        }
+        else if (a == "--history") { const long long n = std::atoll(next()); if (n < 0 || n > 0x7FFFFFFFll) { std::fprintf(stderr, "--history needs a cap of 0 .. 2^31 - 1 samples\n"); return 2; } history.max_history = (uint32_t)n; }
+        else if (a == "--out") orbit_out = next();
         else if (a == "--help" || a == "-h") {
             std::printf("rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N]\n"
                         "         [--depth D] [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] > image.ppm\n%s"
@@ -380,6 +393,9 @@ int main(int argc, char** argv) {
                         "                                     exceeds TAU display units (0.00390625 = one code value), at the latest after M samples (default --spp)\n"
                         "  --adaptive                         with --progressive N and --until-error TAU: every pass samples only the pixels whose estimated standard\n"
                         "                                     error still exceeds TAU (and their neighbours), none beyond M samples; ends when no pixel is left\n"
+                        "  --orbit FRAMES,DEGREES             with --progressive N: FRAMES views on a circle around lookat, DEGREES apart, N samples and a new seed each;\n"
+                        "    [--history CAP] [--out FILE]     the frame carries its history from view to view (at most CAP samples' worth, default 64, 0: none) and\n"
+                        "                                     FILE_000.ppm ... (default orbit) are the temporal resolves; with --denoise K through the frame filter\n"
                         "  --panorama FILE                    write the 2:1 equirectangular image (width x width/2) of everything around the scene's\n"
                         "                                     lookfrom instead of the image: --spp samples per ray, --depth, the scene's background\n", AOV_HELP);
             return 0;
@@ -395,6 +411,9 @@ int main(int argc, char** argv) {
     if (albedo_samples != 0u && !want_denoise && aov_kind != "albedo") { std::fprintf(stderr, "--denoise-albedo goes with --denoise K (or --aov albedo)\n"); return 2; }
     if (guide_samples != 0u && !want_denoise && aov_kind != "coverage") { std::fprintf(stderr, "--denoise-guide goes with --denoise K (or --aov coverage)\n"); return 2; }
     if (sigma_v != 0.0 && (!want_denoise || progressive == 0u)) { std::fprintf(stderr, "--denoise-variance goes with --progressive N and --denoise K\n"); return 2; }
+    if (orbit_frames != 0u && (progressive == 0u || adaptive || until_error >= 0.0 || !aov_kind.empty() || albedo_samples != 0u || sigma_v != 0.0)) {
+        std::fprintf(stderr, "--orbit goes with --progressive N, and of the other options only with --denoise K and --denoise-guide N\n"); return 2;
+    }
     const double aspect_ratio = (double)image_width / (double)image_height;
     try {
         Scene s;
@@ -489,6 +508,30 @@ int main(int argc, char** argv) {
             const bool want_moments = until_error >= 0.0 || aov_kind == "error" || sigma_v != 0.0;
             if (want_moments) frame.enable_moments();
             if (guide_samples) frame.set_guide_samples(guide_samples);
+            if (orbit_frames) {
+                // the views: lookfrom turned about the axis vup through lookat (Rodrigues' rotation), everything else the scene's camera
+                const rt_camera& c0 = camera.c;
+                const double al = std::sqrt(c0.vup[0] * c0.vup[0] + c0.vup[1] * c0.vup[1] + c0.vup[2] * c0.vup[2]);
+                const double k[3] = {c0.vup[0] / al, c0.vup[1] / al, c0.vup[2] / al};
+                const double r[3] = {c0.lookfrom[0] - c0.lookat[0], c0.lookfrom[1] - c0.lookat[1], c0.lookfrom[2] - c0.lookat[2]};
+                for (uint32_t f = 0; f < orbit_frames; f++) {
+                    if (f) {
+                        const double a = orbit_degrees * (double)f * 3.141592653589793 / 180.0, ca = std::cos(a), sa = std::sin(a);
+                        const double kr = k[0] * r[0] + k[1] * r[1] + k[2] * r[2];
+                        const double x[3] = {k[1] * r[2] - k[2] * r[1], k[2] * r[0] - k[0] * r[2], k[0] * r[1] - k[1] * r[0]};
+                        Camera view = camera;
+                        for (int e = 0; e < 3; e++) view.c.lookfrom[e] = c0.lookat[e] + r[e] * ca + x[e] * sa + k[e] * kr * (1.0 - ca);
+                        frame.set_view(view, seed + f, history);
+                    }
+                    frame.add(progressive);
+                    char name[32]; std::snprintf(name, sizeof(name), "_%03u.ppm", f);
+                    const uint64_t held = [&]() { uint64_t w[2] = {0, 0}; rt_progressive_history_info(frame.raw(), w); return w[1]; }();
+                    write_ppm_rgb8((orbit_out + name).c_str(), frame.rgb8_temporal(want_denoise ? dn.iterations : 0u, dn), image_width, image_height);
+                    std::fprintf(stderr, "\rView %u / %u: %u samples, history in %llu pixels", f + 1u, orbit_frames, progressive, (unsigned long long)held);
+                }
+                std::fprintf(stderr, "\nDone.\n");
+                return 0;
+            }
             const uint32_t limit = until_error >= 0.0 && max_samples ? max_samples : samples_per_pixel;
             if (adaptive) {
                 frame.enable_adaptive();

@@ -642,7 +642,40 @@ class Progressive:
             raise ValueError(f"checkpoint of shape {a.shape} for a frame of {(self.H, self.W, 3)}")
         _check(self._lib.rt_progressive_load_sum(self._h, a.ctypes.data, samples))
 
+    def set_view(self, cam: CameraParams, seed: int, max_history: int = None, sigma=None) -> None:
+        """rt_progressive_set_view: move the frame to another view of the same scene and keep what it knows — the frame's sums blended with
+        the history it already holds are reprojected into the new view (`reproject`) and become the history; the frame itself then holds 0
+        samples of the new camera and seed, exactly as after `reset`.  Give every view a NEW seed: the random streams are keyed by pixel and
+        sample index, so the same seed under a nearby camera gives the new samples nearly the noise the history already has.  max_history
+        (default REPROJECT_MAX_HISTORY) caps the samples a history pixel counts for; 0 is a plain change of view.  sigma = (normal_min,
+        sigma_p), default REPROJECT_SIGMA.  Not on an adaptive frame."""
+        cap, sg = _reproject_settings(max_history, sigma)
+        _check(self._lib.rt_progressive_set_view(self._h, C.byref(cam), int(seed), cap, sg))
+
+    def history(self):
+        """rt_progressive_read_history -> (hist_sum (H, W, 3) f64, hist_counts (H, W) uint32); all zero without a history."""
+        s = np.zeros((self.H, self.W, 3), dtype=np.float64); n = np.zeros((self.H, self.W), dtype=np.uint32)
+        _check(self._lib.rt_progressive_read_history(self._h, s.ctypes.data, n.ctypes.data))
+        return s, n
+
+    def history_info(self) -> dict:
+        """{"views": the views taken by `set_view` so far, "pixels": the pixels that hold history}."""
+        out = (C.c_uint64 * 2)()
+        _check(self._lib.rt_progressive_history_info(self._h, out))
+        return {"views": int(out[0]), "pixels": int(out[1])}
+
+    def rgb8_temporal(self, iterations: int = 0, sigma=None, flags: int = 0) -> np.ndarray:
+        """rt_progressive_resolve_temporal_rgb8: the resolve of the frame blended with its history -> (H, W, 3) uint8; every pixel is
+        divided by its own count (`temporal_blend_host`, `adaptive_resolve_rgb8_host`).  iterations >= 1: `denoise_frame` with the blend's
+        counts and the frame's guide in between (sigma: DENOISE_SIGMA).  Works with 0 samples once there is history: the preview right after a
+        camera move."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        k, sg = _denoise_settings(int(iterations), sigma)
+        _check(self._lib.rt_progressive_resolve_temporal_rgb8(self._h, k, sg, flags, out.ctypes.data))
+        return out
+
     def reset(self) -> None:
+        """rt_progressive_reset: 0 samples of the same view and seed; drops the history `set_view` keeps."""
         _check(self._lib.rt_progressive_reset(self._h))
 
     def close(self) -> None:
@@ -1541,6 +1574,90 @@ def denoise_frame_device(d_rgb_sum, d_hits, W: int, H: int, d_counts=None, sampl
                                          int(albedo_samples), _ptr_or_none(d_hits), W, H, k, sg, flags, C.c_void_p(out_ptr), _ptr_or_none(d_var_out),
                                          C.c_void_p(ws_ptr), nbytes, C.c_void_p(stream)))
     return d_workspace
+
+
+# ---- temporal accumulation (rt_reproject*, rt_temporal_blend*; csrc/rt_reproject.h): a frame's history reprojected into a new view, and the
+# blend of a frame with such a history.  The two defaults are starting values, NOT tuned: normal_min 0.9 (about 26 degrees) and sigma_p 0.01 (a
+# plane distance of 1 % of the distance from the previous camera) follow the usual SVGF-style tests, and 64 is a cap after which new samples
+# still weigh 1 / 5 at 16 samples per view.
+REPROJECT_SIGMA = (0.9, 0.01)
+REPROJECT_MAX_HISTORY = 64
+
+
+def _reproject_settings(max_history, sigma):
+    cap = REPROJECT_MAX_HISTORY if max_history is None else int(max_history)
+    sg = REPROJECT_SIGMA if sigma is None else tuple(float(x) for x in sigma)
+    if len(sg) != 2:
+        raise ValueError("sigma = (normal_min, sigma_p)")
+    return cap, (C.c_double * 2)(*sg)
+
+
+def _reproject_frames(prev_sum, prev_counts, prev_hits, cur_hits):
+    s = np.ascontiguousarray(prev_sum, dtype=np.float64)
+    g0 = np.ascontiguousarray(prev_hits, dtype=np.float64); g1 = np.ascontiguousarray(cur_hits, dtype=np.float64)
+    if s.ndim != 3 or s.shape[2] != 3 or g0.shape != s.shape[:2] + (HIT_DOUBLES,) or g1.shape != g0.shape:
+        raise ValueError(f"prev_sum of shape {s.shape}, prev_hits {g0.shape}, cur_hits {g1.shape}: want (H, W, 3), (H, W, {HIT_DOUBLES}) twice")
+    n = None if prev_counts is None else np.ascontiguousarray(prev_counts, dtype=np.uint32)
+    if n is not None and n.shape != s.shape[:2]:
+        raise ValueError(f"prev_counts of shape {n.shape} for a frame of {s.shape}: want (H, W)")
+    return s, n, g0, g1
+
+
+def _reproject_call(fn, prev_sum, prev_hits, prev_cam, cur_hits, prev_counts, prev_samples, max_history, sigma, flags):
+    s, n, g0, g1 = _reproject_frames(prev_sum, prev_counts, prev_hits, cur_hits)
+    cap, sg = _reproject_settings(max_history, sigma)
+    hs = np.zeros_like(s); hn = np.zeros(s.shape[:2], dtype=np.uint32)
+    _check(fn(s.ctypes.data, None if n is None else n.ctypes.data, int(prev_samples), g0.ctypes.data, C.byref(prev_cam), g1.ctypes.data, s.shape[1], s.shape[0],
+              cap, sg, flags, hs.ctypes.data, hn.ctypes.data))
+    return hs, hn
+
+
+def reproject_host(prev_sum, prev_hits, prev_cam: CameraParams, cur_hits, prev_counts=None, prev_samples: int = 1, max_history: int = None, sigma=None,
+                   flags: int = 0):
+    """rt_reproject_host (no GPU): the history of the previous view's frame in the new view, csrc/rt_reproject.h as plain C++.  prev_sum
+    (H, W, 3) sums with prev_counts (H, W) uint32 or, when None, prev_samples samples in every pixel; prev_hits / cur_hits (H, W, 16): the
+    `query_camera` or `query_camera_guide` records of the previous view (camera prev_cam) and of the new one.  -> (hist_sum (H, W, 3),
+    hist_counts (H, W) uint32): a frame with counts, 0 where a pixel has no history."""
+    return _reproject_call(_rt().rt_reproject_host, prev_sum, prev_hits, prev_cam, cur_hits, prev_counts, prev_samples, max_history, sigma, flags)
+
+
+def reproject(prev_sum, prev_hits, prev_cam: CameraParams, cur_hits, prev_counts=None, prev_samples: int = 1, max_history: int = None, sigma=None,
+              flags: int = 0):
+    """rt_reproject: the same call computed by the HIP kernel on the current device — the same words as reproject_host."""
+    return _reproject_call(_rt().rt_reproject, prev_sum, prev_hits, prev_cam, cur_hits, prev_counts, prev_samples, max_history, sigma, flags)
+
+
+def reproject_device(d_prev_sum, d_prev_hits, prev_cam: CameraParams, d_cur_hits, W: int, H: int, d_hist_sum_out, d_hist_counts_out, d_prev_counts=None,
+                     prev_samples: int = 1, max_history: int = None, sigma=None, flags: int = 0, stream: int = 0) -> None:
+    """rt_reproject_device: `reproject` for frames in device memory (torch tensors or raw pointers; records 16-byte aligned), enqueued on
+    `stream`; never waits, never allocates.  The outputs may overlap no input."""
+    cap, sg = _reproject_settings(max_history, sigma)
+    _check(_rt().rt_reproject_device(_ptr_or_none(d_prev_sum), _ptr_or_none(d_prev_counts), int(prev_samples), _ptr_or_none(d_prev_hits), C.byref(prev_cam),
+                                     _ptr_or_none(d_cur_hits), W, H, cap, sg, flags, _ptr_or_none(d_hist_sum_out), _ptr_or_none(d_hist_counts_out), C.c_void_p(stream)))
+
+
+def temporal_blend_host(rgb_sum, hist_sum, hist_counts, counts=None, samples: int = 0):
+    """rt_temporal_blend_host (no GPU): a frame — rgb_sum (H, W, 3) with counts (H, W) uint32 or, when None, `samples` samples in every
+    pixel — blended with a history -> (sum (H, W, 3), counts (H, W) uint32): the sums added, the counts added and held at 2^32 - 1.  The
+    result goes to `adaptive_resolve_rgb8_host` and `denoise_frame_host(counts=...)` as it is."""
+    s = np.ascontiguousarray(rgb_sum, dtype=np.float64); hs = np.ascontiguousarray(hist_sum, dtype=np.float64)
+    hn = np.ascontiguousarray(hist_counts, dtype=np.uint32)
+    n = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    if s.ndim != 3 or s.shape[2] != 3 or hs.shape != s.shape or hn.shape != s.shape[:2] or (n is not None and n.shape != hn.shape):
+        raise ValueError(f"rgb_sum of shape {s.shape}, hist_sum {hs.shape}, hist_counts {hn.shape}: want (H, W, 3) twice and (H, W)")
+    out = np.zeros_like(s); out_n = np.zeros_like(hn)
+    _check(_rt().rt_temporal_blend_host(s.ctypes.data, None if n is None else n.ctypes.data, int(samples), hs.ctypes.data, hn.ctypes.data, s.shape[1], s.shape[0],
+                                        out.ctypes.data, out_n.ctypes.data))
+    return out, out_n
+
+
+def temporal_blend_device(d_rgb_sum, d_hist_sum, d_hist_counts, W: int, H: int, d_sum_out=None, d_counts_out=None, d_counts=None, samples: int = 0,
+                          stream: int = 0) -> None:
+    """rt_temporal_blend_device: `temporal_blend_host` for frames in device memory, enqueued on `stream`; never waits.  d_sum_out None: in
+    place in d_rgb_sum; d_counts_out None: in place in d_counts (which must then be given)."""
+    _check(_rt().rt_temporal_blend_device(_ptr_or_none(d_rgb_sum), _ptr_or_none(d_counts), int(samples), _ptr_or_none(d_hist_sum), _ptr_or_none(d_hist_counts), W, H,
+                                          _ptr_or_none(d_rgb_sum if d_sum_out is None else d_sum_out), _ptr_or_none(d_counts if d_counts_out is None else d_counts_out),
+                                          C.c_void_p(stream)))
 
 
 def kernel_time_total(b: SceneBuilder, reset: bool = False):
