@@ -1,6 +1,6 @@
 // csrc/rt_adaptive.h — adaptive progressive frames: per-pixel sample counts through error, selection, merge and resolve.  The specification,
 // the host twin's seams (rt_adaptive_cpu.cpp, plain C++) and the launches of the HIP kernels (rt_adaptive.hip) as the host library
-// (rt_host.cpp) sees them.  No HIP include: a stream travels as a void* and a HIP status as an int (0 = hipSuccess), as in rt_moments.h.
+// (rt_frames.cpp) sees them.  No HIP include: a stream travels as a void* and a HIP status as an int (0 = hipSuccess), as in rt_moments.h.
 //
 // THE INVARIANT: pixel p of an adaptive frame with count n[p] holds exactly samples 0 .. n[p] - 1 of the streams rng_for_path(seed, p, s) —
 // the very samples a one-shot frame of the same view and seed holds at those indices.  A pass has ONE size n_b for every listed pixel: a

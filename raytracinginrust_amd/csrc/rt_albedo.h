@@ -1,5 +1,5 @@
 // csrc/rt_albedo.h — the first-hit albedo query and albedo-demodulated denoising: the two specifications, the host twin's seams
-// (rt_albedo_cpu.cpp, plain C++) and the launches of the HIP kernels (rt_albedo.hip) as the host library (rt_host.cpp) sees them.  No HIP
+// (rt_albedo_cpu.cpp, plain C++) and the launches of the HIP kernels (rt_albedo.hip) as the host library (rt_host.cpp, rt_frames.cpp) sees them.  No HIP
 // include unless RT_ALBEDO_QUERIES asks for the query kernels' interface at the end: for the element-wise kernels a stream travels as a
 // void* and a HIP status as an int (0 = hipSuccess), as in rt_denoise.h, so that the host twin and its stand-alone sanitizer program
 // compile with any C++ compiler.

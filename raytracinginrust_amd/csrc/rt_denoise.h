@@ -1,5 +1,5 @@
 // csrc/rt_denoise.h — the denoiser's seams: the host twin (rt_denoise_cpu.cpp, plain C++) and the launches of the HIP kernels
-// (rt_denoise.hip) as the host library (rt_host.cpp) sees them.  No HIP include: a stream travels as a void* and a HIP status as an int
+// (rt_denoise.hip) as the host library (rt_frames.cpp) sees them.  No HIP include: a stream travels as a void* and a HIP status as an int
 // (0 = hipSuccess), so that the host twin and its stand-alone sanitizer program compile with any C++ compiler.
 //
 // The filter is the edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010) over the f64 sum frame, guided by the hit

@@ -1,6 +1,6 @@
 // csrc/rt_denoise_frame.h — denoising a frame as it is: one sample count for the frame or a count per pixel (an adaptive frame, rt_adaptive.h),
 // with or without a variance frame (rt_denoise_var.h), with or without albedo sums (rt_albedo.h (2)).  The specification, the host twin's
-// seams (rt_denoise_frame_cpu.cpp, plain C++) and the launches of the HIP kernels (rt_denoise_frame.hip) as the host library (rt_host.cpp)
+// seams (rt_denoise_frame_cpu.cpp, plain C++) and the launches of the HIP kernels (rt_denoise_frame.hip) as the host library (rt_frames.cpp)
 // sees them.  No HIP include: a stream travels as a void* and a HIP status as an int (0 = hipSuccess), as in rt_denoise.h.
 //
 // The filters themselves do not change: they compute c = rgb_sum / samples at their start and c_K * samples at their end, so a frame of

@@ -1,5 +1,5 @@
 // csrc/rt_denoise_var.h — the variance-guided form of the denoiser of rt_denoise.h: the specification, the host twin's seams
-// (rt_denoise_var_cpu.cpp, plain C++) and the launches of the HIP kernels (rt_denoise_var.hip) as the host library (rt_host.cpp) sees them.
+// (rt_denoise_var_cpu.cpp, plain C++) and the launches of the HIP kernels (rt_denoise_var.hip) as the host library (rt_frames.cpp) sees them.
 // No HIP include, as in rt_denoise.h: a stream travels as a void* and a HIP status as an int (0 = hipSuccess).
 //
 // rt_denoise.h stops colour bleeding with one sigma_c for the whole frame, tightened fourfold per iteration by hand.  Here the stop is

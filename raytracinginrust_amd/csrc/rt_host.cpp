@@ -1,6 +1,6 @@
 // csrc/rt_host.cpp — C-ABI of librt_amd.so (include/rt_amd.h): scene builder handles, device upload,
 // kernel launch, format_color / PPM emitter.  There is NO CPU rendering path in this library: without a
-// HIP device rt_render* fail with an error.
+// HIP device rt_render* fail with an error.  Progressive frames and the image operations over them: rt_frames.cpp.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -10,13 +10,11 @@
 #include <exception>
 #include <string>
 #include <vector>
-#include "../../include/rt_amd.h"
-#include "rt_scene.h"
+#include "rt_host_shared.h"
 #include "rt_launch.h"
 #include "rt_short.h"
 #include "rt_primary.h"
 #include "rt_device.h"
-#include "rt_resolve.h"
 #include "rt_query.h"
 #include "rt_radiance.h"
 #include "rt_denoise.h"
@@ -24,13 +22,12 @@
 #include "rt_albedo.h"
 #define RT_GUIDE_QUERIES
 #include "rt_guide.h"
-#include "rt_moments.h"
+#include "rt_pixels.h"
+#include "rt_kat.h"
+#include "rt_resolve.h"     // (these four: the loop sizes rt_debug_loop_limits reports)
 #include "rt_denoise_var.h"
 #include "rt_adaptive.h"
 #include "rt_denoise_frame.h"
-#include "rt_reproject.h"
-#include "rt_pixels.h"
-#include "rt_kat.h"
 
 using namespace rt;
 
@@ -41,66 +38,10 @@ bool parse_obj(const char* data, size_t size, const double offset[3], double sca
 
 struct rt_rng { Rng r; };
 
-// A progressive frame (rt_progressive_*, include/rt_amd.h): one fixed view of one scene, the device-resident f64 sum frame its passes
-// accumulate into, and two RGB8 images — the most recent resolve and the one before it, which the next resolve is compared with and
-// then overwrites.  Everything lives on `device`.  The handle the C-ABI passes around (a void*) is a pointer to this.
-struct Progressive {
-    rt_scene* sc = nullptr;                // nullptr once the scene has been destroyed: the frame can still be read, resolved and destroyed
-    unsigned long long scene_version = 0;  // Scene::version at create / reset: a pass after a change to the scene is refused
-    rt_camera cam; double bg[3] = {0, 0, 0};
-    uint32_t W = 0, H = 0, max_depth = 0, flags = 0; uint64_t seed = 0;
-    int device = -1;
-    uint64_t done = 0;                     // samples per pixel accumulated so far
-    void* d_sum = nullptr;                 // W*H*3 doubles, output order
-    void* d_rgb8[2] = {nullptr, nullptr}; int cur = 0; bool have_prev = false, resolved = false;     // d_rgb8[cur]: the most recent resolve
-    void* d_changed = nullptr;             // one 64-bit word: the most recent resolve's changed-pixel count
-    // rt_progressive_resolve_denoised_rgb8's own buffers, allocated at its first call: the filter's workspace (two packed colour frames and
-    // the packed guide, rt_denoise.h), the filtered sums, their RGB8 image and the count word its resolve launch needs.  The guide — sample
-    // 0's camera hits of this view, keyed for guide_flags — is built once and kept until rt_progressive_reset.
-    void* d_dn_ws = nullptr; void* d_dn_sum = nullptr; void* d_dn_rgb8 = nullptr; void* d_dn_changed = nullptr;
-    bool guide_valid = false; uint32_t guide_flags = 0;
-    // rt_progressive_set_guide_samples: 1 is the guide above; n > 1 builds it from samples [0, n) of this view under the frame's seed instead
-    // (rt_query_camera_guide_device, rt_guide.h).  guide_builds counts the guides built, of either kind.
-    uint32_t guide_samples = 1; uint64_t guide_builds = 0;
-    // rt_progressive_resolve_denoised_albedo_rgb8's own, beside the above: the albedo sums of samples [0, albedo_samples) of this view under
-    // the frame's seed (rt_query_camera_albedo_device), built when first asked for and kept until rt_progressive_reset or another
-    // albedo_samples, and the demodulated frame of a run (24 + 24 bytes per pixel).  albedo_builds counts the launches that built d_alb_sum.
-    void* d_alb_sum = nullptr; void* d_alb_x = nullptr;
-    uint32_t albedo_samples = 0; uint64_t albedo_builds = 0;
-    // rt_progressive_enable_moments (rt_moments.h): the second moments Q (d_sq) and the pass frame a pass renders into before the merge
-    // kernel adds it to d_sum and d_sq and zeroes it again (24 + 24 bytes per pixel); `passes` merges so far; moments_valid: d_sq describes
-    // the samples d_sum holds (rt_progressive_load_sum breaks that).  ev_merged is recorded behind every merge: the next pass's stream waits
-    // for it, because passes on different streams share d_pass.  d_e2 (rt_progressive_error_map*, allocated at the first call) and the
-    // four statistics words.
-    bool moments = false, moments_valid = false, merge_recorded = false; uint64_t passes = 0;
-    void* d_sq = nullptr; void* d_pass = nullptr; void* d_e2 = nullptr; void* d_mstats = nullptr;
-    hipEvent_t ev_merged = nullptr;
-    // rt_progressive_variance / rt_progressive_resolve_denoised_variance_rgb8: the per-channel variance frame (rt_moments.h (4)) of the sums
-    // as they are at that call, allocated at the first one (24 bytes per pixel)
-    void* d_var = nullptr;
-    // rt_progressive_enable_adaptive (rt_adaptive.h): per-pixel counts n (d_cnt) and b (d_pas), the pixel list of a pass with its length and
-    // the largest count behind a list merge (d_words: two uint32), and the selection's workspace.  `uniform`: every n[p] equals `done` and
-    // every b[p] equals `passes` — true until the first pass over a proper subset; from then on `done` is the largest n[p] and `passes` the
-    // passes of the frame.  total: the sum of n[p].
-    bool adaptive = false, uniform = true; uint64_t total = 0;
-    void* d_cnt = nullptr; void* d_pas = nullptr; void* d_list = nullptr; void* d_words = nullptr; void* d_sel_ws = nullptr;
-    // rt_progressive_resolve_denoised_frame_rgb8's own, beside the denoised resolves': the per-pixel means c and the demodulated variance Vd
-    // of a run (rt_denoise_frame.h (F): two frames of 24 bytes per pixel, each padded to 16), allocated at its first call
-    void* d_fr_planes = nullptr;
-    // rt_progressive_set_view (rt_reproject.h): the history H_sum (24 bytes per pixel) and H_cnt (4), allocated at first use; hist_valid: they
-    // hold a history (rt_progressive_reset drops it; an all-zero one is made when one is needed); hist_px: the pixels with H_cnt > 0;
-    // views: the views taken over the frame's life
-    void* d_hist_sum = nullptr; void* d_hist_cnt = nullptr;
-    bool hist_valid = false; uint64_t hist_px = 0, views = 0;
-    size_t n_px() const { return (size_t)W * H; }
-};
-
 static thread_local std::string g_err;
 static int set_err(const std::string& m) { g_err = m; return -1; }
 namespace rt { int set_error(const std::string& m) { return set_err(m); } }
 static int scene_err(rt_scene* sc, const std::string& m) { sc->s.error = m; g_err = m; return -1; }
-
-#define HIP_OK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_err = std::string(#call) + ": " + hipGetErrorString(e_); return -1; } } while (0)
 
 static void free_dev(void*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
 // a buffer kept with the scene (d_trace, d_calib), freed on the device it lives on once nothing there can still be using it
@@ -134,7 +75,7 @@ rt_scene* rt_scene_create(void) { return new rt_scene(); }
 
 void rt_scene_destroy(rt_scene* sc) {
     if (!sc) return;
-    for (void* f : sc->s.frames) ((Progressive*)f)->sc = nullptr;      // progressive frames outlive their scene (they own their buffers)
+    rt::frames_scene_gone(sc->s);                   // progressive frames outlive their scene (rt_frames.cpp)
     rt::multi_release(sc->s);
     free_on_device(sc->s.d_trace, sc->s.trace_device);
     free_on_device(sc->s.d_calib, sc->s.calib_device);
@@ -920,7 +861,10 @@ int render_impl(Scene& s, const rt_camera* camp, const double bg[3], uint32_t W,
     return 0;
 }
 
-int check_frame_args(rt_scene* sc, const rt_camera* cam, const double* bg, uint32_t W, uint32_t H, uint32_t spp) {
+} // namespace
+
+namespace rt {     // (what rt_frames.cpp shares: rt_host_shared.h)
+static int check_frame_args(rt_scene* sc, const rt_camera* cam, const double* bg, uint32_t W, uint32_t H, uint32_t spp) {
     if (!sc || !cam || !bg) return set_err("null argument");
     if (W < 2 || H < 2) return set_err("W and H must be >= 2 (u,v divide by W-1 and H-1, src/main.rs:817-818)");
     if (spp == 0) return set_err("samples_per_pixel must be >= 1");
@@ -936,6 +880,10 @@ int need_device_and_flat(Scene& s) {
 }
 int frame_prologue(rt_scene* sc, const rt_camera* cam, const double* bg, uint32_t W, uint32_t H, uint32_t spp) {
     return check_frame_args(sc, cam, bg, W, H, spp) ? -1 : need_device_and_flat(sc->s);
+}
+int query_aligned(const void* p, const char* what) {
+    if (((uintptr_t)p & 15u) != 0u) return set_err(std::string(what) + " must be 16-byte aligned");
+    return 0;
 }
 
 // Worlds that are ONE bare BVH: tune the filter tree's contraction for this view (rt_flatten.cpp tune_filter_tree: host arithmetic, < 1 ms)
@@ -1011,7 +959,7 @@ static int calibrate_loop_shape(Scene& s, const rt_camera* cam, const double bg[
 
 int render_any(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
                uint64_t seed, uint32_t flags, uint32_t tile_px, uint32_t rank, uint32_t world, void* d_out, size_t d_out_bytes,
-               void* d_samples, hipStream_t stream, bool may_calibrate, uint32_t first_sample = 0u, bool accumulate = false) {
+               void* d_samples, hipStream_t stream, bool may_calibrate, uint32_t first_sample, bool accumulate) {
     if (check_frame_args(sc, cam, bg, W, H, spp)) return -1;
     if (tile_px == 0 || world == 0 || rank >= world) return set_err("bad tile decomposition");
     if ((uint64_t)first_sample + spp > 0xFFFFFFFFull) return set_err("first_sample + samples_per_pixel must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
@@ -1029,7 +977,7 @@ int render_any(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t 
     return BY_PRECISION(flags, render_impl, sc->s, cam, bg, W, H, spp, max_depth, pass_seed, flags, tile_px, rank, world, d_out, d_out_bytes, d_samples, stream, accumulate);
 }
 
-} // namespace
+} // namespace rt
 
 extern "C" {
 
@@ -1521,10 +1469,6 @@ static int query_flags(uint32_t flags) {
     if (flags != 0u) return set_err("ray queries take flags = 0: they run in f64 and in the reference's traversal order (RT_F32 and every other flag: not supported)");
     return 0;
 }
-static int query_aligned(const void* p, const char* what) {
-    if (((uintptr_t)p & 15u) != 0u) return set_err(std::string(what) + " must be 16-byte aligned");
-    return 0;
-}
 // The LDS node cache of a query launch: P.n_cached / shmem for the filter tree staged whole or not at all, and the resident workgroups per CU
 // (`occupancy(shmem)`: the kernel's own) that go with it.
 extern "C++" {     // (a template inside this file's extern "C" block)
@@ -1883,391 +1827,32 @@ int rt_query_radiance(rt_scene* sc, uint32_t n, const double* rays, const double
     return 0;
 }
 
-// ---------------------------------------------------------------- progressive frames
-// (the reference's loop prints `Scanlines remaining` while it works, src/main.rs:772-775, and formats each pixel as it is finished,
-// src/main.rs:832: a frame that accumulates passes of samples and can be resolved to the 8-bit image at any time is that, per pass)
-// what a call that knows one sample count for the whole frame checks first on an adaptive frame
-static int adaptive_needs_uniform(const Progressive* p, const char* what) {
-    if (p && p->adaptive && !p->uniform)
-        return set_err(std::string(what) + ": the pixels of this adaptive frame hold different sample counts, and this call knows one count for the whole frame (rt_progressive_read_counts has them; rt_progressive_variance_counts and rt_progressive_resolve_denoised_frame_rgb8 take the frame as it is)");
-    return 0;
-}
-static void progressive_free(Progressive* p) {
-    DeviceGuard guard(p->device);
-    (void)hipDeviceSynchronize();                   // passes and resolves may still be in flight on the caller's streams
-    free_dev(p->d_sum); free_dev(p->d_rgb8[0]); free_dev(p->d_rgb8[1]); free_dev(p->d_changed);
-    free_dev(p->d_dn_ws); free_dev(p->d_dn_sum); free_dev(p->d_dn_rgb8); free_dev(p->d_dn_changed);
-    free_dev(p->d_alb_sum); free_dev(p->d_alb_x);
-    free_dev(p->d_sq); free_dev(p->d_pass); free_dev(p->d_e2); free_dev(p->d_mstats); free_dev(p->d_var);
-    free_dev(p->d_cnt); free_dev(p->d_pas); free_dev(p->d_list); free_dev(p->d_words); free_dev(p->d_sel_ws);
-    free_dev(p->d_fr_planes);
-    free_dev(p->d_hist_sum); free_dev(p->d_hist_cnt);
-    if (p->ev_merged) { (void)hipEventDestroy(p->ev_merged); p->ev_merged = nullptr; }
-}
-void* rt_progressive_create(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t max_depth,
-                            uint64_t seed, uint32_t flags) {
-    if (frame_prologue(sc, cam, bg, W, H, 1u)) return nullptr;
-    Progressive* p = new Progressive();
-    p->sc = sc; p->scene_version = sc->s.version; std::memcpy(&p->cam, cam, sizeof(rt_camera));
-    for (int k = 0; k < 3; k++) p->bg[k] = bg[k];
-    p->W = W; p->H = H; p->max_depth = max_depth; p->flags = flags; p->seed = seed;
-    const size_t n = p->n_px();
-    hipError_t e = hipGetDevice(&p->device);
-    if (e == hipSuccess) e = hipMalloc(&p->d_sum, n * 3 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&p->d_rgb8[0], n * 3);
-    if (e == hipSuccess) e = hipMalloc(&p->d_rgb8[1], n * 3);
-    if (e == hipSuccess) e = hipMalloc(&p->d_changed, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_sum, 0, n * 3 * sizeof(double), nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        set_err(std::string("rt_progressive_create: ") + hipGetErrorString(e));
-        if (p->device >= 0) progressive_free(p);
-        delete p; return nullptr;
-    }
-    sc->s.frames.push_back(p);
-    return p;
-}
-void rt_progressive_destroy(void* frame) {
-    Progressive* p = (Progressive*)frame;
-    if (!p) return;
-    if (p->sc) { std::vector<void*>& fr = p->sc->s.frames; fr.erase(std::remove(fr.begin(), fr.end(), (void*)p), fr.end()); }
-    progressive_free(p);
-    delete p;
-}
-// what both forms of a pass check before anything is launched
-static int progressive_pass_args(Progressive* p, uint32_t n) {
-    if (n == 0) return set_err("n_samples must be >= 1");
-    if (!p) return set_err("null argument");
-    if (!p->sc) return set_err("the scene of this progressive frame has been destroyed");
-    if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
-    if (p->done + n > 0xFFFFFFFFull) return set_err("samples done + n_samples must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
-    return 0;
-}
-static int progressive_pass(Progressive* p, uint32_t n, void* d_samples, hipStream_t stream, bool may_calibrate) {
-    const size_t n_px = p->n_px();
-    if (p->moments) {
-        // the pass frame is shared: this pass starts behind the merge of the one before it, whatever stream that was on (the host does not wait)
-        if (p->merge_recorded) HIP_OK(hipStreamWaitEvent(stream, p->ev_merged, 0));
-        if (render_any(p->sc, &p->cam, p->bg, p->W, p->H, n, p->max_depth, p->seed, p->flags, (uint32_t)n_px, 0, 1, p->d_pass, n_px * 3 * sizeof(double),
-                       d_samples, stream, may_calibrate, (uint32_t)p->done, true)) return -1;
-        HIP_OK((hipError_t)launch_moments_merge((double*)p->d_pass, n, (double*)p->d_sum, (double*)p->d_sq, (uint64_t)n_px * 3u, stream));
-        // (an adaptive frame comes here only while it is uniform: (C) over all pixels is the merge above and the counts)
-        if (p->adaptive) { HIP_OK((hipError_t)launch_adaptive_bump((uint32_t*)p->d_cnt, (uint32_t*)p->d_pas, n, (uint32_t)n_px, stream)); p->total += (uint64_t)n_px * n; }
-        HIP_OK(hipEventRecord(p->ev_merged, stream));
-        p->merge_recorded = true;
-        p->done += n; p->passes++;
-        return 0;
-    }
-    if (render_any(p->sc, &p->cam, p->bg, p->W, p->H, n, p->max_depth, p->seed, p->flags, (uint32_t)n_px, 0, 1, p->d_sum, n_px * 3 * sizeof(double),
-                   d_samples, stream, may_calibrate, (uint32_t)p->done, true)) return -1;
-    p->done += n;
-    return 0;
-}
-static int adaptive_pass_over_all(Progressive* p, uint32_t n, double* samples_out);
-int rt_progressive_add(void* frame, uint32_t n, double* samples_out) {
-    Progressive* p = (Progressive*)frame;
-    if (progressive_pass_args(p, n)) return -1;
-    if (p->adaptive && !p->uniform) return adaptive_pass_over_all(p, n, samples_out);
-    DeviceGuard guard(p->device);
-    DeviceBuffer d_samples;
-    const size_t sample_bytes = p->n_px() * n * 3 * sizeof(double);
-    if (samples_out) HIP_OK(d_samples.alloc(sample_bytes));
-    if (progressive_pass(p, n, d_samples.get(), nullptr, true)) return -1;
+int rt_render_samples(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
+                      uint64_t seed, uint32_t flags, double* rgb_sum_out, double* samples_out) {
+    if (!rgb_sum_out) return set_err("null output");
+    if (frame_prologue(sc, cam, bg, W, H, spp)) return -1;
+    const size_t n_px = (size_t)W * H, sum_bytes = n_px * 3 * sizeof(double), sample_bytes = sum_bytes * spp;
+    DeviceBuffer d_out, d_samples;
+    HIP_OK(d_out.alloc(sum_bytes));
+    if (samples_out) { const hipError_t e = d_samples.alloc(sample_bytes); if (e != hipSuccess) return set_err(std::string("hipMalloc(samples): ") + hipGetErrorString(e)); }
+    if (render_any(sc, cam, bg, W, H, spp, max_depth, seed, flags, (uint32_t)n_px, 0, 1, d_out.get(), sum_bytes, d_samples.get(), nullptr, true)) return -1;
     hipError_t e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = hipMemcpy(rgb_sum_out, d_out.get(), sum_bytes, hipMemcpyDeviceToHost);
     if (e == hipSuccess && samples_out) e = hipMemcpy(samples_out, d_samples.get(), sample_bytes, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? 0 : set_err(std::string("rt_progressive_add: ") + hipGetErrorString(e));
-}
-int rt_progressive_add_async(void* frame, uint32_t n, void* hip_stream) {
-    Progressive* p = (Progressive*)frame;
-    if (progressive_pass_args(p, n)) return -1;
-    if (p->adaptive) return set_err("rt_progressive_add_async: not available on an adaptive frame (a pass selects, renders, merges and waits: rt_progressive_add, rt_progressive_add_adaptive)");
-    DeviceGuard guard(p->device);
-    return progressive_pass(p, n, nullptr, (hipStream_t)hip_stream, false);
-}
-int rt_progressive_samples(void* frame, uint64_t* done_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !done_out) return set_err("null argument");
-    *done_out = p->done;
-    return 0;
-}
-int rt_progressive_resolve_rgb8_device(void* frame, void** d_rgb8_out, void* hip_stream) {
-    Progressive* p = (Progressive*)frame;
-    if (!p) return set_err("null argument");
-    if (p->done == 0) return set_err("nothing to resolve: the frame holds 0 samples (format_color divides by the sample count, src/vec.rs:126)");
-    DeviceGuard guard(p->device);
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const int next = 1 - p->cur;
-    HIP_OK(hipMemsetAsync(p->d_changed, 0, sizeof(unsigned long long), stream));
-    if (p->adaptive)
-        HIP_OK((hipError_t)launch_adaptive_resolve((const double*)p->d_sum, (const uint32_t*)p->d_cnt, p->have_prev ? (const uint8_t*)p->d_rgb8[p->cur] : nullptr,
-                                                   (uint8_t*)p->d_rgb8[next], (unsigned long long*)p->d_changed, (uint32_t)p->n_px(), stream));
-    else
-        HIP_OK(launch_resolve_rgb8((const double*)p->d_sum, p->done, p->have_prev ? (const uint8_t*)p->d_rgb8[p->cur] : nullptr, (uint8_t*)p->d_rgb8[next],
-                                   (unsigned long long*)p->d_changed, (uint32_t)p->n_px(), stream));
-    p->cur = next; p->have_prev = true; p->resolved = true;
-    if (d_rgb8_out) *d_rgb8_out = p->d_rgb8[next];
-    return 0;
-}
-int rt_progressive_copy_rgb8(void* frame, uint8_t* rgb8_out, uint64_t* changed_px_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !rgb8_out) return set_err("null argument");
-    if (!p->resolved) return set_err("the frame has not been resolved (rt_progressive_resolve_rgb8_device)");
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(rgb8_out, p->d_rgb8[p->cur], p->n_px() * 3, hipMemcpyDeviceToHost));
-    unsigned long long changed = 0;
-    HIP_OK(hipMemcpy(&changed, p->d_changed, sizeof(changed), hipMemcpyDeviceToHost));
-    if (changed_px_out) *changed_px_out = changed;
-    return 0;
-}
-int rt_progressive_resolve_rgb8(void* frame, uint8_t* rgb8_out, uint64_t* changed_px_out) {
-    if (!frame || !rgb8_out) return set_err("null argument");
-    {   // passes enqueued on the caller's streams (rt_progressive_add_async) belong to the image
-        DeviceGuard guard(((Progressive*)frame)->device);
-        HIP_OK(hipDeviceSynchronize());
-    }
-    if (rt_progressive_resolve_rgb8_device(frame, nullptr, nullptr)) return -1;
-    return rt_progressive_copy_rgb8(frame, rgb8_out, changed_px_out);
-}
-int rt_progressive_read_sum(void* frame, double* rgb_sum_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !rgb_sum_out) return set_err("null argument");
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(rgb_sum_out, p->d_sum, p->n_px() * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-static int progressive_restart(Progressive* p, const double* rgb_sum, uint64_t samples_done) {
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());                 // nothing of the old frame may still be adding to the buffer
-    if (rgb_sum) HIP_OK(hipMemcpy(p->d_sum, rgb_sum, p->n_px() * 3 * sizeof(double), hipMemcpyHostToDevice));
-    else { HIP_OK(hipMemsetAsync(p->d_sum, 0, p->n_px() * 3 * sizeof(double), nullptr)); HIP_OK(hipStreamSynchronize(nullptr)); }
-    p->done = samples_done; p->have_prev = false; p->resolved = false;       // the next resolve is a first one: every pixel counts as changed
-    if (p->moments) {
-        // a frame of sums alone (rt_progressive_load_sum) holds samples the second moments know nothing of: they are invalid until a reset
-        // or rt_progressive_load_moments; a reset starts them again.  The pass frame is +0.0 either way (a pass that failed half-way too).
-        p->moments_valid = rgb_sum == nullptr;
-        p->passes = 0;
-        HIP_OK(hipMemsetAsync(p->d_sq, 0, p->n_px() * 3 * sizeof(double), nullptr));
-        HIP_OK(hipMemsetAsync(p->d_pass, 0, p->n_px() * 3 * sizeof(double), nullptr));
-        if (p->adaptive) {                              // every pixel holds samples_done samples of 0 passes (the loads set the passes afterwards)
-            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)p->d_cnt, (int)(uint32_t)samples_done, p->n_px(), nullptr));
-            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)p->d_pas, 0, p->n_px(), nullptr));
-            p->uniform = true; p->total = (uint64_t)p->n_px() * samples_done;
-        }
-        HIP_OK(hipStreamSynchronize(nullptr));
-    }
-    return 0;
-}
-int rt_progressive_load_sum(void* frame, const double* rgb_sum, uint64_t samples_done) {
-    Progressive* p = (Progressive*)frame;
-    if (!rgb_sum) return set_err("null argument");
-    if (samples_done > 0xFFFFFFFFull) return set_err("samples_done must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
-    if (!p) return set_err("null argument");
-    if (adaptive_needs_uniform(p, "rt_progressive_load_sum")) return -1;
-    if (samples_done == 0) {                        // 0 samples is the empty frame and nothing else (-0.0 is not empty either: its bits are a checkpoint's)
-        const size_t n = p->n_px() * 3;
-        for (size_t i = 0; i < n; i++) { uint64_t w; std::memcpy(&w, rgb_sum + i, sizeof(w)); if (w != 0) return set_err("samples_done = 0 with a non-zero frame: a checkpoint is a sum AND its sample count"); }
-    }
-    return progressive_restart(p, rgb_sum, samples_done);
-}
-int rt_progressive_reset(void* frame) {
-    Progressive* p = (Progressive*)frame;
-    if (!p) return set_err("null argument");
-    if (p->sc) p->scene_version = p->sc->s.version;     // a new frame, of the scene as it is now
-    p->guide_valid = false;                             // ... and so is its denoising guide, rebuilt when it is next needed
-    p->albedo_samples = 0;                              // ... and its albedo sums
-    p->hist_valid = false; p->hist_px = 0;              // ... and the history of the views before it (rt_progressive_set_view keeps it)
-    return progressive_restart(p, nullptr, 0);
+    return e == hipSuccess ? 0 : set_err(std::string("copy back: ") + hipGetErrorString(e));
 }
 
-// ---------------------------------------------------------------- moments (csrc/rt_moments.h: the specification; rt_moments.hip: the kernels)
-int rt_moments_merge_device(void* d_pass_sum, uint64_t n_samples, void* d_rgb_sum, void* d_sq_sum, uint64_t n_doubles, void* hip_stream) {
-    if (!d_pass_sum || !d_rgb_sum || !d_sq_sum) return set_err("null argument");
-    const std::string problem = moments_merge_check(n_samples);
-    if (!problem.empty()) return set_err(problem);
-    if ((((uintptr_t)d_pass_sum | (uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum) & 7u) != 0u) return set_err("d_pass_sum, d_rgb_sum and d_sq_sum must be 8-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    HIP_OK((hipError_t)launch_moments_merge((double*)d_pass_sum, n_samples, (double*)d_rgb_sum, (double*)d_sq_sum, n_doubles, hip_stream));
-    return 0;
-}
-int rt_moments_error_device(const void* d_rgb_sum, const void* d_sq_sum, uint64_t samples, uint64_t passes, uint32_t W, uint32_t H,
-                            void* d_e2_out, double tau, void* d_stats_out, void* hip_stream) {
-    if (!d_rgb_sum || !d_sq_sum) return set_err("null argument");
-    std::string problem = moments_error_check(samples, passes, W, H);
-    if (problem.empty() && d_stats_out) problem = moments_tau_check(tau);
-    if (!problem.empty()) return set_err(problem);
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum | (uintptr_t)d_e2_out | (uintptr_t)d_stats_out) & 7u) != 0u) return set_err("d_rgb_sum, d_sq_sum, d_e2_out and d_stats_out must be 8-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    if (!d_e2_out && !d_stats_out) return 0;                    // nothing asked for
-    if (d_stats_out) HIP_OK(hipMemsetAsync(d_stats_out, 0, MOMENTS_STATS_WORDS * sizeof(uint64_t), (hipStream_t)hip_stream));
-    HIP_OK((hipError_t)launch_moments_error((const double*)d_rgb_sum, (const double*)d_sq_sum, samples, passes, W * H, (double*)d_e2_out, tau * tau,
-                                            (unsigned long long*)d_stats_out, hip_stream));
-    return 0;
-}
-int rt_progressive_enable_moments(void* frame) {
-    Progressive* p = (Progressive*)frame;
-    if (!p) return set_err("null argument");
-    if (p->moments) return 0;
-    if (p->done != 0) return set_err("moments can only be enabled while the frame holds 0 samples (the second moments must cover every sample of the sums): rt_progressive_reset first");
-    DeviceGuard guard(p->device);
-    const size_t bytes = p->n_px() * 3 * sizeof(double);
-    hipError_t e = hipMalloc(&p->d_sq, bytes);
-    if (e == hipSuccess) e = hipMalloc(&p->d_pass, bytes);
-    if (e == hipSuccess) e = hipMalloc(&p->d_mstats, MOMENTS_STATS_WORDS * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_merged, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_sq, 0, bytes, nullptr);
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_pass, 0, bytes, nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        free_dev(p->d_sq); free_dev(p->d_pass); free_dev(p->d_mstats);
-        if (p->ev_merged) { (void)hipEventDestroy(p->ev_merged); p->ev_merged = nullptr; }
-        return set_err(std::string("rt_progressive_enable_moments: ") + hipGetErrorString(e));
-    }
-    p->moments = true; p->moments_valid = true; p->merge_recorded = false; p->passes = 0;
-    return 0;
-}
-static int moments_frame(Progressive* p) {
-    if (!p) return set_err("null argument");
-    if (!p->moments) return set_err("this progressive frame has no moments (rt_progressive_enable_moments, while it holds 0 samples)");
-    return 0;
-}
-// what the three error calls check: moments that describe the sums, and two passes
-static int moments_error_ready(Progressive* p) {
-    if (moments_frame(p)) return -1;
-    if (!p->moments_valid) return set_err("the moments of this frame are invalid: rt_progressive_load_sum loaded sums whose second moments are unknown (rt_progressive_reset or rt_progressive_load_moments)");
-    const std::string problem = moments_error_check(p->done, p->passes, p->W, p->H);
-    return problem.empty() ? 0 : set_err(problem);
-}
-int rt_progressive_passes(void* frame, uint64_t* passes_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !passes_out) return set_err("null argument");
-    *passes_out = p->moments ? p->passes : 0u;
-    return 0;
-}
-int rt_progressive_read_moments(void* frame, double* sq_sum_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!sq_sum_out) return set_err("null argument");
-    if (moments_frame(p)) return -1;
-    if (!p->moments_valid) return set_err("the moments of this frame are invalid: rt_progressive_load_sum loaded sums whose second moments are unknown (rt_progressive_reset or rt_progressive_load_moments)");
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(sq_sum_out, p->d_sq, p->n_px() * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-int rt_progressive_load_moments(void* frame, const double* rgb_sum, const double* sq_sum, uint64_t samples_done, uint64_t passes) {
-    Progressive* p = (Progressive*)frame;
-    if (!rgb_sum || !sq_sum) return set_err("null argument");
-    if (moments_frame(p)) return -1;
-    if (adaptive_needs_uniform(p, "rt_progressive_load_moments")) return -1;
-    if (samples_done > 0xFFFFFFFFull) return set_err("samples_done must be <= 2^32 - 1 (the sample field of a path's RNG key is 32 bits, csrc/rt_rng.h)");
-    if (passes > samples_done) return set_err("passes must be <= samples_done: a pass holds at least one sample");
-    if ((samples_done == 0) != (passes == 0)) return set_err("samples_done = 0 and passes = 0 go together: a checkpoint is the sums, the second moments, the sample count AND the pass count");
-    if (samples_done == 0) {
-        const size_t n = p->n_px() * 3;
-        for (size_t i = 0; i < n; i++) {
-            uint64_t w, v; std::memcpy(&w, rgb_sum + i, sizeof(w)); std::memcpy(&v, sq_sum + i, sizeof(v));
-            if ((w | v) != 0) return set_err("samples_done = 0 with a non-zero frame: a checkpoint is the sums, the second moments, the sample count AND the pass count");
-        }
-    }
-    if (progressive_restart(p, rgb_sum, samples_done)) return -1;
-    DeviceGuard guard(p->device);
-    HIP_OK(hipMemcpy(p->d_sq, sq_sum, p->n_px() * 3 * sizeof(double), hipMemcpyHostToDevice));
-    if (p->adaptive) { HIP_OK(hipMemsetD32Async((hipDeviceptr_t)p->d_pas, (int)(uint32_t)passes, p->n_px(), nullptr)); HIP_OK(hipStreamSynchronize(nullptr)); }
-    p->passes = passes; p->moments_valid = true;
-    return 0;
-}
-int rt_progressive_error_map_device(void* frame, void** d_e2_out, void* hip_stream) {
-    Progressive* p = (Progressive*)frame;
-    if (moments_error_ready(p)) return -1;
-    DeviceGuard guard(p->device);
-    if (!p->d_e2) HIP_OK(hipMalloc(&p->d_e2, p->n_px() * sizeof(double)));
-    if (p->adaptive)
-        HIP_OK((hipError_t)launch_adaptive_error((const double*)p->d_sum, (const double*)p->d_sq, (const uint32_t*)p->d_cnt, (const uint32_t*)p->d_pas, (uint32_t)p->n_px(),
-                                                 (double*)p->d_e2, 0.0, nullptr, hip_stream));
-    else
-        HIP_OK((hipError_t)launch_moments_error((const double*)p->d_sum, (const double*)p->d_sq, p->done, p->passes, (uint32_t)p->n_px(), (double*)p->d_e2, 0.0, nullptr, hip_stream));
-    if (d_e2_out) *d_e2_out = p->d_e2;
-    return 0;
-}
-int rt_progressive_error_map(void* frame, double* e2_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!e2_out) return set_err("null argument");
-    if (moments_error_ready(p)) return -1;
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the estimate
-    if (rt_progressive_error_map_device(frame, nullptr, nullptr)) return -1;
-    HIP_OK(hipMemcpy(e2_out, p->d_e2, p->n_px() * sizeof(double), hipMemcpyDeviceToHost));      // (waits for the kernel: the null stream)
-    return 0;
-}
-int rt_progressive_error_stats(void* frame, double tau, uint64_t stats_out[4]) {
-    Progressive* p = (Progressive*)frame;
-    if (!stats_out) return set_err("null argument");
-    if (moments_error_ready(p)) return -1;
-    const std::string problem = moments_tau_check(tau);
-    if (!problem.empty()) return set_err(problem);
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemsetAsync(p->d_mstats, 0, MOMENTS_STATS_WORDS * sizeof(uint64_t), nullptr));
-    if (p->adaptive)
-        HIP_OK((hipError_t)launch_adaptive_error((const double*)p->d_sum, (const double*)p->d_sq, (const uint32_t*)p->d_cnt, (const uint32_t*)p->d_pas, (uint32_t)p->n_px(),
-                                                 nullptr, tau * tau, (unsigned long long*)p->d_mstats, nullptr));
-    else
-        HIP_OK((hipError_t)launch_moments_error((const double*)p->d_sum, (const double*)p->d_sq, p->done, p->passes, (uint32_t)p->n_px(), nullptr, tau * tau,
-                                                (unsigned long long*)p->d_mstats, nullptr));
-    HIP_OK(hipMemcpy(stats_out, p->d_mstats, MOMENTS_STATS_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return 0;
-}
-// (4) of rt_moments.h
-int rt_moments_variance_device(const void* d_rgb_sum, const void* d_sq_sum, uint64_t samples, uint64_t passes, uint32_t W, uint32_t H, void* d_var_out, void* hip_stream) {
-    if (!d_rgb_sum || !d_sq_sum || !d_var_out) return set_err("null argument");
-    const std::string problem = moments_error_check(samples, passes, W, H);
-    if (!problem.empty()) return set_err(problem);
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum | (uintptr_t)d_var_out) & 7u) != 0u) return set_err("d_rgb_sum, d_sq_sum and d_var_out must be 8-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    HIP_OK((hipError_t)launch_moments_variance((const double*)d_rgb_sum, (const double*)d_sq_sum, samples, passes, (uint64_t)W * H * 3u, (double*)d_var_out, hip_stream));
-    return 0;
-}
-// ... on the frame's own sums, into the frame's own variance frame, on `stream`
-static int progressive_variance_enqueue(Progressive* p, hipStream_t stream) {
-    if (!p->d_var) HIP_OK(hipMalloc(&p->d_var, p->n_px() * 3 * sizeof(double)));
-    HIP_OK((hipError_t)launch_moments_variance((const double*)p->d_sum, (const double*)p->d_sq, p->done, p->passes, (uint64_t)p->n_px() * 3u, (double*)p->d_var, stream));
-    return 0;
-}
-int rt_progressive_variance(void* frame, double* var_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!var_out) return set_err("null argument");
-    if (adaptive_needs_uniform(p, "rt_progressive_variance")) return -1;
-    if (moments_error_ready(p)) return -1;
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the estimate
-    if (progressive_variance_enqueue(p, nullptr)) return -1;
-    HIP_OK(hipMemcpy(var_out, p->d_var, p->n_px() * 3 * sizeof(double), hipMemcpyDeviceToHost));      // (waits for the kernel: the null stream)
-    return 0;
+int rt_render(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
+              uint64_t seed, uint32_t flags, double* rgb_sum_out) {
+    return rt_render_samples(sc, cam, bg, W, H, spp, max_depth, seed, flags, rgb_sum_out, nullptr);
 }
 
-// ---------------------------------------------------------------- adaptive frames (csrc/rt_adaptive.h: the specification; rt_adaptive.hip: the kernels)
-static int pixels_args(rt_scene* sc, const rt_camera* cam, const double* bg, uint32_t W, uint32_t H, uint32_t n_samples, uint32_t flags) {
-    if (!sc || !cam || !bg) return set_err("null argument");
-    if (W < 2 || H < 2) return set_err("W and H must be >= 2 (u,v divide by W-1 and H-1, src/main.rs:817-818)");
-    if ((uint64_t)W * H > 0x7FFFFFFFull) return set_err("frame too large: W*H must be <= 2^31 - 1 (per-path RNG keys, csrc/rt_rng.h)");
-    if (n_samples == 0) return set_err("n_samples must be >= 1");
-    if (flags & ~(uint32_t)(RT_STOP_ON_ZERO | RT_ISOTROPIC_SCATTER))
-        return set_err("pixel-list passes take RT_STOP_ON_ZERO and RT_ISOTROPIC_SCATTER only: they run in f64 and in the reference's traversal order (RT_F32 and every other flag: not supported)");
-    return 0;
-}
-int rt_render_pixels_device(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t n_samples, uint32_t max_depth,
-                            uint64_t seed, uint32_t flags, const void* d_list, uint32_t n_list, const void* d_counts, void* d_out, size_t d_out_bytes,
-                            void* hip_stream) {
-    if (pixels_args(sc, cam, bg, W, H, n_samples, flags)) return -1;
-    if (!d_out || (!d_list && n_list)) return set_err("null argument");
-    if (n_list > W * H) return set_err("n_list must be <= W * H: the list names each pixel at most once");
-    if (d_out_bytes < (size_t)W * H * 3u * sizeof(double)) return set_err("output buffer too small for W * H * 3 doubles (24 bytes per pixel)");
-    if (((uintptr_t)d_out & 7u) || ((uintptr_t)d_list & 3u) || ((uintptr_t)d_counts & 3u)) return set_err("d_out must be 8-byte aligned, d_list and d_counts 4-byte aligned");
-    Scene& s = sc->s;
-    if (need_device_and_flat(s)) return -1;
-    if (n_list == 0) return 0;
-    hipStream_t stream = (hipStream_t)hip_stream;
+} // extern "C"
+
+// The pixel-list kernel of adaptive frames (rt_pixels.h; rt_frames.cpp rt_render_pixels_device has checked the arguments): one launch on the
+// calling thread's current device, planned as a query launch is — the scene's f64 tables, the LDS node cache, the query event pair.
+int rt::launch_pixel_list(Scene& s, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t n_samples, uint32_t max_depth,
+                          uint64_t seed, uint32_t flags, const void* d_list, uint32_t n_list, const void* d_counts, void* d_out, hipStream_t stream) {
     Scene::DeviceCtx* cp = nullptr;
     if (current_ctx(s, &cp)) return -1;
     Scene::DeviceCtx& c = *cp;
@@ -2305,820 +1890,3 @@ int rt_render_pixels_device(rt_scene* sc, const rt_camera* cam, const double bg[
     s.q_recorded = true;
     return 0;
 }
-int rt_adaptive_error_device(const void* d_rgb_sum, const void* d_sq_sum, const void* d_counts, const void* d_passes, uint32_t W, uint32_t H,
-                             void* d_e2_out, double tau, void* d_stats_out, void* hip_stream) {
-    if (!d_rgb_sum || !d_sq_sum || !d_counts || !d_passes) return set_err("null argument");
-    std::string problem = adaptive_frame_check(W, H);
-    if (problem.empty() && d_stats_out) problem = moments_tau_check(tau);
-    if (!problem.empty()) return set_err(problem);
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum | (uintptr_t)d_e2_out | (uintptr_t)d_stats_out) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_passes) & 3u) != 0u)
-        return set_err("d_rgb_sum, d_sq_sum, d_e2_out and d_stats_out must be 8-byte aligned, d_counts and d_passes 4-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    if (!d_e2_out && !d_stats_out) return 0;                    // nothing asked for
-    if (d_stats_out) HIP_OK(hipMemsetAsync(d_stats_out, 0, MOMENTS_STATS_WORDS * sizeof(uint64_t), (hipStream_t)hip_stream));
-    HIP_OK((hipError_t)launch_adaptive_error((const double*)d_rgb_sum, (const double*)d_sq_sum, (const uint32_t*)d_counts, (const uint32_t*)d_passes, W * H,
-                                             (double*)d_e2_out, tau * tau, (unsigned long long*)d_stats_out, hip_stream));
-    return 0;
-}
-size_t rt_adaptive_select_workspace_bytes(uint32_t W, uint32_t H) { return adaptive_select_workspace_bytes((uint64_t)W * H); }
-int rt_adaptive_select_device(const void* d_rgb_sum, const void* d_sq_sum, const void* d_counts, const void* d_passes, uint32_t W, uint32_t H,
-                              uint32_t n_samples, double tau, uint64_t max_samples, uint32_t spread, void* d_list_out, void* d_n_list_out,
-                              void* d_workspace, size_t workspace_bytes, void* hip_stream) {
-    if (!d_rgb_sum || !d_sq_sum || !d_counts || !d_passes || !d_list_out || !d_n_list_out || !d_workspace) return set_err("null argument");
-    const std::string problem = adaptive_select_check(W, H, n_samples, tau, max_samples, spread);
-    if (!problem.empty()) return set_err(problem);
-    if (workspace_bytes < rt_adaptive_select_workspace_bytes(W, H)) return set_err("adaptive: workspace too small: rt_adaptive_select_workspace_bytes(W, H) bytes are needed");
-    if (query_aligned(d_workspace, "d_workspace")) return -1;
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_passes | (uintptr_t)d_list_out | (uintptr_t)d_n_list_out) & 3u) != 0u)
-        return set_err("d_rgb_sum and d_sq_sum must be 8-byte aligned, d_counts, d_passes, d_list_out and d_n_list_out 4-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    HIP_OK((hipError_t)launch_adaptive_select((const double*)d_rgb_sum, (const double*)d_sq_sum, (const uint32_t*)d_counts, (const uint32_t*)d_passes, W, H, n_samples,
-                                              tau * tau, max_samples, spread, (uint32_t*)d_list_out, (uint32_t*)d_n_list_out, d_workspace, hip_stream));
-    return 0;
-}
-int rt_adaptive_merge_device(void* d_pass_sum, uint32_t n_samples, void* d_rgb_sum, void* d_sq_sum, void* d_counts, void* d_passes, const void* d_list,
-                             uint32_t n_list, void* hip_stream) {
-    if (!d_pass_sum || !d_rgb_sum || !d_sq_sum || !d_counts || !d_passes || (!d_list && n_list)) return set_err("null argument");
-    if (n_samples == 0u) return set_err("adaptive: n_samples must be >= 1 (a pass's square is divided by its sample count)");
-    if (n_list > 0x7FFFFFFFu) return set_err("adaptive: n_list must be <= 2^31 - 1");
-    if ((((uintptr_t)d_pass_sum | (uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_passes | (uintptr_t)d_list) & 3u) != 0u)
-        return set_err("d_pass_sum, d_rgb_sum and d_sq_sum must be 8-byte aligned, d_counts, d_passes and d_list 4-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    HIP_OK((hipError_t)launch_adaptive_merge((double*)d_pass_sum, n_samples, (double*)d_rgb_sum, (double*)d_sq_sum, (uint32_t*)d_counts, (uint32_t*)d_passes,
-                                             (const uint32_t*)d_list, n_list, nullptr, hip_stream));
-    return 0;
-}
-int rt_adaptive_resolve_rgb8_device(const void* d_rgb_sum, const void* d_counts, uint32_t W, uint32_t H, const void* d_rgb8_prev, void* d_rgb8_out,
-                                    void* d_changed_px_out, void* hip_stream) {
-    if (!d_rgb_sum || !d_counts || !d_rgb8_out) return set_err("null argument");
-    const std::string problem = adaptive_frame_check(W, H);
-    if (!problem.empty()) return set_err(problem);
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_changed_px_out) & 7u) != 0u || ((uintptr_t)d_counts & 3u) != 0u) return set_err("d_rgb_sum and d_changed_px_out must be 8-byte aligned, d_counts 4-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    HIP_OK((hipError_t)launch_adaptive_resolve((const double*)d_rgb_sum, (const uint32_t*)d_counts, (const uint8_t*)d_rgb8_prev, (uint8_t*)d_rgb8_out,
-                                               (unsigned long long*)d_changed_px_out, W * H, hip_stream));
-    return 0;
-}
-
-static int adaptive_frame(Progressive* p) {
-    if (!p) return set_err("null argument");
-    if (!p->adaptive) return set_err("this progressive frame is not adaptive (rt_progressive_enable_adaptive, on a frame with moments while it holds 0 samples)");
-    return 0;
-}
-int rt_progressive_enable_adaptive(void* frame) {
-    Progressive* p = (Progressive*)frame;
-    if (moments_frame(p)) return -1;
-    if (p->adaptive) return 0;
-    if (p->done != 0) return set_err("adaptive sampling can only be enabled while the frame holds 0 samples (the counts must cover every sample of the sums): rt_progressive_reset first");
-    if (p->flags & ~(uint32_t)(RT_STOP_ON_ZERO | RT_ISOTROPIC_SCATTER))
-        return set_err("adaptive frames take RT_STOP_ON_ZERO and RT_ISOTROPIC_SCATTER only: the pixel-list kernel runs in f64 and in the reference's traversal order (RT_F32 and every other flag: not supported)");
-    DeviceGuard guard(p->device);
-    const size_t n = p->n_px();
-    hipError_t e = hipMalloc(&p->d_cnt, n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&p->d_pas, n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&p->d_list, n * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&p->d_words, 2 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&p->d_sel_ws, rt_adaptive_select_workspace_bytes(p->W, p->H));
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_cnt, 0, n * sizeof(uint32_t), nullptr);
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_pas, 0, n * sizeof(uint32_t), nullptr);
-    if (e == hipSuccess) e = hipMemsetAsync(p->d_words, 0, 2 * sizeof(uint32_t), nullptr);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        free_dev(p->d_cnt); free_dev(p->d_pas); free_dev(p->d_list); free_dev(p->d_words); free_dev(p->d_sel_ws);
-        return set_err(std::string("rt_progressive_enable_adaptive: ") + hipGetErrorString(e));
-    }
-    p->adaptive = true; p->uniform = true; p->total = 0;
-    return 0;
-}
-// one pass of n samples over the n_list pixels of the frame's list (already in d_list) through the list kernel, merged, waited for
-static int adaptive_list_pass(Progressive* p, uint32_t n, uint32_t n_list) {
-    const size_t n_px = p->n_px();
-    uint32_t* words = (uint32_t*)p->d_words;                    // [0] the list's length, [1] the largest count behind the merge
-    if (p->merge_recorded) HIP_OK(hipStreamWaitEvent(nullptr, p->ev_merged, 0));
-    if (rt_render_pixels_device(p->sc, &p->cam, p->bg, p->W, p->H, n, p->max_depth, p->seed, p->flags, p->d_list, n_list, p->d_cnt, p->d_pass,
-                                n_px * 3 * sizeof(double), nullptr)) return -1;
-    HIP_OK(hipMemsetAsync(words + 1, 0, sizeof(uint32_t), nullptr));
-    HIP_OK((hipError_t)launch_adaptive_merge((double*)p->d_pass, n, (double*)p->d_sum, (double*)p->d_sq, (uint32_t*)p->d_cnt, (uint32_t*)p->d_pas,
-                                             (const uint32_t*)p->d_list, n_list, words + 1, nullptr));
-    HIP_OK(hipEventRecord(p->ev_merged, nullptr));
-    p->merge_recorded = true;
-    uint32_t largest = 0;
-    HIP_OK(hipMemcpy(&largest, words + 1, sizeof(largest), hipMemcpyDeviceToHost));       // (waits for the pass: the null stream)
-    if (n_list != n_px) p->uniform = false;
-    if (largest > p->done) p->done = largest;
-    p->passes++; p->total += (uint64_t)n_list * n;
-    return 0;
-}
-// rt_progressive_add on an adaptive frame whose counts differ: a pass over all pixels through the list kernel
-static int adaptive_pass_over_all(Progressive* p, uint32_t n, double* samples_out) {
-    if (samples_out) return set_err("rt_progressive_add: samples_out is not available on an adaptive frame whose pixels hold different sample counts");
-    DeviceGuard guard(p->device);
-    const size_t n_px = p->n_px();
-    std::vector<uint32_t> all(n_px);
-    for (size_t i = 0; i < n_px; i++) all[i] = (uint32_t)i;
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(p->d_list, all.data(), n_px * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return adaptive_list_pass(p, n, (uint32_t)n_px);
-}
-int rt_progressive_add_adaptive(void* frame, uint32_t n, double tau, uint64_t max_samples, uint32_t spread, uint64_t info_out[4]) {
-    Progressive* p = (Progressive*)frame;
-    if (!info_out) return set_err("null argument");
-    if (adaptive_frame(p)) return -1;
-    if (max_samples == 0u) max_samples = ADAPTIVE_MAX_SAMPLES;
-    const std::string problem = adaptive_select_check(p->W, p->H, n, tau, max_samples, spread);
-    if (!problem.empty()) return set_err(problem);
-    if (!p->sc) return set_err("the scene of this progressive frame has been destroyed");
-    if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
-    if (!p->moments_valid) return set_err("the moments of this frame are invalid: rt_progressive_load_sum loaded sums whose second moments are unknown (rt_progressive_reset or rt_progressive_load_adaptive)");
-    DeviceGuard guard(p->device);
-    const size_t n_px = p->n_px();
-    uint32_t* words = (uint32_t*)p->d_words;
-    HIP_OK((hipError_t)launch_adaptive_select((const double*)p->d_sum, (const double*)p->d_sq, (const uint32_t*)p->d_cnt, (const uint32_t*)p->d_pas, p->W, p->H, n,
-                                              tau * tau, max_samples, spread, (uint32_t*)p->d_list, words, p->d_sel_ws, nullptr));
-    uint32_t n_list = 0;
-    HIP_OK(hipMemcpy(&n_list, words, sizeof(n_list), hipMemcpyDeviceToHost));             // (waits for the selection: the null stream)
-    info_out[0] = n_list; info_out[1] = (uint64_t)n_list * n; info_out[2] = p->total; info_out[3] = 0;
-    if (n_list == 0u) return 0;                                  // nothing listed: the stop condition
-    if (n_list == n_px && p->uniform) {                          // still a uniform frame: the frames' own kernels are the fast ones
-        if (progressive_pass(p, n, nullptr, nullptr, true)) return -1;
-        HIP_OK(hipStreamSynchronize(nullptr));
-    } else {
-        if (adaptive_list_pass(p, n, n_list)) return -1;
-        info_out[3] = 1;
-    }
-    info_out[2] = p->total;
-    return 0;
-}
-int rt_progressive_read_counts(void* frame, uint32_t* counts_out, uint32_t* passes_out) {
-    Progressive* p = (Progressive*)frame;
-    if (adaptive_frame(p)) return -1;
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());
-    if (counts_out) HIP_OK(hipMemcpy(counts_out, p->d_cnt, p->n_px() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (passes_out) HIP_OK(hipMemcpy(passes_out, p->d_pas, p->n_px() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return 0;
-}
-int rt_progressive_load_adaptive(void* frame, const double* rgb_sum, const double* sq_sum, const uint32_t* counts, const uint32_t* passes) {
-    Progressive* p = (Progressive*)frame;
-    if (!rgb_sum || !sq_sum || !counts || !passes) return set_err("null argument");
-    if (adaptive_frame(p)) return -1;
-    const size_t n_px = p->n_px();
-    uint32_t most = 0, most_b = 0; uint64_t total = 0; bool uniform = true;
-    for (size_t i = 0; i < n_px; i++) {
-        if (passes[i] > counts[i]) return set_err("passes must be <= counts for every pixel: a pass holds at least one sample");
-        if (counts[i] == 0u)
-            for (size_t k = 0; k < 3; k++) {
-                uint64_t w, v; std::memcpy(&w, rgb_sum + 3 * i + k, sizeof(w)); std::memcpy(&v, sq_sum + 3 * i + k, sizeof(v));
-                if ((w | v) != 0) return set_err("a pixel with count 0 that is not all zero: a checkpoint is the sums, the second moments AND the counts");
-            }
-        if (counts[i] != counts[0] || passes[i] != passes[0]) uniform = false;
-        if (counts[i] > most) most = counts[i];
-        if (passes[i] > most_b) most_b = passes[i];
-        total += counts[i];
-    }
-    if (progressive_restart(p, rgb_sum, most)) return -1;
-    DeviceGuard guard(p->device);
-    HIP_OK(hipMemcpy(p->d_sq, sq_sum, n_px * 3 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(p->d_cnt, counts, n_px * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(p->d_pas, passes, n_px * sizeof(uint32_t), hipMemcpyHostToDevice));
-    p->passes = most_b; p->moments_valid = true; p->uniform = uniform; p->total = total;
-    return 0;
-}
-
-// ---------------------------------------------------------------- denoiser (csrc/rt_denoise.h: the specification; rt_denoise.hip: the kernels)
-size_t rt_denoise_workspace_bytes(uint32_t W, uint32_t H) { return (size_t)W * H * DENOISE_WORKSPACE_BYTES_PER_PX; }
-
-// The launches of one run, enqueued on `stream`: pack (the colour always; the guide when d_hits is given — a progressive frame brings a guide
-// it packed earlier), then the iterations, alternating between the workspace's two colour frames, the last one writing sums to d_out.
-// The workspace is {colour A, colour B, guide}: 32 + 32 + 64 bytes per pixel.
-// `marks` (rt_debug_denoise_ms only): iterations + 2 events, recorded in front of every launch and behind the last.
-static int denoise_enqueue(const double* d_sum, uint64_t samples, const double* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
-                           const double sigma[3], uint32_t flags, double* d_out, void* d_workspace, hipStream_t stream, hipEvent_t* marks = nullptr) {
-    const size_t n = (size_t)W * H;
-    double* color[2] = {(double*)d_workspace, (double*)d_workspace + n * DENOISE_COLOR_DOUBLES};
-    double* guide = (double*)d_workspace + 2u * n * DENOISE_COLOR_DOUBLES;
-    double inv[3];
-    denoise_inverse_squares(sigma, inv);
-    if (marks) HIP_OK(hipEventRecord(marks[0], stream));
-    HIP_OK((hipError_t)launch_denoise_pack(d_sum, samples, d_hits, flags, color[0], guide, (uint32_t)n, stream));
-    for (uint32_t i = 0; i < iterations; i++) {
-        const bool last = i + 1u == iterations;
-        if (marks) HIP_OK(hipEventRecord(marks[i + 1u], stream));
-        HIP_OK((hipError_t)launch_denoise_filter(color[i & 1u], guide, last ? nullptr : color[(i + 1u) & 1u], last ? d_out : nullptr, W, H, 1u << i,
-                                                 inv[0] * (double)(1ull << (2u * i)), inv[1], inv[2], samples, stream));
-    }
-    if (marks) HIP_OK(hipEventRecord(marks[iterations + 1u], stream));
-    return 0;
-}
-int rt_denoise_device(const void* d_rgb_sum, uint64_t samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
-                      const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
-    if (!d_rgb_sum || !d_hits || !sigma || !d_rgb_sum_out || !d_workspace) return set_err("null argument");
-    const std::string problem = denoise_check(samples, W, H, iterations, sigma, flags);
-    if (!problem.empty()) return set_err(problem);
-    if (workspace_bytes < rt_denoise_workspace_bytes(W, H)) return set_err("denoise: workspace too small: rt_denoise_workspace_bytes(W, H) = 128 bytes per pixel are needed");
-    if (query_aligned(d_hits, "d_hits") || query_aligned(d_workspace, "d_workspace")) return -1;
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_rgb_sum_out) & 7u) != 0u) return set_err("d_rgb_sum and d_rgb_sum_out must be 8-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    return denoise_enqueue((const double*)d_rgb_sum, samples, (const double*)d_hits, W, H, iterations, sigma, flags, (double*)d_rgb_sum_out,
-                           d_workspace, (hipStream_t)hip_stream);
-}
-int rt_denoise(const double* rgb_sum, uint64_t samples, const double* hits, uint32_t W, uint32_t H, uint32_t iterations,
-               const double sigma[3], uint32_t flags, double* rgb_sum_out) {
-    if (!rgb_sum || !hits || !sigma || !rgb_sum_out) return set_err("null argument");
-    const std::string problem = denoise_check(samples, W, H, iterations, sigma, flags);
-    if (!problem.empty()) return set_err(problem);
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
-    DeviceBuffer d_sum, d_hits, d_ws;
-    HIP_OK(d_sum.alloc(sum_bytes)); HIP_OK(d_hits.alloc(hit_bytes)); HIP_OK(d_ws.alloc(rt_denoise_workspace_bytes(W, H)));
-    HIP_OK(hipMemcpy(d_sum.get(), rgb_sum, sum_bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_hits.get(), hits, hit_bytes, hipMemcpyHostToDevice));
-    if (rt_denoise_device(d_sum.get(), samples, d_hits.get(), W, H, iterations, sigma, flags, d_sum.get(), d_ws.get(), rt_denoise_workspace_bytes(W, H), nullptr)) return -1;
-    HIP_OK(hipMemcpy(rgb_sum_out, d_sum.get(), sum_bytes, hipMemcpyDeviceToHost));       // (waits for the kernels: the null stream)
-    return 0;
-}
-int rt_debug_denoise_ms(const void* d_rgb_sum, uint64_t samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
-                        const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, float* ms_out) {
-    if (!ms_out) return set_err("null argument");
-    hipEvent_t marks[DENOISE_MAX_ITERATIONS + 2u] = {};
-    const uint32_t n_marks = (iterations <= DENOISE_MAX_ITERATIONS ? iterations : 0u) + 2u;
-    int rc = 0;
-    for (uint32_t k = 0; k < n_marks && rc == 0; k++) if (hipEventCreate(&marks[k]) != hipSuccess) rc = set_err("hipEventCreate failed");
-    // (the arguments are rt_denoise_device's and are checked there; nothing is recorded for a refused call)
-    if (rc == 0) {
-        if (!d_rgb_sum || !d_hits || !sigma || !d_rgb_sum_out || !d_workspace) rc = set_err("null argument");
-        else if (rt_denoise_device(d_rgb_sum, samples, d_hits, W, H, iterations, sigma, flags, d_rgb_sum_out, d_workspace, workspace_bytes, nullptr)) rc = -1;     // the checks, and a warm run
-        else rc = denoise_enqueue((const double*)d_rgb_sum, samples, (const double*)d_hits, W, H, iterations, sigma, flags, (double*)d_rgb_sum_out, d_workspace, nullptr, marks);
-    }
-    if (rc == 0 && hipEventSynchronize(marks[iterations + 1u]) != hipSuccess) rc = set_err("hipEventSynchronize failed");
-    for (uint32_t k = 0; k <= iterations && rc == 0; k++) if (hipEventElapsedTime(&ms_out[k], marks[k], marks[k + 1u]) != hipSuccess) rc = set_err("hipEventElapsedTime failed");
-    for (uint32_t k = 0; k < n_marks; k++) if (marks[k]) (void)hipEventDestroy(marks[k]);
-    return rc;
-}
-// What every denoised resolve does before it filters: the checks, the frame's own buffers, and the packed guide — sample 0's camera hits of
-// this view or, with guide_samples > 1, the averaged record of samples [0, guide_samples) (rt_guide.h), keyed for `flags` — in its place in
-// the workspace.  allow_no_samples: the temporal resolve's, which has a history to show while the frame holds 0 samples.
-static int progressive_denoise_prepare(Progressive* p, uint32_t iterations, const double sigma[3], uint32_t flags, bool allow_no_samples = false) {
-    const std::string problem = denoise_check(p->done ? p->done : 1u, p->W, p->H, iterations, sigma, flags);
-    if (!problem.empty()) return set_err(problem);
-    if (p->done == 0 && !allow_no_samples) return set_err("nothing to resolve: the frame holds 0 samples (format_color divides by the sample count, src/vec.rs:126)");
-    HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the image
-    const size_t n = p->n_px();
-    if (!p->guide_valid || p->guide_flags != flags) {
-        if (!p->sc) return set_err("the scene of this progressive frame has been destroyed and the frame holds no denoising guide for these flags: the guide is built from the scene (rt_query_camera_device)");
-        if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
-    }
-    if (!p->d_dn_ws) HIP_OK(hipMalloc(&p->d_dn_ws, rt_denoise_workspace_bytes(p->W, p->H)));
-    if (!p->d_dn_sum) HIP_OK(hipMalloc(&p->d_dn_sum, n * 3 * sizeof(double)));
-    if (!p->d_dn_rgb8) HIP_OK(hipMalloc(&p->d_dn_rgb8, n * 3));
-    if (!p->d_dn_changed) HIP_OK(hipMalloc(&p->d_dn_changed, sizeof(unsigned long long)));
-    if (!p->guide_valid || p->guide_flags != flags) {           // the guide's records of this view, packed; the records themselves are not kept
-        const size_t hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
-        DeviceBuffer d_hits;
-        HIP_OK(d_hits.alloc(hit_bytes));
-        p->guide_valid = false;
-        if (p->guide_samples == 1u) { if (rt_query_camera_device(p->sc, &p->cam, p->W, p->H, 0u, p->seed, 0u, nullptr, d_hits.get(), hit_bytes, nullptr)) return -1; }
-        else if (rt_query_camera_guide_device(p->sc, &p->cam, p->W, p->H, 0u, p->guide_samples, p->seed, 0u, d_hits.get(), hit_bytes, nullptr, 0u, nullptr)) return -1;
-        HIP_OK((hipError_t)launch_denoise_pack(nullptr, 1u, (const double*)d_hits.get(), flags, nullptr, (double*)p->d_dn_ws + 2u * n * DENOISE_COLOR_DOUBLES, (uint32_t)n, nullptr));
-        HIP_OK(hipStreamSynchronize(nullptr));
-        p->guide_valid = true; p->guide_flags = flags; p->guide_builds++;
-    }
-    return 0;
-}
-int rt_progressive_set_guide_samples(void* frame, uint32_t n_samples) {
-    Progressive* p = (Progressive*)frame;
-    if (!p) return set_err("null argument");
-    if (n_samples == 0u) return set_err("guide_samples must be >= 1 (1: the camera hits of sample 0; n: the averaged record of samples 0 .. n - 1)");
-    if (n_samples != p->guide_samples) { p->guide_samples = n_samples; p->guide_valid = false; }
-    return 0;
-}
-int rt_progressive_guide_info(void* frame, uint32_t* guide_samples_out, uint64_t* builds_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !guide_samples_out || !builds_out) return set_err("null argument");
-    *guide_samples_out = p->guide_samples; *builds_out = p->guide_builds;
-    return 0;
-}
-// ... and after: the filtered sums in d_dn_sum resolved and copied out
-static int progressive_denoise_finish(Progressive* p, uint8_t* rgb8_out) {
-    const size_t n = p->n_px();
-    HIP_OK(hipMemsetAsync(p->d_dn_changed, 0, sizeof(unsigned long long), nullptr));
-    HIP_OK(launch_resolve_rgb8((const double*)p->d_dn_sum, p->done, nullptr, (uint8_t*)p->d_dn_rgb8, (unsigned long long*)p->d_dn_changed, (uint32_t)n, nullptr));
-    HIP_OK(hipMemcpy(rgb8_out, p->d_dn_rgb8, n * 3, hipMemcpyDeviceToHost));             // (waits for the kernels: the null stream)
-    return 0;
-}
-// The frame's sums filtered and resolved, into buffers of the frame's own: d_sum, the plain resolve's two images and its count stay as they are.
-int rt_progressive_resolve_denoised_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !sigma || !rgb8_out) return set_err("null argument");
-    if (adaptive_needs_uniform(p, "rt_progressive_resolve_denoised_rgb8")) return -1;
-    DeviceGuard guard(p->device);
-    if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
-    if (denoise_enqueue((const double*)p->d_sum, p->done, nullptr, p->W, p->H, iterations, sigma, flags, (double*)p->d_dn_sum, p->d_dn_ws, nullptr)) return -1;
-    return progressive_denoise_finish(p, rgb8_out);
-}
-
-// ---------------------------------------------------------------- variance-guided denoising (csrc/rt_denoise_var.h: the specification; rt_denoise_var.hip: the kernels)
-size_t rt_denoise_variance_workspace_bytes(uint32_t W, uint32_t H) { return rt_denoise_workspace_bytes(W, H); }
-
-// The launches of one run on `stream`, in denoise_enqueue's workspace {colour A, colour B, guide}: the guide when d_hits is given, the pack
-// into B, the prefilter of v from B to A, then the iterations alternating from A, the last one writing sums to d_out and v to d_var_out.
-static int denoise_variance_enqueue(const double* d_sum, uint64_t samples, const double* d_var, const double* d_hits, uint32_t W, uint32_t H,
-                                    uint32_t iterations, const double sigma[3], uint32_t flags, double* d_out, double* d_var_out, void* d_workspace,
-                                    hipStream_t stream, hipEvent_t* marks = nullptr) {
-    const size_t n = (size_t)W * H;
-    double* color[2] = {(double*)d_workspace, (double*)d_workspace + n * DENOISE_COLOR_DOUBLES};
-    double* guide = (double*)d_workspace + 2u * n * DENOISE_COLOR_DOUBLES;
-    double inv[3];
-    denoise_inverse_squares(sigma, inv);
-    const double kv = sigma[0] * sigma[0];
-    if (marks) HIP_OK(hipEventRecord(marks[0], stream));
-    if (d_hits) HIP_OK((hipError_t)launch_denoise_pack(nullptr, samples, d_hits, flags, nullptr, guide, (uint32_t)n, stream));
-    HIP_OK((hipError_t)launch_denoise_var_pack(d_sum, samples, d_var, color[1], (uint32_t)n, stream));
-    if (marks) HIP_OK(hipEventRecord(marks[1], stream));
-    HIP_OK((hipError_t)launch_denoise_var_prefilter(color[1], guide, color[0], W, H, stream));
-    for (uint32_t i = 0; i < iterations; i++) {
-        const bool last = i + 1u == iterations;
-        if (marks) HIP_OK(hipEventRecord(marks[i + 2u], stream));
-        HIP_OK((hipError_t)launch_denoise_var_filter(color[i & 1u], guide, last ? nullptr : color[(i + 1u) & 1u], last ? d_out : nullptr, last ? d_var_out : nullptr,
-                                                     W, H, 1u << i, kv, inv[1], inv[2], samples, stream));
-    }
-    if (marks) HIP_OK(hipEventRecord(marks[iterations + 2u], stream));
-    return 0;
-}
-int rt_denoise_variance_device(const void* d_rgb_sum, uint64_t samples, const void* d_var, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
-                               const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_var_out, void* d_workspace, size_t workspace_bytes,
-                               void* hip_stream) {
-    if (!d_rgb_sum || !d_var || !d_hits || !sigma || !d_rgb_sum_out || !d_workspace) return set_err("null argument");
-    const std::string problem = denoise_variance_check(samples, W, H, iterations, sigma, flags);
-    if (!problem.empty()) return set_err(problem);
-    if (workspace_bytes < rt_denoise_variance_workspace_bytes(W, H)) return set_err("denoise: workspace too small: rt_denoise_variance_workspace_bytes(W, H) = 128 bytes per pixel are needed");
-    if (query_aligned(d_hits, "d_hits") || query_aligned(d_workspace, "d_workspace")) return -1;
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_rgb_sum_out | (uintptr_t)d_var | (uintptr_t)d_var_out) & 7u) != 0u) return set_err("d_rgb_sum, d_var, d_rgb_sum_out and d_var_out must be 8-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    return denoise_variance_enqueue((const double*)d_rgb_sum, samples, (const double*)d_var, (const double*)d_hits, W, H, iterations, sigma, flags,
-                                    (double*)d_rgb_sum_out, (double*)d_var_out, d_workspace, (hipStream_t)hip_stream);
-}
-int rt_denoise_variance(const double* rgb_sum, uint64_t samples, const double* var, const double* hits, uint32_t W, uint32_t H, uint32_t iterations,
-                        const double sigma[3], uint32_t flags, double* rgb_sum_out, double* var_out) {
-    if (!rgb_sum || !var || !hits || !sigma || !rgb_sum_out) return set_err("null argument");
-    const std::string problem = denoise_variance_check(samples, W, H, iterations, sigma, flags);
-    if (!problem.empty()) return set_err(problem);
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
-    const size_t ws_bytes = rt_denoise_variance_workspace_bytes(W, H);
-    DeviceBuffer d_sum, d_var, d_hits, d_ws, d_vout;
-    HIP_OK(d_sum.alloc(sum_bytes)); HIP_OK(d_var.alloc(sum_bytes)); HIP_OK(d_hits.alloc(hit_bytes)); HIP_OK(d_ws.alloc(ws_bytes));
-    if (var_out) HIP_OK(d_vout.alloc(n * sizeof(double)));
-    HIP_OK(hipMemcpy(d_sum.get(), rgb_sum, sum_bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_var.get(), var, sum_bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_hits.get(), hits, hit_bytes, hipMemcpyHostToDevice));
-    if (rt_denoise_variance_device(d_sum.get(), samples, d_var.get(), d_hits.get(), W, H, iterations, sigma, flags, d_sum.get(), var_out ? d_vout.get() : nullptr,
-                                   d_ws.get(), ws_bytes, nullptr)) return -1;
-    HIP_OK(hipMemcpy(rgb_sum_out, d_sum.get(), sum_bytes, hipMemcpyDeviceToHost));       // (waits for the kernels: the null stream)
-    if (var_out) HIP_OK(hipMemcpy(var_out, d_vout.get(), n * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-int rt_debug_denoise_variance_ms(const void* d_rgb_sum, uint64_t samples, const void* d_var, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations,
-                                 const double sigma[3], uint32_t flags, void* d_rgb_sum_out, void* d_workspace, size_t workspace_bytes, float* ms_out) {
-    if (!ms_out) return set_err("null argument");
-    hipEvent_t marks[DENOISE_MAX_ITERATIONS + 3u] = {};
-    const uint32_t n_marks = (iterations <= DENOISE_MAX_ITERATIONS ? iterations : 0u) + 3u;
-    int rc = 0;
-    for (uint32_t k = 0; k < n_marks && rc == 0; k++) if (hipEventCreate(&marks[k]) != hipSuccess) rc = set_err("hipEventCreate failed");
-    // (the arguments are rt_denoise_variance_device's and are checked there; nothing is recorded for a refused call)
-    if (rc == 0) {
-        if (rt_denoise_variance_device(d_rgb_sum, samples, d_var, d_hits, W, H, iterations, sigma, flags, d_rgb_sum_out, nullptr, d_workspace, workspace_bytes, nullptr)) rc = -1;     // the checks, and a warm run
-        else rc = denoise_variance_enqueue((const double*)d_rgb_sum, samples, (const double*)d_var, (const double*)d_hits, W, H, iterations, sigma, flags,
-                                           (double*)d_rgb_sum_out, nullptr, d_workspace, nullptr, marks);
-    }
-    if (rc == 0 && hipEventSynchronize(marks[iterations + 2u]) != hipSuccess) rc = set_err("hipEventSynchronize failed");
-    for (uint32_t k = 0; k <= iterations + 1u && rc == 0; k++) if (hipEventElapsedTime(&ms_out[k], marks[k], marks[k + 1u]) != hipSuccess) rc = set_err("hipEventElapsedTime failed");
-    for (uint32_t k = 0; k < n_marks; k++) if (marks[k]) (void)hipEventDestroy(marks[k]);
-    return rc;
-}
-// The frame's sums filtered under the guidance of the frame's own variance, and resolved; everything the other resolves own stays as it is.
-int rt_progressive_resolve_denoised_variance_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !sigma || !rgb8_out) return set_err("null argument");
-    if (adaptive_needs_uniform(p, "rt_progressive_resolve_denoised_variance_rgb8")) return -1;
-    if (moments_error_ready(p)) return -1;
-    const std::string problem = denoise_variance_check(p->done, p->W, p->H, iterations, sigma, flags);
-    if (!problem.empty()) return set_err(problem);
-    DeviceGuard guard(p->device);
-    if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
-    if (progressive_variance_enqueue(p, nullptr)) return -1;
-    if (denoise_variance_enqueue((const double*)p->d_sum, p->done, (const double*)p->d_var, nullptr, p->W, p->H, iterations, sigma, flags, (double*)p->d_dn_sum,
-                                 nullptr, p->d_dn_ws, nullptr)) return -1;
-    return progressive_denoise_finish(p, rgb8_out);
-}
-
-// ---------------------------------------------------------------- albedo-demodulated denoising (csrc/rt_albedo.h (2))
-size_t rt_denoise_albedo_workspace_bytes(uint32_t W, uint32_t H) { return (size_t)W * H * DENOISE_ALBEDO_WORKSPACE_BYTES_PER_PX; }
-
-// The launches of one run on `stream`: demodulate into d_x, the filter's own launches from d_x to d_out, remodulate d_out in place.
-// d_out may be d_sum: the demodulate kernel has read it by the time anything is written there (stream order).
-static int denoise_albedo_enqueue(const double* d_sum, uint64_t samples, const double* d_albedo_sum, uint64_t albedo_samples, const double* d_hits,
-                                  uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3], uint32_t flags, double* d_out,
-                                  void* d_workspace, double* d_x, hipStream_t stream) {
-    const uint64_t n = (uint64_t)W * H * 3u;
-    HIP_OK((hipError_t)launch_albedo_demodulate(d_sum, d_albedo_sum, albedo_samples, d_x, n, stream));
-    if (denoise_enqueue(d_x, samples, d_hits, W, H, iterations, sigma, flags, d_out, d_workspace, stream)) return -1;
-    HIP_OK((hipError_t)launch_albedo_remodulate(d_out, d_albedo_sum, albedo_samples, n, stream));
-    return 0;
-}
-int rt_denoise_albedo_device(const void* d_rgb_sum, uint64_t samples, const void* d_albedo_sum, uint64_t albedo_samples, const void* d_hits,
-                             uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3], uint32_t flags, void* d_rgb_sum_out,
-                             void* d_workspace, size_t workspace_bytes, void* hip_stream) {
-    if (!d_rgb_sum || !d_albedo_sum || !d_hits || !sigma || !d_rgb_sum_out || !d_workspace) return set_err("null argument");
-    const std::string problem = denoise_albedo_check(samples, albedo_samples, W, H, iterations, sigma, flags);
-    if (!problem.empty()) return set_err(problem);
-    if (workspace_bytes < rt_denoise_albedo_workspace_bytes(W, H)) return set_err("denoise: workspace too small: rt_denoise_albedo_workspace_bytes(W, H) = 152 bytes per pixel are needed");
-    if (query_aligned(d_hits, "d_hits") || query_aligned(d_workspace, "d_workspace")) return -1;
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_rgb_sum_out | (uintptr_t)d_albedo_sum) & 7u) != 0u) return set_err("d_rgb_sum, d_albedo_sum and d_rgb_sum_out must be 8-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    double* d_x = (double*)((unsigned char*)d_workspace + rt_denoise_workspace_bytes(W, H));
-    return denoise_albedo_enqueue((const double*)d_rgb_sum, samples, (const double*)d_albedo_sum, albedo_samples, (const double*)d_hits, W, H, iterations,
-                                  sigma, flags, (double*)d_rgb_sum_out, d_workspace, d_x, (hipStream_t)hip_stream);
-}
-int rt_denoise_albedo(const double* rgb_sum, uint64_t samples, const double* albedo_sum, uint64_t albedo_samples, const double* hits,
-                      uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3], uint32_t flags, double* rgb_sum_out) {
-    if (!rgb_sum || !albedo_sum || !hits || !sigma || !rgb_sum_out) return set_err("null argument");
-    const std::string problem = denoise_albedo_check(samples, albedo_samples, W, H, iterations, sigma, flags);
-    if (!problem.empty()) return set_err(problem);
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
-    const size_t ws_bytes = rt_denoise_albedo_workspace_bytes(W, H);
-    DeviceBuffer d_sum, d_alb, d_hits, d_ws;
-    HIP_OK(d_sum.alloc(sum_bytes)); HIP_OK(d_alb.alloc(sum_bytes)); HIP_OK(d_hits.alloc(hit_bytes)); HIP_OK(d_ws.alloc(ws_bytes));
-    HIP_OK(hipMemcpy(d_sum.get(), rgb_sum, sum_bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_alb.get(), albedo_sum, sum_bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_hits.get(), hits, hit_bytes, hipMemcpyHostToDevice));
-    if (rt_denoise_albedo_device(d_sum.get(), samples, d_alb.get(), albedo_samples, d_hits.get(), W, H, iterations, sigma, flags, d_sum.get(), d_ws.get(), ws_bytes, nullptr)) return -1;
-    HIP_OK(hipMemcpy(rgb_sum_out, d_sum.get(), sum_bytes, hipMemcpyDeviceToHost));       // (waits for the kernels: the null stream)
-    return 0;
-}
-// The frame's sums demodulated by its own albedo frame, filtered, remodulated and resolved; everything the other resolves own stays as it is.
-int rt_progressive_resolve_denoised_albedo_rgb8(void* frame, uint32_t albedo_samples, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !sigma || !rgb8_out) return set_err("null argument");
-    if (albedo_samples == 0u) return set_err("denoise: albedo_samples must be >= 1 (the frame is demodulated by albedo_sum / albedo_samples)");
-    if (adaptive_needs_uniform(p, "rt_progressive_resolve_denoised_albedo_rgb8")) return -1;
-    DeviceGuard guard(p->device);
-    if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
-    const size_t n = p->n_px(), sum_bytes = n * 3 * sizeof(double);
-    if (p->albedo_samples != albedo_samples) {
-        if (!p->sc) return set_err("the scene of this progressive frame has been destroyed and the frame holds no albedo sums for this albedo_samples: they are built from the scene (rt_query_camera_albedo_device)");
-        if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
-    }
-    if (!p->d_alb_sum) HIP_OK(hipMalloc(&p->d_alb_sum, sum_bytes));
-    if (!p->d_alb_x) HIP_OK(hipMalloc(&p->d_alb_x, sum_bytes));
-    if (p->albedo_samples != albedo_samples) {
-        p->albedo_samples = 0;
-        if (rt_query_camera_albedo_device(p->sc, &p->cam, p->W, p->H, 0u, albedo_samples, p->seed, 0u, p->d_alb_sum, sum_bytes, nullptr)) return -1;
-        p->albedo_samples = albedo_samples; p->albedo_builds++;
-    }
-    if (denoise_albedo_enqueue((const double*)p->d_sum, p->done, (const double*)p->d_alb_sum, albedo_samples, nullptr, p->W, p->H, iterations, sigma, flags,
-                               (double*)p->d_dn_sum, p->d_dn_ws, (double*)p->d_alb_x, nullptr)) return -1;
-    return progressive_denoise_finish(p, rgb8_out);
-}
-int rt_debug_albedo_modulate_ms(const void* d_rgb_sum, const void* d_albedo_sum, uint64_t albedo_samples, void* d_x, uint64_t n_doubles, float ms_out[2]) {
-    if (!d_rgb_sum || !d_albedo_sum || !d_x || !ms_out) return set_err("null argument");
-    if (albedo_samples == 0u || n_doubles == 0u || n_doubles > 3ull * 0x7FFFFFFFull) return set_err("albedo_samples and n_doubles must be >= 1 (n_doubles <= 3 (2^31 - 1))");
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_albedo_sum | (uintptr_t)d_x) & 7u) != 0u) return set_err("the buffers must be 8-byte aligned");
-    hipEvent_t marks[3] = {};
-    int rc = 0;
-    for (int k = 0; k < 3 && rc == 0; k++) if (hipEventCreate(&marks[k]) != hipSuccess) rc = set_err("hipEventCreate failed");
-    for (int pass = 0; pass < 2 && rc == 0; pass++) {             // a warm run, then the one that is timed
-        if (hipEventRecord(marks[0], nullptr) != hipSuccess || launch_albedo_demodulate((const double*)d_rgb_sum, (const double*)d_albedo_sum, albedo_samples, (double*)d_x, n_doubles, nullptr) != 0 ||
-            hipEventRecord(marks[1], nullptr) != hipSuccess || launch_albedo_remodulate((double*)d_x, (const double*)d_albedo_sum, albedo_samples, n_doubles, nullptr) != 0 ||
-            hipEventRecord(marks[2], nullptr) != hipSuccess) rc = set_err("rt_debug_albedo_modulate_ms: a launch failed");
-    }
-    if (rc == 0 && hipEventSynchronize(marks[2]) != hipSuccess) rc = set_err("hipEventSynchronize failed");
-    for (int k = 0; k < 2 && rc == 0; k++) if (hipEventElapsedTime(&ms_out[k], marks[k], marks[k + 1]) != hipSuccess) rc = set_err("hipEventElapsedTime failed");
-    for (int k = 0; k < 3; k++) if (marks[k]) (void)hipEventDestroy(marks[k]);
-    return rc;
-}
-int rt_progressive_albedo_info(void* frame, uint32_t* albedo_samples_out, uint64_t* builds_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !albedo_samples_out || !builds_out) return set_err("null argument");
-    *albedo_samples_out = p->albedo_samples; *builds_out = p->albedo_builds;
-    return 0;
-}
-
-// ---------------------------------------------------------------- denoising a frame as it is (csrc/rt_denoise_frame.h: the specification; rt_denoise_frame.hip: the kernels)
-int rt_adaptive_variance_device(const void* d_rgb_sum, const void* d_sq_sum, const void* d_counts, const void* d_passes, uint32_t W, uint32_t H,
-                                void* d_var_out, void* hip_stream) {
-    if (!d_rgb_sum || !d_sq_sum || !d_counts || !d_passes || !d_var_out) return set_err("null argument");
-    const std::string problem = adaptive_frame_check(W, H);
-    if (!problem.empty()) return set_err(problem);
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_sq_sum | (uintptr_t)d_var_out) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_passes) & 3u) != 0u)
-        return set_err("d_rgb_sum, d_sq_sum and d_var_out must be 8-byte aligned, d_counts and d_passes 4-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    HIP_OK((hipError_t)launch_frame_variance((const double*)d_rgb_sum, (const double*)d_sq_sum, (const uint32_t*)d_counts, (const uint32_t*)d_passes, W * H,
-                                             (double*)d_var_out, hip_stream));
-    return 0;
-}
-size_t rt_denoise_frame_workspace_bytes(uint32_t W, uint32_t H) { return denoise_frame_workspace_bytes((uint64_t)W * H); }
-
-// The launches of one run on `stream`: prepare (c into d_c; Vd into d_vd when there are both a variance frame and albedo sums), the filter's
-// own launches from d_c with samples = 1 to d_out, finish on d_out in place.  d_out may be d_sum: prepare has read it by the time anything
-// is written there (stream order).
-static int denoise_frame_enqueue(const double* d_sum, const uint32_t* d_counts, uint64_t samples, const double* d_var, const double* d_albedo_sum,
-                                 uint64_t albedo_samples, const double* d_hits, uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3],
-                                 uint32_t flags, double* d_out, double* d_var_out, void* d_workspace, double* d_c, double* d_vd, hipStream_t stream) {
-    const uint32_t n_px = W * H;
-    HIP_OK((hipError_t)launch_frame_prepare(d_sum, d_counts, samples, d_var, d_albedo_sum, albedo_samples, d_c, d_vd, n_px, stream));
-    if (d_var) {
-        if (denoise_variance_enqueue(d_c, 1u, d_albedo_sum ? d_vd : d_var, d_hits, W, H, iterations, sigma, flags, d_out, d_var_out, d_workspace, stream)) return -1;
-    } else if (denoise_enqueue(d_c, 1u, d_hits, W, H, iterations, sigma, flags, d_out, d_workspace, stream)) return -1;
-    HIP_OK((hipError_t)launch_frame_finish(d_out, d_counts, samples, d_albedo_sum, albedo_samples, n_px, stream));
-    return 0;
-}
-int rt_denoise_frame_device(const void* d_rgb_sum, const void* d_counts, uint64_t samples, const void* d_var, const void* d_albedo_sum,
-                            uint64_t albedo_samples, const void* d_hits, uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3],
-                            uint32_t flags, void* d_rgb_sum_out, void* d_var_out, void* d_workspace, size_t workspace_bytes, void* hip_stream) {
-    if (!d_rgb_sum || !d_hits || !sigma || !d_rgb_sum_out || !d_workspace) return set_err("null argument");
-    const std::string problem = denoise_frame_check(d_counts != nullptr, samples, d_var != nullptr, d_albedo_sum != nullptr, albedo_samples, W, H, iterations, sigma,
-                                                    flags, d_var_out != nullptr);
-    if (!problem.empty()) return set_err(problem);
-    if (workspace_bytes < rt_denoise_frame_workspace_bytes(W, H))
-        return set_err("denoise: workspace too small: rt_denoise_frame_workspace_bytes(W, H) — the filter's 128 bytes per pixel and two frames of 24 — are needed");
-    if (query_aligned(d_hits, "d_hits") || query_aligned(d_workspace, "d_workspace")) return -1;
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_rgb_sum_out | (uintptr_t)d_var | (uintptr_t)d_var_out | (uintptr_t)d_albedo_sum) & 7u) != 0u || ((uintptr_t)d_counts & 3u) != 0u)
-        return set_err("d_rgb_sum, d_var, d_albedo_sum, d_rgb_sum_out and d_var_out must be 8-byte aligned, d_counts 4-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    const uint64_t n_px = (uint64_t)W * H;
-    unsigned char* planes = (unsigned char*)d_workspace + rt_denoise_workspace_bytes(W, H);
-    return denoise_frame_enqueue((const double*)d_rgb_sum, (const uint32_t*)d_counts, samples, (const double*)d_var, (const double*)d_albedo_sum, albedo_samples,
-                                 (const double*)d_hits, W, H, iterations, sigma, flags, (double*)d_rgb_sum_out, (double*)d_var_out, d_workspace,
-                                 (double*)planes, (double*)(planes + denoise_frame_plane_bytes(n_px)), (hipStream_t)hip_stream);
-}
-int rt_denoise_frame(const double* rgb_sum, const uint32_t* counts, uint64_t samples, const double* var, const double* albedo_sum,
-                     uint64_t albedo_samples, const double* hits, uint32_t W, uint32_t H, uint32_t iterations, const double sigma[3],
-                     uint32_t flags, double* rgb_sum_out, double* var_out) {
-    if (!rgb_sum || !hits || !sigma || !rgb_sum_out) return set_err("null argument");
-    const std::string problem = denoise_frame_check(counts != nullptr, samples, var != nullptr, albedo_sum != nullptr, albedo_samples, W, H, iterations, sigma,
-                                                    flags, var_out != nullptr);
-    if (!problem.empty()) return set_err(problem);
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), hit_bytes = n * DENOISE_HIT_DOUBLES * sizeof(double);
-    const size_t ws_bytes = rt_denoise_frame_workspace_bytes(W, H);
-    DeviceBuffer d_sum, d_cnt, d_var, d_alb, d_hits, d_ws, d_vout;
-    HIP_OK(d_sum.alloc(sum_bytes)); HIP_OK(d_hits.alloc(hit_bytes)); HIP_OK(d_ws.alloc(ws_bytes));
-    if (counts) { HIP_OK(d_cnt.alloc(n * sizeof(uint32_t))); HIP_OK(hipMemcpy(d_cnt.get(), counts, n * sizeof(uint32_t), hipMemcpyHostToDevice)); }
-    if (var) { HIP_OK(d_var.alloc(sum_bytes)); HIP_OK(hipMemcpy(d_var.get(), var, sum_bytes, hipMemcpyHostToDevice)); }
-    if (albedo_sum) { HIP_OK(d_alb.alloc(sum_bytes)); HIP_OK(hipMemcpy(d_alb.get(), albedo_sum, sum_bytes, hipMemcpyHostToDevice)); }
-    if (var_out) HIP_OK(d_vout.alloc(n * sizeof(double)));
-    HIP_OK(hipMemcpy(d_sum.get(), rgb_sum, sum_bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_hits.get(), hits, hit_bytes, hipMemcpyHostToDevice));
-    if (rt_denoise_frame_device(d_sum.get(), counts ? d_cnt.get() : nullptr, samples, var ? d_var.get() : nullptr, albedo_sum ? d_alb.get() : nullptr, albedo_samples,
-                                d_hits.get(), W, H, iterations, sigma, flags, d_sum.get(), var_out ? d_vout.get() : nullptr, d_ws.get(), ws_bytes, nullptr)) return -1;
-    HIP_OK(hipMemcpy(rgb_sum_out, d_sum.get(), sum_bytes, hipMemcpyDeviceToHost));       // (waits for the kernels: the null stream)
-    if (var_out) HIP_OK(hipMemcpy(var_out, d_vout.get(), n * sizeof(double), hipMemcpyDeviceToHost));
-    return 0;
-}
-// what the variance of a frame with counts needs: moments that describe the sums (two passes are every pixel's own matter, (E))
-static int frame_variance_ready(Progressive* p) {
-    if (!p->adaptive) return moments_error_ready(p);
-    if (!p->moments_valid) return set_err("the moments of this frame are invalid: rt_progressive_load_sum loaded sums whose second moments are unknown (rt_progressive_reset or rt_progressive_load_moments)");
-    return 0;
-}
-// (E) on an adaptive frame, (4) on any other: into the frame's own variance frame, on `stream`
-static int frame_variance_enqueue(Progressive* p, hipStream_t stream) {
-    if (!p->adaptive) return progressive_variance_enqueue(p, stream);
-    if (!p->d_var) HIP_OK(hipMalloc(&p->d_var, p->n_px() * 3 * sizeof(double)));
-    HIP_OK((hipError_t)launch_frame_variance((const double*)p->d_sum, (const double*)p->d_sq, (const uint32_t*)p->d_cnt, (const uint32_t*)p->d_pas, (uint32_t)p->n_px(),
-                                             (double*)p->d_var, stream));
-    return 0;
-}
-int rt_progressive_variance_counts(void* frame, double* var_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!var_out) return set_err("null argument");
-    if (moments_frame(p) || frame_variance_ready(p)) return -1;
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the estimate
-    if (frame_variance_enqueue(p, nullptr)) return -1;
-    HIP_OK(hipMemcpy(var_out, p->d_var, p->n_px() * 3 * sizeof(double), hipMemcpyDeviceToHost));      // (waits for the kernel: the null stream)
-    return 0;
-}
-// The frame as it is — its counts when it has them, its variance under the variance stop, its albedo sums when asked for — filtered and
-// resolved; everything the other resolves own stays as it is.
-int rt_progressive_resolve_denoised_frame_rgb8(void* frame, uint32_t stop, uint32_t albedo_samples, uint32_t iterations, const double sigma[3],
-                                               uint32_t flags, uint8_t* rgb8_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !sigma || !rgb8_out) return set_err("null argument");
-    if (stop > (uint32_t)RT_DENOISE_STOP_VARIANCE) return set_err("denoise: stop must be RT_DENOISE_STOP_COLOUR = 0 or RT_DENOISE_STOP_VARIANCE = 1");
-    const bool variance = stop == (uint32_t)RT_DENOISE_STOP_VARIANCE;
-    if (variance) {
-        if (moments_frame(p) || frame_variance_ready(p)) return -1;
-        const std::string problem = denoise_variance_check(p->done ? p->done : 1u, p->W, p->H, iterations, sigma, flags);
-        if (!problem.empty()) return set_err(problem);
-    }
-    DeviceGuard guard(p->device);
-    if (progressive_denoise_prepare(p, iterations, sigma, flags)) return -1;
-    const size_t n = p->n_px(), sum_bytes = n * 3 * sizeof(double);
-    if (albedo_samples) {                                       // the albedo sums rt_progressive_resolve_denoised_albedo_rgb8 keeps, built as it builds them
-        if (p->albedo_samples != albedo_samples) {
-            if (!p->sc) return set_err("the scene of this progressive frame has been destroyed and the frame holds no albedo sums for this albedo_samples: they are built from the scene (rt_query_camera_albedo_device)");
-            if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
-        }
-        if (!p->d_alb_sum) HIP_OK(hipMalloc(&p->d_alb_sum, sum_bytes));
-        if (p->albedo_samples != albedo_samples) {
-            p->albedo_samples = 0;
-            if (rt_query_camera_albedo_device(p->sc, &p->cam, p->W, p->H, 0u, albedo_samples, p->seed, 0u, p->d_alb_sum, sum_bytes, nullptr)) return -1;
-            p->albedo_samples = albedo_samples; p->albedo_builds++;
-        }
-    }
-    const size_t plane = denoise_frame_plane_bytes(n);
-    if (!p->d_fr_planes) HIP_OK(hipMalloc(&p->d_fr_planes, 2u * plane));
-    if (variance && frame_variance_enqueue(p, nullptr)) return -1;
-    if (denoise_frame_enqueue((const double*)p->d_sum, p->adaptive ? (const uint32_t*)p->d_cnt : nullptr, p->done, variance ? (const double*)p->d_var : nullptr,
-                              albedo_samples ? (const double*)p->d_alb_sum : nullptr, albedo_samples, nullptr, p->W, p->H, iterations, sigma, flags,
-                              (double*)p->d_dn_sum, nullptr, p->d_dn_ws, (double*)p->d_fr_planes, (double*)((unsigned char*)p->d_fr_planes + plane), nullptr)) return -1;
-    if (!p->adaptive) return progressive_denoise_finish(p, rgb8_out);
-    HIP_OK(hipMemsetAsync(p->d_dn_changed, 0, sizeof(unsigned long long), nullptr));
-    HIP_OK((hipError_t)launch_adaptive_resolve((const double*)p->d_dn_sum, (const uint32_t*)p->d_cnt, nullptr, (uint8_t*)p->d_dn_rgb8, (unsigned long long*)p->d_dn_changed,
-                                               (uint32_t)n, nullptr));
-    HIP_OK(hipMemcpy(rgb8_out, p->d_dn_rgb8, n * 3, hipMemcpyDeviceToHost));             // (waits for the kernels: the null stream)
-    return 0;
-}
-
-// ---------------------------------------------------------------- temporal accumulation (csrc/rt_reproject.h: the specification; rt_reproject.hip: the kernels)
-int rt_reproject_device(const void* d_prev_sum, const void* d_prev_counts, uint64_t prev_samples, const void* d_prev_hits, const rt_camera* prev_cam,
-                        const void* d_cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2], uint32_t flags,
-                        void* d_hist_sum_out, void* d_hist_counts_out, void* hip_stream) {
-    if (!d_prev_sum || !d_prev_hits || !prev_cam || !d_cur_hits || !sigma || !d_hist_sum_out || !d_hist_counts_out) return set_err("null argument");
-    const std::string problem = reproject_check(d_prev_counts != nullptr, prev_samples, W, H, max_history, sigma, flags);
-    if (!problem.empty()) return set_err(problem);
-    if (query_aligned(d_prev_hits, "d_prev_hits") || query_aligned(d_cur_hits, "d_cur_hits")) return -1;
-    if ((((uintptr_t)d_prev_sum | (uintptr_t)d_hist_sum_out) & 7u) != 0u || (((uintptr_t)d_prev_counts | (uintptr_t)d_hist_counts_out) & 3u) != 0u)
-        return set_err("d_prev_sum and d_hist_sum_out must be 8-byte aligned, d_prev_counts and d_hist_counts_out 4-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    double fields[21];
-    rt_camera_fields(prev_cam, fields);
-    HIP_OK((hipError_t)launch_reproject(reproject_consts(fields, prev_samples, W, H, max_history, sigma), (const double*)d_prev_sum, (const uint32_t*)d_prev_counts,
-                                        (const double*)d_prev_hits, (const double*)d_cur_hits, (double*)d_hist_sum_out, (uint32_t*)d_hist_counts_out, hip_stream));
-    return 0;
-}
-int rt_reproject(const double* prev_sum, const uint32_t* prev_counts, uint64_t prev_samples, const double* prev_hits, const rt_camera* prev_cam,
-                 const double* cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2], uint32_t flags,
-                 double* hist_sum_out, uint32_t* hist_counts_out) {
-    if (!prev_sum || !prev_hits || !prev_cam || !cur_hits || !sigma || !hist_sum_out || !hist_counts_out) return set_err("null argument");
-    const std::string problem = reproject_check(prev_counts != nullptr, prev_samples, W, H, max_history, sigma, flags);
-    if (!problem.empty()) return set_err(problem);
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), cnt_bytes = n * sizeof(uint32_t), hit_bytes = n * REPROJECT_HIT_DOUBLES * sizeof(double);
-    DeviceBuffer d_sum, d_cnt, d_prev, d_cur, d_hsum, d_hcnt;
-    HIP_OK(d_sum.alloc(sum_bytes)); HIP_OK(d_prev.alloc(hit_bytes)); HIP_OK(d_cur.alloc(hit_bytes)); HIP_OK(d_hsum.alloc(sum_bytes)); HIP_OK(d_hcnt.alloc(cnt_bytes));
-    if (prev_counts) { HIP_OK(d_cnt.alloc(cnt_bytes)); HIP_OK(hipMemcpy(d_cnt.get(), prev_counts, cnt_bytes, hipMemcpyHostToDevice)); }
-    HIP_OK(hipMemcpy(d_sum.get(), prev_sum, sum_bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_prev.get(), prev_hits, hit_bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_cur.get(), cur_hits, hit_bytes, hipMemcpyHostToDevice));
-    if (rt_reproject_device(d_sum.get(), prev_counts ? d_cnt.get() : nullptr, prev_samples, d_prev.get(), prev_cam, d_cur.get(), W, H, max_history, sigma, flags,
-                            d_hsum.get(), d_hcnt.get(), nullptr)) return -1;
-    HIP_OK(hipMemcpy(hist_sum_out, d_hsum.get(), sum_bytes, hipMemcpyDeviceToHost));     // (waits for the kernel: the null stream)
-    HIP_OK(hipMemcpy(hist_counts_out, d_hcnt.get(), cnt_bytes, hipMemcpyDeviceToHost));
-    return 0;
-}
-int rt_temporal_blend_device(const void* d_rgb_sum, const void* d_counts, uint64_t samples, const void* d_hist_sum, const void* d_hist_counts,
-                             uint32_t W, uint32_t H, void* d_sum_out, void* d_counts_out, void* hip_stream) {
-    if (!d_rgb_sum || !d_hist_sum || !d_hist_counts || !d_sum_out || !d_counts_out) return set_err("null argument");
-    const std::string problem = reproject_frame_check(W, H);
-    if (!problem.empty()) return set_err(problem);
-    if ((((uintptr_t)d_rgb_sum | (uintptr_t)d_hist_sum | (uintptr_t)d_sum_out) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_hist_counts | (uintptr_t)d_counts_out) & 3u) != 0u)
-        return set_err("d_rgb_sum, d_hist_sum and d_sum_out must be 8-byte aligned, d_counts, d_hist_counts and d_counts_out 4-byte aligned");
-    if (rt_device_count() <= 0) return set_err("no HIP device: librt_amd has no CPU rendering path");
-    HIP_OK((hipError_t)launch_temporal_blend((const double*)d_rgb_sum, (const uint32_t*)d_counts, samples, (const double*)d_hist_sum, (const uint32_t*)d_hist_counts,
-                                             W * H, (double*)d_sum_out, (uint32_t*)d_counts_out, hip_stream));
-    return 0;
-}
-// The history's buffers, allocated at first use; without a history they are made the empty one (all +0.0 and 0), so that every caller blends
-// with something.  On the null stream; nothing waits.
-static int progressive_history_ready(Progressive* p) {
-    const size_t n = p->n_px();
-    if (!p->d_hist_sum) HIP_OK(hipMalloc(&p->d_hist_sum, n * 3 * sizeof(double)));
-    if (!p->d_hist_cnt) HIP_OK(hipMalloc(&p->d_hist_cnt, n * sizeof(uint32_t)));
-    if (!p->hist_valid) {
-        HIP_OK(hipMemsetAsync(p->d_hist_sum, 0, n * 3 * sizeof(double), nullptr));
-        HIP_OK(hipMemsetAsync(p->d_hist_cnt, 0, n * sizeof(uint32_t), nullptr));
-        p->hist_valid = true; p->hist_px = 0;
-    }
-    return 0;
-}
-// the guide records of a view of the frame's scene, as progressive_denoise_prepare builds them: sample 0's, or the averaged record
-static int progressive_view_records(Progressive* p, const rt_camera* cam, uint64_t seed, void* d_hits, size_t hit_bytes) {
-    if (p->guide_samples == 1u) return rt_query_camera_device(p->sc, cam, p->W, p->H, 0u, seed, 0u, nullptr, d_hits, hit_bytes, nullptr);
-    return rt_query_camera_guide_device(p->sc, cam, p->W, p->H, 0u, p->guide_samples, seed, 0u, d_hits, hit_bytes, nullptr, 0u, nullptr);
-}
-int rt_progressive_set_view(void* frame, const rt_camera* cam, uint64_t seed, uint32_t max_history, const double sigma[2]) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !cam || !sigma) return set_err("null argument");
-    if (p->adaptive) return set_err("rt_progressive_set_view: not available on an adaptive frame (rt_reproject_device and rt_temporal_blend_device take per-pixel counts: a caller can compose them)");
-    if (!p->sc) return set_err("the scene of this progressive frame has been destroyed");
-    if (p->scene_version != p->sc->s.version) return set_err("the scene changed after this progressive frame was created: the frame is forgotten (rt_progressive_reset starts a new one)");
-    const std::string problem = reproject_check(true, 0u, p->W, p->H, max_history, sigma, 0u);
-    if (!problem.empty()) return set_err(problem);
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the previous frame
-    if (progressive_history_ready(p)) return -1;
-    const size_t n = p->n_px(), sum_bytes = n * 3 * sizeof(double), cnt_bytes = n * sizeof(uint32_t), hit_bytes = n * REPROJECT_HIT_DOUBLES * sizeof(double);
-    if (max_history == 0u || (p->done == 0 && p->hist_px == 0)) {     // nothing is carried over: the empty history, as (R5) gives it
-        HIP_OK(hipMemsetAsync(p->d_hist_sum, 0, sum_bytes, nullptr));
-        HIP_OK(hipMemsetAsync(p->d_hist_cnt, 0, cnt_bytes, nullptr));
-        p->hist_px = 0;
-    } else {
-        DeviceBuffer d_bsum, d_bcnt, d_prev, d_cur;
-        HIP_OK(d_bsum.alloc(sum_bytes)); HIP_OK(d_bcnt.alloc(cnt_bytes)); HIP_OK(d_prev.alloc(hit_bytes)); HIP_OK(d_cur.alloc(hit_bytes));
-        HIP_OK((hipError_t)launch_temporal_blend((const double*)p->d_sum, nullptr, p->done, (const double*)p->d_hist_sum, (const uint32_t*)p->d_hist_cnt, (uint32_t)n,
-                                                 (double*)d_bsum.get(), (uint32_t*)d_bcnt.get(), nullptr));
-        if (progressive_view_records(p, &p->cam, p->seed, d_prev.get(), hit_bytes)) return -1;
-        if (progressive_view_records(p, cam, seed, d_cur.get(), hit_bytes)) return -1;
-        if (rt_reproject_device(d_bsum.get(), d_bcnt.get(), 0u, d_prev.get(), &p->cam, d_cur.get(), p->W, p->H, max_history, sigma, 0u, p->d_hist_sum, p->d_hist_cnt, nullptr)) return -1;
-        std::vector<uint32_t> cnt(n);
-        HIP_OK(hipMemcpy(cnt.data(), p->d_hist_cnt, cnt_bytes, hipMemcpyDeviceToHost));      // (waits for the kernels: the null stream)
-        uint64_t px = 0;
-        for (size_t k = 0; k < n; k++) px += cnt[k] != 0u;
-        p->hist_px = px;
-    }
-    std::memcpy(&p->cam, cam, sizeof(rt_camera)); p->seed = seed;
-    p->guide_valid = false; p->albedo_samples = 0;      // as rt_progressive_reset: a new frame of the new view ...
-    p->views++;
-    return progressive_restart(p, nullptr, 0);          // ... that keeps its history
-}
-int rt_progressive_read_history(void* frame, double* hist_sum_out, uint32_t* hist_counts_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !hist_sum_out || !hist_counts_out) return set_err("null argument");
-    const size_t n = p->n_px();
-    if (!p->hist_valid) {
-        std::memset(hist_sum_out, 0, n * 3 * sizeof(double)); std::memset(hist_counts_out, 0, n * sizeof(uint32_t));
-        return 0;
-    }
-    DeviceGuard guard(p->device);
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(hist_sum_out, p->d_hist_sum, n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(hist_counts_out, p->d_hist_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return 0;
-}
-int rt_progressive_history_info(void* frame, uint64_t out[2]) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !out) return set_err("null argument");
-    out[0] = p->views; out[1] = p->hist_valid ? p->hist_px : 0u;
-    return 0;
-}
-// The blend of the frame with its history resolved with the blend's counts, with the frame filter in between when iterations >= 1; into
-// the denoised resolves' buffers: d_sum, the history, the plain resolve's two images and its count stay as they are.
-int rt_progressive_resolve_temporal_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out) {
-    Progressive* p = (Progressive*)frame;
-    if (!p || !rgb8_out || (iterations && !sigma)) return set_err("null argument");
-    if (p->adaptive) return set_err("rt_progressive_resolve_temporal_rgb8: not available on an adaptive frame (it has no history: rt_progressive_set_view refuses it)");
-    if (iterations > DENOISE_MAX_ITERATIONS) return set_err("denoise: iterations must be 0 .. 8 (0: the resolve of the blend without a filter)");
-    const bool history = p->hist_valid && p->hist_px > 0;
-    if (p->done == 0 && !history) return set_err("nothing to resolve: the frame holds 0 samples and no history (rt_progressive_add, rt_progressive_set_view)");
-    DeviceGuard guard(p->device);
-    const size_t n = p->n_px(), sum_bytes = n * 3 * sizeof(double);
-    if (iterations) { if (progressive_denoise_prepare(p, iterations, sigma, flags, true)) return -1; }
-    else {
-        HIP_OK(hipDeviceSynchronize());             // passes enqueued on the caller's streams belong to the image
-        if (!p->d_dn_rgb8) HIP_OK(hipMalloc(&p->d_dn_rgb8, n * 3));
-        if (!p->d_dn_changed) HIP_OK(hipMalloc(&p->d_dn_changed, sizeof(unsigned long long)));
-    }
-    if (progressive_history_ready(p)) return -1;
-    DeviceBuffer d_bsum, d_bcnt;
-    HIP_OK(d_bsum.alloc(sum_bytes)); HIP_OK(d_bcnt.alloc(n * sizeof(uint32_t)));
-    HIP_OK((hipError_t)launch_temporal_blend((const double*)p->d_sum, nullptr, p->done, (const double*)p->d_hist_sum, (const uint32_t*)p->d_hist_cnt, (uint32_t)n,
-                                             (double*)d_bsum.get(), (uint32_t*)d_bcnt.get(), nullptr));
-    const double* d_resolved = (const double*)d_bsum.get();
-    if (iterations) {
-        const size_t plane = denoise_frame_plane_bytes(n);
-        if (!p->d_fr_planes) HIP_OK(hipMalloc(&p->d_fr_planes, 2u * plane));
-        if (denoise_frame_enqueue((const double*)d_bsum.get(), (const uint32_t*)d_bcnt.get(), 0u, nullptr, nullptr, 0u, nullptr, p->W, p->H, iterations, sigma, flags,
-                                  (double*)p->d_dn_sum, nullptr, p->d_dn_ws, (double*)p->d_fr_planes, (double*)((unsigned char*)p->d_fr_planes + plane), nullptr)) return -1;
-        d_resolved = (const double*)p->d_dn_sum;
-    }
-    HIP_OK(hipMemsetAsync(p->d_dn_changed, 0, sizeof(unsigned long long), nullptr));
-    HIP_OK((hipError_t)launch_adaptive_resolve(d_resolved, (const uint32_t*)d_bcnt.get(), nullptr, (uint8_t*)p->d_dn_rgb8, (unsigned long long*)p->d_dn_changed, (uint32_t)n, nullptr));
-    HIP_OK(hipMemcpy(rgb8_out, p->d_dn_rgb8, n * 3, hipMemcpyDeviceToHost));             // (waits for the kernels, before the blend's buffers go: the null stream)
-    return 0;
-}
-
-int rt_render_samples(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
-                      uint64_t seed, uint32_t flags, double* rgb_sum_out, double* samples_out) {
-    if (!rgb_sum_out) return set_err("null output");
-    if (frame_prologue(sc, cam, bg, W, H, spp)) return -1;
-    const size_t n_px = (size_t)W * H, sum_bytes = n_px * 3 * sizeof(double), sample_bytes = sum_bytes * spp;
-    DeviceBuffer d_out, d_samples;
-    HIP_OK(d_out.alloc(sum_bytes));
-    if (samples_out) { const hipError_t e = d_samples.alloc(sample_bytes); if (e != hipSuccess) return set_err(std::string("hipMalloc(samples): ") + hipGetErrorString(e)); }
-    if (render_any(sc, cam, bg, W, H, spp, max_depth, seed, flags, (uint32_t)n_px, 0, 1, d_out.get(), sum_bytes, d_samples.get(), nullptr, true)) return -1;
-    hipError_t e = hipStreamSynchronize(nullptr);
-    if (e == hipSuccess) e = hipMemcpy(rgb_sum_out, d_out.get(), sum_bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && samples_out) e = hipMemcpy(samples_out, d_samples.get(), sample_bytes, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? 0 : set_err(std::string("copy back: ") + hipGetErrorString(e));
-}
-
-int rt_render(rt_scene* sc, const rt_camera* cam, const double bg[3], uint32_t W, uint32_t H, uint32_t spp, uint32_t max_depth,
-              uint64_t seed, uint32_t flags, double* rgb_sum_out) {
-    return rt_render_samples(sc, cam, bg, W, H, spp, max_depth, seed, flags, rgb_sum_out, nullptr);
-}
-
-} // extern "C"

@@ -1,5 +1,5 @@
 // csrc/rt_moments.h — the second moment of a progressive frame and its per-pixel error estimate: the specification, the host twin's
-// seams (rt_moments_cpu.cpp, plain C++) and the launches of the HIP kernels (rt_moments.hip) as the host library (rt_host.cpp) sees them.
+// seams (rt_moments_cpu.cpp, plain C++) and the launches of the HIP kernels (rt_moments.hip) as the host library (rt_frames.cpp) sees them.
 // No HIP include: a stream travels as a void* and a HIP status as an int (0 = hipSuccess), as in rt_denoise.h, so that the host twin and its
 // stand-alone sanitizer program compile with any C++ compiler.
 //

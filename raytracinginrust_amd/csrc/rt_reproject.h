@@ -1,6 +1,6 @@
 // csrc/rt_reproject.h — temporal accumulation: the history of a frame reprojected into a new view of the same scene, and the blend of a
 // frame with such a history.  The specification, the host twin's seams (rt_reproject_cpu.cpp, plain C++) and the launches of the HIP kernels
-// (rt_reproject.hip) as the host library (rt_host.cpp) sees them.  No HIP include: a stream travels as a void* and a HIP status as an int
+// (rt_reproject.hip) as the host library (rt_frames.cpp) sees them.  No HIP include: a stream travels as a void* and a HIP status as an int
 // (0 = hipSuccess), as in rt_denoise_frame.h.
 //
 // Only + - * /, floor, comparisons and integer conversion, every operation rounded once (-ffp-contract=off), in the order written.

@@ -1,4 +1,4 @@
-// csrc/rt_resolve.h — interface between the host library (rt_host.cpp) and the resolve kernel (rt_resolve.hip), the same kind of seam
+// csrc/rt_resolve.h — interface between the host library (rt_host.cpp, rt_frames.cpp) and the resolve kernel (rt_resolve.hip), the same kind of seam
 // rt_launch.h is for the path-tracing kernels: plain C++ against the HIP headers, so that the sanitizer build compiles the host side.
 #pragma once
 #include <hip/hip_runtime.h>

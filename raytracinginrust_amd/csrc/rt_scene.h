@@ -146,7 +146,7 @@ struct Scene {
     void* q_ev[2] = {nullptr, nullptr}; int q_device = -1; bool q_recorded = false;
     uint32_t q_launch[4] = {0, 0, 0, 0};               // rt_last_query_launch: workgroups, threads per workgroup, chunk, chunks of that kernel
 
-    // Progressive frames (rt_progressive_*, rt_host.cpp) of this scene: a frame holds the `version` it was created at — every change to the
+    // Progressive frames (rt_progressive_*, rt_frames.cpp) of this scene: a frame holds the `version` it was created at — every change to the
     // scene moves it on, and the frame's next pass is refused — and is told when the scene is destroyed before it.
     unsigned long long version = 0; std::vector<void*> frames;
 

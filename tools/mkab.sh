@@ -9,6 +9,6 @@ BASE="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-fu
 /opt/rocm/bin/hipcc $BASE -mllvm -enable-misched=0 $f1 -DRT_TU=1 -c $src -o abx/${name}_lean.o &
 /opt/rocm/bin/hipcc $BASE $f2 -DRT_TU=2 -c $src -o abx/${name}_rest.o &
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abx/$name.so abx/${name}_lean.o abx/${name}_rest.o rt_denoise.o rt_denoise_cpu.o rt_host.o rt_multi.o rt_flatten.o rt_jpeg.o rt_obj.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o abx/$name.so abx/${name}_lean.o abx/${name}_rest.o rt_denoise.o rt_denoise_cpu.o rt_host.o rt_frames.o rt_multi.o rt_flatten.o rt_jpeg.o rt_obj.o
 rm -f abx/${name}_lean.o abx/${name}_rest.o
 echo built abx/$name.so

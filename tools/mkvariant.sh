@@ -18,5 +18,5 @@ for i in range(2, len(sys.argv), 2):
 open(dst, 'w').write(s)
 PY
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 -I. -I../../include "${defs[@]}" -c variants/src/$name.hip -o variants/src/$name.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/$name.so variants/src/$name.o rt_denoise.o rt_denoise_cpu.o rt_host.o rt_flatten.o rt_jpeg.o
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o variants/$name.so variants/src/$name.o rt_denoise.o rt_denoise_cpu.o rt_host.o rt_frames.o rt_flatten.o rt_jpeg.o
 echo built variants/$name.so
