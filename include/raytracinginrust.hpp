@@ -282,6 +282,33 @@ inline std::vector<double> query_camera_guide(Scene& s, const Camera& cam, uint3
     if (rt_query_camera_guide(s.raw(), &cam.c, W, H, first_sample, n_samples, seed, 0, out.data(), albedo_sum_out ? albedo_sum_out->data() : nullptr) != 0) throw Error(rt_last_error());
     return out;
 }
+// Specular-chain guides (rt_query_chain, rt_query_camera_chain_guide, csrc/rt_chain.h): rays followed through mirrors (fuzz <= max_fuzz) and glass
+// to the first non-specular surface, up to max_links (0 .. 64) links.  The records are in query_camera_records' layout with word [1] the path
+// length in units of the first ray's parameter and word [15] the links followed; the albedo is that surface's times the mirrors' tints.
+// max_links = 0 gives the first-hit queries' words.  The default max_fuzz follows perfect mirrors only: an untuned starting value.
+struct ChainSettings { uint32_t max_links = 4; double max_fuzz = 0.0; };
+// rays: n x 7 doubles (origin, direction, time) -> n x 16; albedo_out (optional): n x 3
+inline std::vector<double> query_chain(Scene& s, const std::vector<double>& rays, const ChainSettings& c = ChainSettings(), double t_min = 1e-5, uint64_t seed = 0,
+                                       std::vector<double>* albedo_out = nullptr) {
+    if (rays.size() % 7u != 0u) throw Error("query_chain: rays are 7 doubles each");
+    const uint32_t n = (uint32_t)(rays.size() / 7u);
+    std::vector<double> out((size_t)n * 16);
+    if (albedo_out) albedo_out->assign((size_t)n * 3, 0.0);
+    if (rt_query_chain(s.raw(), n, rays.data(), t_min, seed, c.max_links, c.max_fuzz, 0, out.data(), albedo_out ? albedo_out->data() : nullptr) != 0) throw Error(rt_last_error());
+    return out;
+}
+// query_camera_guide over chain records: what every `hit_records` parameter of the denoise family takes; albedo_sum_out (optional) W*H*3 sums of
+// the chain albedos, links_out (optional) W*H counts of the links followed over all samples
+inline std::vector<double> query_camera_chain_guide(Scene& s, const Camera& cam, uint32_t W, uint32_t H, const ChainSettings& c = ChainSettings(), uint32_t first_sample = 0,
+                                                    uint32_t n_samples = 16, uint64_t seed = 0x5EED, std::vector<double>* albedo_sum_out = nullptr,
+                                                    std::vector<uint32_t>* links_out = nullptr) {
+    std::vector<double> out((size_t)W * H * 16);
+    if (albedo_sum_out) albedo_sum_out->assign((size_t)W * H * 3, 0.0);
+    if (links_out) links_out->assign((size_t)W * H, 0u);
+    if (rt_query_camera_chain_guide(s.raw(), &cam.c, W, H, first_sample, n_samples, seed, c.max_links, c.max_fuzz, 0, out.data(),
+                                    albedo_sum_out ? albedo_sum_out->data() : nullptr, links_out ? links_out->data() : nullptr) != 0) throw Error(rt_last_error());
+    return out;
+}
 // the specification on the host (no device): hit_records = n_samples x n_px x 16 doubles, sample-major -> n_px x 16
 inline std::vector<double> guide_from_hits(const std::vector<double>& hit_records, uint32_t n_samples, uint64_t n_px) {
     if (n_samples == 0 || hit_records.size() != (size_t)n_samples * n_px * 16) throw Error("guide_from_hits: records of another size");
@@ -440,6 +467,10 @@ public:
     // the guide of every denoised resolve: 1 (the default) the camera hits of sample 0, n > 1 `query_camera_guide` over samples [0, n); another
     // value drops the packed guide and the next denoised resolve builds it.  guide_info: the value in force and the guides built so far
     void set_guide_samples(uint32_t n_samples) { chk(rt_progressive_set_guide_samples(p_, n_samples)); }
+    // max_links > 0: the guide AND the albedo sums of every denoised resolve come from `query_camera_chain_guide` over samples [0, guide_samples)
+    // (the albedo resolves then divide by those sums over guide_samples); 0 (the default): first hits.  set_view reprojects with first hits always.
+    void set_guide_chain(uint32_t max_links, double max_fuzz = 0.0) { chk(rt_progressive_set_guide_chain(p_, max_links, max_fuzz)); }
+    ChainSettings guide_chain() const { ChainSettings c; chk(rt_progressive_guide_chain_info(p_, &c.max_links, &c.max_fuzz)); return c; }
     struct GuideInfo { uint32_t guide_samples; uint64_t builds; };
     GuideInfo guide_info() const { GuideInfo g{0u, 0u}; chk(rt_progressive_guide_info(p_, &g.guide_samples, &g.builds)); return g; }
     std::vector<double> sum() const { std::vector<double> out(n_px_ * 3); chk(rt_progressive_read_sum(p_, out.data())); return out; }

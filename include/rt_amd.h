@@ -420,7 +420,7 @@ int rt_last_query_launch(rt_scene*, uint32_t out4[4]);
  *        Lambertian: Texture::mapping(u, v, p) of its texture, the frames' own texture walk on the record (constant, checker, Perlin noise,
  *        image); PBR: the same of its base-colour texture; a ConstantMedium hit (handle -1): the same of the medium's texture; Metal: its
  *        albedo; Dielectric, DiffuseLight and a miss: (1, 1, 1) — radiance of emitters and of the background is not reflectance and stays
- *        un-demodulated.  Specular chains are NOT followed to the first diffuse surface: the albedo is the first hit's.
+ *        un-demodulated.  The albedo is the FIRST hit's; rt_query_chain* below follow specular chains to the first rough surface.
  * rt_query_albedo: albedo_out = n x 3 doubles; hits_out: NULL, or n x 16 — the very words rt_query_hits writes for these rays and this seed.
  * rt_query_camera_albedo: albedo_sum_out = W*H*3 doubles in output order, per pixel the SUM over samples first_sample .. first_sample +
  * n_samples - 1 of the albedo under that sample's camera ray (the ray of rt_query_camera(sample)), added in ascending order into
@@ -458,8 +458,8 @@ int rt_query_camera_albedo_device(rt_scene*, const rt_camera*, uint32_t W, uint3
  * buffer that is too small is an error and nothing is launched), rt_last_query_ms, rt_last_query_launch — is as for rt_query_camera_albedo*.
  * rt_guide_from_hits_host: the specification on the host, no GPU: hits = n_samples x n_px x 16 doubles (sample-major: the stacked outputs
  * of rt_query_camera), guide_out = n_px x 16.  Errors: null arguments, n_samples = 0.
- * Not done: a coverage or depth-spread stop inside the filters (they read words [0]-[7] and [11] only), following specular chains, f32,
- * rt_render_multi. */
+ * Not done: a coverage or depth-spread stop inside the filters (they read words [0]-[7] and [11] only), f32, rt_render_multi.  Following
+ * specular chains: rt_query_camera_chain_guide* below. */
 int rt_query_camera_guide(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
                           uint64_t seed, uint32_t flags, double* guide_out, double* albedo_sum_out);
 int rt_query_camera_guide_device(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
@@ -473,6 +473,55 @@ int rt_guide_from_hits_host(const double* hits, uint32_t n_samples, uint64_t n_p
  * has built so far.  The frame's albedo sums are built as before, by their own launch. */
 int rt_progressive_set_guide_samples(void* frame, uint32_t n_samples);
 int rt_progressive_guide_info(void* frame, uint32_t* guide_samples_out, uint64_t* builds_out);
+
+/* ---- specular-chain guides: the record and the albedo at the first NON-specular surface along the deterministic specular path of a ray,
+ * for denoising guides and albedo frames in which a mirror or a glass ball shows what is seen in it, not its own smooth surface
+ * (csrc/rt_chain.h: the exact f64 definition (C1)-(C8) and the link step; csrc/rt_chain.hip: the kernel).  Briefly:
+ *   (C1) link l searches world.hit(r_l, t_min, +inf) as rt_query_hits does; link 0 draws from rt_query_hits' / rt_query_camera's stream, link
+ *        l >= 1 of item k from rng_for_stream(seed + ((sample_index << 8) | l) * 0x9E3779B97F4A7C15, k) (sample_index 0 for caller rays):
+ *        link l of all items is one rt_query_hits call.  The step draws nothing.
+ *   (C2) the chain ends at a miss, at l = max_links (0 .. 64), at a medium hit, at a material that is neither Metal nor Dielectric, at a Metal
+ *        with !(fuzz <= max_fuzz) (max_fuzz >= 0 or +inf), at a new direction that is not finite, and at a Metal whose reflected direction
+ *        has !(dot(new_d, n) > 0) (the frames absorb that path, main.rs:108-110).
+ *   (C3) Metal: the centre of the lobe, reflect(d, n) normalised (mat.rs:280-293 without the fuzz term); the weight is multiplied by its albedo.
+ *   (C4) Dielectric: mat.rs:343-374 expression for expression with `refl > 0.5` in the place of the random draw; weight unchanged.
+ *   (C5) the new ray starts at the record's position, time unchanged.
+ *   (C6) the record is the LAST link's, in rt_query_hits' layout, but word [1] = the path length in units of the first ray's parameter
+ *        ((t_0 L_0 + t_1 L_1 + ...) / L_0, L_l the length of link l's direction; with 0 links the record's own t, bit for bit) and word [15] =
+ *        the number of links followed.  A chain that ends in a miss has hit = 0.
+ *   (C7) the chain albedo is the weight times rt_query_albedo's table on the last record ((1, 1, 1) for a miss).
+ *   (C8) camera form: the chain records of samples first_sample .. first_sample + n_samples - 1 reduced by rt_query_camera_guide's rule
+ *        (word [15] = the hit count), the chain albedos summed in ascending order, links_out (may be NULL) = per pixel the links followed
+ *        over all samples.
+ * With max_links = 0 the words are those of rt_query_hits, rt_query_albedo and rt_query_camera_guide.  albedo outputs may be NULL.
+ * Errors: max_links > 64, a negative or NaN max_fuzz, flags != 0, and rt_query_albedo* / rt_query_camera_guide*'s own (null arguments, sizes,
+ * alignment, ranges).  The _device forms take DEVICE pointers (rays, hits, guide 16-byte aligned, albedo 8-byte, links 4-byte), check the sizes,
+ * only enqueue on hip_stream and never wait or allocate; a buffer that is too small is an error and nothing is launched.  rt_last_query_ms and
+ * rt_last_query_launch report these launches (threads per workgroup: rt_debug_loop_limits word [12]).
+ * rt_chain_step_host: the link step (C2)-(C5) on the host, no GPU, on n (ray, record) pairs; the material comes from the scene's host-side table
+ * by the record's word [11].  next_rays_out n x 7: the new ray where status is 0, else the input ray; weight_out n x 3: the factor of this
+ * link (a followed Metal's albedo, else (1, 1, 1)); status_out: 0 continue, 1 ended at a non-specular surface, 2 miss, 3 absorbed, 4 not
+ * finite, 5 fuzz above the limit.  max_links is the caller's loop.  A word [11] that names no material is an error and nothing is written.
+ * Not done: chain records in reprojection, the Fresnel split as two weighted branches, refilling ended lanes, f32, rt_render_multi. */
+int rt_query_chain(rt_scene*, uint32_t n, const double* rays, double t_min, uint64_t seed, uint32_t max_links, double max_fuzz, uint32_t flags,
+                   double* hits_out, double* albedo_out);
+int rt_query_chain_device(rt_scene*, uint32_t n, const void* d_rays, double t_min, uint64_t seed, uint32_t max_links, double max_fuzz, uint32_t flags,
+                          void* d_hits_out, size_t d_hits_bytes, void* d_albedo_out, size_t d_albedo_bytes, void* hip_stream);
+int rt_query_camera_chain_guide(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
+                                uint32_t max_links, double max_fuzz, uint32_t flags, double* guide_out, double* albedo_sum_out, uint32_t* links_out);
+int rt_query_camera_chain_guide_device(rt_scene*, const rt_camera*, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples, uint64_t seed,
+                                       uint32_t max_links, double max_fuzz, uint32_t flags, void* d_guide, size_t d_guide_bytes,
+                                       void* d_albedo_sum, size_t d_albedo_sum_bytes, void* d_links, size_t d_links_bytes, void* hip_stream);
+int rt_chain_step_host(rt_scene*, uint32_t n, const double* rays, const double* hits, double max_fuzz,
+                       double* next_rays_out, double* weight_out, uint32_t* status_out);
+/* A progressive frame's guide through specular chains: after set_guide_chain(L > 0, max_fuzz) every denoised resolve builds its guide AND its
+ * albedo sums from rt_query_camera_chain_guide_device(first_sample 0, the frame's guide_samples, the frame's seed, L, max_fuzz) — one launch.
+ * The albedo resolves then demodulate by those sums over guide_samples: their albedo_samples argument only says that the frame is demodulated.
+ * Setting another value drops the packed guide and the albedo sums, as rt_progressive_set_guide_samples does.  L = 0 (the default): the
+ * frame is byte for byte what it is without this call.  rt_progressive_set_view reprojects with FIRST-hit records whatever the setting
+ * (a chain record's point is not seen directly from the camera).  Checkpoints do not carry the setting.  Errors: L > 64, max_fuzz negative or NaN. */
+int rt_progressive_set_guide_chain(void* frame, uint32_t max_links, double max_fuzz);
+int rt_progressive_guide_chain_info(void* frame, uint32_t* max_links_out, double* max_fuzz_out);
 
 /* What a material handle stands for (host only, no GPU): kind_texture_out[0] = the kind (0 Lambertian, 1 Metal, 2 Dielectric, 3 DiffuseLight,
  * 4 Isotropic, 5 PBR), [1] = its texture handle (-1 for Metal and Dielectric); albedo_out = Metal's albedo (0 otherwise).  A bad handle is an error. */

@@ -154,6 +154,15 @@ SIGNATURES = {
     "guide_from_hits_host": (_int, [_ptr, _u32, _u64, _ptr]),
     "progressive_set_guide_samples": (_int, [_ptr, _u32]),
     "progressive_guide_info": (_int, [_ptr, c_u32_p, c_u64_p]),
+    # specular-chain guides
+    "query_chain": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _f64, _u32, _ptr, _ptr]),
+    "query_chain_device": (_int, [_ptr, _u32, _ptr, _f64, _u64, _u32, _f64, _u32, _ptr, C.c_size_t, _ptr, C.c_size_t, _ptr]),
+    "query_camera_chain_guide": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u32, _u64, _u32, _f64, _u32, _ptr, _ptr, _ptr]),
+    "query_camera_chain_guide_device": (_int, [_ptr, _cam_p, _u32, _u32, _u32, _u32, _u64, _u32, _f64, _u32, _ptr, C.c_size_t, _ptr, C.c_size_t,
+                                               _ptr, C.c_size_t, _ptr]),
+    "chain_step_host": (_int, [_ptr, _u32, _ptr, _ptr, _f64, _ptr, _ptr, _ptr]),
+    "progressive_set_guide_chain": (_int, [_ptr, _u32, _f64]),
+    "progressive_guide_chain_info": (_int, [_ptr, c_u32_p, c_double_p]),
     "material_info": (_int, [_ptr, _int, C.POINTER(C.c_int32), c_double_p]),
     # denoising
     "denoise_host": (_int, [_ptr, _u64, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr]),

@@ -15,6 +15,7 @@
 #include "rt_adaptive.h"
 #include "rt_denoise_frame.h"
 #include "rt_reproject.h"
+#include "rt_chain.h"
 
 using namespace rt;
 
@@ -41,6 +42,9 @@ struct Progressive {
     // rt_progressive_set_guide_samples: 1 is the guide above; n > 1 builds it from samples [0, n) of this view under the frame's seed instead
     // (rt_query_camera_guide_device, rt_guide.h).  guide_builds counts the guides built, of either kind.
     uint32_t guide_samples = 1; uint64_t guide_builds = 0;
+    // rt_progressive_set_guide_chain: chain_links > 0 builds the guide AND the albedo sums from the specular-chain records of samples
+    // [0, guide_samples) (rt_query_camera_chain_guide_device, rt_chain.h) in one launch; albedo_chain says that d_alb_sum holds such sums
+    uint32_t chain_links = 0; double chain_fuzz = 0.0; bool albedo_chain = false;
     // rt_progressive_resolve_denoised_albedo_rgb8's own, beside the above: the albedo sums of samples [0, albedo_samples) of this view under
     // the frame's seed (rt_query_camera_albedo_device), built when first asked for and kept until rt_progressive_reset or another
     // albedo_samples, and the demodulated frame of a run (24 + 24 bytes per pixel).  albedo_builds counts the launches that built d_alb_sum.
@@ -721,6 +725,17 @@ static int progressive_view_records(Progressive* p, const rt_camera* cam, uint64
     if (p->guide_samples == 1u) return rt_query_camera_device(p->sc, cam, p->W, p->H, 0u, seed, 0u, nullptr, d_hits, hit_bytes, nullptr);
     return rt_query_camera_guide_device(p->sc, cam, p->W, p->H, 0u, p->guide_samples, seed, 0u, d_hits, hit_bytes, nullptr, 0u, nullptr);
 }
+// ... and with the chain on (rt_progressive_set_guide_chain) the guide a denoised resolve filters with: the chain records of samples
+// [0, guide_samples) reduced as the averaged guide is, and the frame's albedo sums from the same launch.  rt_progressive_set_view does not
+// come here: it reprojects with progressive_view_records' first hits, whose points are seen directly from the camera.
+static int progressive_chain_records(Progressive* p, void* d_hits, size_t hit_bytes) {
+    HIP_OK(p->d_alb_sum.ensure(p->sum_bytes()));
+    p->albedo_samples = 0; p->albedo_chain = false;
+    if (rt_query_camera_chain_guide_device(p->sc, &p->cam, p->W, p->H, 0u, p->guide_samples, p->seed, p->chain_links, p->chain_fuzz, 0u, d_hits, hit_bytes,
+                                           p->d_alb_sum.get(), p->sum_bytes(), nullptr, 0u, nullptr)) return -1;
+    p->albedo_samples = p->guide_samples; p->albedo_chain = true; p->albedo_builds++;
+    return 0;
+}
 // the image the denoised resolves write and the count word their resolve launch needs, allocated at the first of them
 static int frame_image_ready(Progressive* p) {
     HIP_OK(p->d_dn_rgb8.ensure(p->n_px() * 3)); HIP_OK(p->d_dn_changed.ensure(sizeof(unsigned long long)));
@@ -744,7 +759,7 @@ static int progressive_denoise_prepare(Progressive* p, uint32_t iterations, cons
         DeviceBuffer d_hits;
         HIP_OK(d_hits.alloc(hit_bytes));
         p->guide_valid = false;
-        if (progressive_view_records(p, &p->cam, p->seed, d_hits.get(), hit_bytes)) return -1;
+        if (p->chain_links ? progressive_chain_records(p, d_hits.get(), hit_bytes) : progressive_view_records(p, &p->cam, p->seed, d_hits.get(), hit_bytes)) return -1;
         HIP_OK((hipError_t)launch_denoise_pack(nullptr, 1u, d_hits.as<double>(), flags, nullptr, p->d_dn_ws.as<double>() + 2u * n * DENOISE_COLOR_DOUBLES, (uint32_t)n, nullptr));
         HIP_OK(hipStreamSynchronize(nullptr));
         p->guide_valid = true; p->guide_flags = flags; p->guide_builds++;
@@ -756,6 +771,22 @@ int rt_progressive_set_guide_samples(void* frame, uint32_t n_samples) {
     if (!p) return set_error("null argument");
     if (n_samples == 0u) return set_error("guide_samples must be >= 1 (1: the camera hits of sample 0; n: the averaged record of samples 0 .. n - 1)");
     if (n_samples != p->guide_samples) { p->guide_samples = n_samples; p->guide_valid = false; }
+    return 0;
+}
+int rt_progressive_set_guide_chain(void* frame, uint32_t max_links, double max_fuzz) {
+    Progressive* p = (Progressive*)frame;
+    if (!p) return set_error("null argument");
+    if (refused(chain_check(max_links, max_fuzz, 0u))) return -1;
+    if (max_links != p->chain_links || (max_links != 0u && max_fuzz != p->chain_fuzz)) {
+        p->guide_valid = false; p->albedo_samples = 0; p->albedo_chain = false;
+    }
+    p->chain_links = max_links; p->chain_fuzz = max_fuzz;
+    return 0;
+}
+int rt_progressive_guide_chain_info(void* frame, uint32_t* max_links_out, double* max_fuzz_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!p || !max_links_out || !max_fuzz_out) return set_error("null argument");
+    *max_links_out = p->chain_links; *max_fuzz_out = p->chain_fuzz;
     return 0;
 }
 int rt_progressive_guide_info(void* frame, uint32_t* guide_samples_out, uint64_t* builds_out) {
@@ -909,12 +940,25 @@ int rt_denoise_albedo(const double* rgb_sum, uint64_t samples, const double* alb
 }
 // The albedo sums of samples [0, albedo_samples) of the frame's view in d_alb_sum: built from the scene when the frame holds none or those
 // of another albedo_samples (it holds none while the build is in flight), kept until then or rt_progressive_reset.
-static int frame_albedo_ready(Progressive* p, uint32_t albedo_samples) {
-    const bool build = p->albedo_samples != albedo_samples;
+// With the chain on (rt_progressive_set_guide_chain) the sums are the chain albedos of samples [0, guide_samples), from the launch that builds
+// the guide, and albedo_samples is SET to guide_samples: the caller's value only says that the frame is to be demodulated.
+static int frame_albedo_ready(Progressive* p, uint32_t& albedo_samples) {
+    if (p->chain_links) {
+        albedo_samples = p->guide_samples;
+        if (p->albedo_chain && p->albedo_samples == albedo_samples) return 0;
+        if (frame_scene_current(p, SCENE_GONE_NO_ALBEDO)) return -1;
+        const size_t hit_bytes = p->n_px() * DENOISE_HIT_DOUBLES * sizeof(double);
+        DeviceBuffer d_hits;                        // (the records go: the packed guide the frame holds is that of the same launch arguments)
+        HIP_OK(d_hits.alloc(hit_bytes));
+        if (progressive_chain_records(p, d_hits.get(), hit_bytes)) return -1;
+        HIP_OK(hipStreamSynchronize(nullptr));
+        return 0;
+    }
+    const bool build = p->albedo_samples != albedo_samples || p->albedo_chain;
     if (build && frame_scene_current(p, SCENE_GONE_NO_ALBEDO)) return -1;
     HIP_OK(p->d_alb_sum.ensure(p->sum_bytes()));
     if (build) {
-        p->albedo_samples = 0;
+        p->albedo_samples = 0; p->albedo_chain = false;
         if (rt_query_camera_albedo_device(p->sc, &p->cam, p->W, p->H, 0u, albedo_samples, p->seed, 0u, p->d_alb_sum.get(), p->sum_bytes(), nullptr)) return -1;
         p->albedo_samples = albedo_samples; p->albedo_builds++;
     }

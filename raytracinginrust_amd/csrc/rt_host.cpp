@@ -22,6 +22,8 @@
 #include "rt_albedo.h"
 #define RT_GUIDE_QUERIES
 #include "rt_guide.h"
+#define RT_CHAIN_QUERIES
+#include "rt_chain.h"
 #include "rt_pixels.h"
 #include "rt_kat.h"
 #include "rt_resolve.h"     // (these four: the loop sizes rt_debug_loop_limits reports)
@@ -1743,6 +1745,99 @@ int rt_query_camera_guide(rt_scene* sc, const rt_camera* cam, uint32_t W, uint32
     HIP_OK(hipMemcpy(guide_out, d_guide.get(), guide_bytes, hipMemcpyDeviceToHost));    // (waits for the kernel: the null stream)
     if (albedo_sum_out) HIP_OK(hipMemcpy(albedo_sum_out, d_alb.get(), alb_bytes, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// ---------------------------------------------------------------- specular-chain guides (csrc/rt_chain.h: the definition and the link step;
+// rt_chain.hip: the kernel; rt_chain_cpu.cpp: the step on the host)
+static int chain_args(uint32_t max_links, double max_fuzz, uint32_t flags) {
+    const std::string m = chain_check(max_links, max_fuzz, flags);
+    return m.empty() ? 0 : set_err(m);
+}
+// One chain launch: query_launch with the chain kernels in the query kernels' place
+static int chain_launch(Scene& s, const rt_camera* camp, uint32_t W, uint32_t H, ChainArgs A, hipStream_t stream) {
+    return query_launch_as(s, camp, W, H, A.seed, A.n, "chain-query",
+                           [&](uint32_t feats, bool camera, size_t lds) { return chain_blocks_per_cu(feats, camera, A.albedo != nullptr, lds); },
+                           [&](const KParams<double>& P, uint32_t feats, bool camera, uint32_t n_blocks, size_t shmem, hipStream_t st) {
+                               return launch_chain(P, A, feats, camera, n_blocks, shmem, st); }, stream);
+}
+int rt_query_chain_device(rt_scene* sc, uint32_t n, const void* d_rays, double t_min, uint64_t seed, uint32_t max_links, double max_fuzz, uint32_t flags,
+                          void* d_hits_out, size_t d_hits_bytes, void* d_albedo_out, size_t d_albedo_bytes, void* hip_stream) {
+    if (!sc || !d_rays || !d_hits_out) return set_err("null argument");
+    if (chain_args(max_links, max_fuzz, flags)) return -1;
+    if (n == 0) return 0;
+    if (d_hits_bytes < (size_t)n * QUERY_HIT_DOUBLES * sizeof(double)) return set_err("hit buffer too small for n * 16 doubles (128 bytes per ray)");
+    if (d_albedo_out && d_albedo_bytes < (size_t)n * 3u * sizeof(double)) return set_err("albedo buffer too small for n * 3 doubles (24 bytes per ray)");
+    if (query_aligned(d_rays, "d_rays") || query_aligned(d_hits_out, "d_hits_out")) return -1;
+    if (((uintptr_t)d_albedo_out & 7u) != 0u) return set_err("d_albedo_out must be 8-byte aligned");
+    if (need_device_and_flat(sc->s)) return -1;
+    ChainArgs A; A.rays = (const double*)d_rays; A.hits = (double*)d_hits_out; A.albedo = (double*)d_albedo_out; A.links = nullptr;
+    A.n = n; A.first_sample = 0u; A.n_samples = 1u; A.max_links = max_links; A.t_min = t_min; A.max_fuzz = max_fuzz; A.seed = seed;
+    return chain_launch(sc->s, nullptr, 0u, 0u, A, (hipStream_t)hip_stream);
+}
+int rt_query_chain(rt_scene* sc, uint32_t n, const double* rays, double t_min, uint64_t seed, uint32_t max_links, double max_fuzz, uint32_t flags,
+                   double* hits_out, double* albedo_out) {
+    if (!sc || !rays || !hits_out) return set_err("null argument");
+    if (chain_args(max_links, max_fuzz, flags)) return -1;
+    if (n == 0) return 0;
+    if (need_device_and_flat(sc->s)) return -1;
+    const size_t ray_bytes = (size_t)n * QUERY_RAY_DOUBLES * sizeof(double), alb_bytes = (size_t)n * 3u * sizeof(double), hit_bytes = (size_t)n * QUERY_HIT_DOUBLES * sizeof(double);
+    DeviceBuffer d_rays, d_alb, d_hits;
+    HIP_OK(d_rays.alloc(ray_bytes)); HIP_OK(d_hits.alloc(hit_bytes));
+    if (albedo_out) HIP_OK(d_alb.alloc(alb_bytes));
+    HIP_OK(hipMemcpy(d_rays.get(), rays, ray_bytes, hipMemcpyHostToDevice));
+    if (rt_query_chain_device(sc, n, d_rays.get(), t_min, seed, max_links, max_fuzz, flags, d_hits.get(), hit_bytes, d_alb.get(), alb_bytes, nullptr)) return -1;
+    HIP_OK(hipMemcpy(hits_out, d_hits.get(), hit_bytes, hipMemcpyDeviceToHost));        // (waits for the kernel: the null stream)
+    if (albedo_out) HIP_OK(hipMemcpy(albedo_out, d_alb.get(), alb_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+int rt_query_camera_chain_guide_device(rt_scene* sc, const rt_camera* cam, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
+                                       uint64_t seed, uint32_t max_links, double max_fuzz, uint32_t flags, void* d_guide, size_t d_guide_bytes,
+                                       void* d_albedo_sum, size_t d_albedo_sum_bytes, void* d_links, size_t d_links_bytes, void* hip_stream) {
+    if (query_camera_albedo_args(sc, cam, d_guide, W, H, first_sample, n_samples, 0u)) return -1;
+    if (chain_args(max_links, max_fuzz, flags)) return -1;
+    if ((uint64_t)n_samples * max_links > 0xFFFFFFFFull) return set_err("n_samples * max_links must be <= 2^32 - 1 (a pixel's link count is 32 bits)");
+    const uint32_t n = W * H;
+    if (d_guide_bytes < (size_t)n * GUIDE_DOUBLES * sizeof(double)) return set_err("guide buffer too small for W * H * 16 doubles (128 bytes per pixel)");
+    if (query_aligned(d_guide, "d_guide")) return -1;
+    if (d_albedo_sum && d_albedo_sum_bytes < (size_t)n * 3u * sizeof(double)) return set_err("albedo buffer too small for W * H * 3 doubles (24 bytes per pixel)");
+    if (((uintptr_t)d_albedo_sum & 7u) != 0u) return set_err("d_albedo_sum must be 8-byte aligned");
+    if (d_links && d_links_bytes < (size_t)n * sizeof(uint32_t)) return set_err("links buffer too small for W * H uint32 (4 bytes per pixel)");
+    if (((uintptr_t)d_links & 3u) != 0u) return set_err("d_links must be 4-byte aligned");
+    if (need_device_and_flat(sc->s)) return -1;
+    ChainArgs A; A.rays = nullptr; A.hits = (double*)d_guide; A.albedo = (double*)d_albedo_sum; A.links = (uint32_t*)d_links;
+    A.n = n; A.first_sample = first_sample; A.n_samples = n_samples; A.max_links = max_links; A.t_min = 0.00001; A.max_fuzz = max_fuzz; A.seed = seed;
+    return chain_launch(sc->s, cam, W, H, A, (hipStream_t)hip_stream);
+}
+int rt_query_camera_chain_guide(rt_scene* sc, const rt_camera* cam, uint32_t W, uint32_t H, uint32_t first_sample, uint32_t n_samples,
+                                uint64_t seed, uint32_t max_links, double max_fuzz, uint32_t flags, double* guide_out, double* albedo_sum_out, uint32_t* links_out) {
+    if (query_camera_albedo_args(sc, cam, guide_out, W, H, first_sample, n_samples, 0u)) return -1;
+    if (chain_args(max_links, max_fuzz, flags)) return -1;
+    if (need_device_and_flat(sc->s)) return -1;
+    const size_t n = (size_t)W * H, guide_bytes = n * GUIDE_DOUBLES * sizeof(double), alb_bytes = n * 3u * sizeof(double), link_bytes = n * sizeof(uint32_t);
+    DeviceBuffer d_guide, d_alb, d_links;
+    HIP_OK(d_guide.alloc(guide_bytes));
+    if (albedo_sum_out) HIP_OK(d_alb.alloc(alb_bytes));
+    if (links_out) HIP_OK(d_links.alloc(link_bytes));
+    if (rt_query_camera_chain_guide_device(sc, cam, W, H, first_sample, n_samples, seed, max_links, max_fuzz, flags, d_guide.get(), guide_bytes, d_alb.get(), alb_bytes,
+                                           d_links.get(), link_bytes, nullptr)) return -1;
+    HIP_OK(hipMemcpy(guide_out, d_guide.get(), guide_bytes, hipMemcpyDeviceToHost));    // (waits for the kernel: the null stream)
+    if (albedo_sum_out) HIP_OK(hipMemcpy(albedo_sum_out, d_alb.get(), alb_bytes, hipMemcpyDeviceToHost));
+    if (links_out) HIP_OK(hipMemcpy(links_out, d_links.get(), link_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+// The link step on the host, no device: the materials come from the scene's host-side table, by the records' word [11]
+int rt_chain_step_host(rt_scene* sc, uint32_t n, const double* rays, const double* hits, double max_fuzz,
+                       double* next_rays_out, double* weight_out, uint32_t* status_out) {
+    if (!sc || !rays || !hits || !next_rays_out || !weight_out || !status_out) return set_err("null argument");
+    if (chain_args(0u, max_fuzz, 0u)) return -1;
+    std::vector<ChainMaterial> table(sc->s.materials.size());
+    for (size_t k = 0; k < table.size(); k++) {
+        const DMaterial<double>& m = sc->s.materials[k];
+        table[k].kind = m.kind & MAT_KIND_MASK; table[k].param = m.param;
+        for (int j = 0; j < 3; j++) table[k].albedo[j] = m.albedo[j];
+    }
+    const std::string msg = chain_step_host(table.data(), table.size(), n, rays, hits, max_fuzz, next_rays_out, weight_out, status_out);
+    return msg.empty() ? 0 : set_err(msg);
 }
 
 // ---------------------------------------------------------------- radiance queries

@@ -6,7 +6,8 @@
 //     rtrender [--scene cornell|random|final|teapot|two_sphere|two_perlin|earth|light_room|smoke|progress] [--width W] [--height H] [--spp N] [--depth D]
 //              [--seed S] [--obj teapot.obj] [--earth earth.ppm] [--f32] [--fast-bvh] [--gpus N] [--progressive N] [--aov normal|depth|material|albedo FILE] [--panorama FILE]
 //              [--denoise K[,SIGMA_C,SIGMA_N,SIGMA_P]] [--denoise-albedo N] [--denoise-variance SIGMA_V] [--until-error TAU] [--max-samples M] [--aov error FILE]
-//              [--adaptive] [--aov samples FILE] [--denoise-guide N] [--aov coverage FILE] [--orbit FRAMES,DEGREES [--history CAP] [--out FILE]] > image.ppm
+//              [--adaptive] [--aov samples FILE] [--denoise-guide N] [--aov coverage FILE] [--denoise-chain LINKS[,FUZZ]] [--aov links FILE]
+//              [--orbit FRAMES,DEGREES [--history CAP] [--out FILE]] > image.ppm
 //
 // --denoise K[,c,n,p] (opt-in): the frame through the edge-avoiding a-trous filter before it is written (rt_denoise: K iterations, guided by
 // sample 0's camera hits of this --seed, or --denoise-guide's record); with --progressive the frame resolves itself denoised on the device (rt_progressive_resolve_denoised_rgb8).
@@ -15,6 +16,10 @@
 // --denoise-guide N (with --denoise): the filter is guided by the averaged first-hit record of samples [0, N) of this --seed
 // (rt_query_camera_guide: what the lens, the shutter and the pixel's area see) instead of sample 0's; with --progressive the frame builds it
 // (rt_progressive_set_guide_samples).  --aov coverage FILE: that record's hit count / N as a grey image.
+// --denoise-chain LINKS[,FUZZ] (with --denoise): the guide — and with --denoise-albedo the albedo, then over --denoise-guide N's samples — is taken at
+// the first non-specular surface behind up to LINKS (1 .. 64) mirrors (fuzz <= FUZZ, default 0) and glass surfaces (rt_query_camera_chain_guide);
+// with --progressive the frame builds it (rt_progressive_set_guide_chain).  --aov links FILE: the links followed per pixel over those samples,
+// grey, 255 at LINKS per sample.
 // --denoise-variance SIGMA_V (with --progressive N and --denoise K): the colour stop is SIGMA_V standard deviations of the frame's own
 // per-pixel variance instead of SIGMA_C (rt_progressive_resolve_denoised_variance_rgb8); the frame keeps moments and needs at least two passes.
 // With --denoise-albedo as well, and on an --adaptive frame with any of the three, the frame is denoised as it is — per-pixel counts, its
@@ -260,6 +265,8 @@ static const char* AOV_HELP =
     "                --denoise-albedo N when that is given, else sample 0's (a miss, glass and emitters: 255 255 255)\n"
     "      coverage  grey, the fraction of the samples [0, N) of --denoise-guide N (default 1) whose camera ray hits anything: hits / N * 255.999\n"
     "                truncated (rt_query_camera_guide's word 15)\n"
+    "      links     (with --denoise-chain LINKS[,FUZZ]) grey, the links followed through mirrors and glass over the samples [0, N) of\n"
+    "                --denoise-guide N (default 1): links / (N * LINKS) * 255.999 truncated (rt_query_camera_chain_guide's links_out)\n"
     "      error     (with --progressive N, written BESIDE the image when the frame ends) grey, the estimated standard error of the pixel in\n"
     "                display units: sqrt(e2) * 256 * 8 truncated, held to 255 — one code value of standard error is grey 8; not finite: 255\n"
     "      samples   (with --adaptive, written BESIDE the image when the frame ends) grey, the samples the pixel holds: 255 * n / the largest n, truncated\n";
@@ -277,6 +284,11 @@ static void write_albedo_aov(const std::string& path, const std::vector<double>&
 static void write_coverage_aov(const std::string& path, const std::vector<double>& guide, uint32_t n_samples, uint32_t W, uint32_t H) {
     std::vector<uint8_t> img(guide.size() / 16u * 3u);
     for (size_t p = 0; p < guide.size() / 16u; p++) img[p * 3] = img[p * 3 + 1] = img[p * 3 + 2] = (uint8_t)aov_level(guide[p * 16 + 15] / (double)n_samples * 255.999);
+    write_ppm_rgb8(path.c_str(), img, W, H);
+}
+static void write_links_aov(const std::string& path, const std::vector<uint32_t>& links, uint32_t n_samples, uint32_t max_links, uint32_t W, uint32_t H) {
+    std::vector<uint8_t> img(links.size() * 3u);
+    for (size_t p = 0; p < links.size(); p++) img[p * 3] = img[p * 3 + 1] = img[p * 3 + 2] = (uint8_t)aov_level((double)links[p] / ((double)n_samples * (double)max_links) * 255.999);
     write_ppm_rgb8(path.c_str(), img, W, H);
 }
 static void write_error_aov(const std::string& path, const std::vector<double>& e2, uint32_t W, uint32_t H) {
@@ -323,6 +335,7 @@ int main(int argc, char** argv) {
     bool want_denoise = false; DenoiseSettings dn;                          // --denoise K[,sigma_c,sigma_n,sigma_p]: filter the frame before it is written
     uint32_t guide_samples = 0;                                             // --denoise-guide N: guide the filter by the averaged record of samples [0, N) (0: sample 0's)
     uint32_t albedo_samples = 0;                                            // --denoise-albedo N: demodulate by the albedo of samples [0, N) (0: the plain filter)
+    ChainSettings chain; chain.max_links = 0u;                              // --denoise-chain LINKS[,FUZZ]: guide and albedo behind mirrors and glass (0: first hits)
     double sigma_v = 0.0;                                                   // --denoise-variance SIGMA_V: the variance-guided colour stop (0: the plain filter)
     uint32_t progressive = 0;                                               // --progressive N: passes of N samples per pixel (0: one call)
     bool adaptive = false;                                                  // --adaptive: sample only the pixels whose estimated error still exceeds --until-error
@@ -354,7 +367,7 @@ int main(int argc, char** argv) {
         else if (a == "--progressive") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--progressive needs a pass size >= 1\n"); return 2; } progressive = (uint32_t)n; }
         else if (a == "--aov") {
             aov_kind = next(); aov_path = next();
-            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material" && aov_kind != "albedo" && aov_kind != "error" && aov_kind != "samples" && aov_kind != "coverage") { std::fprintf(stderr, "--aov needs normal, depth, material, albedo, coverage, error or samples\n%s", AOV_HELP); return 2; }
+            if (aov_kind != "normal" && aov_kind != "depth" && aov_kind != "material" && aov_kind != "albedo" && aov_kind != "error" && aov_kind != "samples" && aov_kind != "coverage" && aov_kind != "links") { std::fprintf(stderr, "--aov needs normal, depth, material, albedo, coverage, links, error or samples\n%s", AOV_HELP); return 2; }
         }
         else if (a == "--panorama") panorama_path = next();
         else if (a == "--until-error") { until_error = std::atof(next()); if (!(until_error >= 0.0)) { std::fprintf(stderr, "--until-error needs a standard error >= 0 in display units (0.00390625 is one code value)\n"); return 2; } }
@@ -369,6 +382,12 @@ int main(int argc, char** argv) {
         }
         else if (a == "--denoise-albedo") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--denoise-albedo needs a sample count >= 1\n"); return 2; } albedo_samples = (uint32_t)n; }
         else if (a == "--denoise-guide") { const int n = std::atoi(next()); if (n < 1) { std::fprintf(stderr, "--denoise-guide needs a sample count >= 1\n"); return 2; } guide_samples = (uint32_t)n; }
+        else if (a == "--denoise-chain") {
+            unsigned links = 0; double fuzz = 0.0;
+            const int got = std::sscanf(next(), "%u,%lf", &links, &fuzz);
+            if ((got != 1 && got != 2) || links < 1u || links > 64u || !(fuzz >= 0.0)) { std::fprintf(stderr, "--denoise-chain needs LINKS (1 .. 64) or LINKS,FUZZ (FUZZ >= 0)\n"); return 2; }
+            chain.max_links = links; chain.max_fuzz = fuzz;
+        }
         else if (a == "--denoise-variance") { sigma_v = std::atof(next()); if (!(sigma_v > 0.0)) { std::fprintf(stderr, "--denoise-variance needs a colour stop > 0 in standard deviations (inf switches it off)\n"); return 2; } }
         else if (a == "--orbit") {
             unsigned n = 0;
@@ -386,6 +405,8 @@ int main(int argc, char** argv) {
                         "                                     and multiply back: textures are kept (textured scenes need it); also with --progressive\n"
                         "  --denoise-guide N                  with --denoise: guide the filter by the averaged first-hit record of samples 0 .. N-1 (lens, shutter and\n"
                         "                                     pixel area) instead of sample 0's; also with --progressive\n"
+                        "  --denoise-chain LINKS[,FUZZ]       with --denoise: guide (and albedo) at the first non-specular surface behind up to LINKS mirrors\n"
+                        "                                     (fuzz <= FUZZ, default 0) and glass surfaces; --aov links FILE: the links followed per pixel\n"
                         "  --denoise-variance SIGMA_V         with --progressive N and --denoise K: the colour stop in standard deviations of the frame's own\n"
                         "                                     per-pixel variance instead of SIGMA_C; needs at least two passes (--spp more than N);\n"
                         "                                     also with --denoise-albedo, and all three also with --adaptive\n"
@@ -409,7 +430,9 @@ int main(int argc, char** argv) {
     if (aov_kind == "samples" && !adaptive) { std::fprintf(stderr, "--aov samples goes with --adaptive\n"); return 2; }
     if (max_samples != 0u && until_error < 0.0) { std::fprintf(stderr, "--max-samples goes with --until-error TAU\n"); return 2; }
     if (albedo_samples != 0u && !want_denoise && aov_kind != "albedo") { std::fprintf(stderr, "--denoise-albedo goes with --denoise K (or --aov albedo)\n"); return 2; }
-    if (guide_samples != 0u && !want_denoise && aov_kind != "coverage") { std::fprintf(stderr, "--denoise-guide goes with --denoise K (or --aov coverage)\n"); return 2; }
+    if (guide_samples != 0u && !want_denoise && aov_kind != "coverage" && aov_kind != "links") { std::fprintf(stderr, "--denoise-guide goes with --denoise K (or --aov coverage)\n"); return 2; }
+    if (chain.max_links != 0u && !want_denoise && aov_kind != "links") { std::fprintf(stderr, "--denoise-chain goes with --denoise K (or --aov links)\n"); return 2; }
+    if (aov_kind == "links" && chain.max_links == 0u) { std::fprintf(stderr, "--aov links goes with --denoise-chain LINKS\n"); return 2; }
     if (sigma_v != 0.0 && (!want_denoise || progressive == 0u)) { std::fprintf(stderr, "--denoise-variance goes with --progressive N and --denoise K\n"); return 2; }
     if (orbit_frames != 0u && (progressive == 0u || adaptive || until_error >= 0.0 || !aov_kind.empty() || albedo_samples != 0u || sigma_v != 0.0)) {
         std::fprintf(stderr, "--orbit goes with --progressive N, and of the other options only with --denoise K and --denoise-guide N\n"); return 2;
@@ -486,6 +509,11 @@ int main(int argc, char** argv) {
             } else if (aov_kind == "coverage") {
                 const uint32_t n = guide_samples ? guide_samples : 1u;
                 write_coverage_aov(aov_path, query_camera_guide(s, camera, image_width, image_height, 0u, n, seed), n, image_width, image_height);
+            } else if (aov_kind == "links") {
+                const uint32_t n = guide_samples ? guide_samples : 1u;
+                std::vector<uint32_t> links;
+                query_camera_chain_guide(s, camera, image_width, image_height, chain, 0u, n, seed, nullptr, &links);
+                write_links_aov(aov_path, links, n, chain.max_links, image_width, image_height);
             } else
             write_aov(aov_kind, aov_path, query_camera(s, camera, image_width, image_height, 0u, seed), image_width, image_height);
             std::fprintf(stderr, "Done.\n");
@@ -508,6 +536,7 @@ int main(int argc, char** argv) {
             const bool want_moments = until_error >= 0.0 || aov_kind == "error" || sigma_v != 0.0;
             if (want_moments) frame.enable_moments();
             if (guide_samples) frame.set_guide_samples(guide_samples);
+            if (chain.max_links) frame.set_guide_chain(chain.max_links, chain.max_fuzz);
             if (orbit_frames) {
                 // the views: lookfrom turned about the axis vup through lookat (Rodrigues' rotation), everything else the scene's camera
                 const rt_camera& c0 = camera.c;
@@ -590,6 +619,14 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "rt_render_multi: slowest kernel %.2f ms, gather %.3f ms, un-permute %.3f ms, call %.2f ms\n", ms[0], ms[1], ms[2], ms[3]);
         }
         // the guide: sample 0's records, or the averaged records of samples [0, --denoise-guide N)
+        if (want_denoise && chain.max_links) {                              // guide and albedo from one chain query over the guide's samples
+            const uint32_t n = guide_samples ? guide_samples : 1u;
+            std::vector<double> albedo_sum;
+            const std::vector<double> guide = query_camera_chain_guide(s, camera, image_width, image_height, chain, 0u, n, seed, albedo_samples ? &albedo_sum : nullptr);
+            pixel_sums = albedo_samples ? denoise_albedo(pixel_sums, samples_per_pixel, albedo_sum, n, guide, image_width, image_height, dn)
+                                        : denoise(pixel_sums, samples_per_pixel, guide, image_width, image_height, dn);
+            want_denoise = false;
+        }
         auto guide_records = [&]() { return guide_samples > 1u ? query_camera_guide(s, camera, image_width, image_height, 0u, guide_samples, seed)
                                                                : query_camera_records(s, camera, image_width, image_height, 0u, seed); };
         if (want_denoise && albedo_samples)

@@ -423,7 +423,7 @@ class Progressive:
     """
 
     def __init__(self, b: SceneBuilder, cam: CameraParams, background, W: int, H: int, max_depth: int, seed: int = 0x5EED, flags: int = RT_F64,
-                 moments: bool = False, adaptive: bool = False, guide_samples: int = 1):
+                 moments: bool = False, adaptive: bool = False, guide_samples: int = 1, guide_chain=None):
         self._lib = _rt()
         self.W, self.H = int(W), int(H)
         bg = (C.c_double * 3)(*[float(x) for x in background])
@@ -439,6 +439,21 @@ class Progressive:
             self.enable_adaptive()
         if guide_samples != 1:
             self.set_guide_samples(guide_samples)
+        if guide_chain is not None:
+            self.set_guide_chain(*guide_chain)
+
+    def set_guide_chain(self, max_links: int, max_fuzz: float = 0.0) -> None:
+        """rt_progressive_set_guide_chain: max_links > 0 builds the guide and the albedo sums of every denoised resolve from specular-chain
+        records of samples [0, guide_samples) (`query_camera_chain_guide`); the albedo resolves then demodulate by those sums over
+        guide_samples, whatever albedo_samples they are given.  0 (the default): first hits, as without this call.  Another value drops the
+        packed guide and the albedo sums.  `set_view` reprojects with first-hit records whatever the setting."""
+        _check(self._lib.rt_progressive_set_guide_chain(self._h, int(max_links), float(max_fuzz)))
+
+    def guide_chain_info(self):
+        """(max_links, max_fuzz) in force."""
+        n, f = C.c_uint32(), C.c_double()
+        _check(self._lib.rt_progressive_guide_chain_info(self._h, C.byref(n), C.byref(f)))
+        return int(n.value), float(f.value)
 
     def set_guide_samples(self, n: int) -> None:
         """rt_progressive_set_guide_samples: the guide of every denoised resolve — 1 (the default): the camera hits of sample 0; n > 1: the
@@ -1014,6 +1029,88 @@ def query_camera_guide_device(b: SceneBuilder, cam: CameraParams, W: int, H: int
         raise ValueError("d_guide_bytes / d_albedo_sum_bytes are needed with raw pointers")
     _check(_rt().rt_query_camera_guide_device(b.h, C.byref(cam), W, H, first_sample, n_samples, seed, 0, C.c_void_p(g_ptr), gbytes,
                                               C.c_void_p(a_ptr), abytes, C.c_void_p(stream)))
+
+
+# ---- specular-chain guides (rt_query_chain*, rt_query_camera_chain_guide*, rt_chain_step_host): csrc/rt_chain.h
+# the Metal fuzz up to which a chain follows a mirror: 0.0 follows perfect mirrors only.  An untuned starting value, not a measured optimum.
+CHAIN_MAX_FUZZ = 0.0
+CHAIN_MAX_LINKS = 64
+CHAIN_STATUS = ("continue", "non_specular", "miss", "absorbed", "non_finite", "fuzz")
+# the chain record's 16 doubles by name: HIT_FIELDS with t the path length in units of the first ray's parameter, and the links followed
+CHAIN_FIELDS = dict(HIT_FIELDS, links=slice(15, 16))
+
+
+def query_chain(b: SceneBuilder, rays, max_links: int, max_fuzz: float = CHAIN_MAX_FUZZ, t_min: float = 1e-5, seed: int = 0, want_albedo: bool = False):
+    """rt_query_chain: n rays followed through mirrors and glass to the first non-specular surface, (n, 7) f64 -> (n, 16) (CHAIN_FIELDS);
+    with want_albedo also (n, 3), the albedo there times the mirrors' tints.  max_links = 0 gives `query_hits`' and `query_albedo`'s words."""
+    r = np.ascontiguousarray(rays, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] != RAY_DOUBLES:
+        raise ValueError(f"rays of shape {r.shape}: want (n, {RAY_DOUBLES})")
+    hits = np.zeros((len(r), HIT_DOUBLES), dtype=np.float64)
+    alb = np.zeros((len(r), 3), dtype=np.float64) if want_albedo else None
+    _check(_rt().rt_query_chain(b.h, len(r), r.ctypes.data, float(t_min), seed, int(max_links), float(max_fuzz), 0, hits.ctypes.data,
+                                alb.ctypes.data if want_albedo else None))
+    return (hits, alb) if want_albedo else hits
+
+
+def query_chain_device(b: SceneBuilder, n: int, d_rays, d_hits, max_links: int, max_fuzz: float = CHAIN_MAX_FUZZ, d_albedo=None, t_min: float = 1e-5,
+                       seed: int = 0, stream: int = 0, d_hits_bytes=None, d_albedo_bytes=None) -> None:
+    """rt_query_chain_device: the same for buffers in device memory (torch tensors of f64, or raw pointers with their sizes), enqueued on
+    `stream`; never waits.  d_rays and d_hits 16-byte aligned."""
+    rays_ptr, _ = _device_buffer(d_rays)
+    hits_ptr, hbytes = _device_buffer(d_hits)
+    hbytes = hbytes if d_hits_bytes is None else int(d_hits_bytes)
+    alb_ptr, abytes = (None, 0) if d_albedo is None else _device_buffer(d_albedo)
+    abytes = abytes if d_albedo_bytes is None else int(d_albedo_bytes)
+    if abytes is None or hbytes is None:
+        raise ValueError("d_hits_bytes / d_albedo_bytes are needed with raw pointers")
+    _check(_rt().rt_query_chain_device(b.h, n, C.c_void_p(rays_ptr), float(t_min), seed, int(max_links), float(max_fuzz), 0, C.c_void_p(hits_ptr), hbytes,
+                                       C.c_void_p(alb_ptr), abytes, C.c_void_p(stream)))
+
+
+def query_camera_chain_guide(b: SceneBuilder, cam: CameraParams, W: int, H: int, max_links: int, max_fuzz: float = CHAIN_MAX_FUZZ, first_sample: int = 0,
+                             n_samples: int = 16, seed: int = DEFAULT_SEED, want_albedo: bool = False, want_links: bool = False):
+    """rt_query_camera_chain_guide: per pixel the chain records of samples [first_sample, first_sample + n_samples) reduced as
+    `query_camera_guide` reduces first hits -> (H, W, 16) (GUIDE_FIELDS); with want_albedo also the (H, W, 3) sums of the chain albedos, with
+    want_links also (H, W) uint32, the links followed over all samples.  Returns the guide, or a tuple in that order."""
+    out = np.zeros((H, W, HIT_DOUBLES), dtype=np.float64)
+    alb = np.zeros((H, W, 3), dtype=np.float64) if want_albedo else None
+    links = np.zeros((H, W), dtype=np.uint32) if want_links else None
+    _check(_rt().rt_query_camera_chain_guide(b.h, C.byref(cam), W, H, first_sample, n_samples, seed, int(max_links), float(max_fuzz), 0, out.ctypes.data,
+                                             alb.ctypes.data if want_albedo else None, links.ctypes.data if want_links else None))
+    res = (out,) + ((alb,) if want_albedo else ()) + ((links,) if want_links else ())
+    return res if len(res) > 1 else out
+
+
+def query_camera_chain_guide_device(b: SceneBuilder, cam: CameraParams, W: int, H: int, d_guide, max_links: int, max_fuzz: float = CHAIN_MAX_FUZZ,
+                                    d_albedo_sum=None, d_links=None, first_sample: int = 0, n_samples: int = 16, seed: int = DEFAULT_SEED, stream: int = 0,
+                                    d_guide_bytes=None, d_albedo_sum_bytes=None, d_links_bytes=None) -> None:
+    """rt_query_camera_chain_guide_device: the W*H*16 records (and, when given, the W*H*3 albedo sums and the W*H uint32 link counts) into
+    device memory (torch tensors, or raw pointers with their sizes), enqueued on `stream`; never waits."""
+    g_ptr, gbytes = _device_buffer(d_guide)
+    gbytes = gbytes if d_guide_bytes is None else int(d_guide_bytes)
+    a_ptr, abytes = _device_buffer(d_albedo_sum) if d_albedo_sum is not None else (None, 0)
+    abytes = abytes if d_albedo_sum_bytes is None else int(d_albedo_sum_bytes)
+    l_ptr, lbytes = _device_buffer(d_links) if d_links is not None else (None, 0)
+    lbytes = lbytes if d_links_bytes is None else int(d_links_bytes)
+    if gbytes is None or abytes is None or lbytes is None:
+        raise ValueError("d_guide_bytes / d_albedo_sum_bytes / d_links_bytes are needed with raw pointers")
+    _check(_rt().rt_query_camera_chain_guide_device(b.h, C.byref(cam), W, H, first_sample, n_samples, seed, int(max_links), float(max_fuzz), 0,
+                                                    C.c_void_p(g_ptr), gbytes, C.c_void_p(a_ptr), abytes, C.c_void_p(l_ptr), lbytes, C.c_void_p(stream)))
+
+
+def chain_step_host(b: SceneBuilder, rays, hits, max_fuzz: float = CHAIN_MAX_FUZZ):
+    """rt_chain_step_host (no GPU): one link of a chain on n (ray, record) pairs, (n, 7) and (n, 16) -> the next rays (n, 7), this link's
+    weight factors (n, 3) and the status words (n,) uint32 (CHAIN_STATUS)."""
+    r = np.ascontiguousarray(rays, dtype=np.float64)
+    h = np.ascontiguousarray(hits, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] != RAY_DOUBLES or h.shape != (len(r), HIT_DOUBLES):
+        raise ValueError(f"rays of shape {r.shape} and hits of shape {h.shape}: want (n, {RAY_DOUBLES}) and (n, {HIT_DOUBLES})")
+    nxt = np.zeros_like(r)
+    weight = np.zeros((len(r), 3), dtype=np.float64)
+    status = np.zeros(len(r), dtype=np.uint32)
+    _check(_rt().rt_chain_step_host(b.h, len(r), r.ctypes.data, h.ctypes.data, float(max_fuzz), nxt.ctypes.data, weight.ctypes.data, status.ctypes.data))
+    return nxt, weight, status
 
 
 def guide_from_hits(hits) -> np.ndarray:
