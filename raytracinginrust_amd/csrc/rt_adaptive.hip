@@ -3,8 +3,8 @@
 //
 // A translation unit of its own over rt_kernel.hip's device functions, as rt_radiance.hip is (RT_TU == 3 leaves that file's kernels and launch
 // code out): the bounce loop is radiance_kernel's — world_hit / world_hit_list, finalize_hit, shade_hit, add_radiance, flush_acc, the code the
-// frames run — and nothing is added to the units the frames, the queries and the moments are built from: their objects stay byte for byte
-// what they were.  camera_ray is restated from rt_query.hip for that reason, as rt_albedo.hip restates it.
+// frames run — and nothing is added to the units the frames and the moments are built from.  camera_ray, the cursor's path_step, the
+// staging loop and the scene-class dispatch are the query units' own: rt_query_dev.h.
 //
 // PIXELS: path q = k * n_b + s is sample n[list[k]] + s of output-order pixel list[k], one path per lane, pixel-major: the list is ascending,
 // so the lanes of a wave start on the same pixel or on neighbouring ones.  A lane whose path has ended takes the wave's next path (__ballot +
@@ -17,15 +17,15 @@
 //
 // ELEMENT-WISE: pure streams, no LDS beyond a few words for the block reductions, no scratch.  Doubles of pixel p sit at byte 24 p: 16-byte
 // aligned for even p and 8 bytes past that for odd p when the buffer is 16-byte aligned — one 16-byte and one 8-byte access either way
-// (ld3 / st3; rt_radiance.hip's load_ray is the pattern); buffers that are only 8-byte aligned go through 8-byte accesses.
+// (ld3 / st3; rt_query_dev.h's load_ray is the pattern); buffers that are only 8-byte aligned go through 8-byte accesses.
 #define RT_TU 3
 #include "rt_kernel.hip"
 #include "rt_pixels.h"
 #include "rt_adaptive.h"
+#include "rt_query_dev.h"
 
 namespace rt {
 
-typedef double ad2 __attribute__((ext_vector_type(2)));
 typedef uint32_t au4 __attribute__((ext_vector_type(4)));
 
 // Resident waves per SIMD the register allocation is held to, from -Rpass-analysis=kernel-resource-usage and the loop depth of every scratch
@@ -38,62 +38,10 @@ template <uint32_t FEATS> struct PixelsWaves {
     static constexpr uint32_t v = FEATS == 0u ? RT_PIXELS_LEAN_WAVES :((FEATS & F_NESTED) ? 1u : ((FEATS & ~(uint32_t)(F_BVH | F_TRIS)) == 0u ? 4u : 3u));
 };
 
-// Camera::get_ray for sample `sample` of output-order pixel gp: rt_query.hip camera_ray, expression for expression, the draws in its order
-DEV void pixels_camera_ray(const KParams<double>& P, uint64_t seed, uint32_t gp, uint32_t sample, RayT<double>& ray, Rng& g) {
-    typedef double T;
-    const uint32_t row = gp / P.W;
-    const uint32_t g_i = gp - row * P.W, g_j = P.H - 1u - row;      // row 0 is j = H-1, main.rs:772
-    g = rng_for_path(seed, gp, sample);
-    T random_u = rng_u01(g, T(0));
-    T random_v = rng_u01(g, T(0));
-    T u = (T(g_i) + random_u) / T(P.W - 1u);
-    T v = (T(g_j) + random_v) / T(P.H - 1u);
-    T da, db;
-    for (;;) {
-        da = rng_range(g, T(-1.0), T(1.0));
-        db = rng_range(g, T(-1.0), T(1.0));
-        V3<T> pd = mk<T>(da, db, T(0));
-        if (dot(pd, pd) < T(1.0)) break;
-    }
-    V3<T> rd = P.cam.lens_radius * mk<T>(da, db, T(0));
-    V3<T> offset = ld3(P.cam.cu) * rd.x + ld3(P.cam.cv) * rd.y;
-    T time = P.cam.time0 + rng_u01(g, T(0)) * (P.cam.time1 - P.cam.time0);
-    ray.o = ld3(P.cam.origin) + offset;
-    ray.d = ld3(P.cam.lower_left_corner) + u * ld3(P.cam.horizontal) + v * ld3(P.cam.vertical) - (ld3(P.cam.origin) + offset);
-    ray.tm = time;
-}
-
-// (k, s) + add paths, add <= 64, s < spp: rt_radiance.hip's path_step — no 64-bit division; with spp >= 64 the sample index wraps at most once
-DEV void pixels_path_step(uint32_t k, uint32_t s, uint32_t add, uint32_t spp, uint32_t& k_out, uint32_t& s_out) {
-    const uint64_t t = (uint64_t)s + add;
-    if (spp >= 64u) {
-        const bool wrap = t >= spp;
-        k_out = k + (wrap ? 1u : 0u); s_out = (uint32_t)(wrap ? t - spp : t);
-    } else {
-        const uint32_t q = (uint32_t)t / spp;
-        k_out = k + q; s_out = (uint32_t)t - q * spp;
-    }
-}
-
 template <uint32_t FEATS>
 __global__ void __launch_bounds__(PIXELS_THREADS, PixelsWaves<FEATS>::v) pixels_kernel(const KParams<double> P, const PixelsArgs X) {
     typedef double T;
-    if ((FEATS & F_BVH) && P.n_cached != 0u) {
-        // the filter tree, once per workgroup (rt_query.hip's staging: the host stages the whole tree or nothing): links become LDS addresses
-        typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-        const uint32_t nodes_bytes = P.n_cached * (uint32_t)sizeof(DFNode);
-        const u4* src = (const u4*)P.bvh_f; u4* dst = (u4*)lds_raw;
-        const uint32_t base = lds_base();
-        for (uint32_t i = threadIdx.x; i < nodes_bytes / 16u; i += PIXELS_THREADS) {
-            u4 w = src[i];
-            if (i & 1u) {                                         // second half of a DFNode: max.z-side bounds, skip, info
-                if (w.z != ST_DONE) w.z = base + w.z * (uint32_t)sizeof(DFNode);
-                if (!(w.w & FNODE_LEAF)) w.w = base + w.w * (uint32_t)sizeof(DFNode);
-            }
-            dst[i] = w;
-        }
-        __syncthreads();                                          // the only barrier
-    }
+    if ((FEATS & F_BVH) && P.n_cached != 0u) stage_filter_tree<PIXELS_THREADS>(P);      // once per workgroup
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave_in_block = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // the wave's cursor (wave-uniform: scalar registers): next chunk, and paths [.., + left) of the current one starting at (cur_k, cur_s)
@@ -130,14 +78,14 @@ __global__ void __launch_bounds__(PIXELS_THREADS, PixelsWaves<FEATS>::v) pixels_
             const uint32_t rank = lane_rank(want);
             if (!alive && !got_new && rank < take) {
                 uint32_t k, s;
-                pixels_path_step(cur_k, cur_s, rank, P.spp, k, s);
+                path_step(cur_k, cur_s, rank, P.spp, k, s);
                 const uint32_t gp = X.list[k];                    // k < n_list: the path is one of n_list * n_b
                 if (gp < X.n_px) {
                     const uint32_t first = X.counts ? X.counts[gp] : 0u;
                     if ((uint64_t)first + P.spp <= 0xFFFFFFFFull) { got_new = true; new_px = gp; path_s = first + s; }
                 }
             }
-            pixels_path_step(cur_k, cur_s, take, P.spp, cur_k, cur_s);
+            path_step(cur_k, cur_s, take, P.spp, cur_k, cur_s);
             left -= take;
         }
         if (__ballot(alive || got_new) == 0ull) break;            // no chunk left and every path finished
@@ -147,7 +95,7 @@ __global__ void __launch_bounds__(PIXELS_THREADS, PixelsWaves<FEATS>::v) pixels_
 
         if (got_new) {
             if (acc_px != new_px) { acc_px = new_px; acc.set(0, 0.0); acc.set(1, 0.0); acc.set(2, 0.0); }
-            pixels_camera_ray(P, P.seed, new_px, path_s, ray, rng);       // the pixel's own sample: no seed folding
+            camera_ray(P, P.seed, new_px, path_s, ray, rng);       // the pixel's own sample: no seed folding
             beta = mk<T>(T(1.0), T(1.0), T(1.0));
             depth_left = P.max_depth;
             alive = true;
@@ -183,36 +131,15 @@ __global__ void __launch_bounds__(PIXELS_THREADS, PixelsWaves<FEATS>::v) pixels_
     if (X.nonfinite && n_nonfinite) atomicAdd(X.nonfinite, (unsigned long long)n_nonfinite);
 }
 
-// the instantiation by scene class: radiance_dispatch's rule, restated
-static const uint32_t PF_MESH = F_BVH | F_TRIS, PF_NO_PBR = F_ALL & ~F_PBR, PF_NESTED = F_ALL | F_NESTED;
-template <typename F> static auto pixels_dispatch(uint32_t scene_feats, F&& f) {
-    if (scene_feats == 0u) return f(std::integral_constant<uint32_t, 0u>());
-    if (scene_feats & F_NESTED) return f(std::integral_constant<uint32_t, PF_NESTED>());
-    if ((scene_feats & ~PF_MESH) == 0u) return f(std::integral_constant<uint32_t, PF_MESH>());
-    if ((scene_feats & ~PF_NO_PBR) == 0u) return f(std::integral_constant<uint32_t, PF_NO_PBR>());
-    return f(std::integral_constant<uint32_t, (uint32_t)F_ALL>());
-}
-template <uint32_t FEATS> static hipError_t pixels_allow_lds(size_t shmem) {     // more than the default 64 KB of dynamic LDS needs to be asked for
-    if (shmem <= 65536u) return hipSuccess;
-    return hipFuncSetAttribute((const void*)pixels_kernel<FEATS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+// the instantiation: radiance_kernel's five scene classes
+template <typename G> static auto pixels_kernel_for(uint32_t scene_feats, G&& g) {
+    return scene_class_dispatch_pbr(scene_feats, [&](auto feats) { return g(pixels_kernel<decltype(feats)::value>); });
 }
 int pixels_blocks_per_cu(uint32_t scene_feats, size_t shmem) {
-    return pixels_dispatch(scene_feats, [&](auto feats) {
-        constexpr uint32_t FEATS = decltype(feats)::value;
-        int nb = 0;
-        if (pixels_allow_lds<FEATS>(shmem) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, pixels_kernel<FEATS>, (int)PIXELS_THREADS, shmem) != hipSuccess) return 0;
-        return nb;
-    });
+    return pixels_kernel_for(scene_feats, [&](auto kernel) { return kernel_blocks_per_cu(kernel, PIXELS_THREADS, shmem); });
 }
 hipError_t launch_pixels(const KParams<double>& P, const PixelsArgs& X, uint32_t scene_feats, uint32_t n_blocks, size_t shmem, hipStream_t stream) {
-    return pixels_dispatch(scene_feats, [&](auto feats) {
-        constexpr uint32_t FEATS = decltype(feats)::value;
-        const hipError_t e = pixels_allow_lds<FEATS>(shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((pixels_kernel<FEATS>), dim3(n_blocks), dim3(PIXELS_THREADS), shmem, stream, P, X);
-        return hipGetLastError();
-    });
+    return pixels_kernel_for(scene_feats, [&](auto kernel) { return kernel_launch(kernel, PIXELS_THREADS, n_blocks, shmem, stream, P, X); });
 }
 
 // ------------------------------------------------------------------ the element-wise kernels (rt_adaptive.h (A) - (D))
@@ -221,7 +148,7 @@ template <bool A16> DEV void ld3d(const double* base, uint64_t p, double v[3]) {
     const double* q = base + 3u * p;
     if constexpr (A16) {
         const uint32_t odd = (uint32_t)p & 1u;
-        const ad2 t = *(const ad2*)(q + odd);
+        const d2 t = *(const d2*)(q + odd);
         const double s = odd ? q[0] : q[2];
         v[0] = odd ? s : t.x; v[1] = odd ? t.x : t.y; v[2] = odd ? t.y : s;
     } else { v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; }
@@ -230,8 +157,8 @@ template <bool A16> DEV void st3d(double* base, uint64_t p, const double v[3]) {
     double* q = base + 3u * p;
     if constexpr (A16) {
         const uint32_t odd = (uint32_t)p & 1u;
-        ad2 t; t.x = odd ? v[1] : v[0]; t.y = odd ? v[2] : v[1];
-        *(ad2*)(q + odd) = t;
+        d2 t; t.x = odd ? v[1] : v[0]; t.y = odd ? v[2] : v[1];
+        *(d2*)(q + odd) = t;
         if (odd) q[0] = v[0]; else q[2] = v[2];
     } else { q[0] = v[0]; q[1] = v[1]; q[2] = v[2]; }
 }
@@ -451,8 +378,8 @@ __global__ __launch_bounds__(256) void adaptive_resolve4_kernel(const double* __
     const uint32_t stride = gridDim.x * ADAPTIVE_THREADS;
     uint32_t changed = 0u;
     for (uint32_t g = blockIdx.x * ADAPTIVE_THREADS + threadIdx.x; g < n_groups; g += stride) {
-        const ad2* in = reinterpret_cast<const ad2*>(sum) + (size_t)g * 6u;
-        ad2 v[6];
+        const d2* in = reinterpret_cast<const d2*>(sum) + (size_t)g * 6u;
+        d2 v[6];
 #pragma unroll
         for (int k = 0; k < 6; k++) v[k] = in[k];
         const au4 n4 = reinterpret_cast<const au4*>(cnt)[g];

@@ -3,8 +3,8 @@
 //
 // A translation unit of its own over rt_kernel.hip's device functions (RT_TU == 3, as rt_query.hip and rt_radiance.hip): the search, the
 // record and the texture walk are world_hit / world_hit_list / finalize_hit / tex_eval — the code the frames run — and nothing is added to
-// the units the frames, the queries and the filter are built from: their objects stay byte for byte what they were.  load_ray, camera_ray
-// and the scene-class dispatch are restated from rt_query.hip for that reason (a shared header would have to leave rt_query.o unchanged).
+// the units the frames and the filter are built from.  load_ray, camera_ray, albedo_of and the scene-class dispatch are the query units' own:
+// rt_query_dev.h.
 //
 // Shape: query_kernel's — 256-thread workgroups, at most (CUs x resident workgroups) of them, the filter tree staged in LDS when the WHOLE
 // tree fits, batches of 256 lanes grid-stride, whole waves in every voting search (lanes past n repeat the last lane's work and only skip
@@ -15,10 +15,9 @@
 #include "rt_kernel.hip"
 #define RT_ALBEDO_QUERIES
 #include "rt_albedo.h"
+#include "rt_query_dev.h"
 
 namespace rt {
-
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 // Resident waves per SIMD the register allocation is held to, from -Rpass-analysis=kernel-resource-usage (make asm) and the loop depth of
 // every scratch access (tools/scratch_map.py); the table is in DESIGN §15.  QueryWaves' classes: tex_eval (Perlin turbulence, the image
@@ -27,61 +26,11 @@ template <uint32_t FEATS> struct AlbedoWaves {
     static constexpr uint32_t v = FEATS == 0u ? 5u : ((FEATS & ~(uint32_t)(F_BVH | F_TRIS)) == 0u ? 5u : ((FEATS & F_NESTED) ? 1u : 3u));
 };
 
-// seven doubles at a 16-byte aligned base + 56 k bytes (rt_query.hip load_ray): three 16-byte accesses and one of 8 bytes
-DEV void albedo_load_ray(const double* rays, uint32_t k, RayT<double>& ray) {
-    const double* p = rays + 7ull * k;
-    const uint32_t odd = k & 1u;
-    const d2* q = (const d2*)(p + odd);
-    const d2 a = q[0], b = q[1], c = q[2];
-    const double s = odd ? p[0] : p[6];
-    ray.o = odd ? mk<double>(s, a.x, a.y) : mk<double>(a.x, a.y, b.x);
-    ray.d = odd ? mk<double>(b.x, b.y, c.x) : mk<double>(b.y, c.x, c.y);
-    ray.tm = odd ? c.y : s;
-}
-
-// Camera::get_ray for sample `sample` of output-order pixel gp: rt_query.hip camera_ray, expression for expression, the draws in its order
-DEV void albedo_camera_ray(const KParams<double>& P, uint64_t seed, uint32_t gp, uint32_t sample, RayT<double>& ray, Rng& g) {
-    typedef double T;
-    const uint32_t row = gp / P.W;
-    const uint32_t g_i = gp - row * P.W, g_j = P.H - 1u - row;      // row 0 is j = H-1, main.rs:772
-    g = rng_for_path(seed, gp, sample);
-    T random_u = rng_u01(g, T(0));
-    T random_v = rng_u01(g, T(0));
-    T u = (T(g_i) + random_u) / T(P.W - 1u);
-    T v = (T(g_j) + random_v) / T(P.H - 1u);
-    T da, db;
-    for (;;) {
-        da = rng_range(g, T(-1.0), T(1.0));
-        db = rng_range(g, T(-1.0), T(1.0));
-        V3<T> pd = mk<T>(da, db, T(0));
-        if (dot(pd, pd) < T(1.0)) break;
-    }
-    V3<T> rd = P.cam.lens_radius * mk<T>(da, db, T(0));
-    V3<T> offset = ld3(P.cam.cu) * rd.x + ld3(P.cam.cv) * rd.y;
-    T time = P.cam.time0 + rng_u01(g, T(0)) * (P.cam.time1 - P.cam.time0);
-    ray.o = ld3(P.cam.origin) + offset;
-    ray.d = ld3(P.cam.lower_left_corner) + u * ld3(P.cam.horizontal) + v * ld3(P.cam.vertical) - (ld3(P.cam.origin) + offset);
-    ray.tm = time;
-}
-
-// the table of rt_albedo.h on a finalized record.  List scenes (FEATS == 0: constant textures only) take the colour from the material record,
-// as the frames' const_or_tex does; the others walk the texture graph.
-template <uint32_t FEATS> DEV V3<double> albedo_of(const KParams<double>& P, bool any, const Rec<double>& rec) {
-    const V3<double> one = mk<double>(1.0, 1.0, 1.0);
-    if (!any) return one;
-    const DMaterial<double> mt = ld_mat(P.materials + rec.mat);
-    if (mt.kind == M_METAL) return ld3(mt.albedo);
-    if (mt.kind == M_LAMBERTIAN || mt.kind == M_PBR || mt.kind == M_ISOTROPIC) {
-        if constexpr (FEATS == 0u) return ld3(mt.albedo);
-        else return tex_eval<double, FEATS>(P, mt.tex, rec.u, rec.v, rec.p);
-    }
-    return one;                                                     // Dielectric, DiffuseLight
-}
-
 template <uint32_t FEATS, bool CAMERA>
 __global__ void __launch_bounds__(QUERY_THREADS, AlbedoWaves<FEATS>::v) albedo_kernel(const KParams<double> P, const AlbedoArgs A) {
     if ((FEATS & F_BVH) && P.n_cached != 0u) {
-        // the filter tree, once per workgroup: query_kernel's staging (the host stages the whole tree or nothing)
+        // the filter tree, once per workgroup: rt_query_dev.h's stage_filter_tree<QUERY_THREADS>(P), restated — with the call in its place a
+        // kernel time of this family left the parent's spread in the A/B (docs/history.md), so the prologue stays the parent's to the line
         typedef uint32_t u4 __attribute__((ext_vector_type(4)));
         const uint32_t nodes_bytes = P.n_cached * (uint32_t)sizeof(DFNode);
         const u4* src = (const u4*)P.bvh_f; u4* dst = (u4*)lds_raw;
@@ -106,8 +55,8 @@ __global__ void __launch_bounds__(QUERY_THREADS, AlbedoWaves<FEATS>::v) albedo_k
         double s0 = 0.0, s1 = 0.0, s2 = 0.0;
         for (uint32_t s = 0; s < n_samples; s++) {
             RayT<double> ray; Rng rng;
-            if (CAMERA) albedo_camera_ray(P, A.seed, k, A.first_sample + s, ray, rng);
-            else { albedo_load_ray(A.rays, k, ray); rng = rng_for_stream(A.seed, k); }
+            if (CAMERA) camera_ray(P, A.seed, k, A.first_sample + s, ray, rng);
+            else { load_ray(A.rays, k, ray); rng = rng_for_stream(A.seed, k); }
             double t_hit; HitId id; id.obj = 0u; id.prim = 0u;
             bool any;
             if constexpr (FEATS == 0u) any = world_hit_list<double>(P, ray, A.t_min, rng, t_hit, id);
@@ -118,7 +67,7 @@ __global__ void __launch_bounds__(QUERY_THREADS, AlbedoWaves<FEATS>::v) albedo_k
             if (CAMERA) { s0 += a.x; s1 += a.y; s2 += a.z; }
             else {
                 s0 = a.x; s1 = a.y; s2 = a.z;
-                if (mine && A.hits) {                             // the words query_kernel writes
+                if (mine && A.hits) {                             // the words query_kernel writes (a twin of its stores, as chain_kernel's are)
                     const bool medium = any && id.prim == PRIM_MEDIUM;
                     const bool named = any && !medium;
                     d2* o = (d2*)(A.hits + 16ull * k);
@@ -138,36 +87,17 @@ __global__ void __launch_bounds__(QUERY_THREADS, AlbedoWaves<FEATS>::v) albedo_k
     }
 }
 
-// the instantiation by scene class: rt_query.hip's query_dispatch, restated
-static const uint32_t AF_MESH = F_BVH | F_TRIS, AF_NO_PBR = F_ALL & ~F_PBR, AF_NESTED = F_ALL | F_NESTED;
-template <typename F> static auto albedo_dispatch(uint32_t scene_feats, bool camera, F&& f) {
-    auto by_mode = [&](auto feats) { return camera ? f(feats, std::true_type()) : f(feats, std::false_type()); };
-    if (scene_feats == 0u) return by_mode(std::integral_constant<uint32_t, 0u>());
-    if (scene_feats & F_NESTED) return by_mode(std::integral_constant<uint32_t, AF_NESTED>());
-    if ((scene_feats & ~AF_MESH) == 0u) return by_mode(std::integral_constant<uint32_t, AF_MESH>());
-    return by_mode(std::integral_constant<uint32_t, AF_NO_PBR>());
-}
-template <uint32_t FEATS, bool CAMERA> static hipError_t albedo_allow_lds(size_t shmem) {    // more than the default 64 KB of dynamic LDS needs to be asked for
-    if (shmem <= 65536u) return hipSuccess;
-    return hipFuncSetAttribute((const void*)albedo_kernel<FEATS, CAMERA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+// the instantiation: query_kernel's classes and forms
+template <typename G> static auto albedo_kernel_for(uint32_t scene_feats, bool camera, G&& g) {
+    return scene_class_dispatch(scene_feats, [&](auto feats) {
+        return flag_dispatch(camera, [&](auto cam) { return g(albedo_kernel<decltype(feats)::value, decltype(cam)::value>); });
+    });
 }
 int albedo_blocks_per_cu(uint32_t scene_feats, bool camera, size_t shmem) {
-    return albedo_dispatch(scene_feats, camera, [&](auto feats, auto cam) {
-        constexpr uint32_t FEATS = decltype(feats)::value; constexpr bool CAMERA = decltype(cam)::value;
-        int nb = 0;
-        if (albedo_allow_lds<FEATS, CAMERA>(shmem) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, albedo_kernel<FEATS, CAMERA>, (int)QUERY_THREADS, shmem) != hipSuccess) return 0;
-        return nb;
-    });
+    return albedo_kernel_for(scene_feats, camera, [&](auto kernel) { return kernel_blocks_per_cu(kernel, QUERY_THREADS, shmem); });
 }
 hipError_t launch_albedo(const KParams<double>& P, const AlbedoArgs& A, uint32_t scene_feats, bool camera, uint32_t n_blocks, size_t shmem, hipStream_t stream) {
-    return albedo_dispatch(scene_feats, camera, [&](auto feats, auto cam) {
-        constexpr uint32_t FEATS = decltype(feats)::value; constexpr bool CAMERA = decltype(cam)::value;
-        const hipError_t e = albedo_allow_lds<FEATS, CAMERA>(shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((albedo_kernel<FEATS, CAMERA>), dim3(n_blocks), dim3(QUERY_THREADS), shmem, stream, P, A);
-        return hipGetLastError();
-    });
+    return albedo_kernel_for(scene_feats, camera, [&](auto kernel) { return kernel_launch(kernel, QUERY_THREADS, n_blocks, shmem, stream, P, A); });
 }
 
 // ------------------------------------------------------------------ demodulate / remodulate (rt_albedo.h (2)): element-wise over the 3 n_px

@@ -3,8 +3,8 @@
 //
 // A translation unit of its own over rt_kernel.hip's device functions (RT_TU == 3, as rt_query.hip, rt_albedo.hip and rt_guide.hip): the
 // search and the record are world_hit / world_hit_list / finalize_hit — the code the frames run — and nothing is added to the units the
-// frames, the queries and the filters are built from: their objects stay byte for byte what they were.  load_ray, camera_ray, albedo_of and
-// the scene-class dispatch are restated from rt_query.hip and rt_albedo.hip for that reason.
+// frames and the filters are built from.  load_ray, camera_ray, albedo_of and the scene-class dispatch are the query units' own:
+// rt_query_dev.h.
 //
 // Shape: guide_kernel's — 256-thread workgroups, at most (CUs x resident workgroups) of them, the filter tree staged in LDS when the WHOLE
 // tree fits, batches of 256 lanes grid-stride, one ITEM per lane (a caller's ray, or a pixel that loops over its samples in ascending order),
@@ -20,13 +20,12 @@
 #include "rt_kernel.hip"
 #define RT_CHAIN_QUERIES
 #include "rt_chain.h"
+#include "rt_query_dev.h"
 
 namespace rt {
 
 static_assert(CHAIN_KIND_METAL == (uint32_t)M_METAL && CHAIN_KIND_DIELECTRIC == (uint32_t)M_DIELECTRIC, "rt_chain.h restates rt_ir.h's material kinds");
 static_assert(CHAIN_HIT_DOUBLES == QUERY_HIT_DOUBLES && CHAIN_RAY_DOUBLES == QUERY_RAY_DOUBLES, "rt_chain.h restates rt_query.h's record sizes");
-
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 // Resident waves per SIMD the register allocation is held to, from -Rpass-analysis=kernel-resource-usage (make asm) and the loop depth of
 // every scratch access (tools/scratch_map.py); the table is in DESIGN §23.  GuideWaves' classes and values: across a search the lane carries
@@ -41,60 +40,11 @@ template <uint32_t FEATS> struct ChainWaves {
     static constexpr uint32_t v = FEATS == 0u ? RT_CHAIN_LIST_WAVES : ((FEATS & ~(uint32_t)(F_BVH | F_TRIS)) == 0u ? RT_CHAIN_MESH_WAVES : ((FEATS & F_NESTED) ? 1u : 3u));
 };
 
-// seven doubles at a 16-byte aligned base + 56 k bytes (rt_query.hip load_ray): three 16-byte accesses and one of 8 bytes
-DEV void chain_load_ray(const double* rays, uint32_t k, RayT<double>& ray) {
-    const double* p = rays + 7ull * k;
-    const uint32_t odd = k & 1u;
-    const d2* q = (const d2*)(p + odd);
-    const d2 a = q[0], b = q[1], c = q[2];
-    const double s = odd ? p[0] : p[6];
-    ray.o = odd ? mk<double>(s, a.x, a.y) : mk<double>(a.x, a.y, b.x);
-    ray.d = odd ? mk<double>(b.x, b.y, c.x) : mk<double>(b.y, c.x, c.y);
-    ray.tm = odd ? c.y : s;
-}
-
-// Camera::get_ray for sample `sample` of output-order pixel gp: rt_query.hip camera_ray, expression for expression, the draws in its order
-DEV void chain_camera_ray(const KParams<double>& P, uint64_t seed, uint32_t gp, uint32_t sample, RayT<double>& ray, Rng& g) {
-    typedef double T;
-    const uint32_t row = gp / P.W;
-    const uint32_t g_i = gp - row * P.W, g_j = P.H - 1u - row;      // row 0 is j = H-1, main.rs:772
-    g = rng_for_path(seed, gp, sample);
-    T random_u = rng_u01(g, T(0));
-    T random_v = rng_u01(g, T(0));
-    T u = (T(g_i) + random_u) / T(P.W - 1u);
-    T v = (T(g_j) + random_v) / T(P.H - 1u);
-    T da, db;
-    for (;;) {
-        da = rng_range(g, T(-1.0), T(1.0));
-        db = rng_range(g, T(-1.0), T(1.0));
-        V3<T> pd = mk<T>(da, db, T(0));
-        if (dot(pd, pd) < T(1.0)) break;
-    }
-    V3<T> rd = P.cam.lens_radius * mk<T>(da, db, T(0));
-    V3<T> offset = ld3(P.cam.cu) * rd.x + ld3(P.cam.cv) * rd.y;
-    T time = P.cam.time0 + rng_u01(g, T(0)) * (P.cam.time1 - P.cam.time0);
-    ray.o = ld3(P.cam.origin) + offset;
-    ray.d = ld3(P.cam.lower_left_corner) + u * ld3(P.cam.horizontal) + v * ld3(P.cam.vertical) - (ld3(P.cam.origin) + offset);
-    ray.tm = time;
-}
-
-// the table of rt_albedo.h (1) on a finalized record: rt_albedo.hip albedo_of, restated
-template <uint32_t FEATS> DEV V3<double> chain_albedo_of(const KParams<double>& P, bool any, const Rec<double>& rec) {
-    const V3<double> one = mk<double>(1.0, 1.0, 1.0);
-    if (!any) return one;
-    const DMaterial<double> mt = ld_mat(P.materials + rec.mat);
-    if (mt.kind == M_METAL) return ld3(mt.albedo);
-    if (mt.kind == M_LAMBERTIAN || mt.kind == M_PBR || mt.kind == M_ISOTROPIC) {
-        if constexpr (FEATS == 0u) return ld3(mt.albedo);
-        else return tex_eval<double, FEATS>(P, mt.tex, rec.u, rec.v, rec.p);
-    }
-    return one;                                                     // Dielectric, DiffuseLight
-}
-
 template <uint32_t FEATS, bool CAMERA, bool ALBEDO>
 __global__ void __launch_bounds__(QUERY_THREADS, (ChainWaves<FEATS>::v)) chain_kernel(const KParams<double> P, const ChainArgs A) {
     if ((FEATS & F_BVH) && P.n_cached != 0u) {
-        // the filter tree, once per workgroup: query_kernel's staging (the host stages the whole tree or nothing)
+        // the filter tree, once per workgroup: rt_query_dev.h's stage_filter_tree<QUERY_THREADS>(P), restated — with the call in its place a
+        // kernel time of this family left the parent's spread in the A/B (docs/history.md), so the prologue stays the parent's to the line
         typedef uint32_t u4 __attribute__((ext_vector_type(4)));
         const uint32_t nodes_bytes = P.n_cached * (uint32_t)sizeof(DFNode);
         const u4* src = (const u4*)P.bvh_f; u4* dst = (u4*)lds_raw;
@@ -119,7 +69,8 @@ __global__ void __launch_bounds__(QUERY_THREADS, (ChainWaves<FEATS>::v)) chain_k
         const uint64_t i64 = base + threadIdx.x;
         const bool mine = i64 < n;
         const uint32_t k = mine ? (uint32_t)i64 : n - 1u;         // a partial last wave repeats the last item: every lane takes part in the votes
-        // guide_kernel's accumulators (camera form)
+        // guide_kernel's accumulators (camera form).  (They and the eight stores below are rt_guide.hip's, written out in both files: as one
+        // struct they move every instantiation's register allocation, docs/history.md)
         double st = 0.0, p0 = 0.0, p1 = 0.0, p2 = 0.0, n0 = 0.0, n1 = 0.0, n2 = 0.0;
         double a0 = 0.0, a1 = 0.0, a2 = 0.0;
         uint32_t h = 0u, hf = 0u, links_sum = 0u;
@@ -128,8 +79,8 @@ __global__ void __launch_bounds__(QUERY_THREADS, (ChainWaves<FEATS>::v)) chain_k
         for (uint32_t s = 0; s < n_samples; s++) {
             const uint32_t sample_index = CAMERA ? A.first_sample + s : 0u;
             RayT<double> ray; Rng rng;
-            if (CAMERA) chain_camera_ray(P, A.seed, k, sample_index, ray, rng);
-            else { chain_load_ray(A.rays, k, ray); rng = rng_for_stream(A.seed, k); }
+            if (CAMERA) camera_ray(P, A.seed, k, sample_index, ray, rng);
+            else { load_ray(A.rays, k, ray); rng = rng_for_stream(A.seed, k); }
             double wgt[3] = {1.0, 1.0, 1.0};
             double S = 0.0, L0 = 0.0;                             // (C6): the path length so far, and the first ray's length
             uint32_t links = 0u;
@@ -167,7 +118,7 @@ __global__ void __launch_bounds__(QUERY_THREADS, (ChainWaves<FEATS>::v)) chain_k
                         live = false;
                         V3<double> a = mk<double>(1.0, 1.0, 1.0);
                         if constexpr (ALBEDO) {
-                            const V3<double> al = chain_albedo_of<FEATS>(P, any, rec);
+                            const V3<double> al = albedo_of<FEATS>(P, any, rec);
                             a = mk<double>(wgt[0] * al.x, wgt[1] * al.y, wgt[2] * al.z);
                         }
                         const bool medium = any && id.prim == PRIM_MEDIUM;    // (its Isotropic was appended by the flattener: no handle)
@@ -186,7 +137,7 @@ __global__ void __launch_bounds__(QUERY_THREADS, (ChainWaves<FEATS>::v)) chain_k
                                 p0 += rec.p.x; p1 += rec.p.y; p2 += rec.p.z;
                                 n0 += rec.n.x; n1 += rec.n.y; n2 += rec.n.z;
                             }
-                        } else if (mine) {                        // the words query_kernel writes, but for [1] and [15]
+                        } else if (mine) {                        // the words query_kernel writes, but for [1] and [15] (a twin of its stores)
                             d2* o = (d2*)(A.hits + 16ull * k);
                             d2 w;
                             w.x = any ? 1.0 : 0.0; w.y = t_word; o[0] = w;
@@ -224,39 +175,19 @@ __global__ void __launch_bounds__(QUERY_THREADS, (ChainWaves<FEATS>::v)) chain_k
     }
 }
 
-// the instantiation by scene class: rt_query.hip's query_dispatch, restated, with the optional albedo output as a third argument
-static const uint32_t CF_MESH = F_BVH | F_TRIS, CF_NO_PBR = F_ALL & ~F_PBR, CF_NESTED = F_ALL | F_NESTED;
-template <typename F> static auto chain_dispatch(uint32_t scene_feats, bool camera, bool albedo, F&& f) {
-    auto by_mode = [&](auto feats) {
-        if (camera) return albedo ? f(feats, std::true_type(), std::true_type()) : f(feats, std::true_type(), std::false_type());
-        return albedo ? f(feats, std::false_type(), std::true_type()) : f(feats, std::false_type(), std::false_type());
-    };
-    if (scene_feats == 0u) return by_mode(std::integral_constant<uint32_t, 0u>());
-    if (scene_feats & F_NESTED) return by_mode(std::integral_constant<uint32_t, CF_NESTED>());
-    if ((scene_feats & ~CF_MESH) == 0u) return by_mode(std::integral_constant<uint32_t, CF_MESH>());
-    return by_mode(std::integral_constant<uint32_t, CF_NO_PBR>());
-}
-template <uint32_t FEATS, bool CAMERA, bool ALBEDO> static hipError_t chain_allow_lds(size_t shmem) {    // more than the default 64 KB of dynamic LDS needs to be asked for
-    if (shmem <= 65536u) return hipSuccess;
-    return hipFuncSetAttribute((const void*)chain_kernel<FEATS, CAMERA, ALBEDO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+// the instantiation: query_kernel's classes and forms, with the optional albedo output as a third argument
+template <typename G> static auto chain_kernel_for(uint32_t scene_feats, bool camera, bool albedo, G&& g) {
+    return scene_class_dispatch(scene_feats, [&](auto feats) {
+        return flag_dispatch(camera, [&](auto cam) {
+            return flag_dispatch(albedo, [&](auto alb) { return g(chain_kernel<decltype(feats)::value, decltype(cam)::value, decltype(alb)::value>); });
+        });
+    });
 }
 int chain_blocks_per_cu(uint32_t scene_feats, bool camera, bool albedo, size_t shmem) {
-    return chain_dispatch(scene_feats, camera, albedo, [&](auto feats, auto cam, auto alb) {
-        constexpr uint32_t FEATS = decltype(feats)::value; constexpr bool CAMERA = decltype(cam)::value; constexpr bool ALBEDO = decltype(alb)::value;
-        int nb = 0;
-        if (chain_allow_lds<FEATS, CAMERA, ALBEDO>(shmem) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, chain_kernel<FEATS, CAMERA, ALBEDO>, (int)QUERY_THREADS, shmem) != hipSuccess) return 0;
-        return nb;
-    });
+    return chain_kernel_for(scene_feats, camera, albedo, [&](auto kernel) { return kernel_blocks_per_cu(kernel, QUERY_THREADS, shmem); });
 }
 hipError_t launch_chain(const KParams<double>& P, const ChainArgs& A, uint32_t scene_feats, bool camera, uint32_t n_blocks, size_t shmem, hipStream_t stream) {
-    return chain_dispatch(scene_feats, camera, A.albedo != nullptr, [&](auto feats, auto cam, auto alb) {
-        constexpr uint32_t FEATS = decltype(feats)::value; constexpr bool CAMERA = decltype(cam)::value; constexpr bool ALBEDO = decltype(alb)::value;
-        const hipError_t e = chain_allow_lds<FEATS, CAMERA, ALBEDO>(shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((chain_kernel<FEATS, CAMERA, ALBEDO>), dim3(n_blocks), dim3(QUERY_THREADS), shmem, stream, P, A);
-        return hipGetLastError();
-    });
+    return chain_kernel_for(scene_feats, camera, A.albedo != nullptr, [&](auto kernel) { return kernel_launch(kernel, QUERY_THREADS, n_blocks, shmem, stream, P, A); });
 }
 
 } // namespace rt

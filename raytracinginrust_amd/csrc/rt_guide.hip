@@ -3,9 +3,7 @@
 //
 // A translation unit of its own over rt_kernel.hip's device functions (RT_TU == 3, as rt_query.hip, rt_radiance.hip and rt_albedo.hip): the
 // search and the record are world_hit / world_hit_list / finalize_hit — the code the frames run — and nothing is added to the units the
-// frames, the queries and the filters are built from: their objects stay byte for byte what they were.  camera_ray, albedo_of and the
-// scene-class dispatch are restated from rt_query.hip and rt_albedo.hip for that reason (a shared header would have to leave those objects
-// unchanged).
+// frames and the filters are built from.  camera_ray, albedo_of and the scene-class dispatch are the query units' own: rt_query_dev.h.
 //
 // Shape: the camera form of albedo_kernel — 256-thread workgroups, at most (CUs x resident workgroups) of them, the filter tree staged in
 // LDS when the WHOLE tree fits, batches of 256 lanes grid-stride, whole waves in every voting search (lanes past n repeat the last pixel
@@ -18,10 +16,9 @@
 #include "rt_kernel.hip"
 #define RT_GUIDE_QUERIES
 #include "rt_guide.h"
+#include "rt_query_dev.h"
 
 namespace rt {
-
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 // Resident waves per SIMD the register allocation is held to, from -Rpass-analysis=kernel-resource-usage (make asm), the loop depth of
 // every scratch access (tools/scratch_map.py) and an A/B on the device; the table is in DESIGN §20.  AlbedoWaves' camera column for the two
@@ -39,48 +36,11 @@ template <uint32_t FEATS, bool ALBEDO> struct GuideWaves {
     static constexpr uint32_t v = FEATS == 0u ? RT_GUIDE_LIST_WAVES : ((FEATS & ~(uint32_t)(F_BVH | F_TRIS)) == 0u ? RT_GUIDE_MESH_WAVES : ((FEATS & F_NESTED) ? 1u : 3u));
 };
 
-// Camera::get_ray for sample `sample` of output-order pixel gp: rt_query.hip camera_ray, expression for expression, the draws in its order
-DEV void guide_camera_ray(const KParams<double>& P, uint64_t seed, uint32_t gp, uint32_t sample, RayT<double>& ray, Rng& g) {
-    typedef double T;
-    const uint32_t row = gp / P.W;
-    const uint32_t g_i = gp - row * P.W, g_j = P.H - 1u - row;      // row 0 is j = H-1, main.rs:772
-    g = rng_for_path(seed, gp, sample);
-    T random_u = rng_u01(g, T(0));
-    T random_v = rng_u01(g, T(0));
-    T u = (T(g_i) + random_u) / T(P.W - 1u);
-    T v = (T(g_j) + random_v) / T(P.H - 1u);
-    T da, db;
-    for (;;) {
-        da = rng_range(g, T(-1.0), T(1.0));
-        db = rng_range(g, T(-1.0), T(1.0));
-        V3<T> pd = mk<T>(da, db, T(0));
-        if (dot(pd, pd) < T(1.0)) break;
-    }
-    V3<T> rd = P.cam.lens_radius * mk<T>(da, db, T(0));
-    V3<T> offset = ld3(P.cam.cu) * rd.x + ld3(P.cam.cv) * rd.y;
-    T time = P.cam.time0 + rng_u01(g, T(0)) * (P.cam.time1 - P.cam.time0);
-    ray.o = ld3(P.cam.origin) + offset;
-    ray.d = ld3(P.cam.lower_left_corner) + u * ld3(P.cam.horizontal) + v * ld3(P.cam.vertical) - (ld3(P.cam.origin) + offset);
-    ray.tm = time;
-}
-
-// the table of rt_albedo.h (1) on a finalized record: rt_albedo.hip albedo_of, restated
-template <uint32_t FEATS> DEV V3<double> guide_albedo_of(const KParams<double>& P, bool any, const Rec<double>& rec) {
-    const V3<double> one = mk<double>(1.0, 1.0, 1.0);
-    if (!any) return one;
-    const DMaterial<double> mt = ld_mat(P.materials + rec.mat);
-    if (mt.kind == M_METAL) return ld3(mt.albedo);
-    if (mt.kind == M_LAMBERTIAN || mt.kind == M_PBR || mt.kind == M_ISOTROPIC) {
-        if constexpr (FEATS == 0u) return ld3(mt.albedo);
-        else return tex_eval<double, FEATS>(P, mt.tex, rec.u, rec.v, rec.p);
-    }
-    return one;                                                     // Dielectric, DiffuseLight
-}
-
 template <uint32_t FEATS, bool ALBEDO>
 __global__ void __launch_bounds__(QUERY_THREADS, (GuideWaves<FEATS, ALBEDO>::v)) guide_kernel(const KParams<double> P, const GuideArgs A) {
     if ((FEATS & F_BVH) && P.n_cached != 0u) {
-        // the filter tree, once per workgroup: query_kernel's staging (the host stages the whole tree or nothing)
+        // the filter tree, once per workgroup: rt_query_dev.h's stage_filter_tree<QUERY_THREADS>(P), restated — with the call in its place
+        // this kernel's registers are numbered differently down to its stores, which the other five units' are not (docs/history.md)
         typedef uint32_t u4 __attribute__((ext_vector_type(4)));
         const uint32_t nodes_bytes = P.n_cached * (uint32_t)sizeof(DFNode);
         const u4* src = (const u4*)P.bvh_f; u4* dst = (u4*)lds_raw;
@@ -102,6 +62,8 @@ __global__ void __launch_bounds__(QUERY_THREADS, (GuideWaves<FEATS, ALBEDO>::v))
         const uint64_t i64 = base + threadIdx.x;
         const bool mine = i64 < n;
         const uint32_t k = mine ? (uint32_t)i64 : n - 1u;         // a partial last wave repeats the last pixel: every lane takes part in the votes
+        // (these accumulators and the eight stores below have a twin in rt_chain.hip's camera form, written out in both: as one struct they
+        // move every instantiation's register allocation, docs/history.md)
         double st = 0.0, p0 = 0.0, p1 = 0.0, p2 = 0.0, n0 = 0.0, n1 = 0.0, n2 = 0.0;
         double a0 = 0.0, a1 = 0.0, a2 = 0.0;
         uint32_t h = 0u, hf = 0u;
@@ -109,7 +71,7 @@ __global__ void __launch_bounds__(QUERY_THREADS, (GuideWaves<FEATS, ALBEDO>::v))
         bool m_same = true, o_same = true;
         for (uint32_t s = 0; s < n_samples; s++) {
             RayT<double> ray; Rng rng;
-            guide_camera_ray(P, A.seed, k, A.first_sample + s, ray, rng);
+            camera_ray(P, A.seed, k, A.first_sample + s, ray, rng);
             double t_hit; HitId id; id.obj = 0u; id.prim = 0u;
             bool any;
             if constexpr (FEATS == 0u) any = world_hit_list<double>(P, ray, A.t_min, rng, t_hit, id);
@@ -117,7 +79,7 @@ __global__ void __launch_bounds__(QUERY_THREADS, (GuideWaves<FEATS, ALBEDO>::v))
             Rec<double> rec; rec.p = mk<double>(0.0, 0.0, 0.0); rec.n = rec.p; rec.t = 0.0; rec.u = rec.v = 0.0; rec.front = false; rec.mat = 0u;
             if (any) finalize_hit<double, FEATS>(P, ray, t_hit, id, ALBEDO, rec);
             if constexpr (ALBEDO) {
-                const V3<double> a = guide_albedo_of<FEATS>(P, any, rec);
+                const V3<double> a = albedo_of<FEATS>(P, any, rec);
                 a0 += a.x; a1 += a.y; a2 += a.z;
             }
             if (any) {
@@ -150,36 +112,17 @@ __global__ void __launch_bounds__(QUERY_THREADS, (GuideWaves<FEATS, ALBEDO>::v))
     }
 }
 
-// the instantiation by scene class: rt_query.hip's query_dispatch, restated, with the optional output in the camera flag's place
-static const uint32_t GF_MESH = F_BVH | F_TRIS, GF_NO_PBR = F_ALL & ~F_PBR, GF_NESTED = F_ALL | F_NESTED;
-template <typename F> static auto guide_dispatch(uint32_t scene_feats, bool albedo, F&& f) {
-    auto by_mode = [&](auto feats) { return albedo ? f(feats, std::true_type()) : f(feats, std::false_type()); };
-    if (scene_feats == 0u) return by_mode(std::integral_constant<uint32_t, 0u>());
-    if (scene_feats & F_NESTED) return by_mode(std::integral_constant<uint32_t, GF_NESTED>());
-    if ((scene_feats & ~GF_MESH) == 0u) return by_mode(std::integral_constant<uint32_t, GF_MESH>());
-    return by_mode(std::integral_constant<uint32_t, GF_NO_PBR>());
-}
-template <uint32_t FEATS, bool ALBEDO> static hipError_t guide_allow_lds(size_t shmem) {     // more than the default 64 KB of dynamic LDS needs to be asked for
-    if (shmem <= 65536u) return hipSuccess;
-    return hipFuncSetAttribute((const void*)guide_kernel<FEATS, ALBEDO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+// the instantiation: query_kernel's classes, with the optional output in the camera flag's place
+template <typename G> static auto guide_kernel_for(uint32_t scene_feats, bool albedo, G&& g) {
+    return scene_class_dispatch(scene_feats, [&](auto feats) {
+        return flag_dispatch(albedo, [&](auto alb) { return g(guide_kernel<decltype(feats)::value, decltype(alb)::value>); });
+    });
 }
 int guide_blocks_per_cu(uint32_t scene_feats, bool albedo, size_t shmem) {
-    return guide_dispatch(scene_feats, albedo, [&](auto feats, auto alb) {
-        constexpr uint32_t FEATS = decltype(feats)::value; constexpr bool ALBEDO = decltype(alb)::value;
-        int nb = 0;
-        if (guide_allow_lds<FEATS, ALBEDO>(shmem) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, guide_kernel<FEATS, ALBEDO>, (int)QUERY_THREADS, shmem) != hipSuccess) return 0;
-        return nb;
-    });
+    return guide_kernel_for(scene_feats, albedo, [&](auto kernel) { return kernel_blocks_per_cu(kernel, QUERY_THREADS, shmem); });
 }
 hipError_t launch_guide(const KParams<double>& P, const GuideArgs& A, uint32_t scene_feats, uint32_t n_blocks, size_t shmem, hipStream_t stream) {
-    return guide_dispatch(scene_feats, A.albedo != nullptr, [&](auto feats, auto alb) {
-        constexpr uint32_t FEATS = decltype(feats)::value; constexpr bool ALBEDO = decltype(alb)::value;
-        const hipError_t e = guide_allow_lds<FEATS, ALBEDO>(shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((guide_kernel<FEATS, ALBEDO>), dim3(n_blocks), dim3(QUERY_THREADS), shmem, stream, P, A);
-        return hipGetLastError();
-    });
+    return guide_kernel_for(scene_feats, A.albedo != nullptr, [&](auto kernel) { return kernel_launch(kernel, QUERY_THREADS, n_blocks, shmem, stream, P, A); });
 }
 
 } // namespace rt

@@ -5,6 +5,8 @@
 // A translation unit of its own over rt_kernel.hip's device functions (RT_TU == 3 leaves that file's kernels and launch code out): the
 // search and the record are world_hit / world_hit_list / finalize_hit — the code the frames run, one ray per lane — and nothing is
 // added to the two units the frames are built from (one more caller there changes other kernels' machine code, docs/history.md).
+// What the six query units have in common — ray load and store, camera_ray, the dispatch by scene class, occupancy and launch — is in
+// rt_query_dev.h, once.
 //
 // Shape: 256-thread workgroups, at most (CUs x resident workgroups) of them.  A workgroup stages the filter tree in LDS once when the
 // WHOLE tree fits its share of the CU's LDS (pathtrace_kernel's staging loop with its links rewritten to LDS addresses; *measured*,
@@ -15,10 +17,9 @@
 #define RT_TU 3
 #include "rt_kernel.hip"
 #include "rt_query.h"
+#include "rt_query_dev.h"
 
 namespace rt {
-
-typedef double d2 __attribute__((ext_vector_type(2)));
 
 // Resident waves per SIMD the register allocation is held to (workgroups of four waves, one per SIMD: this is also the resident
 // workgroups per CU the registers allow).  From -Rpass-analysis=kernel-resource-usage and the loop depth of every scratch access in the
@@ -30,60 +31,11 @@ template <uint32_t FEATS> struct QueryWaves {
     static constexpr uint32_t v = FEATS == 0u ? 5u : ((FEATS & ~(uint32_t)(F_BVH | F_TRIS)) == 0u ? 5u : ((FEATS & F_NESTED) ? 1u : 3u));
 };
 
-// seven doubles at a 16-byte aligned base + 56 k bytes: 16-byte aligned for even k, 8 bytes past that for odd k — three 16-byte accesses
-// and one of 8 bytes either way
-DEV void load_ray(const double* rays, uint32_t k, RayT<double>& ray) {
-    const double* p = rays + 7ull * k;
-    const uint32_t odd = k & 1u;
-    const d2* q = (const d2*)(p + odd);
-    const d2 a = q[0], b = q[1], c = q[2];
-    const double s = odd ? p[0] : p[6];
-    ray.o = odd ? mk<double>(s, a.x, a.y) : mk<double>(a.x, a.y, b.x);
-    ray.d = odd ? mk<double>(b.x, b.y, c.x) : mk<double>(b.y, c.x, c.y);
-    ray.tm = odd ? c.y : s;
-}
-DEV void store_ray(double* rays, uint32_t k, const RayT<double>& ray) {
-    double* p = rays + 7ull * k;
-    const uint32_t odd = k & 1u;
-    d2* q = (d2*)(p + odd);
-    d2 a, b, c;
-    if (odd) { a.x = ray.o.y; a.y = ray.o.z; b.x = ray.d.x; b.y = ray.d.y; c.x = ray.d.z; c.y = ray.tm; p[0] = ray.o.x; }
-    else { a.x = ray.o.x; a.y = ray.o.y; b.x = ray.o.z; b.y = ray.d.x; c.x = ray.d.y; c.y = ray.d.z; p[6] = ray.tm; }
-    q[0] = a; q[1] = b; q[2] = c;
-}
-
-// Camera::get_ray for sample `sample` of output-order pixel gp: refill_queue's arithmetic (main.rs:813-820, camera.rs:51-59), expression
-// for expression, the draws in its order — u, v, the lens disk's rejection loop, time.  `g` is left where the path's stream stands then.
-DEV void camera_ray(const KParams<double>& P, uint64_t seed, uint32_t gp, uint32_t sample, RayT<double>& ray, Rng& g) {
-    typedef double T;
-    const uint32_t row = gp / P.W;
-    const uint32_t g_i = gp - row * P.W, g_j = P.H - 1u - row;      // row 0 is j = H-1, main.rs:772
-    g = rng_for_path(seed, gp, sample);
-    T random_u = rng_u01(g, T(0));
-    T random_v = rng_u01(g, T(0));
-    T u = (T(g_i) + random_u) / T(P.W - 1u);
-    T v = (T(g_j) + random_v) / T(P.H - 1u);
-    T da, db;
-    for (;;) {
-        da = rng_range(g, T(-1.0), T(1.0));
-        db = rng_range(g, T(-1.0), T(1.0));
-        V3<T> pd = mk<T>(da, db, T(0));
-        if (dot(pd, pd) < T(1.0)) break;
-    }
-    V3<T> rd = P.cam.lens_radius * mk<T>(da, db, T(0));
-    V3<T> offset = ld3(P.cam.cu) * rd.x + ld3(P.cam.cv) * rd.y;
-    T time = P.cam.time0 + rng_u01(g, T(0)) * (P.cam.time1 - P.cam.time0);
-    ray.o = ld3(P.cam.origin) + offset;
-    ray.d = ld3(P.cam.lower_left_corner) + u * ld3(P.cam.horizontal) + v * ld3(P.cam.vertical) - (ld3(P.cam.origin) + offset);
-    ray.tm = time;
-}
-
 template <uint32_t FEATS, bool CAMERA>
 __global__ void __launch_bounds__(QUERY_THREADS, QueryWaves<FEATS>::v) query_kernel(const KParams<double> P, const QueryArgs Q) {
     if ((FEATS & F_BVH) && P.n_cached != 0u) {
-        // the filter tree, once per workgroup (pathtrace_kernel's staging of a tree that fits: the host stages the whole tree or nothing):
-        // 16-byte pieces, consecutive threads consecutive pieces; links become LDS addresses (a node state IS where its record lies:
-        // bvh_hit_filt), a leaf's info stays its id
+        // the filter tree, once per workgroup: rt_query_dev.h's stage_filter_tree<QUERY_THREADS>(P), restated — with the call in its place a
+        // kernel time of this family left the parent's spread in the A/B (docs/history.md), so the prologue stays the parent's to the line
         typedef uint32_t u4 __attribute__((ext_vector_type(4)));
         const uint32_t nodes_bytes = P.n_cached * (uint32_t)sizeof(DFNode);
         const u4* src = (const u4*)P.bvh_f; u4* dst = (u4*)lds_raw;
@@ -114,6 +66,8 @@ __global__ void __launch_bounds__(QUERY_THREADS, QueryWaves<FEATS>::v) query_ker
         Rec<double> rec; rec.p = mk<double>(0.0, 0.0, 0.0); rec.n = rec.p; rec.t = 0.0; rec.u = rec.v = 0.0; rec.front = false; rec.mat = 0u;
         if (any) finalize_hit<double, FEATS>(P, ray, t_hit, id, true, rec);
         if (mine) {
+            // (these sixteen words have twins in albedo_kernel and in chain_kernel's caller-ray form: as one function they move instructions
+            // outside the staging prologue, docs/history.md)
             const bool medium = any && id.prim == PRIM_MEDIUM;    // (its Isotropic was appended by the flattener: no handle)
             const bool named = any && !medium;
             d2* o = (d2*)(Q.hits + 16ull * k);
@@ -131,40 +85,20 @@ __global__ void __launch_bounds__(QUERY_THREADS, QueryWaves<FEATS>::v) query_ker
     }
 }
 
-// the instantiation by scene class: pathtrace_kernel's rule (rt_kernel.hip dispatch) without its scheduling variants — reference order,
-// no persistent loop, no walk-ahead — and without the principled material, which changes no hit
-static const uint32_t QF_MESH = F_BVH | F_TRIS, QF_NO_PBR = F_ALL & ~F_PBR, QF_NESTED = F_ALL | F_NESTED;
-template <typename F> static auto query_dispatch(uint32_t scene_feats, bool camera, F&& f) {
-    auto by_mode = [&](auto feats) { return camera ? f(feats, std::true_type()) : f(feats, std::false_type()); };
-    if (scene_feats == 0u) return by_mode(std::integral_constant<uint32_t, 0u>());
-    if (scene_feats & F_NESTED) return by_mode(std::integral_constant<uint32_t, QF_NESTED>());
-    if ((scene_feats & ~QF_MESH) == 0u) return by_mode(std::integral_constant<uint32_t, QF_MESH>());
-    return by_mode(std::integral_constant<uint32_t, QF_NO_PBR>());
+// the instantiation: the four scene classes of the searches (the principled material changes no hit), caller rays or camera rays
+template <typename G> static auto query_kernel_for(uint32_t scene_feats, bool camera, G&& g) {
+    return scene_class_dispatch(scene_feats, [&](auto feats) {
+        return flag_dispatch(camera, [&](auto cam) { return g(query_kernel<decltype(feats)::value, decltype(cam)::value>); });
+    });
 }
 uint32_t query_feats(uint32_t scene_feats) {
-    return query_dispatch(scene_feats, false, [](auto feats, auto) { return (uint32_t) decltype(feats)::value; });
-}
-template <uint32_t FEATS, bool CAMERA> static hipError_t query_allow_lds(size_t shmem) {     // more than the default 64 KB of dynamic LDS needs to be asked for
-    if (shmem <= 65536u) return hipSuccess;
-    return hipFuncSetAttribute((const void*)query_kernel<FEATS, CAMERA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    return scene_class_dispatch(scene_feats, [](auto feats) { return (uint32_t) decltype(feats)::value; });
 }
 int query_blocks_per_cu(uint32_t scene_feats, bool camera, size_t shmem) {
-    return query_dispatch(scene_feats, camera, [&](auto feats, auto cam) {
-        constexpr uint32_t FEATS = decltype(feats)::value; constexpr bool CAMERA = decltype(cam)::value;
-        int nb = 0;
-        if (query_allow_lds<FEATS, CAMERA>(shmem) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, query_kernel<FEATS, CAMERA>, (int)QUERY_THREADS, shmem) != hipSuccess) return 0;
-        return nb;
-    });
+    return query_kernel_for(scene_feats, camera, [&](auto kernel) { return kernel_blocks_per_cu(kernel, QUERY_THREADS, shmem); });
 }
 hipError_t launch_query(const KParams<double>& P, const QueryArgs& Q, uint32_t scene_feats, bool camera, uint32_t n_blocks, size_t shmem, hipStream_t stream) {
-    return query_dispatch(scene_feats, camera, [&](auto feats, auto cam) {
-        constexpr uint32_t FEATS = decltype(feats)::value; constexpr bool CAMERA = decltype(cam)::value;
-        const hipError_t e = query_allow_lds<FEATS, CAMERA>(shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((query_kernel<FEATS, CAMERA>), dim3(n_blocks), dim3(QUERY_THREADS), shmem, stream, P, Q);
-        return hipGetLastError();
-    });
+    return query_kernel_for(scene_feats, camera, [&](auto kernel) { return kernel_launch(kernel, QUERY_THREADS, n_blocks, shmem, stream, P, Q); });
 }
 
 } // namespace rt

@@ -5,7 +5,8 @@
 // A translation unit of its own over rt_kernel.hip's device functions, as rt_query.hip is (RT_TU == 3 leaves that file's kernels and launch
 // code out): the bounce loop is trace_lockstep's body — world_hit / world_hit_list, finalize_hit, shade_hit, add_radiance, flush_acc, the
 // code the frames run — and nothing is added to the units the frames are built from (one more caller there changes other kernels' machine
-// code, docs/history.md).
+// code, docs/history.md).  load_ray, the cursor's path_step, the staging loop and the scene-class dispatch are the query units' own:
+// rt_query_dev.h.
 //
 // Work: path p = k * spp + s is sample s of ray k, one path per lane, ray-major: the lanes of a wave start on the same ray or on neighbouring
 // ones.  A lane whose path has ended takes the wave's next path (__ballot + mbcnt prefix: the frames' regeneration without their LDS queue —
@@ -17,10 +18,9 @@
 #define RT_TU 3
 #include "rt_kernel.hip"
 #include "rt_radiance.h"
+#include "rt_query_dev.h"
 
 namespace rt {
-
-typedef double rd2 __attribute__((ext_vector_type(2)));
 
 // Resident waves per SIMD the register allocation is held to, from -Rpass-analysis=kernel-resource-usage and the loop depth of every scratch
 // access in the ISA (make asm, tools/scratch_map.py); the whole table is DESIGN §13's:
@@ -33,50 +33,10 @@ template <uint32_t FEATS> struct RadianceWaves {
     static constexpr uint32_t v = FEATS == 0u ? 5u : ((FEATS & F_NESTED) ? 1u : ((FEATS & ~(uint32_t)(F_BVH | F_TRIS)) == 0u ? 4u : 3u));
 };
 
-// seven doubles at a 16-byte aligned base + 56 k bytes: 16-byte aligned for even k, 8 bytes past that for odd k — three 16-byte accesses
-// and one of 8 bytes either way (rt_query.hip's load_ray; a copy: that unit's object stays what it was)
-DEV void radiance_load_ray(const double* rays, uint32_t k, RayT<double>& ray) {
-    const double* p = rays + 7ull * k;
-    const uint32_t odd = k & 1u;
-    const rd2* q = (const rd2*)(p + odd);
-    const rd2 a = q[0], b = q[1], c = q[2];
-    const double s = odd ? p[0] : p[6];
-    ray.o = odd ? mk<double>(s, a.x, a.y) : mk<double>(a.x, a.y, b.x);
-    ray.d = odd ? mk<double>(b.x, b.y, c.x) : mk<double>(b.y, c.x, c.y);
-    ray.tm = odd ? c.y : s;
-}
-
-// (k, s) + add paths, add <= 64, s < spp: no 64-bit division — with spp >= 64 the sample index wraps at most once
-DEV void path_step(uint32_t k, uint32_t s, uint32_t add, uint32_t spp, uint32_t& k_out, uint32_t& s_out) {
-    const uint64_t t = (uint64_t)s + add;
-    if (spp >= 64u) {
-        const bool wrap = t >= spp;
-        k_out = k + (wrap ? 1u : 0u); s_out = (uint32_t)(wrap ? t - spp : t);
-    } else {
-        const uint32_t q = (uint32_t)t / spp;
-        k_out = k + q; s_out = (uint32_t)t - q * spp;
-    }
-}
-
 template <uint32_t FEATS>
 __global__ void __launch_bounds__(RADIANCE_THREADS, RadianceWaves<FEATS>::v) radiance_kernel(const KParams<double> P, const RadianceArgs R) {
     typedef double T;
-    if ((FEATS & F_BVH) && P.n_cached != 0u) {
-        // the filter tree, once per workgroup (rt_query.hip's staging: the host stages the whole tree or nothing): links become LDS addresses
-        typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-        const uint32_t nodes_bytes = P.n_cached * (uint32_t)sizeof(DFNode);
-        const u4* src = (const u4*)P.bvh_f; u4* dst = (u4*)lds_raw;
-        const uint32_t base = lds_base();
-        for (uint32_t i = threadIdx.x; i < nodes_bytes / 16u; i += RADIANCE_THREADS) {
-            u4 w = src[i];
-            if (i & 1u) {                                         // second half of a DFNode: max.z-side bounds, skip, info
-                if (w.z != ST_DONE) w.z = base + w.z * (uint32_t)sizeof(DFNode);
-                if (!(w.w & FNODE_LEAF)) w.w = base + w.w * (uint32_t)sizeof(DFNode);
-            }
-            dst[i] = w;
-        }
-        __syncthreads();                                          // the only barrier
-    }
+    if ((FEATS & F_BVH) && P.n_cached != 0u) stage_filter_tree<RADIANCE_THREADS>(P);      // once per workgroup
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave_in_block = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // the wave's cursor (wave-uniform: scalar registers): next chunk, and paths [.., + left) of the current one starting at (cur_k, cur_s)
@@ -125,7 +85,7 @@ __global__ void __launch_bounds__(RADIANCE_THREADS, RadianceWaves<FEATS>::v) rad
 
         if (got_new) {
             if (acc_k != new_k) { acc_k = new_k; acc.set(0, 0.0); acc.set(1, 0.0); acc.set(2, 0.0); }
-            radiance_load_ray(R.rays, new_k, ray);
+            load_ray(R.rays, new_k, ray);
             rng = rng_for_path(P.seed, new_k, path_s);            // the frames' keying with the ray's index in the pixel's place; no camera draws
             beta = mk<T>(T(1.0), T(1.0), T(1.0));
             depth_left = P.max_depth;
@@ -162,37 +122,15 @@ __global__ void __launch_bounds__(RADIANCE_THREADS, RadianceWaves<FEATS>::v) rad
     if (R.nonfinite && n_nonfinite) atomicAdd(R.nonfinite, (unsigned long long)n_nonfinite);
 }
 
-// the instantiation by scene class: pathtrace_kernel's rule (rt_kernel.hip dispatch) without its scheduling variants — reference order,
-// no persistent loop, no walk-ahead, so no BVH stack — and, unlike the ray queries, with the principled material
-static const uint32_t RF_MESH = F_BVH | F_TRIS, RF_NO_PBR = F_ALL & ~F_PBR, RF_NESTED = F_ALL | F_NESTED;
-template <typename F> static auto radiance_dispatch(uint32_t scene_feats, F&& f) {
-    if (scene_feats == 0u) return f(std::integral_constant<uint32_t, 0u>());
-    if (scene_feats & F_NESTED) return f(std::integral_constant<uint32_t, RF_NESTED>());
-    if ((scene_feats & ~RF_MESH) == 0u) return f(std::integral_constant<uint32_t, RF_MESH>());
-    if ((scene_feats & ~RF_NO_PBR) == 0u) return f(std::integral_constant<uint32_t, RF_NO_PBR>());
-    return f(std::integral_constant<uint32_t, (uint32_t)F_ALL>());
-}
-template <uint32_t FEATS> static hipError_t radiance_allow_lds(size_t shmem) {     // more than the default 64 KB of dynamic LDS needs to be asked for
-    if (shmem <= 65536u) return hipSuccess;
-    return hipFuncSetAttribute((const void*)radiance_kernel<FEATS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+// the instantiation: the five scene classes of the path-tracing forms — unlike the ray queries, with the principled material
+template <typename G> static auto radiance_kernel_for(uint32_t scene_feats, G&& g) {
+    return scene_class_dispatch_pbr(scene_feats, [&](auto feats) { return g(radiance_kernel<decltype(feats)::value>); });
 }
 int radiance_blocks_per_cu(uint32_t scene_feats, size_t shmem) {
-    return radiance_dispatch(scene_feats, [&](auto feats) {
-        constexpr uint32_t FEATS = decltype(feats)::value;
-        int nb = 0;
-        if (radiance_allow_lds<FEATS>(shmem) != hipSuccess) return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, radiance_kernel<FEATS>, (int)RADIANCE_THREADS, shmem) != hipSuccess) return 0;
-        return nb;
-    });
+    return radiance_kernel_for(scene_feats, [&](auto kernel) { return kernel_blocks_per_cu(kernel, RADIANCE_THREADS, shmem); });
 }
 hipError_t launch_radiance(const KParams<double>& P, const RadianceArgs& R, uint32_t scene_feats, uint32_t n_blocks, size_t shmem, hipStream_t stream) {
-    return radiance_dispatch(scene_feats, [&](auto feats) {
-        constexpr uint32_t FEATS = decltype(feats)::value;
-        const hipError_t e = radiance_allow_lds<FEATS>(shmem);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((radiance_kernel<FEATS>), dim3(n_blocks), dim3(RADIANCE_THREADS), shmem, stream, P, R);
-        return hipGetLastError();
-    });
+    return radiance_kernel_for(scene_feats, [&](auto kernel) { return kernel_launch(kernel, RADIANCE_THREADS, n_blocks, shmem, stream, P, R); });
 }
 
 } // namespace rt

@@ -241,6 +241,22 @@ def test_small_shapes_of_the_list_kernel(pixels, n_b):
         _check_pixels("cornell", _render_pixels("cornell", pixels, None, n_b), pixels, None, n_b, 0)
 
 
+def test_the_staged_filter_tree_changes_no_word(monkeypatch):
+    """Every pixel of a 17 x 16 view of the random spheres, 2 samples at max_depth 4, added to a frame of zeros (two terms: one order)."""
+    import torch
+    from test_ray_query_gpu import STAGE_H, STAGE_W, assert_staging_changes_no_word
+    pb, cam, bg = _scene("random")
+    n = STAGE_W * STAGE_H
+    d_list = torch.arange(n, dtype=torch.int32, device="cuda")
+
+    def call():
+        d_out = torch.zeros(n * 3, dtype=torch.float64, device="cuda")
+        R.render_pixels_device(pb, cam, bg, STAGE_W, STAGE_H, 2, 4, d_list, n, d_out, None, seed=SEED)
+        torch.cuda.synchronize()
+        return (d_out.cpu().numpy(),)
+    assert_staging_changes_no_word(pb, call, monkeypatch)
+
+
 def test_an_empty_list_is_a_no_op_and_bad_entries_are_skipped():
     sent = _sentinel()
     assert differing_words(_render_pixels("cornell", np.zeros(0, np.uint32), None, 4), sent) == 0

@@ -259,6 +259,16 @@ def test_camera_form_equals_the_caller_ray_form_and_its_own_sums(name):
     assert (three != 3.0).any() and R.last_query_ms(pb) > 0.0
 
 
+@pytest.mark.parametrize("form", ["caller_rays", "camera"])
+def test_the_staged_filter_tree_changes_no_word(form, monkeypatch):
+    pb, _, cam = RQ._scene("random")
+    rays = RQ._rays("random")[:RQ.STAGE_W * RQ.STAGE_H]
+    if form == "camera":
+        RQ.assert_staging_changes_no_word(pb, lambda: (R.query_camera_albedo(pb, cam, RQ.STAGE_W, RQ.STAGE_H, 1, 3, CSEED),), monkeypatch)
+    else:
+        RQ.assert_staging_changes_no_word(pb, lambda: R.query_albedo(pb, rays, 1e-5, RQ.SEED, want_hits=True), monkeypatch)
+
+
 def test_camera_form_against_the_oracle():
     """(c) sample 0 of the random spheres: the oracle's camera ray and hit record (position, u, v), the material the device's record names,
     the oracle's texture value — under the rules of the caller-ray test."""

@@ -190,6 +190,22 @@ def test_caller_rays_in_the_second_batch():
     assert (want["links"] >= 1).any()
 
 
+@pytest.mark.parametrize("form", ["caller_rays", "camera", "camera_and_albedo"])
+def test_the_staged_filter_tree_changes_no_word(form, monkeypatch):
+    from test_ray_query_gpu import STAGE_H, STAGE_W, assert_staging_changes_no_word
+    pb, cam, _ = _scene("random")
+    rays = R.query_camera(pb, cam, STAGE_W, STAGE_H, 0, SEED, want_rays=True)[1].reshape(-1, 7)
+
+    def call():
+        if form == "caller_rays":
+            return R.query_chain(pb, rays, 4, 1.0, CC.T_MIN, SEED, want_albedo=True)
+        albedo = form == "camera_and_albedo"
+        out = R.query_camera_chain_guide(pb, cam, STAGE_W, STAGE_H, 4, 1.0, 1, 3, SEED, want_albedo=albedo, want_links=True)
+        return tuple(np.asarray(a, np.float64) for a in out)
+    assert_staging_changes_no_word(pb, call, monkeypatch)
+    assert form != "caller_rays" or (call()[0][:, 15] >= 1.0).any()              # some chain followed a link
+
+
 def test_one_ray_and_no_rays():
     pb, _, mats = _scene("chain")
     ray = CC.aimed_rays()[CC.NAMED["many_links"]:CC.NAMED["many_links"] + 1]

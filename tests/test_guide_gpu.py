@@ -115,6 +115,16 @@ def test_guide_in_the_second_batch():
             assert G.differing_words(out[1], R.query_camera_albedo(pb, cam, W, H, 0, n_samples, seed)) == 0
 
 
+@pytest.mark.parametrize("albedo", [False, True], ids=["guide", "guide_and_albedo"])
+def test_the_staged_filter_tree_changes_no_word(albedo, monkeypatch):
+    pb, _, cam = RQ._scene("random")
+
+    def call():
+        out = R.query_camera_guide(pb, cam, RQ.STAGE_W, RQ.STAGE_H, 1, 3, GSEED, want_albedo=albedo)
+        return out if albedo else (out,)
+    RQ.assert_staging_changes_no_word(pb, call, monkeypatch)
+
+
 # ---------------------------------------------------------------- 4. the _device form
 @pytest.mark.parametrize("name", ["cornell", "random"])
 def test_device_form(name):

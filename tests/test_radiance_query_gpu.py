@@ -218,6 +218,14 @@ def test_small_shapes(name, n, spp):
         assert (np.abs(sums - exact)[fin] <= bound[fin]).all()
 
 
+def test_the_staged_filter_tree_changes_no_word(monkeypatch):
+    """272 rays x 2 samples at max_depth 4 on the random spheres (a ray's two samples are two terms: their sum has one order)."""
+    from test_ray_query_gpu import STAGE_H, STAGE_W, assert_staging_changes_no_word
+    pb, _, _, bg = _scene("random")
+    rays = _rays("random")[:STAGE_W * STAGE_H]
+    assert_staging_changes_no_word(pb, lambda: R.query_radiance(pb, rays, 2, 4, bg, SEED, want_samples=True)[:2], monkeypatch)
+
+
 def test_known_answers_without_the_oracle():
     pb, _, _, bg = _scene("cornell")
     rays = _rays("cornell")[:200]

@@ -188,6 +188,39 @@ def test_small_batches(name, n):
     assert n_bad == 0, text
 
 
+STAGE_W, STAGE_H = 17, 16                      # 272 items: one whole workgroup and a second whose only wave is partial
+
+
+def assert_staging_changes_no_word(pb, call, monkeypatch):
+    """Every query kernel copies the filter tree into LDS once per workgroup when the whole tree fits (the random spheres' does) and walks
+    it from global memory otherwise.  `call()` -> the output arrays of one query of STAGE_W * STAGE_H items on scene `pb`: as it is, with
+    nothing staged (RT_NODE_CACHE_MAX=0) and with the limit one node short of the tree, which is a second way to nothing — the launch
+    report does not say what was staged, so the staged call is held to both.  Equal word for word.  (Shared by the six families' files.)"""
+    nodes = R.flatten(pb)["bvh_nodes"]
+    # the tree fits the workgroup's share of LDS, so the first call does stage: 32 bytes a filter node; the random spheres' class is held to 3
+    # waves per SIMD in every family (the *Waves tables), so at most 3 workgroups share a CU's 160 KB, and the host rounds down to 1 KB
+    assert nodes > 8 and nodes * 32 <= (160 * 1024 // 3) & ~1023, nodes
+    monkeypatch.delenv("RT_NODE_CACHE_MAX", raising=False)
+    staged = [np.array(a, np.float64) for a in call()]
+    assert any((a != 0.0).any() for a in staged)
+    for limit in ("0", str(nodes - 1)):
+        monkeypatch.setenv("RT_NODE_CACHE_MAX", limit)
+        for a, b in zip(staged, call()):
+            words, other = np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b, np.float64).view(np.uint64)
+            assert int((words != other).sum()) == 0, f"RT_NODE_CACHE_MAX={limit}"
+    monkeypatch.delenv("RT_NODE_CACHE_MAX")
+
+
+@pytest.mark.parametrize("form", ["caller_rays", "camera"])
+def test_the_staged_filter_tree_changes_no_word(form, monkeypatch):
+    pb, _, cam = _scene("random")
+    rays = _rays("random")[:STAGE_W * STAGE_H]
+    if form == "camera":
+        assert_staging_changes_no_word(pb, lambda: R.query_camera(pb, cam, STAGE_W, STAGE_H, 1, SEED, want_rays=True), monkeypatch)
+    else:
+        assert_staging_changes_no_word(pb, lambda: (R.query_hits(pb, rays, 1e-5, SEED),), monkeypatch)
+
+
 def _material_scene(be):
     """Three spheres, four walls and a sphere of smoke, every one with a material of its own -> (scene, [(kind, geometry, material id)])."""
     b = SceneBuilder(be)
