@@ -49,7 +49,60 @@
 #include <atomic>
 #include <string>
 #include <chrono>
+#include <mutex>
+#include <unordered_map>
+#include <unordered_set>
 #include "orc_rng.h"
+
+// ---------------------------------------------------------------- the libm table (tests/libm_replay.py)
+// Every libm call of the restatement that has a counterpart on the device goes through one hook (orc::lm and its two-result forms, below).
+// With no table set the hook IS the glibc call it replaces.  With one set, it looks (op, operand bits, second operand bits) up — all NaNs
+// one key — and computes with the table's value; what it does not find it notes once in a miss list, with the glibc value it went on
+// with.  A test fills the table with the DEVICE's values of exactly these operands (rt_debug_math) and so compares a kernel with a
+// restatement that differs from it in nothing but + - x / sqrt.  Op numbers are rt_debug_math's: each site names the device function
+// the kernel calls at the same place.  The table is read-only while a batch runs; the miss list takes a lock.
+// (Plain f64 here: this stands before `double` is renamed for the op-counting build.)
+namespace orc_lm {
+enum Op { SINCOS_0_2PI = 0, SIN, COS, TAN, ATAN, ATAN2, ACOS, LOG, LOG2, POW, N_OPS };
+struct Key {
+    uint32_t op; uint64_t a, b;
+    bool operator==(const Key& o) const { return op == o.op && a == o.a && b == o.b; }
+};
+struct KeyHash {
+    size_t operator()(const Key& k) const {
+        uint64_t h = (k.a + 0x9E3779B97F4A7C15ull * (k.op + 1u)) * 0xBF58476D1CE4E5B9ull;
+        h ^= h >> 31; h += k.b * 0x94D049BB133111EBull; h ^= h >> 29;
+        return (size_t)h;
+    }
+};
+struct Val { double v0, v1; };
+struct Miss { Key k; double g0, g1; };
+typedef std::unordered_map<Key, Val, KeyHash> Table;
+static Table* g_table = nullptr;
+static std::mutex g_miss_lock;
+static std::vector<Miss> g_misses;
+static std::unordered_set<Key, KeyHash> g_missed;
+static std::atomic<uint64_t> g_lookups[N_OPS], g_matches[N_OPS];
+static thread_local uint32_t g_touched = 0;        // bit op: the current record looked that op up (orc_libm_touch_out)
+static uint32_t* g_touch_out = nullptr;
+static inline uint64_t bits_of(double x) {
+    if (x != x) return 0x7FF8000000000000ull;
+    uint64_t u; std::memcpy(&u, &x, sizeof u); return u;
+}
+static inline double of_bits(uint64_t u) { double x; std::memcpy(&x, &u, sizeof x); return x; }
+// the table's entry for (op, a, b), or — noted once in the miss list — the glibc values the caller hands in
+[[maybe_unused]] static Val replay(Op op, double a, double b, double g0, double g1) {      // (unused in the builds that do not replay)
+    const Key k{(uint32_t)op, bits_of(a), bits_of(b)};
+    g_touched |= 1u << op;
+    g_lookups[op].fetch_add(1, std::memory_order_relaxed);
+    const Table::const_iterator it = g_table->find(k);
+    if (it != g_table->end()) { g_matches[op].fetch_add(1, std::memory_order_relaxed); return it->second; }
+    std::lock_guard<std::mutex> hold(g_miss_lock);
+    if (g_missed.insert(k).second) g_misses.push_back(Miss{k, g0, g1});
+    return Val{g0, g1};
+}
+} // namespace orc_lm
+typedef double orc_ops_raw;            // the C API's arrays are plain f64 in every build
 
 // -DORC_COUNT_OPS (liboracle_opcount.so only): `double` names a counting stand-in from here on, so that every f64 operation of the
 // restatement is tallied by kind (oracle/orc_opcount.h); the arithmetic and the samples are unchanged.
@@ -140,6 +193,42 @@ struct Sampler {
 static inline void orc_sincos(double x, double& s, double& c) { orc_ops::tick(orc_ops::SIN); orc_ops::tick(orc_ops::COS); orc_ops::raw_f64 rs, rc; ::sincos(x.v, &rs, &rc); s = double(rs); c = double(rc); }
 #else
 static inline void orc_sincos(double x, double& s, double& c) { ::sincos(x, &s, &c); }
+#endif
+
+// The libm hook (orc_lm, above).  lm: one result; lm_sincos: the pair where the kernel calls sincos_0_2pi; lm_sin_cos: the pair where the
+// kernel calls sin and cos of one operand — two table entries; glibc's side is ONE sincos call there as well (pdf.rs `phi.sin()` /
+// `phi.cos()` in one block, see Rotate::new; it is also what g++ -O3 made of the two calls these sites used to be).
+// Replays in the default build only: the timed build and the op-counting build call glibc and nothing else.
+static inline double lm_glibc(orc_lm::Op op, double a, double b) {
+    switch (op) {
+    case orc_lm::SIN: return std::sin(a);
+    case orc_lm::COS: return std::cos(a);
+    case orc_lm::TAN: return std::tan(a);
+    case orc_lm::ATAN: return std::atan(a);
+    case orc_lm::ATAN2: return std::atan2(a, b);
+    case orc_lm::ACOS: return std::acos(a);
+    case orc_lm::LOG: return std::log(a);
+    case orc_lm::LOG2: return std::log2(a);
+    default: return std::pow(a, b);
+    }
+}
+#if defined(ORC_NO_COUNTERS) || defined(ORC_COUNT_OPS)
+static inline double lm(orc_lm::Op op, double a, double b = 0.0) { return lm_glibc(op, a, b); }
+static inline void lm_sincos(double x, double& s, double& c) { orc_sincos(x, s, c); }
+static inline void lm_sin_cos(double x, double& s, double& c) { orc_sincos(x, s, c); }
+#else
+static inline double lm(orc_lm::Op op, double a, double b = 0.0) {
+    const double g = lm_glibc(op, a, b);
+    return orc_lm::g_table ? orc_lm::replay(op, a, b, g, 0.0).v0 : g;
+}
+static inline void lm_sincos(double x, double& s, double& c) {
+    orc_sincos(x, s, c);
+    if (orc_lm::g_table) { const orc_lm::Val v = orc_lm::replay(orc_lm::SINCOS_0_2PI, x, 0.0, s, c); s = v.v0; c = v.v1; }
+}
+static inline void lm_sin_cos(double x, double& s, double& c) {
+    orc_sincos(x, s, c);
+    if (orc_lm::g_table) { s = orc_lm::replay(orc_lm::SIN, x, 0.0, s, 0.0).v0; c = orc_lm::replay(orc_lm::COS, x, 0.0, c, 0.0).v0; }
+}
 #endif
 
 // Rust float semantics helpers
@@ -289,7 +378,7 @@ struct CheckTexture : Texture {
     const Texture* odd; const Texture* even;
     CheckTexture(const Texture* o, const Texture* e) : odd(o), even(e) {}
     Color mapping(double u, double v, const Vec3& p, Sampler& s) const override {          // texture.rs:45-54
-        double sines = std::sin(10.0 * p.x()) * std::sin(10.0 * p.y()) * std::sin(10.0 * p.z());
+        double sines = lm(orc_lm::SIN, 10.0 * p.x()) * lm(orc_lm::SIN, 10.0 * p.y()) * lm(orc_lm::SIN, 10.0 * p.z());      // rt_kernel.hip tex_eval: m_sin
         if (sines < 0.0) return odd->mapping(u, v, p, s);
         return even->mapping(u, v, p, s);
     }
@@ -365,7 +454,7 @@ struct NoiseTexture : Texture {
     NoiseTexture(double sc, Sampler& s) : noise(s), scale(sc) {}     // texture.rs:63-68
     Color mapping(double, double, const Vec3& p, Sampler& s) const override {   // texture.rs:71-79
         ORC_COUNT(s.c.perlin_evals += 7);
-        return Color(1.0, 1.0, 1.0) * 0.5 * (1.0 + std::sin(scale * p.z() + 10.0 * noise.turb(p, scale, 7)));
+        return Color(1.0, 1.0, 1.0) * 0.5 * (1.0 + lm(orc_lm::SIN, scale * p.z() + 10.0 * noise.turb(p, scale, 7)));   // tex_eval: m_sin
     }
 };
 struct ImageTexture : Texture {
@@ -458,7 +547,7 @@ static Vec3 random_cosine_direction(Sampler& s) {                      // pdf.rs
     double z = std::sqrt(1.0 - r2);
     double phi = 2.0 * PI * r1;
     double sin_phi, cos_phi;
-    orc_sincos(phi, sin_phi, cos_phi);       // pdf.rs:14-15 `phi.cos()` / `phi.sin()`: one operand, one block -> one sincos libcall (see Rotate::new)
+    lm_sincos(phi, sin_phi, cos_phi);        // pdf.rs:14-15 `phi.cos()` / `phi.sin()`: one operand, one block -> one sincos libcall (see Rotate::new); the kernel: sincos_0_2pi
     double x = cos_phi * std::sqrt(r2);
     double y = sin_phi * std::sqrt(r2);
     return Vec3(x, y, z);
@@ -473,7 +562,7 @@ static inline double GTR_1(double n_dot_h, double a) {                          
     if (a >= 1.0) return 1.0 / PI;
     double a2 = a * a;
     double t = 1.0 + (a2 - 1.0) * n_dot_h * n_dot_h;
-    return (a2 - 1.0) / (PI * std::log2(a2) * t);
+    return (a2 - 1.0) / (PI * lm(orc_lm::LOG2, a2) * t);                                                        // the kernel: m_log2
 }
 static inline double GTR_2_aniso(double n_dot_h, double h_dot_x, double h_dot_y, double ax, double ay) {        // mat.rs:32-34
     double p = h_dot_x / ax, q = h_dot_y / ay;
@@ -488,7 +577,7 @@ static inline double smithG_GGX_aniso(double n_dot_v, double v_dot_x, double v_d
     double p = v_dot_x * ax, q = v_dot_y * ay;
     return 1.0 / (n_dot_v + std::sqrt(p * p + q * q + n_dot_v * n_dot_v));
 }
-static inline Vec3 mon_to_lin(const Vec3& x) { return Vec3(std::pow(x.x(), 2.2), std::pow(x.y(), 2.2), std::pow(x.z(), 2.2)); }   // mat.rs:46-48
+static inline Vec3 mon_to_lin(const Vec3& x) { return Vec3(lm(orc_lm::POW, x.x(), 2.2), lm(orc_lm::POW, x.y(), 2.2), lm(orc_lm::POW, x.z(), 2.2)); }   // mat.rs:46-48
 static inline Vec3 spherical_direction(double sin_theta, double cos_theta, double sin_phi, double cos_phi) {    // pdf.rs:20-22
     return Vec3(sin_theta * cos_phi, sin_theta * sin_phi, cos_theta);
 }
@@ -497,10 +586,12 @@ static Vec3 GTR_1_direction(const Vec3& r_in, double clearcoat_gloss, Sampler& s
     double r2 = s.rng.range(0.0, 1.0);
     double a = mixf(0.1, 0.001, clearcoat_gloss);
     double a2 = a * a;
-    double cos_theta = std::sqrt(f_max(0.001, (1.0 - std::pow(a2, 1.0 - r1)) / (1.0 - a2)));
+    double cos_theta = std::sqrt(f_max(0.001, (1.0 - lm(orc_lm::POW, a2, 1.0 - r1)) / (1.0 - a2)));               // the kernel: m_pow
     double sin_theta = std::sqrt(f_max(0.001, 1.0 - cos_theta * cos_theta));
     double phi = PI * 2.0 * r2;
-    Vec3 wh = spherical_direction(sin_theta, cos_theta, std::sin(phi), std::cos(phi));
+    double sin_phi, cos_phi;
+    lm_sin_cos(phi, sin_phi, cos_phi);                                                                             // the kernel: m_sin, m_cos
+    Vec3 wh = spherical_direction(sin_theta, cos_theta, sin_phi, cos_phi);
     return r_in.reflect(wh);
 }
 static Vec3 GTR_2_aniso_direction(const Vec3& r_in, double roughness, double anisotropic, Sampler& s) {         // pdf.rs:38-60
@@ -509,17 +600,19 @@ static Vec3 GTR_2_aniso_direction(const Vec3& r_in, double roughness, double ani
     double aspect = std::sqrt(1.0 - anisotropic * 0.9);
     double ax = f_max(roughness * roughness / aspect, 0.001);
     double ay = f_max(roughness * roughness * aspect, 0.001);
-    double phi = std::atan(ay / ax * std::tan(2.0 * PI * r2 + 0.5 * PI));
+    double phi = lm(orc_lm::ATAN, ay / ax * lm(orc_lm::TAN, 2.0 * PI * r2 + 0.5 * PI));                            // the kernel: m_atan, m_tan
     if (r2 > 0.5) phi += PI;
-    double sin_phi = std::sin(phi);
-    double cos_phi = std::cos(phi);
+    double sin_phi, cos_phi;
+    lm_sin_cos(phi, sin_phi, cos_phi);                                                                             // the kernel: m_sin, m_cos
     double ax_2 = ax * ax;
     double ay_2 = ay * ay;
     double a2 = 1.0 / (cos_phi * cos_phi / ax_2 + sin_phi * sin_phi / ay_2);
     double tan_theta_2 = a2 * r1 / (1.0 - r1);
     double cos_theta = 1.0 / std::sqrt(1.0 + tan_theta_2);
     double sin_theta = std::sqrt(f_max(0.001, 1.0 - cos_theta * cos_theta));
-    Vec3 wh = spherical_direction(sin_theta, cos_theta, std::sin(phi), std::cos(phi));
+    double sin_phi_2, cos_phi_2;
+    lm_sin_cos(phi, sin_phi_2, cos_phi_2);                                                                         // pdf.rs:58 takes them again
+    Vec3 wh = spherical_direction(sin_theta, cos_theta, sin_phi_2, cos_phi_2);
     return r_in.reflect(wh);
 }
 
@@ -723,8 +816,8 @@ struct Isotropic : Material {                                          // mat.rs
 
 // ---------------------------------------------------------------- src/sphere.rs
 static void get_sphere_uv(const Vec3& p, double& u, double& v) {       // sphere.rs:11-25
-    double phi = std::atan2(-p.z(), p.x()) + PI;
-    double theta = std::acos(-p.y());
+    double phi = lm(orc_lm::ATAN2, -p.z(), p.x()) + PI;                // the kernel: m_atan2
+    double theta = lm(orc_lm::ACOS, -p.y());                           // m_acos
     u = phi / (2.0 * PI);
     v = theta / PI;
 }
@@ -734,7 +827,7 @@ static Vec3 random_to_sphere(double radius, double distance_squared, Sampler& s)
     double z = 1.0 + r2 * (std::sqrt(1.0 - radius * radius / distance_squared) - 1.0);
     double phi = 2.0 * PI * r1;
     double sin_phi, cos_phi;
-    orc_sincos(phi, sin_phi, cos_phi);       // sphere.rs:33-34: one sincos libcall, as above
+    lm_sincos(phi, sin_phi, cos_phi);        // sphere.rs:33-34: one sincos libcall, as above; the kernel: sincos_0_2pi
     double x = cos_phi * std::sqrt(1.0 - z * z);
     double y = sin_phi * std::sqrt(1.0 - z * z);
     return Vec3(x, y, z);
@@ -961,6 +1054,7 @@ struct Rotate : Hittable {
         // rotate.rs:35-36 `radians.sin()` / `radians.cos()`: one operand, one block — LLVM emits ONE sincos libcall for the pair on
         // x86-64 linux-gnu (and g++ -O3 does the same to the two calls below it used to be); glibc's sincos differs from sin() / cos() in the
         // last ulp for 0.13 % of arguments, so the choice is made explicit here and in the product's flattener (csrc/rt_flatten.cpp).
+        // Not routed through the libm table: the product's flattener runs this on the host too, with glibc.
         orc_sincos(radiants, sin_theta, cos_theta);
         AABB b;
         has_box = h->bounding_box(0.0, 1.0, b);
@@ -1024,7 +1118,7 @@ struct ConstantMedium : Hittable {
                 if (hit2.t > t_max) hit2.t = t_max;
                 if (hit1.t < hit2.t) {
                     double distance_inside_boundary = (hit2.t - hit1.t) * r.direction().length();
-                    double hit_distance = (-(1.0 / density)) * std::log(s.rng.u01());
+                    double hit_distance = (-(1.0 / density)) * lm(orc_lm::LOG, s.rng.u01());                     // the kernel: m_log
                     if (hit_distance < distance_inside_boundary) {
                         double t = hit1.t + hit_distance / r.direction().length();
                         rec.position = r.at(t);
@@ -1096,7 +1190,7 @@ struct Camera {
     Camera(const Point3& lookfrom, const Point3& lookat, const Vec3& vup, double vfov, double aspect_ratio,
            double aperture, double focus_dist, double t0, double t1) {                               // camera.rs:19-49
         double theta = PI / 180.0 * vfov;
-        double viewport_height = 2.0 * std::tan(theta / 2.0);
+        double viewport_height = 2.0 * std::tan(theta / 2.0);          // not routed through the libm table: the product computes the camera on the host too, with glibc
         double viewport_width = viewport_height * aspect_ratio;
         Vec3 cw = (lookfrom - lookat).normalized();
         cu = vup.cross(cw).normalized();
@@ -1590,7 +1684,9 @@ void orc_hit_records(void* s, uint32_t n, const double* rays, uint64_t seed, dou
         const double* ry = rays + 7 * (size_t)k; double* o = out + 16 * (size_t)k;
         Sampler smp; smp.rng = Rng::for_stream(seed, k);
         HitRecord rec;
+        orc_lm::g_touched = 0;
         const bool any = SC->world->hit(Ray(V(ry), V(ry + 3), ry[6]), 0.00001, F64_INF, smp, rec);
+        if (orc_lm::g_touch_out) orc_lm::g_touch_out[k] = orc_lm::g_touched;
         for (int i = 0; i < 16; i++) o[i] = 0.0;
         o[11] = o[12] = o[13] = o[14] = -1.0;
         if (!any) continue;
@@ -1638,6 +1734,50 @@ void orc_libm(uint32_t op, uint32_t n, const double* a, const double* b, double*
         }
     }
 }
+// ---- the libm table's entry points (orc_lm, at the top of this file).  Not to be called while a batch runs on another thread.
+// Set or extend the table: n entries of op (rt_debug_math's number, 0 = sincos_0_2pi ... 9 = pow) — operands a, b (b may be null: one
+// operand), values v0, v1 (v1 may be null: one result).  An entry that exists is overwritten.  Returns the table's size, -1: no such op.
+int64_t orc_libm_table_extend(uint32_t op, uint32_t n, const double* a, const double* b, const double* v0, const double* v1) {
+    if (op >= (uint32_t)orc_lm::N_OPS) return -1;
+    if (!orc_lm::g_table) orc_lm::g_table = new orc_lm::Table();
+    for (uint32_t i = 0; i < n; i++) {
+        const orc_lm::Key k{op, orc_lm::bits_of(((const orc_ops_raw*)a)[i]), b ? orc_lm::bits_of(((const orc_ops_raw*)b)[i]) : 0u};
+        (*orc_lm::g_table)[k] = orc_lm::Val{((const orc_ops_raw*)v0)[i], v1 ? ((const orc_ops_raw*)v1)[i] : 0.0};
+    }
+    return (int64_t)orc_lm::g_table->size();
+}
+// Back to glibc: no table, an empty miss list, zeroed counts.
+void orc_libm_table_clear() {
+    delete orc_lm::g_table; orc_lm::g_table = nullptr;
+    std::lock_guard<std::mutex> hold(orc_lm::g_miss_lock);
+    orc_lm::g_misses.clear(); orc_lm::g_missed.clear();
+    for (int k = 0; k < orc_lm::N_OPS; k++) { orc_lm::g_lookups[k] = 0; orc_lm::g_matches[k] = 0; }
+}
+// Fetch and empty the miss list: per miss its op, the two operands (0 where the op has one; every NaN as the default NaN) and the glibc
+// value(s) the run went on with, g[2 i], g[2 i + 1].  Returns the number of misses; where that exceeds cap nothing is copied or emptied.
+uint32_t orc_libm_misses_take(uint32_t cap, uint32_t* ops, double* a, double* b, double* g) {
+    std::lock_guard<std::mutex> hold(orc_lm::g_miss_lock);
+    const uint32_t n = (uint32_t)orc_lm::g_misses.size();
+    if (n > cap) return n;
+    for (uint32_t i = 0; i < n; i++) {
+        const orc_lm::Miss& m = orc_lm::g_misses[i];
+        ops[i] = m.k.op;
+        ((orc_ops_raw*)a)[i] = orc_lm::of_bits(m.k.a); ((orc_ops_raw*)b)[i] = orc_lm::of_bits(m.k.b);
+        ((orc_ops_raw*)g)[2 * (size_t)i] = m.g0; ((orc_ops_raw*)g)[2 * (size_t)i + 1] = m.g1;
+    }
+    orc_lm::g_misses.clear(); orc_lm::g_missed.clear();
+    return n;
+}
+// Lookups and matches per op since the last call (out[2 op], out[2 op + 1]; reset on read), and the table's size in out[2 N_OPS].
+int orc_libm_n_ops() { return orc_lm::N_OPS; }
+void orc_libm_stats(uint64_t* out) {
+    for (int k = 0; k < orc_lm::N_OPS; k++) { out[2 * k] = orc_lm::g_lookups[k].exchange(0); out[2 * k + 1] = orc_lm::g_matches[k].exchange(0); }
+    out[2 * orc_lm::N_OPS] = orc_lm::g_table ? (uint64_t)orc_lm::g_table->size() : 0u;
+}
+// While buf is not null, orc_shade_batch and orc_hit_records write buf[k] = the ops record k looked up in the table (bit op), so that a
+// test knows which records a table entry can reach; buf must hold the batch's n words.  Null: off.
+void orc_libm_touch_out(uint32_t* buf) { orc_lm::g_touch_out = buf; }
+
 // One level of ray_color after the hit (ray_color_level: the code ray_color runs) for n caller hit records, the counterpart of the product's
 // rt_debug_shade: records n x 16 (hit, t, position[3], normal[3], front_face, u, v, material handle, ...), rays n x 7, record k on the
 // stream Rng::for_path(seed, k, 0).  flags: 2 = the product's RT_STOP_ON_ZERO rule on the outgoing beta, 4 = Isotropic scatters.  out: n x 19
@@ -1658,6 +1798,7 @@ int orc_shade_batch(void* s, uint32_t n, const double* records, const double* ra
         rec.material = MAT((size_t)mat);
         const Ray ray(V(ry), V(ry + 3), ry[6]);
         Sampler smp; smp.rng = Rng::for_path(seed, k, 0);
+        orc_lm::g_touched = 0;
         double margin = F64_INF;
 #if !defined(ORC_NO_COUNTERS) && !defined(ORC_COUNT_OPS)
         g_margin = &margin;
@@ -1682,6 +1823,7 @@ int orc_shade_batch(void* s, uint32_t n, const double* records, const double* ra
         o[6] = after.tm; o[13] = done ? 1.0 : 0.0; o[14] = (double)left;
         for (int i = 0; i < 4; i++) o[15 + i] = (double)smp.rng.s[i];
         if (margin_out) margin_out[k] = margin;
+        if (orc_lm::g_touch_out) orc_lm::g_touch_out[k] = orc_lm::g_touched;
     }
     SC->isotropic_scatters = iso_before;
     return rc;

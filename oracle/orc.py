@@ -143,6 +143,17 @@ def _declare(lib) -> Backend:
     lib.orc_sincos_batch.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
     lib.orc_libm.restype = None
     lib.orc_libm.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.orc_libm_table_extend.restype = C.c_int64
+    lib.orc_libm_table_extend.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.orc_libm_table_clear.restype = None
+    lib.orc_libm_table_clear.argtypes = []
+    lib.orc_libm_misses_take.restype = C.c_uint32
+    lib.orc_libm_misses_take.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.orc_libm_n_ops.restype = C.c_int
+    lib.orc_libm_stats.restype = None
+    lib.orc_libm_stats.argtypes = [C.c_void_p]
+    lib.orc_libm_touch_out.restype = None
+    lib.orc_libm_touch_out.argtypes = [C.c_void_p]
     lib.orc_shade_batch.restype = C.c_int
     lib.orc_shade_batch.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                     C.c_void_p, C.c_void_p]
@@ -291,6 +302,72 @@ def libm(op, a, b=None):
     out = np.zeros(len(a), np.float64)
     load().lib.orc_libm(LIBM_OPS.index(op), len(a), a.ctypes.data, b.ctypes.data, out.ctypes.data)
     return out
+
+
+# ---- the libm table (oracle.cpp orc_lm): the oracle computes with the caller's values of its libm calls.  tests/libm_replay.py fills it.
+TABLE_OPS = ("sincos_0_2pi",) + LIBM_OPS[1:]                   # rt_debug_math's numbering (the product's KAT_OPS, first ten)
+TABLE_TWO_OPERANDS = ("atan2", "pow")
+
+
+def libm_table_extend(op, a, b, v0, v1=None):
+    """orc_libm_table_extend: set or extend the table with entries of one op (a name of TABLE_OPS) — operands a and, for atan2 / pow, b;
+    values v0 and, for sincos_0_2pi, v1 (sin, cos).  -> the table's size.  With a table set, every routed libm call of the default build
+    takes its value from it; what it does not find goes to the miss list and is computed by glibc."""
+    arrs = [None if x is None else np.ascontiguousarray(x, np.float64).reshape(-1) for x in (a, b, v0, v1)]
+    if len({len(x) for x in arrs if x is not None}) != 1:
+        raise ValueError("operands and values differ in length")
+    if (arrs[1] is None) != (op not in TABLE_TWO_OPERANDS) or (arrs[3] is None) != (op != "sincos_0_2pi"):
+        raise ValueError(f"{op}: wrong number of operands or values")
+    n = load().lib.orc_libm_table_extend(TABLE_OPS.index(op), len(arrs[0]), *[None if x is None else x.ctypes.data for x in arrs])
+    if n < 0:
+        raise ValueError(op)
+    return int(n)
+
+
+def libm_table_clear():
+    """orc_libm_table_clear: back to glibc everywhere; the miss list and the counts are emptied too."""
+    load().lib.orc_libm_table_clear()
+
+
+def libm_misses():
+    """orc_libm_misses_take: fetch and empty the miss list -> {op name: (a, b, g)}: the operands that were looked up and not found (b zeros
+    where the op has one operand; any NaN operand as the default NaN) and g (n, 2), the glibc value(s) the oracle went on with."""
+    lib = load().lib
+    n = int(lib.orc_libm_misses_take(0, None, None, None, None))
+    ops = np.zeros(n, np.uint32); a = np.zeros(n); b = np.zeros(n); g = np.zeros((n, 2))
+    if n:
+        got = int(lib.orc_libm_misses_take(n, ops.ctypes.data, a.ctypes.data, b.ctypes.data, g.ctypes.data))
+        assert got == n
+    return {name: (a[ops == k], b[ops == k], g[ops == k]) for k, name in enumerate(TABLE_OPS) if (ops == k).any()}
+
+
+def libm_stats():
+    """orc_libm_stats: ({op name: (lookups, matches)} since the last call, the table's size)."""
+    lib = load().lib
+    n = int(lib.orc_libm_n_ops())
+    assert n == len(TABLE_OPS)
+    out = np.zeros(2 * n + 1, np.uint64)
+    lib.orc_libm_stats(out.ctypes.data)
+    return {name: (int(out[2 * k]), int(out[2 * k + 1])) for k, name in enumerate(TABLE_OPS)}, int(out[2 * n])
+
+
+class libm_touched:
+    """with libm_touched(n) as t: shade_batch(...) or hit_records(...) of n records -> t.ops[k]: the set of ops (bit TABLE_OPS.index) that
+    record k looked up in the table (all zero with no table set)."""
+
+    def __init__(self, n):
+        self.ops = np.zeros(max(int(n), 1), np.uint32)
+
+    def __enter__(self):
+        load().lib.orc_libm_touch_out(self.ops.ctypes.data)
+        return self
+
+    def __exit__(self, *exc):
+        load().lib.orc_libm_touch_out(None)
+        return False
+
+    def touched(self, op):
+        return (self.ops >> np.uint32(TABLE_OPS.index(op))) & np.uint32(1) != 0
 
 
 def shade_batch(b, records, rays, beta=(1.0, 1.0, 1.0), seed=0, depth_left=50, flags=0):

@@ -363,6 +363,31 @@ def set_records(what, mats, hits_fn):
     return np.concatenate([a[0], b[0]]), np.concatenate([a[1], b[1]])
 
 
+def sphere_light_records(mats, n=2400, seed=7407):
+    """(records, rays, family per record) for full_scene(.., "sphere") and "nested": Lambertian and PBR records whose shading point lies
+    where Sphere::random and Sphere::pdf_value (sphere.rs:104-119) are hostile — "inside" the light (1 - r^2 / d^2 < 0: the sampled
+    direction is NaN), at its "centre" (d = 0), on its "surface" within 1e-12 radii (1 - r^2 / d^2 about 0, either sign), "far" away
+    at 1e6 ... 1e9 radii (from 1.35e8 radii on 1 - r^2 / d^2 rounds to 1) — and "near" ones, 1.01 ... 100 radii, between them.  Normals, incoming rays and the
+    rest of a record are synthetic_records'."""
+    r = np.random.default_rng(seed)
+    pbr = [h.id for h in mats["pbr"]]
+    # a third Lambertian, the rest every PBR set in turn: half of those draw from the BRDF's pdf and a third of that from each of its
+    # arms, n / 9 records, so that each arm's libm calls see some 260 operands
+    ids = [mats["lam"].id if i % 3 == 0 else pbr[(i - i // 3) % len(pbr)] for i in range(n)]
+    rec, rays = synthetic_records(ids, n, seed)
+    c, rad = np.array(LIGHT_SPHERE[0]), LIGHT_SPHERE[1]
+    fam = np.array(["inside"] * (n * 3 // 8) + ["centre"] * (n // 40) + ["surface"] * (n // 8) + ["far"] * (n // 8), dtype=object)
+    fam = np.concatenate([fam, np.array(["near"] * (n - len(fam)), dtype=object)])[r.permutation(n)]
+    u = r.normal(size=(n, 3)); u /= np.sqrt((u * u).sum(1))[:, None]
+    dist = np.select([fam == "inside", fam == "centre", fam == "surface", fam == "far"],
+                     [rad * r.uniform(0.001, 0.999, n), 0.0, rad * (1.0 + r.integers(-4, 5, n) * 2.0e-13), rad * 10.0 ** r.uniform(6.1, 9.0, n)],
+                     rad * 10.0 ** r.uniform(np.log10(1.01), 2.0, n))
+    p = c + dist[:, None] * u
+    rays[:, 0:3] = p - rays[:, 3:6]
+    rec[:, 2:5] = p
+    return rec, rays, fam
+
+
 def first_draw_is_light(obe, seed, n):
     """per record k whether the first draw of rng_path(seed, k, 0) — the mixture pdf's coin, pdf.rs:167-173 — picks the lights"""
     import ctypes as C
