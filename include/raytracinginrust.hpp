@@ -443,6 +443,33 @@ inline History temporal_blend(const std::vector<double>& rgb_sum, const std::vec
     return out;
 }
 
+// Temporal variance (rt_reproject_variance, csrc/rt_reproject_var.h): `reproject` with prev_var — W*H*3 variances of the previous frame's per-pixel
+// mean — carried along; the history's sums and counts are reproject's words, var is +inf where a pixel has history of unknown variance and +0.0
+// where it has none.  host = true: the plain-C++ twin, no device.
+struct HistoryVariance { History history; std::vector<double> var; };
+inline HistoryVariance reproject_variance(const std::vector<double>& prev_sum, const std::vector<uint32_t>* prev_counts, uint64_t prev_samples, const std::vector<double>& prev_var,
+                                          const std::vector<double>& prev_records, const Camera& prev_cam, const std::vector<double>& cur_records, uint32_t W, uint32_t H,
+                                          const ReprojectSettings& r = ReprojectSettings(), bool host = false) {
+    if (prev_sum.size() != (size_t)W * H * 3 || prev_var.size() != prev_sum.size() || prev_records.size() != (size_t)W * H * 16 || cur_records.size() != prev_records.size() ||
+        (prev_counts && prev_counts->size() != (size_t)W * H)) throw Error("reproject_variance: frame, variance, counts or records of another size");
+    HistoryVariance h; h.history.sum.resize(prev_sum.size()); h.history.counts.resize((size_t)W * H); h.var.resize(prev_sum.size());
+    if ((host ? rt_reproject_variance_host : rt_reproject_variance)(prev_sum.data(), prev_counts ? prev_counts->data() : nullptr, prev_samples, prev_var.data(), prev_records.data(),
+                                                                    &prev_cam.c, cur_records.data(), W, H, r.max_history, r.sigma, 0, h.history.sum.data(), h.history.counts.data(),
+                                                                    h.var.data()) != 0) throw Error(rt_last_error());
+    return h;
+}
+// The variance of the mean of temporal_blend's frame (rt_temporal_blend_variance_host; no device): var null = unknown everywhere (a frame with
+// fewer than two passes); the result is what denoise_frame(counts = the blend's counts, var = ...) takes.
+inline std::vector<double> temporal_blend_variance(const std::vector<double>* var, const std::vector<uint32_t>* counts, uint64_t samples, const std::vector<double>& hist_var,
+                                                   const std::vector<uint32_t>& hist_counts) {
+    if (hist_var.size() != hist_counts.size() * 3 || (var && var->size() != hist_var.size()) || (counts && counts->size() != hist_counts.size()))
+        throw Error("temporal_blend_variance: variance, counts or history of another size");
+    std::vector<double> out(hist_var.size());
+    if (rt_temporal_blend_variance_host(var ? var->data() : nullptr, counts ? counts->data() : nullptr, samples, hist_var.data(), hist_counts.data(), hist_counts.size(),
+                                        out.data()) != 0) throw Error(rt_last_error());
+    return out;
+}
+
 // A progressive frame (rt_progressive_*): the same loop in passes of samples that accumulate on the device, with the reference's
 // format_color (src/vec.rs:125-131) resolved there too — progress, preview, stop half-way, "another 1000 samples", save and resume.
 class Progressive {
@@ -489,6 +516,12 @@ public:
     // counts in between.  Works with 0 samples once there is history: the preview right after a camera move
     std::vector<uint8_t> rgb8_temporal(uint32_t iterations = 0, const DenoiseSettings& d = DenoiseSettings()) {
         std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_temporal_rgb8(p_, iterations, d.sigma, d.flags, out.data())); return out;
+    }
+    // ... on a frame with moments: the variance of the history's mean, which set_view carries along (+inf: unknown; all +0.0 without a history), and
+    // the temporal resolve through the variance stop on the blend's own variance, d.sigma = {sigma_v, sigma_n, sigma_p}, iterations 1 .. 8
+    std::vector<double> history_variance() const { std::vector<double> out(n_px_ * 3); chk(rt_progressive_read_history_variance(p_, out.data())); return out; }
+    std::vector<uint8_t> rgb8_temporal_variance(const DenoiseVarianceSettings& d = DenoiseVarianceSettings(), uint32_t albedo_samples = 0) {
+        std::vector<uint8_t> out(n_px_ * 3); chk(rt_progressive_resolve_temporal_variance_rgb8(p_, albedo_samples, d.iterations, d.sigma, d.flags, out.data())); return out;
     }
     // moments (rt_progressive_enable_moments): only while the frame holds 0 samples; from then on every pass is also merged into the second
     // moment of the pass sums, and once two passes are in error_map / error_stats estimate every pixel's standard error

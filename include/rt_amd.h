@@ -640,8 +640,9 @@ int rt_progressive_albedo_info(void* frame, uint32_t* albedo_samples_out, uint64
  * filtered mean, were the taps independent.  The other arguments, the errors (plus a null var) and the three forms are those of
  * rt_denoise_host / rt_denoise / rt_denoise_device; the workspace is rt_denoise_variance_workspace_bytes(W, H) = 128 bytes per pixel;
  * d_var and d_var_out are 8-byte aligned, d_var is only read.
- * Not done: the combination with albedo demodulation (per-channel V / albedo^2 — which is why var is per channel), temporal accumulation
- * (now rt_reproject below, for the colour sums only), variance gathered inside the path-tracing kernels, rt_render_multi. */
+ * Not done: the combination with albedo demodulation (per-channel V / albedo^2 — which is why var is per channel; now rt_denoise_frame
+ * below), temporal accumulation (now rt_reproject and, for the variance itself, rt_reproject_variance below), variance gathered inside the
+ * path-tracing kernels, rt_render_multi. */
 int rt_denoise_variance_host(const double* rgb_sum, uint64_t samples, const double* var, const double* hits, uint32_t W, uint32_t H,
                              uint32_t iterations, const double sigma[3], uint32_t flags, double* rgb_sum_out, double* var_out);
 int rt_denoise_variance(const double* rgb_sum, uint64_t samples, const double* var, const double* hits, uint32_t W, uint32_t H,
@@ -728,7 +729,8 @@ int rt_progressive_resolve_denoised_frame_rgb8(void* frame, uint32_t stop, uint3
  * and never allocates.  Errors (non-zero, rt_last_error, nothing written or launched): a null argument, W or H < 2, W*H > 2^31 - 1,
  * max_history > 2^31 - 1, normal_min outside [0, 1] or NaN, sigma_p <= 0 or NaN, flags != 0, prev_samples = 0 without counts.
  * Not done: history for pixels that miss (the background), a wider search when all four taps fail, objects that move between the views,
- * reflections and refractions (a mirror's image is reprojected as if painted on it), second moments or a variance frame, f32. */
+ * reflections and refractions (a mirror's image is reprojected as if painted on it), f32.  (A variance frame travels with
+ * rt_reproject_variance below.) */
 int rt_reproject_host(const double* prev_sum, const uint32_t* prev_counts, uint64_t prev_samples, const double* prev_hits, const rt_camera* prev_cam,
                       const double* cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2], uint32_t flags,
                       double* hist_sum_out, uint32_t* hist_counts_out);
@@ -747,6 +749,40 @@ int rt_temporal_blend_host(const double* rgb_sum, const uint32_t* counts, uint64
                            uint32_t W, uint32_t H, double* sum_out, uint32_t* counts_out);
 int rt_temporal_blend_device(const void* d_rgb_sum, const void* d_counts, uint64_t samples, const void* d_hist_sum, const void* d_hist_counts,
                              uint32_t W, uint32_t H, void* d_sum_out, void* d_counts_out, void* hip_stream);
+/* Temporal variance: rt_reproject with the variance of the previous frame's per-pixel mean carried along, so that the variance-guided filter
+ * (rt_denoise_variance, rt_denoise_frame(var = ...)) has its stop in the instant after a camera move.  A variance is KNOWN when it is finite
+ * and >= 0; NaN, +-inf and negative values are unknown, and unknown is written as +inf (what rt_adaptive_variance writes for a pixel with
+ * fewer than two passes, and what the filter reads as "no information").  prev_var: W*H*3 doubles — rt_progressive_variance,
+ * rt_adaptive_variance, or rt_temporal_blend_variance of an earlier view.  hist_sum_out and hist_counts_out are rt_reproject's words.  A tap
+ * rt_reproject accepts whose three variances are known contributes its PER-SAMPLE variance prev_var * count (a property of the surface
+ * point), and hist_var_out is the weighted mean of those divided by hist_counts: the history is hist_counts samples of that per-sample
+ * variance, so max_history, which caps the count, raises the variance the history claims.  The averaging over the bilinear footprint is not
+ * credited: neighbouring pixels share taps, and the filter's stop assumes independent pixels.  A pixel with history none of whose taps has a
+ * known variance gets +inf; a pixel without history +0.0, like its sums.  csrc/rt_reproject_var.h is the exact specification, which the
+ * fused HIP kernel (csrc/rt_reproject_var.hip: sums, counts and variances in one launch), the host twin and a NumPy restatement
+ * (tests/reproject_var_cases.py) satisfy bit for bit.
+ * The three forms, the alignment (variances 8-byte) and the errors are rt_reproject's, plus a null prev_var or hist_var_out; no output may
+ * overlap an input.  Not done: what rt_reproject does not do; adaptive frames in rt_progressive_set_view; history in checkpoints. */
+int rt_reproject_variance_host(const double* prev_sum, const uint32_t* prev_counts, uint64_t prev_samples, const double* prev_var, const double* prev_hits,
+                               const rt_camera* prev_cam, const double* cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2],
+                               uint32_t flags, double* hist_sum_out, uint32_t* hist_counts_out, double* hist_var_out);
+int rt_reproject_variance(const double* prev_sum, const uint32_t* prev_counts, uint64_t prev_samples, const double* prev_var, const double* prev_hits,
+                          const rt_camera* prev_cam, const double* cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2],
+                          uint32_t flags, double* hist_sum_out, uint32_t* hist_counts_out, double* hist_var_out);
+int rt_reproject_variance_device(const void* d_prev_sum, const void* d_prev_counts, uint64_t prev_samples, const void* d_prev_var, const void* d_prev_hits,
+                                 const rt_camera* prev_cam, const void* d_cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2],
+                                 uint32_t flags, void* d_hist_sum_out, void* d_hist_counts_out, void* d_hist_var_out, void* hip_stream);
+/* The variance of the mean of rt_temporal_blend's frame, per pixel and channel, from the frame's variance V (var: n_px*3 doubles, or NULL:
+ * unknown everywhere — a frame with fewer than two passes) with N = counts ? counts[p] : samples, and the history's Vh (hist_var) with
+ * h = hist_counts[p]:  h = 0: V when N > 0 and V is known, else +inf;  N = 0: Vh when known, else +inf;  both known:
+ * (N^2 V + h^2 Vh) / (N + h)^2;  only Vh known: Vh h / (N + h) — the new samples borrow the history's per-sample variance Vh h, which is what
+ * gives the filter a stop one pass after a move;  only V known: V N / (N + h);  neither: +inf.  var_out (n_px*3 doubles) may be var; it is
+ * what rt_denoise_frame*(counts = the blend's counts, var = ...) takes.  The device form takes device pointers (variances 8-byte aligned,
+ * counts 4-byte), only enqueues, never waits, never allocates.  Errors: a null hist_var, hist_counts or var_out; n_px > 2^31 - 1. */
+int rt_temporal_blend_variance_host(const double* var, const uint32_t* counts, uint64_t samples, const double* hist_var, const uint32_t* hist_counts,
+                                    uint64_t n_px, double* var_out);
+int rt_temporal_blend_variance_device(const void* d_var, const void* d_counts, uint64_t samples, const void* d_hist_var, const void* d_hist_counts,
+                                      uint64_t n_px, void* d_var_out, void* hip_stream);
 /* A progressive frame moved to another view WITH its history (rt_progressive_reset moves nothing and drops the history).  Waits for the
  * passes enqueued so far.  The previous frame is the blend of the frame's sums (rt_progressive_samples samples) with the history it holds, so
  * history chains from view to view; prev_hits and cur_hits are the frame's guide records — rt_query_camera(sample 0), or
@@ -756,19 +792,35 @@ int rt_temporal_blend_device(const void* d_rgb_sum, const void* d_counts, uint64
  * first-resolve state), and keeps the history.  Give the new view a NEW SEED: a sample's random stream is keyed by pixel and sample index,
  * so the same seed under a nearby camera gives the new samples nearly the noise the history already carries, and the two do not average
  * out.  max_history = 0 is a plain change of view.  Every call that existed before ignores the history.
+ * On a frame WITH MOMENTS (rt_progressive_enable_moments) the history carries its variance too: the previous frame's variance is
+ * rt_temporal_blend_variance of the frame's own (rt_progressive_variance when the moments are valid and the frame holds two passes, else
+ * NULL) with the history variance it holds, and rt_reproject_variance fills H_sum, H_cnt and H_var in one launch (H_var: 24 more bytes per
+ * pixel, allocated at first use; +inf where a history taken before the moments were enabled has none).  A frame without moments takes the
+ * path above unchanged.
  * Errors: those of rt_reproject; an adaptive frame (compose rt_reproject_device and rt_temporal_blend_device instead); a scene that has been
  * destroyed or changed.
  * rt_progressive_read_history: H_sum (W*H*3 doubles) and H_cnt (W*H uint32); all zero without a history.
- * rt_progressive_history_info: out[0] the views taken by rt_progressive_set_view over the frame's life, out[1] the pixels with H_cnt > 0. */
+ * rt_progressive_history_info: out[0] the views taken by rt_progressive_set_view over the frame's life, out[1] the pixels with H_cnt > 0.
+ * rt_progressive_read_history_variance: H_var (W*H*3 doubles); all +0.0 without a history; an error on a frame without moments. */
 int rt_progressive_set_view(void* frame, const rt_camera* cam, uint64_t seed, uint32_t max_history, const double sigma[2]);
 int rt_progressive_read_history(void* frame, double* hist_sum_out, uint32_t* hist_counts_out);
 int rt_progressive_history_info(void* frame, uint64_t out[2]);
+int rt_progressive_read_history_variance(void* frame, double* hist_var_out);
 /* The resolve of the frame blended with its history.  iterations = 0: byte for byte rt_adaptive_resolve_rgb8_host of rt_temporal_blend_host(
  * rt_progressive_read_sum, rt_progressive_samples, rt_progressive_read_history); sigma may be NULL.  iterations 1 .. 8: that resolve of
  * rt_denoise_frame_host(the blend's sums, counts = the blend's counts, no variance, no albedo, the frame's guide, iterations, sigma = {sigma_c,
  * sigma_n, sigma_p}, flags).  Allowed with 0 samples when a pixel has history — the preview in the instant after a camera move; an error
  * with neither samples nor history, and on an adaptive frame.  The sums, the history and what the other resolves own are untouched. */
 int rt_progressive_resolve_temporal_rgb8(void* frame, uint32_t iterations, const double sigma[3], uint32_t flags, uint8_t* rgb8_out);
+/* ... with the VARIANCE stop: byte for byte rt_adaptive_resolve_rgb8_host of rt_denoise_frame_host(the blend's sums, counts = the blend's
+ * counts, var = rt_temporal_blend_variance_host(the frame's variance or NULL as rt_progressive_set_view takes it, rt_progressive_samples,
+ * rt_progressive_read_history_variance, H_cnt), the frame's albedo sums as rt_progressive_resolve_denoised_frame_rgb8 builds them when
+ * albedo_samples > 0 (else none), the frame's guide, iterations 1 .. 8, sigma = {sigma_v, sigma_n, sigma_p}, flags).  Allowed with 0 samples
+ * when a pixel has history, and with one pass: the history's variance is the stop.  Errors: a frame without moments, an adaptive frame,
+ * neither samples nor history, iterations = 0 or > 8, those of rt_denoise_variance.  The sums, the moments, the history and what the other
+ * resolves own are untouched.  Not done: a filtered variance out. */
+int rt_progressive_resolve_temporal_variance_rgb8(void* frame, uint32_t albedo_samples, uint32_t iterations, const double sigma[3], uint32_t flags,
+                                                  uint8_t* rgb8_out);
 
 /* The whole frame on several GPUs of this node from ONE call: what a host that owns the node's GPUs itself (the reference's `main`,
  * src/main.rs:767-835) calls instead of rt_render.  device_mask: bit d selects HIP device d (0 = every visible device).  The scene

@@ -200,6 +200,14 @@ SIGNATURES = {
     "progressive_read_history": (_int, [_ptr, _ptr, _ptr]),
     "progressive_history_info": (_int, [_ptr, c_u64_p]),
     "progressive_resolve_temporal_rgb8": (_int, [_ptr, _u32, c_double_p, _u32, _ptr]),
+    # temporal variance: the variance of a frame's mean carried through a camera move, and its blend with a history's
+    "reproject_variance_host": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _cam_p, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, _ptr]),
+    "reproject_variance": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _cam_p, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, _ptr]),
+    "reproject_variance_device": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _cam_p, _ptr, _u32, _u32, _u32, c_double_p, _u32, _ptr, _ptr, _ptr, _ptr]),
+    "temporal_blend_variance_host": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _u64, _ptr]),
+    "temporal_blend_variance_device": (_int, [_ptr, _ptr, _u64, _ptr, _ptr, _u64, _ptr, _ptr]),
+    "progressive_read_history_variance": (_int, [_ptr, _ptr]),
+    "progressive_resolve_temporal_variance_rgb8": (_int, [_ptr, _u32, _u32, c_double_p, _u32, _ptr]),
     # radiance queries
     "query_radiance":(_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _ptr, _ptr, c_u64_p]),
     "query_radiance_device": (_int, [_ptr, _u32, _ptr, c_double_p, _u32, _u32, _u64, _u32, _u32, _int, _ptr, C.c_size_t, _ptr, _ptr, _ptr]),

@@ -15,6 +15,7 @@
 #include "rt_adaptive.h"
 #include "rt_denoise_frame.h"
 #include "rt_reproject.h"
+#include "rt_reproject_var.h"
 #include "rt_chain.h"
 
 using namespace rt;
@@ -75,6 +76,10 @@ struct Progressive {
     // views: the views taken over the frame's life
     DeviceBuffer d_hist_sum, d_hist_cnt;
     bool hist_valid = false; uint64_t hist_px = 0, views = 0;
+    // ... on a frame with moments (rt_reproject_var.h): the history's variance H_var (24 bytes per pixel), allocated at first use;
+    // hist_var_valid: it describes the history the two buffers above hold
+    DeviceBuffer d_hist_var;
+    bool hist_var_valid = false;
     size_t n_px() const { return (size_t)W * H; }
     size_t sum_bytes() const { return n_px() * 3 * sizeof(double); }
     const uint32_t* counts() const { return adaptive ? d_cnt.as<uint32_t>() : nullptr; }
@@ -303,6 +308,7 @@ int rt_progressive_reset(void* frame) {
     p->guide_valid = false;                             // ... and so is its denoising guide, rebuilt when it is next needed
     p->albedo_samples = 0;                              // ... and its albedo sums
     p->hist_valid = false; p->hist_px = 0;              // ... and the history of the views before it (rt_progressive_set_view keeps it)
+    p->hist_var_valid = false;                          // ... with its variance
     return progressive_restart(p, nullptr, 0);
 }
 
@@ -1148,6 +1154,54 @@ int rt_temporal_blend_device(const void* d_rgb_sum, const void* d_counts, uint64
                                              W * H, (double*)d_sum_out, (uint32_t*)d_counts_out, hip_stream));
     return 0;
 }
+// ---- temporal variance (csrc/rt_reproject_var.h: the specification; rt_reproject_var.hip: the kernels)
+int rt_reproject_variance_device(const void* d_prev_sum, const void* d_prev_counts, uint64_t prev_samples, const void* d_prev_var, const void* d_prev_hits,
+                                 const rt_camera* prev_cam, const void* d_cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2],
+                                 uint32_t flags, void* d_hist_sum_out, void* d_hist_counts_out, void* d_hist_var_out, void* hip_stream) {
+    if (!d_prev_sum || !d_prev_var || !d_prev_hits || !prev_cam || !d_cur_hits || !sigma || !d_hist_sum_out || !d_hist_counts_out || !d_hist_var_out)
+        return set_error("null argument");
+    if (refused(reproject_check(d_prev_counts != nullptr, prev_samples, W, H, max_history, sigma, flags))) return -1;
+    if (query_aligned(d_prev_hits, "d_prev_hits") || query_aligned(d_cur_hits, "d_cur_hits")) return -1;
+    if ((((uintptr_t)d_prev_sum | (uintptr_t)d_prev_var | (uintptr_t)d_hist_sum_out | (uintptr_t)d_hist_var_out) & 7u) != 0u ||
+        (((uintptr_t)d_prev_counts | (uintptr_t)d_hist_counts_out) & 3u) != 0u)
+        return set_error("d_prev_sum, d_prev_var, d_hist_sum_out and d_hist_var_out must be 8-byte aligned, d_prev_counts and d_hist_counts_out 4-byte aligned");
+    if (rt_device_count() <= 0) return set_error("no HIP device: librt_amd has no CPU rendering path");
+    double fields[21];
+    rt_camera_fields(prev_cam, fields);
+    HIP_OK((hipError_t)launch_reproject_variance(reproject_consts(fields, prev_samples, W, H, max_history, sigma), (const double*)d_prev_sum, (const uint32_t*)d_prev_counts,
+                                                 (const double*)d_prev_var, (const double*)d_prev_hits, (const double*)d_cur_hits, (double*)d_hist_sum_out,
+                                                 (uint32_t*)d_hist_counts_out, (double*)d_hist_var_out, hip_stream));
+    return 0;
+}
+int rt_reproject_variance(const double* prev_sum, const uint32_t* prev_counts, uint64_t prev_samples, const double* prev_var, const double* prev_hits,
+                          const rt_camera* prev_cam, const double* cur_hits, uint32_t W, uint32_t H, uint32_t max_history, const double sigma[2],
+                          uint32_t flags, double* hist_sum_out, uint32_t* hist_counts_out, double* hist_var_out) {
+    if (!prev_sum || !prev_var || !prev_hits || !prev_cam || !cur_hits || !sigma || !hist_sum_out || !hist_counts_out || !hist_var_out) return set_error("null argument");
+    if (refused(reproject_check(prev_counts != nullptr, prev_samples, W, H, max_history, sigma, flags))) return -1;
+    if (rt_device_count() <= 0) return set_error("no HIP device: librt_amd has no CPU rendering path");
+    const size_t n = (size_t)W * H, sum_bytes = n * 3 * sizeof(double), cnt_bytes = n * sizeof(uint32_t), hit_bytes = n * REPROJECT_HIT_DOUBLES * sizeof(double);
+    DeviceBuffer d_sum, d_cnt, d_var, d_prev, d_cur, d_hsum, d_hcnt, d_hvar;
+    if (upload(d_sum, prev_sum, sum_bytes) || upload(d_cnt, prev_counts, cnt_bytes) || upload(d_var, prev_var, sum_bytes) || upload(d_prev, prev_hits, hit_bytes) ||
+        upload(d_cur, cur_hits, hit_bytes)) return -1;
+    HIP_OK(d_hsum.alloc(sum_bytes)); HIP_OK(d_hcnt.alloc(cnt_bytes)); HIP_OK(d_hvar.alloc(sum_bytes));
+    if (rt_reproject_variance_device(d_sum.get(), d_cnt.get(), prev_samples, d_var.get(), d_prev.get(), prev_cam, d_cur.get(), W, H, max_history, sigma, flags, d_hsum.get(),
+                                     d_hcnt.get(), d_hvar.get(), nullptr)) return -1;
+    HIP_OK(hipMemcpy(hist_sum_out, d_hsum.get(), sum_bytes, hipMemcpyDeviceToHost));     // (waits for the kernel: the null stream)
+    HIP_OK(hipMemcpy(hist_counts_out, d_hcnt.get(), cnt_bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(hist_var_out, d_hvar.get(), sum_bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+int rt_temporal_blend_variance_device(const void* d_var, const void* d_counts, uint64_t samples, const void* d_hist_var, const void* d_hist_counts,
+                                      uint64_t n_px, void* d_var_out, void* hip_stream) {
+    if (!d_hist_var || !d_hist_counts || !d_var_out) return set_error("null argument");
+    if (refused(blend_variance_check(n_px))) return -1;
+    if ((((uintptr_t)d_var | (uintptr_t)d_hist_var | (uintptr_t)d_var_out) & 7u) != 0u || (((uintptr_t)d_counts | (uintptr_t)d_hist_counts) & 3u) != 0u)
+        return set_error("d_var, d_hist_var and d_var_out must be 8-byte aligned, d_counts and d_hist_counts 4-byte aligned");
+    if (rt_device_count() <= 0) return set_error("no HIP device: librt_amd has no CPU rendering path");
+    HIP_OK((hipError_t)launch_temporal_blend_variance((const double*)d_var, (const uint32_t*)d_counts, samples, (const double*)d_hist_var, (const uint32_t*)d_hist_counts,
+                                                      (uint32_t)n_px, (double*)d_var_out, hip_stream));
+    return 0;
+}
 // The history's buffers, allocated at first use; without a history they are made the empty one (all +0.0 and 0), so that every caller blends
 // with something.  On the null stream; nothing waits.
 static int progressive_history_ready(Progressive* p) {
@@ -1158,6 +1212,41 @@ static int progressive_history_ready(Progressive* p) {
         HIP_OK(hipMemsetAsync(p->d_hist_cnt.get(), 0, n * sizeof(uint32_t), nullptr));
         p->hist_valid = true; p->hist_px = 0;
     }
+    return 0;
+}
+// ... and, on a frame with moments, the history's variance beside them (rt_reproject_var.h).  A history taken before the moments were
+// enabled has none: unknown (+inf) where H_cnt > 0 and +0.0 elsewhere, as (V) writes a pixel none of whose taps knows its variance.
+static int progressive_history_variance_ready(Progressive* p) {
+    if (progressive_history_ready(p)) return -1;
+    HIP_OK(p->d_hist_var.ensure(p->sum_bytes()));
+    if (p->hist_var_valid) return 0;
+    if (p->hist_px == 0) HIP_OK(hipMemsetAsync(p->d_hist_var.get(), 0, p->sum_bytes(), nullptr));
+    else {
+        const size_t n = p->n_px();
+        std::vector<uint32_t> cnt(n);
+        HIP_OK(hipMemcpy(cnt.data(), p->d_hist_cnt.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));      // (waits: the null stream)
+        std::vector<double> var(n * 3u, 0.0);
+        for (size_t k = 0; k < n; k++) if (cnt[k] != 0u) var[3u * k] = var[3u * k + 1u] = var[3u * k + 2u] = variance_unknown();
+        HIP_OK(hipMemcpy(p->d_hist_var.get(), var.data(), p->sum_bytes(), hipMemcpyHostToDevice));
+    }
+    p->hist_var_valid = true;
+    return 0;
+}
+// the frame's own variance for (BV): rt_moments.h (4) into d_var when the moments describe the sums and hold two passes, else none (null)
+static int frame_variance_or_null(Progressive* p, const double*& d_var_out) {
+    d_var_out = nullptr;
+    if (!p->moments_valid || p->passes < 2u || p->done < 2u) return 0;
+    if (progressive_variance_enqueue(p, nullptr)) return -1;
+    d_var_out = p->d_var.as<double>();
+    return 0;
+}
+// the variance of the frame blended with its history (rt_reproject_var.h (BV)) into a buffer of one call, on the null stream
+static int frame_blend_variance_with_history(Progressive* p, DeviceBuffer& d_bvar) {
+    const double* d_var = nullptr;
+    if (frame_variance_or_null(p, d_var)) return -1;
+    HIP_OK(d_bvar.alloc(p->sum_bytes()));
+    HIP_OK((hipError_t)launch_temporal_blend_variance(d_var, nullptr, p->done, p->d_hist_var.as<double>(), p->d_hist_cnt.as<uint32_t>(), (uint32_t)p->n_px(),
+                                                      d_bvar.as<double>(), nullptr));
     return 0;
 }
 // the frame's sums blended with its history (rt_reproject.h (B)) into two buffers of one call, on the null stream
@@ -1176,19 +1265,25 @@ int rt_progressive_set_view(void* frame, const rt_camera* cam, uint64_t seed, ui
     if (refused(reproject_check(true, 0u, p->W, p->H, max_history, sigma, 0u))) return -1;
     DeviceGuard guard(p->device);
     HIP_OK(hipDeviceSynchronize());                 // passes enqueued on the caller's streams belong to the previous frame
-    if (progressive_history_ready(p)) return -1;
+    if (p->moments ? progressive_history_variance_ready(p) : progressive_history_ready(p)) return -1;
     const size_t n = p->n_px(), cnt_bytes = n * sizeof(uint32_t), hit_bytes = n * REPROJECT_HIT_DOUBLES * sizeof(double);
     if (max_history == 0u || (p->done == 0 && p->hist_px == 0)) {     // nothing is carried over: the empty history, as (R5) gives it
         HIP_OK(hipMemsetAsync(p->d_hist_sum.get(), 0, p->sum_bytes(), nullptr));
         HIP_OK(hipMemsetAsync(p->d_hist_cnt.get(), 0, cnt_bytes, nullptr));
+        if (p->moments) HIP_OK(hipMemsetAsync(p->d_hist_var.get(), 0, p->sum_bytes(), nullptr));
         p->hist_px = 0;
     } else {
-        DeviceBuffer d_bsum, d_bcnt, d_prev, d_cur;
+        // (the blends go to buffers of this call: the kernel reads the old history through them while it writes the new one)
+        DeviceBuffer d_bsum, d_bcnt, d_bvar, d_prev, d_cur;
         if (frame_blend_with_history(p, d_bsum, d_bcnt)) return -1;
+        if (p->moments && frame_blend_variance_with_history(p, d_bvar)) return -1;
         HIP_OK(d_prev.alloc(hit_bytes)); HIP_OK(d_cur.alloc(hit_bytes));
         if (progressive_view_records(p, &p->cam, p->seed, d_prev.get(), hit_bytes)) return -1;
         if (progressive_view_records(p, cam, seed, d_cur.get(), hit_bytes)) return -1;
-        if (rt_reproject_device(d_bsum.get(), d_bcnt.get(), 0u, d_prev.get(), &p->cam, d_cur.get(), p->W, p->H, max_history, sigma, 0u, p->d_hist_sum.get(), p->d_hist_cnt.get(), nullptr)) return -1;
+        // a frame with moments: sums, counts and variances in one launch (rt_reproject_var.h (V)); any other frame: rt_reproject as before
+        if (p->moments ? rt_reproject_variance_device(d_bsum.get(), d_bcnt.get(), 0u, d_bvar.get(), d_prev.get(), &p->cam, d_cur.get(), p->W, p->H, max_history, sigma, 0u,
+                                                      p->d_hist_sum.get(), p->d_hist_cnt.get(), p->d_hist_var.get(), nullptr)
+                       : rt_reproject_device(d_bsum.get(), d_bcnt.get(), 0u, d_prev.get(), &p->cam, d_cur.get(), p->W, p->H, max_history, sigma, 0u, p->d_hist_sum.get(), p->d_hist_cnt.get(), nullptr)) return -1;
         std::vector<uint32_t> cnt(n);
         HIP_OK(hipMemcpy(cnt.data(), p->d_hist_cnt.get(), cnt_bytes, hipMemcpyDeviceToHost));      // (waits for the kernels: the null stream)
         uint64_t px = 0;
@@ -1212,6 +1307,20 @@ int rt_progressive_read_history(void* frame, double* hist_sum_out, uint32_t* his
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipMemcpy(hist_sum_out, p->d_hist_sum.get(), p->sum_bytes(), hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(hist_counts_out, p->d_hist_cnt.get(), n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+int rt_progressive_read_history_variance(void* frame, double* hist_var_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!hist_var_out) return set_error("null argument");
+    if (moments_frame(p)) return -1;
+    if (!p->hist_valid) {
+        std::memset(hist_var_out, 0, p->sum_bytes());
+        return 0;
+    }
+    DeviceGuard guard(p->device);
+    HIP_OK(hipDeviceSynchronize());
+    if (progressive_history_variance_ready(p)) return -1;
+    HIP_OK(hipMemcpy(hist_var_out, p->d_hist_var.get(), p->sum_bytes(), hipMemcpyDeviceToHost));      // (waits: the null stream)
     return 0;
 }
 int rt_progressive_history_info(void* frame, uint64_t out[2]) {
@@ -1242,6 +1351,28 @@ int rt_progressive_resolve_temporal_rgb8(void* frame, uint32_t iterations, const
     HIP_OK(p->d_fr_planes.ensure(2u * denoise_frame_plane_bytes(p->n_px())));
     if (denoise_frame_enqueue(d_bsum.as<double>(), d_bcnt.as<uint32_t>(), 0u, nullptr, nullptr, 0u, nullptr, p->W, p->H, iterations, sigma, flags,
                               p->d_dn_sum.as<double>(), nullptr, p->d_dn_ws.get(), p->d_fr_planes.get(), nullptr)) return -1;
+    return frame_resolve_out(p, p->d_dn_sum.as<double>(), d_bcnt.as<uint32_t>(), 0u, rgb8_out);
+}
+
+// ... with the variance stop: the blend's variance (rt_reproject_var.h (BV)) beside the blend's sums and counts, albedo sums when asked for
+int rt_progressive_resolve_temporal_variance_rgb8(void* frame, uint32_t albedo_samples, uint32_t iterations, const double sigma[3], uint32_t flags,
+                                                  uint8_t* rgb8_out) {
+    Progressive* p = (Progressive*)frame;
+    if (!sigma || !rgb8_out) return set_error("null argument");
+    if (moments_frame(p)) return -1;
+    if (p->adaptive) return set_error("rt_progressive_resolve_temporal_variance_rgb8: not available on an adaptive frame (it has no history: rt_progressive_set_view refuses it)");
+    if (refused(denoise_variance_check(p->done ? p->done : 1u, p->W, p->H, iterations, sigma, flags))) return -1;
+    const bool history = p->hist_valid && p->hist_px > 0;
+    if (p->done == 0 && !history) return set_error("nothing to resolve: the frame holds 0 samples and no history (rt_progressive_add, rt_progressive_set_view)");
+    DeviceGuard guard(p->device);
+    if (progressive_denoise_prepare(p, iterations, sigma, flags, true)) return -1;
+    if (albedo_samples && frame_albedo_ready(p, albedo_samples)) return -1;
+    if (progressive_history_variance_ready(p)) return -1;
+    DeviceBuffer d_bsum, d_bcnt, d_bvar;            // (they go when this call returns: frame_resolve_out has waited for the kernels by then)
+    if (frame_blend_with_history(p, d_bsum, d_bcnt) || frame_blend_variance_with_history(p, d_bvar)) return -1;
+    HIP_OK(p->d_fr_planes.ensure(2u * denoise_frame_plane_bytes(p->n_px())));
+    if (denoise_frame_enqueue(d_bsum.as<double>(), d_bcnt.as<uint32_t>(), 0u, d_bvar.as<double>(), albedo_samples ? p->d_alb_sum.as<double>() : nullptr, albedo_samples,
+                              nullptr, p->W, p->H, iterations, sigma, flags, p->d_dn_sum.as<double>(), nullptr, p->d_dn_ws.get(), p->d_fr_planes.get(), nullptr)) return -1;
     return frame_resolve_out(p, p->d_dn_sum.as<double>(), d_bcnt.as<uint32_t>(), 0u, rgb8_out);
 }
 

@@ -41,8 +41,8 @@
 //     counts[p] : samples.  The result is a (sum, counts) frame in the adaptive frames' layout (rt_adaptive.h): rt_adaptive_resolve_rgb8_*
 //     and rt_denoise_frame*(counts = ...) take it unchanged.
 //
-// Not done: adaptive frames inside rt_progressive_set_view, second moments or a variance frame, history for pixels that miss, a wider
-// search when all four taps fail, moving objects, specular chains, f32.
+// Not done: adaptive frames inside rt_progressive_set_view, history for pixels that miss, a wider search when all four taps fail, moving
+// objects, specular chains, f32.  (A variance frame travels through rt_reproject_var.h, which restates reproject_pixel's tap loop.)
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -89,7 +89,7 @@ inline ReprojectConsts reproject_consts(const double* fields, uint64_t prev_samp
 }
 
 // (R1)-(R5) of output-order pixel p: the three sums into out3, the count returned.  The reads: the pixel's own record, and of each of up to
-// four previous records words [0], [2..7] and [12], three sums and a count.
+// four previous records words [0], [2..7] and [12], three sums and a count.  (Its twin: reproject_variance_pixel, rt_reproject_var.h.)
 RT_REPROJECT_FN uint32_t reproject_pixel(const ReprojectConsts& K, const double* prev_sum, const uint32_t* prev_counts, const double* prev_hits,
                                          const double* cur_hits, uint64_t p, double* out3) {
     out3[0] = 0.0; out3[1] = 0.0; out3[2] = 0.0;

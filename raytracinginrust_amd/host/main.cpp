@@ -38,6 +38,9 @@
 // vup, DEGREES apart, each with a new seed (--seed + view) and N samples; from the second view on the frame carries its history along
 // (rt_progressive_set_view, at most CAP samples' worth per pixel, default 64; 0: none) and FILE_000.ppm, FILE_001.ppm ... (default orbit) are the
 // temporal resolves (rt_progressive_resolve_temporal_rgb8), through K iterations of the frame filter with --denoise.  Nothing goes to stdout.
+// With --denoise K --denoise-variance SIGMA_V [--denoise-albedo N] the frame keeps moments, its history carries its variance from view to view
+// and every view resolves through the variance stop (rt_progressive_resolve_temporal_variance_rgb8); a view's N samples are then two passes,
+// (N + 1) / 2 and the rest, so that the frame has a variance to hand on.
 // --aov error FILE (with --progressive N, beside the frame): the frame's error map when it ends (rt_progressive_error_map).
 //
 // --aov KIND FILE (opt-in, one GPU, instead of the frame): a feature frame for a denoiser or a compositor — the closest hit of sample 0's
@@ -416,7 +419,8 @@ int main(int argc, char** argv) {
                         "                                     error still exceeds TAU (and their neighbours), none beyond M samples; ends when no pixel is left\n"
                         "  --orbit FRAMES,DEGREES             with --progressive N: FRAMES views on a circle around lookat, DEGREES apart, N samples and a new seed each;\n"
                         "    [--history CAP] [--out FILE]     the frame carries its history from view to view (at most CAP samples' worth, default 64, 0: none) and\n"
-                        "                                     FILE_000.ppm ... (default orbit) are the temporal resolves; with --denoise K through the frame filter\n"
+                        "                                     FILE_000.ppm ... (default orbit) are the temporal resolves; with --denoise K through the frame filter,\n"
+                        "                                     with --denoise-variance SIGMA_V [--denoise-albedo N] as well through its variance stop (the history carries the variance)\n"
                         "  --panorama FILE                    write the 2:1 equirectangular image (width x width/2) of everything around the scene's\n"
                         "                                     lookfrom instead of the image: --spp samples per ray, --depth, the scene's background\n", AOV_HELP);
             return 0;
@@ -434,8 +438,8 @@ int main(int argc, char** argv) {
     if (chain.max_links != 0u && !want_denoise && aov_kind != "links") { std::fprintf(stderr, "--denoise-chain goes with --denoise K (or --aov links)\n"); return 2; }
     if (aov_kind == "links" && chain.max_links == 0u) { std::fprintf(stderr, "--aov links goes with --denoise-chain LINKS\n"); return 2; }
     if (sigma_v != 0.0 && (!want_denoise || progressive == 0u)) { std::fprintf(stderr, "--denoise-variance goes with --progressive N and --denoise K\n"); return 2; }
-    if (orbit_frames != 0u && (progressive == 0u || adaptive || until_error >= 0.0 || !aov_kind.empty() || albedo_samples != 0u || sigma_v != 0.0)) {
-        std::fprintf(stderr, "--orbit goes with --progressive N, and of the other options only with --denoise K and --denoise-guide N\n"); return 2;
+    if (orbit_frames != 0u && (progressive == 0u || adaptive || until_error >= 0.0 || !aov_kind.empty() || (albedo_samples != 0u && sigma_v == 0.0))) {
+        std::fprintf(stderr, "--orbit goes with --progressive N, and of the other options only with --denoise K, --denoise-guide N and --denoise-variance SIGMA_V [--denoise-albedo N]\n"); return 2;
     }
     const double aspect_ratio = (double)image_width / (double)image_height;
     try {
@@ -552,10 +556,19 @@ int main(int argc, char** argv) {
                         for (int e = 0; e < 3; e++) view.c.lookfrom[e] = c0.lookat[e] + r[e] * ca + x[e] * sa + k[e] * kr * (1.0 - ca);
                         frame.set_view(view, seed + f, history);
                     }
-                    frame.add(progressive);
+                    // with the variance stop a view's N samples come as two passes (N + 1) / 2 and the rest: a frame's own variance needs two, and a
+                    // history knows a variance only if some view before it had one
+                    if (sigma_v != 0.0 && progressive >= 2u) { frame.add((progressive + 1u) / 2u); frame.add(progressive / 2u); }
+                    else frame.add(progressive);
                     char name[32]; std::snprintf(name, sizeof(name), "_%03u.ppm", f);
                     const uint64_t held = [&]() { uint64_t w[2] = {0, 0}; rt_progressive_history_info(frame.raw(), w); return w[1]; }();
-                    write_ppm_rgb8((orbit_out + name).c_str(), frame.rgb8_temporal(want_denoise ? dn.iterations : 0u, dn), image_width, image_height);
+                    if (sigma_v != 0.0) {               // the variance stop on the blend's own variance (the frame has moments: want_moments above)
+                        DenoiseVarianceSettings dv;
+                        dv.iterations = dn.iterations; dv.sigma[0] = sigma_v; dv.sigma[1] = dn.sigma[1]; dv.sigma[2] = dn.sigma[2];
+                        write_ppm_rgb8((orbit_out + name).c_str(), frame.rgb8_temporal_variance(dv, albedo_samples), image_width, image_height);
+                    } else {
+                        write_ppm_rgb8((orbit_out + name).c_str(), frame.rgb8_temporal(want_denoise ? dn.iterations : 0u, dn), image_width, image_height);
+                    }
                     std::fprintf(stderr, "\rView %u / %u: %u samples, history in %llu pixels", f + 1u, orbit_frames, progressive, (unsigned long long)held);
                 }
                 std::fprintf(stderr, "\nDone.\n");

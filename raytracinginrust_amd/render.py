@@ -679,12 +679,29 @@ class Progressive:
         _check(self._lib.rt_progressive_history_info(self._h, out))
         return {"views": int(out[0]), "pixels": int(out[1])}
 
-    def rgb8_temporal(self, iterations: int = 0, sigma=None, flags: int = 0) -> np.ndarray:
+    def history_variance(self) -> np.ndarray:
+        """rt_progressive_read_history_variance -> hist_var (H, W, 3) f64: the variance of the history's per-pixel mean, which `set_view`
+        carries along on a frame with moments (`reproject_variance`); +inf where it is unknown, all +0.0 without a history."""
+        out = np.zeros((self.H, self.W, 3), dtype=np.float64)
+        _check(self._lib.rt_progressive_read_history_variance(self._h, out.ctypes.data))
+        return out
+
+    def rgb8_temporal(self, iterations: int = 0, sigma=None, flags: int = 0, variance: bool = False, albedo_samples: int = 0) -> np.ndarray:
         """rt_progressive_resolve_temporal_rgb8: the resolve of the frame blended with its history -> (H, W, 3) uint8; every pixel is
         divided by its own count (`temporal_blend_host`, `adaptive_resolve_rgb8_host`).  iterations >= 1: `denoise_frame` with the blend's
         counts and the frame's guide in between (sigma: DENOISE_SIGMA).  Works with 0 samples once there is history: the preview right after a
-        camera move."""
+        camera move.
+        variance=True (rt_progressive_resolve_temporal_variance_rgb8; a frame with moments, iterations 1 .. 8): the filter's colour stop is
+        measured in standard deviations of the blend's own variance (`temporal_blend_variance_host` of the frame's variance, when it has two
+        passes, with `history_variance`); sigma = (sigma_v, sigma_n, sigma_p), default DENOISE_VARIANCE_SIGMA; albedo_samples >= 1
+        demodulates as `rgb8_denoised_frame` does."""
         out = np.zeros((self.H, self.W, 3), dtype=np.uint8)
+        if variance:
+            k, sg = _denoise_variance_settings(int(iterations), sigma)
+            _check(self._lib.rt_progressive_resolve_temporal_variance_rgb8(self._h, int(albedo_samples), k, sg, flags, out.ctypes.data))
+            return out
+        if albedo_samples:
+            raise ValueError("rgb8_temporal: albedo_samples goes with variance=True")
         k, sg = _denoise_settings(int(iterations), sigma)
         _check(self._lib.rt_progressive_resolve_temporal_rgb8(self._h, k, sg, flags, out.ctypes.data))
         return out
@@ -1755,6 +1772,67 @@ def temporal_blend_device(d_rgb_sum, d_hist_sum, d_hist_counts, W: int, H: int, 
     _check(_rt().rt_temporal_blend_device(_ptr_or_none(d_rgb_sum), _ptr_or_none(d_counts), int(samples), _ptr_or_none(d_hist_sum), _ptr_or_none(d_hist_counts), W, H,
                                           _ptr_or_none(d_rgb_sum if d_sum_out is None else d_sum_out), _ptr_or_none(d_counts if d_counts_out is None else d_counts_out),
                                           C.c_void_p(stream)))
+
+
+# ---- temporal variance (rt_reproject_variance*, rt_temporal_blend_variance*; csrc/rt_reproject_var.h): the variance of a frame's per-pixel mean
+# carried through a camera move beside the history.  A variance is known when it is finite and >= 0; unknown is +inf.
+def _reproject_variance_call(fn, prev_sum, prev_var, prev_hits, prev_cam, cur_hits, prev_counts, prev_samples, max_history, sigma, flags):
+    s, n, g0, g1 = _reproject_frames(prev_sum, prev_counts, prev_hits, cur_hits)
+    v = np.ascontiguousarray(prev_var, dtype=np.float64)
+    if v.shape != s.shape:
+        raise ValueError(f"prev_var of shape {v.shape} for a frame of {s.shape}: the variance of the mean per pixel and channel")
+    cap, sg = _reproject_settings(max_history, sigma)
+    hs = np.zeros_like(s); hn = np.zeros(s.shape[:2], dtype=np.uint32); hv = np.zeros_like(s)
+    _check(fn(s.ctypes.data, None if n is None else n.ctypes.data, int(prev_samples), v.ctypes.data, g0.ctypes.data, C.byref(prev_cam), g1.ctypes.data, s.shape[1],
+              s.shape[0], cap, sg, flags, hs.ctypes.data, hn.ctypes.data, hv.ctypes.data))
+    return hs, hn, hv
+
+
+def reproject_variance_host(prev_sum, prev_var, prev_hits, prev_cam: CameraParams, cur_hits, prev_counts=None, prev_samples: int = 1, max_history: int = None,
+                            sigma=None, flags: int = 0):
+    """rt_reproject_variance_host (no GPU): `reproject_host` with prev_var (H, W, 3), the variance of the previous frame's per-pixel mean
+    (`Progressive.variance`, `adaptive_variance_host` or an earlier `temporal_blend_variance_host`), carried along -> (hist_sum, hist_counts,
+    hist_var (H, W, 3)).  The first two are `reproject_host`'s words; hist_var is +inf where a pixel has history of unknown variance and +0.0
+    where it has none."""
+    return _reproject_variance_call(_rt().rt_reproject_variance_host, prev_sum, prev_var, prev_hits, prev_cam, cur_hits, prev_counts, prev_samples, max_history, sigma, flags)
+
+
+def reproject_variance(prev_sum, prev_var, prev_hits, prev_cam: CameraParams, cur_hits, prev_counts=None, prev_samples: int = 1, max_history: int = None,
+                       sigma=None, flags: int = 0):
+    """rt_reproject_variance: the same call computed by the fused HIP kernel on the current device — the same words as reproject_variance_host."""
+    return _reproject_variance_call(_rt().rt_reproject_variance, prev_sum, prev_var, prev_hits, prev_cam, cur_hits, prev_counts, prev_samples, max_history, sigma, flags)
+
+
+def reproject_variance_device(d_prev_sum, d_prev_var, d_prev_hits, prev_cam: CameraParams, d_cur_hits, W: int, H: int, d_hist_sum_out, d_hist_counts_out,
+                              d_hist_var_out, d_prev_counts=None, prev_samples: int = 1, max_history: int = None, sigma=None, flags: int = 0, stream: int = 0) -> None:
+    """rt_reproject_variance_device: `reproject_variance` for frames in device memory (torch tensors or raw pointers; records 16-byte
+    aligned), one launch enqueued on `stream`; never waits, never allocates.  The outputs may overlap no input."""
+    cap, sg = _reproject_settings(max_history, sigma)
+    _check(_rt().rt_reproject_variance_device(_ptr_or_none(d_prev_sum), _ptr_or_none(d_prev_counts), int(prev_samples), _ptr_or_none(d_prev_var),
+                                              _ptr_or_none(d_prev_hits), C.byref(prev_cam), _ptr_or_none(d_cur_hits), W, H, cap, sg, flags,
+                                              _ptr_or_none(d_hist_sum_out), _ptr_or_none(d_hist_counts_out), _ptr_or_none(d_hist_var_out), C.c_void_p(stream)))
+
+
+def temporal_blend_variance_host(var, hist_var, hist_counts, counts=None, samples: int = 0):
+    """rt_temporal_blend_variance_host (no GPU): the variance of the mean of `temporal_blend_host`'s frame -> (H, W, 3).  var (H, W, 3) or
+    None (unknown everywhere: a frame with fewer than two passes) with counts (H, W) uint32 or `samples`; hist_var / hist_counts from
+    `reproject_variance`.  The result goes to `denoise_frame_host(counts=the blend's counts, var=...)` as it is."""
+    hv = np.ascontiguousarray(hist_var, dtype=np.float64); hn = np.ascontiguousarray(hist_counts, dtype=np.uint32)
+    v = None if var is None else np.ascontiguousarray(var, dtype=np.float64)
+    n = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+    if hv.ndim != 3 or hv.shape[2] != 3 or hn.shape != hv.shape[:2] or (v is not None and v.shape != hv.shape) or (n is not None and n.shape != hn.shape):
+        raise ValueError(f"hist_var of shape {hv.shape}, hist_counts {hn.shape}: want (H, W, 3) and (H, W), var and counts alike")
+    out = np.zeros_like(hv)
+    _check(_rt().rt_temporal_blend_variance_host(None if v is None else v.ctypes.data, None if n is None else n.ctypes.data, int(samples), hv.ctypes.data,
+                                                 hn.ctypes.data, hn.size, out.ctypes.data))
+    return out
+
+
+def temporal_blend_variance_device(d_var, d_hist_var, d_hist_counts, n_px: int, d_var_out=None, d_counts=None, samples: int = 0, stream: int = 0) -> None:
+    """rt_temporal_blend_variance_device: `temporal_blend_variance_host` for frames in device memory, enqueued on `stream`; never waits.
+    d_var may be None; d_var_out None: in place in d_var (which must then be given)."""
+    _check(_rt().rt_temporal_blend_variance_device(_ptr_or_none(d_var), _ptr_or_none(d_counts), int(samples), _ptr_or_none(d_hist_var), _ptr_or_none(d_hist_counts),
+                                                   int(n_px), _ptr_or_none(d_var if d_var_out is None else d_var_out), C.c_void_p(stream)))
 
 
 def kernel_time_total(b: SceneBuilder, reset: bool = False):
